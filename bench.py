@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mreads/s decombined on synthetic 150 bp human-beta reads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]     (N > 1: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): 10 M x 150 bp synthetic human-beta reads
@@ -21,12 +21,21 @@ per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in
 their environment), waits for them, relays rank 0's JSON line and exits non-zero
 if any of them did.  Under torch.distributed.run the ranks are the launcher's.
 
-Rank 0 prints ONE JSON line with the whole-job rate, the HBM roofline of the
-hot path (algorithmic 54 B/read divided by the device time of ALL launches of a
-step, measured with HIP events around them on their stream; the dominant
-kernel's own launch time rides along) and a CPU baseline: the oracle (a C port
-of the reference's algorithm) timed on a bounded sample of the same reads on the
-host cores, threaded inside the C library, at several thread counts.
+Rank 0 prints ONE JSON line with the whole-job rate (`value`), `ms_per_step` (the
+timed region's wall clock over its K steps) and the HBM roofline of the hot path
+(algorithmic 54 B/read divided by the device time of ALL launches of a step,
+measured with HIP events around them on their stream on every 5th timed step;
+the dominant kernel's own launch time rides along).  A plain run does no more:
+it sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line.
+
+--full adds what takes runs of its own behind the timed region: 200 further
+steps (`ms_per_step_steady`), the steps on one handle alone where two batches
+are in flight (`ms_per_step_one_batch_in_flight`), with several ranks the same
+steps without the gather (`gather.exposed_ms_per_step`), and a CPU baseline:
+the oracle (a C port of the reference's algorithm) timed on a bounded sample of
+the same reads on the host cores, threaded inside the C library, at several
+thread counts.  Without --full those keys are null.
 
 --config 3 / 5 run the other single-GPU workloads of BASELINE.json (human
 alpha+beta on extended-like tag sets, both chains per step; mouse gamma+delta);
@@ -59,6 +68,8 @@ SEED = 2
 ALGO_BYTES_PER_READ = 54      # 38 B packed 150-mer (rounded up) + 16 B record: SURVEY.md §8(d)
 HBM_PEAK_GBS = 8000.0         # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
 CONFIG_SEED = {2: SEED, 3: 3, 4: 4, 5: 5}
+DUMP_SAMPLE_READS = 1 << 20   # --dump-outputs: records of one step written at most (shared by its chains): about 50 MB of .npy
+DUMP_SEED = 20261015          # --dump-outputs: the sample of a larger step is the same in every run and build
 
 
 def parse_args(argv=None):
@@ -79,6 +90,12 @@ def parse_args(argv=None):
                          "so that a step's finishing launches run beside the next step's scan; 1 = one stream, each step behind the last; "
                          "0 (default) = 2 for config 2 on one rank without a gather, else 1 (configs 3 and 5 overlap their two chains instead: a stream per chain)")
     ap.add_argument("--no-gather-ab", action="store_true", help="N > 1: skip the second loop that prices the exposed gather time")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of their own behind the timed region: the CPU baseline, "
+                         "ms_per_step_steady, ms_per_step_one_batch_in_flight and (N > 1) the gather's exposed time; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's records and counters) as DIR/<name>.npy "
+                         "in float32 / float64: a fixed, seeded sample of at most %d records per step, every field" % DUMP_SAMPLE_READS)
     return ap.parse_args(argv)
 
 
@@ -235,6 +252,32 @@ def cpu_baseline(nat, tables, ts, cfg_synth, sample_reads: int):
     }
 
 
+def dump_outputs(path: str, outputs) -> list:
+    """--dump-outputs: `outputs` = [(records, counters)] per chain of the last timed step, as the decombine call left them
+    (records: nat.RECORD_DTYPE, one per read of the step; counters: the chain's counter block).  Written as DIR/<name>.npy:
+    sample_index (float64, the sampled reads' indices in the step's batch), records_[chain<c>_]<field> (float32, the sampled
+    reads' records field by field: every field is an integer below 2^16) and counters[_chain<c>] (float64, the whole block).
+    A step of more than DUMP_SAMPLE_READS reads is sampled at the same indices in every run (DUMP_SEED)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = len(outputs[0][0])
+    keep = DUMP_SAMPLE_READS // len(outputs)
+    idx = np.arange(n) if n <= keep else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    written = []
+
+    def save(name, arr):
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written.append(name)
+    save("sample_index", idx.astype(np.float64))
+    for c, (rec, cnt) in enumerate(outputs):
+        tag = f"chain{c}_" if len(outputs) > 1 else ""
+        for f in rec.dtype.names:
+            save(f"records_{tag}{f}", rec[f][idx].astype(np.float32))
+        save("counters" + (f"_chain{c}" if len(outputs) > 1 else ""), cnt.astype(np.float64))
+    return written
+
+
 def run_rank(args, device_factory=None, comm_factory=None):
     """One rank.  `device_factory` / `comm_factory` are given only by tests/bench_dry.py: a CPU stand-in for the device and a
     gloo communicator + host-memory backend (the line then says "dry_run": true and carries no rate); the command line of this
@@ -378,22 +421,26 @@ def run_rank(args, device_factory=None, comm_factory=None):
     timed = [k for k in range(args.steps) if k % every == every - 1 or args.steps < every]
     events = device.make_events(args.steps, timed)
     elapsed = timed_loop(gather, args.steps, events, set(timed))
-    # the same steps once more, 200 of them, behind the timed region: the steady-state figure beside the headline (an extra key)
+    dumped = None
+    if args.dump_outputs and rank == 0:      # (before anything else runs a step: what the timed region's last step computed)
+        dumped = dump_outputs(args.dump_outputs, device.outputs())
+    # --full only, from here to the CPU baseline: runs of their own behind the timed region, for the figures beside the headline.
+    # The same steps once more, 200 of them, behind the timed region: the steady-state figure (an extra key)
     elapsed_steady = None
     steady_steps = int(os.environ.get("DCRX_BENCH_STEADY_STEPS", "200"))
-    if not dry and steady_steps > 0 and args.config != 4:
+    if args.full and not dry and steady_steps > 0 and args.config != 4:
         elapsed_steady = timed_loop(gather, steady_steps)
     # ... and, where two batches are in flight, as many steps as the timed region's on the first handle alone — each step behind the
     # last, as rounds 1-5 timed them: the figure beside the headline (an extra key)
     elapsed_one = None
-    if not dry and len(getattr(device, "slots", [0])) > 1:
+    if args.full and not dry and len(getattr(device, "slots", [0])) > 1:
         all_slots = device.slots
         device.slots = all_slots[:1]
         timed_loop(None, 5)
         elapsed_one = timed_loop(None, max(args.steps, 50))
         device.slots = all_slots
     elapsed_nogather = None
-    if gather is not None and not args.no_gather_ab:
+    if args.full and gather is not None and not args.no_gather_ab:
         # the same steps without the gather: the difference is the gather time the steps do not hide
         elapsed_nogather = timed_loop(None, args.steps)
 
@@ -439,7 +486,7 @@ def run_rank(args, device_factory=None, comm_factory=None):
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "ms_per_step_steady": None if elapsed_steady is None else round(elapsed_steady / steady_steps * 1e3, 4),
             "ms_per_step_one_batch_in_flight": None if elapsed_one is None else round(elapsed_one / max(args.steps, 50) * 1e3, 4),
-            "preroll_steps": preroll_steps,
+            "preroll_steps": preroll_steps, "full": args.full, "dumped_outputs": dumped,
             "higher_is_better": True, "scaling": "strong" if args.config == 4 else "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic", "world_size": world, "per_rank_ms_per_step": per_rank_ms,
             "config": {
@@ -541,7 +588,7 @@ def run_rank(args, device_factory=None, comm_factory=None):
                 "ms_per_step_without_gather": None if elapsed_nogather is None else round(elapsed_nogather / args.steps * 1e3, 4),
                 "exposed_ms_per_step": None if elapsed_nogather is None else round((elapsed - elapsed_nogather) / args.steps * 1e3, 4),
             }
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             line["cpu_baseline"] = cpu_baseline(nat, tables, ts, cfg_synth, min(args.cpu_sample, n))
         else:
             line["cpu_baseline"] = None
@@ -664,6 +711,7 @@ class HipDevice:
         if gather is not None:           # alternating record buffers: the previous step's tuples are still being compacted
             gather.before_scan()
             rec = gather.records()
+        self.last_rec = rec              # (--dump-outputs: where the last chain's records of this step go)
         for c, tb in enumerate(tables):
             last = c == len(tables) - 1
             if ev is not None:           # events: (step start, step stop, kernel start, kernel stop) per chain; the step's pair on
@@ -713,6 +761,15 @@ class HipDevice:
         np, nat = self.np, self.nat
         nat.synchronize()
         return int(self.d_cnts[-1][self.last_batch].to_host(np.uint64, nat.N_COUNTERS)[nat.COUNTER_NAMES.index("vj_count")])
+
+    def outputs(self):
+        """--dump-outputs: [(records, counters)] per chain of the last step, on the host."""
+        np, nat = self.np, self.nat
+        nat.synchronize()
+        n = self.bc[self.last_batch].n_reads
+        planes = self.d_recs[:-1] + [self.last_rec]
+        return [(planes[c].to_host(nat.RECORD_DTYPE, n), self.d_cnts[c][self.last_batch].to_host(np.uint64, nat.N_COUNTERS))
+                for c in range(len(self.all_tables))]
 
 
 def main():

@@ -16,9 +16,10 @@ class DryDevice:
         self.all_tables = all_tables
         self.codec = None
         self.records = []          # per batch: the records of the last chain (what the gather carries)
+        self.chain_records = []    # per batch: per chain records (what --dump-outputs writes)
         self.counts = []           # per batch: per chain counters
         for first, cnt in batches:
-            recs, cnts = None, []
+            recs, cnts, all_recs = None, [], []
             for k, (tb, ts) in enumerate(zip(all_tables, tagsets)):
                 ot = orc.OracleTables(ts.v_tags, ts.v_jumps, [r.upper() for r in ts.v_regions], ts.j_tags, ts.j_jumps,
                                       [r.upper() for r in ts.j_regions], *ts.half_splits)
@@ -29,8 +30,10 @@ class DryDevice:
                         reads += nat.unpack_reads(nat.synth_reads_host(tbc, cfg_synth, first + lo, hi - lo))
                 rec, c64 = pu.oracle_records(ot, reads, "reverse", False, 130)
                 recs = rec
+                all_recs.append(rec)
                 cnts.append(c64.astype(np.uint64))
             self.records.append(recs)
+            self.chain_records.append(all_recs)
             self.counts.append(cnts)
         self.sum = [np.zeros(nat.N_COUNTERS, dtype=np.uint64) for _ in all_tables]
         self.last = None
@@ -92,3 +95,6 @@ class DryDevice:
     def last_step_hits(self):
         nat = self.nat
         return int(self.counts[self.last][-1][nat.COUNTER_NAMES.index("vj_count")])
+
+    def outputs(self):
+        return [(rec, cnt) for rec, cnt in zip(self.chain_records[self.last], self.counts[self.last])]

@@ -28,7 +28,11 @@ def stage():
 
 
 @pytest.fixture()
-def workdir(tmp_path, stage):
+def workdir(tmp_path, stage, monkeypatch):
+    # The stage names its sample after everything before the first "." of the input path, as the reference
+    # does (decombine.py): the tests name their inputs relative to the work directory, so that a "." in the
+    # temporary directory's own path cannot change the sample name the summary log carries.
+    monkeypatch.chdir(tmp_path)
     ts = stage["tagset"]
     t = synth.TagSet(species=ts["species"], tags=ts["tags"], chain=ts["chain"], v_tags=ts["v_tags"],
                      v_jumps=ts["v_jumps"], v_names=ts["v_names"], v_regions=ts["v_regions"], j_tags=ts["j_tags"],
@@ -53,7 +57,7 @@ def _oracle_device(stage):
 def _run_and_compare(stage, workdir, run):
     outdir = workdir / f"out_{run['bc_read']}_{run['orientation']}"
     outdir.mkdir()
-    args = dio.create_args_dict(infile=str(workdir / "SYNTH_1.fq"), chain="b", bc_read=run["bc_read"], dontgzip=True,
+    args = dio.create_args_dict(infile="SYNTH_1.fq", chain="b", bc_read=run["bc_read"], dontgzip=True,
                                 dontcount=True, orientation=run["orientation"], allowNs=run["allowNs"],
                                 tagfastadir=str(workdir / "tags"), outpath=str(outdir) + os.sep, command="decombine")
     rows = dec.decombinator(args)
@@ -118,7 +122,7 @@ def test_fastq_check_and_empty_input_log(workdir, monkeypatch, stage):
     out.mkdir()
     empty = workdir / "empty_merge.fq"
     empty.write_text("")
-    args = dio.create_args_dict(infile=str(empty), chain="b", bc_read="R2", tagfastadir=str(workdir / "tags"),
+    args = dio.create_args_dict(infile=empty.name, chain="b", bc_read="R2", tagfastadir=str(workdir / "tags"),
                                 outpath=str(out) + os.sep)
     date = time.strftime("%Y_%m_%d")
     for n in ("", "2"):   # the second run must open ..._Summary2.csv (reference tests/test_decombine.py:75-94)
@@ -129,10 +133,10 @@ def test_fastq_check_and_empty_input_log(workdir, monkeypatch, stage):
     bad = workdir / "bad_1.fq"
     bad.write_text("@r\nACGT\n+\nIIII\n>r2\nACGT\n+\nIIII\n")
     with pytest.raises(ValueError, match="Expected @ symbol"):
-        dec.decombinator(dict(args, infile=str(bad)))
+        dec.decombinator(dict(args, infile=bad.name))
     bad.write_text("@r\nACGT\n+\nIIII\n@r2\nACGT\n+\nIII\n")
     with pytest.raises(ValueError, match="read quality"):
-        dec.decombinator(dict(args, infile=str(bad)))
+        dec.decombinator(dict(args, infile=bad.name))
 
 
 def test_cli_parser_flags():

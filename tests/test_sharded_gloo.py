@@ -277,9 +277,12 @@ def test_sharded_stage_equals_single_process(tmp_path, monkeypatch, world, run_i
         (work / name).write_bytes((wrapped(text) if cut == "wrapped" else text.replace("\n", eol)).encode())
     (work / "single").mkdir()
     (work / "sharded").mkdir()
+    # the input is named relative to the work directory (here and in the ranks): the sample name is everything before the
+    # first "." of the input path (the reference's rule), which a "." in the temporary directory's path would change
+    monkeypatch.chdir(work)
 
     def make_args(out):
-        return dio.create_args_dict(infile=str(work / "SYNTH_1.fq"), chain="b", bc_read=run["bc_read"], dontgzip=True, dontcount=True,
+        return dio.create_args_dict(infile="SYNTH_1.fq", chain="b", bc_read=run["bc_read"], dontgzip=True, dontcount=True,
                                     orientation=run["orientation"], allowNs=run["allowNs"], tagfastadir=str(work / "tags"),
                                     outpath=str(work / out) + os.sep, command="decombine")
     json.dump(make_args("sharded"), open(work / "args.json", "w"))
@@ -300,7 +303,7 @@ def test_sharded_stage_equals_single_process(tmp_path, monkeypatch, world, run_i
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    DCRX_ROOT=ROOT, DCRX_WORK=str(work), OMP_NUM_THREADS="1")
         procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
+                                      stderr=subprocess.STDOUT, text=True, cwd=str(work)))
     outs = [p.communicate(timeout=600)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
     got = json.load(open(work / "sharded.json"))

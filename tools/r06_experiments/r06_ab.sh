@@ -15,7 +15,7 @@ cd /tmp
 for rep in $(seq 1 $REPS); do
 for v in "$@"; do
   export DCRX_LIB_PATH=$R/tools/variants/libdcrx_$v.so
-  python3 $R/bench.py --no-cpu-baseline --steps ${STEPS:-100} --warmup 10 $BENCH_ARGS 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('RUN $v', d['ms_per_step'], d.get('ms_per_step_steady'), d['roofline']['dominant_kernel_ms_avg'], round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4))" || tail -3 $O/err.log
+  python3 $R/bench.py --full --no-cpu-baseline --steps ${STEPS:-100} --warmup 10 $BENCH_ARGS 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('RUN $v', d['ms_per_step'], d.get('ms_per_step_steady'), d['roofline']['dominant_kernel_ms_avg'], round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4))" || tail -3 $O/err.log
 done
 done
 ) 2>&1 | tee $O/raw.log

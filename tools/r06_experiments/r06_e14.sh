@@ -10,7 +10,7 @@ DCRX_DEBUG_FUSE_E_WAVES=2 timeout 600 python3 tests/forced_shape_worker.py 2 209
 DCRX_DEBUG_FUSE_E_WAVES=5 timeout 600 python3 tests/forced_shape_worker.py 2 2097152 2 2>&1 | tail -1 | cut -c1-200
 cd /tmp
 run() { n=$1; shift
-  python3 $R/bench.py --no-cpu-baseline --steps 60 --warmup 10 "$@" 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('RUN $n', d['ms_per_step'], d.get('ms_per_step_steady'), d['roofline']['dominant_kernel_ms_avg'], round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4))" || tail -3 $O/err.log
+  python3 $R/bench.py --full --no-cpu-baseline --steps 60 --warmup 10 "$@" 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('RUN $n', d['ms_per_step'], d.get('ms_per_step_steady'), d['roofline']['dominant_kernel_ms_avg'], round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4))" || tail -3 $O/err.log
 }
 for rep in 1 2 3; do
 DCRX_DEBUG_FUSE_E=0 run "list_E_a_role"

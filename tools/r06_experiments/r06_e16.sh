@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; cd /tmp
 O=$R/gpurun_out/r06_e16; mkdir -p $O
 export DCRX_LIB_PATH=$R/tools/variants/libdcrx_fuse_e.so
 run() { n=$1; shift
-  python3 $R/bench.py --no-cpu-baseline --steps 60 --warmup 10 "$@" 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('RUN $n', d['ms_per_step'], d.get('ms_per_step_steady'), d['roofline']['dominant_kernel_ms_avg'], round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4))" || tail -3 $O/err.log
+  python3 $R/bench.py --full --no-cpu-baseline --steps 60 --warmup 10 "$@" 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('RUN $n', d['ms_per_step'], d.get('ms_per_step_steady'), d['roofline']['dominant_kernel_ms_avg'], round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4))" || tail -3 $O/err.log
 }
 (
 for rep in 1 2 3 4; do

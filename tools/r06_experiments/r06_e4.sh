@@ -11,7 +11,7 @@ DCRX_LIB_PATH=$R/tools/variants/libdcrx_landed.so timeout 600 python3 tests/forc
 cd /tmp
 run() { n=$1; lib=$2; shift 2
   export DCRX_LIB_PATH=$R/tools/variants/libdcrx_$lib.so
-  python3 $R/bench.py --no-cpu-baseline --steps 50 --warmup 10 "$@" 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$n', d['ms_per_step'], 'steady', d.get('ms_per_step_steady'), 'scan', d['roofline']['dominant_kernel_ms_avg'], 'rest', round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4), 'frac', d['roofline']['frac'])" || tail -3 $O/err.log
+  python3 $R/bench.py --full --no-cpu-baseline --steps 50 --warmup 10 "$@" 2>$O/err.log | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$n', d['ms_per_step'], 'steady', d.get('ms_per_step_steady'), 'scan', d['roofline']['dominant_kernel_ms_avg'], 'rest', round(d['roofline']['step_device_ms_avg']-d['roofline']['dominant_kernel_ms_avg'],4), 'frac', d['roofline']['frac'])" || tail -3 $O/err.log
 }
 for rep in 1 2 3; do
 run "round 5 kernels      " r05
