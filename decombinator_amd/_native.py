@@ -181,6 +181,144 @@ def collapse_front(text: bytes, oligo: str, allow_ns: bool, lenthreshold: int, q
     return rows[:n], offs, cnt
 
 
+# ---- stage 2 of collapse: UMI neighbour search (dcrx_umi.hip), grouping and counting (dcrx_collapse_back.cpp) ----
+
+UMI_MAX_LEN, UMI_MAX_SYMBOLS, UMI_TILE, UMI_REC_WORDS, UMI_TILE_WORDS = 24, 8, 256, 16, 8
+GRP_COUNTERS = ["readdata_barcode_dcretc_keys", "number_input_unique_dcrs", "number_input_total_dcrs", "multi_tcr_barcodes",
+                "multi_tcr_barcode_reads"]
+
+
+def text_and_offsets(strings):
+    """(bytes, uint64 offsets of len + 1) of a list of str / bytes, or the pair itself when given one."""
+    if isinstance(strings, tuple) and len(strings) == 2 and isinstance(strings[0], (bytes, bytearray)):
+        return bytes(strings[0]), np.ascontiguousarray(strings[1], dtype=np.uint64)
+    bs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in strings]
+    off = np.zeros(len(bs) + 1, dtype=np.uint64)
+    if bs:
+        off[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+    return b"".join(bs), off
+
+
+def _buf(text: bytes):
+    return np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
+
+
+def umi_encode(umis):
+    """dcrx_umi_encode: (records uint32[n_tiles * UMI_TILE, UMI_REC_WORDS], tiles uint32[n_tiles, UMI_TILE_WORDS])."""
+    text, off = text_and_offsets(umis)
+    n = len(off) - 1
+    t = _buf(text)
+    n_tiles = check(lib().dcrx_umi_encode(t.ctypes.data, off.ctypes.data, n, None, None))
+    recs = np.zeros((max(n_tiles, 1) * UMI_TILE, UMI_REC_WORDS), dtype=np.uint32)
+    tiles = np.zeros((max(n_tiles, 1), UMI_TILE_WORDS), dtype=np.uint32)
+    check(lib().dcrx_umi_encode(t.ctypes.data, off.ctypes.data, n, recs.ctypes.data, tiles.ctypes.data))
+    return recs[:n_tiles * UMI_TILE], tiles[:n_tiles]
+
+
+def umi_neighbours_keys(umis, k: int, cap: int | None = None) -> np.ndarray:
+    """dcrx_umi_neighbours on the current device: uint64 keys (i << 32 | j), i < j, ascending.  `cap`: the first call's room
+    (a call that finds more pairs is repeated with room for all of them)."""
+    text, off = text_and_offsets(umis)
+    n = len(off) - 1
+    t = _buf(text)
+    if k < 0:
+        raise ValueError("the UMI distance threshold (-bc) must be >= 0")
+    cap = int(4 * n + 1024) if cap is None else int(cap)
+    for _ in range(2):
+        out = np.empty(max(cap, 1), dtype=np.uint64)
+        total = check(lib().dcrx_umi_neighbours(t.ctypes.data, off.ctypes.data, n, int(k), out.ctypes.data, cap))
+        if total <= cap:
+            return out[:total]
+        cap = total
+    raise DcrxError(-1, "dcrx_umi_neighbours: the pair count changed between two calls")
+
+
+def umi_neighbours(umis, k: int):
+    """Every pair (i, j), i < j, of UMIs within Levenshtein distance k, ascending: (rows, cols) as int64 arrays.  The one
+    function collapse.make_merge_groups calls for the search (tests on a CPU-only host put a stand-in here)."""
+    keys = umi_neighbours_keys(umis, k)
+    return (keys >> np.uint64(32)).astype(np.int64), (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)
+
+
+def seqs_equivalent(a: str, b: str, lev_fraction: float) -> bool:
+    """dcrx_seqs_equivalent: the host's are_seqs_equivalent."""
+    ab, bb = a.encode("latin-1"), b.encode("latin-1")
+    return bool(check(lib().dcrx_seqs_equivalent(ab, len(ab), bb, len(bb), float(lev_fraction))))
+
+
+class Groups:
+    """dcrx_collapse_group's handle over the rows of a front half (keeps the text and rows it points into alive)."""
+
+    def __init__(self, text: bytes, offsets, rows, field_sep: str, lev_fraction: float, sampling_analysis: bool):
+        self._text = _buf(text)
+        self._off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._rows = np.ascontiguousarray(rows)
+        h = C.c_void_p()
+        cnt = np.zeros(len(GRP_COUNTERS), dtype=np.uint64)
+        check(lib().dcrx_collapse_group(self._text.ctypes.data, len(text), self._off.ctypes.data, self._rows.ctypes.data, len(self._rows),
+                                        field_sep.encode("ascii"), float(lev_fraction), int(bool(sampling_analysis)), C.byref(h),
+                                        cnt.ctypes.data))
+        self.handle = h.value
+        self.counters = dict(zip(GRP_COUNTERS, (int(x) for x in cnt)))
+        ng, nm, ub, pb = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().dcrx_groups_info(self.handle, C.byref(ng), C.byref(nm), C.byref(ub), C.byref(pb)))
+        self.n_groups = int(ng.value)
+        umi, umi_off = np.zeros(max(ub.value, 1), dtype=np.uint8), np.zeros(self.n_groups + 1, dtype=np.uint64)
+        proto, proto_off = np.zeros(max(pb.value, 1), dtype=np.uint8), np.zeros(self.n_groups + 1, dtype=np.uint64)
+        self.member_off = np.zeros(self.n_groups + 1, dtype=np.uint64)
+        self.member_rows = np.zeros(max(nm.value, 1), dtype=np.uint64)
+        check(lib().dcrx_groups_export(self.handle, umi.ctypes.data, umi_off.ctypes.data, proto.ctypes.data, proto_off.ctypes.data,
+                                       self.member_off.ctypes.data, self.member_rows.ctypes.data))
+        self.member_rows = self.member_rows[:nm.value]
+        self.umi_text, self.umi_off = umi.tobytes()[:ub.value], umi_off
+        self.proto_text, self.proto_off = proto.tobytes()[:pb.value], proto_off
+
+    def umi(self, g: int) -> str:
+        return self.umi_text[int(self.umi_off[g]):int(self.umi_off[g + 1])].decode("latin-1")
+
+    def protoseq(self, g: int) -> str:
+        return self.proto_text[int(self.proto_off[g]):int(self.proto_off[g + 1])].decode("latin-1")
+
+    def equivalent(self, rows, cols, lev_fraction: float, n_threads: int = 0) -> np.ndarray:
+        """make_clusters' edge test on the pairs (rows[e], cols[e]): a bool per pair."""
+        keys = (np.asarray(rows, dtype=np.uint64) << np.uint64(32)) | np.asarray(cols, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys)
+        keep = np.zeros(max(len(keys), 1), dtype=np.uint8)
+        check(lib().dcrx_groups_equivalent(self.handle, keys.ctypes.data, len(keys), float(lev_fraction), keep.ctypes.data, int(n_threads)))
+        return keep[:len(keys)].astype(bool)
+
+    def count(self, cluster_groups, cluster_off, extra: bool = False):
+        """dcrx_collapse_count: (votes, size_sum, freq text, -wc text or None, -bd text or None)."""
+        cg = np.ascontiguousarray(cluster_groups, dtype=np.uint32)
+        co = np.ascontiguousarray(cluster_off, dtype=np.uint64)
+        nc = len(co) - 1
+        nd, fb, wb, bb = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L = lib()
+        check(L.dcrx_collapse_count(self.handle, cg.ctypes.data, co.ctypes.data, nc, C.byref(nd), None, None, C.byref(fb), None,
+                                    int(extra), C.byref(wb), None, C.byref(bb), None))
+        votes = np.zeros(max(nd.value, 1), dtype=np.uint64)
+        ssum = np.zeros(max(nd.value, 1), dtype=np.uint64)
+        freq = np.zeros(max(fb.value, 1), dtype=np.uint8)
+        wc = np.zeros(max(wb.value, 1), dtype=np.uint8)
+        bd = np.zeros(max(bb.value, 1), dtype=np.uint8)
+        check(L.dcrx_collapse_count(self.handle, cg.ctypes.data, co.ctypes.data, nc, C.byref(nd), votes.ctypes.data, ssum.ctypes.data,
+                                    C.byref(fb), freq.ctypes.data, int(extra), C.byref(wb), wc.ctypes.data, C.byref(bb), bd.ctypes.data))
+        n = int(nd.value)
+        return (votes[:n], ssum[:n], freq.tobytes()[:fb.value], wc.tobytes()[:wb.value] if extra else None,
+                bd.tobytes()[:bb.value] if extra else None)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().dcrx_groups_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Cdr3GenesC(C.Structure):
     _fields_ = [("n_v", C.c_uint32), ("n_j", C.c_uint32),
                 ("v_regions", C.c_void_p), ("v_region_off", C.c_void_p), ("j_regions", C.c_void_p), ("j_region_off", C.c_void_p),
@@ -245,6 +383,9 @@ class SynthCfgC(C.Structure):
 
 # every symbol include/dcrx.h and include/dcrx_synth.h declare
 EXPORTS = [
+    "dcrx_umi_encode", "dcrx_umi_neighbours_device", "dcrx_umi_neighbours", "dcrx_collapse_group",
+    "dcrx_groups_destroy", "dcrx_groups_info", "dcrx_groups_export", "dcrx_groups_equivalent", "dcrx_collapse_count",
+    "dcrx_seqs_equivalent",
     "dcrx_tables_create", "dcrx_tables_destroy", "dcrx_tables_info", "dcrx_pack_reads", "dcrx_pack_reads_span",
     "dcrx_unpack_reads", "dcrx_fastq_open", "dcrx_fastq_open_range", "dcrx_fastq_lines", "dcrx_fastq_close", "dcrx_fastq_next", "dcrx_count_prefix_byte", "dcrx_assemble_rows",
     "dcrx_decombine", "dcrx_decombine_device", "dcrx_set_timing_events", "dcrx_set_step_events", "dcrx_reserve_device", "dcrx_compact_hits_device",
@@ -305,6 +446,17 @@ def lib():
         "dcrx_set_tuple_sink": (i32, [vp, C.POINTER(TupleLayoutC), vp, u64, vp]),
         "dcrx_collapse_front": (C.c_int64, [vp, u64, C.POINTER(CollapseCfgC), vp, u64, vp, vp, i32]),
         "dcrx_spacer_search": (i32, [C.c_char_p, i32, C.c_char_p, i32, vp, vp, i32, C.POINTER(C.c_int32)]),
+        "dcrx_umi_encode": (C.c_int64, [vp, vp, u64, vp, vp]),
+        "dcrx_umi_neighbours_device": (i32, [vp, vp, u64, C.c_int32, vp, u64, vp, vp]),
+        "dcrx_umi_neighbours": (C.c_int64, [vp, vp, u64, C.c_int32, vp, u64]),
+        "dcrx_collapse_group": (i32, [vp, u64, vp, vp, u64, C.c_char_p, C.c_double, i32, C.POINTER(vp), vp]),
+        "dcrx_groups_destroy": (None, [vp]),
+        "dcrx_groups_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "dcrx_groups_export": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "dcrx_groups_equivalent": (i32, [vp, vp, u64, C.c_double, vp, i32]),
+        "dcrx_collapse_count": (i32, [vp, vp, vp, u64, C.POINTER(u64), vp, vp, C.POINTER(u64), vp, i32, C.POINTER(u64), vp,
+                                      C.POINTER(u64), vp]),
+        "dcrx_seqs_equivalent": (i32, [C.c_char_p, u32, C.c_char_p, u32, C.c_double]),
         "dcrx_set_reserved_cus": (i32, [vp, u32]),
         "dcrx_tune_state": (i32, [vp, i32, u64, C.POINTER(TuneStateC)]),
         "dcrx_cdr3_batch": (C.c_int64, [C.POINTER(Cdr3GenesC), u64, vp, vp, vp, vp, vp, vp, vp, vp, u64]),

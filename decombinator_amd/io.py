@@ -27,8 +27,10 @@ def create_args_dict(
     barcodeduplication: bool = False, positionalbarcodes: bool = False, oligo: str = "M13",
     writeclusters: bool = False, UMIhistogram: bool = False, nonproductivefilter: bool = False,
     outpath: str = None, dontsave: bool = False, command: str = None, sampling_analysis: bool = False,
+    cluster: bool = False,
 ) -> dict:
-    """The function-argument dictionary threaded through the stages (33 keys)."""
+    """The function-argument dictionary threaded through the stages (the reference's 33 keys, and `cluster`: run the
+    grouping / clustering half of collapse, writing the `.freq`)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -38,7 +40,7 @@ def create_args_dict(
         dontcheckinput=dontcheckinput, barcodeduplication=barcodeduplication,
         positionalbarcodes=positionalbarcodes, oligo=oligo, writeclusters=writeclusters,
         UMIhistogram=UMIhistogram, nonproductivefilter=nonproductivefilter, outpath=outpath,
-        dontsave=dontsave, command=command, sampling_analysis=sampling_analysis)
+        dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -84,20 +86,29 @@ def _later_stage_flags(p: argparse.ArgumentParser):
     p.add_argument("-npf", "--nonproductivefilter", action="store_true")
 
 
+def _cluster_flag(p: argparse.ArgumentParser):
+    p.add_argument("--cluster", action="store_true",
+                   help="Run the whole collapse stage: group reads by UMI, cluster UMIs (GPU neighbour search), count DCRs and "
+                        "write the .freq (and the Collapsing_Summary.csv); without it only the per-row front half runs")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
         description="Decombinator `decombine` stage on MI355X (HIP), the per-row front half of `collapse` and `translate` (CDR3 per DCR).  "
-                    "Sub-commands as in the reference; the grouping / clustering half of `collapse` is not part of this build.")
+                    "Sub-commands as in the reference; the grouping / clustering half of `collapse` (UMI clustering, the "
+                    ".freq) runs with --cluster.")
     parser.add_argument("-v", "--version", action="version", version=__version__)
     sub = parser.add_subparsers(dest="command", help="Available commands")
     sub.required = False
-    pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse (its grouping half: not in this build)")
-    _common(pipe); _decombine(pipe); _later_stage_flags(pipe)
+    pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
+                                           "translate (.n12, .freq, .tsv)")
+    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe)
     dec = sub.add_parser("decombine", help="Decombine TCR reads")
     _common(dec); _decombine(dec)
-    col = sub.add_parser("collapse", help="front half of collapse over an .n12 file: barcode extraction and the row filters")
-    _common(col); _later_stage_flags(col)
+    col = sub.add_parser("collapse", help="front half of collapse over an .n12 file: barcode extraction and the row filters "
+                                          "(writes .n12u); with --cluster the whole stage (writes .freq)")
+    _common(col); _later_stage_flags(col); _cluster_flag(col)
     col.add_argument("-in", "--infile", type=str, required=True, help=".n12 file of the decombine stage (optionally gzipped)")
     col.add_argument("-N", "--allowNs", action="store_true", help="Allow barcodes containing N")
     col.add_argument("-ln", "--lenthreshold", type=int, default=130, help="Inter-tag length threshold")

@@ -3,7 +3,9 @@ GPU) and the per-row front half of stage 2 (`collapse`: spacer search, UMI extra
 collapse.read_in_data up to where it starts grouping rows, collapse.py:482-565).  The grouping / clustering rest of
 `collapse` and the `translate` stage are host stages of the reference that BASELINE.json's north_star leaves on the host
 (`translate.get_cdr3` is available as a function: decombinator_amd/translate.py).  `pipeline` therefore writes the `.n12`,
-runs the front half over the rows and reports its counters."""
+runs the front half over the rows and reports its counters.  With `cluster` (--cluster) it is the reference's run
+(pipeline.py:10-38): decombine, the whole of `collapse` (collapse.collapsinator: grouping, UMI clustering on the GPU,
+counting), then `translate`, writing the `.n12`, `.freq` and `.tsv`."""
 from __future__ import annotations
 
 from datetime import datetime
@@ -39,10 +41,22 @@ def run(args: Optional[dict[str, Any]] = None, cli_args: Optional[dict[str, Any]
     if not inp["dontsave"]:
         write_out_intermediate(data, inp, ".n12")
     print("Decombinator complete...")
+    if inp.get("cluster"):
+        from . import translate
+        from .io import write_out_translated
+        data = collapse.collapsinator(inp, data=data)
+        if not inp["dontsave"]:
+            write_out_intermediate(data, inp, ".freq")
+        print("Collapsinator complete...")
+        data = translate.cdr3translator(inp, data=data)
+        print("CDR3translator complete...")
+        if not inp["dontsave"]:
+            write_out_translated(data, translate.out_headers, inp)
+        print(f"Pipeline complete in {datetime.now() - start}")
+        return data
     if len(data) and inp.get("oligo") and not inp.get("nobarcoding"):
         collapse_front(data, inp)
-    print("The grouping / clustering half of `collapse` is not part of this build: feed the .n12 to the reference's "
-          "`decombinator collapse`; `decombinator translate` of this build takes its .freq.")
+    print("The grouping / clustering half of `collapse` was not asked for: run with --cluster for the .freq and the .tsv.")
     print(f"Pipeline complete in {datetime.now() - start}")
     return data
 
@@ -54,6 +68,10 @@ def main(argv=None):
         write_out_intermediate(data, inp, ".n12")
     elif inp["command"] == "pipeline":
         run(cli_args=inp)
+    elif inp["command"] == "collapse" and inp.get("cluster"):
+        # the whole stage (reference pipeline.py:45-47): the `.freq`, named <outpath><file id>.freq
+        data = collapse.collapsinator(inp)
+        write_out_intermediate(data, inp, ".freq")
     elif inp["command"] == "collapse":
         # the front half over an `.n12` file: the rows that pass, each with its barcode and barcode quality appended
         # (this build's intermediate: the reference goes on to group them in memory)

@@ -425,6 +425,77 @@ int dcrx_gzip_open(const char *path, int level, int n_threads, void **writer);
 int dcrx_gzip_write(void *writer, const void *data, uint64_t n_bytes);
 int dcrx_gzip_close(void *writer);
 
+/* ---- stage 2 of `collapse`: UMI neighbour search (GPU), grouping and counting (host) -------------------------------
+ * The reference's make_merge_groups (src/decombinator/collapse.py:723-751) asks pyrepseq.nn.symdel for every pair of
+ * distinct UMIs within Levenshtein distance `bcthreshold`, then keeps the upper triangle in ascending (i, j) order.  Here:
+ *
+ *   dcrx_umi_encode            host: UMIs (ASCII + offsets) -> records sorted by (length, composition), one per UMI, and a
+ *                              summary per tile of DCRX_UMI_TILE records (the device search's input)
+ *   dcrx_umi_neighbours_device device buffers in, asynchronous on `hip_stream`: every pair within distance k as a 64-bit
+ *                              key (i << 32 | j, i < j, original indices), in no particular order; up to pair_cap of them
+ *                              are written and *d_total receives the number found (zeroed by the call itself)
+ *   dcrx_umi_neighbours        host convenience: encode, search on the current device, sort.  Returns the number of pairs;
+ *                              when it exceeds pair_cap nothing is written to `pairs` and the caller calls again with room
+ *                              for that many (as dcrx_pack_reads)
+ *
+ * Limits: a UMI is at most DCRX_UMI_MAX_LEN bytes (what dcrx_collapse_row_t.barcode holds) and one call sees at most
+ * DCRX_UMI_MAX_SYMBOLS distinct byte values (A, C, G, T, N, and the S / L of set_barcode fit); beyond either the call
+ * returns DCRX_E_UNSUPPORTED.  Any k >= 0. */
+#define DCRX_UMI_MAX_LEN 24
+#define DCRX_UMI_MAX_SYMBOLS 8
+#define DCRX_UMI_TILE 256
+#define DCRX_UMI_REC_WORDS 16   /* per record: Peq[8], packed codes[3], length, composition[2], original index, pad */
+#define DCRX_UMI_TILE_WORDS 8   /* per tile: min length, max length, composition minima[2], maxima[2], record count, pad */
+/* The records (n_tiles * DCRX_UMI_TILE of them, the tail padded) and tiles of n UMIs; returns n_tiles, or an error.
+ * recs == NULL: only checks the limits and returns n_tiles. */
+int64_t dcrx_umi_encode(const char *ascii, const uint64_t *offsets, uint64_t n, uint32_t *recs, uint32_t *tiles);
+int dcrx_umi_neighbours_device(const uint32_t *d_recs, const uint32_t *d_tiles, uint64_t n_tiles, int32_t k,
+                               uint64_t *d_pairs, uint64_t pair_cap, uint64_t *d_total, void *hip_stream);
+int64_t dcrx_umi_neighbours(const char *ascii, const uint64_t *offsets, uint64_t n, int32_t k, uint64_t *pairs,
+                            uint64_t pair_cap);
+
+/* Grouping (read_in_data, collapse.py:585-683), over the rows dcrx_collapse_front left (status DCRX_CF_OK join groups;
+ * DCRX_CF_OVERLONG rows count towards the input DCRs only, :555-563), in input order: a barcode has at most one group
+ * (index 0); a read joins it when are_seqs_equivalent(protoseq, seq, lev_fraction) (:349-354), else the barcode turns
+ * multi-TCR for good; the protoseq is the group's most common seq (ties: the first seen); a changed protoseq re-keys the
+ * group, which moves it to the end of the reference's dict.  `text` and the row offsets must outlive the handle.
+ * counters[DCRX_GRP_N_COUNTERS] receive the reference's keys below. */
+enum dcrx_group_counter {
+  DCRX_GRP_C_KEYS = 0,            /* readdata_barcode_dcretc_keys */
+  DCRX_GRP_C_INPUT_UNIQUE = 1,    /* number_input_unique_dcrs */
+  DCRX_GRP_C_INPUT_TOTAL = 2,     /* number_input_total_dcrs */
+  DCRX_GRP_C_MULTI_BARCODES = 3,  /* multi_tcr_barcodes */
+  DCRX_GRP_C_MULTI_READS = 4,     /* multi_tcr_barcode_reads */
+  DCRX_GRP_N_COUNTERS = 5
+};
+typedef struct dcrx_groups dcrx_groups_t;
+int dcrx_collapse_group(const char *text, uint64_t n_bytes, const uint64_t *row_offsets, const dcrx_collapse_row_t *rows,
+                        uint64_t n_rows, const char *field_sep, double lev_fraction, int sampling_analysis,
+                        dcrx_groups_t **groups, uint64_t *counters);
+void dcrx_groups_destroy(dcrx_groups_t *groups);
+/* Sizes: groups, member rows, bytes of all UMIs, bytes of all protoseqs. */
+int dcrx_groups_info(const dcrx_groups_t *groups, uint64_t *n_groups, uint64_t *n_members, uint64_t *umi_bytes,
+                     uint64_t *proto_bytes);
+/* In group order: the UMIs and protoseqs (text + n_groups + 1 offsets each; any may be NULL) and each group's member rows
+ * (member_off: n_groups + 1 entries; member_rows: input row indices in join order). */
+int dcrx_groups_export(const dcrx_groups_t *groups, char *umi_text, uint64_t *umi_off, char *proto_text, uint64_t *proto_off,
+                       uint64_t *member_off, uint64_t *member_rows);
+/* keep[e] = are_seqs_equivalent(protoseq of group a, of group b, lev_fraction) for the pairs (a, b) = (pairs[e] >> 32,
+ * pairs[e] & 0xffffffff) — make_clusters' edge test (collapse.py:771-779). */
+int dcrx_groups_equivalent(const dcrx_groups_t *groups, const uint64_t *pairs, uint64_t n_pairs, double lev_fraction,
+                           uint8_t *keep, int n_threads);
+/* collapsinate (collapse.py:897-977) over clusters given as group lists in concatenation order
+ * (cluster c = cluster_groups[cluster_off[c] .. cluster_off[c + 1])): each cluster votes for its most common DCR (ties: the
+ * first seen), DCRs in order of their first cluster.  Per DCR: votes[d], size_sum[d] (reads of its clusters); freq_text
+ * receives the `.freq` lines "v, j, vdel, jdel, insert, count, round(mean cluster size)" (round half to even).
+ * Pass freq_text == NULL to learn *n_dcrs and *freq_bytes first.  With extra != 0 also *wc_bytes / wc_text (the
+ * write_clusters lines, :813-843, without the header) and *bd_bytes / bd_text (the -bd lines, :959-967). */
+int dcrx_collapse_count(const dcrx_groups_t *groups, const uint32_t *cluster_groups, const uint64_t *cluster_off,
+                        uint64_t n_clusters, uint64_t *n_dcrs, uint64_t *votes, uint64_t *size_sum, uint64_t *freq_bytes,
+                        char *freq_text, int extra, uint64_t *wc_bytes, char *wc_text, uint64_t *bd_bytes, char *bd_text);
+/* are_seqs_equivalent on its own (tests): 1 when levenshtein(a, b) <= len(shorter) * lev_fraction. */
+int dcrx_seqs_equivalent(const char *a, uint32_t na, const char *b, uint32_t nb, double lev_fraction);
+
 /* ---- translate.get_cdr3 for a batch of DCRs (host only) ----
  * Replaces the per-row body of the reference's CDR3 step (src/decombinator/translate.py:257-357, called per unique DCR from
  * cdr3translator :388-533): from the gene tables of import_gene_information (:163-254) and the five fields of each DCR,
