@@ -388,7 +388,7 @@ EXPORTS = [
     "dcrx_seqs_equivalent",
     "dcrx_tables_create", "dcrx_tables_destroy", "dcrx_tables_info", "dcrx_pack_reads", "dcrx_pack_reads_span",
     "dcrx_unpack_reads", "dcrx_fastq_open", "dcrx_fastq_open_range", "dcrx_fastq_lines", "dcrx_fastq_close", "dcrx_fastq_next", "dcrx_count_prefix_byte", "dcrx_assemble_rows",
-    "dcrx_decombine", "dcrx_decombine_device", "dcrx_set_timing_events", "dcrx_set_step_events", "dcrx_reserve_device", "dcrx_compact_hits_device",
+    "dcrx_decombine", "dcrx_decombine_chains", "dcrx_decombine_device", "dcrx_set_timing_events", "dcrx_set_step_events", "dcrx_reserve_device", "dcrx_compact_hits_device",
     "dcrx_compact_hits_bitmap_device", "dcrx_compact_hits_packed_device", "dcrx_set_reserved_cus", "dcrx_tune_state", "dcrx_cdr3_batch",
     "dcrx_device_count", "dcrx_set_device", "dcrx_device_name", "dcrx_malloc_device", "dcrx_free_device",
     "dcrx_malloc_host", "dcrx_free_host", "dcrx_memcpy_h2d", "dcrx_memcpy_d2h", "dcrx_memset_device", "dcrx_synchronize", "dcrx_event_create",
@@ -432,6 +432,7 @@ def lib():
                                            C.POINTER(SpansC), C.POINTER(SpansC), C.POINTER(SpansC), C.c_char_p, vp, u64,
                                            C.POINTER(u64)]),
         "dcrx_decombine": (i32, [vp, C.POINTER(CfgC), C.POINTER(BatchC), vp, vp]),
+        "dcrx_decombine_chains": (i32, [vp, u32, C.POINTER(CfgC), C.POINTER(BatchC), vp, vp]),
         "dcrx_decombine_device": (i32, [vp, C.POINTER(CfgC), C.POINTER(BatchC), vp, vp, vp]),
         "dcrx_set_timing_events": (i32, [vp, vp, vp]),
         "dcrx_set_step_events": (i32, [vp, vp, vp]),
@@ -953,6 +954,30 @@ def decombine(tables: Tables, batch: PackedBatch, orientation="reverse", allow_n
     if int(cnt[DEVICE_ERRORS]):      # (include/dcrx_codes.h: a wave gave up waiting for another — the records are not complete)
         raise RuntimeError(f"dcrx_decombine: {int(cnt[DEVICE_ERRORS])} device-side wait(s) timed out; the records of this call are incomplete")
     return rec, cnt
+
+
+MAX_CHAINS = 4          # DCRX_MAX_CHAINS
+
+
+def decombine_chains(tables_list, batch: PackedBatch, orientation="reverse", allow_ns=False, lenthreshold=130, flags=0):
+    """dcrx_decombine_chains: one host batch, uploaded once, resolved against every chain's tables.  Returns
+    [(records[RECORD_DTYPE], counters uint64[32]), ...] in the order of `tables_list`; each pair equals what decombine()
+    gives for that chain alone."""
+    tables_list = list(tables_list)
+    cfg = make_cfg(orientation, allow_ns, lenthreshold, flags)
+    n = batch.n_reads
+    recs = [np.zeros(n, dtype=RECORD_DTYPE) for _ in tables_list]
+    cnts = [np.zeros(N_COUNTERS, dtype=np.uint64) for _ in tables_list]
+    k = max(1, len(tables_list))
+    handles = (C.c_void_p * k)(*[t.handle for t in tables_list])
+    rec_ptrs = (C.c_void_p * k)(*[r.ctypes.data if n else None for r in recs])
+    cnt_ptrs = (C.c_void_p * k)(*[c.ctypes.data for c in cnts])
+    b = batch.as_c()
+    check(lib().dcrx_decombine_chains(handles, len(tables_list), C.byref(cfg), C.byref(b), rec_ptrs, cnt_ptrs))
+    for cnt in cnts:
+        if int(cnt[DEVICE_ERRORS]):
+            raise RuntimeError(f"dcrx_decombine_chains: {int(cnt[DEVICE_ERRORS])} device-side wait(s) timed out; the records of this call are incomplete")
+    return list(zip(recs, cnts))
 
 
 def synth_cfg(seed: int, read_len: int = 150, p_rearranged: float = 0.45, sub_rate: float = 0.005,

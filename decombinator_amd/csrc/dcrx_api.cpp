@@ -509,15 +509,49 @@ int dcrx_decombine(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *
   return rc;
 }
 
+static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
+                                 dcrx_record_t *const *records, uint64_t *const *counters);
+
+// The multi-chain host-buffer entry: the same epilogue as dcrx_decombine, over every stream the call used.
+int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                          const dcrx_batch_t *hb, dcrx_record_t *const *records, uint64_t *const *counters) {
+  if (!tables || !cfg || !records || !counters) return set_err(DCRX_E_INVALID, "null argument");
+  if (n_chains == 0 || n_chains > DCRX_MAX_CHAINS) return set_err(DCRX_E_INVALID, "n_chains must be 1 .. DCRX_MAX_CHAINS");
+  for (uint32_t c = 0; c < n_chains; c++) {
+    if (!tables[c]) return set_err(DCRX_E_INVALID, "tables[c] is null");
+    for (uint32_t e = 0; e < c; e++)
+      if (tables[e] == tables[c]) return set_err(DCRX_E_INVALID, "the same tables handle twice: every chain needs a handle (and a workspace) of its own");
+  }
+  bool sink_was_on[DCRX_MAX_CHAINS];
+  for (uint32_t c = 0; c < n_chains; c++) { sink_was_on[c] = tables[c]->sink_on; tables[c]->sink_on = false; }
+  int rc;
+  try { rc = decombine_chains_host(tables, n_chains, cfg, hb, records, counters); }
+  catch (const std::bad_alloc &) { rc = set_err(DCRX_E_NOMEM, "out of host memory in dcrx_decombine_chains"); }
+  catch (const std::exception &e) { rc = set_err(DCRX_E_NOMEM, std::string("dcrx_decombine_chains: ") + e.what()); }
+  catch (...) { rc = set_err(DCRX_E_NOMEM, "dcrx_decombine_chains: unexpected exception"); }
+  if (rc != DCRX_OK) {
+    const std::string keep = g_err;
+    for (uint32_t c = 0; c < n_chains; c++) {
+      dcrx_tables *t = tables[c];
+      if (t->hs_in) (void)hipStreamSynchronize(t->hs_in);
+      if (t->hs_run) (void)hipStreamSynchronize(t->hs_run);
+      if (t->hs_out) (void)hipStreamSynchronize(t->hs_out);
+      t->ws_dirty = true;
+    }
+    (void)hipGetLastError();
+    g_err = keep;
+  }
+  for (uint32_t c = 0; c < n_chains; c++) tables[c]->sink_on = sink_was_on[c];
+  return rc;
+}
+
 }  // extern "C"
 
-static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters) {
-  if (!t || !cfg || !counters) return set_err(DCRX_E_INVALID, "null argument");
-  int rc = check_batch(hb);
-  if (rc) return rc;
+// ---- the host-buffer entries' common parts ----------------------------------------------------------------------------
+
+// host-side validation of a host batch that the device entry cannot afford (after check_batch)
+static int check_host_batch(const dcrx_batch_t *hb) {
   const uint64_t n = hb->n_reads;
-  if (n && !records) return set_err(DCRX_E_INVALID, "records is null");
-  // host-side validation the device entry cannot afford
   if (hb->lens) {
     for (uint64_t r = 0; r < n; r++) {
       if (hb->lens[r] > 4 * hb->stride) return set_err(DCRX_E_INVALID, "a read is longer than 4*stride");
@@ -534,65 +568,103 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
     const uint32_t len = hb->lens ? hb->lens[hb->exc_read[i]] : hb->read_len;
     if (hb->exc_pos[i] >= len) return set_err(DCRX_E_INVALID, "exception position beyond the read");
   }
+  return DCRX_OK;
+}
+
+// One chunk's staging: the input half (packed | lens | exc_read | exc_pos | exc_chr) and the output half (records |
+// counters), offsets inside each half.  (long reads: a chunk's packed bytes stay within what 2 M reads of 150 nt take)
+struct HostLayout {
+  uint64_t chunk = 0;
+  size_t o_lens = 0, o_er = 0, o_ep = 0, o_ec = 0, in_bytes = 0;
+  size_t o_cnt = 0, out_bytes = 0;
+};
+static HostLayout host_layout(const dcrx_batch_t *hb) {
+  HostLayout L;
+  const uint64_t n = hb->n_reads;
+  L.chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), std::max<uint64_t>(1024, std::min<uint64_t>(DCRX_HOST_CHUNK, ((uint64_t)DCRX_HOST_CHUNK * 40) / hb->stride)));
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  uint64_t max_exc = 0;       // the most exception entries any chunk holds
+  uint64_t e = 0;
+  for (uint64_t c0 = 0; c0 < n; c0 += L.chunk) {
+    const uint64_t e0 = e;
+    while (e < hb->n_exc && hb->exc_read[e] < c0 + L.chunk) e++;
+    max_exc = std::max(max_exc, e - e0);
+  }
+  L.o_lens = al(L.chunk * hb->stride + 16);
+  L.o_er = L.o_lens + al(hb->lens ? L.chunk * 2 : 0);
+  L.o_ep = L.o_er + al(max_exc * 4);
+  L.o_ec = L.o_ep + al(max_exc * 2);
+  L.in_bytes = L.o_ec + al(max_exc);
+  L.o_cnt = al(L.chunk * sizeof(dcrx_record_t));
+  L.out_bytes = L.o_cnt + al(DCRX_N_COUNTERS * 8);
+  return L;
+}
+
+// the handle's staging buffers hold at least `bytes`, on the device and pinned on the host
+static int ensure_staging(dcrx_tables *t, size_t bytes) {
+  if (bytes > t->stage_bytes) {
+    (void)hipFree(t->d_stage); t->d_stage = nullptr; t->stage_bytes = 0;
+    HIP_TRY(hipMalloc(&t->d_stage, bytes));
+    t->stage_bytes = bytes;
+  }
+  if (bytes > t->h_stage_bytes) {
+    if (t->h_stage) (void)hipHostFree(t->h_stage);
+    t->h_stage = nullptr; t->h_stage_bytes = 0;
+    HIP_TRY(hipHostMalloc(&t->h_stage, bytes, hipHostMallocDefault));
+    t->h_stage_bytes = bytes;
+  }
+  return DCRX_OK;
+}
+
+// the handle's host-entry streams that a call asks for (each made once), and the events that order them
+static int ensure_host_streams(dcrx_tables *t, bool in, bool run, bool out) {
+  if (in && !t->hs_in) HIP_TRY(hipStreamCreateWithFlags(&t->hs_in, hipStreamNonBlocking));
+  if (run && !t->hs_run) HIP_TRY(hipStreamCreateWithFlags(&t->hs_run, hipStreamNonBlocking));
+  if (out && !t->hs_out) HIP_TRY(hipStreamCreateWithFlags(&t->hs_out, hipStreamNonBlocking));
+  for (int k = 0; k < 2; k++) {
+    if (!t->hev_in[k]) HIP_TRY(hipEventCreateWithFlags(&t->hev_in[k], hipEventDisableTiming));
+    if (!t->hev_run[k]) HIP_TRY(hipEventCreateWithFlags(&t->hev_run[k], hipEventDisableTiming));
+    if (!t->hev_out[k]) HIP_TRY(hipEventCreateWithFlags(&t->hev_out[k], hipEventDisableTiming));
+  }
+  return DCRX_OK;
+}
+
+// Buffers the caller has pinned (dcrx_malloc_host, hipHostMalloc, hipHostRegister) are copied from and to directly: the
+// staging copies — half of a call's time from pageable memory — fall away for them.
+static bool host_pinned(const void *p) {
+  hipPointerAttribute_t a;
+  if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return a.type == hipMemoryTypeHost;
+}
+
+static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters) {
+  if (!t || !cfg || !counters) return set_err(DCRX_E_INVALID, "null argument");
+  int rc = check_batch(hb);
+  if (rc) return rc;
+  const uint64_t n = hb->n_reads;
+  if (n && !records) return set_err(DCRX_E_INVALID, "records is null");
+  rc = check_host_batch(hb);
+  if (rc) return rc;
   // The batch goes through in chunks of DCRX_HOST_CHUNK reads, three streams deep: while the kernels of chunk k run, chunk
   // k + 1 is copied in and the records of chunk k - 1 are copied out (PCIe is full duplex: 40 bytes per read one way, 16 the
   // other), through pinned staging buffers (a copy from pageable memory would not overlap anything).  The loop it stands
   // for is the reference's read loop (decombine.py:963-1050).
-  // (long reads: a chunk's packed bytes stay within what 2 M reads of 150 nt take)
-  const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), std::max<uint64_t>(1024, std::min<uint64_t>(DCRX_HOST_CHUNK, ((uint64_t)DCRX_HOST_CHUNK * 40) / hb->stride)));
+  const HostLayout Lay = host_layout(hb);
+  const uint64_t chunk = Lay.chunk;
   rc = ensure_device(t, chunk, hb->stride);
   if (rc) return rc;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // one chunk's staging: packed | lens | exc_read | exc_pos | exc_chr || records | counters    (x 2 sets)
-  uint64_t max_exc = 0;       // the most exception entries any chunk holds
-  {
-    uint64_t e = 0;
-    for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
-      const uint64_t e0 = e;
-      while (e < hb->n_exc && hb->exc_read[e] < c0 + chunk) e++;
-      max_exc = std::max(max_exc, e - e0);
-    }
-  }
-  const size_t o_packed = 0;
-  const size_t o_lens = o_packed + al(chunk * hb->stride + 16);
-  const size_t o_er = o_lens + al(hb->lens ? chunk * 2 : 0);
-  const size_t o_ep = o_er + al(max_exc * 4);
-  const size_t o_ec = o_ep + al(max_exc * 2);
-  const size_t in_bytes = o_ec + al(max_exc);
+  const size_t o_packed = 0, o_lens = Lay.o_lens, o_er = Lay.o_er, o_ep = Lay.o_ep, o_ec = Lay.o_ec, in_bytes = Lay.in_bytes;
   const size_t o_rec = in_bytes;
-  const size_t o_cnt = o_rec + al(chunk * sizeof(dcrx_record_t));
-  const size_t set_bytes = o_cnt + al(DCRX_N_COUNTERS * 8);
-  if (2 * set_bytes > t->stage_bytes) {
-    (void)hipFree(t->d_stage); t->d_stage = nullptr; t->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&t->d_stage, 2 * set_bytes));
-    t->stage_bytes = 2 * set_bytes;
-  }
-  if (2 * set_bytes > t->h_stage_bytes) {
-    if (t->h_stage) (void)hipHostFree(t->h_stage);
-    t->h_stage = nullptr; t->h_stage_bytes = 0;
-    HIP_TRY(hipHostMalloc(&t->h_stage, 2 * set_bytes, hipHostMallocDefault));
-    t->h_stage_bytes = 2 * set_bytes;
-  }
-  if (!t->hs_in) {
-    HIP_TRY(hipStreamCreateWithFlags(&t->hs_in, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&t->hs_run, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&t->hs_out, hipStreamNonBlocking));
-    for (int k = 0; k < 2; k++) {
-      HIP_TRY(hipEventCreateWithFlags(&t->hev_in[k], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&t->hev_run[k], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&t->hev_out[k], hipEventDisableTiming));
-    }
-  }
+  const size_t o_cnt = o_rec + Lay.o_cnt;
+  const size_t set_bytes = in_bytes + Lay.out_bytes;
+  rc = ensure_staging(t, 2 * set_bytes);
+  if (rc) return rc;
+  rc = ensure_host_streams(t, true, true, true);
+  if (rc) return rc;
   for (int c = 0; c < DCRX_N_COUNTERS; c++) counters[c] = 0;
-  // Buffers the caller has pinned (dcrx_malloc_host, hipHostMalloc, hipHostRegister) are copied from and to directly: the
-  // staging copies — half of this call's time from pageable memory — fall away for them.
-  auto pinned = [](const void *p) {
-    hipPointerAttribute_t a;
-    if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-  };
-  const bool in_direct = n && pinned(hb->packed) && pinned(hb->packed + (size_t)n * hb->stride - 1);
-  const bool out_direct = n && pinned(records) && pinned(reinterpret_cast<const uint8_t *>(records + n) - 1);
+  const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
+  const bool out_direct = n && host_pinned(records) && host_pinned(reinterpret_cast<const uint8_t *>(records + n) - 1);
   const uint64_t n_chunks = n ? (n + chunk - 1) / chunk : 1;
   uint64_t exc_at = 0;
   auto drain = [&](uint64_t k) -> int {       // chunk k's records and counters: from the pinned buffer to the caller's
@@ -663,6 +735,116 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   // (include/dcrx_codes.h: a wave that gave up waiting for another says so in the call's counters — the records would not be
   // complete, and this entry, which has the counters in hand, does not return them as if they were)
   if (counters[DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
+  return DCRX_OK;
+}
+
+// decombine_host for several chains over one batch (arguments checked by dcrx_decombine_chains).  The chunks' input sets
+// live in the first handle's staging, in front of its output sets; every other handle's staging holds only its output sets.
+// Streams: tables[0]'s copy-in stream, and per chain its run stream, which carries the chain's launches and its copy out.
+static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
+                                 dcrx_record_t *const *records, uint64_t *const *counters) {
+  int rc = check_batch(hb);
+  if (rc) return rc;
+  const uint64_t n = hb->n_reads;
+  for (uint32_t c = 0; c < nc; c++) {
+    if (!counters[c]) return set_err(DCRX_E_INVALID, "counters[c] is null");
+    if (n && !records[c]) return set_err(DCRX_E_INVALID, "records[c] is null");
+  }
+  rc = check_host_batch(hb);
+  if (rc) return rc;
+  const HostLayout Lay = host_layout(hb);
+  const uint64_t chunk = Lay.chunk;
+  for (uint32_t c = 0; c < nc; c++) {
+    rc = ensure_device(T[c], chunk, hb->stride);
+    if (rc) return rc;
+    rc = ensure_staging(T[c], (c == 0 ? 2 * Lay.in_bytes : 0) + 2 * Lay.out_bytes);
+    if (rc) return rc;
+    rc = ensure_host_streams(T[c], c == 0, true, false);
+    if (rc) return rc;
+    for (int k = 0; k < DCRX_N_COUNTERS; k++) counters[c][k] = 0;
+  }
+  hipStream_t s_in = T[0]->hs_in;
+  auto in_h = [&](int set) { return T[0]->h_stage + (size_t)set * Lay.in_bytes; };
+  auto in_d = [&](int set) { return T[0]->d_stage + (size_t)set * Lay.in_bytes; };
+  auto out_at = [&](uint32_t c, int set) { return (c == 0 ? 2 * Lay.in_bytes : 0) + (size_t)set * Lay.out_bytes; };
+  const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
+  bool out_direct[DCRX_MAX_CHAINS];
+  for (uint32_t c = 0; c < nc; c++)
+    out_direct[c] = n && host_pinned(records[c]) && host_pinned(reinterpret_cast<const uint8_t *>(records[c] + n) - 1);
+  const uint64_t n_chunks = n ? (n + chunk - 1) / chunk : 1;
+  uint64_t exc_at = 0;
+  auto drain = [&](uint64_t k) -> int {       // chunk k's records and counters of every chain: pinned buffers to the caller's
+    const int set = (int)(k & 1);
+    const uint64_t c0 = k * chunk, cn = std::min<uint64_t>(chunk, n - c0);
+    for (uint32_t c = 0; c < nc; c++) {
+      HIP_TRY(hipEventSynchronize(T[c]->hev_out[set]));
+      const uint8_t *h = T[c]->h_stage + out_at(c, set);
+      if (cn && !out_direct[c]) par_memcpy(records[c] + c0, h, cn * sizeof(dcrx_record_t));
+      const uint64_t *hc = reinterpret_cast<const uint64_t *>(h + Lay.o_cnt);
+      for (int i = 0; i < DCRX_N_COUNTERS; i++) counters[c][i] += hc[i];
+    }
+    return DCRX_OK;
+  };
+  for (uint64_t k = 0; k < n_chunks; k++) {
+    const int set = (int)(k & 1);
+    const uint64_t c0 = k * chunk, cn = n ? std::min<uint64_t>(chunk, n - c0) : 0;
+    uint8_t *h = in_h(set), *d = in_d(set);
+    // chunk k - 2's records leave the pinned buffers on a helper thread while this thread fills the input set (the
+    // input and output sets do not overlap), once the copy in of chunk k - 2, which read the same bytes, is over
+    int drc = DCRX_OK;
+    std::thread helper;
+    if (k >= 2) helper = std::thread([&, k] { drc = drain(k - 2); });
+    struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_helper{helper};
+    if (k >= 2) HIP_TRY(hipEventSynchronize(T[0]->hev_in[set]));
+    const uint64_t e0 = exc_at;
+    while (exc_at < hb->n_exc && hb->exc_read[exc_at] < c0 + cn) exc_at++;
+    const uint64_t ne = exc_at - e0;
+    if (cn && !in_direct) par_memcpy(h, hb->packed + c0 * hb->stride, cn * hb->stride);
+    if (hb->lens && cn) std::memcpy(h + Lay.o_lens, hb->lens + c0, cn * 2);
+    uint32_t *her = reinterpret_cast<uint32_t *>(h + Lay.o_er);
+    for (uint64_t i = 0; i < ne; i++) her[i] = hb->exc_read[e0 + i] - (uint32_t)c0;
+    if (ne) { std::memcpy(h + Lay.o_ep, hb->exc_pos + e0, ne * 2); std::memcpy(h + Lay.o_ec, hb->exc_chr + e0, ne); }
+    if (helper.joinable()) helper.join();
+    if (drc) return drc;
+    // copy in, once every chain's kernels that read this input set (chunk k - 2) are over
+    if (k >= 2)
+      for (uint32_t c = 0; c < nc; c++) HIP_TRY(hipStreamWaitEvent(s_in, T[c]->hev_run[set], 0));
+    if (in_direct) {
+      HIP_TRY(hipMemcpyAsync(d, hb->packed + c0 * hb->stride, cn * hb->stride, hipMemcpyHostToDevice, s_in));
+      if (Lay.in_bytes > Lay.o_lens) HIP_TRY(hipMemcpyAsync(d + Lay.o_lens, h + Lay.o_lens, Lay.in_bytes - Lay.o_lens, hipMemcpyHostToDevice, s_in));
+    } else {
+      HIP_TRY(hipMemcpyAsync(d, h, Lay.in_bytes, hipMemcpyHostToDevice, s_in));
+    }
+    HIP_TRY(hipEventRecord(T[0]->hev_in[set], s_in));
+    dcrx_batch_t db = *hb;
+    db.n_reads = cn;
+    db.packed = d;
+    db.lens = hb->lens ? reinterpret_cast<const uint16_t *>(d + Lay.o_lens) : nullptr;
+    db.n_exc = ne;
+    db.exc_read = reinterpret_cast<const uint32_t *>(d + Lay.o_er);
+    db.exc_pos = reinterpret_cast<const uint16_t *>(d + Lay.o_ep);
+    db.exc_chr = d + Lay.o_ec;
+    // every chain: kernels, then its copy out, on its own stream (which orders chunk k's kernels behind chunk k - 2's copy
+    // out of the same output set)
+    for (uint32_t c = 0; c < nc; c++) {
+      dcrx_tables *t = T[c];
+      uint8_t *od = t->d_stage + out_at(c, set), *oh = t->h_stage + out_at(c, set);
+      HIP_TRY(hipStreamWaitEvent(t->hs_run, T[0]->hev_in[set], 0));
+      rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(od), reinterpret_cast<uint64_t *>(od + Lay.o_cnt), t->hs_run);
+      if (rc) return rc;          // (dcrx_decombine_chains drains the streams)
+      HIP_TRY(hipEventRecord(t->hev_run[set], t->hs_run));
+      if (out_direct[c]) {
+        if (cn) HIP_TRY(hipMemcpyAsync(records[c] + c0, od, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_run));
+        HIP_TRY(hipMemcpyAsync(oh + Lay.o_cnt, od + Lay.o_cnt, Lay.out_bytes - Lay.o_cnt, hipMemcpyDeviceToHost, t->hs_run));
+      } else {
+        HIP_TRY(hipMemcpyAsync(oh, od, Lay.out_bytes, hipMemcpyDeviceToHost, t->hs_run));
+      }
+      HIP_TRY(hipEventRecord(t->hev_out[set], t->hs_run));
+    }
+  }
+  for (uint64_t k = n_chunks >= 2 ? n_chunks - 2 : 0; k < n_chunks; k++) { rc = drain(k); if (rc) return rc; }
+  for (uint32_t c = 0; c < nc; c++)
+    if (counters[c][DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
   return DCRX_OK;
 }
 

@@ -38,13 +38,44 @@ _COMP = str.maketrans("ACGTMRWSYKVHDBXNUacgtmrwsykvhdbxnu", "TGCAKYWSRMBDHVXNAtg
 # reads sent to the GPU per dcrx_decombine call
 BATCH_READS = 1 << 20
 # wall seconds of the last decombinator() call by phase: FASTQ read, 2-bit pack, device call (H2D + kernels
-# + D2H), row assembly
+# + D2H), row assembly; after decombinator_chains() "device" is the one call for all chains and "rows" is split per chain
+# as "rows:<chain letter>"
 stage_seconds: dict = {}
 stage_info: dict = {}          # how the last stage read its input: sharded_input, byte_ranges (this rank's), rank, world
 
 # module-level state kept for callers that used the reference's globals
 counts: coll.Counter = coll.Counter()
 _current = None  # the ChainTables of the last import_tcr_info()
+# decombinator_chains(): per chain letter, its counters (what `counts` holds after a single-chain run) and its copy of the
+# arguments (with the reference's in-place `tags` rewrite for that chain only)
+chain_counts: dict = {}
+chain_args: dict = {}
+
+# what -c takes for one chain (reference :609-627), case-insensitive
+_CHAIN_SPELLINGS = {"A": "a", "ALPHA": "a", "TRA": "a", "TCRA": "a", "B": "b", "BETA": "b", "TRB": "b", "TCRB": "b",
+                    "G": "g", "GAMMA": "g", "TRG": "g", "TCRG": "g", "D": "d", "DELTA": "d", "TRD": "d", "TCRD": "d"}
+
+
+def chain_list(chain):
+    """The items of a comma-separated -c value ("a,b", "alpha, beta"), or None for a single chain (or none)."""
+    if not chain or "," not in chain:
+        return None
+    return [x.strip() for x in chain.split(",")]
+
+
+def resolve_chain_list(items) -> list:
+    """The chain letters of a -c list, in the order given; ValueError for an item no single -c takes, or for a chain named
+    twice (b,beta)."""
+    letters = []
+    for item in items:
+        c = _CHAIN_SPELLINGS.get(item.upper())
+        if c is None:
+            raise ValueError(f"-c {','.join(items)}: {item!r} is not a chain (a/b/g/d, alpha/beta/gamma/delta, tra/trb/..., "
+                             "case-insensitive)")
+        if c in letters:
+            raise ValueError(f"-c {','.join(items)}: the {chainnams[c]} chain is named twice")
+        letters.append(c)
+    return letters
 
 
 def opener_check(inputargs):
@@ -121,6 +152,21 @@ def _new_summary_file(summaryname, logpath, date, chain_given, chain, samplenam)
     raise RuntimeError("no free summary file name")
 
 
+class EmptyInput(ValueError):
+    """fastq_check(): fewer than four lines."""
+
+
+def _empty_input_log(inputargs, samplenam, summaryname, logpath, chain) -> None:
+    """The two-line summary log of an input with fewer than four lines (reference :130-140)."""
+    if inputargs["suppresssummary"] == False:  # noqa: E712
+        inout_name = "_".join(f"{samplenam}".split("_")[:-1]) + f"_{chainnams[chain]}"
+        summstr = "OutputFile," + inout_name + "\nNumberReadsInput," + "0"
+        name, fh = _new_summary_file(summaryname, logpath, strftime("%Y_%m_%d"), inputargs["chain"], chain, samplenam)
+        print(summstr, file=fh)
+        fh.close()
+        sort_permissions(name)
+
+
 def fastq_check(inputargs, opener, samplenam, summaryname, logpath, chain=None) -> None:
     """Rudimentary FASTQ sanity check (reference :126-179): fewer than four lines is a
     ValueError (after writing the two-line empty-input log); then a '@' header, a '+'
@@ -129,14 +175,8 @@ def fastq_check(inputargs, opener, samplenam, summaryname, logpath, chain=None) 
     with opener(inputargs["infile"], "rt") as possfq:
         head = list(itertools.islice(possfq, 4))
         if len(head) < 4:
-            if inputargs["suppresssummary"] == False:  # noqa: E712
-                inout_name = "_".join(f"{samplenam}".split("_")[:-1]) + f"_{chainnams[chain]}"
-                summstr = "OutputFile," + inout_name + "\nNumberReadsInput," + "0"
-                name, fh = _new_summary_file(summaryname, logpath, strftime("%Y_%m_%d"), inputargs["chain"], chain, samplenam)
-                print(summstr, file=fh)
-                fh.close()
-                sort_permissions(name)
-            raise ValueError(
+            _empty_input_log(inputargs, samplenam, summaryname, logpath, chain)
+            raise EmptyInput(
                 "There are fewer than four lines in this file, and thus it is not a valid FASTQ file. "
                 "Please check input and try again.")
         # the reference validates the NEXT four lines (its islice continues on the same handle);
@@ -241,10 +281,7 @@ def import_tcr_info(inputargs) -> ChainTables:
     if len(inner) == 1:
         counts["chain_detected"] = 1
     if inputargs["chain"]:
-        c = inputargs["chain"].upper()
-        chain = {"A": "a", "ALPHA": "a", "TRA": "a", "TCRA": "a", "B": "b", "BETA": "b", "TRB": "b", "TCRB": "b",
-                 "G": "g", "GAMMA": "g", "TRG": "g", "TCRG": "g", "D": "d", "DELTA": "d", "TRD": "d",
-                 "TCRD": "d"}.get(c)
+        chain = _CHAIN_SPELLINGS.get(inputargs["chain"].upper())
         if chain is None:
             print(nochain_error)
             sys.exit()
@@ -305,13 +342,14 @@ def dcr(read, inputargs, tcr: ChainTables | None = None):
     return [int(r["v"]), int(r["j"]), int(r["vdel"]), int(r["jdel"]), read[s:s + l], int(r["v_start"]), int(r["j_end"])]
 
 
-def _add_counts(cnt, skip=()):
+def _add_counts(cnt, skip=(), into=None):
+    into = counts if into is None else into
     for i, name in enumerate(nat.COUNTER_NAMES):
         if name in skip or name == "frame_forward":
             continue
         v = int(cnt[i])
         if v:
-            counts[name] += v
+            into[name] += v
 
 
 def assemble_rows(records, reads, quals, ids, bcs, bcqs, sampling_tails=None):
@@ -541,8 +579,10 @@ def _assemble_rows_spans_py(records, sp):
     return rows
 
 
-def _summary_text(inputargs, chain, samplenam, date, timetaken):
-    """The Decombinator summary CSV body (reference :1097-1195), line for line."""
+def _summary_text(inputargs, chain, samplenam, date, timetaken, counts=None):
+    """The Decombinator summary CSV body (reference :1097-1195), line for line (`counts`: the chain's counters, the
+    module's by default)."""
+    counts = globals()["counts"] if counts is None else counts
     inout_name = "_".join(f"{samplenam}".split("_")[:-1]) + f"_{chainnams[chain]}"
     lines = ["Property,Value", "Directory," + os.getcwd(), "InputFile," + inout_name, "OutputFile," + inout_name,
              "DateFinished," + date, "TimeFinished," + strftime("%H:%M:%S"),
@@ -578,11 +618,9 @@ def _summary_text(inputargs, chain, samplenam, date, timetaken):
     return "\n".join(lines)
 
 
-def _decombinator_setup(inputargs: dict, rank: int, world: int, state: dict) -> None:
-    """This rank's part of the stage before anything is read: tables, (rank 0) log directory and FASTQ check.  No collective
-    in here: a sharded run exchanges what this raised before it goes on (decombinator())."""
-    print("Running Decombinator (MI355X / HIP build) version", __version__)
-    opener = opener_check(inputargs)
+def _chain_setup(inputargs: dict, rank: int) -> dict:
+    """One chain's part of the setup: its tables (import_tcr_info: resets `counts`, rewrites inputargs["tags"] where the
+    reference does), the sample name and its summary log's name; rank 0 creates the log directory."""
     tcr = import_tcr_info(inputargs)
     chain = tcr.chain
     samplenam = str(inputargs["infile"].split(".")[0])
@@ -599,27 +637,63 @@ def _decombinator_setup(inputargs: dict, rank: int, world: int, state: dict) -> 
         if inputargs["chain"]:
             summaryname += chainnams[chain] + "_"
         summaryname += samplenam + "_Decombinator_Summary.csv"
+    return dict(tcr=tcr, chain=chain, samplenam=samplenam, summaryname=summaryname, logpath=logpath, date=date,
+                counts=counts, args=inputargs)
+
+
+def _input_checks(inputargs: dict, rank: int, chains: list) -> None:
+    """The FASTQ check (once, whatever the number of chains: an input with fewer than four lines leaves every chain's
+    two-line log) and the orientation / barcode-read arguments."""
+    opener = opener_check(inputargs)
     if inputargs["dontcheck"] == False and rank == 0:  # noqa: E712
         # (the reference crashes here with suppresssummary=True, SURVEY.md A.7 #14; this build checks anyway)
-        fastq_check(inputargs, opener, samplenam, summaryname, logpath, chain)
+        ch = chains[0]
+        try:
+            fastq_check(ch["args"], opener, ch["samplenam"], ch["summaryname"], ch["logpath"], ch["chain"])
+        except EmptyInput:
+            for ch in chains[1:]:
+                _empty_input_log(ch["args"], ch["samplenam"], ch["summaryname"], ch["logpath"], ch["chain"])
+            raise
 
     if inputargs["orientation"] not in nat.ORIENTATIONS:
         raise ValueError("orientation must be forward, reverse or both")
     if inputargs["nobarcoding"] == False and inputargs["bc_read"] not in ("R1", "R2"):  # noqa: E712
         raise ValueError("bc_read must be R1 or R2")
-    state.update(tcr=tcr, chain=chain, samplenam=samplenam, summaryname=summaryname, logpath=logpath, date=date)
+
+
+def _decombinator_setup(inputargs: dict, rank: int, world: int, state: dict) -> None:
+    """This rank's part of the stage before anything is read: tables, (rank 0) log directory and FASTQ check.  No collective
+    in here: a sharded run exchanges what this raised before it goes on (decombinator())."""
+    print("Running Decombinator (MI355X / HIP build) version", __version__)
+    ch = _chain_setup(inputargs, rank)
+    _input_checks(inputargs, rank, [ch])
+    state.update({k: ch[k] for k in ("tcr", "chain", "samplenam", "summaryname", "logpath", "date")})
+    state["chains"] = [ch]
+
+
+def _device_call(tables: list, batch, inputargs: dict) -> list:
+    """[(records, counters)] per chain: dcrx_decombine for one chain, dcrx_decombine_chains (one upload) for several."""
+    args = (inputargs["orientation"], inputargs["allowNs"], inputargs["lenthreshold"])
+    if len(tables) == 1:
+        return [nat.decombine(tables[0], batch, *args)]
+    return nat.decombine_chains(tables, batch, *args)
 
 
 def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan_shards=None) -> None:
     """The read loop (reference :948-1050) over this rank's records: every rank of a sharded run comes here (the shard plan is
-    a collective), and leaves its rows in `state`."""
-    tcr = state["tcr"]
+    a collective), and leaves its rows in `state` — for every chain of state["chains"], each batch read, packed and handed
+    to the device once."""
+    chains = state["chains"]
+    tables = [ch["tcr"].tables for ch in chains]
+    cnts = [ch["counts"] for ch in chains]
+    multi = len(chains) > 1
+    max_read_len = min(ch["tcr"].max_read_len for ch in chains)
     bclength = inputargs["bclength"]
-    counts["start_time"] = time()
+    for c in cnts:
+        c["start_time"] = time()
     stage_seconds.clear()
     print("Decombining FASTQ data...")
-    outdata = N12Rows()
-    orientation = inputargs["orientation"]
+    outdatas = [N12Rows() for _ in chains]
 
     if inputargs["nobarcoding"] == False:  # noqa: E712
         paired = inputargs["bc_read"] == "R2"
@@ -652,46 +726,53 @@ def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan
                     if spans.last:
                         break
                     continue
-                outdata._tag = rank if ranges is not None else batch_index
+                for od in outdatas:
+                    od._tag = rank if ranges is not None else batch_index
                 n = len(spans.v_start)
                 if inputargs["allowNs"] == False:  # noqa: E712    counted, never dropped (:985-989)
-                    counts["dcrfilter_barcodeN"] += nat.count_prefix_byte(spans.bc_text, spans.bc_start, spans.bc_len,
-                                                                          1 << 30, "N")
-                before = counts["read_count"]
-                counts["read_count"] += n
-                if inputargs["dontcount"] == False and counts["read_count"] // 100000 > before // 100000:  # noqa: E712
-                    print("\t read", (counts["read_count"] // 100000) * 100000)
+                    bc_n = nat.count_prefix_byte(spans.bc_text, spans.bc_start, spans.bc_len, 1 << 30, "N")
+                    for c in cnts:
+                        c["dcrfilter_barcodeN"] += bc_n
+                before = cnts[0]["read_count"]
+                for c in cnts:
+                    c["read_count"] += n
+                if inputargs["dontcount"] == False and cnts[0]["read_count"] // 100000 > before // 100000:  # noqa: E712
+                    print("\t read", (cnts[0]["read_count"] // 100000) * 100000)
                 t1 = time()
                 # reads of up to 511 nt run on the register shapes; longer ones (merged pairs, long amplicons: the reference has no
                 # length limit, decombine.py:228-265, :534-585) leave the batch for a call of their own — one read per lane from
                 # memory, dcrx's long form — and come back into their places; beyond 65 535 nt (the 16-bit lengths and offsets of
                 # the record) nothing decombines them: said before anything of the batch is processed
                 longest = int(spans.v_len.max()) if n else 0
-                if longest > tcr.max_read_len:
-                    raise ValueError(f"a read of {longest} nt exceeds the {tcr.max_read_len} nt this build decombines "
+                if longest > max_read_len:
+                    raise ValueError(f"a read of {longest} nt exceeds the {max_read_len} nt this build decombines "
                                      f"(dcrx_tables_info.max_read_len); trim or split the reads")
                 t2 = t1
                 if longest > nat.FAST_MAX_READ_LEN:
                     is_long = spans.v_len > nat.FAST_MAX_READ_LEN
-                    rec = np.empty(n, dtype=nat.RECORD_DTYPE)
-                    cnt = np.zeros(nat.N_COUNTERS, dtype=np.uint64)
+                    res = [(np.empty(n, dtype=nat.RECORD_DTYPE), np.zeros(nat.N_COUNTERS, dtype=np.uint64)) for _ in chains]
                     for idx in (np.nonzero(~is_long)[0], np.nonzero(is_long)[0]):
                         if len(idx) == 0:
                             continue
                         tp = time()
                         batch = nat.pack_reads_span(spans.v_text, spans.v_start[idx], spans.v_len[idx])
                         t2 += time() - tp
-                        r_part, c_part = nat.decombine(tcr.tables, batch, orientation, inputargs["allowNs"], inputargs["lenthreshold"])
-                        rec[idx] = r_part
-                        cnt += c_part.astype(np.uint64)
+                        for (rec, cnt), (r_part, c_part) in zip(res, _device_call(tables, batch, inputargs)):
+                            rec[idx] = r_part
+                            cnt += c_part.astype(np.uint64)
                 else:
                     batch = nat.pack_reads_span(spans.v_text, spans.v_start, spans.v_len)
                     t2 = time()
-                    rec, cnt = nat.decombine(tcr.tables, batch, orientation, inputargs["allowNs"], inputargs["lenthreshold"])
+                    res = _device_call(tables, batch, inputargs)
                 t3 = time()
-                _add_counts(cnt, skip=("read_count",))
-                assemble_rows_spans(rec, spans, into=outdata)
-                t4 = time()
+                t4 = t3
+                for ch, (rec, cnt), od in zip(chains, res, outdatas):
+                    ta = time()
+                    _add_counts(cnt, skip=("read_count",), into=ch["counts"])
+                    assemble_rows_spans(rec, spans, into=od)
+                    t4 = time()
+                    if multi:
+                        stage_seconds["rows:" + ch["chain"]] = stage_seconds.get("rows:" + ch["chain"], 0.0) + (t4 - ta)
                 for key, dt in (("read", t1 - t0), ("pack", t2 - t1), ("device", t3 - t2), ("rows", t4 - t3)):
                     stage_seconds[key] = stage_seconds.get(key, 0.0) + dt
                 if spans.last:
@@ -708,7 +789,9 @@ def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan
             print("Non-barcoding option selected, but default output file extension (n12) detected. "
                   "Automatically changing to 'nbc'.")
 
-    state.update(outdata=outdata)
+    for ch, od in zip(chains, outdatas):
+        ch["outdata"] = od
+    state.update(outdata=outdatas[0])
 
 
 def decombinator(inputargs: dict, shard=None, reduce_counts=None, exchange_error=None, plan_shards=None) -> list:
@@ -757,3 +840,47 @@ def decombinator(inputargs: dict, shard=None, reduce_counts=None, exchange_error
         fh.close()
         sort_permissions(name)
     return outdata
+
+
+def decombinator_chains(inputargs: dict) -> dict:
+    """The decombine stage for every chain of a comma-separated -c (`a,b`, `alpha,beta`, `g,d`, ...) in one pass over the
+    FASTQ: the FASTQ check runs once, each reader is opened once, each batch is packed once and handed to the device once
+    for all chains (nat.decombine_chains).  Returns {chain letter: N12Rows} in the order given.
+
+    Each chain runs with its own copy of `inputargs` (chain set to its item, kept in `chain_args`: the reference's in-place
+    `tags` rewrite for gamma / delta and mouse applies to that chain's copy alone), its own tables, counters (kept in
+    `chain_counts`) and summary log: every chain's rows, counters and log equal those of a run with that item alone."""
+    items = chain_list(inputargs.get("chain"))
+    if items is None:
+        raise ValueError("decombinator_chains needs a comma-separated list of chains in inputargs['chain'] (e.g. 'a,b')")
+    resolve_chain_list(items)           # (refused before anything is read: an unknown item, a chain named twice)
+    global counts
+    print("Running Decombinator (MI355X / HIP build) version", __version__)
+    chain_counts.clear()
+    chain_args.clear()
+    chains = []
+    for item in items:
+        args = dict(inputargs, chain=item)
+        ch = _chain_setup(args, 0)
+        chain_counts[ch["chain"]] = ch["counts"]
+        chain_args[ch["chain"]] = args
+        chains.append(ch)
+    _input_checks(inputargs, 0, chains)
+    _decombinator_loop(inputargs, 0, 1, {"chains": chains})
+    out = {}
+    for ch in chains:
+        counts = ch["counts"]
+        args, chain, samplenam = ch["args"], ch["chain"], ch["samplenam"]
+        counts["end_time"] = time()
+        timetaken = counts["end_time"] - counts["start_time"]
+        print("Analysed", "{:,}".format(counts["read_count"]), "reads, finding", "{:,}".format(counts["vj_count"]),
+              chainnams[chain], "VJ rearrangements")
+        print("Reading from", args["infile"] + ", writing to variable")
+        print("Took", str(round(timetaken, 2)), "seconds")
+        if args["suppresssummary"] == False:  # noqa: E712
+            name, fh = _new_summary_file(ch["summaryname"], ch["logpath"], ch["date"], args["chain"], chain, samplenam)
+            print(_summary_text(args, chain, samplenam, ch["date"], timetaken, counts), file=fh)
+            fh.close()
+            sort_permissions(name)
+        out[chain] = ch["outdata"]
+    return out

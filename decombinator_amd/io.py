@@ -48,7 +48,9 @@ def _common(p: argparse.ArgumentParser):
     p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
     p.add_argument("-dc", "--dontcount", action="store_true", help="Do not print the running count")
     p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
-    p.add_argument("-c", "--chain", type=str, help="TCR chain (a/b/g/d)")
+    p.add_argument("-c", "--chain", type=str,
+                   help="TCR chain (a/b/g/d); decombine and pipeline also take a comma-separated list (a,b or alpha,beta; g,d), "
+                        "resolved in one pass over the FASTQ with the outputs each chain alone would give")
     p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
     p.add_argument("-ds", "--dontsave", action="store_true", help="Do not save output files")
     p.add_argument("-sa", "--sampling_analysis", action="store_true", help="Keep the R2 V-gene tail per row")

@@ -12,6 +12,7 @@ from datetime import datetime
 from typing import Any, Optional
 
 from . import collapse
+from . import decombine as dec
 from .decombine import decombinator
 from .io import cli_args, write_out_intermediate
 
@@ -35,9 +36,30 @@ def _opener(path):
 
 
 def run(args: Optional[dict[str, Any]] = None, cli_args: Optional[dict[str, Any]] = None):
-    start = datetime.now()
     inp = cli_args if cli_args else args
+    if dec.chain_list(inp.get("chain")) is not None:
+        return run_chains(inp)
+    start = datetime.now()
     data = decombinator(inp)
+    return _after_decombine(data, inp, start)
+
+
+def run_chains(inp: dict) -> dict:
+    """`pipeline -c a,b`: the FASTQ decombined once for every chain (decombine.decombinator_chains), then per chain, with
+    that chain's arguments, what run() does after decombining.  Returns {chain letter: what run() returns}."""
+    start = datetime.now()
+    per_chain = dec.decombinator_chains(inp)
+    return {chain: _after_decombine(data, _files_args(chain), start) for chain, data in per_chain.items()}
+
+
+def _files_args(chain: str) -> dict:
+    """A chain's arguments of the last decombinator_chains() for what follows the decombine step: the chain as its letter
+    (the writers and collapse name files by chainnams[chain], which holds letters; for a list of letters this is the
+    chain's own copy as it is)."""
+    return dict(dec.chain_args[chain], chain=chain)
+
+
+def _after_decombine(data, inp, start):
     if not inp["dontsave"]:
         write_out_intermediate(data, inp, ".n12")
     print("Decombinator complete...")
@@ -63,7 +85,20 @@ def run(args: Optional[dict[str, Any]] = None, cli_args: Optional[dict[str, Any]
 
 def main(argv=None):
     inp = cli_args(argv)
-    if inp["command"] == "decombine":
+    if inp["command"] in ("collapse", "translate") and dec.chain_list(inp.get("chain")) is not None:
+        from .io import create_parser
+        create_parser().error(f"{inp['command']} works on one per-chain file: -c takes one chain there, not a list "
+                              f"({inp['chain']})")
+    if inp["command"] in ("decombine", "pipeline") and dec.chain_list(inp.get("chain")) is not None:
+        try:
+            dec.resolve_chain_list(dec.chain_list(inp["chain"]))      # refused before anything is read
+        except ValueError as e:
+            from .io import create_parser
+            create_parser().error(str(e))
+    if inp["command"] == "decombine" and dec.chain_list(inp.get("chain")) is not None:
+        for chain, data in dec.decombinator_chains(inp).items():
+            write_out_intermediate(data, _files_args(chain), ".n12")
+    elif inp["command"] == "decombine":
         data = decombinator(inp)
         write_out_intermediate(data, inp, ".n12")
     elif inp["command"] == "pipeline":

@@ -507,6 +507,9 @@ def decombinator_sharded(inputargs: dict, comm, device_index: int | None = None)
     from decombinator_amd import _native as nat
     from decombinator_amd import decombine as dec
 
+    if dec.chain_list(inputargs.get("chain")) is not None:
+        raise ValueError(f"-c {inputargs['chain']}: the sharded multi-GPU run resolves one chain; run a list of chains on one "
+                         "GPU (decombine.decombinator_chains) or one sharded run per chain")
     if comm is None:
         raise RuntimeError("decombinator_sharded needs a communicator (decombinator_amd._native.comm_from_env())")
     rank, world = comm.rank, comm.world

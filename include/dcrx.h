@@ -244,6 +244,19 @@ int64_t dcrx_assemble_rows(const dcrx_record_t *records, uint64_t n_reads, const
 int dcrx_decombine(dcrx_tables_t *tables, const dcrx_cfg_t *cfg, const dcrx_batch_t *host_batch,
                    dcrx_record_t *records, uint64_t *counters);
 
+/* Several chains of one library (alpha + beta, gamma + delta) over ONE host batch: dcrx_decombine's chunk pipeline with
+ * one upload per chunk and n_chains resolutions of it.  Each chunk is copied in once, into the staging of tables[0];
+ * each chain's launches run on that handle's own stream, with its own workspace, gated by an event on the copy in, and
+ * the same stream copies the chain's records and counters out into records[c] (n_reads entries) and counters[c]
+ * (DCRX_N_COUNTERS uint64, OVERWRITTEN).  An input staging set is refilled only once every chain's scan of it is over.
+ * records[c] and counters[c] equal what dcrx_decombine(tables[c], ...) gives on the same batch, byte for byte.
+ * Pinned caller buffers skip the staging copies as in dcrx_decombine; the tuple sink is off for the call on every
+ * handle.  DCRX_E_INVALID for n_chains of 0 or above DCRX_MAX_CHAINS, a null pointer, or the same handle twice (the
+ * chains would share one workspace).  Synchronous; on an error every stream has drained before this returns. */
+#define DCRX_MAX_CHAINS 4
+int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                          const dcrx_batch_t *host_batch, dcrx_record_t *const *records, uint64_t *const *counters);
+
 /* Device buffers in, device buffers out, asynchronous on `hip_stream`
  * (a hipStream_t, NULL = default stream).  Every pointer inside `device_batch`,
  * d_records and d_counters (DCRX_N_COUNTERS uint64, overwritten) are device
@@ -255,7 +268,8 @@ int dcrx_decombine(dcrx_tables_t *tables, const dcrx_cfg_t *cfg, const dcrx_batc
  * stream may be captured or run arbitrarily far ahead of the host.
  * Calls on one handle are ordered on one stream (the workspace hangs off the handle); batches that should overlap —
  * a batch's finishing launch beside the next batch's scan, or the two chains of a two-chain library — take one handle
- * and one stream each ("Ownership, errors, threading"). */
+ * and one stream each ("Ownership, errors, threading"); dcrx_decombine_chains does that for host
+ * buffers, uploading the batch once for all chains. */
 int dcrx_decombine_device(dcrx_tables_t *tables, const dcrx_cfg_t *cfg,
                           const dcrx_batch_t *device_batch, dcrx_record_t *d_records,
                           uint64_t *d_counters, void *hip_stream);
