@@ -398,6 +398,8 @@ EXPORTS = [
     "dcrx_comm_allreduce_u64", "dcrx_comm_allreduce_f64", "dcrx_comm_allgather", "dcrx_comm_gather_v", "dcrx_comm_barrier", "dcrx_comm_allgather_host",
     "dcrx_comm_allreduce_host_u64", "dcrx_decombine_sharded", "dcrx_event_synchronize", "dcrx_event_create_ordering", "dcrx_stream_create", "dcrx_stream_destroy", "dcrx_stream_synchronize",
     "dcrx_stream_wait_event", "dcrx_memcpy_d2h_async", "dcrx_memcpy_d2d_async", "dcrx_memset_device_async",
+    "dcrx_counts_create", "dcrx_counts_destroy", "dcrx_counts_reset", "dcrx_counts_set_hash_bits", "dcrx_count_device", "dcrx_decombine_count",
+    "dcrx_decombine_chains_count", "dcrx_counts_read", "dcrx_format_counts",
 ]
 
 _lib = None
@@ -509,6 +511,15 @@ def lib():
         "dcrx_memcpy_d2h_async": (i32, [vp, vp, C.c_size_t, vp]),
         "dcrx_memcpy_d2d_async": (i32, [vp, vp, C.c_size_t, vp]),
         "dcrx_memset_device_async": (i32, [vp, i32, C.c_size_t, vp]),
+        "dcrx_counts_create": (i32, [C.POINTER(vp)]),
+        "dcrx_counts_destroy": (None, [vp]),
+        "dcrx_counts_reset": (i32, [vp]),
+        "dcrx_counts_set_hash_bits": (i32, [vp, u32]),
+        "dcrx_count_device": (i32, [vp, vp, C.POINTER(BatchC), u64, vp, vp]),
+        "dcrx_decombine_count": (i32, [vp, C.POINTER(CfgC), C.POINTER(BatchC), vp, u64, vp, vp]),
+        "dcrx_decombine_chains_count": (i32, [vp, u32, C.POINTER(CfgC), C.POINTER(BatchC), vp, u64, vp, vp]),
+        "dcrx_counts_read": (C.c_int64, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]),
+        "dcrx_format_counts": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -978,6 +989,143 @@ def decombine_chains(tables_list, batch: PackedBatch, orientation="reverse", all
         if int(cnt[DEVICE_ERRORS]):
             raise RuntimeError(f"dcrx_decombine_chains: {int(cnt[DEVICE_ERRORS])} device-side wait(s) timed out; the records of this call are incomplete")
     return list(zip(recs, cnts))
+
+
+class DcrCounts:
+    """Opaque dcrx_counts_t: the distinct DCRs (v, j, vdel, jdel, insert) of the barcode-free stage with their read counts,
+    in a table on the device that grows across calls (replaces the reference's `Counter` over dcr() results,
+    decombine.py:1041-1060)."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        self._h = None
+        check(lib().dcrx_counts_create(C.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def reset(self):
+        check(lib().dcrx_counts_reset(self._h))
+
+    def set_hash_bits(self, bits: int):
+        """dcrx_counts_set_hash_bits (tests): keys keep `bits` hash bits, so that distinct DCRs collide; same results."""
+        check(lib().dcrx_counts_set_hash_bits(self._h, int(bits)))
+
+    def read(self) -> dict:
+        """dcrx_counts_read: the distinct DCRs in Counter.most_common() order — arrays v, j, vdel, jdel, count, first (the
+        first read's ordinal), ins_off (n + 1) and the inserts' text `ins_text` (bytes)."""
+        tb = C.c_uint64(0)
+        n = check(int(lib().dcrx_counts_read(self._h, None, None, None, None, None, None, None, None, 0, 0, C.byref(tb))))
+        out = {"v": np.zeros(n, np.uint16), "j": np.zeros(n, np.uint16), "vdel": np.zeros(n, np.uint8),
+               "jdel": np.zeros(n, np.uint8), "count": np.zeros(n, np.uint64), "first": np.zeros(n, np.uint64),
+               "ins_off": np.zeros(n + 1, np.uint64)}
+        text = np.zeros(max(1, int(tb.value)), np.uint8)
+        got = check(int(lib().dcrx_counts_read(self._h, *[out[k].ctypes.data for k in ("v", "j", "vdel", "jdel", "count", "first", "ins_off")],
+                                                text.ctypes.data, n, len(text), C.byref(tb))))
+        if got != n:
+            raise DcrxError(-1, "dcrx_counts_read: the number of distinct DCRs changed between two calls")
+        out["ins_text"] = text[:int(tb.value)].tobytes()
+        return out
+
+    def close(self):
+        if self._h is not None:
+            lib().dcrx_counts_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def count_rows(counted: dict) -> list:
+    """The six-field rows [v, j, vdel, jdel, insert, count] of what DcrCounts.read() gives (the first five as the `.n12` row
+    holds them, text; the count an int)."""
+    text, off = counted["ins_text"], counted["ins_off"]
+    return [[str(int(counted["v"][k])), str(int(counted["j"][k])), str(int(counted["vdel"][k])), str(int(counted["jdel"][k])),
+             text[int(off[k]):int(off[k + 1])].decode("latin-1"), int(counted["count"][k])] for k in range(len(counted["v"]))]
+
+
+COUNTS_LINE_BOUND = 54      # DCRX_COUNTS_LINE_BOUND
+
+
+def format_counts(counted: dict, field_sep: str = ", ") -> bytes:
+    """dcrx_format_counts: the `.nbc` text of what DcrCounts.read() gives, one "v, j, vdel, jdel, insert, count" line per DCR."""
+    n = len(counted["v"])
+    arrs = [np.ascontiguousarray(counted[k]) for k in ("v", "j", "vdel", "jdel", "count", "ins_off")]
+    text = np.frombuffer(counted["ins_text"], np.uint8) if counted["ins_text"] else np.zeros(1, np.uint8)
+    sep = field_sep.encode("latin-1")
+    args = [n] + [a.ctypes.data for a in arrs] + [text.ctypes.data, sep]
+    # a buffer that always fits (DCRX_COUNTS_LINE_BOUND): the library writes it in one pass
+    bound = n * (COUNTS_LINE_BOUND + 5 * len(sep)) + len(counted["ins_text"])
+    out = _uninitialised_bytes(max(1, bound))
+    got = check(int(lib().dcrx_format_counts(*args, _bytes_address(out), max(1, bound))))
+    if got > bound:
+        raise DcrxError(-1, f"dcrx_format_counts needs {got} bytes, more than the {bound} bound")
+    return out[:got]
+
+
+def _index_arg(index, n):
+    if index is None:
+        return None, None
+    idx = np.ascontiguousarray(index, dtype=np.uint32)
+    if idx.shape != (n,):
+        raise ValueError("index: one uint32 entry per read of the batch")
+    return idx, idx.ctypes.data
+
+
+def decombine_count(tables: Tables, batch: PackedBatch, counts: DcrCounts, first_index: int = 0, index=None,
+                    orientation="reverse", allow_ns=False, lenthreshold=130, flags=0) -> np.ndarray:
+    """dcrx_decombine_count: the batch decombined and its DCRs added into `counts`, read r as ordinal first_index + r (or
+    first_index + index[r]).  Returns the counters (uint64[32]); no records come back."""
+    cfg = make_cfg(orientation, allow_ns, lenthreshold, flags)
+    cnt = np.zeros(N_COUNTERS, dtype=np.uint64)
+    idx, idx_ptr = _index_arg(index, batch.n_reads)
+    b = batch.as_c()
+    check(lib().dcrx_decombine_count(tables.handle, C.byref(cfg), C.byref(b), counts.handle, int(first_index), idx_ptr,
+                                     cnt.ctypes.data))
+    return cnt
+
+
+def decombine_chains_count(tables_list, batch: PackedBatch, counts_list, first_index: int = 0, index=None,
+                           orientation="reverse", allow_ns=False, lenthreshold=130, flags=0) -> list:
+    """dcrx_decombine_chains_count: one upload of the batch, chain c's DCRs added into counts_list[c].  Returns the counters
+    per chain; each equals what decombine_count() gives for that chain alone."""
+    tables_list, counts_list = list(tables_list), list(counts_list)
+    if len(tables_list) != len(counts_list):
+        raise ValueError("one DcrCounts per chain")
+    cfg = make_cfg(orientation, allow_ns, lenthreshold, flags)
+    k = max(1, len(tables_list))
+    cnts = [np.zeros(N_COUNTERS, dtype=np.uint64) for _ in tables_list]
+    handles = (C.c_void_p * k)(*[t.handle for t in tables_list])
+    counts_h = (C.c_void_p * k)(*[c.handle for c in counts_list])
+    cnt_ptrs = (C.c_void_p * k)(*[c.ctypes.data for c in cnts])
+    idx, idx_ptr = _index_arg(index, batch.n_reads)
+    b = batch.as_c()
+    check(lib().dcrx_decombine_chains_count(handles, len(tables_list), C.byref(cfg), C.byref(b), counts_h, int(first_index),
+                                            idx_ptr, cnt_ptrs))
+    return cnts
+
+
+def count_dcrs(tables_list, batch: PackedBatch, counts_list, first_index: int = 0, index=None, orientation="reverse",
+               allow_ns=False, lenthreshold=130) -> list:
+    """The barcode-free stage's one call per batch: decombine the batch for every chain and add its DCRs into that chain's
+    DcrCounts (dcrx_decombine_count for one chain, dcrx_decombine_chains_count — one upload — for several).  Returns the
+    counters per chain."""
+    if len(tables_list) == 1:
+        return [decombine_count(tables_list[0], batch, counts_list[0], first_index, index, orientation, allow_ns, lenthreshold)]
+    return decombine_chains_count(tables_list, batch, counts_list, first_index, index, orientation, allow_ns, lenthreshold)
+
+
+def count_device(counts: DcrCounts, d_records: "DeviceBuffer", batch: "DeviceBatch", first_index: int = 0,
+                 d_index: "DeviceBuffer | None" = None, stream=None):
+    """dcrx_count_device: the count step over records already in HBM, asynchronous on `stream`."""
+    b = batch.as_c()
+    check(lib().dcrx_count_device(counts.handle, d_records.ptr, C.byref(b), int(first_index),
+                                  d_index.ptr if d_index is not None else None, stream))
 
 
 def synth_cfg(seed: int, read_len: int = 150, p_rearranged: float = 0.45, sub_rate: float = 0.005,

@@ -25,6 +25,10 @@
 namespace dcrx {
 hipError_t launch_synth(const DevTables &T, const SynthParams &P, uint64_t first, uint64_t n, uint32_t stride,
                         uint8_t *d_packed, hipStream_t s);
+// dcrx_count.hip: the host entries' count step over one chunk, and the figures a count settles once its stream is drained
+int count_chunk(dcrx_counts_t *c, const dcrx_record_t *d_records, const dcrx_batch_t *d_batch, uint64_t first_index,
+                const uint32_t *h_index, hipStream_t s);
+int count_settle(dcrx_counts_t *c, hipStream_t s);
 }
 
 using namespace dcrx;
@@ -484,17 +488,19 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   return DCRX_OK;
 }
 
-static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters);
+// (counts: the count entry's table — the chunks' records stay on the device and feed it, only the counters come back)
+static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters,
+                          dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index);
 
 // The host-buffer entry.  Whatever goes wrong inside the chunk pipeline — a HIP error, no memory, a helper thread that cannot
 // be started — comes back as a code, and only after the three streams have drained: their asynchronous copies may target the
 // caller's own (pinned) `packed` and `records` buffers, which the caller is free to release once this returns.
-int dcrx_decombine(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records,
-                   uint64_t *counters) {
+static int decombine_entry(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records,
+                           uint64_t *counters, dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index) {
   int rc;
   const bool sink_was_on = t && t->sink_on;      // (the tuple sink concerns the device entry: a chunked host call has no one message)
   if (t) t->sink_on = false;
-  try { rc = decombine_host(t, cfg, hb, records, counters); }
+  try { rc = decombine_host(t, cfg, hb, records, counters, counts, first_index, index); }
   catch (const std::bad_alloc &) { rc = set_err(DCRX_E_NOMEM, "out of host memory in dcrx_decombine"); }
   catch (const std::exception &e) { rc = set_err(DCRX_E_NOMEM, std::string("dcrx_decombine: ") + e.what()); }
   catch (...) { rc = set_err(DCRX_E_NOMEM, "dcrx_decombine: unexpected exception"); }
@@ -509,23 +515,42 @@ int dcrx_decombine(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *
   return rc;
 }
 
+int dcrx_decombine(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records,
+                   uint64_t *counters) {
+  return decombine_entry(t, cfg, hb, records, counters, nullptr, 0, nullptr);
+}
+
+int dcrx_decombine_count(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_counts_t *counts,
+                         uint64_t first_index, const uint32_t *index, uint64_t *counters) {
+  if (!counts) return set_err(DCRX_E_INVALID, "counts is null");
+  return decombine_entry(t, cfg, hb, nullptr, counters, counts, first_index, index);
+}
+
 static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
-                                 dcrx_record_t *const *records, uint64_t *const *counters);
+                                 dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
+                                 uint64_t first_index, const uint32_t *index);
 
 // The multi-chain host-buffer entry: the same epilogue as dcrx_decombine, over every stream the call used.
-int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
-                          const dcrx_batch_t *hb, dcrx_record_t *const *records, uint64_t *const *counters) {
-  if (!tables || !cfg || !records || !counters) return set_err(DCRX_E_INVALID, "null argument");
+static int decombine_chains_entry(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
+                                  dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
+                                  uint64_t first_index, const uint32_t *index) {
+  if (!tables || !cfg || (!records && !counts) || !counters) return set_err(DCRX_E_INVALID, "null argument");
   if (n_chains == 0 || n_chains > DCRX_MAX_CHAINS) return set_err(DCRX_E_INVALID, "n_chains must be 1 .. DCRX_MAX_CHAINS");
   for (uint32_t c = 0; c < n_chains; c++) {
     if (!tables[c]) return set_err(DCRX_E_INVALID, "tables[c] is null");
     for (uint32_t e = 0; e < c; e++)
       if (tables[e] == tables[c]) return set_err(DCRX_E_INVALID, "the same tables handle twice: every chain needs a handle (and a workspace) of its own");
   }
+  if (counts)
+    for (uint32_t c = 0; c < n_chains; c++) {
+      if (!counts[c]) return set_err(DCRX_E_INVALID, "counts[c] is null");
+      for (uint32_t e = 0; e < c; e++)
+        if (counts[e] == counts[c]) return set_err(DCRX_E_INVALID, "the same counts handle twice: every chain needs a table of its own");
+    }
   bool sink_was_on[DCRX_MAX_CHAINS];
   for (uint32_t c = 0; c < n_chains; c++) { sink_was_on[c] = tables[c]->sink_on; tables[c]->sink_on = false; }
   int rc;
-  try { rc = decombine_chains_host(tables, n_chains, cfg, hb, records, counters); }
+  try { rc = decombine_chains_host(tables, n_chains, cfg, hb, records, counters, counts, first_index, index); }
   catch (const std::bad_alloc &) { rc = set_err(DCRX_E_NOMEM, "out of host memory in dcrx_decombine_chains"); }
   catch (const std::exception &e) { rc = set_err(DCRX_E_NOMEM, std::string("dcrx_decombine_chains: ") + e.what()); }
   catch (...) { rc = set_err(DCRX_E_NOMEM, "dcrx_decombine_chains: unexpected exception"); }
@@ -543,6 +568,19 @@ int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const
   }
   for (uint32_t c = 0; c < n_chains; c++) tables[c]->sink_on = sink_was_on[c];
   return rc;
+}
+
+int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                          const dcrx_batch_t *hb, dcrx_record_t *const *records, uint64_t *const *counters) {
+  if (!records) return set_err(DCRX_E_INVALID, "null argument");
+  return decombine_chains_entry(tables, n_chains, cfg, hb, records, counters, nullptr, 0, nullptr);
+}
+
+int dcrx_decombine_chains_count(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                                const dcrx_batch_t *hb, dcrx_counts_t *const *counts, uint64_t first_index,
+                                const uint32_t *index, uint64_t *const *counters) {
+  if (!counts) return set_err(DCRX_E_INVALID, "null argument");
+  return decombine_chains_entry(tables, n_chains, cfg, hb, nullptr, counters, counts, first_index, index);
 }
 
 }  // extern "C"
@@ -637,12 +675,13 @@ static bool host_pinned(const void *p) {
   return a.type == hipMemoryTypeHost;
 }
 
-static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters) {
+static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters,
+                          dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index) {
   if (!t || !cfg || !counters) return set_err(DCRX_E_INVALID, "null argument");
   int rc = check_batch(hb);
   if (rc) return rc;
   const uint64_t n = hb->n_reads;
-  if (n && !records) return set_err(DCRX_E_INVALID, "records is null");
+  if (n && !records && !counts) return set_err(DCRX_E_INVALID, "records is null");
   rc = check_host_batch(hb);
   if (rc) return rc;
   // The batch goes through in chunks of DCRX_HOST_CHUNK reads, three streams deep: while the kernels of chunk k run, chunk
@@ -664,7 +703,7 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   if (rc) return rc;
   for (int c = 0; c < DCRX_N_COUNTERS; c++) counters[c] = 0;
   const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
-  const bool out_direct = n && host_pinned(records) && host_pinned(reinterpret_cast<const uint8_t *>(records + n) - 1);
+  const bool out_direct = n && !counts && host_pinned(records) && host_pinned(reinterpret_cast<const uint8_t *>(records + n) - 1);
   const uint64_t n_chunks = n ? (n + chunk - 1) / chunk : 1;
   uint64_t exc_at = 0;
   auto drain = [&](uint64_t k) -> int {       // chunk k's records and counters: from the pinned buffer to the caller's
@@ -672,7 +711,7 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
     HIP_TRY(hipEventSynchronize(t->hev_out[set]));
     const uint8_t *h = t->h_stage + (size_t)set * set_bytes;
     const uint64_t c0 = k * chunk, cn = std::min<uint64_t>(chunk, n - c0);
-    if (cn && !out_direct) par_memcpy(records + c0, h + o_rec, cn * sizeof(dcrx_record_t));
+    if (cn && !out_direct && !counts) par_memcpy(records + c0, h + o_rec, cn * sizeof(dcrx_record_t));
     const uint64_t *hc = reinterpret_cast<const uint64_t *>(h + o_cnt);
     for (int c = 0; c < DCRX_N_COUNTERS; c++) counters[c] += hc[c];
     return DCRX_OK;
@@ -721,10 +760,15 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
     db.exc_chr = d + o_ec;
     rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(d + o_rec), reinterpret_cast<uint64_t *>(d + o_cnt), t->hs_run);
     if (rc) return rc;          // (the caller of this function drains the streams)
+    if (counts && cn) {         // the count step reads the chunk's records and its packed reads: before the set is refilled
+      rc = count_chunk(counts, reinterpret_cast<const dcrx_record_t *>(d + o_rec), &db, index ? first_index : first_index + c0,
+                       index ? index + c0 : nullptr, t->hs_run);
+      if (rc) return rc;
+    }
     HIP_TRY(hipEventRecord(t->hev_run[set], t->hs_run));
     HIP_TRY(hipStreamWaitEvent(t->hs_out, t->hev_run[set], 0));
-    if (out_direct) {
-      if (cn) HIP_TRY(hipMemcpyAsync(records + c0, d + o_rec, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_out));
+    if (out_direct || counts) {
+      if (cn && !counts) HIP_TRY(hipMemcpyAsync(records + c0, d + o_rec, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_out));
       HIP_TRY(hipMemcpyAsync(h + o_cnt, d + o_cnt, set_bytes - o_cnt, hipMemcpyDeviceToHost, t->hs_out));
     } else {
       HIP_TRY(hipMemcpyAsync(h + o_rec, d + o_rec, set_bytes - o_rec, hipMemcpyDeviceToHost, t->hs_out));
@@ -735,6 +779,7 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   // (include/dcrx_codes.h: a wave that gave up waiting for another says so in the call's counters — the records would not be
   // complete, and this entry, which has the counters in hand, does not return them as if they were)
   if (counters[DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
+  if (counts) return count_settle(counts, t->hs_run);
   return DCRX_OK;
 }
 
@@ -742,13 +787,14 @@ static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
 // live in the first handle's staging, in front of its output sets; every other handle's staging holds only its output sets.
 // Streams: tables[0]'s copy-in stream, and per chain its run stream, which carries the chain's launches and its copy out.
 static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
-                                 dcrx_record_t *const *records, uint64_t *const *counters) {
+                                 dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
+                                 uint64_t first_index, const uint32_t *index) {
   int rc = check_batch(hb);
   if (rc) return rc;
   const uint64_t n = hb->n_reads;
   for (uint32_t c = 0; c < nc; c++) {
     if (!counters[c]) return set_err(DCRX_E_INVALID, "counters[c] is null");
-    if (n && !records[c]) return set_err(DCRX_E_INVALID, "records[c] is null");
+    if (n && !counts && !records[c]) return set_err(DCRX_E_INVALID, "records[c] is null");
   }
   rc = check_host_batch(hb);
   if (rc) return rc;
@@ -770,7 +816,7 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
   const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
   bool out_direct[DCRX_MAX_CHAINS];
   for (uint32_t c = 0; c < nc; c++)
-    out_direct[c] = n && host_pinned(records[c]) && host_pinned(reinterpret_cast<const uint8_t *>(records[c] + n) - 1);
+    out_direct[c] = n && !counts && host_pinned(records[c]) && host_pinned(reinterpret_cast<const uint8_t *>(records[c] + n) - 1);
   const uint64_t n_chunks = n ? (n + chunk - 1) / chunk : 1;
   uint64_t exc_at = 0;
   auto drain = [&](uint64_t k) -> int {       // chunk k's records and counters of every chain: pinned buffers to the caller's
@@ -779,7 +825,7 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
     for (uint32_t c = 0; c < nc; c++) {
       HIP_TRY(hipEventSynchronize(T[c]->hev_out[set]));
       const uint8_t *h = T[c]->h_stage + out_at(c, set);
-      if (cn && !out_direct[c]) par_memcpy(records[c] + c0, h, cn * sizeof(dcrx_record_t));
+      if (cn && !out_direct[c] && !counts) par_memcpy(records[c] + c0, h, cn * sizeof(dcrx_record_t));
       const uint64_t *hc = reinterpret_cast<const uint64_t *>(h + Lay.o_cnt);
       for (int i = 0; i < DCRX_N_COUNTERS; i++) counters[c][i] += hc[i];
     }
@@ -832,9 +878,14 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
       HIP_TRY(hipStreamWaitEvent(t->hs_run, T[0]->hev_in[set], 0));
       rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(od), reinterpret_cast<uint64_t *>(od + Lay.o_cnt), t->hs_run);
       if (rc) return rc;          // (dcrx_decombine_chains drains the streams)
+      if (counts && cn) {         // the count step reads the packed chunk too: it is among what the next refill of the set waits for
+        rc = count_chunk(counts[c], reinterpret_cast<const dcrx_record_t *>(od), &db, index ? first_index : first_index + c0,
+                         index ? index + c0 : nullptr, t->hs_run);
+        if (rc) return rc;
+      }
       HIP_TRY(hipEventRecord(t->hev_run[set], t->hs_run));
-      if (out_direct[c]) {
-        if (cn) HIP_TRY(hipMemcpyAsync(records[c] + c0, od, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_run));
+      if (out_direct[c] || counts) {
+        if (cn && !counts) HIP_TRY(hipMemcpyAsync(records[c] + c0, od, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_run));
         HIP_TRY(hipMemcpyAsync(oh + Lay.o_cnt, od + Lay.o_cnt, Lay.out_bytes - Lay.o_cnt, hipMemcpyDeviceToHost, t->hs_run));
       } else {
         HIP_TRY(hipMemcpyAsync(oh, od, Lay.out_bytes, hipMemcpyDeviceToHost, t->hs_run));
@@ -845,6 +896,8 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
   for (uint64_t k = n_chunks >= 2 ? n_chunks - 2 : 0; k < n_chunks; k++) { rc = drain(k); if (rc) return rc; }
   for (uint32_t c = 0; c < nc; c++)
     if (counters[c][DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
+  if (counts)
+    for (uint32_t c = 0; c < nc; c++) { rc = count_settle(counts[c], T[c]->hs_run); if (rc) return rc; }
   return DCRX_OK;
 }
 

@@ -641,11 +641,20 @@ def _chain_setup(inputargs: dict, rank: int) -> dict:
                 counts=counts, args=inputargs)
 
 
+def _count_fasta(inputargs: dict, opener) -> bool:
+    """A FASTA input of the barcode-free count (count_dcrs): its records are reads as they are, so the FASTQ check does not
+    apply to it."""
+    if not inputargs.get("count_dcrs"):
+        return False
+    with opener(inputargs["infile"], "rt") as fh:
+        return fh.read(1) == ">"
+
+
 def _input_checks(inputargs: dict, rank: int, chains: list) -> None:
     """The FASTQ check (once, whatever the number of chains: an input with fewer than four lines leaves every chain's
     two-line log) and the orientation / barcode-read arguments."""
     opener = opener_check(inputargs)
-    if inputargs["dontcheck"] == False and rank == 0:  # noqa: E712
+    if inputargs["dontcheck"] == False and rank == 0 and not _count_fasta(inputargs, opener):  # noqa: E712
         # (the reference crashes here with suppresssummary=True, SURVEY.md A.7 #14; this build checks anyway)
         ch = chains[0]
         try:
@@ -783,6 +792,11 @@ def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan
             if rd2 is not None:
                 rd2.close()
             stage_seconds["close"] = time() - tc
+    elif inputargs.get("count_dcrs"):
+        if inputargs["extension"] == "n12":
+            print("Non-barcoding option selected, but default output file extension (n12) detected. "
+                  "Automatically changing to 'nbc'.")
+        outdatas = _count_loop(inputargs, chains, cnts, max_read_len)
     else:
         # reference behaviour: with nobarcoding the read loop never runs
         if inputargs["extension"] == "n12":
@@ -792,6 +806,121 @@ def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan
     for ch, od in zip(chains, outdatas):
         ch["outdata"] = od
     state.update(outdata=outdatas[0])
+
+
+class NbcRows(coll.abc.Sequence):
+    """What decombinator() returns with count_dcrs: the distinct DCRs as six-field rows [v, j, vdel, jdel, insert, count]
+    in collections.Counter.most_common() order over the reads in file order.  Kept as the arrays DcrCounts.read() gave
+    (`counted`) and turned into lists only when somebody asks; write_out_intermediate() writes the `.nbc` text that libdcrx
+    formats from the arrays."""
+
+    def __init__(self, counted: dict):
+        self.counted = counted
+        self._lists = None
+
+    def _all(self):
+        if self._lists is None:
+            self._lists = nat.count_rows(self.counted)
+        return self._lists
+
+    def __len__(self):
+        return len(self.counted["v"])
+
+    def __getitem__(self, k):
+        return self._all()[k]
+
+    def __iter__(self):
+        return iter(self._all())
+
+    def __eq__(self, other):
+        if isinstance(other, (list, NbcRows)):
+            return len(self) == len(other) and all(a == b for a, b in zip(self, other))
+        return NotImplemented
+
+    def __repr__(self):
+        return f"NbcRows({len(self)} DCRs)"
+
+    def write_text(self, fh, joiner: str = ", ") -> None:
+        fh.flush()
+        fh.buffer.write(nat.format_counts(self.counted, joiner))
+
+
+def check_count_args(inputargs: dict) -> None:
+    """count_dcrs (--count-dcrs) is the barcode-free stage's DCR count: refused, before anything is read, without
+    nobarcoding (-nbc), with cluster (--cluster: UMIs are what it clusters) and with sampling_analysis (-sa: the V tail comes
+    from the barcode read)."""
+    if not inputargs.get("count_dcrs"):
+        return
+    if not inputargs.get("nobarcoding"):
+        raise ValueError("--count-dcrs counts the DCRs of a barcode-free run: it needs -nbc (--nobarcoding)")
+    if inputargs.get("cluster"):
+        raise ValueError("--count-dcrs and --cluster exclude each other: without barcodes there are no UMIs to cluster")
+    if inputargs.get("sampling_analysis"):
+        raise ValueError("--count-dcrs and -sa exclude each other: the V tail of -sa comes from the barcode read")
+
+
+def _count_loop(inputargs: dict, chains: list, cnts: list, max_read_len: int) -> list:
+    """The barcode-free read loop (count_dcrs): every record of the one input file is a read, whole (no barcode is cut, no
+    second file is opened, FASTA records are reads too).  Each batch is packed and handed to the device once for all chains
+    (nat.count_dcrs): the records stay there and feed each chain's DcrCounts, only the counters come back.  Read ordinals
+    are the records' places in the file.  Returns an NbcRows per chain."""
+    tables = [ch["tcr"].tables for ch in chains]
+    dcs = [nat.DcrCounts() for _ in chains]
+    args = (inputargs["orientation"], inputargs["allowNs"], inputargs["lenthreshold"])
+    stage_info.clear()
+    stage_info.update(sharded_input=False, byte_ranges=None, rank=0, world=1)
+    rd = nat.FastqReader(inputargs["infile"], inputargs["infile"].endswith(".gz"))
+    ordinal = 0
+    try:
+        while True:
+            t0 = time()
+            b = rd.next(BATCH_READS, copy=False)
+            n = b.n
+            if n == 0:
+                break
+            before = cnts[0]["read_count"]
+            for c in cnts:
+                c["read_count"] += n
+            if inputargs["dontcount"] == False and cnts[0]["read_count"] // 100000 > before // 100000:  # noqa: E712
+                print("\t read", (cnts[0]["read_count"] // 100000) * 100000)
+            longest = int(b.seq_len.max())
+            if longest > max_read_len:
+                raise ValueError(f"a read of {longest} nt exceeds the {max_read_len} nt this build decombines "
+                                 f"(dcrx_tables_info.max_read_len); trim or split the reads")
+            t1 = time()
+            tp = 0.0
+            if longest > nat.FAST_MAX_READ_LEN:
+                # (as in the barcoded loop: reads over 511 nt in a call of their own, each read keeping its ordinal)
+                is_long = b.seq_len > nat.FAST_MAX_READ_LEN
+                res = [np.zeros(nat.N_COUNTERS, dtype=np.uint64) for _ in chains]
+                for idx in (np.nonzero(~is_long)[0], np.nonzero(is_long)[0]):
+                    if len(idx) == 0:
+                        continue
+                    ta = time()
+                    batch = nat.pack_reads_span(b.text, b.seq_off[idx], b.seq_len[idx])
+                    tp += time() - ta
+                    for acc, part in zip(res, nat.count_dcrs(tables, batch, dcs, ordinal, idx.astype(np.uint32), *args)):
+                        acc += part.astype(np.uint64)
+            else:
+                batch = nat.pack_reads_span(b.text, b.seq_off, b.seq_len)
+                tp = time() - t1
+                res = nat.count_dcrs(tables, batch, dcs, ordinal, None, *args)
+            t3 = time()
+            for ch, cnt in zip(chains, res):
+                _add_counts(cnt, skip=("read_count",), into=ch["counts"])
+            ordinal += n
+            for key, dt in (("read", t1 - t0), ("pack", tp), ("device", t3 - t1 - tp)):
+                stage_seconds[key] = stage_seconds.get(key, 0.0) + dt
+    finally:
+        tc = time()
+        rd.close()
+        stage_seconds["close"] = time() - tc
+    tr = time()
+    out = [NbcRows(dc.read()) for dc in dcs]
+    for dc in dcs:
+        dc.close()
+    stage_seconds["rows"] = time() - tr
+    return out
 
 
 def decombinator(inputargs: dict, shard=None, reduce_counts=None, exchange_error=None, plan_shards=None) -> list:
@@ -808,6 +937,9 @@ def decombinator(inputargs: dict, shard=None, reduce_counts=None, exchange_error
     rank's part raised: it must raise on every rank when any rank failed (a rank that died alone would leave the
     others waiting in reduce_counts for ever).  decombinator_amd.sharded.decombinator_sharded drives this."""
     rank, world = shard if shard is not None else (0, 1)
+    if inputargs.get("count_dcrs") and shard is not None:
+        raise ValueError("--count-dcrs has no sharded (multi-GPU) form: run it on one GPU")
+    check_count_args(inputargs)
     state = {}
     for part in (_decombinator_setup, _decombinator_loop):
         err = None
@@ -854,6 +986,7 @@ def decombinator_chains(inputargs: dict) -> dict:
     if items is None:
         raise ValueError("decombinator_chains needs a comma-separated list of chains in inputargs['chain'] (e.g. 'a,b')")
     resolve_chain_list(items)           # (refused before anything is read: an unknown item, a chain named twice)
+    check_count_args(inputargs)
     global counts
     print("Running Decombinator (MI355X / HIP build) version", __version__)
     chain_counts.clear()

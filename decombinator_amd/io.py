@@ -27,10 +27,11 @@ def create_args_dict(
     barcodeduplication: bool = False, positionalbarcodes: bool = False, oligo: str = "M13",
     writeclusters: bool = False, UMIhistogram: bool = False, nonproductivefilter: bool = False,
     outpath: str = None, dontsave: bool = False, command: str = None, sampling_analysis: bool = False,
-    cluster: bool = False,
+    cluster: bool = False, count_dcrs: bool = False,
 ) -> dict:
-    """The function-argument dictionary threaded through the stages (the reference's 33 keys, and `cluster`: run the
-    grouping / clustering half of collapse, writing the `.freq`)."""
+    """The function-argument dictionary threaded through the stages (the reference's 33 keys, `cluster`: run the
+    grouping / clustering half of collapse, writing the `.freq`, and `count_dcrs`: with nobarcoding, count the DCRs on the
+    GPU and write the `.nbc`)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -40,7 +41,8 @@ def create_args_dict(
         dontcheckinput=dontcheckinput, barcodeduplication=barcodeduplication,
         positionalbarcodes=positionalbarcodes, oligo=oligo, writeclusters=writeclusters,
         UMIhistogram=UMIhistogram, nonproductivefilter=nonproductivefilter, outpath=outpath,
-        dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster)
+        dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster,
+        count_dcrs=count_dcrs)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -94,6 +96,12 @@ def _cluster_flag(p: argparse.ArgumentParser):
                         "write the .freq (and the Collapsing_Summary.csv); without it only the per-row front half runs")
 
 
+def _count_flag(p: argparse.ArgumentParser):
+    p.add_argument("--count-dcrs", dest="count_dcrs", action="store_true",
+                   help="With -nbc: count the distinct DCRs of a barcode-free run on the GPU and write them with their read "
+                        "counts (.nbc: v, j, vdel, jdel, insert, count); translate reads such a file")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -105,12 +113,12 @@ def create_parser() -> argparse.ArgumentParser:
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
                                            "translate (.n12, .freq, .tsv)")
-    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe)
+    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe); _count_flag(pipe)
     dec = sub.add_parser("decombine", help="Decombine TCR reads")
-    _common(dec); _decombine(dec)
+    _common(dec); _decombine(dec); _count_flag(dec)
     col = sub.add_parser("collapse", help="front half of collapse over an .n12 file: barcode extraction and the row filters "
                                           "(writes .n12u); with --cluster the whole stage (writes .freq)")
-    _common(col); _later_stage_flags(col); _cluster_flag(col)
+    _common(col); _later_stage_flags(col); _cluster_flag(col); _count_flag(col)
     col.add_argument("-in", "--infile", type=str, required=True, help=".n12 file of the decombine stage (optionally gzipped)")
     col.add_argument("-N", "--allowNs", action="store_true", help="Allow barcodes containing N")
     col.add_argument("-ln", "--lenthreshold", type=int, default=130, help="Inter-tag length threshold")
@@ -121,6 +129,7 @@ def create_parser() -> argparse.ArgumentParser:
     tr.add_argument("-sp", "--species", type=str, default="human")
     tr.add_argument("-tfdir", "--tagfastadir", type=str, default="Decombinator-Tags-FASTAs")
     tr.add_argument("-nbc", "--nobarcoding", action="store_true")
+    _count_flag(tr)
     return parser
 
 
@@ -186,6 +195,12 @@ def write_out_intermediate(data: list, inputargs: dict, suffix: str):
                     outfile.write(", ".join(map(str, line)) + "\n")
     sort_permissions(outfilename)
     return outfilename
+
+
+def nbc_suffix(inputargs: dict) -> str:
+    """The suffix of the barcode-free count's file: `.nbc` while the extension is the default n12 (the reference's own
+    message, decombine.py:1054-1057), `.<extension>` otherwise."""
+    return ".nbc" if inputargs["extension"] == "n12" else "." + inputargs["extension"]
 
 
 def write_out_translated(rows, headers, inputargs: dict):

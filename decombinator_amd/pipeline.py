@@ -14,7 +14,7 @@ from typing import Any, Optional
 from . import collapse
 from . import decombine as dec
 from .decombine import decombinator
-from .io import cli_args, write_out_intermediate
+from .io import cli_args, nbc_suffix, write_out_intermediate
 
 
 def collapse_front(data, inp):
@@ -60,6 +60,19 @@ def _files_args(chain: str) -> dict:
 
 
 def _after_decombine(data, inp, start):
+    if inp.get("count_dcrs"):
+        # the barcode-free count (-nbc --count-dcrs): the `.nbc`, then translate; no collapse (there are no UMIs)
+        from . import translate
+        from .io import write_out_translated
+        if not inp["dontsave"]:
+            write_out_intermediate(data, inp, nbc_suffix(inp))
+        print("Decombinator complete...")
+        data = translate.cdr3translator(inp, data=data)
+        print("CDR3translator complete...")
+        if not inp["dontsave"]:
+            write_out_translated(data, translate.out_headers, inp)
+        print(f"Pipeline complete in {datetime.now() - start}")
+        return data
     if not inp["dontsave"]:
         write_out_intermediate(data, inp, ".n12")
     print("Decombinator complete...")
@@ -85,6 +98,18 @@ def _after_decombine(data, inp, start):
 
 def main(argv=None):
     inp = cli_args(argv)
+    if inp.get("count_dcrs"):           # refused before anything is read
+        from .io import create_parser
+        if inp["command"] == "collapse":
+            create_parser().error("--count-dcrs has no collapse step: a barcode-free run has no UMIs to collapse "
+                                  "(decombine or pipeline -nbc --count-dcrs write the counts)")
+        if inp["command"] != "translate":
+            try:
+                dec.check_count_args(inp)
+            except ValueError as e:
+                create_parser().error(str(e))
+        elif not inp.get("nobarcoding"):
+            create_parser().error("--count-dcrs reads the .nbc of a barcode-free run: it needs -nbc (--nobarcoding)")
     if inp["command"] in ("collapse", "translate") and dec.chain_list(inp.get("chain")) is not None:
         from .io import create_parser
         create_parser().error(f"{inp['command']} works on one per-chain file: -c takes one chain there, not a list "
@@ -95,12 +120,13 @@ def main(argv=None):
         except ValueError as e:
             from .io import create_parser
             create_parser().error(str(e))
+    suffix = nbc_suffix(inp) if inp.get("count_dcrs") and inp["command"] == "decombine" else ".n12"
     if inp["command"] == "decombine" and dec.chain_list(inp.get("chain")) is not None:
         for chain, data in dec.decombinator_chains(inp).items():
-            write_out_intermediate(data, _files_args(chain), ".n12")
+            write_out_intermediate(data, _files_args(chain), suffix)
     elif inp["command"] == "decombine":
         data = decombinator(inp)
-        write_out_intermediate(data, inp, ".n12")
+        write_out_intermediate(data, inp, suffix)
     elif inp["command"] == "pipeline":
         run(cli_args=inp)
     elif inp["command"] == "collapse" and inp.get("cluster"):

@@ -507,6 +507,8 @@ def decombinator_sharded(inputargs: dict, comm, device_index: int | None = None)
     from decombinator_amd import _native as nat
     from decombinator_amd import decombine as dec
 
+    if inputargs.get("count_dcrs"):
+        raise ValueError("--count-dcrs has no sharded (multi-GPU) form: run the barcode-free count on one GPU")
     if dec.chain_list(inputargs.get("chain")) is not None:
         raise ValueError(f"-c {inputargs['chain']}: the sharded multi-GPU run resolves one chain; run a list of chains on one "
                          "GPU (decombine.decombinator_chains) or one sharded run per chain")

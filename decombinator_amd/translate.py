@@ -238,7 +238,9 @@ def cdr3translator(inputargs: dict, data=None) -> list:
     """translate.py:388-533 without the file writing: one row of `out_headers` fields per input DCR (non-productive ones too
     unless inputargs["nonproductivefilter"]).  `data`: rows whose first five fields are the DCR, then the frequency and the
     average UMI cluster size (what the reference's collapse returns); with inputargs["command"] == "translate" the rows are
-    read from the comma-separated file inputargs["infile"] (a `.freq`).  inputargs["nobarcoding"]: every row counts once."""
+    read from the comma-separated file inputargs["infile"] (a `.freq`).  inputargs["nobarcoding"]: every row counts once;
+    with inputargs["count_dcrs"] too the rows are those of a `.nbc` (v, j, vdel, jdel, insert, count): the count is the
+    duplicate_count and av_UMI_cluster_size is empty."""
     import gzip
     global counts
     counts = coll.Counter()
@@ -267,12 +269,17 @@ def cdr3translator(inputargs: dict, data=None) -> list:
     pending, meta, stop = [], [], None
     for line in rows:
         counts["line_count"] += 1
-        if inputargs["command"] == "translate":
+        if inputargs["command"] == "translate" and inputargs.get("count_dcrs"):
+            tcr = line.rstrip().split(",")          # a `.nbc` row: v, j, vdel, jdel, insert, count
+            tcr[5] = int(tcr[5])
+        elif inputargs["command"] == "translate":
             tcr = line.rstrip().split(",")
             tcr[5], tcr[6] = int(tcr[5]), int(tcr[6])
         else:
             tcr = line
-        if inputargs.get("nobarcoding"):
+        if inputargs.get("count_dcrs"):
+            frequency, cluster = int(tcr[5]), ""
+        elif inputargs.get("nobarcoding"):
             frequency, cluster = 1, ""
         else:
             if not isinstance(tcr[5], int):

@@ -274,6 +274,68 @@ int dcrx_decombine_device(dcrx_tables_t *tables, const dcrx_cfg_t *cfg,
                           const dcrx_batch_t *device_batch, dcrx_record_t *d_records,
                           uint64_t *d_counters, void *hip_stream);
 
+/* ---- the DCR count of the barcode-free stage (decombine -nbc --count-dcrs): replaces the
+ * reference's `Counter` over dcr() results that its non-barcode branch never filled
+ * (decombine.py:1041-1060) ---- */
+
+/* Opaque table of distinct DCRs, resident on the device it is first used on, growing across calls.  A DCR is
+ * (v, j, vdel, jdel, insert) of a record with status DCRX_S_OK; insert is the frame read's bytes
+ * [ins_start, ins_start + ins_len) exactly as the `.n12` row's fifth field holds them (exception bytes included,
+ * complemented as revcomp() does in the reverse frame).  Each entry keeps the key, a 64-bit count and the smallest
+ * read ordinal that carried the key.  Two DCRs are merged only when their full keys compare equal.  Like a tables
+ * handle it is not thread-safe, and the steps that feed one table run on ONE stream.  Reset empties it and keeps its
+ * device memory. */
+typedef struct dcrx_counts dcrx_counts_t;
+int dcrx_counts_create(dcrx_counts_t **out);
+void dcrx_counts_destroy(dcrx_counts_t *counts);
+int dcrx_counts_reset(dcrx_counts_t *counts);
+/* Keeps only the low `bits` bits (0 .. 63; 63 by default) of every key's hash, on an empty table (after create or reset).
+ * The results do not change: with few bits, distinct DCRs share hashes and every merge goes through the full-key
+ * comparisons (the same hash inside a batch, a published slot of that hash in the table).  For tests; slower. */
+int dcrx_counts_set_hash_bits(dcrx_counts_t *counts, uint32_t bits);
+
+/* The count step (the primitive): adds the DCR of every OK record of d_records (device_batch->n_reads entries, device
+ * memory) into `counts`, asynchronously on `hip_stream`.  device_batch is the batch those records came from (packed
+ * reads, lengths, exceptions: device memory), as dcrx_decombine_device read it.  Read r's ordinal is
+ * first_index + r, or first_index + d_index[r] when d_index (device, n_reads uint32) is given — for a batch that the
+ * caller has split (reads over 511 nt in calls of their own).  The step aggregates a batch before it touches the
+ * table: each distinct DCR of the batch costs one update of the table.  It allocates (and then synchronises the stream)
+ * only when the table, the arena of inserts or its work space must grow. */
+int dcrx_count_device(dcrx_counts_t *counts, const dcrx_record_t *d_records, const dcrx_batch_t *device_batch,
+                      uint64_t first_index, const uint32_t *d_index, void *hip_stream);
+
+/* dcrx_decombine with the count step on each chunk, on the same stream as the chunk's kernels: the records stay on the
+ * device, only the counters (DCRX_N_COUNTERS uint64, OVERWRITTEN) come back.  Ordinals as in dcrx_count_device, with
+ * `index` a host array of n_reads entries (or NULL).  Synchronous. */
+int dcrx_decombine_count(dcrx_tables_t *tables, const dcrx_cfg_t *cfg, const dcrx_batch_t *host_batch,
+                         dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index, uint64_t *counters);
+
+/* dcrx_decombine_chains with the count step of chain c into counts[c] on that chain's stream, behind its kernels.  The
+ * count step reads the packed chunk, so it is among the launches an input set waits for before it is refilled.
+ * counts[c] and counters[c] equal what dcrx_decombine_count(tables[c], ..., counts[c], ...) gives on the same batch.
+ * DCRX_E_INVALID for the same counts handle twice.  Synchronous. */
+int dcrx_decombine_chains_count(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                                const dcrx_batch_t *host_batch, dcrx_counts_t *const *counts, uint64_t first_index,
+                                const uint32_t *index, uint64_t *const *counters);
+
+/* The distinct DCRs of `counts` in collections.Counter.most_common() order over the reads in ordinal order: count
+ * descending, ties by the smaller first ordinal.  Entry k: v[k], j[k], vdel[k], jdel[k], count[k], first[k] (its first
+ * ordinal), and its insert ins_text[ins_off[k] .. ins_off[k + 1]) (ins_off: n + 1 entries, no terminator).  Returns n,
+ * the number of distinct DCRs, and sets *text_bytes; writes the arrays only when cap >= n and text_cap >= *text_bytes
+ * (call with cap = 0 to size them: that call only counts, it neither compacts nor sorts).  Synchronises the device. */
+int64_t dcrx_counts_read(dcrx_counts_t *counts, uint16_t *v, uint16_t *j, uint8_t *vdel, uint8_t *jdel, uint64_t *count,
+                         uint64_t *first, uint64_t *ins_off, char *ins_text, uint64_t cap, uint64_t text_cap,
+                         uint64_t *text_bytes);
+
+/* The `.nbc` text of n counted DCRs (what dcrx_counts_read gives): one line per DCR, "v j vdel jdel insert count" with
+ * field_sep between the fields and '\n' after the line.  Returns the bytes the text takes; writes it only when out != NULL
+ * and it fits out_cap.  A buffer of n * (DCRX_COUNTS_LINE_BOUND + 5 * strlen(field_sep)) + ins_off[n] - ins_off[0] bytes
+ * always fits, and is written in one pass.  Host only. */
+#define DCRX_COUNTS_LINE_BOUND 54   /* digits of v, j (5 each), vdel, jdel (3 each), count (20), and the newline */
+int64_t dcrx_format_counts(uint64_t n, const uint16_t *v, const uint16_t *j, const uint8_t *vdel, const uint8_t *jdel,
+                           const uint64_t *count, const uint64_t *ins_off, const char *ins_text, const char *field_sep,
+                           char *out, uint64_t out_cap);
+
 /* Profiling aid: the following dcrx_decombine_device calls on `tables` record
  * start_event right before and stop_event right after the dominant kernel (the scan),
  * on the stream that kernel is launched on (hipEvent_t handles, e.g. from
