@@ -950,6 +950,30 @@ def pinned_empty(shape, dtype) -> np.ndarray:
     return np.frombuffer(buf, dtype=np.uint8, count=n).view(dtype).reshape(shape)
 
 
+def _host_call(tables_list, batch: PackedBatch, cfg: CfgC, recs=None, counts_list=None, first_index: int = 0, index=None,
+               chains: bool = True) -> list:
+    """The host-buffer entries over tables_list: records into recs (a records array per chain), or DCRs into counts_list
+    (a DcrCounts per chain) read r as ordinal first_index + r (or first_index + index[r]).  The chains entry, or with
+    chains=False the single-chain entry over the one chain.  Returns the counters (uint64[32]) per chain."""
+    L, k = lib(), max(1, len(tables_list))
+    cnts = [np.zeros(N_COUNTERS, dtype=np.uint64) for _ in tables_list]
+    handles = (C.c_void_p * k)(*[t.handle for t in tables_list])
+    cnt_ptrs = (C.c_void_p * k)(*[c.ctypes.data for c in cnts])
+    cfg_p, b = C.byref(cfg), batch.as_c()
+    if counts_list is None:
+        rec_ptrs = (C.c_void_p * k)(*[r.ctypes.data if batch.n_reads else None for r in recs])
+        rc = (L.dcrx_decombine_chains(handles, len(tables_list), cfg_p, C.byref(b), rec_ptrs, cnt_ptrs) if chains else
+              L.dcrx_decombine(handles[0], cfg_p, C.byref(b), rec_ptrs[0], cnt_ptrs[0]))
+    else:
+        idx, idx_ptr = _index_arg(index, batch.n_reads)
+        counts_h = (C.c_void_p * k)(*[c.handle for c in counts_list])
+        rc = (L.dcrx_decombine_chains_count(handles, len(tables_list), cfg_p, C.byref(b), counts_h, int(first_index), idx_ptr,
+                                            cnt_ptrs) if chains else
+              L.dcrx_decombine_count(handles[0], cfg_p, C.byref(b), counts_h[0], int(first_index), idx_ptr, cnt_ptrs[0]))
+    check(rc)
+    return cnts
+
+
 def decombine(tables: Tables, batch: PackedBatch, orientation="reverse", allow_ns=False,
               lenthreshold=130, flags=0, out: np.ndarray | None = None):
     """dcrx_decombine on host buffers.  Returns (records[RECORD_DTYPE], counters uint64[32]).  `out`: a records array to
@@ -958,13 +982,7 @@ def decombine(tables: Tables, batch: PackedBatch, orientation="reverse", allow_n
     if out is not None:
         assert out.dtype == RECORD_DTYPE and out.shape == (batch.n_reads,) and out.flags.c_contiguous
     rec = out if out is not None else np.zeros(batch.n_reads, dtype=RECORD_DTYPE)
-    cnt = np.zeros(N_COUNTERS, dtype=np.uint64)
-    b = batch.as_c()
-    check(lib().dcrx_decombine(tables.handle, C.byref(cfg), C.byref(b),
-                               rec.ctypes.data if batch.n_reads else None, cnt.ctypes.data))
-    if int(cnt[DEVICE_ERRORS]):      # (include/dcrx_codes.h: a wave gave up waiting for another — the records are not complete)
-        raise RuntimeError(f"dcrx_decombine: {int(cnt[DEVICE_ERRORS])} device-side wait(s) timed out; the records of this call are incomplete")
-    return rec, cnt
+    return rec, _host_call([tables], batch, cfg, recs=[rec], chains=False)[0]
 
 
 MAX_CHAINS = 4          # DCRX_MAX_CHAINS
@@ -976,19 +994,8 @@ def decombine_chains(tables_list, batch: PackedBatch, orientation="reverse", all
     gives for that chain alone."""
     tables_list = list(tables_list)
     cfg = make_cfg(orientation, allow_ns, lenthreshold, flags)
-    n = batch.n_reads
-    recs = [np.zeros(n, dtype=RECORD_DTYPE) for _ in tables_list]
-    cnts = [np.zeros(N_COUNTERS, dtype=np.uint64) for _ in tables_list]
-    k = max(1, len(tables_list))
-    handles = (C.c_void_p * k)(*[t.handle for t in tables_list])
-    rec_ptrs = (C.c_void_p * k)(*[r.ctypes.data if n else None for r in recs])
-    cnt_ptrs = (C.c_void_p * k)(*[c.ctypes.data for c in cnts])
-    b = batch.as_c()
-    check(lib().dcrx_decombine_chains(handles, len(tables_list), C.byref(cfg), C.byref(b), rec_ptrs, cnt_ptrs))
-    for cnt in cnts:
-        if int(cnt[DEVICE_ERRORS]):
-            raise RuntimeError(f"dcrx_decombine_chains: {int(cnt[DEVICE_ERRORS])} device-side wait(s) timed out; the records of this call are incomplete")
-    return list(zip(recs, cnts))
+    recs = [np.zeros(batch.n_reads, dtype=RECORD_DTYPE) for _ in tables_list]
+    return list(zip(recs, _host_call(tables_list, batch, cfg, recs=recs)))
 
 
 class DcrCounts:
@@ -1082,12 +1089,7 @@ def decombine_count(tables: Tables, batch: PackedBatch, counts: DcrCounts, first
     """dcrx_decombine_count: the batch decombined and its DCRs added into `counts`, read r as ordinal first_index + r (or
     first_index + index[r]).  Returns the counters (uint64[32]); no records come back."""
     cfg = make_cfg(orientation, allow_ns, lenthreshold, flags)
-    cnt = np.zeros(N_COUNTERS, dtype=np.uint64)
-    idx, idx_ptr = _index_arg(index, batch.n_reads)
-    b = batch.as_c()
-    check(lib().dcrx_decombine_count(tables.handle, C.byref(cfg), C.byref(b), counts.handle, int(first_index), idx_ptr,
-                                     cnt.ctypes.data))
-    return cnt
+    return _host_call([tables], batch, cfg, counts_list=[counts], first_index=first_index, index=index, chains=False)[0]
 
 
 def decombine_chains_count(tables_list, batch: PackedBatch, counts_list, first_index: int = 0, index=None,
@@ -1098,25 +1100,13 @@ def decombine_chains_count(tables_list, batch: PackedBatch, counts_list, first_i
     if len(tables_list) != len(counts_list):
         raise ValueError("one DcrCounts per chain")
     cfg = make_cfg(orientation, allow_ns, lenthreshold, flags)
-    k = max(1, len(tables_list))
-    cnts = [np.zeros(N_COUNTERS, dtype=np.uint64) for _ in tables_list]
-    handles = (C.c_void_p * k)(*[t.handle for t in tables_list])
-    counts_h = (C.c_void_p * k)(*[c.handle for c in counts_list])
-    cnt_ptrs = (C.c_void_p * k)(*[c.ctypes.data for c in cnts])
-    idx, idx_ptr = _index_arg(index, batch.n_reads)
-    b = batch.as_c()
-    check(lib().dcrx_decombine_chains_count(handles, len(tables_list), C.byref(cfg), C.byref(b), counts_h, int(first_index),
-                                            idx_ptr, cnt_ptrs))
-    return cnts
+    return _host_call(tables_list, batch, cfg, counts_list=counts_list, first_index=first_index, index=index)
 
 
 def count_dcrs(tables_list, batch: PackedBatch, counts_list, first_index: int = 0, index=None, orientation="reverse",
                allow_ns=False, lenthreshold=130) -> list:
     """The barcode-free stage's one call per batch: decombine the batch for every chain and add its DCRs into that chain's
-    DcrCounts (dcrx_decombine_count for one chain, dcrx_decombine_chains_count — one upload — for several).  Returns the
-    counters per chain."""
-    if len(tables_list) == 1:
-        return [decombine_count(tables_list[0], batch, counts_list[0], first_index, index, orientation, allow_ns, lenthreshold)]
+    DcrCounts (dcrx_decombine_chains_count: one upload, whatever the number of chains).  Returns the counters per chain."""
     return decombine_chains_count(tables_list, batch, counts_list, first_index, index, orientation, allow_ns, lenthreshold)
 
 

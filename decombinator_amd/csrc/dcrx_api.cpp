@@ -488,104 +488,9 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   return DCRX_OK;
 }
 
-// (counts: the count entry's table — the chunks' records stay on the device and feed it, only the counters come back)
-static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters,
-                          dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index);
-
-// The host-buffer entry.  Whatever goes wrong inside the chunk pipeline — a HIP error, no memory, a helper thread that cannot
-// be started — comes back as a code, and only after the three streams have drained: their asynchronous copies may target the
-// caller's own (pinned) `packed` and `records` buffers, which the caller is free to release once this returns.
-static int decombine_entry(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records,
-                           uint64_t *counters, dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index) {
-  int rc;
-  const bool sink_was_on = t && t->sink_on;      // (the tuple sink concerns the device entry: a chunked host call has no one message)
-  if (t) t->sink_on = false;
-  try { rc = decombine_host(t, cfg, hb, records, counters, counts, first_index, index); }
-  catch (const std::bad_alloc &) { rc = set_err(DCRX_E_NOMEM, "out of host memory in dcrx_decombine"); }
-  catch (const std::exception &e) { rc = set_err(DCRX_E_NOMEM, std::string("dcrx_decombine: ") + e.what()); }
-  catch (...) { rc = set_err(DCRX_E_NOMEM, "dcrx_decombine: unexpected exception"); }
-  if (rc != DCRX_OK && t && t->hs_in) {
-    const std::string keep = g_err;       // (the synchronising calls must not replace the message of what failed)
-    (void)hipStreamSynchronize(t->hs_in); (void)hipStreamSynchronize(t->hs_run); (void)hipStreamSynchronize(t->hs_out);
-    (void)hipGetLastError();
-    t->ws_dirty = true;
-    g_err = keep;
-  }
-  if (t) t->sink_on = sink_was_on;
-  return rc;
-}
-
-int dcrx_decombine(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records,
-                   uint64_t *counters) {
-  return decombine_entry(t, cfg, hb, records, counters, nullptr, 0, nullptr);
-}
-
-int dcrx_decombine_count(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_counts_t *counts,
-                         uint64_t first_index, const uint32_t *index, uint64_t *counters) {
-  if (!counts) return set_err(DCRX_E_INVALID, "counts is null");
-  return decombine_entry(t, cfg, hb, nullptr, counters, counts, first_index, index);
-}
-
-static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
-                                 dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
-                                 uint64_t first_index, const uint32_t *index);
-
-// The multi-chain host-buffer entry: the same epilogue as dcrx_decombine, over every stream the call used.
-static int decombine_chains_entry(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
-                                  dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
-                                  uint64_t first_index, const uint32_t *index) {
-  if (!tables || !cfg || (!records && !counts) || !counters) return set_err(DCRX_E_INVALID, "null argument");
-  if (n_chains == 0 || n_chains > DCRX_MAX_CHAINS) return set_err(DCRX_E_INVALID, "n_chains must be 1 .. DCRX_MAX_CHAINS");
-  for (uint32_t c = 0; c < n_chains; c++) {
-    if (!tables[c]) return set_err(DCRX_E_INVALID, "tables[c] is null");
-    for (uint32_t e = 0; e < c; e++)
-      if (tables[e] == tables[c]) return set_err(DCRX_E_INVALID, "the same tables handle twice: every chain needs a handle (and a workspace) of its own");
-  }
-  if (counts)
-    for (uint32_t c = 0; c < n_chains; c++) {
-      if (!counts[c]) return set_err(DCRX_E_INVALID, "counts[c] is null");
-      for (uint32_t e = 0; e < c; e++)
-        if (counts[e] == counts[c]) return set_err(DCRX_E_INVALID, "the same counts handle twice: every chain needs a table of its own");
-    }
-  bool sink_was_on[DCRX_MAX_CHAINS];
-  for (uint32_t c = 0; c < n_chains; c++) { sink_was_on[c] = tables[c]->sink_on; tables[c]->sink_on = false; }
-  int rc;
-  try { rc = decombine_chains_host(tables, n_chains, cfg, hb, records, counters, counts, first_index, index); }
-  catch (const std::bad_alloc &) { rc = set_err(DCRX_E_NOMEM, "out of host memory in dcrx_decombine_chains"); }
-  catch (const std::exception &e) { rc = set_err(DCRX_E_NOMEM, std::string("dcrx_decombine_chains: ") + e.what()); }
-  catch (...) { rc = set_err(DCRX_E_NOMEM, "dcrx_decombine_chains: unexpected exception"); }
-  if (rc != DCRX_OK) {
-    const std::string keep = g_err;
-    for (uint32_t c = 0; c < n_chains; c++) {
-      dcrx_tables *t = tables[c];
-      if (t->hs_in) (void)hipStreamSynchronize(t->hs_in);
-      if (t->hs_run) (void)hipStreamSynchronize(t->hs_run);
-      if (t->hs_out) (void)hipStreamSynchronize(t->hs_out);
-      t->ws_dirty = true;
-    }
-    (void)hipGetLastError();
-    g_err = keep;
-  }
-  for (uint32_t c = 0; c < n_chains; c++) tables[c]->sink_on = sink_was_on[c];
-  return rc;
-}
-
-int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
-                          const dcrx_batch_t *hb, dcrx_record_t *const *records, uint64_t *const *counters) {
-  if (!records) return set_err(DCRX_E_INVALID, "null argument");
-  return decombine_chains_entry(tables, n_chains, cfg, hb, records, counters, nullptr, 0, nullptr);
-}
-
-int dcrx_decombine_chains_count(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
-                                const dcrx_batch_t *hb, dcrx_counts_t *const *counts, uint64_t first_index,
-                                const uint32_t *index, uint64_t *const *counters) {
-  if (!counts) return set_err(DCRX_E_INVALID, "null argument");
-  return decombine_chains_entry(tables, n_chains, cfg, hb, nullptr, counters, counts, first_index, index);
-}
-
 }  // extern "C"
 
-// ---- the host-buffer entries' common parts ----------------------------------------------------------------------------
+// ---- the host-buffer entries ------------------------------------------------------------------------------------------
 
 // host-side validation of a host batch that the device entry cannot afford (after check_batch)
 static int check_host_batch(const dcrx_batch_t *hb) {
@@ -609,8 +514,8 @@ static int check_host_batch(const dcrx_batch_t *hb) {
   return DCRX_OK;
 }
 
-// One chunk's staging: the input half (packed | lens | exc_read | exc_pos | exc_chr) and the output half (records |
-// counters), offsets inside each half.  (long reads: a chunk's packed bytes stay within what 2 M reads of 150 nt take)
+// One chunk's staging: the input set (packed | lens | exc_read | exc_pos | exc_chr) and the output set (records |
+// counters), offsets inside each set.  (long reads: a chunk's packed bytes stay within what 2 M reads of 150 nt take)
 struct HostLayout {
   uint64_t chunk = 0;
   size_t o_lens = 0, o_er = 0, o_ep = 0, o_ec = 0, in_bytes = 0;
@@ -675,143 +580,31 @@ static bool host_pinned(const void *p) {
   return a.type == hipMemoryTypeHost;
 }
 
-static int decombine_host(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records, uint64_t *counters,
-                          dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index) {
-  if (!t || !cfg || !counters) return set_err(DCRX_E_INVALID, "null argument");
-  int rc = check_batch(hb);
-  if (rc) return rc;
+// The chunk pipeline of the host-buffer entries, over nc = 1 .. DCRX_MAX_CHAINS handles (arguments checked by host_entry);
+// chain c fills records[c], or counts[c] (the chunks' records then stay on the device and feed it, only the counters come
+// back).  The batch goes through in chunks of DCRX_HOST_CHUNK reads, three streams deep: while the kernels of chunk k run,
+// chunk k + 1 is copied in and the records of chunk k - 1 are copied out (PCIe is full duplex: 40 bytes per read one way,
+// 16 the other), through pinned staging buffers (a copy from pageable memory would not overlap anything).  Each chunk is
+// copied in once, on T[0]'s copy-in stream, into the input sets of T[0]'s staging, in front of its output sets; every
+// other handle's staging holds only its output sets.  Each chain's launches run on its handle's run stream.  The loop it
+// stands for is the reference's read loop (decombine.py:963-1050).
+static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
+                         dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
+                         uint64_t first_index, const uint32_t *index) {
   const uint64_t n = hb->n_reads;
-  if (n && !records && !counts) return set_err(DCRX_E_INVALID, "records is null");
-  rc = check_host_batch(hb);
-  if (rc) return rc;
-  // The batch goes through in chunks of DCRX_HOST_CHUNK reads, three streams deep: while the kernels of chunk k run, chunk
-  // k + 1 is copied in and the records of chunk k - 1 are copied out (PCIe is full duplex: 40 bytes per read one way, 16 the
-  // other), through pinned staging buffers (a copy from pageable memory would not overlap anything).  The loop it stands
-  // for is the reference's read loop (decombine.py:963-1050).
   const HostLayout Lay = host_layout(hb);
   const uint64_t chunk = Lay.chunk;
-  rc = ensure_device(t, chunk, hb->stride);
-  if (rc) return rc;
-  // one chunk's staging: packed | lens | exc_read | exc_pos | exc_chr || records | counters    (x 2 sets)
-  const size_t o_packed = 0, o_lens = Lay.o_lens, o_er = Lay.o_er, o_ep = Lay.o_ep, o_ec = Lay.o_ec, in_bytes = Lay.in_bytes;
-  const size_t o_rec = in_bytes;
-  const size_t o_cnt = o_rec + Lay.o_cnt;
-  const size_t set_bytes = in_bytes + Lay.out_bytes;
-  rc = ensure_staging(t, 2 * set_bytes);
-  if (rc) return rc;
-  rc = ensure_host_streams(t, true, true, true);
-  if (rc) return rc;
-  for (int c = 0; c < DCRX_N_COUNTERS; c++) counters[c] = 0;
-  const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
-  const bool out_direct = n && !counts && host_pinned(records) && host_pinned(reinterpret_cast<const uint8_t *>(records + n) - 1);
-  const uint64_t n_chunks = n ? (n + chunk - 1) / chunk : 1;
-  uint64_t exc_at = 0;
-  auto drain = [&](uint64_t k) -> int {       // chunk k's records and counters: from the pinned buffer to the caller's
-    const int set = (int)(k & 1);
-    HIP_TRY(hipEventSynchronize(t->hev_out[set]));
-    const uint8_t *h = t->h_stage + (size_t)set * set_bytes;
-    const uint64_t c0 = k * chunk, cn = std::min<uint64_t>(chunk, n - c0);
-    if (cn && !out_direct && !counts) par_memcpy(records + c0, h + o_rec, cn * sizeof(dcrx_record_t));
-    const uint64_t *hc = reinterpret_cast<const uint64_t *>(h + o_cnt);
-    for (int c = 0; c < DCRX_N_COUNTERS; c++) counters[c] += hc[c];
-    return DCRX_OK;
-  };
-  for (uint64_t k = 0; k < n_chunks; k++) {
-    const int set = (int)(k & 1);
-    const uint64_t c0 = k * chunk, cn = n ? std::min<uint64_t>(chunk, n - c0) : 0;
-    uint8_t *h = t->h_stage + (size_t)set * set_bytes, *d = t->d_stage + (size_t)set * set_bytes;
-    // the records of chunk k - 2 leave the set's pinned buffer on a helper thread while this thread fills its input half
-    // (the halves do not overlap; the copy out of chunk k - 2 has landed before the helper touches anything)
-    int drc = DCRX_OK;
-    std::thread helper;
-    if (k >= 2) helper = std::thread([&, k] { drc = drain(k - 2); });
-    struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_helper{helper};
-    // the chunk into the pinned buffer (several threads: one memcpy does not keep up with the link) — once the copy in of
-    // chunk k - 2, which read the same bytes, is over
-    if (k >= 2) HIP_TRY(hipEventSynchronize(t->hev_in[set]));
-    uint64_t e0 = exc_at;
-    while (exc_at < hb->n_exc && hb->exc_read[exc_at] < c0 + cn) exc_at++;
-    const uint64_t ne = exc_at - e0;
-    if (cn && !in_direct) par_memcpy(h + o_packed, hb->packed + c0 * hb->stride, cn * hb->stride);
-    if (hb->lens && cn) std::memcpy(h + o_lens, hb->lens + c0, cn * 2);
-    uint32_t *her = reinterpret_cast<uint32_t *>(h + o_er);
-    for (uint64_t i = 0; i < ne; i++) her[i] = hb->exc_read[e0 + i] - (uint32_t)c0;      // read indices inside the chunk
-    if (ne) { std::memcpy(h + o_ep, hb->exc_pos + e0, ne * 2); std::memcpy(h + o_ec, hb->exc_chr + e0, ne); }
-    if (helper.joinable()) helper.join();
-    if (drc) return drc;
-    // copy in (after the kernels that last read this set's device buffers), kernels, copy out
-    if (k >= 2) HIP_TRY(hipStreamWaitEvent(t->hs_in, t->hev_run[set], 0));
-    if (in_direct) {
-      HIP_TRY(hipMemcpyAsync(d + o_packed, hb->packed + c0 * hb->stride, cn * hb->stride, hipMemcpyHostToDevice, t->hs_in));
-      if (in_bytes > o_lens) HIP_TRY(hipMemcpyAsync(d + o_lens, h + o_lens, in_bytes - o_lens, hipMemcpyHostToDevice, t->hs_in));
-    } else {
-      HIP_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, t->hs_in));
-    }
-    HIP_TRY(hipEventRecord(t->hev_in[set], t->hs_in));
-    HIP_TRY(hipStreamWaitEvent(t->hs_run, t->hev_in[set], 0));
-    if (k >= 2) HIP_TRY(hipStreamWaitEvent(t->hs_run, t->hev_out[set], 0));     // (the records buffer of chunk k - 2 has been copied out)
-    dcrx_batch_t db = *hb;
-    db.n_reads = cn;
-    db.packed = d + o_packed;
-    db.lens = hb->lens ? reinterpret_cast<const uint16_t *>(d + o_lens) : nullptr;
-    db.n_exc = ne;
-    db.exc_read = reinterpret_cast<const uint32_t *>(d + o_er);
-    db.exc_pos = reinterpret_cast<const uint16_t *>(d + o_ep);
-    db.exc_chr = d + o_ec;
-    rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(d + o_rec), reinterpret_cast<uint64_t *>(d + o_cnt), t->hs_run);
-    if (rc) return rc;          // (the caller of this function drains the streams)
-    if (counts && cn) {         // the count step reads the chunk's records and its packed reads: before the set is refilled
-      rc = count_chunk(counts, reinterpret_cast<const dcrx_record_t *>(d + o_rec), &db, index ? first_index : first_index + c0,
-                       index ? index + c0 : nullptr, t->hs_run);
-      if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(t->hev_run[set], t->hs_run));
-    HIP_TRY(hipStreamWaitEvent(t->hs_out, t->hev_run[set], 0));
-    if (out_direct || counts) {
-      if (cn && !counts) HIP_TRY(hipMemcpyAsync(records + c0, d + o_rec, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_out));
-      HIP_TRY(hipMemcpyAsync(h + o_cnt, d + o_cnt, set_bytes - o_cnt, hipMemcpyDeviceToHost, t->hs_out));
-    } else {
-      HIP_TRY(hipMemcpyAsync(h + o_rec, d + o_rec, set_bytes - o_rec, hipMemcpyDeviceToHost, t->hs_out));
-    }
-    HIP_TRY(hipEventRecord(t->hev_out[set], t->hs_out));
-  }
-  for (uint64_t k = n_chunks >= 2 ? n_chunks - 2 : 0; k < n_chunks; k++) { rc = drain(k); if (rc) return rc; }
-  // (include/dcrx_codes.h: a wave that gave up waiting for another says so in the call's counters — the records would not be
-  // complete, and this entry, which has the counters in hand, does not return them as if they were)
-  if (counters[DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
-  if (counts) return count_settle(counts, t->hs_run);
-  return DCRX_OK;
-}
-
-// decombine_host for several chains over one batch (arguments checked by dcrx_decombine_chains).  The chunks' input sets
-// live in the first handle's staging, in front of its output sets; every other handle's staging holds only its output sets.
-// Streams: tables[0]'s copy-in stream, and per chain its run stream, which carries the chain's launches and its copy out.
-static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
-                                 dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
-                                 uint64_t first_index, const uint32_t *index) {
-  int rc = check_batch(hb);
-  if (rc) return rc;
-  const uint64_t n = hb->n_reads;
-  for (uint32_t c = 0; c < nc; c++) {
-    if (!counters[c]) return set_err(DCRX_E_INVALID, "counters[c] is null");
-    if (n && !counts && !records[c]) return set_err(DCRX_E_INVALID, "records[c] is null");
-  }
-  rc = check_host_batch(hb);
-  if (rc) return rc;
-  const HostLayout Lay = host_layout(hb);
-  const uint64_t chunk = Lay.chunk;
+  int rc;
   for (uint32_t c = 0; c < nc; c++) {
     rc = ensure_device(T[c], chunk, hb->stride);
     if (rc) return rc;
     rc = ensure_staging(T[c], (c == 0 ? 2 * Lay.in_bytes : 0) + 2 * Lay.out_bytes);
     if (rc) return rc;
-    rc = ensure_host_streams(T[c], c == 0, true, false);
+    rc = ensure_host_streams(T[c], c == 0, true, nc == 1);
     if (rc) return rc;
     for (int k = 0; k < DCRX_N_COUNTERS; k++) counters[c][k] = 0;
   }
   hipStream_t s_in = T[0]->hs_in;
-  auto in_h = [&](int set) { return T[0]->h_stage + (size_t)set * Lay.in_bytes; };
-  auto in_d = [&](int set) { return T[0]->d_stage + (size_t)set * Lay.in_bytes; };
   auto out_at = [&](uint32_t c, int set) { return (c == 0 ? 2 * Lay.in_bytes : 0) + (size_t)set * Lay.out_bytes; };
   const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
   bool out_direct[DCRX_MAX_CHAINS];
@@ -834,9 +627,10 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
   for (uint64_t k = 0; k < n_chunks; k++) {
     const int set = (int)(k & 1);
     const uint64_t c0 = k * chunk, cn = n ? std::min<uint64_t>(chunk, n - c0) : 0;
-    uint8_t *h = in_h(set), *d = in_d(set);
-    // chunk k - 2's records leave the pinned buffers on a helper thread while this thread fills the input set (the
-    // input and output sets do not overlap), once the copy in of chunk k - 2, which read the same bytes, is over
+    uint8_t *h = T[0]->h_stage + (size_t)set * Lay.in_bytes, *d = T[0]->d_stage + (size_t)set * Lay.in_bytes;
+    // chunk k - 2's records leave the pinned buffers on a helper thread while this thread fills the input set (several
+    // threads: one memcpy does not keep up with the link; the input and output sets do not overlap), once the copy in of
+    // chunk k - 2, which read the same bytes, is over
     int drc = DCRX_OK;
     std::thread helper;
     if (k >= 2) helper = std::thread([&, k] { drc = drain(k - 2); });
@@ -848,7 +642,7 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
     if (cn && !in_direct) par_memcpy(h, hb->packed + c0 * hb->stride, cn * hb->stride);
     if (hb->lens && cn) std::memcpy(h + Lay.o_lens, hb->lens + c0, cn * 2);
     uint32_t *her = reinterpret_cast<uint32_t *>(h + Lay.o_er);
-    for (uint64_t i = 0; i < ne; i++) her[i] = hb->exc_read[e0 + i] - (uint32_t)c0;
+    for (uint64_t i = 0; i < ne; i++) her[i] = hb->exc_read[e0 + i] - (uint32_t)c0;      // read indices inside the chunk
     if (ne) { std::memcpy(h + Lay.o_ep, hb->exc_pos + e0, ne * 2); std::memcpy(h + Lay.o_ec, hb->exc_chr + e0, ne); }
     if (helper.joinable()) helper.join();
     if (drc) return drc;
@@ -870,36 +664,122 @@ static int decombine_chains_host(dcrx_tables *const *T, uint32_t nc, const dcrx_
     db.exc_read = reinterpret_cast<const uint32_t *>(d + Lay.o_er);
     db.exc_pos = reinterpret_cast<const uint16_t *>(d + Lay.o_ep);
     db.exc_chr = d + Lay.o_ec;
-    // every chain: kernels, then its copy out, on its own stream (which orders chunk k's kernels behind chunk k - 2's copy
-    // out of the same output set)
+    // every chain: kernels, then its copy out
     for (uint32_t c = 0; c < nc; c++) {
       dcrx_tables *t = T[c];
+      // (one chain: the handle's out stream, beside the next chunk's kernels; several: behind the chain's kernels)
+      const hipStream_t s_out = nc == 1 ? t->hs_out : t->hs_run;
       uint8_t *od = t->d_stage + out_at(c, set), *oh = t->h_stage + out_at(c, set);
       HIP_TRY(hipStreamWaitEvent(t->hs_run, T[0]->hev_in[set], 0));
+      // (the records of chunk k - 2 have left this output set: a copy out on the run stream itself is ordered already)
+      if (k >= 2 && s_out != t->hs_run) HIP_TRY(hipStreamWaitEvent(t->hs_run, t->hev_out[set], 0));
       rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(od), reinterpret_cast<uint64_t *>(od + Lay.o_cnt), t->hs_run);
-      if (rc) return rc;          // (dcrx_decombine_chains drains the streams)
+      if (rc) return rc;          // (host_entry drains the streams)
       if (counts && cn) {         // the count step reads the packed chunk too: it is among what the next refill of the set waits for
         rc = count_chunk(counts[c], reinterpret_cast<const dcrx_record_t *>(od), &db, index ? first_index : first_index + c0,
                          index ? index + c0 : nullptr, t->hs_run);
         if (rc) return rc;
       }
       HIP_TRY(hipEventRecord(t->hev_run[set], t->hs_run));
+      if (s_out != t->hs_run) HIP_TRY(hipStreamWaitEvent(s_out, t->hev_run[set], 0));
       if (out_direct[c] || counts) {
-        if (cn && !counts) HIP_TRY(hipMemcpyAsync(records[c] + c0, od, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, t->hs_run));
-        HIP_TRY(hipMemcpyAsync(oh + Lay.o_cnt, od + Lay.o_cnt, Lay.out_bytes - Lay.o_cnt, hipMemcpyDeviceToHost, t->hs_run));
+        if (cn && !counts) HIP_TRY(hipMemcpyAsync(records[c] + c0, od, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, s_out));
+        HIP_TRY(hipMemcpyAsync(oh + Lay.o_cnt, od + Lay.o_cnt, Lay.out_bytes - Lay.o_cnt, hipMemcpyDeviceToHost, s_out));
       } else {
-        HIP_TRY(hipMemcpyAsync(oh, od, Lay.out_bytes, hipMemcpyDeviceToHost, t->hs_run));
+        HIP_TRY(hipMemcpyAsync(oh, od, Lay.out_bytes, hipMemcpyDeviceToHost, s_out));
       }
-      HIP_TRY(hipEventRecord(t->hev_out[set], t->hs_run));
+      HIP_TRY(hipEventRecord(t->hev_out[set], s_out));
     }
   }
   for (uint64_t k = n_chunks >= 2 ? n_chunks - 2 : 0; k < n_chunks; k++) { rc = drain(k); if (rc) return rc; }
+  // (include/dcrx_codes.h: a wave that gave up waiting for another says so in the call's counters — the records would not be
+  // complete, and this entry, which has the counters in hand, does not return them as if they were)
   for (uint32_t c = 0; c < nc; c++)
     if (counters[c][DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
   if (counts)
     for (uint32_t c = 0; c < nc; c++) { rc = count_settle(counts[c], T[c]->hs_run); if (rc) return rc; }
   return DCRX_OK;
 }
+
+// The one epilogue of the four host-buffer entries.  Whatever goes wrong inside the chunk pipeline — a HIP error, no memory,
+// a helper thread that cannot be started — comes back as a code, and only after every stream of every handle has drained:
+// their asynchronous copies may target the caller's own (pinned) `packed` and `records` buffers, which the caller is free to
+// release once this returns.  (The tuple sink concerns the device entry: a chunked host call has no one message.)
+static int host_entry(dcrx_tables_t *const *T, uint32_t nc, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb,
+                      dcrx_record_t *const *records, uint64_t *const *counters, dcrx_counts_t *const *counts,
+                      uint64_t first_index, const uint32_t *index) {
+  if (!T || !cfg || (!records && !counts) || !counters) return set_err(DCRX_E_INVALID, "null argument");
+  if (nc == 0 || nc > DCRX_MAX_CHAINS) return set_err(DCRX_E_INVALID, "n_chains must be 1 .. DCRX_MAX_CHAINS");
+  for (uint32_t c = 0; c < nc; c++) {
+    if (!T[c]) return set_err(DCRX_E_INVALID, "tables[c] is null");
+    for (uint32_t e = 0; e < c; e++)
+      if (T[e] == T[c]) return set_err(DCRX_E_INVALID, "the same tables handle twice: every chain needs a handle (and a workspace) of its own");
+  }
+  if (counts)
+    for (uint32_t c = 0; c < nc; c++) {
+      if (!counts[c]) return set_err(DCRX_E_INVALID, "counts[c] is null");
+      for (uint32_t e = 0; e < c; e++)
+        if (counts[e] == counts[c]) return set_err(DCRX_E_INVALID, "the same counts handle twice: every chain needs a table of its own");
+    }
+  int rc = check_batch(hb);
+  if (rc) return rc;
+  for (uint32_t c = 0; c < nc; c++) {
+    if (!counters[c]) return set_err(DCRX_E_INVALID, "counters[c] is null");
+    if (hb->n_reads && !counts && !records[c]) return set_err(DCRX_E_INVALID, "records[c] is null");
+  }
+  rc = check_host_batch(hb);
+  if (rc) return rc;
+  bool sink_was_on[DCRX_MAX_CHAINS];
+  for (uint32_t c = 0; c < nc; c++) { sink_was_on[c] = T[c]->sink_on; T[c]->sink_on = false; }
+  try { rc = host_pipeline(T, nc, cfg, hb, records, counters, counts, first_index, index); }
+  catch (const std::bad_alloc &) { rc = set_err(DCRX_E_NOMEM, "out of host memory in the host-buffer entry"); }
+  catch (const std::exception &e) { rc = set_err(DCRX_E_NOMEM, std::string("host-buffer entry: ") + e.what()); }
+  catch (...) { rc = set_err(DCRX_E_NOMEM, "host-buffer entry: unexpected exception"); }
+  if (rc != DCRX_OK) {
+    const std::string keep = g_err;       // (the synchronising calls must not replace the message of what failed)
+    for (uint32_t c = 0; c < nc; c++) {
+      dcrx_tables *t = T[c];
+      if (t->hs_in) (void)hipStreamSynchronize(t->hs_in);
+      if (t->hs_run) (void)hipStreamSynchronize(t->hs_run);
+      if (t->hs_out) (void)hipStreamSynchronize(t->hs_out);
+      t->ws_dirty = true;
+    }
+    (void)hipGetLastError();
+    g_err = keep;
+  }
+  for (uint32_t c = 0; c < nc; c++) T[c]->sink_on = sink_was_on[c];
+  return rc;
+}
+
+extern "C" {
+
+int dcrx_decombine(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_record_t *records,
+                   uint64_t *counters) {
+  if (!t || !cfg || !counters) return set_err(DCRX_E_INVALID, "null argument");
+  return host_entry(&t, 1, cfg, hb, &records, &counters, nullptr, 0, nullptr);
+}
+
+int dcrx_decombine_count(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_batch_t *hb, dcrx_counts_t *counts,
+                         uint64_t first_index, const uint32_t *index, uint64_t *counters) {
+  if (!counts) return set_err(DCRX_E_INVALID, "counts is null");
+  if (!t || !cfg || !counters) return set_err(DCRX_E_INVALID, "null argument");
+  return host_entry(&t, 1, cfg, hb, nullptr, &counters, &counts, first_index, index);
+}
+
+int dcrx_decombine_chains(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                          const dcrx_batch_t *hb, dcrx_record_t *const *records, uint64_t *const *counters) {
+  if (!records) return set_err(DCRX_E_INVALID, "null argument");
+  return host_entry(tables, n_chains, cfg, hb, records, counters, nullptr, 0, nullptr);
+}
+
+int dcrx_decombine_chains_count(dcrx_tables_t *const *tables, uint32_t n_chains, const dcrx_cfg_t *cfg,
+                                const dcrx_batch_t *hb, dcrx_counts_t *const *counts, uint64_t first_index,
+                                const uint32_t *index, uint64_t *const *counters) {
+  if (!counts) return set_err(DCRX_E_INVALID, "null argument");
+  return host_entry(tables, n_chains, cfg, hb, nullptr, counters, counts, first_index, index);
+}
+
+}  // extern "C"
 
 // tile counts and offsets of a compaction: a process-wide slot keyed by device (compaction does not need tables)
 static int compact_workspace(uint64_t n_reads, uint32_t **tc, uint64_t **to) {

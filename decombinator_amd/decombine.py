@@ -676,7 +676,6 @@ def _decombinator_setup(inputargs: dict, rank: int, world: int, state: dict) -> 
     print("Running Decombinator (MI355X / HIP build) version", __version__)
     ch = _chain_setup(inputargs, rank)
     _input_checks(inputargs, rank, [ch])
-    state.update({k: ch[k] for k in ("tcr", "chain", "samplenam", "summaryname", "logpath", "date")})
     state["chains"] = [ch]
 
 
@@ -686,6 +685,50 @@ def _device_call(tables: list, batch, inputargs: dict) -> list:
     if len(tables) == 1:
         return [nat.decombine(tables[0], batch, *args)]
     return nat.decombine_chains(tables, batch, *args)
+
+
+def _batch_to_device(inputargs: dict, cnts: list, max_read_len: int, text, start, length, call):
+    """What both read loops do with a batch of reads (the spans start/length of text) once it is read: the read count and
+    its progress line, the length check, and the reads packed and handed to the device by call(packed batch, idx) -> per
+    chain (records or None, counters), idx being the places in the batch of the reads it holds (None: all of them).
+    Returns (call's results for the whole batch, the time the progress line was done, the seconds spent packing).
+
+    Reads of up to 511 nt run on the register shapes; longer ones (merged pairs, long amplicons: the reference has no
+    length limit, decombine.py:228-265, :534-585) leave the batch for a call of their own — one read per lane from memory,
+    dcrx's long form — and come back into their places; beyond 65 535 nt (the 16-bit lengths and offsets of the record)
+    nothing decombines them: said before anything of the batch is processed."""
+    n = len(start)
+    before = cnts[0]["read_count"]
+    for c in cnts:
+        c["read_count"] += n
+    if inputargs["dontcount"] == False and cnts[0]["read_count"] // 100000 > before // 100000:  # noqa: E712
+        print("\t read", (cnts[0]["read_count"] // 100000) * 100000)
+    t1 = time()
+    longest = int(length.max()) if n else 0
+    if longest > max_read_len:
+        raise ValueError(f"a read of {longest} nt exceeds the {max_read_len} nt this build decombines "
+                         f"(dcrx_tables_info.max_read_len); trim or split the reads")
+    if longest <= nat.FAST_MAX_READ_LEN:
+        batch = nat.pack_reads_span(text, start, length)
+        tp = time() - t1
+        return call(batch, None), t1, tp
+    is_long = length > nat.FAST_MAX_READ_LEN
+    res, tp = None, 0.0
+    for idx in (np.nonzero(~is_long)[0], np.nonzero(is_long)[0]):
+        if len(idx) == 0:
+            continue
+        ta = time()
+        batch = nat.pack_reads_span(text, start[idx], length[idx])
+        tp += time() - ta
+        part = call(batch, idx)
+        if res is None:
+            res = [(None if r is None else np.empty(n, dtype=nat.RECORD_DTYPE), np.zeros(nat.N_COUNTERS, dtype=np.uint64))
+                   for r, _ in part]
+        for (rec, cnt), (r_part, c_part) in zip(res, part):
+            if rec is not None:
+                rec[idx] = r_part
+            cnt += c_part.astype(np.uint64)
+    return res, t1, tp
 
 
 def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan_shards=None) -> None:
@@ -737,42 +780,12 @@ def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan
                     continue
                 for od in outdatas:
                     od._tag = rank if ranges is not None else batch_index
-                n = len(spans.v_start)
                 if inputargs["allowNs"] == False:  # noqa: E712    counted, never dropped (:985-989)
                     bc_n = nat.count_prefix_byte(spans.bc_text, spans.bc_start, spans.bc_len, 1 << 30, "N")
                     for c in cnts:
                         c["dcrfilter_barcodeN"] += bc_n
-                before = cnts[0]["read_count"]
-                for c in cnts:
-                    c["read_count"] += n
-                if inputargs["dontcount"] == False and cnts[0]["read_count"] // 100000 > before // 100000:  # noqa: E712
-                    print("\t read", (cnts[0]["read_count"] // 100000) * 100000)
-                t1 = time()
-                # reads of up to 511 nt run on the register shapes; longer ones (merged pairs, long amplicons: the reference has no
-                # length limit, decombine.py:228-265, :534-585) leave the batch for a call of their own — one read per lane from
-                # memory, dcrx's long form — and come back into their places; beyond 65 535 nt (the 16-bit lengths and offsets of
-                # the record) nothing decombines them: said before anything of the batch is processed
-                longest = int(spans.v_len.max()) if n else 0
-                if longest > max_read_len:
-                    raise ValueError(f"a read of {longest} nt exceeds the {max_read_len} nt this build decombines "
-                                     f"(dcrx_tables_info.max_read_len); trim or split the reads")
-                t2 = t1
-                if longest > nat.FAST_MAX_READ_LEN:
-                    is_long = spans.v_len > nat.FAST_MAX_READ_LEN
-                    res = [(np.empty(n, dtype=nat.RECORD_DTYPE), np.zeros(nat.N_COUNTERS, dtype=np.uint64)) for _ in chains]
-                    for idx in (np.nonzero(~is_long)[0], np.nonzero(is_long)[0]):
-                        if len(idx) == 0:
-                            continue
-                        tp = time()
-                        batch = nat.pack_reads_span(spans.v_text, spans.v_start[idx], spans.v_len[idx])
-                        t2 += time() - tp
-                        for (rec, cnt), (r_part, c_part) in zip(res, _device_call(tables, batch, inputargs)):
-                            rec[idx] = r_part
-                            cnt += c_part.astype(np.uint64)
-                else:
-                    batch = nat.pack_reads_span(spans.v_text, spans.v_start, spans.v_len)
-                    t2 = time()
-                    res = _device_call(tables, batch, inputargs)
+                res, t1, tp = _batch_to_device(inputargs, cnts, max_read_len, spans.v_text, spans.v_start, spans.v_len,
+                                               lambda batch, idx: _device_call(tables, batch, inputargs))
                 t3 = time()
                 t4 = t3
                 for ch, (rec, cnt), od in zip(chains, res, outdatas):
@@ -782,7 +795,7 @@ def _decombinator_loop(inputargs: dict, rank: int, world: int, state: dict, plan
                     t4 = time()
                     if multi:
                         stage_seconds["rows:" + ch["chain"]] = stage_seconds.get("rows:" + ch["chain"], 0.0) + (t4 - ta)
-                for key, dt in (("read", t1 - t0), ("pack", t2 - t1), ("device", t3 - t2), ("rows", t4 - t3)):
+                for key, dt in (("read", t1 - t0), ("pack", tp), ("device", t3 - t1 - tp), ("rows", t4 - t3)):
                     stage_seconds[key] = stage_seconds.get(key, 0.0) + dt
                 if spans.last:
                     break
@@ -871,6 +884,11 @@ def _count_loop(inputargs: dict, chains: list, cnts: list, max_read_len: int) ->
     stage_info.update(sharded_input=False, byte_ranges=None, rank=0, world=1)
     rd = nat.FastqReader(inputargs["infile"], inputargs["infile"].endswith(".gz"))
     ordinal = 0
+
+    def count(batch, idx):      # (a part of a split batch passes its reads' places: each read keeps its ordinal)
+        idx = None if idx is None else idx.astype(np.uint32)
+        return [(None, cnt) for cnt in nat.count_dcrs(tables, batch, dcs, ordinal, idx, *args)]
+
     try:
         while True:
             t0 = time()
@@ -878,35 +896,9 @@ def _count_loop(inputargs: dict, chains: list, cnts: list, max_read_len: int) ->
             n = b.n
             if n == 0:
                 break
-            before = cnts[0]["read_count"]
-            for c in cnts:
-                c["read_count"] += n
-            if inputargs["dontcount"] == False and cnts[0]["read_count"] // 100000 > before // 100000:  # noqa: E712
-                print("\t read", (cnts[0]["read_count"] // 100000) * 100000)
-            longest = int(b.seq_len.max())
-            if longest > max_read_len:
-                raise ValueError(f"a read of {longest} nt exceeds the {max_read_len} nt this build decombines "
-                                 f"(dcrx_tables_info.max_read_len); trim or split the reads")
-            t1 = time()
-            tp = 0.0
-            if longest > nat.FAST_MAX_READ_LEN:
-                # (as in the barcoded loop: reads over 511 nt in a call of their own, each read keeping its ordinal)
-                is_long = b.seq_len > nat.FAST_MAX_READ_LEN
-                res = [np.zeros(nat.N_COUNTERS, dtype=np.uint64) for _ in chains]
-                for idx in (np.nonzero(~is_long)[0], np.nonzero(is_long)[0]):
-                    if len(idx) == 0:
-                        continue
-                    ta = time()
-                    batch = nat.pack_reads_span(b.text, b.seq_off[idx], b.seq_len[idx])
-                    tp += time() - ta
-                    for acc, part in zip(res, nat.count_dcrs(tables, batch, dcs, ordinal, idx.astype(np.uint32), *args)):
-                        acc += part.astype(np.uint64)
-            else:
-                batch = nat.pack_reads_span(b.text, b.seq_off, b.seq_len)
-                tp = time() - t1
-                res = nat.count_dcrs(tables, batch, dcs, ordinal, None, *args)
+            res, t1, tp = _batch_to_device(inputargs, cnts, max_read_len, b.text, b.seq_off, b.seq_len, count)
             t3 = time()
-            for ch, cnt in zip(chains, res):
+            for ch, (_, cnt) in zip(chains, res):
                 _add_counts(cnt, skip=("read_count",), into=ch["counts"])
             ordinal += n
             for key, dt in (("read", t1 - t0), ("pack", tp), ("device", t3 - t1 - tp)):
@@ -954,24 +946,28 @@ def decombinator(inputargs: dict, shard=None, reduce_counts=None, exchange_error
             err = e
         if exchange_error is not None:
             exchange_error(err)
-    outdata, chain, samplenam, summaryname, logpath, date = (state[k] for k in ("outdata", "chain", "samplenam", "summaryname", "logpath", "date"))
     if reduce_counts is not None:
         reduce_counts(counts)
     counts["end_time"] = time()
+    if rank == 0:
+        _chain_report(state["chains"][0], counts)
+    return state["outdata"]
+
+
+def _chain_report(ch: dict, counts) -> None:
+    """A chain's end of the stage (its `counts` hold end_time): the totals on stdout and, unless suppresssummary, the
+    summary log."""
+    args, chain, samplenam = ch["args"], ch["chain"], ch["samplenam"]
     timetaken = counts["end_time"] - counts["start_time"]
-    if rank != 0:
-        return outdata
     print("Analysed", "{:,}".format(counts["read_count"]), "reads, finding", "{:,}".format(counts["vj_count"]),
           chainnams[chain], "VJ rearrangements")
-    print("Reading from", inputargs["infile"] + ", writing to variable")
+    print("Reading from", args["infile"] + ", writing to variable")
     print("Took", str(round(timetaken, 2)), "seconds")
-
-    if inputargs["suppresssummary"] == False:  # noqa: E712
-        name, fh = _new_summary_file(summaryname, logpath, date, inputargs["chain"], chain, samplenam)
-        print(_summary_text(inputargs, chain, samplenam, date, timetaken), file=fh)
+    if args["suppresssummary"] == False:  # noqa: E712
+        name, fh = _new_summary_file(ch["summaryname"], ch["logpath"], ch["date"], args["chain"], chain, samplenam)
+        print(_summary_text(args, chain, samplenam, ch["date"], timetaken, counts), file=fh)
         fh.close()
         sort_permissions(name)
-    return outdata
 
 
 def decombinator_chains(inputargs: dict) -> dict:
@@ -987,7 +983,6 @@ def decombinator_chains(inputargs: dict) -> dict:
         raise ValueError("decombinator_chains needs a comma-separated list of chains in inputargs['chain'] (e.g. 'a,b')")
     resolve_chain_list(items)           # (refused before anything is read: an unknown item, a chain named twice)
     check_count_args(inputargs)
-    global counts
     print("Running Decombinator (MI355X / HIP build) version", __version__)
     chain_counts.clear()
     chain_args.clear()
@@ -1000,20 +995,7 @@ def decombinator_chains(inputargs: dict) -> dict:
         chains.append(ch)
     _input_checks(inputargs, 0, chains)
     _decombinator_loop(inputargs, 0, 1, {"chains": chains})
-    out = {}
     for ch in chains:
-        counts = ch["counts"]
-        args, chain, samplenam = ch["args"], ch["chain"], ch["samplenam"]
-        counts["end_time"] = time()
-        timetaken = counts["end_time"] - counts["start_time"]
-        print("Analysed", "{:,}".format(counts["read_count"]), "reads, finding", "{:,}".format(counts["vj_count"]),
-              chainnams[chain], "VJ rearrangements")
-        print("Reading from", args["infile"] + ", writing to variable")
-        print("Took", str(round(timetaken, 2)), "seconds")
-        if args["suppresssummary"] == False:  # noqa: E712
-            name, fh = _new_summary_file(ch["summaryname"], ch["logpath"], ch["date"], args["chain"], chain, samplenam)
-            print(_summary_text(args, chain, samplenam, ch["date"], timetaken, counts), file=fh)
-            fh.close()
-            sort_permissions(name)
-        out[chain] = ch["outdata"]
-    return out
+        ch["counts"]["end_time"] = time()
+        _chain_report(ch, ch["counts"])
+    return {ch["chain"]: ch["outdata"] for ch in chains}

@@ -240,15 +240,17 @@ int64_t dcrx_assemble_rows(const dcrx_record_t *records, uint64_t n_reads, const
 
 /* Host buffers in, host buffers out (H2D copy, kernels, D2H copy, synchronous).
  * records: n_reads entries; counters: DCRX_N_COUNTERS uint64, OVERWRITTEN with
- * this batch's tallies (the caller adds them into its Counter). */
+ * this batch's tallies (the caller adds them into its Counter).  The one-chain case of
+ * dcrx_decombine_chains (the same chunk pipeline): the same bytes as dcrx_decombine_chains(&tables, 1, ...). */
 int dcrx_decombine(dcrx_tables_t *tables, const dcrx_cfg_t *cfg, const dcrx_batch_t *host_batch,
                    dcrx_record_t *records, uint64_t *counters);
 
-/* Several chains of one library (alpha + beta, gamma + delta) over ONE host batch: dcrx_decombine's chunk pipeline with
- * one upload per chunk and n_chains resolutions of it.  Each chunk is copied in once, into the staging of tables[0];
- * each chain's launches run on that handle's own stream, with its own workspace, gated by an event on the copy in, and
- * the same stream copies the chain's records and counters out into records[c] (n_reads entries) and counters[c]
- * (DCRX_N_COUNTERS uint64, OVERWRITTEN).  An input staging set is refilled only once every chain's scan of it is over.
+/* Several chains of one library (alpha + beta, gamma + delta) over ONE host batch: the host-buffer chunk pipeline with
+ * one upload per chunk and n_chains resolutions of it (dcrx_decombine is its one-chain case).  Each chunk is copied in
+ * once, into the staging of tables[0]; each chain's launches run on that handle's own stream, with its own workspace,
+ * gated by an event on the copy in, and with several chains the same stream copies the chain's records and counters
+ * out (one chain: the handle's copy-out stream) into records[c] (n_reads entries) and counters[c] (DCRX_N_COUNTERS
+ * uint64, OVERWRITTEN).  An input staging set is refilled only once every chain's scan of it is over.
  * records[c] and counters[c] equal what dcrx_decombine(tables[c], ...) gives on the same batch, byte for byte.
  * Pinned caller buffers skip the staging copies as in dcrx_decombine; the tuple sink is off for the call on every
  * handle.  DCRX_E_INVALID for n_chains of 0 or above DCRX_MAX_CHAINS, a null pointer, or the same handle twice (the
@@ -306,7 +308,8 @@ int dcrx_count_device(dcrx_counts_t *counts, const dcrx_record_t *d_records, con
 
 /* dcrx_decombine with the count step on each chunk, on the same stream as the chunk's kernels: the records stay on the
  * device, only the counters (DCRX_N_COUNTERS uint64, OVERWRITTEN) come back.  Ordinals as in dcrx_count_device, with
- * `index` a host array of n_reads entries (or NULL).  Synchronous. */
+ * `index` a host array of n_reads entries (or NULL).  Synchronous.  The one-chain case of dcrx_decombine_chains_count:
+ * the same bytes as dcrx_decombine_chains_count(&tables, 1, ...). */
 int dcrx_decombine_count(dcrx_tables_t *tables, const dcrx_cfg_t *cfg, const dcrx_batch_t *host_batch,
                          dcrx_counts_t *counts, uint64_t first_index, const uint32_t *index, uint64_t *counters);
 
