@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DCRX_LIB_PATH") or os.path.join(_HERE, "csrc", "libdcrx.so")
 
 N_COUNTERS = 32
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # enum dcrx_counter order; the strings are the reference's Counter keys
 # (reference decombine.py:598 and the increments cited in include/dcrx_codes.h)
@@ -381,6 +381,15 @@ class SynthCfgC(C.Structure):
                 ("sub_rate", C.c_float), ("n_rate", C.c_float)]
 
 
+MERGE_ANCHOR = 32            # DCRX_MERGE_ANCHOR
+MERGE_MAX_JUNCTION = 128     # DCRX_MERGE_MAX_JUNCTION
+MERGE_STATS = ("entries_in", "roots_out", "out_of_reach", "merged", "reads_moved", "longest_chain")
+
+
+class MergeStatsC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in MERGE_STATS]
+
+
 # every symbol include/dcrx.h and include/dcrx_synth.h declare
 EXPORTS = [
     "dcrx_umi_encode", "dcrx_umi_neighbours_device", "dcrx_umi_neighbours", "dcrx_collapse_group",
@@ -400,6 +409,7 @@ EXPORTS = [
     "dcrx_stream_wait_event", "dcrx_memcpy_d2h_async", "dcrx_memcpy_d2d_async", "dcrx_memset_device_async",
     "dcrx_counts_create", "dcrx_counts_destroy", "dcrx_counts_reset", "dcrx_counts_set_hash_bits", "dcrx_count_device", "dcrx_decombine_count",
     "dcrx_decombine_chains_count", "dcrx_counts_read", "dcrx_format_counts",
+    "dcrx_merge_work_bytes", "dcrx_merge_parents_device", "dcrx_merge_dcrs", "dcrx_merge_gather",
 ]
 
 _lib = None
@@ -520,6 +530,10 @@ def lib():
         "dcrx_decombine_chains_count": (i32, [vp, u32, C.POINTER(CfgC), C.POINTER(BatchC), vp, u64, vp, vp]),
         "dcrx_counts_read": (C.c_int64, [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u64, C.POINTER(u64)]),
         "dcrx_format_counts": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, vp, C.c_char_p, vp, u64]),
+        "dcrx_merge_gather": (C.c_int64, [u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dcrx_merge_work_bytes": (u64, [u64]),
+        "dcrx_merge_parents_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, u64, vp]),
+        "dcrx_merge_dcrs": (C.c_int64, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, C.POINTER(MergeStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1073,6 +1087,51 @@ def format_counts(counted: dict, field_sep: str = ", ") -> bytes:
     if got > bound:
         raise DcrxError(-1, f"dcrx_format_counts needs {got} bytes, more than the {bound} bound")
     return out[:got]
+
+
+def merged_counts(counted: dict, order, count, first) -> dict:
+    """dcrx_merge_gather: the table of the roots — entry m is input entry order[m] with the tree's count[m] and first[m] (the
+    dict of arrays DcrCounts.read() gives, so NbcRows and format_counts take it as they take a counted table)."""
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    n, m = len(counted["v"]), len(order)
+    src = [np.ascontiguousarray(counted[k], dtype=t) for k, t in (("v", np.uint16), ("j", np.uint16), ("vdel", np.uint8),
+                                                                   ("jdel", np.uint8), ("ins_off", np.uint64))]
+    text = np.frombuffer(counted["ins_text"], np.uint8) if counted["ins_text"] else np.zeros(1, np.uint8)
+    out = {"v": np.zeros(m, np.uint16), "j": np.zeros(m, np.uint16), "vdel": np.zeros(m, np.uint8), "jdel": np.zeros(m, np.uint8),
+           "count": np.array(count, np.uint64), "first": np.array(first, np.uint64), "ins_off": np.zeros(m + 1, np.uint64)}
+    new_text = np.zeros(max(1, len(counted["ins_text"])), np.uint8)
+    got = check(int(lib().dcrx_merge_gather(n, m, order.ctypes.data, *[a.ctypes.data for a in src], text.ctypes.data,
+                                            *[out[k].ctypes.data for k in ("v", "j", "vdel", "jdel", "ins_off")],
+                                            new_text.ctypes.data)))
+    out["ins_text"] = new_text[:got].tobytes()
+    return out
+
+
+def merge_dcrs(tables: "Tables", counted: dict, distance: int = 1, ratio: int = 10):
+    """dcrx_merge_dcrs on the current device: the counted table (what DcrCounts.read() gives) with every erroneous DCR folded
+    into its root — (merged table, statistics dict over MERGE_STATS, root_of: the rank of every input entry's root)."""
+    n = len(counted["v"])
+    arrs = [np.ascontiguousarray(counted[k], dtype=t) for k, t in (("v", np.uint16), ("j", np.uint16), ("vdel", np.uint8),
+                                                                    ("jdel", np.uint8), ("count", np.uint64), ("first", np.uint64),
+                                                                    ("ins_off", np.uint64))]
+    text = np.frombuffer(counted["ins_text"], np.uint8) if counted["ins_text"] else np.zeros(1, np.uint8)
+    root_of, order = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    cnt, fst = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    st = MergeStatsC()
+    m = check(int(lib().dcrx_merge_dcrs(tables.handle, n, *[a.ctypes.data for a in arrs], text.ctypes.data, int(distance),
+                                        int(ratio), root_of.ctypes.data, order.ctypes.data, cnt.ctypes.data, fst.ctypes.data,
+                                        C.byref(st))))
+    stats = {k: int(getattr(st, k)) for k in MERGE_STATS}
+    return merged_counts(counted, order[:m], cnt[:m], fst[:m]), stats, root_of
+
+
+def merge_parents_device(tables: "Tables", n: int, d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, d_ins_text, text_bytes: int,
+                         distance: int, ratio: int, d_parent, d_reach, d_work, work_bytes: int, stream=None):
+    """dcrx_merge_parents_device: parent(c) of every entry of a counted table in HBM (DeviceBuffers), asynchronous on `stream`."""
+    check(lib().dcrx_merge_parents_device(tables.handle, int(n), d_v.ptr, d_j.ptr, d_vdel.ptr, d_jdel.ptr, d_count.ptr, d_ins_off.ptr,
+                                          d_ins_text.ptr if d_ins_text is not None else None, int(text_bytes), int(distance),
+                                          int(ratio), d_parent.ptr, d_reach.ptr if d_reach is not None else None, d_work.ptr,
+                                          int(work_bytes), stream))
 
 
 def _index_arg(index, n):

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <thread>
 
+#include "dcrx_merge_core.h"
 #include "dcrx_tables.h"
 
 namespace dcrx {
@@ -29,6 +30,7 @@ hipError_t launch_synth(const DevTables &T, const SynthParams &P, uint64_t first
 int count_chunk(dcrx_counts_t *c, const dcrx_record_t *d_records, const dcrx_batch_t *d_batch, uint64_t first_index,
                 const uint32_t *h_index, hipStream_t s);
 int count_settle(dcrx_counts_t *c, hipStream_t s);
+int merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v, uint32_t *n_j);
 }
 
 using namespace dcrx;
@@ -112,6 +114,9 @@ struct dcrx_tables {
   V2SinkDev *d_sink = nullptr;
   void *d_sink_items = nullptr; uint32_t *d_sink_ctr = nullptr;
   uint64_t sink_items_cap = 0; uint32_t sink_regions_cap = 0;
+  // the error merge's germline windows (dcrx_merge_core.h), on the device they were last asked for
+  uint32_t *d_merge_rows = nullptr;
+  int merge_device = -1;
 };
 
 static int layout_dev(dcrx_tables *t, const dcrx_tuple_layout_t *L, TupleLayoutDev *D);
@@ -162,6 +167,38 @@ static void free_device_state(dcrx_tables *t) {
   t->exc_flag_reads = 0; t->stage_bytes = 0; t->device = -1; t->constants_ready = false;
 }
 
+static void free_merge_rows(dcrx_tables *t) {
+  if (t->merge_device < 0) return;
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess) {
+    if (cur != t->merge_device) (void)hipSetDevice(t->merge_device);
+    (void)hipFree(t->d_merge_rows);
+    if (cur != t->merge_device && cur >= 0) (void)hipSetDevice(cur);
+  }
+  t->d_merge_rows = nullptr; t->merge_device = -1;
+}
+
+// dcrx_merge.hip: one window row per gene (V rows, then J rows) out of the handle's regions, on the current device
+int dcrx::merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v, uint32_t *n_j) {
+  int dev = -1;
+  HIP_TRY(hipGetDevice(&dev));
+  if (t->merge_device != dev) {
+    free_merge_rows(t);
+    const uint32_t nv = t->host.g[0].n, nj = t->host.g[1].n;
+    std::vector<uint32_t> rows((size_t)(nv + nj) * dcrx_merge::WIN_WORDS + 1, 0u);
+    for (int g = 0; g < 2; g++)
+      for (uint32_t k = 0; k < t->host.g[g].n; k++) {
+        const std::string &r = t->host.g[g].regions[k];
+        dcrx_merge::make_window(r.data(), (uint32_t)r.size(), g == 0, rows.data() + (size_t)((g ? nv : 0) + k) * dcrx_merge::WIN_WORDS);
+      }
+    HIP_TRY(hipMalloc(&t->d_merge_rows, rows.size() * sizeof(uint32_t)));
+    t->merge_device = dev;
+    HIP_TRY(hipMemcpy(t->d_merge_rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  *d_rows = t->d_merge_rows; *n_v = t->host.g[0].n; *n_j = t->host.g[1].n;
+  return DCRX_OK;
+}
+
 extern "C" {
 
 int dcrx_abi_version(void) { return DCRX_ABI_VERSION; }
@@ -184,6 +221,7 @@ int dcrx_tables_create(const dcrx_tagset_t *tagset, dcrx_tables_t **out) {
 
 void dcrx_tables_destroy(dcrx_tables_t *t) {
   if (!t) return;
+  free_merge_rows(t);
   if (t->device >= 0) {
     int cur = -1;
     if (hipGetDevice(&cur) == hipSuccess) {

@@ -1,0 +1,474 @@
+// dcrx_merge.hip — the error merge of the barcode-free count (`decombine -nbc --count-dcrs --merge-errors`): every counted
+// DCR whose junction (dcrx_merge_core.h) lies within D substitutions of a DCR of the same (v, j, length) that is at least R
+// times as abundant is folded into it; include/dcrx.h holds the contract.
+//
+// The primitive (dcrx_merge_parents_device), all on the caller's stream and in the caller's work space:
+//   keys     one lane per entry: the junction's length and reach flag, hence the bucket key (v, j, length); entries out of
+//            reach get a key behind every bucket
+//   sort     the keys with the entries' ranks (hipCUB radix sort, 41 bits; stable: a bucket stays in rank order, which is
+//            count descending)
+//   gather   one lane per sorted position: the junction's eight dwords and the count next to each other in sorted order,
+//            and a flag where a bucket starts (a max scan then gives every position its bucket's start)
+//   parents  one lane per child.  Its eligible parents by ratio are a PREFIX of its bucket (the bucket is in count order),
+//            and the parent wanted is the first hit there.  A block of BLOCK consecutive children walks the sorted entries
+//            from its first child's bucket start upwards in tiles of TILE: the tile's junctions and counts go to LDS, and
+//            every lane reads the same staged entry at the same time (one broadcast read per dword, no bank conflicts),
+//            XORs its own eight dwords held in registers against it and counts the mismatches, giving up after four
+//            dwords once the limit is passed.  A lane drops out at its first hit, at the first staged count below
+//            R * its own, or when the walk reaches the lane itself; a wave leaves a tile, and the block the walk, once all
+//            lanes have.  Every child writes its own parent: no atomics.
+// The host entry (dcrx_merge_dcrs) adds: pointer jumping to the roots (with the depth of every entry), the trees' totals
+// (integer atomicAdd / atomicMin onto the roots, results unused), and the roots compacted in rank order (exclusive scan)
+// and ordered by the two stable radix sorts of the count's read-out.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dcrx.h"
+#include "dcrx_merge_core.h"
+
+namespace dcrx {
+int set_err(int code, const char *msg);
+// dcrx_api.cpp: the handle's window rows (n_v rows for V, then n_j for J) on the current device
+int merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v, uint32_t *n_j);
+}
+using dcrx::set_err;
+using namespace dcrx_merge;
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int TILE = 256;        // staged entries per step: 8 KB of junctions + 2 KB of counts
+constexpr uint64_t ALIGN = 256;
+
+#define HIP_TRY(call)                                                           \
+  do {                                                                          \
+    hipError_t e_ = (call);                                                     \
+    if (e_ != hipSuccess) return hip_fail(e_, #call);                           \
+  } while (0)
+
+int hip_fail(hipError_t e, const char *what) {
+  std::string m = std::string("merge: ") + what + ": " + hipGetErrorString(e);
+  return set_err((e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? DCRX_E_NOGPU : DCRX_E_HIP, m.c_str());
+}
+
+inline unsigned grid_for(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+inline uint64_t aligned(uint64_t bytes) { return (bytes + ALIGN - 1) & ~(ALIGN - 1); }
+
+struct Entries {
+  const uint16_t *v, *j;
+  const uint8_t *vdel, *jdel;
+  const uint64_t *count, *ins_off;
+  const uint8_t *ins_text;
+  uint64_t text_bytes;
+  const uint32_t *rows;
+  uint32_t n_v, n_j;
+};
+
+// the junction of entry e (false and zeroes when it is out of reach)
+__device__ __forceinline__ bool encode_entry(const Entries &E, uint32_t e, uint32_t *out, uint32_t *length) {
+  const uint32_t v = E.v[e], j = E.j[e];
+  const uint64_t a = E.ins_off[e], b = E.ins_off[e + 1];
+  if (v >= E.n_v || j >= E.n_j || b < a || b > E.text_bytes) {
+    for (uint32_t w = 0; w < WORDS; w++) out[w] = 0;
+    *length = 0;
+    return false;
+  }
+  return encode(E.rows + (size_t)v * WIN_WORDS, E.rows + (size_t)(E.n_v + j) * WIN_WORDS, E.vdel[e], E.jdel[e], E.ins_text + a,
+                b - a, out, length);
+}
+
+__global__ __launch_bounds__(BLOCK) void merge_keys_kernel(Entries E, uint32_t n, uint64_t *__restrict__ key,
+                                                           uint32_t *__restrict__ idx) {
+  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= n) return;
+  uint32_t words[WORDS], length;
+  const bool reach = encode_entry(E, e, words, &length);
+  key[e] = reach ? bucket_key(E.v[e], E.j[e], length) : KEY_OUT_OF_REACH;
+  idx[e] = e;
+}
+
+__global__ __launch_bounds__(BLOCK) void merge_gather_kernel(Entries E, uint32_t n, const uint64_t *__restrict__ key,
+                                                             const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
+                                                             uint64_t *__restrict__ sc, uint32_t *__restrict__ head) {
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= n) return;
+  const uint32_t e = idx[s];
+  uint32_t w[WORDS], length;
+  encode_entry(E, e, w, &length);
+  sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
+  sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+  sc[s] = E.count[e];
+  head[s] = (s == 0 || key[s] != key[s - 1]) ? s : 0u;
+}
+
+__global__ __launch_bounds__(BLOCK) void merge_parents_kernel(const uint4 *__restrict__ sj, const uint64_t *__restrict__ sc,
+                                                              const uint64_t *__restrict__ key, const uint32_t *__restrict__ idx,
+                                                              const uint32_t *__restrict__ bstart, uint32_t n, uint32_t limit,
+                                                              uint64_t ratio, uint32_t *__restrict__ parent,
+                                                              uint8_t *__restrict__ reach_out) {
+  __shared__ uint4 lds_j[TILE * 2];
+  __shared__ uint64_t lds_c[TILE];
+  const uint32_t s0 = blockIdx.x * BLOCK;
+  const uint32_t s = s0 + threadIdx.x;
+  const bool valid = s < n;
+  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t start = s, found = s;
+  uint64_t need = 0;
+  bool done = true, reach = false;
+  if (valid) {
+    reach = key[s] != KEY_OUT_OF_REACH;
+    start = bstart[s];
+    // nothing to search: out of reach, first of its bucket, or even the bucket's largest count is below R * own
+    if (reach && start < s && needed_count(sc[s], ratio, &need) && sc[start] >= need) {
+      done = false;
+      const uint4 a = sj[2 * (size_t)s], b = sj[2 * (size_t)s + 1];
+      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
+    }
+  }
+  const uint32_t lo = bstart[s0];                           // (bstart never falls along s: the block's smallest)
+  const uint32_t hi = min(n, s0 + (uint32_t)BLOCK);         // a parent stands before its child
+  for (uint32_t t = lo; t < hi; t += TILE) {
+    if (!__syncthreads_or(!done)) break;                    // (also: the previous tile is no longer read)
+    const uint32_t tile_n = min((uint32_t)TILE, hi - t);
+    if (threadIdx.x < tile_n) {
+      const uint32_t p = t + threadIdx.x;
+      lds_j[2 * threadIdx.x] = sj[2 * (size_t)p];
+      lds_j[2 * threadIdx.x + 1] = sj[2 * (size_t)p + 1];
+      lds_c[threadIdx.x] = sc[p];
+    }
+    __syncthreads();
+    const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
+    for (uint32_t q = 0; q < tile_n; q++) {
+      const uint32_t p = t + q;
+      if (!done && p >= start) {
+        if (p >= s || lds_c[q] < need) done = true;         // the walk reached the child, or its prefix has ended
+        else if (distance(own, lj + q * WORDS, limit) <= limit) { found = p; done = true; }
+      }
+      if ((q & 7u) == 7u && !__ballot(!done)) break;        // the whole wave has dropped out
+    }
+  }
+  if (valid) {
+    const uint32_t e = idx[s];
+    parent[e] = found == s ? e : idx[found];
+    if (reach_out) reach_out[e] = reach ? 1 : 0;
+  }
+}
+
+// ---- roots, totals, order (the host entry) ----
+
+__global__ __launch_bounds__(BLOCK) void merge_depth_init_kernel(const uint32_t *__restrict__ parent, uint32_t n,
+                                                                 uint32_t *__restrict__ depth) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < n) depth[i] = parent[i] != i ? 1u : 0u;
+}
+
+// one round of pointer jumping: every entry's pointer moves to its pointer's pointer, its depth grows by that entry's
+__global__ __launch_bounds__(BLOCK) void merge_jump_kernel(const uint32_t *__restrict__ r_in, const uint32_t *__restrict__ d_in,
+                                                           uint32_t n, uint32_t *__restrict__ r_out, uint32_t *__restrict__ d_out,
+                                                           uint32_t *__restrict__ changed) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  bool moved = false;
+  if (i < n) {
+    const uint32_t r = r_in[i], rr = r_in[r];
+    r_out[i] = rr;
+    d_out[i] = d_in[i] + (rr != r ? d_in[r] : 0u);
+    moved = rr != r;
+  }
+  if (__ballot(moved) && __lane_id() == 0) *changed = 1u;
+}
+
+enum { MS_OUT_OF_REACH = 0, MS_MERGED = 1, MS_MOVED = 2, MS_CHAIN = 3, MS_WORDS = 4 };
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
+#pragma unroll
+  for (int d = warpSize / 2; d > 0; d >>= 1) x += __shfl_down(x, d);
+  return x;
+}
+
+__global__ __launch_bounds__(BLOCK) void merge_totals_kernel(const uint32_t *__restrict__ root, const uint32_t *__restrict__ depth,
+                                                             const uint8_t *__restrict__ reach, const uint64_t *__restrict__ count,
+                                                             const uint64_t *__restrict__ first, uint32_t n,
+                                                             unsigned long long *__restrict__ tot_count,
+                                                             unsigned long long *__restrict__ tot_first,
+                                                             uint32_t *__restrict__ is_root, unsigned long long *__restrict__ stats) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  unsigned long long oor = 0, merged = 0, moved = 0, chain = 0;
+  if (i < n) {
+    const uint32_t r = root[i];
+    is_root[i] = r == i ? 1u : 0u;
+    oor = reach[i] ? 0 : 1;
+    chain = depth[i];
+    if (r != i) {
+      merged = 1;
+      moved = count[i];
+      atomicAdd(&tot_count[r], (unsigned long long)count[i]);
+      atomicMin(&tot_first[r], (unsigned long long)first[i]);
+    }
+  }
+#pragma unroll
+  for (int d = warpSize / 2; d > 0; d >>= 1) chain = max(chain, (unsigned long long)__shfl_down(chain, d));
+  oor = wave_sum(oor); merged = wave_sum(merged); moved = wave_sum(moved);
+  if (__lane_id() == 0) {
+    if (oor) atomicAdd(&stats[MS_OUT_OF_REACH], oor);
+    if (merged) atomicAdd(&stats[MS_MERGED], merged);
+    if (moved) atomicAdd(&stats[MS_MOVED], moved);
+    if (chain) atomicMax(&stats[MS_CHAIN], chain);
+  }
+}
+
+__global__ __launch_bounds__(BLOCK) void merge_list_kernel(const uint32_t *__restrict__ is_root, const uint32_t *__restrict__ slot,
+                                                           uint32_t n, uint32_t *__restrict__ list) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < n && is_root[i]) list[slot[i]] = i;
+}
+
+__global__ __launch_bounds__(BLOCK) void merge_pick_kernel(const unsigned long long *__restrict__ src, const uint32_t *__restrict__ list,
+                                                           uint32_t m, int negate, uint64_t *__restrict__ dst) {
+  const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+  if (k >= m) return;
+  const uint64_t x = src[list[k]];
+  dst[k] = negate ? ~x : x;
+}
+
+struct WorkPlan {
+  uint64_t key[2], idx[2], sj, sc, head, bstart, cub, cub_bytes, total;
+};
+
+int plan_work(uint64_t n, WorkPlan *W) {
+  // (the largest of the primitive's sort and scan and of the host entry's scan and 64-bit sorts, which reuse the space)
+  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0, sort64_bytes = 0;
+  const int wn = (int)std::max<uint64_t>(n, 1);
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                             (uint32_t *)nullptr, wn, 0, (int)KEY_BITS));
+  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), wn));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, wn));
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort64_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                             (uint32_t *)nullptr, wn, 0, 64));
+  uint64_t at = 0;
+  auto take = [&](uint64_t bytes) { const uint64_t here = at; at += aligned(std::max<uint64_t>(bytes, 1)); return here; };
+  W->key[0] = take(n * 8); W->key[1] = take(n * 8);
+  W->idx[0] = take(n * 4); W->idx[1] = take(n * 4);
+  W->sj = take(n * WORDS * 4); W->sc = take(n * 8);
+  W->head = take(n * 4); W->bstart = take(n * 4);
+  W->cub_bytes = std::max(std::max(sort_bytes, scan_bytes), std::max(sum_bytes, sort64_bytes));
+  W->cub = take(W->cub_bytes);
+  W->total = at;
+  return DCRX_OK;
+}
+
+// device memory of one call of the host entry: ONE allocation, carved into 256-byte aligned buffers (a first pass over the
+// same requests, with no memory behind it, adds up the size)
+struct Pool {
+  uint8_t *base = nullptr;
+  uint64_t at = 0;
+  ~Pool() { (void)hipFree(base); }
+  template <class T> void get(T **p, uint64_t count) {
+    *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+    at += aligned(std::max<uint64_t>(count, 1) * sizeof(T));
+  }
+  int allocate() {
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&base), std::max<uint64_t>(at, 1)));
+    at = 0;
+    return DCRX_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+uint64_t dcrx_merge_work_bytes(uint64_t n) {
+  WorkPlan W;
+  if (n >= (1ull << 31) || plan_work(n, &W) != DCRX_OK) return 0;
+  return W.total;
+}
+
+int dcrx_merge_parents_device(dcrx_tables_t *tables, uint64_t n, const uint16_t *d_v, const uint16_t *d_j,
+                              const uint8_t *d_vdel, const uint8_t *d_jdel, const uint64_t *d_count,
+                              const uint64_t *d_ins_off, const char *d_ins_text, uint64_t text_bytes, uint32_t distance,
+                              uint64_t ratio, uint32_t *d_parent, uint8_t *d_reach, void *d_work, uint64_t work_bytes,
+                              void *hip_stream) {
+  if (!tables) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: tables is null");
+  if (distance < 1 || distance > 2) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the distance is 1 or 2");
+  if (ratio < 1) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the ratio is an integer >= 1");
+  if (n >= (1ull << 31)) return set_err(DCRX_E_UNSUPPORTED, "dcrx_merge_parents_device: 2^31 or more entries");
+  if (!n) return DCRX_OK;
+  if (!d_v || !d_j || !d_vdel || !d_jdel || !d_count || !d_ins_off || !d_parent || !d_work || (text_bytes && !d_ins_text))
+    return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: null argument");
+  if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is not 256-byte aligned");
+  WorkPlan W;
+  int rc = plan_work(n, &W);
+  if (rc) return rc;
+  if (work_bytes < W.total) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is smaller than dcrx_merge_work_bytes(n)");
+  Entries E{d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, reinterpret_cast<const uint8_t *>(d_ins_text), text_bytes, nullptr, 0, 0};
+  rc = dcrx::merge_windows(tables, &E.rows, &E.n_v, &E.n_j);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  uint8_t *w = static_cast<uint8_t *>(d_work);
+  uint64_t *key[2] = {reinterpret_cast<uint64_t *>(w + W.key[0]), reinterpret_cast<uint64_t *>(w + W.key[1])};
+  uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(w + W.idx[0]), reinterpret_cast<uint32_t *>(w + W.idx[1])};
+  uint4 *sj = reinterpret_cast<uint4 *>(w + W.sj);
+  uint64_t *sc = reinterpret_cast<uint64_t *>(w + W.sc);
+  uint32_t *head = reinterpret_cast<uint32_t *>(w + W.head), *bstart = reinterpret_cast<uint32_t *>(w + W.bstart);
+  const uint32_t n32 = (uint32_t)n;
+  merge_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, key[0], idx[0]);
+  HIP_TRY(hipGetLastError());
+  size_t tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(w + W.cub, tb, key[0], key[1], idx[0], idx[1], (int)n, 0, (int)KEY_BITS, s));
+  merge_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, key[1], idx[1], sj, sc, head);
+  HIP_TRY(hipGetLastError());
+  tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceScan::InclusiveScan(w + W.cub, tb, head, bstart, hipcub::Max(), (int)n, s));
+  merge_parents_kernel<<<grid_for(n), BLOCK, 0, s>>>(sj, sc, key[1], idx[1], bstart, n32, distance, ratio, d_parent, d_reach);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
+int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, const uint16_t *j, const uint8_t *vdel,
+                        const uint8_t *jdel, const uint64_t *count, const uint64_t *first, const uint64_t *ins_off,
+                        const char *ins_text, uint32_t distance, uint64_t ratio, uint32_t *root_of_out,
+                        uint32_t *order_out, uint64_t *count_out, uint64_t *first_out, dcrx_merge_stats_t *stats_out) {
+  if (!tables) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: tables is null");
+  if (distance < 1 || distance > 2) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: the distance is 1 or 2");
+  if (ratio < 1) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: the ratio is an integer >= 1");
+  if (n >= (1ull << 31)) return set_err(DCRX_E_UNSUPPORTED, "dcrx_merge_dcrs: 2^31 or more entries");
+  if (stats_out) { *stats_out = dcrx_merge_stats_t{}; stats_out->entries_in = n; }
+  if (!n) return 0;
+  if (!v || !j || !vdel || !jdel || !count || !first || !ins_off || !root_of_out || !order_out || !count_out || !first_out)
+    return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: null argument");
+  const uint32_t *rows = nullptr;
+  uint32_t n_v = 0, n_j = 0;
+  int rc = dcrx::merge_windows(tables, &rows, &n_v, &n_j);
+  if (rc) return rc;
+  for (uint64_t k = 0; k < n; k++) {
+    if (v[k] >= n_v || j[k] >= n_j) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: an entry names a v or j the tables do not have");
+    if (ins_off[k + 1] < ins_off[k]) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: offsets go backwards");
+  }
+  const uint64_t text0 = ins_off[0], text_bytes = ins_off[n] - text0;
+  if (text_bytes && !ins_text) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: ins_text is null");
+  const uint32_t n32 = (uint32_t)n;
+  const uint64_t work_bytes = dcrx_merge_work_bytes(n);
+  if (!work_bytes) return DCRX_E_HIP;                      // (plan_work left the message)
+
+  Pool P;
+  uint16_t *d_v, *d_j;
+  uint8_t *d_vdel, *d_jdel, *d_reach, *d_text, *d_work;
+  uint64_t *d_count, *d_first, *d_off, *d_key[2];
+  unsigned long long *d_tc, *d_tf, *d_stats;
+  uint32_t *d_r[2], *d_d[2], *d_changed, *d_isroot, *d_slot, *d_list[2];
+  for (int pass = 0; pass < 2; pass++) {
+    P.get(&d_v, n); P.get(&d_j, n); P.get(&d_vdel, n); P.get(&d_jdel, n); P.get(&d_reach, n); P.get(&d_text, text_bytes);
+    P.get(&d_count, n); P.get(&d_first, n); P.get(&d_off, n + 1); P.get(&d_tc, n); P.get(&d_tf, n); P.get(&d_stats, MS_WORDS);
+    P.get(&d_r[0], n); P.get(&d_r[1], n); P.get(&d_d[0], n); P.get(&d_d[1], n); P.get(&d_changed, 1); P.get(&d_work, work_bytes);
+    if (pass == 0 && (rc = P.allocate())) return rc;
+  }
+  std::vector<uint64_t> off(n + 1);
+  for (uint64_t k = 0; k <= n; k++) off[k] = ins_off[k] - text0;
+  HIP_TRY(hipMemcpy(d_v, v, n * 2, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_j, j, n * 2, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_vdel, vdel, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_jdel, jdel, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_count, count, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_first, first, n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+  if (text_bytes) HIP_TRY(hipMemcpy(d_text, ins_text + text0, text_bytes, hipMemcpyHostToDevice));
+
+  rc = dcrx_merge_parents_device(tables, n, d_v, d_j, d_vdel, d_jdel, d_count, d_off, reinterpret_cast<const char *>(d_text),
+                                 text_bytes, distance, ratio, d_r[0], d_reach, d_work, work_bytes, nullptr);
+  if (rc) return rc;
+
+  // roots: pointer jumping until no pointer moves (a round halves every entry's way to its root)
+  merge_depth_init_kernel<<<grid_for(n), BLOCK>>>(d_r[0], n32, d_d[0]);
+  HIP_TRY(hipGetLastError());
+  int cur = 0;
+  for (int round = 0; round < 40; round++) {
+    uint32_t changed = 0;
+    HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), nullptr));
+    merge_jump_kernel<<<grid_for(n), BLOCK>>>(d_r[cur], d_d[cur], n32, d_r[cur ^ 1], d_d[cur ^ 1], d_changed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&changed, d_changed, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!changed) break;                                    // (both buffers hold the same roots and depths now)
+    cur ^= 1;
+  }
+  uint32_t *d_root = d_r[cur], *d_depth = d_d[cur];
+
+  // totals onto the roots, and the statistics
+  d_isroot = d_r[cur ^ 1];                                  // (free from here on)
+  d_slot = d_d[cur ^ 1];
+  HIP_TRY(hipMemcpyAsync(d_tc, d_count, n * 8, hipMemcpyDeviceToDevice, nullptr));
+  HIP_TRY(hipMemcpyAsync(d_tf, d_first, n * 8, hipMemcpyDeviceToDevice, nullptr));
+  HIP_TRY(hipMemsetAsync(d_stats, 0, MS_WORDS * sizeof(unsigned long long), nullptr));
+  merge_totals_kernel<<<grid_for(n), BLOCK>>>(d_root, d_depth, d_reach, d_count, d_first, n32, d_tc, d_tf, d_isroot, d_stats);
+  HIP_TRY(hipGetLastError());
+  unsigned long long st[MS_WORDS];
+  HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(root_of_out, d_root, n * 4, hipMemcpyDeviceToHost));
+  const uint64_t m = n - st[MS_MERGED];
+  const uint32_t m32 = (uint32_t)m;
+
+  // the roots in rank order, then by first ordinal, then (stably) by count descending; the work space is free again
+  WorkPlan W;
+  if ((rc = plan_work(n, &W))) return rc;
+  d_key[0] = reinterpret_cast<uint64_t *>(d_work + W.key[0]); d_key[1] = reinterpret_cast<uint64_t *>(d_work + W.key[1]);
+  d_list[0] = reinterpret_cast<uint32_t *>(d_work + W.idx[0]); d_list[1] = reinterpret_cast<uint32_t *>(d_work + W.idx[1]);
+  void *d_cub = d_work + W.cub;
+  size_t tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_cub, tb, d_isroot, d_slot, (int)n));
+  merge_list_kernel<<<grid_for(n), BLOCK>>>(d_isroot, d_slot, n32, d_list[0]);
+  HIP_TRY(hipGetLastError());
+  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tf, d_list[0], m32, 0, d_key[0]);
+  HIP_TRY(hipGetLastError());
+  tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_list[0], d_list[1], (int)m, 0, 64));
+  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tc, d_list[1], m32, 1, d_key[0]);
+  HIP_TRY(hipGetLastError());
+  tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_list[1], d_list[0], (int)m, 0, 64));
+  HIP_TRY(hipMemcpy(order_out, d_list[0], m * 4, hipMemcpyDeviceToHost));
+  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tc, d_list[0], m32, 0, d_key[1]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(count_out, d_key[1], m * 8, hipMemcpyDeviceToHost));
+  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tf, d_list[0], m32, 0, d_key[1]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(first_out, d_key[1], m * 8, hipMemcpyDeviceToHost));
+  if (stats_out) {
+    stats_out->roots_out = m;
+    stats_out->out_of_reach = st[MS_OUT_OF_REACH];
+    stats_out->merged = st[MS_MERGED];
+    stats_out->reads_moved = st[MS_MOVED];
+    stats_out->longest_chain = st[MS_CHAIN];
+  }
+  return (int64_t)m;
+}
+
+int64_t dcrx_merge_gather(uint64_t n, uint64_t m, const uint32_t *order, const uint16_t *v, const uint16_t *j,
+                          const uint8_t *vdel, const uint8_t *jdel, const uint64_t *ins_off, const char *ins_text,
+                          uint16_t *out_v, uint16_t *out_j, uint8_t *out_vdel, uint8_t *out_jdel, uint64_t *out_ins_off,
+                          char *out_ins_text) {
+  if (!out_ins_off) return set_err(DCRX_E_INVALID, "dcrx_merge_gather: null argument");
+  out_ins_off[0] = 0;
+  if (m > n) return set_err(DCRX_E_INVALID, "dcrx_merge_gather: more roots than entries");
+  if (m && (!order || !v || !j || !vdel || !jdel || !ins_off || !out_v || !out_j || !out_vdel || !out_jdel))
+    return set_err(DCRX_E_INVALID, "dcrx_merge_gather: null argument");
+  uint64_t at = 0;
+  for (uint64_t k = 0; k < m; k++) {
+    const uint64_t e = order[k];
+    if (e >= n || ins_off[e + 1] < ins_off[e]) return set_err(DCRX_E_INVALID, "dcrx_merge_gather: an entry outside the table");
+    out_v[k] = v[e]; out_j[k] = j[e]; out_vdel[k] = vdel[e]; out_jdel[k] = jdel[e];
+    const uint64_t len = ins_off[e + 1] - ins_off[e];
+    if (len) {
+      if (!ins_text || !out_ins_text) return set_err(DCRX_E_INVALID, "dcrx_merge_gather: null text");
+      std::memcpy(out_ins_text + at, ins_text + ins_off[e], len);
+    }
+    at += len;
+    out_ins_off[k + 1] = at;
+  }
+  return (int64_t)at;
+}
+
+}  // extern "C"

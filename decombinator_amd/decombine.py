@@ -50,6 +50,9 @@ _current = None  # the ChainTables of the last import_tcr_info()
 # arguments (with the reference's in-place `tags` rewrite for that chain only)
 chain_counts: dict = {}
 chain_args: dict = {}
+# the error merge's statistics (--merge-errors: nat.MERGE_STATS) of the last stage, and per chain of the last list run
+merge_stats: dict = {}
+chain_merge_stats: dict = {}
 
 # what -c takes for one chain (reference :609-627), case-insensitive
 _CHAIN_SPELLINGS = {"A": "a", "ALPHA": "a", "TRA": "a", "TCRA": "a", "B": "b", "BETA": "b", "TRB": "b", "TCRB": "b",
@@ -858,10 +861,39 @@ class NbcRows(coll.abc.Sequence):
         fh.buffer.write(nat.format_counts(self.counted, joiner))
 
 
+MERGE_DISTANCE_DEFAULT, MERGE_RATIO_DEFAULT = 1, 10      # a design choice, not a measured optimum
+
+
+def merge_parameters(inputargs: dict) -> tuple:
+    """(distance, ratio) of --merge-errors: the values given, or the defaults."""
+    d, r = inputargs.get("merge_distance"), inputargs.get("merge_ratio")
+    return (MERGE_DISTANCE_DEFAULT if d is None else d, MERGE_RATIO_DEFAULT if r is None else r)
+
+
 def check_count_args(inputargs: dict) -> None:
     """count_dcrs (--count-dcrs) is the barcode-free stage's DCR count: refused, before anything is read, without
     nobarcoding (-nbc), with cluster (--cluster: UMIs are what it clusters) and with sampling_analysis (-sa: the V tail comes
-    from the barcode read)."""
+    from the barcode read).  merge_errors (--merge-errors) is a step of that count: refused without count_dcrs, as are
+    merge_distance / merge_ratio / write_merges without merge_errors, a distance other than 1 or 2 and a ratio that is not an
+    integer >= 1."""
+    given = set(inputargs.get("merge_options_given") or ())
+    d, r = merge_parameters(inputargs)
+    if d != MERGE_DISTANCE_DEFAULT:
+        given.add("--merge-distance")
+    if r != MERGE_RATIO_DEFAULT:
+        given.add("--merge-ratio")
+    if inputargs.get("write_merges"):
+        given.add("--write-merges")
+    if inputargs.get("merge_errors"):
+        if not inputargs.get("count_dcrs"):
+            raise ValueError("--merge-errors folds erroneous DCRs of the barcode-free count into their parents: it needs "
+                             "--count-dcrs")
+        if isinstance(d, bool) or not isinstance(d, int) or d not in (1, 2):
+            raise ValueError(f"--merge-distance is 1 or 2 substitutions, not {d!r}")
+        if isinstance(r, bool) or not isinstance(r, int) or r < 1 or r >= 1 << 64:
+            raise ValueError(f"--merge-ratio is an integer >= 1, not {r!r}")
+    elif given:
+        raise ValueError(f"{', '.join(sorted(given))}: only with --merge-errors")
     if not inputargs.get("count_dcrs"):
         return
     if not inputargs.get("nobarcoding"):
@@ -870,6 +902,16 @@ def check_count_args(inputargs: dict) -> None:
         raise ValueError("--count-dcrs and --cluster exclude each other: without barcodes there are no UMIs to cluster")
     if inputargs.get("sampling_analysis"):
         raise ValueError("--count-dcrs and -sa exclude each other: the V tail of -sa comes from the barcode read")
+
+
+def merges_text(counted: dict, root_of, joiner: str = ", ") -> bytes:
+    """The `.merges` text: one line per merged entry of the counted table, in rank order — the child's key and count,
+    then its root's key."""
+    rows = nat.count_rows(counted)
+    root_of = np.asarray(root_of)
+    lines = [joiner.join(rows[k][:5] + [str(rows[k][5])] + rows[int(root_of[k])][:5]) + "\n"
+             for k in np.nonzero(root_of != np.arange(len(root_of)))[0]]
+    return "".join(lines).encode("latin-1")
 
 
 def _count_loop(inputargs: dict, chains: list, cnts: list, max_read_len: int) -> list:
@@ -908,10 +950,21 @@ def _count_loop(inputargs: dict, chains: list, cnts: list, max_read_len: int) ->
         rd.close()
         stage_seconds["close"] = time() - tc
     tr = time()
-    out = [NbcRows(dc.read()) for dc in dcs]
-    for dc in dcs:
+    out = []
+    for ch, dc in zip(chains, dcs):
+        counted = dc.read()
         dc.close()
-    stage_seconds["rows"] = time() - tr
+        if inputargs.get("merge_errors"):
+            # the error merge, each chain's table on its own with its own tag set (nat.merge_dcrs: the ONE call)
+            tm = time()
+            before = counted
+            counted, ch["merge_stats"], root_of = nat.merge_dcrs(ch["tcr"].tables, before, *merge_parameters(inputargs))
+            stage_seconds["merge"] = stage_seconds.get("merge", 0.0) + (time() - tm)
+        rows = NbcRows(counted)
+        if inputargs.get("merge_errors") and inputargs.get("write_merges"):
+            rows.merges_text = merges_text(before, root_of)
+        out.append(rows)
+    stage_seconds["rows"] = time() - tr - stage_seconds.get("merge", 0.0)
     return out
 
 
@@ -949,9 +1002,23 @@ def decombinator(inputargs: dict, shard=None, reduce_counts=None, exchange_error
     if reduce_counts is not None:
         reduce_counts(counts)
     counts["end_time"] = time()
+    merge_stats.clear()
+    merge_stats.update(state["chains"][0].get("merge_stats") or {})
     if rank == 0:
         _chain_report(state["chains"][0], counts)
     return state["outdata"]
+
+
+def _merge_summary(inputargs: dict, stats) -> str:
+    """The error merge's lines at the end of the summary log: only with merge_errors."""
+    if not inputargs.get("merge_errors") or stats is None:
+        return ""
+    d, r = merge_parameters(inputargs)
+    lines = ["", "ErrorMerge:,", "MergeDistance," + str(d), "MergeRatio," + str(r),
+             "DCRsBeforeMerge," + str(stats["entries_in"]), "DCRsAfterMerge," + str(stats["roots_out"]),
+             "DCRsOutOfReach," + str(stats["out_of_reach"]), "DCRsMerged," + str(stats["merged"]),
+             "ReadsMoved," + str(stats["reads_moved"]), "LongestMergeChain," + str(stats["longest_chain"])]
+    return "\n".join(lines)
 
 
 def _chain_report(ch: dict, counts) -> None:
@@ -965,7 +1032,8 @@ def _chain_report(ch: dict, counts) -> None:
     print("Took", str(round(timetaken, 2)), "seconds")
     if args["suppresssummary"] == False:  # noqa: E712
         name, fh = _new_summary_file(ch["summaryname"], ch["logpath"], ch["date"], args["chain"], chain, samplenam)
-        print(_summary_text(args, chain, samplenam, ch["date"], timetaken, counts), file=fh)
+        print(_summary_text(args, chain, samplenam, ch["date"], timetaken, counts) + _merge_summary(args, ch.get("merge_stats")),
+              file=fh)
         fh.close()
         sort_permissions(name)
 
@@ -986,6 +1054,7 @@ def decombinator_chains(inputargs: dict) -> dict:
     print("Running Decombinator (MI355X / HIP build) version", __version__)
     chain_counts.clear()
     chain_args.clear()
+    chain_merge_stats.clear()
     chains = []
     for item in items:
         args = dict(inputargs, chain=item)
@@ -997,5 +1066,7 @@ def decombinator_chains(inputargs: dict) -> dict:
     _decombinator_loop(inputargs, 0, 1, {"chains": chains})
     for ch in chains:
         ch["counts"]["end_time"] = time()
+        if ch.get("merge_stats") is not None:
+            chain_merge_stats[ch["chain"]] = ch["merge_stats"]
         _chain_report(ch, ch["counts"])
     return {ch["chain"]: ch["outdata"] for ch in chains}

@@ -27,11 +27,14 @@ def create_args_dict(
     barcodeduplication: bool = False, positionalbarcodes: bool = False, oligo: str = "M13",
     writeclusters: bool = False, UMIhistogram: bool = False, nonproductivefilter: bool = False,
     outpath: str = None, dontsave: bool = False, command: str = None, sampling_analysis: bool = False,
-    cluster: bool = False, count_dcrs: bool = False,
+    cluster: bool = False, count_dcrs: bool = False, merge_errors: bool = False, merge_distance: int = 1,
+    merge_ratio: int = 10, write_merges: bool = False,
 ) -> dict:
     """The function-argument dictionary threaded through the stages (the reference's 33 keys, `cluster`: run the
     grouping / clustering half of collapse, writing the `.freq`, and `count_dcrs`: with nobarcoding, count the DCRs on the
-    GPU and write the `.nbc`)."""
+    GPU and write the `.nbc`; `merge_errors`: fold the counted DCRs within `merge_distance` substitutions of a DCR at least
+    `merge_ratio` times as abundant into it before the `.nbc` is written, `write_merges`: list what was folded in a
+    `.merges` file.  The defaults 1 and 10 are a design choice, not a measured optimum)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -42,7 +45,8 @@ def create_args_dict(
         positionalbarcodes=positionalbarcodes, oligo=oligo, writeclusters=writeclusters,
         UMIhistogram=UMIhistogram, nonproductivefilter=nonproductivefilter, outpath=outpath,
         dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster,
-        count_dcrs=count_dcrs)
+        count_dcrs=count_dcrs, merge_errors=merge_errors, merge_distance=merge_distance, merge_ratio=merge_ratio,
+        write_merges=write_merges)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -102,6 +106,22 @@ def _count_flag(p: argparse.ArgumentParser):
                         "counts (.nbc: v, j, vdel, jdel, insert, count); translate reads such a file")
 
 
+def _merge_flags(p: argparse.ArgumentParser):
+    p.add_argument("--merge-errors", dest="merge_errors", action="store_true",
+                   help="With --count-dcrs: fold every DCR within --merge-distance substitutions (over the junction) of a DCR "
+                        "with the same V, J and junction length and at least --merge-ratio times its reads into that DCR "
+                        "before the .nbc is written (GPU)")
+    p.add_argument("--merge-distance", dest="merge_distance", type=int, default=None,
+                   help="Substitutions allowed between a DCR and its parent: 1 (default) or 2.  The default is a design choice, "
+                        "not a measured optimum")
+    p.add_argument("--merge-ratio", dest="merge_ratio", type=int, default=None,
+                   help="A parent has at least this many times the reads of its child (integer >= 1; default 10, a design "
+                        "choice, not a measured optimum)")
+    p.add_argument("--write-merges", dest="write_merges", action="store_true",
+                   help="With --merge-errors: write <same stem>.merges beside the .nbc, one line per folded DCR: its key, its "
+                        "count, its root's key")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -113,9 +133,9 @@ def create_parser() -> argparse.ArgumentParser:
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
                                            "translate (.n12, .freq, .tsv)")
-    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe); _count_flag(pipe)
+    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe); _count_flag(pipe); _merge_flags(pipe)
     dec = sub.add_parser("decombine", help="Decombine TCR reads")
-    _common(dec); _decombine(dec); _count_flag(dec)
+    _common(dec); _decombine(dec); _count_flag(dec); _merge_flags(dec)
     col = sub.add_parser("collapse", help="front half of collapse over an .n12 file: barcode extraction and the row filters "
                                           "(writes .n12u); with --cluster the whole stage (writes .freq)")
     _common(col); _later_stage_flags(col); _cluster_flag(col); _count_flag(col)
@@ -134,7 +154,14 @@ def create_parser() -> argparse.ArgumentParser:
 
 
 def cli_args(argv=None) -> dict:
-    return vars(create_parser().parse_args(argv))
+    inp = vars(create_parser().parse_args(argv))
+    if "merge_errors" in inp:
+        # which of the merge options the command line named (they are refused without --merge-errors), then the defaults
+        inp["merge_options_given"] = [f for f, k in (("--merge-distance", "merge_distance"), ("--merge-ratio", "merge_ratio"))
+                                      if inp[k] is not None]
+        inp["merge_distance"] = 1 if inp["merge_distance"] is None else inp["merge_distance"]
+        inp["merge_ratio"] = 10 if inp["merge_ratio"] is None else inp["merge_ratio"]
+    return inp
 
 
 class _GzText:
@@ -195,6 +222,26 @@ def write_out_intermediate(data: list, inputargs: dict, suffix: str):
                     outfile.write(", ".join(map(str, line)) + "\n")
     sort_permissions(outfilename)
     return outfilename
+
+
+class _RawText:
+    """Text that is bytes already, for write_out_intermediate."""
+
+    def __init__(self, text: bytes):
+        self.text = text
+
+    def write_text(self, fh, joiner: str = ", ") -> None:
+        fh.flush()
+        fh.buffer.write(self.text)
+
+
+def write_out_counts(data, inputargs: dict):
+    """The `.nbc` of the barcode-free count and, with write_merges, `<same stem>.merges` beside it (what --merge-errors
+    folded: decombine.merges_text).  Returns the `.nbc`'s name."""
+    name = write_out_intermediate(data, inputargs, nbc_suffix(inputargs))
+    if inputargs.get("write_merges") and hasattr(data, "merges_text"):
+        write_out_intermediate(_RawText(data.merges_text), inputargs, ".merges")
+    return name
 
 
 def nbc_suffix(inputargs: dict) -> str:

@@ -14,7 +14,7 @@ from typing import Any, Optional
 from . import collapse
 from . import decombine as dec
 from .decombine import decombinator
-from .io import cli_args, nbc_suffix, write_out_intermediate
+from .io import cli_args, write_out_counts, write_out_intermediate
 
 
 def collapse_front(data, inp):
@@ -65,7 +65,7 @@ def _after_decombine(data, inp, start):
         from . import translate
         from .io import write_out_translated
         if not inp["dontsave"]:
-            write_out_intermediate(data, inp, nbc_suffix(inp))
+            write_out_counts(data, inp)
         print("Decombinator complete...")
         data = translate.cdr3translator(inp, data=data)
         print("CDR3translator complete...")
@@ -98,6 +98,12 @@ def _after_decombine(data, inp, start):
 
 def main(argv=None):
     inp = cli_args(argv)
+    if inp.get("merge_errors") or inp.get("write_merges") or inp.get("merge_options_given"):
+        from .io import create_parser          # (decombine and pipeline alone take these flags)
+        try:
+            dec.check_count_args(inp)
+        except ValueError as e:
+            create_parser().error(str(e))
     if inp.get("count_dcrs"):           # refused before anything is read
         from .io import create_parser
         if inp["command"] == "collapse":
@@ -120,13 +126,19 @@ def main(argv=None):
         except ValueError as e:
             from .io import create_parser
             create_parser().error(str(e))
-    suffix = nbc_suffix(inp) if inp.get("count_dcrs") and inp["command"] == "decombine" else ".n12"
+
+    def write(data, args):
+        if args.get("count_dcrs"):
+            write_out_counts(data, args)
+        else:
+            write_out_intermediate(data, args, ".n12")
+
     if inp["command"] == "decombine" and dec.chain_list(inp.get("chain")) is not None:
         for chain, data in dec.decombinator_chains(inp).items():
-            write_out_intermediate(data, _files_args(chain), suffix)
+            write(data, _files_args(chain))
     elif inp["command"] == "decombine":
         data = decombinator(inp)
-        write_out_intermediate(data, inp, suffix)
+        write(data, inp)
     elif inp["command"] == "pipeline":
         run(cli_args=inp)
     elif inp["command"] == "collapse" and inp.get("cluster"):

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define DCRX_ABI_VERSION 4
+#define DCRX_ABI_VERSION 5
 
 enum dcrx_error {
   DCRX_OK = 0,
@@ -338,6 +338,74 @@ int64_t dcrx_counts_read(dcrx_counts_t *counts, uint16_t *v, uint16_t *j, uint8_
 int64_t dcrx_format_counts(uint64_t n, const uint16_t *v, const uint16_t *j, const uint8_t *vdel, const uint8_t *jdel,
                            const uint64_t *count, const uint64_t *ins_off, const char *ins_text, const char *field_sep,
                            char *out, uint64_t out_cap);
+
+/* ---- the error merge of the barcode-free count (decombine -nbc --count-dcrs --merge-errors): low-count DCRs one or
+ * two substitutions away from an abundant one are folded into it.  The reference has no counterpart (its -nbc loop
+ * never runs, decombine.py:950, :1041-1060): the contract below is this library's own ---- */
+
+#define DCRX_MERGE_ANCHOR 32         /* germline bases kept on either side of the junction */
+#define DCRX_MERGE_MAX_JUNCTION 128  /* longest junction compared (256 bits at 2 bits a base) */
+
+/* Input: n counted DCRs as dcrx_counts_read gives them (entry k has rank k: count descending, ties by first ordinal), the
+ * chain's tables, a distance D (1 or 2) and a ratio R (>= 1).
+ *   junction(e) = Vr[len(Vr) - aV : len(Vr) - vdel] + insert + Jr[jdel : aJ], with Vr / Jr the upper-cased regions of the
+ *     entry's genes, aV = min(DCRX_MERGE_ANCHOR, len(Vr)), aJ likewise: the slice of the sequence translate rebuilds
+ *     (V[:-vdel] + insert + J[jdel:]) between two anchors that depend on (v, j) only, so that a substitution the
+ *     deletion walk turned into a larger vdel / jdel and a longer insert is still ONE mismatch between equal lengths.
+ *   e is in reach when vdel <= aV, jdel <= aJ, the insert and both windows hold only ACGT (upper case) and the junction
+ *     has at most DCRX_MERGE_MAX_JUNCTION bases.  An entry out of reach is never a child and never a parent.
+ *   p is an eligible parent of c when both are in reach, v, j and the junction's length are equal,
+ *     hamming(junction_c, junction_p) <= D, rank_p < rank_c and count_c <= count_p / R (integer division; the counts
+ *     are the input's).  parent(c) is the eligible parent of the smallest rank, if any; root(c) follows the parent links to
+ *     their end (so a child of a child joins the grandparent's tree although the two may be 2 D apart).
+ * Output: one entry per root with its own key, the sum of its tree's counts and the smallest first ordinal of its tree,
+ * ordered by count descending, then first ordinal, then rank.  A function of the input table alone. */
+typedef struct dcrx_merge_stats {
+  uint64_t entries_in;     /* n */
+  uint64_t roots_out;      /* entries of the output */
+  uint64_t out_of_reach;   /* entries the step left as they came */
+  uint64_t merged;         /* entries that have a parent */
+  uint64_t reads_moved;    /* sum of the merged entries' counts */
+  uint64_t longest_chain;  /* most parent links between an entry and its root */
+} dcrx_merge_stats_t;
+
+/* Bytes of device work space dcrx_merge_parents_device needs for n entries. */
+uint64_t dcrx_merge_work_bytes(uint64_t n);
+
+/* The primitive: parent(c) of every entry, asynchronously on `hip_stream`, all arrays in device memory.  d_ins_off: n + 1
+ * offsets into d_ins_text (text_bytes bytes; an entry whose insert would leave them counts as out of reach, as one whose
+ * v or j the tables do not have).  d_parent[k] (n uint32) receives parent(k)'s rank, or k itself where there is none;
+ * d_reach[k] (n bytes, may be NULL) 1 when entry k is in reach.  d_work: dcrx_merge_work_bytes(n) bytes, 256-byte
+ * aligned, free for other use once the stream has passed the call.  The germline windows come from `tables` (uploaded on
+ * the handle's first merge on a device: that call synchronises).  n < 2^31.  Encodes every junction (one lane per entry),
+ * sorts the entries by (v, j, length) — stable, so a bucket stays in rank order — and searches each child's parent among
+ * the head of its bucket: the entries that satisfy the ratio are a prefix of the bucket, staged in LDS tile by tile. */
+int dcrx_merge_parents_device(dcrx_tables_t *tables, uint64_t n, const uint16_t *d_v, const uint16_t *d_j,
+                              const uint8_t *d_vdel, const uint8_t *d_jdel, const uint64_t *d_count,
+                              const uint64_t *d_ins_off, const char *d_ins_text, uint64_t text_bytes, uint32_t distance,
+                              uint64_t ratio, uint32_t *d_parent, uint8_t *d_reach, void *d_work, uint64_t work_bytes,
+                              void *hip_stream);
+
+/* The whole step on host arrays, synchronous on the current device: uploads the table, runs the primitive, follows the
+ * parent links to the roots (pointer jumping), adds each tree's counts and first ordinals onto its root (integer
+ * atomics) and orders the roots.  root_of_out[k] (n): the rank of entry k's root (k itself for a root).  The output's
+ * entry m (m < the return value) is input entry order_out[m] with count count_out[m] and first ordinal first_out[m]
+ * (three arrays of n entries).  stats_out may be NULL.  Returns the number of roots, or a negative dcrx_error:
+ * DCRX_E_INVALID for a v or j the tables do not have, offsets that go backwards, a distance outside 1 .. 2 or a ratio
+ * of 0; DCRX_E_UNSUPPORTED for 2^31 entries or more; DCRX_E_HIP when the device cannot hold the table. */
+int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, const uint16_t *j, const uint8_t *vdel,
+                        const uint8_t *jdel, const uint64_t *count, const uint64_t *first, const uint64_t *ins_off,
+                        const char *ins_text, uint32_t distance, uint64_t ratio, uint32_t *root_of_out,
+                        uint32_t *order_out, uint64_t *count_out, uint64_t *first_out, dcrx_merge_stats_t *stats_out);
+
+/* The table of the roots out of the input table and what dcrx_merge_dcrs returned: output entry k (k < m) gets the key of
+ * input entry order[k] — v, j, vdel, jdel and the insert's bytes, out_ins_off[0] = 0 .. out_ins_off[m] — in one pass.
+ * out_ins_text holds at least the inserts' bytes of the whole input table.  Returns the bytes written to out_ins_text.
+ * Host only. */
+int64_t dcrx_merge_gather(uint64_t n, uint64_t m, const uint32_t *order, const uint16_t *v, const uint16_t *j,
+                          const uint8_t *vdel, const uint8_t *jdel, const uint64_t *ins_off, const char *ins_text,
+                          uint16_t *out_v, uint16_t *out_j, uint8_t *out_vdel, uint8_t *out_jdel, uint64_t *out_ins_off,
+                          char *out_ins_text);
 
 /* Profiling aid: the following dcrx_decombine_device calls on `tables` record
  * start_event right before and stop_event right after the dominant kernel (the scan),
