@@ -15,6 +15,7 @@
 
 #include "../../include/dcrx.h"
 #include "../../include/dcrx_synth.h"
+#include "dcrx_hip.h"
 #include "dcrx_launch.h"
 #include "dcrx_synth_core.h"
 #include <cstdlib>
@@ -39,16 +40,6 @@ static thread_local std::string g_err;
 
 static int set_err(int code, const std::string &m) { g_err = m; return code; }
 namespace dcrx { int set_err(int code, const char *msg) { return ::set_err(code, std::string(msg)); } }
-static int hip_err(hipError_t e, const char *what) {
-  g_err = std::string(what) + ": " + hipGetErrorString(e);
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? DCRX_E_NOGPU : DCRX_E_HIP;
-}
-#define HIP_TRY(call)                                   \
-  do {                                                  \
-    hipError_t e_ = (call);                             \
-    if (e_ != hipSuccess) return hip_err(e_, #call);    \
-  } while (0)
-
 // reads per chunk of the host-buffer entry (dcrx_decombine): 80 MB in, 32 MB out at 150 nt
 #ifndef DCRX_HOST_CHUNK
 #define DCRX_HOST_CHUNK (2u << 20)
@@ -73,116 +64,75 @@ static void par_memcpy(void *dst, const void *src, size_t n) {
   for (auto &x : th) if (x.joinable()) x.join();
 }
 
+// Everything a handle keeps on the device its tables were last used on.  All of it is owned here: a fresh DeviceState
+// assigned over this one (with that device current) releases the lot.
+struct DeviceState {
+  int device = -1;
+  DevBuf<uint8_t> blob;
+  DevTables dev{};
+  DevBuf<DevTables> d_dev;      // the same struct in device memory (what a kernel's rare paths read instead of holding it in registers)
+  LaunchPlan plan{};            // (its pointers are copies of the owners below: fill_plan)
+  DevBuf<uint32_t> exc_flag; uint64_t exc_flag_reads = 0;
+  DevBuf<uint32_t> queue;       // [DCRX_QUEUE_HEADER work counters][exc_flag_reads rescue indices][exc_flag_reads general indices]
+  // v2 kernels: the per-wave lists between scan and finishing
+  DevBuf<uint4> v2_tail, v2_events, v2_slow;
+  DevBuf<uint32_t> v2_counts;
+  DevBuf<uint4> v2_left;        // the finishing launch's left list
+  DevBuf<uint64_t> v2_acc;      // the v2 kernels' tallies of the call in flight (zero between calls)
+  Stream v2_side, v2_side2;
+  Event v2_ev_fork, v2_ev_join, v2_ev_join2;
+  // staging for the host-buffer entry point: two sets of device buffers and pinned host buffers, three streams
+  // (copies in, kernels, copies out) and the events that order them
+  DevBuf<uint8_t> d_stage; size_t stage_bytes = 0;
+  PinnedBuf<uint8_t> h_stage; size_t h_stage_bytes = 0;
+  Stream hs_in, hs_run, hs_out;
+  Event hev_in[2], hev_run[2], hev_out[2];
+  V2Tune tune[2];               // the handle's timing of its own finishing launches (launch_v2), per frame
+  // the kernels' side of the tuple sink
+  DevBuf<V2SinkDev> sink; DevBuf<uint2> sink_items; DevBuf<uint32_t> sink_ctr;
+  uint64_t sink_items_cap = 0; uint32_t sink_regions_cap = 0;
+};
+
+// the error merge's germline windows (dcrx_merge_core.h), on the device they were last asked for
+struct MergeRows { int device = -1; DevBuf<uint32_t> rows; };
+
 struct dcrx_tables {
   HostTables host;
-  // state on the device the tables were last used on
-  int device = -1;
-  uint8_t *d_blob = nullptr;
-  DevTables dev{};
-  DevTables *d_dev = nullptr;   // the same struct in device memory (what a kernel's rare paths read instead of holding it in registers)
-  LaunchPlan plan{};
+  DeviceState state;
   bool ws_dirty = true;       // work counters / exception bitmap must be zeroed before the next launch
   uint32_t reserved_cus = 0;
-  uint32_t *d_exc_flag = nullptr;
-  uint64_t exc_flag_reads = 0;
-  uint32_t *d_queue = nullptr;  // [DCRX_QUEUE_HEADER work counters][exc_flag_reads rescue indices][exc_flag_reads general indices]
-  void *d_v2_tail = nullptr, *d_v2_events = nullptr, *d_v2_slow = nullptr;
+  bool tune_may_wait = false;       // dcrx_set_tune_wait
   // the tail list (a third of the lists' bytes) exists only for handles whose calls keep the tail a role of the finishing launch:
   // where the scan takes the tail through its ring in LDS nothing is ever stored in it.  Unknown: decided by the first use
   // (table sizes), corrected by the first launch that turns out to need the list (dcrx_decombine_device allocates it and launches again)
   int want_tail = -1;
-  void *d_v2_left = nullptr;        // the finishing launch's left list
-  uint64_t *d_v2_acc = nullptr;     // the v2 kernels' tallies of the call in flight (zero between calls)  // v2 kernels: the per-wave lists between scan and finishing
-  hipStream_t v2_side = nullptr, v2_side2 = nullptr; hipEvent_t v2_ev_fork = nullptr, v2_ev_join = nullptr, v2_ev_join2 = nullptr;
-  uint32_t *d_v2_counts = nullptr;
-  // staging for the host-buffer entry point: two sets of device buffers and pinned host buffers, three streams
-  // (copies in, kernels, copies out) and the events that order them
-  uint8_t *d_stage = nullptr;
-  size_t stage_bytes = 0;
-  uint8_t *h_stage = nullptr;       // pinned
-  size_t h_stage_bytes = 0;
-  hipStream_t hs_in = nullptr, hs_run = nullptr, hs_out = nullptr;
-  hipEvent_t hev_in[2] = {nullptr, nullptr}, hev_run[2] = {nullptr, nullptr}, hev_out[2] = {nullptr, nullptr};
-  bool constants_ready = false;
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;      // around the dominant kernel
-  hipEvent_t ev_step_start = nullptr, ev_step_stop = nullptr;  // around every launch of a call
-  V2Tune tune[2];                   // the handle's timing of its own finishing launches (launch_v2), per frame
-  // the tuple sink (dcrx_set_tuple_sink): where the next calls leave their message, and the kernels' side of it on the device
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;      // around the dominant kernel (the caller's: dcrx_set_timing_events)
+  hipEvent_t ev_step_start = nullptr, ev_step_stop = nullptr;  // around every launch of a call (the caller's)
+  // the tuple sink (dcrx_set_tuple_sink): where the next calls leave their message
   bool sink_on = false;
   dcrx_tuple_layout_t sink_layout{};
   uint8_t *sink_msg = nullptr; uint64_t sink_slots = 0; uint64_t *sink_total = nullptr;
-  V2SinkDev *d_sink = nullptr;
-  void *d_sink_items = nullptr; uint32_t *d_sink_ctr = nullptr;
-  uint64_t sink_items_cap = 0; uint32_t sink_regions_cap = 0;
-  // the error merge's germline windows (dcrx_merge_core.h), on the device they were last asked for
-  uint32_t *d_merge_rows = nullptr;
-  int merge_device = -1;
+  MergeRows merge;
 };
 
 static int layout_dev(dcrx_tables *t, const dcrx_tuple_layout_t *L, TupleLayoutDev *D);
 static int compact_workspace(uint64_t n_reads, uint32_t **tc, uint64_t **to);
 
 static void free_device_state(dcrx_tables *t) {
-  if (t->device < 0) return;
-  (void)hipFree(t->d_dev); t->d_dev = nullptr;
-  (void)hipFree(t->d_blob); (void)hipFree(t->d_exc_flag); (void)hipFree(t->d_queue); (void)hipFree(t->d_v2_tail); (void)hipFree(t->d_v2_events); (void)hipFree(t->d_v2_counts);
-  (void)hipFree(t->d_v2_slow);
-  for (V2Tune &U : t->tune) {
-    const bool may_wait = U.may_wait;
-    for (V2TuneSlot &K : U.slot) {
-      if (K.created) for (auto &pair : K.ev) { (void)hipEventDestroy(pair[0]); (void)hipEventDestroy(pair[1]); }
-      if (K.ev_counts) (void)hipEventDestroy(K.ev_counts);
-      for (auto &pair : K.ev_e) for (auto &ev : pair) if (ev) (void)hipEventDestroy(ev);
-      if (K.h_counts) (void)hipHostFree(K.h_counts);
-    }
-    U = V2Tune{};
-    U.may_wait = may_wait;
-  }
-  (void)hipFree(t->d_sink); (void)hipFree(t->d_sink_items); (void)hipFree(t->d_sink_ctr);
-  t->d_sink = nullptr; t->d_sink_items = nullptr; t->d_sink_ctr = nullptr; t->sink_items_cap = 0; t->sink_regions_cap = 0;
-  if (t->v2_side) (void)hipStreamDestroy(t->v2_side);
-  if (t->v2_side2) (void)hipStreamDestroy(t->v2_side2);
-  if (t->v2_ev_fork) (void)hipEventDestroy(t->v2_ev_fork);
-  if (t->v2_ev_join) (void)hipEventDestroy(t->v2_ev_join);
-  if (t->v2_ev_join2) (void)hipEventDestroy(t->v2_ev_join2);
-  t->v2_side = t->v2_side2 = nullptr; t->v2_ev_fork = t->v2_ev_join = t->v2_ev_join2 = nullptr;
-  t->d_v2_tail = nullptr; t->d_v2_events = nullptr; t->d_v2_counts = nullptr; t->d_v2_slow = nullptr;
-  (void)hipFree(t->d_v2_acc); t->d_v2_acc = nullptr; t->plan.v2_acc = nullptr;
-  (void)hipFree(t->d_v2_left); t->d_v2_left = nullptr; t->plan.v2_left = nullptr;
-  (void)hipFree(t->d_stage);
-  if (t->h_stage) (void)hipHostFree(t->h_stage);
-  t->h_stage = nullptr; t->h_stage_bytes = 0;
-  if (t->hs_in) (void)hipStreamDestroy(t->hs_in);
-  if (t->hs_run) (void)hipStreamDestroy(t->hs_run);
-  if (t->hs_out) (void)hipStreamDestroy(t->hs_out);
-  t->hs_in = t->hs_run = t->hs_out = nullptr;
-  for (int k = 0; k < 2; k++) {
-    if (t->hev_in[k]) (void)hipEventDestroy(t->hev_in[k]);
-    if (t->hev_run[k]) (void)hipEventDestroy(t->hev_run[k]);
-    if (t->hev_out[k]) (void)hipEventDestroy(t->hev_out[k]);
-    t->hev_in[k] = t->hev_run[k] = t->hev_out[k] = nullptr;
-  }
-  t->d_blob = nullptr; t->d_exc_flag = nullptr; t->d_queue = nullptr;
-  t->d_stage = nullptr;
-  t->exc_flag_reads = 0; t->stage_bytes = 0; t->device = -1; t->constants_ready = false;
+  DeviceGuard on(t->state.device);
+  t->state = DeviceState{};
 }
 
 static void free_merge_rows(dcrx_tables *t) {
-  if (t->merge_device < 0) return;
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess) {
-    if (cur != t->merge_device) (void)hipSetDevice(t->merge_device);
-    (void)hipFree(t->d_merge_rows);
-    if (cur != t->merge_device && cur >= 0) (void)hipSetDevice(cur);
-  }
-  t->d_merge_rows = nullptr; t->merge_device = -1;
+  DeviceGuard on(t->merge.device);
+  t->merge = MergeRows{};
 }
 
 // dcrx_merge.hip: one window row per gene (V rows, then J rows) out of the handle's regions, on the current device
 int dcrx::merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v, uint32_t *n_j) {
   int dev = -1;
   HIP_TRY(hipGetDevice(&dev));
-  if (t->merge_device != dev) {
+  if (t->merge.device != dev) {
     free_merge_rows(t);
     const uint32_t nv = t->host.g[0].n, nj = t->host.g[1].n;
     std::vector<uint32_t> rows((size_t)(nv + nj) * dcrx_merge::WIN_WORDS + 1, 0u);
@@ -191,11 +141,11 @@ int dcrx::merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v
         const std::string &r = t->host.g[g].regions[k];
         dcrx_merge::make_window(r.data(), (uint32_t)r.size(), g == 0, rows.data() + (size_t)((g ? nv : 0) + k) * dcrx_merge::WIN_WORDS);
       }
-    HIP_TRY(hipMalloc(&t->d_merge_rows, rows.size() * sizeof(uint32_t)));
-    t->merge_device = dev;
-    HIP_TRY(hipMemcpy(t->d_merge_rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = t->merge.rows.alloc(rows.size())) return rc;
+    HIP_TRY(hipMemcpy(t->merge.rows, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    t->merge.device = dev;
   }
-  *d_rows = t->d_merge_rows; *n_v = t->host.g[0].n; *n_j = t->host.g[1].n;
+  *d_rows = t->merge.rows; *n_v = t->host.g[0].n; *n_j = t->host.g[1].n;
   return DCRX_OK;
 }
 
@@ -222,14 +172,7 @@ int dcrx_tables_create(const dcrx_tagset_t *tagset, dcrx_tables_t **out) {
 void dcrx_tables_destroy(dcrx_tables_t *t) {
   if (!t) return;
   free_merge_rows(t);
-  if (t->device >= 0) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess) {
-      if (cur != t->device) (void)hipSetDevice(t->device);
-      free_device_state(t);
-      if (cur != t->device && cur >= 0) (void)hipSetDevice(cur);
-    }
-  }
+  free_device_state(t);
   delete t;
 }
 
@@ -295,105 +238,126 @@ int dcrx_event_elapsed_ms(void *a, void *b, float *ms) {
 }  // extern "C"
 
 // ---- per-device state -------------------------------------------------------------
-static int ensure_device(dcrx_tables *t, uint64_t max_reads, uint32_t stride = 40, hipStream_t stream = nullptr) {
+// the tables on the current device and the launch plan of that device: what a handle's first use of a device builds
+static int first_use(const dcrx_tables *t, int dev, DeviceState *out) {
+  DeviceState N;
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, dev));
+  int rc;
+  if ((rc = N.blob.alloc(t->host.blob.size()))) return rc;
+  HIP_TRY(hipMemcpy(N.blob, t->host.blob.data(), t->host.blob.size(), hipMemcpyHostToDevice));
+  N.dev = t->host.resolve(N.blob);
+  if ((rc = N.d_dev.alloc(1))) return rc;
+  HIP_TRY(hipMemcpy(N.d_dev, &N.dev, sizeof(DevTables), hipMemcpyHostToDevice));
+  // launch plan: persistent blocks of DCRX_BLOCK threads, the DFA resident in LDS
+  const uint32_t lds_cap = 160 * 1024;
+  const uint32_t want = t->host.rel.lds_image_bytes + DCRX_N_COUNTERS * 4;
+  LaunchPlan &P = N.plan;
+  P.n_cu = (uint32_t)prop.multiProcessorCount;
+  P.table_in_lds = want <= 120 * 1024;
+  P.lds_bytes = P.table_in_lds ? want : DCRX_N_COUNTERS * 4;
+  const uint32_t side_bytes = t->host.rel.lds_image_bytes - t->host.rel.dfa_bytes;
+  P.lds16_bytes = DCRX_N_COUNTERS * 4 + t->host.rel.dfa16_bytes + side_bytes;
+  P.table16_in_lds = P.table_in_lds && t->host.rel.dfa16_bytes != 0 && P.lds16_bytes + 32768 <= lds_cap;  // + wq and tail buffers of the 1024-thread block
+  uint32_t per_cu = std::min<uint32_t>(2048 / DCRX_BLOCK, std::max<uint32_t>(1, lds_cap / std::max<uint32_t>(P.lds_bytes, 1)));
+  P.grid = (uint32_t)prop.multiProcessorCount * std::max<uint32_t>(per_cu, 1);  // upper bound for either fast kernel
+  const uint32_t q_per_cu = std::min<uint32_t>(2048 / DCRX_QBLOCK, std::max<uint32_t>(1, lds_cap / std::max<uint32_t>(P.lds_bytes, 1)));
+  P.qgrid = (uint32_t)prop.multiProcessorCount * q_per_cu;
+  P.reserved_cus = t->reserved_cus;
+  P.tune_may_wait = t->tune_may_wait;
+  N.device = dev;
+  *out = std::move(N);
+  return DCRX_OK;
+}
+
+// the handle's workspace on the current device holds batches of up to max_reads reads of this stride (sizes kept in the plan
+// say what is allocated; a list that failed to grow is gone and its size is zero)
+static int grow_workspace(dcrx_tables *t, uint64_t max_reads, uint32_t stride) {
   int dev = -1;
   HIP_TRY(hipGetDevice(&dev));
-  if (t->device != dev) {
-    if (t->device >= 0) {  // tables move with the caller's current device
-      int old = t->device;
-      (void)hipSetDevice(old); free_device_state(t); (void)hipSetDevice(dev);
-    }
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    HIP_TRY(hipMalloc(&t->d_blob, t->host.blob.size()));
-    HIP_TRY(hipMemcpy(t->d_blob, t->host.blob.data(), t->host.blob.size(), hipMemcpyHostToDevice));
-    t->dev = t->host.resolve(t->d_blob);
-    HIP_TRY(hipMalloc(&t->d_dev, sizeof(DevTables)));
-    HIP_TRY(hipMemcpy(t->d_dev, &t->dev, sizeof(DevTables), hipMemcpyHostToDevice));
-    // launch plan: persistent blocks of DCRX_BLOCK threads, the DFA resident in LDS
-    const uint32_t lds_cap = 160 * 1024;
-    const uint32_t want = t->host.rel.lds_image_bytes + DCRX_N_COUNTERS * 4;
-    LaunchPlan P;
-    P.n_cu = (uint32_t)prop.multiProcessorCount;
-    P.table_in_lds = want <= 120 * 1024;
-    P.lds_bytes = P.table_in_lds ? want : DCRX_N_COUNTERS * 4;
-    const uint32_t side_bytes = t->host.rel.lds_image_bytes - t->host.rel.dfa_bytes;
-    P.lds16_bytes = DCRX_N_COUNTERS * 4 + t->host.rel.dfa16_bytes + side_bytes;
-    P.table16_in_lds = P.table_in_lds && t->host.rel.dfa16_bytes != 0 && P.lds16_bytes + 32768 <= lds_cap;  // + wq and tail buffers of the 1024-thread block
-    uint32_t per_cu = std::min<uint32_t>(2048 / DCRX_BLOCK, std::max<uint32_t>(1, lds_cap / std::max<uint32_t>(P.lds_bytes, 1)));
-    P.grid = (uint32_t)prop.multiProcessorCount * std::max<uint32_t>(per_cu, 1);  // upper bound for either fast kernel
-    const uint32_t q_per_cu = std::min<uint32_t>(2048 / DCRX_QBLOCK, std::max<uint32_t>(1, lds_cap / std::max<uint32_t>(P.lds_bytes, 1)));
-    P.qgrid = (uint32_t)prop.multiProcessorCount * q_per_cu;
-    P.reserved_cus = t->reserved_cus;
-    P.dev_tables = t->d_dev;
-    P.tune = t->tune;
-    t->plan = P;
-    t->device = dev;
+  if (t->state.device != dev) {
+    free_device_state(t);       // tables move with the caller's current device
+    // (built aside and committed whole: a first use that fails part-way leaves the handle empty, and what it had allocated is freed)
+    int rc = first_use(t, dev, &t->state);
+    if (rc) return rc;
   }
+  DeviceState &S = t->state;
+  LaunchPlan &P = S.plan;
+  int rc;
   if (max_reads < 4096) max_reads = 4096;  // workspace exists even for empty batches
-  if (max_reads > t->exc_flag_reads) {
-    (void)hipFree(t->d_exc_flag); t->d_exc_flag = nullptr;
-    (void)hipFree(t->d_queue); t->d_queue = nullptr;
-    HIP_TRY(hipMalloc(&t->d_exc_flag, ((max_reads + 31) / 32) * 4 + 16));
-    HIP_TRY(hipMalloc(&t->d_queue, (3 * max_reads + DCRX_QUEUE_HEADER) * 4));  // [work counters][rescue queue][general list][its exception-list offsets]
-    t->exc_flag_reads = max_reads;
+  if (max_reads > S.exc_flag_reads) {
+    S.exc_flag_reads = 0;
+    S.exc_flag.reset(); S.queue.reset();
+    if ((rc = S.exc_flag.alloc(((max_reads + 31) / 32) + 4))) return rc;
+    if ((rc = S.queue.alloc(3 * max_reads + DCRX_QUEUE_HEADER))) return rc;  // [work counters][rescue queue][general list][its exception-list offsets]
+    S.exc_flag_reads = max_reads;
     t->ws_dirty = true;
   }
   if (t->host.rel.v2_ok && stride <= DCRX_FAST_MAX_STRIDE) {
     // the lists between the v2 kernels: every wave of the scan kernel (16 per CU) owns a region of tail and of event
     // entries; an entry carries the read's packed words, so the size follows the stride
     uint64_t tr = 0, er = 0;
-    v2_list_rows(max_reads, stride, t->plan.n_cu, &tr, &er);
+    v2_list_rows(max_reads, stride, P.n_cu, &tr, &er);
     // (the fused form: 150-nt shapes, pair tables of up to 64 KB — launch_v2; either frame may be asked for)
     if (t->want_tail < 0)
       t->want_tail = (stride <= 40 && std::max(t->host.rel.v2[0].trans_bytes, t->host.rel.v2[1].trans_bytes) <= 64u * 1024u) ? 0 : 1;
-    if (t->want_tail && tr > t->plan.v2_tail_rows) {
-      (void)hipFree(t->d_v2_tail); t->d_v2_tail = nullptr; t->plan.v2_tail = nullptr; t->plan.v2_tail_rows = 0;
-      HIP_TRY(hipMalloc(&t->d_v2_tail, tr * 16));
-      t->plan.v2_tail = reinterpret_cast<uint4 *>(t->d_v2_tail); t->plan.v2_tail_rows = tr;
+    if (t->want_tail && tr > P.v2_tail_rows) {
+      P.v2_tail_rows = 0;
+      if ((rc = S.v2_tail.alloc(tr))) return rc;
+      P.v2_tail_rows = tr;
     }
-    if (er > t->plan.v2_event_rows || v2_slow_rows(max_reads, stride, t->plan.n_cu) > t->plan.v2_slow_rows) {
-      (void)hipFree(t->d_v2_events); (void)hipFree(t->d_v2_counts); (void)hipFree(t->d_v2_slow);
-      t->d_v2_events = nullptr; t->d_v2_counts = nullptr; t->d_v2_slow = nullptr;
-      t->plan.v2_events = nullptr; t->plan.v2_slow = nullptr;
-      t->plan.v2_event_rows = t->plan.v2_slow_rows = 0;
-      const uint64_t sr = v2_slow_rows(max_reads, stride, t->plan.n_cu);
-      HIP_TRY(hipMalloc(&t->d_v2_events, er * 16));
-      HIP_TRY(hipMalloc(&t->d_v2_slow, sr * 16));
-      HIP_TRY(hipMalloc(&t->d_v2_counts, (size_t)t->plan.n_cu * 16 * 16));
-      HIP_TRY(hipMemset(t->d_v2_counts, 0, (size_t)t->plan.n_cu * 16 * 16));      // (no hint yet of a region's last share of tail reads: scan2_kernel, V2_L_TWHINT)
-      if (!t->d_v2_acc) { HIP_TRY(hipMalloc(&t->d_v2_acc, DCRX_N_COUNTERS * 8)); t->ws_dirty = true; }
-      t->plan.v2_acc = t->d_v2_acc;
-      if (!t->d_v2_left) {      // V2_LEFT_CAP entries of 32-word reads, and a valid word per entry (zero between launches)
-        const size_t left_bytes = (size_t)1024 * ((1 + 2 * DCRX_V2_NWLONG + 3) / 4) * 16 + 1024 * 4;
-        HIP_TRY(hipMalloc(&t->d_v2_left, left_bytes));
-        HIP_TRY(hipMemset(t->d_v2_left, 0, left_bytes));
+    if (er > P.v2_event_rows || v2_slow_rows(max_reads, stride, P.n_cu) > P.v2_slow_rows) {
+      P.v2_event_rows = P.v2_slow_rows = 0;
+      S.v2_events.reset(); S.v2_counts.reset(); S.v2_slow.reset();
+      const uint64_t sr = v2_slow_rows(max_reads, stride, P.n_cu);
+      if ((rc = S.v2_events.alloc(er)) || (rc = S.v2_slow.alloc(sr)) || (rc = S.v2_counts.alloc((size_t)P.n_cu * 16 * 4))) return rc;
+      HIP_TRY(hipMemset(S.v2_counts, 0, (size_t)P.n_cu * 16 * 16));      // (no hint yet of a region's last share of tail reads: scan2_kernel, V2_L_TWHINT)
+      if (!S.v2_acc) {
+        if ((rc = S.v2_acc.alloc(DCRX_N_COUNTERS))) return rc;
+        t->ws_dirty = true;
       }
-      t->plan.v2_left = reinterpret_cast<uint4 *>(t->d_v2_left);
-      t->plan.v2_events = reinterpret_cast<uint4 *>(t->d_v2_events);
-      t->plan.v2_slow = reinterpret_cast<uint4 *>(t->d_v2_slow);
-      t->plan.v2_counts = t->d_v2_counts; t->plan.v2_event_rows = er; t->plan.v2_slow_rows = sr;
-      if (!t->v2_side) {     // the two side streams (tail kernel; general form over list X) and the events that fork them off the caller's stream and join them back
-        if (hipStreamCreateWithFlags(&t->v2_side, hipStreamNonBlocking) != hipSuccess) t->v2_side = nullptr;
-        if (t->v2_side && hipStreamCreateWithFlags(&t->v2_side2, hipStreamNonBlocking) != hipSuccess) t->v2_side2 = nullptr;
-        if (t->v2_side && (!t->v2_side2 || hipEventCreateWithFlags(&t->v2_ev_fork, hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&t->v2_ev_join, hipEventDisableTiming) != hipSuccess ||
-                           hipEventCreateWithFlags(&t->v2_ev_join2, hipEventDisableTiming) != hipSuccess)) {
-          (void)hipStreamDestroy(t->v2_side); t->v2_side = nullptr;
-          if (t->v2_side2) { (void)hipStreamDestroy(t->v2_side2); t->v2_side2 = nullptr; }
+      if (!S.v2_left) {      // V2_LEFT_CAP entries of 32-word reads, and a valid word per entry (zero between launches)
+        const size_t left_rows = (size_t)1024 * ((1 + 2 * DCRX_V2_NWLONG + 3) / 4) + 1024 / 4;
+        DevBuf<uint4> left;
+        if ((rc = left.alloc(left_rows))) return rc;
+        HIP_TRY(hipMemset(left, 0, left_rows * 16));
+        S.v2_left = std::move(left);
+      }
+      P.v2_event_rows = er; P.v2_slow_rows = sr;
+      if (!S.v2_side) {     // the two side streams (tail kernel; general form over list X) and the events that fork them off the caller's stream and join them back
+        // (a device that gives no more streams or events: the launches then do without the side streams)
+        if (S.v2_side.create() || S.v2_side2.create() || S.v2_ev_fork.create(false) || S.v2_ev_join.create(false) || S.v2_ev_join2.create(false)) {
+          S.v2_side.reset(); S.v2_side2.reset();
         }
       }
-      t->plan.v2_side = t->v2_side; t->plan.v2_side2 = t->v2_side2;
-      t->plan.v2_ev_fork = t->v2_ev_fork; t->plan.v2_ev_join = t->v2_ev_join; t->plan.v2_ev_join2 = t->v2_ev_join2;
     }
   }
+  return DCRX_OK;
+}
+
+// The one place the plan's pointers come from: the owners, as they stand after whatever grow_workspace did (or could not do).
+static void fill_plan(DeviceState &S) {
+  LaunchPlan &P = S.plan;
+  P.dev_tables = S.d_dev;
+  P.tune = S.tune;
+  P.v2_tail = S.v2_tail; P.v2_events = S.v2_events; P.v2_slow = S.v2_slow; P.v2_counts = S.v2_counts;
+  P.v2_left = S.v2_left; P.v2_acc = S.v2_acc;
+  P.v2_side = S.v2_side; P.v2_side2 = S.v2_side2;
+  P.v2_ev_fork = S.v2_ev_fork; P.v2_ev_join = S.v2_ev_join; P.v2_ev_join2 = S.v2_ev_join2;
+}
+
+static int ensure_device(dcrx_tables *t, uint64_t max_reads, uint32_t stride = 40, hipStream_t stream = nullptr) {
+  int rc = grow_workspace(t, max_reads, stride);
+  DeviceState &S = t->state;
+  fill_plan(S);
+  if (rc) return rc;
   if (t->ws_dirty) {
     // the kernels leave the work counters and the exception bitmap zeroed; they are zeroed here
     // only once per allocation, or after a launch that failed part-way
     // on the stream the kernels will run on (a non-blocking stream does not order against the null stream)
-    HIP_TRY(hipMemsetAsync(t->d_exc_flag, 0, ((t->exc_flag_reads + 31) / 32) * 4 + 16, stream));
-    HIP_TRY(hipMemsetAsync(t->d_queue, 0, DCRX_QUEUE_HEADER * 4, stream));
-    if (t->d_v2_acc) HIP_TRY(hipMemsetAsync(t->d_v2_acc, 0, DCRX_N_COUNTERS * 8, stream));
+    HIP_TRY(hipMemsetAsync(S.exc_flag, 0, ((S.exc_flag_reads + 31) / 32) * 4 + 16, stream));
+    HIP_TRY(hipMemsetAsync(S.queue, 0, DCRX_QUEUE_HEADER * 4, stream));
+    if (S.v2_acc) HIP_TRY(hipMemsetAsync(S.v2_acc, 0, DCRX_N_COUNTERS * 8, stream));
     // dcrx_reserve_device and the host-buffer entry come here with the null stream: the fills must have landed before a
     // later call's kernels start on a non-blocking stream of the caller's, which nothing orders against the null stream
     if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
@@ -405,21 +369,22 @@ static int ensure_device(dcrx_tables *t, uint64_t max_reads, uint32_t stride = 4
 // The device side of the tuple sink for batches of up to max_reads reads: the regions' slabs of items, their counters and
 // the descriptor the kernels read (allocated on the first call that needs them, grown by a larger batch: synchronises).
 static int ensure_sink(dcrx_tables *t, uint64_t max_reads, hipStream_t stream) {
-  const uint64_t want = v2_sink_items(std::max<uint64_t>(max_reads, 4096), t->plan.n_cu);
-  const uint32_t regions = t->plan.n_cu;
-  if (t->d_sink && want <= t->sink_items_cap && regions <= t->sink_regions_cap) return DCRX_OK;
+  DeviceState &S = t->state;
+  const uint64_t want = v2_sink_items(std::max<uint64_t>(max_reads, 4096), S.plan.n_cu);
+  const uint32_t regions = S.plan.n_cu;
+  if (S.sink && want <= S.sink_items_cap && regions <= S.sink_regions_cap) return DCRX_OK;
   HIP_TRY(hipStreamSynchronize(stream));
-  (void)hipFree(t->d_sink_items); (void)hipFree(t->d_sink_ctr); (void)hipFree(t->d_sink);
-  t->d_sink_items = nullptr; t->d_sink_ctr = nullptr; t->d_sink = nullptr; t->sink_items_cap = 0; t->sink_regions_cap = 0;
-  HIP_TRY(hipMalloc(&t->d_sink_items, want * 8));
-  HIP_TRY(hipMalloc(&t->d_sink_ctr, ((size_t)2 * regions + 16) * 4));
-  HIP_TRY(hipMemset(t->d_sink_ctr, 0, ((size_t)2 * regions + 16) * 4));
-  HIP_TRY(hipMalloc(&t->d_sink, sizeof(V2SinkDev)));
+  S.sink_items.reset(); S.sink_ctr.reset(); S.sink.reset();
+  S.sink_items_cap = 0; S.sink_regions_cap = 0;
+  int rc;
+  if ((rc = S.sink_items.alloc(want)) || (rc = S.sink_ctr.alloc((size_t)2 * regions + 16))) return rc;
+  HIP_TRY(hipMemset(S.sink_ctr, 0, ((size_t)2 * regions + 16) * 4));
+  if ((rc = S.sink.alloc(1))) return rc;
   V2SinkDev D;
-  D.late = t->d_sink_ctr + regions; D.ticket = t->d_sink_ctr + 2 * regions;      // (the regions' counts of decombined reads in front: V2SinkCall::hits)
-  D.j_tag_len = t->dev.g[1].tag_len; D.j_jump = t->dev.g[1].jump;
-  HIP_TRY(hipMemcpy(t->d_sink, &D, sizeof D, hipMemcpyHostToDevice));
-  t->sink_items_cap = want; t->sink_regions_cap = regions;
+  D.late = S.sink_ctr + regions; D.ticket = S.sink_ctr + 2 * regions;      // (the regions' counts of decombined reads in front: V2SinkCall::hits)
+  D.j_tag_len = S.dev.g[1].tag_len; D.j_jump = S.dev.g[1].jump;
+  HIP_TRY(hipMemcpy(S.sink, &D, sizeof D, hipMemcpyHostToDevice));
+  S.sink_items_cap = want; S.sink_regions_cap = regions;
   return DCRX_OK;
 }
 
@@ -471,13 +436,13 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   BatchDev B;
   B.packed = b->packed; B.stride = b->stride; B.read_len = b->read_len; B.lens = b->lens;
   B.n_reads = b->n_reads; B.n_exc = b->n_exc; B.exc_read = b->exc_read; B.exc_pos = b->exc_pos;
-  B.exc_chr = b->exc_chr; B.exc_flag = t->d_exc_flag;
+  B.exc_chr = b->exc_chr; B.exc_flag = t->state.exc_flag;
   CfgDev C{cfg->orientation, cfg->allow_ns, cfg->lenthreshold, cfg->flags};
-  t->plan.ev_step_start = t->ev_step_start; t->plan.ev_step_stop = t->ev_step_stop;
+  t->state.plan.ev_step_start = t->ev_step_start; t->state.plan.ev_step_stop = t->ev_step_stop;
   // the call's tuple sink: the kernels' own (tuples of up to 40 bits, the shipped launch shape: launch_v2), else a compaction
   // of the records behind the call, on the same stream
   bool sink_done = false;
-  t->plan.sink = V2SinkJob{};
+  t->state.plan.sink = V2SinkJob{};
   TupleLayoutDev LD{};
   if (t->sink_on) {
     if (t->sink_slots < b->n_reads) return set_err(DCRX_E_INVALID, "tuple sink: the message holds fewer read slots than the batch has reads");
@@ -493,14 +458,14 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
     if (t->sink_layout.bits <= 40 && t->host.rel.v2_ok && b->stride <= DCRX_FAST_MAX_STRIDE) {
       rc = ensure_sink(t, b->n_reads, (hipStream_t)stream);
       if (rc) return rc;
-      V2SinkJob &J = t->plan.sink;
-      J.dev = t->d_sink; J.items = static_cast<uint2 *>(t->d_sink_items); J.hits = t->d_sink_ctr; J.items_cap = t->sink_items_cap; J.regions_cap = t->sink_regions_cap;
+      V2SinkJob &J = t->state.plan.sink;
+      J.dev = t->state.sink; J.items = static_cast<uint2 *>(t->state.sink_items); J.hits = t->state.sink_ctr; J.items_cap = t->state.sink_items_cap; J.regions_cap = t->state.sink_regions_cap;
       J.wpack = LD.w_v | (LD.w_j << 5) | (LD.w_vdel << 10) | (LD.w_jdel << 15) | (LD.w_pos << 20);
       J.bytes = LD.bytes; J.msg = t->sink_msg; J.n_slots = t->sink_slots; J.d_total = t->sink_total; J.done = &sink_done;
     }
   }
-  hipError_t le = launch_decombine(t->plan, t->dev, B, C, d_records, t->d_queue + DCRX_QUEUE_HEADER,
-                                   t->d_queue + DCRX_QUEUE_HEADER + t->exc_flag_reads, t->d_queue, d_counters,
+  hipError_t le = launch_decombine(t->state.plan, t->state.dev, B, C, d_records, t->state.queue + DCRX_QUEUE_HEADER,
+                                   t->state.queue + DCRX_QUEUE_HEADER + t->state.exc_flag_reads, t->state.queue, d_counters,
                                    (hipStream_t)stream, t->ev_start, t->ev_stop);
   if (le == hipErrorNotReady && !t->want_tail) {
     // the launch keeps the tail a role of the finishing launch (a frame whose table does not fuse, an A/B switch) and the handle
@@ -511,12 +476,12 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
     t->want_tail = 1;
     t->ws_dirty = true;
     rc = ensure_device(t, b->n_reads, b->stride, (hipStream_t)stream);
-    if (rc) { t->plan.sink = V2SinkJob{}; return rc; }
-    le = launch_decombine(t->plan, t->dev, B, C, d_records, t->d_queue + DCRX_QUEUE_HEADER, t->d_queue + DCRX_QUEUE_HEADER + t->exc_flag_reads,
-                          t->d_queue, d_counters, (hipStream_t)stream, t->ev_start, t->ev_stop);
+    if (rc) { t->state.plan.sink = V2SinkJob{}; return rc; }
+    le = launch_decombine(t->state.plan, t->state.dev, B, C, d_records, t->state.queue + DCRX_QUEUE_HEADER, t->state.queue + DCRX_QUEUE_HEADER + t->state.exc_flag_reads,
+                          t->state.queue, d_counters, (hipStream_t)stream, t->ev_start, t->ev_stop);
   }
-  t->plan.sink = V2SinkJob{};
-  if (le != hipSuccess) { t->ws_dirty = true; return hip_err(le, "launch_decombine"); }
+  t->state.plan.sink = V2SinkJob{};
+  if (le != hipSuccess) { t->ws_dirty = true; return hip_fail(le, "launch_decombine"); }
   if (t->sink_on && !sink_done) {
     uint32_t *tc = nullptr; uint64_t *to = nullptr;
     rc = compact_workspace(b->n_reads, &tc, &to);
@@ -583,30 +548,31 @@ static HostLayout host_layout(const dcrx_batch_t *hb) {
 
 // the handle's staging buffers hold at least `bytes`, on the device and pinned on the host
 static int ensure_staging(dcrx_tables *t, size_t bytes) {
-  if (bytes > t->stage_bytes) {
-    (void)hipFree(t->d_stage); t->d_stage = nullptr; t->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&t->d_stage, bytes));
-    t->stage_bytes = bytes;
+  DeviceState &S = t->state;
+  int rc;
+  if (bytes > S.stage_bytes) {
+    S.stage_bytes = 0;
+    if ((rc = S.d_stage.alloc(bytes))) return rc;
+    S.stage_bytes = bytes;
   }
-  if (bytes > t->h_stage_bytes) {
-    if (t->h_stage) (void)hipHostFree(t->h_stage);
-    t->h_stage = nullptr; t->h_stage_bytes = 0;
-    HIP_TRY(hipHostMalloc(&t->h_stage, bytes, hipHostMallocDefault));
-    t->h_stage_bytes = bytes;
+  if (bytes > S.h_stage_bytes) {
+    S.h_stage_bytes = 0;
+    if ((rc = S.h_stage.alloc(bytes))) return rc;
+    S.h_stage_bytes = bytes;
   }
   return DCRX_OK;
 }
 
 // the handle's host-entry streams that a call asks for (each made once), and the events that order them
 static int ensure_host_streams(dcrx_tables *t, bool in, bool run, bool out) {
-  if (in && !t->hs_in) HIP_TRY(hipStreamCreateWithFlags(&t->hs_in, hipStreamNonBlocking));
-  if (run && !t->hs_run) HIP_TRY(hipStreamCreateWithFlags(&t->hs_run, hipStreamNonBlocking));
-  if (out && !t->hs_out) HIP_TRY(hipStreamCreateWithFlags(&t->hs_out, hipStreamNonBlocking));
-  for (int k = 0; k < 2; k++) {
-    if (!t->hev_in[k]) HIP_TRY(hipEventCreateWithFlags(&t->hev_in[k], hipEventDisableTiming));
-    if (!t->hev_run[k]) HIP_TRY(hipEventCreateWithFlags(&t->hev_run[k], hipEventDisableTiming));
-    if (!t->hev_out[k]) HIP_TRY(hipEventCreateWithFlags(&t->hev_out[k], hipEventDisableTiming));
-  }
+  DeviceState &S = t->state;
+  int rc;
+  if (in && !S.hs_in && (rc = S.hs_in.create())) return rc;
+  if (run && !S.hs_run && (rc = S.hs_run.create())) return rc;
+  if (out && !S.hs_out && (rc = S.hs_out.create())) return rc;
+  for (Event *set : {S.hev_in, S.hev_run, S.hev_out})
+    for (int k = 0; k < 2; k++)
+      if (!set[k] && (rc = set[k].create(false))) return rc;
   return DCRX_OK;
 }
 
@@ -642,7 +608,7 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
     if (rc) return rc;
     for (int k = 0; k < DCRX_N_COUNTERS; k++) counters[c][k] = 0;
   }
-  hipStream_t s_in = T[0]->hs_in;
+  hipStream_t s_in = T[0]->state.hs_in;
   auto out_at = [&](uint32_t c, int set) { return (c == 0 ? 2 * Lay.in_bytes : 0) + (size_t)set * Lay.out_bytes; };
   const bool in_direct = n && host_pinned(hb->packed) && host_pinned(hb->packed + (size_t)n * hb->stride - 1);
   bool out_direct[DCRX_MAX_CHAINS];
@@ -654,8 +620,8 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
     const int set = (int)(k & 1);
     const uint64_t c0 = k * chunk, cn = std::min<uint64_t>(chunk, n - c0);
     for (uint32_t c = 0; c < nc; c++) {
-      HIP_TRY(hipEventSynchronize(T[c]->hev_out[set]));
-      const uint8_t *h = T[c]->h_stage + out_at(c, set);
+      HIP_TRY(hipEventSynchronize(T[c]->state.hev_out[set]));
+      const uint8_t *h = T[c]->state.h_stage + out_at(c, set);
       if (cn && !out_direct[c] && !counts) par_memcpy(records[c] + c0, h, cn * sizeof(dcrx_record_t));
       const uint64_t *hc = reinterpret_cast<const uint64_t *>(h + Lay.o_cnt);
       for (int i = 0; i < DCRX_N_COUNTERS; i++) counters[c][i] += hc[i];
@@ -665,7 +631,7 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
   for (uint64_t k = 0; k < n_chunks; k++) {
     const int set = (int)(k & 1);
     const uint64_t c0 = k * chunk, cn = n ? std::min<uint64_t>(chunk, n - c0) : 0;
-    uint8_t *h = T[0]->h_stage + (size_t)set * Lay.in_bytes, *d = T[0]->d_stage + (size_t)set * Lay.in_bytes;
+    uint8_t *h = T[0]->state.h_stage + (size_t)set * Lay.in_bytes, *d = T[0]->state.d_stage + (size_t)set * Lay.in_bytes;
     // chunk k - 2's records leave the pinned buffers on a helper thread while this thread fills the input set (several
     // threads: one memcpy does not keep up with the link; the input and output sets do not overlap), once the copy in of
     // chunk k - 2, which read the same bytes, is over
@@ -673,7 +639,7 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
     std::thread helper;
     if (k >= 2) helper = std::thread([&, k] { drc = drain(k - 2); });
     struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_helper{helper};
-    if (k >= 2) HIP_TRY(hipEventSynchronize(T[0]->hev_in[set]));
+    if (k >= 2) HIP_TRY(hipEventSynchronize(T[0]->state.hev_in[set]));
     const uint64_t e0 = exc_at;
     while (exc_at < hb->n_exc && hb->exc_read[exc_at] < c0 + cn) exc_at++;
     const uint64_t ne = exc_at - e0;
@@ -686,14 +652,14 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
     if (drc) return drc;
     // copy in, once every chain's kernels that read this input set (chunk k - 2) are over
     if (k >= 2)
-      for (uint32_t c = 0; c < nc; c++) HIP_TRY(hipStreamWaitEvent(s_in, T[c]->hev_run[set], 0));
+      for (uint32_t c = 0; c < nc; c++) HIP_TRY(hipStreamWaitEvent(s_in, T[c]->state.hev_run[set], 0));
     if (in_direct) {
       HIP_TRY(hipMemcpyAsync(d, hb->packed + c0 * hb->stride, cn * hb->stride, hipMemcpyHostToDevice, s_in));
       if (Lay.in_bytes > Lay.o_lens) HIP_TRY(hipMemcpyAsync(d + Lay.o_lens, h + Lay.o_lens, Lay.in_bytes - Lay.o_lens, hipMemcpyHostToDevice, s_in));
     } else {
       HIP_TRY(hipMemcpyAsync(d, h, Lay.in_bytes, hipMemcpyHostToDevice, s_in));
     }
-    HIP_TRY(hipEventRecord(T[0]->hev_in[set], s_in));
+    HIP_TRY(hipEventRecord(T[0]->state.hev_in[set], s_in));
     dcrx_batch_t db = *hb;
     db.n_reads = cn;
     db.packed = d;
@@ -706,27 +672,27 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
     for (uint32_t c = 0; c < nc; c++) {
       dcrx_tables *t = T[c];
       // (one chain: the handle's out stream, beside the next chunk's kernels; several: behind the chain's kernels)
-      const hipStream_t s_out = nc == 1 ? t->hs_out : t->hs_run;
-      uint8_t *od = t->d_stage + out_at(c, set), *oh = t->h_stage + out_at(c, set);
-      HIP_TRY(hipStreamWaitEvent(t->hs_run, T[0]->hev_in[set], 0));
+      const hipStream_t s_out = nc == 1 ? t->state.hs_out : t->state.hs_run;
+      uint8_t *od = t->state.d_stage + out_at(c, set), *oh = t->state.h_stage + out_at(c, set);
+      HIP_TRY(hipStreamWaitEvent(t->state.hs_run, T[0]->state.hev_in[set], 0));
       // (the records of chunk k - 2 have left this output set: a copy out on the run stream itself is ordered already)
-      if (k >= 2 && s_out != t->hs_run) HIP_TRY(hipStreamWaitEvent(t->hs_run, t->hev_out[set], 0));
-      rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(od), reinterpret_cast<uint64_t *>(od + Lay.o_cnt), t->hs_run);
+      if (k >= 2 && s_out != t->state.hs_run) HIP_TRY(hipStreamWaitEvent(t->state.hs_run, t->state.hev_out[set], 0));
+      rc = dcrx_decombine_device(t, cfg, &db, reinterpret_cast<dcrx_record_t *>(od), reinterpret_cast<uint64_t *>(od + Lay.o_cnt), t->state.hs_run);
       if (rc) return rc;          // (host_entry drains the streams)
       if (counts && cn) {         // the count step reads the packed chunk too: it is among what the next refill of the set waits for
         rc = count_chunk(counts[c], reinterpret_cast<const dcrx_record_t *>(od), &db, index ? first_index : first_index + c0,
-                         index ? index + c0 : nullptr, t->hs_run);
+                         index ? index + c0 : nullptr, t->state.hs_run);
         if (rc) return rc;
       }
-      HIP_TRY(hipEventRecord(t->hev_run[set], t->hs_run));
-      if (s_out != t->hs_run) HIP_TRY(hipStreamWaitEvent(s_out, t->hev_run[set], 0));
+      HIP_TRY(hipEventRecord(t->state.hev_run[set], t->state.hs_run));
+      if (s_out != t->state.hs_run) HIP_TRY(hipStreamWaitEvent(s_out, t->state.hev_run[set], 0));
       if (out_direct[c] || counts) {
         if (cn && !counts) HIP_TRY(hipMemcpyAsync(records[c] + c0, od, cn * sizeof(dcrx_record_t), hipMemcpyDeviceToHost, s_out));
         HIP_TRY(hipMemcpyAsync(oh + Lay.o_cnt, od + Lay.o_cnt, Lay.out_bytes - Lay.o_cnt, hipMemcpyDeviceToHost, s_out));
       } else {
         HIP_TRY(hipMemcpyAsync(oh, od, Lay.out_bytes, hipMemcpyDeviceToHost, s_out));
       }
-      HIP_TRY(hipEventRecord(t->hev_out[set], s_out));
+      HIP_TRY(hipEventRecord(t->state.hev_out[set], s_out));
     }
   }
   for (uint64_t k = n_chunks >= 2 ? n_chunks - 2 : 0; k < n_chunks; k++) { rc = drain(k); if (rc) return rc; }
@@ -735,7 +701,7 @@ static int host_pipeline(dcrx_tables *const *T, uint32_t nc, const dcrx_cfg_t *c
   for (uint32_t c = 0; c < nc; c++)
     if (counters[c][DCRX_C_DEVICE_ERRORS]) return set_err(DCRX_E_HIP, "a device-side wait timed out (the fused scan's ring): the records of this call are incomplete");
   if (counts)
-    for (uint32_t c = 0; c < nc; c++) { rc = count_settle(counts[c], T[c]->hs_run); if (rc) return rc; }
+    for (uint32_t c = 0; c < nc; c++) { rc = count_settle(counts[c], T[c]->state.hs_run); if (rc) return rc; }
   return DCRX_OK;
 }
 
@@ -777,9 +743,9 @@ static int host_entry(dcrx_tables_t *const *T, uint32_t nc, const dcrx_cfg_t *cf
     const std::string keep = g_err;       // (the synchronising calls must not replace the message of what failed)
     for (uint32_t c = 0; c < nc; c++) {
       dcrx_tables *t = T[c];
-      if (t->hs_in) (void)hipStreamSynchronize(t->hs_in);
-      if (t->hs_run) (void)hipStreamSynchronize(t->hs_run);
-      if (t->hs_out) (void)hipStreamSynchronize(t->hs_out);
+      if (t->state.hs_in) (void)hipStreamSynchronize(t->state.hs_in);
+      if (t->state.hs_run) (void)hipStreamSynchronize(t->state.hs_run);
+      if (t->state.hs_out) (void)hipStreamSynchronize(t->state.hs_out);
       t->ws_dirty = true;
     }
     (void)hipGetLastError();
@@ -821,15 +787,21 @@ int dcrx_decombine_chains_count(dcrx_tables_t *const *tables, uint32_t n_chains,
 
 // tile counts and offsets of a compaction: a process-wide slot keyed by device (compaction does not need tables)
 static int compact_workspace(uint64_t n_reads, uint32_t **tc, uint64_t **to) {
-  static thread_local struct { int dev = -1; uint32_t *tc = nullptr; uint64_t *to = nullptr; uint64_t cap = 0; } ws;
+  struct Slot { int dev = -1; DevBuf<uint32_t> tc; DevBuf<uint64_t> to; uint64_t cap = 0; };
+  // One slot per thread, on the heap and never deleted: a thread_local (or static) Slot would run hipFree from a thread-exit
+  // or process-exit destructor, when the HIP runtime may already be gone.  What a thread's last slot holds goes with the process.
+  static thread_local Slot *const slot = new (std::nothrow) Slot;
+  if (!slot) return set_err(DCRX_E_NOMEM, "out of memory");
+  Slot &ws = *slot;
   int dev = -1; HIP_TRY(hipGetDevice(&dev));
   if (ws.dev != dev || n_reads > ws.cap) {
-    if (ws.dev == dev) { (void)hipFree(ws.tc); (void)hipFree(ws.to); }
-    ws.tc = nullptr; ws.to = nullptr; ws.cap = 0; ws.dev = -1;
+    { DeviceGuard on(ws.dev); ws = Slot{}; }
     const size_t tiles = compact_tiles(n_reads) + 1024;
-    HIP_TRY(hipMalloc(&ws.tc, tiles * 4));
-    HIP_TRY(hipMalloc(&ws.to, tiles * 8));
-    ws.dev = dev; ws.cap = n_reads;
+    Slot N;
+    int rc;
+    if ((rc = N.tc.alloc(tiles)) || (rc = N.to.alloc(tiles))) return rc;
+    N.dev = dev; N.cap = n_reads;
+    ws = std::move(N);
   }
   *tc = ws.tc; *to = ws.to;
   return DCRX_OK;
@@ -905,7 +877,7 @@ static int layout_dev(dcrx_tables *t, const dcrx_tuple_layout_t *L, TupleLayoutD
   if (rc) return rc;
   if (std::memcmp(&want, L, sizeof want) != 0) return set_err(DCRX_E_INVALID, "tuple layout does not belong to these tables");
   D->w_v = L->w_v; D->w_j = L->w_j; D->w_vdel = L->w_vdel; D->w_jdel = L->w_jdel; D->w_pos = L->w_pos; D->bytes = L->bytes;
-  D->j_tag_len = t->dev.g[1].tag_len; D->j_jump = t->dev.g[1].jump;
+  D->j_tag_len = t->state.dev.g[1].tag_len; D->j_jump = t->state.dev.g[1].jump;
   return DCRX_OK;
 }
 
@@ -945,7 +917,7 @@ int dcrx_set_tuple_sink(dcrx_tables_t *t, const dcrx_tuple_layout_t *L, void *d_
 int dcrx_tune_state(const dcrx_tables_t *t, int orientation, uint64_t n_reads, dcrx_tune_state_t *out) {
   if (!t || !out) return set_err(DCRX_E_INVALID, "null argument");
   *out = dcrx_tune_state_t{0u, 0u, 0.f, 0.f, 0u, 0u};
-  const V2Tune &F = t->tune[orientation == DCRX_ORIENT_FORWARD ? 0 : 1];
+  const V2Tune &F = t->state.tune[orientation == DCRX_ORIENT_FORWARD ? 0 : 1];
   out->launch_form = F.last_form;
   out->candidates = n_reads >= V2Tune::BIG_BATCH ? (8192u | (4096u << 16)) : (4096u | (3072u << 16));
   const int k = V2Tune::size_class(n_reads);
@@ -957,14 +929,15 @@ int dcrx_tune_state(const dcrx_tables_t *t, int orientation, uint64_t n_reads, d
 
 int dcrx_set_tune_wait(dcrx_tables_t *t, int allow) {
   if (!t) return set_err(DCRX_E_INVALID, "tables is null");
-  for (V2Tune &U : t->tune) U.may_wait = allow != 0;
+  t->tune_may_wait = allow != 0;
+  t->state.plan.tune_may_wait = t->tune_may_wait;
   return DCRX_OK;
 }
 
 int dcrx_set_reserved_cus(dcrx_tables_t *t, uint32_t n_cus) {
   if (!t) return set_err(DCRX_E_INVALID, "tables is null");
   t->reserved_cus = n_cus;
-  t->plan.reserved_cus = n_cus;
+  t->state.plan.reserved_cus = n_cus;
   return DCRX_OK;
 }
 
@@ -1146,7 +1119,7 @@ int dcrx_synth_reads_device(dcrx_tables_t *t, const dcrx_synth_cfg_t *c, uint64_
   if (n && !d_packed) return set_err(DCRX_E_INVALID, "d_packed is null");
   rc = ensure_device(t, 0);
   if (rc) return rc;
-  HIP_TRY(launch_synth(t->dev, synth_params(c), first, n, stride, d_packed, (hipStream_t)stream));
+  HIP_TRY(launch_synth(t->state.dev, synth_params(c), first, n, stride, d_packed, (hipStream_t)stream));
   return DCRX_OK;
 }
 

@@ -34,9 +34,9 @@
 
 #include "../../include/dcrx.h"
 #include "dcrx_count_core.h"
+#include "dcrx_hip.h"
 
-namespace dcrx { int set_err(int code, const char *msg); }
-using dcrx::set_err;
+using namespace dcrx;
 using namespace dcrx_count;
 
 namespace {
@@ -48,17 +48,6 @@ constexpr uint64_t MIN_ARENA = 16u << 20;
 
 // stats words on the device
 enum { ST_ARENA = 0, ST_KEYS = 1, ST_OVERFLOW = 2, ST_WORDS = 4 };
-
-#define HIP_TRY(call)                                                           \
-  do {                                                                          \
-    hipError_t e_ = (call);                                                     \
-    if (e_ != hipSuccess) return hip_fail(e_, #call);                           \
-  } while (0)
-
-int hip_fail(hipError_t e, const char *what) {
-  std::string m = std::string(what) + ": " + hipGetErrorString(e);
-  return set_err((e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? DCRX_E_NOGPU : DCRX_E_HIP, m.c_str());
-}
 
 struct Rec {
   uint32_t v, j, ins_start, ins_len, vdel, jdel, status, frame;
@@ -279,60 +268,51 @@ __global__ __launch_bounds__(BLOCK) void count_text_kernel(const uint64_t *__res
   if (__lane_id() == 0 && sum) atomicAdd(total, sum);
 }
 
-template <class T> int dev_alloc(T **p, uint64_t count) {
-  *p = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<uint64_t>(count, 1) * sizeof(T)));
-  return DCRX_OK;
-}
+// (an allocation of no elements still gives a pointer a kernel may be handed)
+template <class T> int dev_alloc(DevBuf<T> &b, uint64_t count) { return b.alloc(std::max<uint64_t>(count, 1)); }
+
+// the table's columns in device memory, and the table as the kernels take it
+struct TableBufs {
+  DevBuf<uint64_t> tag, hdr, off, count, first;
+  uint64_t mask = 0;
+  Table view() const { return Table{tag, hdr, off, count, first, mask}; }
+};
+
+// one step's work space, for up to n reads of up to slot bases
+struct Work {
+  uint64_t n = 0, slot = 0;
+  DevBuf<uint8_t> scratch, strag, cub;
+  DevBuf<uint64_t> hash[2], run_first;
+  DevBuf<uint32_t> pos[2], head, head_of, run_len, run_strag;
+  size_t cub_bytes = 0;
+};
 
 }  // namespace
 
 struct dcrx_counts {
   int device = -1;
-  Table T{};
+  TableBufs T;
   uint64_t slots = 0;
-  uint8_t *arena = nullptr;
+  DevBuf<uint8_t> arena;
   uint64_t arena_cap = 0;
-  uint64_t *stats = nullptr;        // ST_WORDS on the device
+  DevBuf<uint64_t> stats;           // ST_WORDS on the device
   uint64_t bound_keys = 0, bound_bytes = 0;    // what the table and the arena can hold at most by now
-  // one step's work space, for up to work_n reads of up to work_slot bases
-  uint64_t work_n = 0, work_slot = 0;
-  uint8_t *scratch = nullptr;
-  uint64_t *hash[2] = {nullptr, nullptr};
-  uint32_t *pos[2] = {nullptr, nullptr};
-  uint32_t *head = nullptr, *head_of = nullptr, *run_len = nullptr, *run_strag = nullptr;
-  uint64_t *run_first = nullptr;
-  uint8_t *strag = nullptr;
-  void *cub = nullptr;
-  size_t cub_bytes = 0;
-  uint32_t *index = nullptr;        // the host entries' copy of a chunk's slice of the caller's index
+  Work work;
+  DevBuf<uint32_t> index;           // the host entries' copy of a chunk's slice of the caller's index
   uint64_t index_cap = 0;
   uint64_t hash_mask = NO_KEY >> 1;  // the hash bits a key keeps (dcrx_counts_set_hash_bits)
 };
 
 namespace {
 
-void free_table(Table &T) {
-  (void)hipFree(T.tag); (void)hipFree(T.hdr); (void)hipFree(T.off); (void)hipFree(T.count); (void)hipFree(T.first);
-  T = Table{};
-}
-
-void free_work(dcrx_counts *c) {
-  (void)hipFree(c->scratch);
-  for (int k = 0; k < 2; k++) { (void)hipFree(c->hash[k]); (void)hipFree(c->pos[k]); c->hash[k] = nullptr; c->pos[k] = nullptr; }
-  (void)hipFree(c->head); (void)hipFree(c->head_of); (void)hipFree(c->run_len); (void)hipFree(c->run_strag);
-  (void)hipFree(c->run_first); (void)hipFree(c->strag); (void)hipFree(c->cub);
-  c->scratch = nullptr; c->head = c->head_of = c->run_len = c->run_strag = nullptr; c->run_first = nullptr; c->strag = nullptr;
-  c->cub = nullptr; c->cub_bytes = 0; c->work_n = c->work_slot = 0;
-}
-
-int alloc_table(Table &T, uint64_t slots, hipStream_t s) {
-  T = Table{};
+int alloc_table(TableBufs &T, uint64_t slots, hipStream_t s) {
+  TableBufs N;
   int rc;
-  if ((rc = dev_alloc(&T.tag, slots)) || (rc = dev_alloc(&T.hdr, slots)) || (rc = dev_alloc(&T.off, slots)) ||
-      (rc = dev_alloc(&T.count, slots)) || (rc = dev_alloc(&T.first, slots))) { free_table(T); return rc; }
-  T.mask = slots - 1;
-  HIP_TRY(hipMemsetAsync(T.tag, 0, slots * sizeof(uint64_t), s));
+  if ((rc = dev_alloc(N.tag, slots)) || (rc = dev_alloc(N.hdr, slots)) || (rc = dev_alloc(N.off, slots)) ||
+      (rc = dev_alloc(N.count, slots)) || (rc = dev_alloc(N.first, slots))) return rc;
+  N.mask = slots - 1;
+  HIP_TRY(hipMemsetAsync(N.tag, 0, slots * sizeof(uint64_t), s));
+  T = std::move(N);
   return DCRX_OK;
 }
 
@@ -346,7 +326,7 @@ int check_device(dcrx_counts *c) {
 
 int ensure_stats(dcrx_counts *c, hipStream_t s) {
   if (c->stats) return DCRX_OK;
-  int rc = dev_alloc(&c->stats, ST_WORDS);
+  int rc = dev_alloc(c->stats, ST_WORDS);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(c->stats, 0, ST_WORDS * sizeof(uint64_t), s));
   return DCRX_OK;
@@ -378,52 +358,52 @@ int ensure_room(dcrx_counts *c, hipStream_t s, uint64_t keys, uint64_t bytes) {
   }
   const uint64_t want_slots = std::max<uint64_t>(MIN_SLOTS, pow2_at_least(2 * (c->bound_keys + keys)));
   if (want_slots > c->slots) {
-    Table N;
+    TableBufs N;
     rc = alloc_table(N, want_slots, s);
     if (rc) return rc;
     if (c->slots) {
-      count_rehash_kernel<<<grid_for(c->slots), BLOCK, 0, s>>>(c->T, c->slots, N);
+      count_rehash_kernel<<<grid_for(c->slots), BLOCK, 0, s>>>(c->T.view(), c->slots, N.view());
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipStreamSynchronize(s));
-      free_table(c->T);
     }
-    c->T = N;
+    c->T = std::move(N);
     c->slots = want_slots;
   }
   const uint64_t need = c->bound_bytes + bytes;
   if (need > c->arena_cap) {
     const uint64_t cap = std::max<uint64_t>({MIN_ARENA, need + need / 2, 2 * c->arena_cap});
-    uint8_t *a = nullptr;
-    rc = dev_alloc(&a, cap);
+    DevBuf<uint8_t> a;
+    rc = dev_alloc(a, cap);
     if (rc) return rc;
     if (c->arena && c->bound_bytes) {
       // (the bound is the true figure here: read_stats ran above)
       HIP_TRY(hipMemcpyAsync(a, c->arena, c->bound_bytes, hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipStreamSynchronize(s));
     }
-    (void)hipFree(c->arena);
-    c->arena = a;
+    c->arena = std::move(a);
     c->arena_cap = cap;
   }
   return DCRX_OK;
 }
 
 int ensure_work(dcrx_counts *c, hipStream_t s, uint64_t n, uint64_t slot) {
-  if (n <= c->work_n && n * slot <= c->work_n * c->work_slot) return DCRX_OK;
+  if (n <= c->work.n && n * slot <= c->work.n * c->work.slot) return DCRX_OK;
   HIP_TRY(hipStreamSynchronize(s));         // (the last step on this stream may still read the old buffers)
-  const uint64_t wn = std::max(n, c->work_n), ws = std::max(slot, c->work_slot);
-  free_work(c);
+  const uint64_t wn = std::max(n, c->work.n), ws = std::max(slot, c->work.slot);
+  c->work = Work{};
+  Work W;
   int rc;
-  if ((rc = dev_alloc(&c->scratch, wn * ws)) || (rc = dev_alloc(&c->hash[0], wn)) || (rc = dev_alloc(&c->hash[1], wn)) ||
-      (rc = dev_alloc(&c->pos[0], wn)) || (rc = dev_alloc(&c->pos[1], wn)) || (rc = dev_alloc(&c->head, wn)) ||
-      (rc = dev_alloc(&c->head_of, wn)) || (rc = dev_alloc(&c->run_len, wn)) || (rc = dev_alloc(&c->run_strag, wn)) ||
-      (rc = dev_alloc(&c->run_first, wn)) || (rc = dev_alloc(&c->strag, wn))) { free_work(c); return rc; }
+  if ((rc = dev_alloc(W.scratch, wn * ws)) || (rc = dev_alloc(W.hash[0], wn)) || (rc = dev_alloc(W.hash[1], wn)) ||
+      (rc = dev_alloc(W.pos[0], wn)) || (rc = dev_alloc(W.pos[1], wn)) || (rc = dev_alloc(W.head, wn)) ||
+      (rc = dev_alloc(W.head_of, wn)) || (rc = dev_alloc(W.run_len, wn)) || (rc = dev_alloc(W.run_strag, wn)) ||
+      (rc = dev_alloc(W.run_first, wn)) || (rc = dev_alloc(W.strag, wn))) return rc;
   size_t sort_bytes = 0, scan_bytes = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, c->hash[0], c->hash[1], c->pos[0], c->pos[1], (int)wn, 0, 64, s));
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, c->head, c->head_of, hipcub::Max(), (int)wn, s));
-  c->cub_bytes = std::max(sort_bytes, scan_bytes);
-  if ((rc = dev_alloc(reinterpret_cast<uint8_t **>(&c->cub), c->cub_bytes))) { free_work(c); return rc; }
-  c->work_n = wn; c->work_slot = ws;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, W.hash[0].get(), W.hash[1].get(), W.pos[0].get(), W.pos[1].get(), (int)wn, 0, 64, s));
+  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, W.head.get(), W.head_of.get(), hipcub::Max(), (int)wn, s));
+  W.cub_bytes = std::max(sort_bytes, scan_bytes);
+  if ((rc = dev_alloc(W.cub, W.cub_bytes))) return rc;
+  W.n = wn; W.slot = ws;
+  c->work = std::move(W);
   return DCRX_OK;
 }
 
@@ -435,20 +415,21 @@ int count_step(dcrx_counts *c, const dcrx_record_t *d_records, const dcrx_batch_
   if (rc) return rc;
   rc = ensure_room(c, s, n, n * slot);
   if (rc) return rc;
+  const Work &W = c->work;
   const unsigned g = grid_for(n);
-  count_keys_kernel<<<g, BLOCK, 0, s>>>(d_records, *b, slot, c->hash_mask, c->scratch, c->hash[0], c->pos[0]);
+  count_keys_kernel<<<g, BLOCK, 0, s>>>(d_records, *b, slot, c->hash_mask, W.scratch, W.hash[0], W.pos[0]);
   HIP_TRY(hipGetLastError());
-  size_t tb = c->cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->cub, tb, c->hash[0], c->hash[1], c->pos[0], c->pos[1], (int)n, 0, 64, s));
-  count_heads_kernel<<<g, BLOCK, 0, s>>>(c->hash[1], c->pos[1], n, first_index, d_index, c->head, c->run_strag, c->run_first, c->strag);
+  size_t tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(W.cub.get(), tb, W.hash[0].get(), W.hash[1].get(), W.pos[0].get(), W.pos[1].get(), (int)n, 0, 64, s));
+  count_heads_kernel<<<g, BLOCK, 0, s>>>(W.hash[1], W.pos[1], n, first_index, d_index, W.head, W.run_strag, W.run_first, W.strag);
   HIP_TRY(hipGetLastError());
-  tb = c->cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(c->cub, tb, c->head, c->head_of, hipcub::Max(), (int)n, s));
-  count_members_kernel<<<g, BLOCK, 0, s>>>(d_records, c->hash[1], c->pos[1], c->head_of, n, c->scratch, slot, first_index, d_index,
-                                           c->run_len, c->run_strag, c->run_first, c->strag);
+  tb = W.cub_bytes;
+  HIP_TRY(hipcub::DeviceScan::InclusiveScan(W.cub.get(), tb, W.head.get(), W.head_of.get(), hipcub::Max(), (int)n, s));
+  count_members_kernel<<<g, BLOCK, 0, s>>>(d_records, W.hash[1], W.pos[1], W.head_of, n, W.scratch, slot, first_index, d_index,
+                                           W.run_len, W.run_strag, W.run_first, W.strag);
   HIP_TRY(hipGetLastError());
-  count_insert_kernel<<<g, BLOCK, 0, s>>>(d_records, c->hash[1], c->pos[1], c->head_of, n, c->scratch, slot, first_index, d_index,
-                                          c->run_len, c->run_strag, c->run_first, c->strag, c->T, c->arena, c->arena_cap, c->stats);
+  count_insert_kernel<<<g, BLOCK, 0, s>>>(d_records, W.hash[1], W.pos[1], W.head_of, n, W.scratch, slot, first_index, d_index,
+                                          W.run_len, W.run_strag, W.run_first, W.strag, c->T.view(), c->arena, c->arena_cap, c->stats);
   HIP_TRY(hipGetLastError());
   c->bound_keys += n;
   c->bound_bytes += n * slot;
@@ -465,8 +446,8 @@ int count_chunk(dcrx_counts *c, const dcrx_record_t *d_records, const dcrx_batch
   if (h_index && d_batch->n_reads) {
     if (d_batch->n_reads > c->index_cap) {
       HIP_TRY(hipStreamSynchronize(s));
-      (void)hipFree(c->index); c->index = nullptr; c->index_cap = 0;
-      int rc = dev_alloc(&c->index, d_batch->n_reads);
+      c->index_cap = 0;
+      int rc = dev_alloc(c->index, d_batch->n_reads);
       if (rc) return rc;
       c->index_cap = d_batch->n_reads;
     }
@@ -496,12 +477,7 @@ int dcrx_counts_create(dcrx_counts_t **out) {
 
 void dcrx_counts_destroy(dcrx_counts_t *c) {
   if (!c) return;
-  if (c->device >= 0) {
-    (void)hipDeviceSynchronize();
-    free_table(c->T);
-    free_work(c);
-    (void)hipFree(c->arena); (void)hipFree(c->stats); (void)hipFree(c->index);
-  }
+  if (c->device >= 0) (void)hipDeviceSynchronize();      // (nothing of it is still read when its buffers go)
   delete c;
 }
 
@@ -559,8 +535,8 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
   if (n >= (1ull << 31)) return set_err(DCRX_E_UNSUPPORTED, "dcrx_counts_read: 2^31 or more distinct DCRs");
   if (cap < n || !v || !j || !vdel || !jdel || !count || !first || !ins_off) {
     // sizes only: the key count and the inserts' bytes, no compaction and no sort
-    unsigned long long *d_total = nullptr;
-    rc = dev_alloc(&d_total, 1);
+    DevBuf<unsigned long long> d_total;
+    rc = dev_alloc(d_total, 1);
     if (rc) return rc;
     unsigned long long total = 0;
     hipError_t e = hipMemset(d_total, 0, sizeof(total));
@@ -569,23 +545,19 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(&total, d_total, sizeof(total), hipMemcpyDeviceToHost);
-    (void)hipFree(d_total);
     if (e != hipSuccess) return hip_fail(e, "dcrx_counts_read (sizes)");
     *text_bytes = total;
     return (int64_t)n;
   }
   // the compact list of live slots, ordered by first ordinal, then (stably) by count descending
-  uint64_t *list[2] = {nullptr, nullptr}, *key[2] = {nullptr, nullptr}, *n_list = nullptr;
-  void *tmp = nullptr;
   std::vector<uint64_t> hdr(n), off(n), cnt(n), fst(n);
-  auto release = [&] {
-    for (int k = 0; k < 2; k++) { (void)hipFree(list[k]); (void)hipFree(key[k]); }
-    (void)hipFree(n_list); (void)hipFree(tmp);
-  };
-  auto run = [&]() -> int {
+  auto run = [&]() -> int {       // (its device buffers go when it returns)
+    DevBuf<uint64_t> list_buf[2], key_buf[2], n_list;
+    DevBuf<uint8_t> tmp;
     int r;
-    if ((r = dev_alloc(&list[0], n)) || (r = dev_alloc(&list[1], n)) || (r = dev_alloc(&key[0], n)) ||
-        (r = dev_alloc(&key[1], n)) || (r = dev_alloc(&n_list, 1))) return r;
+    if ((r = dev_alloc(list_buf[0], n)) || (r = dev_alloc(list_buf[1], n)) || (r = dev_alloc(key_buf[0], n)) ||
+        (r = dev_alloc(key_buf[1], n)) || (r = dev_alloc(n_list, 1))) return r;
+    uint64_t *const list[2] = {list_buf[0], list_buf[1]}, *const key[2] = {key_buf[0], key_buf[1]};
     HIP_TRY(hipMemset(n_list, 0, sizeof(uint64_t)));
     count_compact_kernel<<<grid_for(c->slots), BLOCK>>>(c->T.tag, c->slots, list[0], n_list);
     HIP_TRY(hipGetLastError());
@@ -595,15 +567,15 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
     if (!n) return DCRX_OK;
     size_t tb = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key[0], key[1], list[0], list[1], (int)n, 0, 64));
-    if ((r = dev_alloc(reinterpret_cast<uint8_t **>(&tmp), tb))) return r;
+    if ((r = dev_alloc(tmp, tb))) return r;
     count_gather_kernel<<<grid_for(n), BLOCK>>>(c->T.first, list[0], n, 0, key[0]);
     HIP_TRY(hipGetLastError());
     size_t t1 = tb;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, t1, key[0], key[1], list[0], list[1], (int)n, 0, 64));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t1, key[0], key[1], list[0], list[1], (int)n, 0, 64));
     count_gather_kernel<<<grid_for(n), BLOCK>>>(c->T.count, list[1], n, 1, key[0]);
     HIP_TRY(hipGetLastError());
     t1 = tb;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, t1, key[0], key[1], list[1], list[0], (int)n, 0, 64));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t1, key[0], key[1], list[1], list[0], (int)n, 0, 64));
     // list[0]: the slots in most_common() order
     uint64_t *fields[4] = {c->T.hdr, c->T.off, c->T.count, c->T.first};
     std::vector<uint64_t> *host[4] = {&hdr, &off, &cnt, &fst};
@@ -615,7 +587,6 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
     return DCRX_OK;
   };
   rc = run();
-  release();
   if (rc) return rc;
   uint64_t bytes = 0;
   for (uint64_t k = 0; k < n; k++) bytes += header_len(hdr[k]);

@@ -1824,7 +1824,7 @@ static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const Batch
       bool ok = true;
       constexpr int NP = V2TuneSlot::E_PAIRS, FIRST = V2TuneSlot::E_FIRST;
       if (!eslot->ev_e[0][0])
-        for (int a = 0; a < 2 * NP && ok; a++) for (int b = 0; b < 2 && ok; b++) ok = hipEventCreate(&eslot->ev_e[a][b]) == hipSuccess;
+        for (int a = 0; a < 2 * NP && ok; a++) for (int b = 0; b < 2 && ok; b++) ok = eslot->ev_e[a][b].create(true) == DCRX_OK;
       const int k = eslot->e_phase - FIRST;      // index of this launch among the timed ones
       if (!ok) { (void)hipGetLastError(); eslot->fuse_e = 0; }
       else if (k < 0) eslot->e_phase++;
@@ -2006,8 +2006,8 @@ static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const Batch
   if constexpr (CAN_FUSE_E) {
     if (eslot && eslot->fuse_e == -1 && !eslot->e_sampling && !fuse_e && fuse_e_env < 0 && !S.dev && finish) {
       // the class's first launch: its regions' list counts to pinned memory behind the scan (once per handle, frame and size class)
-      bool ok = eslot->h_counts || hipHostMalloc(reinterpret_cast<void **>(&eslot->h_counts), (size_t)4096 * V2_L_COUNTS * 4, hipHostMallocDefault) == hipSuccess;
-      ok = ok && (eslot->ev_counts || hipEventCreateWithFlags(&eslot->ev_counts, hipEventDisableTiming) == hipSuccess);
+      bool ok = eslot->h_counts || eslot->h_counts.alloc((size_t)4096 * V2_L_COUNTS) == DCRX_OK;
+      ok = ok && (eslot->ev_counts || eslot->ev_counts.create(false) == DCRX_OK);
       ok = ok && grid <= 4096u && hipMemcpyAsync(eslot->h_counts, Q.counts, (size_t)grid * V2_L_COUNTS * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
            hipEventRecord(eslot->ev_counts, s) == hipSuccess;
       if (ok) { eslot->e_sampling = true; eslot->e_regions = grid; eslot->e_reads = B.n_reads; }
@@ -2042,7 +2042,7 @@ static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const Batch
           if (!U.created) {
             bool ok = true;
             for (int i = 0; i < V2Tune::SAMPLES && ok; i++)
-              ok = hipEventCreate(&U.ev[i][0]) == hipSuccess && hipEventCreate(&U.ev[i][1]) == hipSuccess;
+              ok = U.ev[i][0].create(true) == DCRX_OK && U.ev[i][1].create(true) == DCRX_OK;
             U.created = ok;
             if (!ok) { (void)hipGetLastError(); U.choice = waves_first; }
           }
@@ -2051,7 +2051,7 @@ static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const Batch
           // (a big batch's samples may be waited for, once, where the caller has said so — dcrx_set_tune_wait —: a caller that queues
           // such launches ahead of the device — each takes milliseconds — would otherwise never find them complete; without that
           // permission the call keeps its contract of never waiting and the handle stays on the first setting until a query succeeds)
-          if (big && k == V2Tune::SAMPLES && P.tune[o].may_wait) (void)hipEventSynchronize(U.ev[V2Tune::SAMPLES - 1][1]);      // (only where the caller allowed it: dcrx_set_tune_wait)
+          if (big && k == V2Tune::SAMPLES && P.tune_may_wait) (void)hipEventSynchronize(U.ev[V2Tune::SAMPLES - 1][1]);      // (only where the caller allowed it: dcrx_set_tune_wait)
           bool ready = true;
           for (int i = 0; i < V2Tune::SAMPLES && ready; i++) ready = hipEventQuery(U.ev[i][1]) == hipSuccess;
           (void)hipGetLastError();

@@ -7,6 +7,7 @@
 
 #include "../../include/dcrx.h"
 #include "dcrx_device.h"
+#include "dcrx_hip.h"
 
 #include "dcrx_launch_types.h"
 
@@ -55,19 +56,19 @@ struct V2TuneSlot {
   static constexpr int SAMPLES = 2;      // (one per setting — the two differ by a tenth of the launch, samples by a hundredth —: launches 1 and 2 of a size class, so that a caller's third or fourth launch finds them complete and runs on the choice)
   uint32_t choice = 0;               // rescue waves once settled (0: not yet)
   int launches = 0;                  // launches seen in this size class
-  hipEvent_t ev[SAMPLES][2] = {};    // (start, stop) of the finishing launch of sample k
-  bool created = false;
+  Event ev[SAMPLES][2];              // (start, stop) of the finishing launch of sample k
+  bool created = false;              // all of them exist
   // list E inside the scan kernel (FUSE_E) or a role of the finishing launch: decided once per size class from the share of the
   // reads that were list-E entries in the class's first launch (the regions' counts copied to pinned memory behind that launch,
   // read when the copy's event has passed: no wait)
   int fuse_e = -1;                   // -1 not known yet, -2 the share allows it: the two forms are being timed, 0 a role, 1 inside the scan
   static constexpr int E_PAIRS = 3, E_FIRST = 8;      // pairs of timed launches (a role, fused), from the class's E_FIRST-th eligible launch on (the clocks have come up by then)
   int e_phase = 0;                   // (fuse_e == -2) eligible launches seen: E_FIRST + 2 k runs as a role under a pair of events, E_FIRST + 2 k + 1 fused; then the events are read
-  hipEvent_t ev_e[2 * E_PAIRS][2] = {};      // (start on the scan's dispatch, stop on the finishing launch's) per timed launch
+  Event ev_e[2 * E_PAIRS][2];        // (start on the scan's dispatch, stop on the finishing launch's) per timed launch
   float us_e[2] = {0.f, 0.f};        // what the samples said: mean of the launches with list E a role / inside the scan
   bool e_sampling = false;
-  hipEvent_t ev_counts = nullptr;
-  uint32_t *h_counts = nullptr;      // pinned, V2_L_COUNTS words per region
+  Event ev_counts;
+  PinnedBuf<uint32_t> h_counts;      // V2_L_COUNTS words per region
   uint32_t e_regions = 0;
   uint64_t e_reads = 0;
   float e_share = -1.f;
@@ -80,7 +81,6 @@ struct V2Tune {
   static constexpr int CLASSES = 12;
   static constexpr uint64_t BIG_BATCH = 1ull << 25;      // reads: from here a handle chooses between 8 192 and 4 096 rescue waves (below: 4 096 and 3 072)
   V2TuneSlot slot[CLASSES];
-  bool may_wait = false;             // dcrx_set_tune_wait: the fourth call of a big-batch size class may wait for the third's finishing launch, once
   uint32_t last_form = 0;            // the frame's last call: 0 none yet, 1 the three-launch form, 2 the v2 kernels (tail as a role), 3 v2 with the tail inside the scan
   static int size_class(uint64_t n_reads) {      // -1: below a million reads (not tuned)
     if (n_reads < (1ull << 20)) return -1;
@@ -112,7 +112,8 @@ struct LaunchPlan {
   // those kernels' own dispatches (hipExtLaunchKernelGGL): a separate event record costs the stream ~10 us of gap each
   hipEvent_t ev_step_start = nullptr, ev_step_stop = nullptr;
   V2SinkJob sink;              // set per call while a tuple sink is on (dcrx_set_tuple_sink)
-  V2Tune *tune = nullptr;      // [2]: per frame (the handle owns them)
+  V2Tune *tune = nullptr;      // [2]: per frame (the handle owns them, and with them the events and pinned counts launch_v2 makes in their slots)
+  bool tune_may_wait = false;  // dcrx_set_tune_wait: the fourth call of a big-batch size class may wait for the third's finishing launch, once
 };
 
 hipError_t launch_decombine(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,

@@ -29,10 +29,10 @@
 #include <vector>
 
 #include "../../include/dcrx.h"
+#include "dcrx_hip.h"
 #include "dcrx_merge_core.h"
 
 namespace dcrx {
-int set_err(int code, const char *msg);
 // dcrx_api.cpp: the handle's window rows (n_v rows for V, then n_j for J) on the current device
 int merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v, uint32_t *n_j);
 }
@@ -44,17 +44,6 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int TILE = 256;        // staged entries per step: 8 KB of junctions + 2 KB of counts
 constexpr uint64_t ALIGN = 256;
-
-#define HIP_TRY(call)                                                           \
-  do {                                                                          \
-    hipError_t e_ = (call);                                                     \
-    if (e_ != hipSuccess) return hip_fail(e_, #call);                           \
-  } while (0)
-
-int hip_fail(hipError_t e, const char *what) {
-  std::string m = std::string("merge: ") + what + ": " + hipGetErrorString(e);
-  return set_err((e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? DCRX_E_NOGPU : DCRX_E_HIP, m.c_str());
-}
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 inline uint64_t aligned(uint64_t bytes) { return (bytes + ALIGN - 1) & ~(ALIGN - 1); }
@@ -264,17 +253,16 @@ int plan_work(uint64_t n, WorkPlan *W) {
 // device memory of one call of the host entry: ONE allocation, carved into 256-byte aligned buffers (a first pass over the
 // same requests, with no memory behind it, adds up the size)
 struct Pool {
-  uint8_t *base = nullptr;
+  dcrx::DevBuf<uint8_t> base;
   uint64_t at = 0;
-  ~Pool() { (void)hipFree(base); }
   template <class T> void get(T **p, uint64_t count) {
     *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
     at += aligned(std::max<uint64_t>(count, 1) * sizeof(T));
   }
   int allocate() {
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&base), std::max<uint64_t>(at, 1)));
+    const int rc = base.alloc(std::max<uint64_t>(at, 1));
     at = 0;
-    return DCRX_OK;
+    return rc;
   }
 };
 

@@ -19,11 +19,9 @@
 #include <vector>
 
 #include "../../include/dcrx.h"
+#include "dcrx_hip.h"
 
-namespace dcrx {
-int set_err(int code, const char *msg);
-}
-using dcrx::set_err;
+using namespace dcrx;
 
 namespace {
 
@@ -84,30 +82,24 @@ int nccl_err(Rccl *R, ncclResult_t e, const char *what) {
   std::string m = std::string(what) + ": " + (R && R->GetErrorString ? R->GetErrorString(e) : "RCCL error") + " (" + std::to_string((int)e) + ")";
   return set_err(DCRX_E_HIP, m.c_str());
 }
-int hip_fail(hipError_t e, const char *what) {
-  std::string m = std::string(what) + ": " + hipGetErrorString(e);
-  (void)hipGetLastError();
-  return set_err(DCRX_E_HIP, m.c_str());
-}
 #define NCCL_TRY(R, call) do { ncclResult_t e_ = (call); if (e_ != ncclSuccess) return nccl_err(R, e_, #call); } while (0)
-#define HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
 
 }  // namespace
 
 struct dcrx_comm {
   ncclComm_t comm = nullptr;
   int world = 0, rank = 0, device = 0;
-  uint64_t *d_scratch = nullptr;      // [2 + world]: a count, a barrier word, the ranks' counts
-  uint64_t *h_scratch = nullptr;      // pinned, [2 + world]
+  DevBuf<uint64_t> d_scratch;             // [2 + world]: a count, a barrier word, the ranks' counts
+  PinnedBuf<uint64_t> h_scratch;          // [2 + world]
 };
 
 namespace {
 int finish_create(Rccl *R, dcrx_comm *c) {
-  HIP_TRY(hipMalloc(&c->d_scratch, (size_t)(2 + c->world) * 8));
-  HIP_TRY(hipMemset(c->d_scratch, 0, (size_t)(2 + c->world) * 8));
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_scratch), (size_t)(2 + c->world) * 8, hipHostMallocDefault));
   (void)R;
-  return DCRX_OK;
+  int rc = c->d_scratch.alloc((size_t)(2 + c->world));
+  if (rc) return rc;
+  HIP_TRY(hipMemset(c->d_scratch, 0, (size_t)(2 + c->world) * 8));
+  return c->h_scratch.alloc((size_t)(2 + c->world));
 }
 }  // namespace
 
@@ -174,8 +166,7 @@ int dcrx_comm_create_all(int world, const int *devices, dcrx_comm_t **out) {
 void dcrx_comm_destroy(dcrx_comm_t *c) {
   if (!c) return;
   Rccl *R = rccl();
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
-  if (c->h_scratch) (void)hipHostFree(c->h_scratch);
+  c->d_scratch.reset(); c->h_scratch.reset();      // (before the communicator goes, as ever)
   if (R && c->comm) (void)R->CommDestroy(c->comm);
   delete c;
 }
@@ -245,34 +236,28 @@ int dcrx_comm_allgather_host(dcrx_comm_t *c, const void *h_in, void *h_out, uint
   if (!bytes_per_rank) return DCRX_OK;
   if (c->world == 1) { std::memcpy(h_out, h_in, (size_t)bytes_per_rank); return DCRX_OK; }
   Rccl *R = rccl();
-  void *d_in = nullptr, *d_out = nullptr;
-  HIP_TRY(hipMalloc(&d_in, (size_t)bytes_per_rank));
-  hipError_t he = hipMalloc(&d_out, (size_t)bytes_per_rank * (size_t)c->world);
-  if (he != hipSuccess) { (void)hipFree(d_in); return hip_fail(he, "hipMalloc"); }
-  int rc = DCRX_OK;
-  he = hipMemcpy(d_in, h_in, (size_t)bytes_per_rank, hipMemcpyHostToDevice);
-  if (he != hipSuccess) rc = hip_fail(he, "hipMemcpy");
-  if (!rc) { ncclResult_t e = R->AllGather(d_in, d_out, (size_t)bytes_per_rank, ncclUint8, c->comm, nullptr); if (e != ncclSuccess) rc = nccl_err(R, e, "ncclAllGather"); }
-  if (!rc) { he = hipStreamSynchronize(nullptr); if (he != hipSuccess) rc = hip_fail(he, "hipStreamSynchronize"); }
-  if (!rc) { he = hipMemcpy(h_out, d_out, (size_t)bytes_per_rank * (size_t)c->world, hipMemcpyDeviceToHost); if (he != hipSuccess) rc = hip_fail(he, "hipMemcpy"); }
-  (void)hipFree(d_in); (void)hipFree(d_out);
-  return rc;
+  DevBuf<uint8_t> d_in, d_out;
+  int rc;
+  if ((rc = d_in.alloc((size_t)bytes_per_rank)) || (rc = d_out.alloc((size_t)bytes_per_rank * (size_t)c->world))) return rc;
+  HIP_TRY(hipMemcpy(d_in, h_in, (size_t)bytes_per_rank, hipMemcpyHostToDevice));
+  NCCL_TRY(R, R->AllGather(d_in, d_out, (size_t)bytes_per_rank, ncclUint8, c->comm, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(h_out, d_out, (size_t)bytes_per_rank * (size_t)c->world, hipMemcpyDeviceToHost));
+  return DCRX_OK;
 }
 
 int dcrx_comm_allreduce_host_u64(dcrx_comm_t *c, uint64_t *h_inout, uint64_t n, int op) {
   if (!c || (n && !h_inout) || op < 0 || op > 1) return set_err(DCRX_E_INVALID, "dcrx_comm_allreduce_host_u64: bad argument");
   if (!n || c->world == 1) return DCRX_OK;
   Rccl *R = rccl();
-  uint64_t *d = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), (size_t)n * 8));
-  int rc = DCRX_OK;
-  hipError_t he = hipMemcpy(d, h_inout, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (he != hipSuccess) rc = hip_fail(he, "hipMemcpy");
-  if (!rc) { ncclResult_t e = R->AllReduce(d, d, (size_t)n, ncclUint64, op == DCRX_COMM_SUM ? ncclSum : ncclMax, c->comm, nullptr); if (e != ncclSuccess) rc = nccl_err(R, e, "ncclAllReduce"); }
-  if (!rc) { he = hipStreamSynchronize(nullptr); if (he != hipSuccess) rc = hip_fail(he, "hipStreamSynchronize"); }
-  if (!rc) { he = hipMemcpy(h_inout, d, (size_t)n * 8, hipMemcpyDeviceToHost); if (he != hipSuccess) rc = hip_fail(he, "hipMemcpy"); }
-  (void)hipFree(d);
-  return rc;
+  DevBuf<uint64_t> d;
+  const int rc = d.alloc((size_t)n);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(d, h_inout, (size_t)n * 8, hipMemcpyHostToDevice));
+  NCCL_TRY(R, R->AllReduce(d, d, (size_t)n, ncclUint64, op == DCRX_COMM_SUM ? ncclSum : ncclMax, c->comm, nullptr));
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(h_inout, d, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return DCRX_OK;
 }
 
 // ---- the whole exchange of one step, in one call ----

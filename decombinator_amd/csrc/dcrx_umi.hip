@@ -18,10 +18,10 @@
 #include <vector>
 
 #include "../../include/dcrx.h"
+#include "dcrx_hip.h"
 #include "dcrx_umi_core.h"
 
-namespace dcrx { int set_err(int code, const char *msg); }
-using dcrx::set_err;
+using namespace dcrx;
 using namespace dcrx_umi;
 
 namespace {
@@ -194,10 +194,7 @@ extern "C" int dcrx_umi_neighbours_device(const uint32_t *d_recs, const uint32_t
                        (unsigned long long *)d_pairs, (unsigned long long)pair_cap, (unsigned long long *)d_total);
     e = hipGetLastError();
   }
-  if (e != hipSuccess) {
-    const std::string m = std::string("dcrx_umi_neighbours_device: ") + hipGetErrorString(e);
-    return set_err(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? DCRX_E_NOGPU : DCRX_E_HIP, m.c_str());
-  }
+  if (e != hipSuccess) return hip_fail(e, "dcrx_umi_neighbours_device");
   return DCRX_OK;
 }
 
@@ -217,28 +214,19 @@ extern "C" int64_t dcrx_umi_neighbours(const char *ascii, const uint64_t *offset
   }
   const int64_t rc = dcrx_umi_encode(ascii, offsets, n, recs.data(), tiles.data());
   if (rc < 0) return rc;
-  uint32_t *d_recs = nullptr, *d_tiles = nullptr;
-  uint64_t *d_pairs = nullptr, *d_total = nullptr, total = 0;
-  int ret = DCRX_OK;
-  hipError_t e = hipMalloc(&d_recs, recs.size() * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_tiles, tiles.size() * 4);
-  if (e == hipSuccess) e = hipMalloc(&d_total, 8);
-  if (e == hipSuccess && pair_cap) e = hipMalloc(&d_pairs, pair_cap * 8);
-  if (e == hipSuccess) e = hipMemcpy(d_recs, recs.data(), recs.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    ret = dcrx_umi_neighbours_device(d_recs, d_tiles, (uint64_t)n_tiles, k, d_pairs, pair_cap, d_total, nullptr);
-    if (ret == DCRX_OK) e = hipStreamSynchronize(nullptr);
-  }
-  if (ret == DCRX_OK && e == hipSuccess) e = hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost);
-  if (ret == DCRX_OK && e == hipSuccess && total <= pair_cap && total)
-    e = hipMemcpy(pairs, d_pairs, total * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(d_recs); (void)hipFree(d_tiles); (void)hipFree(d_pairs); (void)hipFree(d_total);
+  DevBuf<uint32_t> d_recs, d_tiles;
+  DevBuf<uint64_t> d_pairs, d_total;
+  uint64_t total = 0;
+  int ret;
+  if ((ret = d_recs.alloc(recs.size())) || (ret = d_tiles.alloc(tiles.size())) || (ret = d_total.alloc(1)) ||
+      (pair_cap && (ret = d_pairs.alloc(pair_cap)))) return ret;
+  HIP_TRY(hipMemcpy(d_recs, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
+  ret = dcrx_umi_neighbours_device(d_recs, d_tiles, (uint64_t)n_tiles, k, d_pairs, pair_cap, d_total, nullptr);
   if (ret != DCRX_OK) return ret;
-  if (e != hipSuccess) {
-    const std::string m = std::string("dcrx_umi_neighbours: ") + hipGetErrorString(e);
-    return set_err(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? DCRX_E_NOGPU : DCRX_E_HIP, m.c_str());
-  }
+  HIP_TRY(hipStreamSynchronize(nullptr));
+  HIP_TRY(hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost));
+  if (total <= pair_cap && total) HIP_TRY(hipMemcpy(pairs, d_pairs, total * 8, hipMemcpyDeviceToHost));
   if (total <= pair_cap) std::sort(pairs, pairs + total);
   return (int64_t)total;
 }
