@@ -390,6 +390,23 @@ class MergeStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in MERGE_STATS]
 
 
+CLONOTYPE_STATS = ("entries_in", "reads_in", "productive", "productive_reads", "nonproductive", "nonproductive_reads",
+                   "untranslatable", "untranslatable_reads", "clonotypes_out", "convergent", "largest_n_dcrs")
+CLONOTYPE_COLUMNS = ["v_call", "j_call", "junction_aa", "duplicate_count", "n_dcrs", "junction", "decombinator_id", "top_dcr_count"]
+NOT_A_MEMBER = 0xFFFFFFFF      # clonotype_of of an entry that is in no clonotype
+CLONO_MAX_ENTRIES = 1 << 30    # dcrx_clonotypes / dcrx_cdr3_device: DCRX_E_UNSUPPORTED from here on
+E_UNSUPPORTED = -2             # DCRX_E_UNSUPPORTED
+
+
+class ClonotypeStatsC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in CLONOTYPE_STATS]
+
+
+# dcrx_clono_row_t: what dcrx_cdr3_device leaves of an entry (flags: productive, in_frame, stop, conserved_c, conserved_f from bit 0)
+CLONO_ROW_DTYPE = np.dtype([("hash", "<u8"), ("arena_off", "<u8"), ("start_cdr3", "<i4"), ("end_cdr3", "<i4"), ("seq_len", "<u4"),
+                            ("status", "u1"), ("flags", "u1"), ("pad", "<u2")])
+
+
 # every symbol include/dcrx.h and include/dcrx_synth.h declare
 EXPORTS = [
     "dcrx_umi_encode", "dcrx_umi_neighbours_device", "dcrx_umi_neighbours", "dcrx_collapse_group",
@@ -410,6 +427,8 @@ EXPORTS = [
     "dcrx_counts_create", "dcrx_counts_destroy", "dcrx_counts_reset", "dcrx_counts_set_hash_bits", "dcrx_count_device", "dcrx_decombine_count",
     "dcrx_decombine_chains_count", "dcrx_counts_read", "dcrx_format_counts",
     "dcrx_merge_work_bytes", "dcrx_merge_parents_device", "dcrx_merge_dcrs", "dcrx_merge_gather",
+    "dcrx_clono_genes_create", "dcrx_clono_genes_destroy", "dcrx_clono_set_hash_bits", "dcrx_clono_work_bytes", "dcrx_cdr3_device",
+    "dcrx_clonotypes", "dcrx_clonotypes_text", "dcrx_format_clonotypes",
 ]
 
 _lib = None
@@ -534,6 +553,14 @@ def lib():
         "dcrx_merge_work_bytes": (u64, [u64]),
         "dcrx_merge_parents_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, u32, u64, vp, vp, vp, u64, vp]),
         "dcrx_merge_dcrs": (C.c_int64, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, C.POINTER(MergeStatsC)]),
+        "dcrx_clono_genes_create": (i32, [C.POINTER(Cdr3GenesC), vp, vp, C.POINTER(vp)]),
+        "dcrx_clono_genes_destroy": (None, [vp]),
+        "dcrx_clono_set_hash_bits": (i32, [vp, u32]),
+        "dcrx_clono_work_bytes": (u64, [u64, u64]),
+        "dcrx_cdr3_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, u64, vp]),
+        "dcrx_clonotypes": (C.c_int64, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ClonotypeStatsC)]),
+        "dcrx_clonotypes_text": (C.c_int64, [vp, vp, u64]),
+        "dcrx_format_clonotypes": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1123,6 +1150,135 @@ def merge_dcrs(tables: "Tables", counted: dict, distance: int = 1, ratio: int = 
                                         C.byref(st))))
     stats = {k: int(getattr(st, k)) for k in MERGE_STATS}
     return merged_counts(counted, order[:m], cnt[:m], fst[:m]), stats, root_of
+
+
+def call_groups(names) -> np.ndarray:
+    """One call group per gene: genes whose names up to the '*' are equal (the .tsv's v_call / j_call) share a group."""
+    seen: dict = {}
+    return np.array([seen.setdefault(str(x).split("*")[0], len(seen)) for x in names], dtype=np.uint32)
+
+
+class ClonoGenes:
+    """dcrx_clono_genes_t: the gene set of the clonotype step — the tables of a Cdr3Genes, compiled and uploaded once, with the
+    genes' names (their call groups, and the calls the file shows)."""
+
+    def __init__(self, genes: Cdr3Genes, v_names, j_names):
+        if len(v_names) != genes.n_v or len(j_names) != genes.n_j:
+            raise ValueError("one name per gene")
+        self.cdr3 = genes
+        self.v_calls, self.j_calls = ([str(x).split("*")[0] for x in names] for names in (v_names, j_names))
+        self.v_group, self.j_group = call_groups(v_names), call_groups(j_names)
+        h = C.c_void_p()
+        check(lib().dcrx_clono_genes_create(C.byref(genes.c), self.v_group.ctypes.data, self.j_group.ctypes.data, C.byref(h)))
+        self.handle = h
+
+    def set_hash_bits(self, bits: int) -> None:
+        check(lib().dcrx_clono_set_hash_bits(self.handle, int(bits)))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().dcrx_clono_genes_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _entry_arrays(counted: dict):
+    """(v, j, vdel, jdel as int32, count, ins_off as uint64, the inserts' bytes as uint8) of a counted table."""
+    ints = [np.ascontiguousarray(counted[k], dtype=np.int32) for k in ("v", "j", "vdel", "jdel")]
+    cnt, off = (np.ascontiguousarray(counted[k], dtype=np.uint64) for k in ("count", "ins_off"))
+    text = np.frombuffer(counted["ins_text"], np.uint8) if counted["ins_text"] else np.zeros(1, np.uint8)
+    return ints, cnt, off, text
+
+
+def clono_row_fields(rows: np.ndarray, j_pos=None) -> np.ndarray:
+    """The fields dcrx_clono_row_t shares with dcrx_cdr3_row_t, spelled out as include/dcrx.h derives them (CDR3_ROW_DTYPE;
+    seq_off / aa_off stay 0).  j_pos: the J gene's position per row, for the motif window of MOTIF_LEFT rows."""
+    out = np.zeros(len(rows), dtype=CDR3_ROW_DTYPE)
+    for k, r in enumerate(rows):
+        o = out[k]
+        o["status"] = r["status"]
+        if r["status"] == CDR3_BAD_CODON:
+            o["bad_codon_at"] = int(r["start_cdr3"]) & 0xFFFFFFFF
+        if r["status"] not in (CDR3_OK, CDR3_MOTIF_LEFT):
+            continue
+        fl = int(r["flags"])
+        for bit, name in enumerate(("productive", "in_frame", "stop", "conserved_c", "conserved_f")):
+            o[name] = (fl >> bit) & 1
+        sn, start, end = int(r["seq_len"]), int(r["start_cdr3"]), int(r["end_cdr3"])
+        o["seq_len"], o["aa_len"], o["start_cdr3"], o["end_cdr3"] = sn, sn // 3, start, end
+        if r["status"] == CDR3_MOTIF_LEFT:
+            lo, hi, _ = slice(start, None).indices(sn // 3)
+            jp = int(j_pos[k])
+            a, b, _ = slice(jp, jp + 4).indices(max(0, hi - lo))
+            o["junction_aa_off"], o["junction_aa_len"] = lo + a, max(0, b - a)
+        elif fl & 1:
+            lo, hi, _ = slice(start, end).indices(sn // 3)
+            o["junction_aa_off"], o["junction_aa_len"] = lo, max(0, hi - lo)
+            lo, hi, _ = slice(3 * start, 3 * end).indices(sn)
+            o["junction_off"], o["junction_len"] = lo, max(0, hi - lo)
+    return out
+
+
+def clono_work_bytes(n: int, text_bytes: int) -> int:
+    return int(lib().dcrx_clono_work_bytes(int(n), int(text_bytes)))
+
+
+def cdr3_device(genes: ClonoGenes, n: int, d_v, d_j, d_vdel, d_jdel, d_ins_off, d_ins_text, text_bytes: int, d_rows, d_arena,
+                arena_cap: int, d_arena_need, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_device: the calls of every entry of a table in HBM (DeviceBuffers), asynchronous on `stream`."""
+    check(lib().dcrx_cdr3_device(genes.handle, int(n), d_v.ptr, d_j.ptr, d_vdel.ptr, d_jdel.ptr, d_ins_off.ptr,
+                                 d_ins_text.ptr if d_ins_text is not None else None, int(text_bytes), d_rows.ptr,
+                                 d_arena.ptr if d_arena is not None else None, int(arena_cap),
+                                 d_arena_need.ptr if d_arena_need is not None else None, d_work.ptr, int(work_bytes), stream))
+
+
+def clonotypes(genes: ClonoGenes, counted: dict):
+    """dcrx_clonotypes on the current device: the counted table (v, j, vdel, jdel, count, ins_off, ins_text) grouped into
+    clonotypes — (table, statistics dict over CLONOTYPE_STATS, clonotype_of).  table: rep (the representative's rank),
+    duplicate_count, n_dcrs, top_dcr_count per row, and the rows' junction_aa / junction as junc_off (2 rows + 1) into
+    junc_text."""
+    ints, cnt, off, text = _entry_arrays(counted)
+    n = len(ints[0])
+    rep, nd, of = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    dup, top, joff = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(2 * n + 1, np.uint64)
+    st = ClonotypeStatsC()
+    m = check(int(lib().dcrx_clonotypes(genes.handle, n, *[a.ctypes.data for a in ints], cnt.ctypes.data, off.ctypes.data,
+                                        text.ctypes.data, rep.ctypes.data, dup.ctypes.data, nd.ctypes.data, top.ctypes.data,
+                                        joff.ctypes.data, of.ctypes.data, C.byref(st))))
+    need = check(int(lib().dcrx_clonotypes_text(genes.handle, None, 0)))
+    jtext = np.zeros(max(1, need), np.uint8)
+    check(int(lib().dcrx_clonotypes_text(genes.handle, jtext.ctypes.data, need)))
+    table = {"rep": rep[:m].copy(), "duplicate_count": dup[:m].copy(), "n_dcrs": nd[:m].copy(), "top_dcr_count": top[:m].copy(),
+             "junc_off": joff[:2 * m + 1].copy(), "junc_text": jtext[:need].tobytes()}
+    return table, {k: int(getattr(st, k)) for k in CLONOTYPE_STATS}, of
+
+
+def format_clonotypes(genes: ClonoGenes, table: dict, counted: dict) -> bytes:
+    """dcrx_format_clonotypes: the `.clonotypes.tsv` text of a clonotype table over the counted table it came from."""
+    ints, _, off, text = _entry_arrays(counted)
+
+    def blob(strings):
+        bs = [x.encode("latin-1") for x in strings]
+        o = np.zeros(len(bs) + 1, dtype=np.uint32)
+        o[1:] = np.cumsum([len(b) for b in bs])
+        return np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy(), o
+    (vc, vo), (jc, jo) = blob(genes.v_calls), blob(genes.j_calls)
+    m = len(table["rep"])
+    cols = [np.ascontiguousarray(table[k], dtype=t) for k, t in (("rep", np.uint32), ("duplicate_count", np.uint64), ("n_dcrs", np.uint32),
+                                                                 ("top_dcr_count", np.uint64), ("junc_off", np.uint64))]
+    jtext = np.frombuffer(table["junc_text"], np.uint8) if table["junc_text"] else np.zeros(1, np.uint8)
+    args = [m] + [a.ctypes.data for a in cols] + [jtext.ctypes.data, len(ints[0])] + [a.ctypes.data for a in ints] + \
+           [off.ctypes.data, text.ctypes.data, len(genes.v_calls), vc.ctypes.data, vo.ctypes.data, len(genes.j_calls), jc.ctypes.data,
+            jo.ctypes.data]
+    need = check(int(lib().dcrx_format_clonotypes(*args, None, 0)))
+    out = _uninitialised_bytes(max(1, need))
+    check(int(lib().dcrx_format_clonotypes(*args, _bytes_address(out), need)))
+    return bytes(out[:need])
 
 
 def merge_parents_device(tables: "Tables", n: int, d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, d_ins_text, text_bytes: int,

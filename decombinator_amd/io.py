@@ -28,13 +28,14 @@ def create_args_dict(
     writeclusters: bool = False, UMIhistogram: bool = False, nonproductivefilter: bool = False,
     outpath: str = None, dontsave: bool = False, command: str = None, sampling_analysis: bool = False,
     cluster: bool = False, count_dcrs: bool = False, merge_errors: bool = False, merge_distance: int = 1,
-    merge_ratio: int = 10, write_merges: bool = False,
+    merge_ratio: int = 10, write_merges: bool = False, clonotypes: bool = False,
 ) -> dict:
     """The function-argument dictionary threaded through the stages (the reference's 33 keys, `cluster`: run the
     grouping / clustering half of collapse, writing the `.freq`, and `count_dcrs`: with nobarcoding, count the DCRs on the
     GPU and write the `.nbc`; `merge_errors`: fold the counted DCRs within `merge_distance` substitutions of a DCR at least
     `merge_ratio` times as abundant into it before the `.nbc` is written, `write_merges`: list what was folded in a
-    `.merges` file.  The defaults 1 and 10 are a design choice, not a measured optimum)."""
+    `.merges` file.  The defaults 1 and 10 are a design choice, not a measured optimum.  `clonotypes`: translate also groups the
+    counted DCRs by (v_call, j_call, junction_aa) on the GPU and writes `<the .tsv's stem>.clonotypes.tsv`)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -46,7 +47,7 @@ def create_args_dict(
         UMIhistogram=UMIhistogram, nonproductivefilter=nonproductivefilter, outpath=outpath,
         dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster,
         count_dcrs=count_dcrs, merge_errors=merge_errors, merge_distance=merge_distance, merge_ratio=merge_ratio,
-        write_merges=write_merges)
+        write_merges=write_merges, clonotypes=clonotypes)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -106,6 +107,13 @@ def _count_flag(p: argparse.ArgumentParser):
                         "counts (.nbc: v, j, vdel, jdel, insert, count); translate reads such a file")
 
 
+def _clonotypes_flag(p: argparse.ArgumentParser):
+    p.add_argument("--clonotypes", action="store_true",
+                   help="translate, pipeline --cluster / --count-dcrs: group the counted DCRs by V call, J call and CDR3 amino "
+                        "acids on the GPU and write <the .tsv's stem>.clonotypes.tsv beside the .tsv (one row per clonotype: its "
+                        "reads, its DCRs, its most abundant DCR)")
+
+
 def _merge_flags(p: argparse.ArgumentParser):
     p.add_argument("--merge-errors", dest="merge_errors", action="store_true",
                    help="With --count-dcrs: fold every DCR within --merge-distance substitutions (over the junction) of a DCR "
@@ -133,12 +141,12 @@ def create_parser() -> argparse.ArgumentParser:
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
                                            "translate (.n12, .freq, .tsv)")
-    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe); _count_flag(pipe); _merge_flags(pipe)
+    _common(pipe); _decombine(pipe); _later_stage_flags(pipe); _cluster_flag(pipe); _count_flag(pipe); _merge_flags(pipe); _clonotypes_flag(pipe)
     dec = sub.add_parser("decombine", help="Decombine TCR reads")
-    _common(dec); _decombine(dec); _count_flag(dec); _merge_flags(dec)
+    _common(dec); _decombine(dec); _count_flag(dec); _merge_flags(dec); _clonotypes_flag(dec)
     col = sub.add_parser("collapse", help="front half of collapse over an .n12 file: barcode extraction and the row filters "
                                           "(writes .n12u); with --cluster the whole stage (writes .freq)")
-    _common(col); _later_stage_flags(col); _cluster_flag(col); _count_flag(col)
+    _common(col); _later_stage_flags(col); _cluster_flag(col); _count_flag(col); _clonotypes_flag(col)
     col.add_argument("-in", "--infile", type=str, required=True, help=".n12 file of the decombine stage (optionally gzipped)")
     col.add_argument("-N", "--allowNs", action="store_true", help="Allow barcodes containing N")
     col.add_argument("-ln", "--lenthreshold", type=int, default=130, help="Inter-tag length threshold")
@@ -149,7 +157,7 @@ def create_parser() -> argparse.ArgumentParser:
     tr.add_argument("-sp", "--species", type=str, default="human")
     tr.add_argument("-tfdir", "--tagfastadir", type=str, default="Decombinator-Tags-FASTAs")
     tr.add_argument("-nbc", "--nobarcoding", action="store_true")
-    _count_flag(tr)
+    _count_flag(tr); _clonotypes_flag(tr)
     return parser
 
 
@@ -250,18 +258,40 @@ def nbc_suffix(inputargs: dict) -> str:
     return ".nbc" if inputargs["extension"] == "n12" else "." + inputargs["extension"]
 
 
+def _translated_stem(inputargs: dict) -> str:
+    """The `.tsv`'s name without its suffix (write_out_translated's naming rules)."""
+    chainnams = {"a": "alpha", "b": "beta", "g": "gamma", "d": "delta"}
+    filename_id = os.path.basename(inputargs["infile"]).split(".")[0]
+    if inputargs["command"] in ["collapse", "translate"]:
+        return inputargs["outpath"] + f"{filename_id}"
+    return inputargs["outpath"] + inputargs["prefix"] + f"{filename_id}" + f"_{chainnams[inputargs['chain'].lower()]}"
+
+
+def write_out_clonotypes(clonotypes, inputargs: dict):
+    """The clonotype table of --clonotypes beside the `.tsv`: `<the .tsv's stem>.clonotypes.tsv`, tab separated with a header
+    line, gzipped unless dontgzip, mode 666 (the rules of write_out_translated).  `clonotypes`: translate.ClonotypeTable (or
+    anything with text() -> bytes).  Returns the file's name."""
+    outfilename = _translated_stem(inputargs) + ".clonotypes.tsv"
+    text = clonotypes.text()
+    if not inputargs["dontgzip"]:
+        from . import _native as nat
+        print("Compressing clonotype output file to", outfilename + ".gz")
+        with nat.GzipWriter(outfilename + ".gz", level=int(os.environ.get("DCRX_GZIP_LEVEL", "6"))) as gz:
+            gz.write(text)
+        outfilename += ".gz"
+    else:
+        with open(outfilename, "wb") as fh:
+            fh.write(text)
+    sort_permissions(outfilename)
+    return outfilename
+
+
 def write_out_translated(rows, headers, inputargs: dict):
     """The AIRR table of the translate stage (reference io.py:516-548: `DataFrame.to_csv(sep="\t", index=False)`, then the
     gzip step unless dontgzip, then mode 666): `<outpath><file id>.tsv[.gz]` for the translate / collapse commands, the
     pipeline's `<prefix><file id>_<chain name>.tsv[.gz]` otherwise.  A missing value (None) is an empty field, as to_csv
     writes it."""
-    chainnams = {"a": "alpha", "b": "beta", "g": "gamma", "d": "delta"}
-    filename_id = os.path.basename(inputargs["infile"]).split(".")[0]
-    if inputargs["command"] in ["collapse", "translate"]:
-        outfilename = inputargs["outpath"] + f"{filename_id}" + ".tsv"
-    else:
-        outfilename = (inputargs["outpath"] + inputargs["prefix"] + f"{filename_id}"
-                       + f"_{chainnams[inputargs['chain'].lower()]}" + ".tsv")
+    outfilename = _translated_stem(inputargs) + ".tsv"
 
     def lines():
         yield "\t".join(headers) + "\n"

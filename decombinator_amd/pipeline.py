@@ -17,6 +17,32 @@ from .decombine import decombinator
 from .io import cli_args, write_out_counts, write_out_intermediate
 
 
+def clonotype_refusal(inp: dict):
+    """Why --clonotypes cannot run with these arguments, or None: it needs a stage that counts DCRs in front of translate."""
+    if not inp.get("clonotypes"):
+        return None
+    if inp["command"] in ("decombine", "collapse"):
+        return (f"--clonotypes belongs to the translate step: {inp['command']} does not translate (translate --clonotypes, or "
+                "pipeline --cluster / -nbc --count-dcrs with --clonotypes)")
+    if inp["command"] == "pipeline" and not (inp.get("cluster") or inp.get("count_dcrs")):
+        return "--clonotypes needs counted DCRs: run pipeline with --cluster (barcoded) or -nbc --count-dcrs (barcode-free)"
+    if inp["command"] == "translate" and inp.get("nobarcoding") and not inp.get("count_dcrs"):
+        return ("--clonotypes with -nbc needs --count-dcrs and a .nbc file: without counts every row would count 1")
+    return None
+
+
+def _clonotypes_step(inp: dict):
+    """--clonotypes behind cdr3translator: the table (statistics printed and kept), and its file unless dontsave."""
+    from . import translate
+    from .io import write_out_clonotypes
+    table = translate.clonotypes(inp)
+    if inp.get("chain"):
+        translate.chain_clonotype_stats[str(inp["chain"]).lower()] = dict(translate.clonotype_stats)
+    if not inp.get("dontsave"):
+        write_out_clonotypes(table, inp)
+    return table
+
+
 def collapse_front(data, inp):
     """The rows' front half of `collapse` with the stage's own flags (io.py: -ol, -mq, -bm, -aq, -ln, -N).  Returns the
     FrontRows; prints the reference's counters."""
@@ -37,6 +63,9 @@ def _opener(path):
 
 def run(args: Optional[dict[str, Any]] = None, cli_args: Optional[dict[str, Any]] = None):
     inp = cli_args if cli_args else args
+    why = clonotype_refusal(dict(inp, command=inp.get("command") or "pipeline"))
+    if why:
+        raise ValueError(why)
     if dec.chain_list(inp.get("chain")) is not None:
         return run_chains(inp)
     start = datetime.now()
@@ -67,10 +96,14 @@ def _after_decombine(data, inp, start):
         if not inp["dontsave"]:
             write_out_counts(data, inp)
         print("Decombinator complete...")
+        if inp.get("clonotypes"):
+            inp["clonotype_table"] = getattr(data, "counted", None)      # (the arrays the count read out: translate rebuilds nothing)
         data = translate.cdr3translator(inp, data=data)
         print("CDR3translator complete...")
         if not inp["dontsave"]:
             write_out_translated(data, translate.out_headers, inp)
+        if inp.get("clonotypes"):
+            _clonotypes_step(inp)
         print(f"Pipeline complete in {datetime.now() - start}")
         return data
     if not inp["dontsave"]:
@@ -79,6 +112,7 @@ def _after_decombine(data, inp, start):
     if inp.get("cluster"):
         from . import translate
         from .io import write_out_translated
+        inp["clonotype_table"] = None      # (cdr3translator builds it from the rows of the .freq)
         data = collapse.collapsinator(inp, data=data)
         if not inp["dontsave"]:
             write_out_intermediate(data, inp, ".freq")
@@ -87,6 +121,8 @@ def _after_decombine(data, inp, start):
         print("CDR3translator complete...")
         if not inp["dontsave"]:
             write_out_translated(data, translate.out_headers, inp)
+        if inp.get("clonotypes"):
+            _clonotypes_step(inp)
         print(f"Pipeline complete in {datetime.now() - start}")
         return data
     if len(data) and inp.get("oligo") and not inp.get("nobarcoding"):
@@ -98,6 +134,11 @@ def _after_decombine(data, inp, start):
 
 def main(argv=None):
     inp = cli_args(argv)
+    if inp.get("clonotypes"):           # refused before anything is read
+        why = clonotype_refusal(inp)
+        if why:
+            from .io import create_parser
+            create_parser().error(why)
     if inp.get("merge_errors") or inp.get("write_merges") or inp.get("merge_options_given"):
         from .io import create_parser          # (decombine and pipeline alone take these flags)
         try:
@@ -159,6 +200,9 @@ def main(argv=None):
         rows = translate.cdr3translator(inp)
         name = write_out_translated(rows, translate.out_headers, inp)
         print("Translated", translate.counts["line_count"], "DCRs,", translate.counts["prod_recomb"], "productive ->", name)
+        if inp.get("clonotypes"):
+            inp["dontsave"] = False
+            _clonotypes_step(inp)
     else:
         from .io import create_parser
         create_parser().print_help()

@@ -292,6 +292,9 @@ def cdr3translator(inputargs: dict, data=None) -> list:
         meta.append((str(counts["line_count"]), frequency, cluster))
     out = []
     recs = cdr3_batch(pending, out_headers, inputargs) if pending else []
+    if inputargs.get("clonotypes") and inputargs.get("clonotype_table") is None:
+        # (the caller that already holds the counted table as arrays puts it there itself: nothing is rebuilt from the rows)
+        inputargs["clonotype_table"] = counted_table(pending, [m[1] for m in meta], inputargs["command"] == "translate")
     for rec, (sid, frequency, cluster) in zip(recs, meta):
         rec["sequence_id"] = sid
         rec["duplicate_count"] = frequency
@@ -307,3 +310,79 @@ def cdr3translator(inputargs: dict, data=None) -> list:
         print(stop)
         raise SystemExit
     return out
+
+
+# ---- clonotypes (--clonotypes): the counted DCRs grouped by (v_call, j_call, junction_aa) on the GPU; include/dcrx.h holds the contract ----
+clonotype_stats: dict = {}          # the statistics of the last clonotypes() (_native.CLONOTYPE_STATS)
+chain_clonotype_stats: dict = {}    # ... per chain, for `pipeline -c a,b`
+
+
+class UnsupportedMotif(ValueError):
+    """A J gene's motif needs a regular-expression engine: the clonotype step has no CPU fallback."""
+
+
+def counted_table(dcrs, frequencies, from_file: bool = False) -> dict:
+    """The counted table (v, j, vdel, jdel, count, ins_off, ins_text: what DcrCounts.read() gives, as far as the clonotype step
+    reads it) of rows of five DCR fields and their frequencies; row k has rank k.  from_file: the rows are a file's, whose insert
+    carries a blank in front."""
+    import numpy as np
+    ins = [(d[4][1:] if from_file else d[4]).encode("latin-1") for d in dcrs]
+    off = np.zeros(len(ins) + 1, dtype=np.uint64)
+    if ins:
+        off[1:] = np.cumsum([len(b) for b in ins])
+    cols = {k: np.array([int(d[i]) for d in dcrs], dtype=np.int32) for i, k in enumerate(("v", "j", "vdel", "jdel"))}
+    return dict(cols, count=np.array([int(f) for f in frequencies], dtype=np.uint64), ins_off=off, ins_text=b"".join(ins))
+
+
+def _clono_genes(G: GeneInfo):
+    """The gene set of dcrx_clonotypes for a GeneInfo, built (and uploaded) once per GeneInfo object."""
+    from . import _native as nat
+    cached = getattr(G, "_clono", None)
+    if cached is None:
+        cached = nat.ClonoGenes(_native_genes(G), G.v_names, G.j_names)
+        object.__setattr__(G, "_clono", cached)
+    return cached
+
+
+class ClonotypeTable:
+    """What clonotypes() returns: the table of _native.clonotypes over the counted table it came from; text() is the
+    `.clonotypes.tsv`'s, formatted by libdcrx in one pass."""
+
+    def __init__(self, genes, table: dict, counted: dict, stats: dict, clonotype_of):
+        self.genes, self.table, self.counted, self.stats, self.clonotype_of = genes, table, counted, stats, clonotype_of
+
+    def __len__(self):
+        return len(self.table["rep"])
+
+    def text(self) -> bytes:
+        from . import _native as nat
+        return nat.format_clonotypes(self.genes, self.table, self.counted)
+
+
+def clonotypes(inputargs: dict, counted: dict | None = None, genes: GeneInfo | None = None) -> ClonotypeTable:
+    """The clonotype table of a counted table (default: inputargs["clonotype_table"], which cdr3translator() leaves there when
+    inputargs["clonotypes"] is set and the caller has not put the table there itself), after cdr3translator has set the gene
+    information: one call of _native.clonotypes.  Prints the statistics and keeps them in clonotype_stats."""
+    from . import _native as nat
+    global clonotype_stats
+    G = genes if genes is not None else _genes
+    if G is None:
+        raise RuntimeError("set_gene_information() first (the reference's import_gene_information)")
+    counted = counted if counted is not None else inputargs.get("clonotype_table")
+    if counted is None:
+        raise RuntimeError("clonotypes() follows a cdr3translator() run with inputargs['clonotypes']")
+    if len(counted["v"]) >= nat.CLONO_MAX_ENTRIES:
+        raise ValueError(f"--clonotypes takes fewer than {nat.CLONO_MAX_ENTRIES:,} counted DCRs, not {len(counted['v']):,}")
+    cg = _clono_genes(G)
+    try:
+        table, stats, of = nat.clonotypes(cg, counted)
+    except nat.DcrxError as e:
+        if e.code == nat.E_UNSUPPORTED and "motif" in str(e):      # (the message names the J gene and its motif)
+            raise UnsupportedMotif(f"--clonotypes cannot use this gene set: {e}") from None
+        raise
+    clonotype_stats = stats
+    print(f"Clonotypes: {stats['entries_in']:,} DCRs ({stats['reads_in']:,} reads) in; {stats['productive']:,} productive "
+          f"({stats['productive_reads']:,} reads), {stats['nonproductive']:,} non-productive ({stats['nonproductive_reads']:,}), "
+          f"{stats['untranslatable']:,} untranslatable ({stats['untranslatable_reads']:,}); {stats['clonotypes_out']:,} clonotypes, "
+          f"{stats['convergent']:,} of them with several DCRs (at most {stats['largest_n_dcrs']:,})")
+    return ClonotypeTable(cg, table, counted, stats, of)

@@ -688,6 +688,110 @@ typedef struct dcrx_cdr3_row {
 int64_t dcrx_cdr3_batch(const dcrx_cdr3_genes_t *genes, uint64_t n, const int32_t *v, const int32_t *j, const int32_t *vdel,
                         const int32_t *jdel, const char *ins, const uint64_t *ins_off, dcrx_cdr3_row_t *rows, char *text, uint64_t text_cap);
 
+/* ---- clonotypes (`translate --clonotypes`, `pipeline --clonotypes`): the counted DCRs translated and grouped by
+ * (V call, J call, CDR3 amino acids) on the GPU.  The reference stops at one AIRR row per DCR and has no counterpart: the
+ * contract below is this library's own.  The entries only ADD to ABI 5 (nothing that existed changes) ----
+ *
+ * Input: a counted table of n entries (v, j, vdel, jdel, insert, count) — entry k has rank k — and a gene set: the tables of
+ * dcrx_cdr3_genes_t with one call group per gene (genes whose names up to the '*' are equal share a group; the caller
+ * numbers the groups).
+ * Per entry: the calls of dcrx_cdr3_batch, exactly — status, in_frame, stop, conserved_c, conserved_f, productive,
+ *   start_cdr3, end_cdr3, seq_len, aa_len, bad_codon_at, junction_aa_off / _len, junction_off / _len — and for a productive
+ *   entry the bytes of junction_aa and junction.  Python's index and slice rules, Biopython's rules for ambiguity codes and
+ *   gaps, lower case and IUPAC bytes of an insert as dcrx_cdr3_batch documents them.  dcrx_cdr3_batch itself is untouched
+ *   and shares no code with these entries: it is what they are tested against.
+ * Member: an entry with status OK that is productive.  Non-productive entries and entries with status INDEX_ERROR or
+ *   BAD_CODON are left out and counted in the statistics.  An entry with status MOTIF_LEFT (its J gene's motif needs a
+ *   regular-expression engine) makes dcrx_clonotypes return DCRX_E_UNSUPPORTED: there is no CPU fallback.
+ * Clonotype: the members whose keys (V call group, J call group, junction_aa bytes) compare equal in full, whatever the
+ *   junction's length.  A 64-bit hash of the key only sorts candidates next to each other: a hash match alone never merges.
+ * Output, one row per clonotype: duplicate_count = the sum of its members' counts (64 bits), n_dcrs = the number of members,
+ *   the representative = the member with the largest count (ties: the smallest rank) and that count.  Rows are ordered by
+ *   duplicate_count descending, then the representative's rank ascending.  clonotype_of[k] = the row of entry k, UINT32_MAX
+ *   for a non-member.  The result is a function of the input table and the gene set alone: no launch shape, tile size or
+ *   hash width enters it (integer adds, max and min only), and the duplicate_counts add up to the members' counts. */
+typedef struct dcrx_clono_genes dcrx_clono_genes_t;
+
+/* The gene set: the tables are copied, compiled (per V gene its frame-0 translation with its first stop and first invalid
+ * codon, per J gene and phase the translation and "next stop / invalid codon at or after codon k", the motifs as byte
+ * classes) and uploaded once, on the handle's first use on a device; the handle then belongs to that device (DCRX_E_INVALID on
+ * another: create a handle per device).  Not thread-safe.  v_group / j_group: n_v / n_j call
+ * groups.  DCRX_E_UNSUPPORTED when the tables pass 2^31 bytes. */
+int dcrx_clono_genes_create(const dcrx_cdr3_genes_t *genes, const uint32_t *v_group, const uint32_t *j_group,
+                            dcrx_clono_genes_t **out);
+void dcrx_clono_genes_destroy(dcrx_clono_genes_t *genes);
+/* Keeps only the low `bits` bits (0 .. 64; 64 by default) of every key's hash in dcrx_clonotypes.  The results do not
+ * change: with few bits distinct keys share hashes and the full comparisons decide every merge.  For tests; slower. */
+int dcrx_clono_set_hash_bits(dcrx_clono_genes_t *genes, uint32_t bits);
+
+/* One entry as the device leaves it (32 bytes).  flags: bit 0 productive, 1 in_frame, 2 stop, 3 conserved_c, 4 conserved_f.
+ * The other fields of dcrx_cdr3_row_t follow from these, with s[a:b] Python's slice of a string of that length:
+ *   aa_len = seq_len / 3; status BAD_CODON: bad_codon_at = (uint32_t)start_cdr3 (nothing else is set, as in dcrx_cdr3_batch);
+ *   productive and status OK: junction_aa = sequence_aa[start_cdr3 : end_cdr3], junction = sequence[3 start_cdr3 : 3 end_cdr3];
+ *   hash = the clonotype key's hash, arena_off = where junction_aa, then junction, lie in the arena (else both 0);
+ *   status MOTIF_LEFT: the motif window is sequence_aa[start_cdr3:][j_pos : j_pos + 4]. */
+typedef struct dcrx_clono_row {
+  uint64_t hash, arena_off;
+  int32_t start_cdr3, end_cdr3;
+  uint32_t seq_len;
+  uint8_t status, flags;
+  uint16_t pad;
+} dcrx_clono_row_t;
+
+/* Bytes of device work space dcrx_cdr3_device needs for n entries whose inserts take text_bytes bytes. */
+uint64_t dcrx_clono_work_bytes(uint64_t n, uint64_t text_bytes);
+
+/* The primitive: the calls of every entry, asynchronously on `hip_stream`, all arrays in device memory.  d_v, d_j, d_vdel,
+ * d_jdel: n int32 each, as dcrx_cdr3_batch takes them; d_ins_off: n + 1 offsets into d_ins_text (text_bytes bytes; an entry
+ * whose insert would leave them gets status INDEX_ERROR).  d_rows: n rows.  The junction bytes of the productive entries go
+ * into d_arena at exact offsets, back to back in rank order, nothing truncated: a lengths pass, an exclusive scan, then a
+ * write pass (the write pass re-reads an entry through the gene tables, which costs a few look-ups per residue; a fixed slot
+ * per entry would pay for the longest junction n times).  *d_arena_need (device, uint64) receives the bytes the arena takes;
+ * an entry whose bytes would pass arena_cap is not written, so a caller that finds *d_arena_need > arena_cap calls again
+ * with a larger arena (d_arena may be NULL with arena_cap 0 to size it).  d_work: dcrx_clono_work_bytes(n, text_bytes)
+ * bytes, 256-byte aligned; a smaller one is DCRX_E_INVALID, not a launch.  n < 2^30. */
+int dcrx_cdr3_device(dcrx_clono_genes_t *genes, uint64_t n, const int32_t *d_v, const int32_t *d_j, const int32_t *d_vdel,
+                     const int32_t *d_jdel, const uint64_t *d_ins_off, const char *d_ins_text, uint64_t text_bytes,
+                     dcrx_clono_row_t *d_rows, char *d_arena, uint64_t arena_cap, uint64_t *d_arena_need, void *d_work,
+                     uint64_t work_bytes, void *hip_stream);
+
+typedef struct dcrx_clonotype_stats {
+  uint64_t entries_in, reads_in;
+  uint64_t productive, productive_reads;            /* the members */
+  uint64_t nonproductive, nonproductive_reads;      /* status OK, not productive */
+  uint64_t untranslatable, untranslatable_reads;    /* status INDEX_ERROR or BAD_CODON */
+  uint64_t clonotypes_out;
+  uint64_t convergent;                              /* clonotypes with n_dcrs > 1 */
+  uint64_t largest_n_dcrs;
+} dcrx_clonotype_stats_t;
+
+/* The whole step on host arrays, synchronous on the current device: uploads the table, runs the primitive with an arena of
+ * the exact size, sorts the members by (hash, rank) — a stable radix sort —, compares every member's key in full with the
+ * head of its run (members that differ are resolved exactly, in rounds among themselves), adds the totals onto the heads
+ * (integer atomics whose results are not read) and orders the rows with two stable radix sorts.  Row r (r < the return
+ * value): rep_out[r] = the representative's rank, dup_out[r], ndcrs_out[r], top_out[r] = the representative's count; its
+ * junction_aa is text[junc_off_out[2 r] .. junc_off_out[2 r + 1]) and its junction text[junc_off_out[2 r + 1] ..
+ * junc_off_out[2 r + 2]) of the text dcrx_clonotypes_text gives.  The five arrays hold n entries (junc_off_out 2 n + 1),
+ * clonotype_of_out n; stats_out may be NULL.  Returns the number of clonotypes or a negative dcrx_error: DCRX_E_UNSUPPORTED
+ * for a MOTIF_LEFT entry (the message names the J gene and its motif) and for 2^30 entries or more, DCRX_E_INVALID for
+ * offsets that go backwards. */
+int64_t dcrx_clonotypes(dcrx_clono_genes_t *genes, uint64_t n, const int32_t *v, const int32_t *j, const int32_t *vdel,
+                        const int32_t *jdel, const uint64_t *count, const uint64_t *ins_off, const char *ins_text,
+                        uint32_t *rep_out, uint64_t *dup_out, uint32_t *ndcrs_out, uint64_t *top_out, uint64_t *junc_off_out,
+                        uint32_t *clonotype_of_out, dcrx_clonotype_stats_t *stats_out);
+/* The junction text of the handle's last dcrx_clonotypes: returns its bytes, copied to `out` when they fit `cap`. */
+int64_t dcrx_clonotypes_text(dcrx_clono_genes_t *genes, char *out, uint64_t cap);
+
+/* The `.clonotypes.tsv` text of m rows in one pass: a header line, then per row
+ * "v_call j_call junction_aa duplicate_count n_dcrs junction decombinator_id top_dcr_count", tab separated; v_call / j_call
+ * are the representative's gene's call (calls: one text, n_genes + 1 offsets), decombinator_id its "v, j, vdel, jdel, insert".
+ * Returns the bytes the text takes; writes it when out != NULL and it fits out_cap.  Host only. */
+int64_t dcrx_format_clonotypes(uint64_t m, const uint32_t *rep, const uint64_t *dup, const uint32_t *ndcrs, const uint64_t *top,
+                               const uint64_t *junc_off, const char *junc_text, uint64_t n, const int32_t *v, const int32_t *j,
+                               const int32_t *vdel, const int32_t *jdel, const uint64_t *ins_off, const char *ins_text,
+                               uint32_t n_v, const char *v_calls, const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
+                               const uint32_t *j_call_off, char *out, uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
