@@ -11,10 +11,9 @@
 // The host entry (dcrx_clonotypes) adds: the members compacted in rank order, a stable radix sort of (hash, rank), run
 // heads by a max scan, the full-key compare of every member with its run's head — in rounds: what differs from the head
 // stays, and the first of what stays in a run is the next head —, totals onto the heads by integer atomics whose results
-// are not read (add, max, then min of the rank among the members that hold the max), and the rows ordered by two stable
-// radix sorts as the count's read-out does.
+// are not read (add, max, then min of the rank among the members that hold the max), and the rows in most_common() order.
+// The sorts, scans, run heads, compactions and that order are dcrx_group.h's.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -23,10 +22,11 @@
 
 #include "../../include/dcrx.h"
 #include "dcrx_clono_core.h"
-#include "dcrx_hip.h"
+#include "dcrx_group.h"
 
 using dcrx::set_err;
 using namespace dcrx_clono;
+using namespace dcrx_group;
 
 struct dcrx_clono_genes {
   std::vector<uint8_t> blob;
@@ -40,12 +40,7 @@ struct dcrx_clono_genes {
 
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr uint64_t ALIGN = 256;
 constexpr uint64_t MAX_ENTRIES = 1ull << 30;      // (the scans over two words per row count in an int)
-
-inline unsigned grid_for(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-inline uint64_t aligned(uint64_t bytes) { return (bytes + ALIGN - 1) & ~(ALIGN - 1); }
 
 struct Entries {
   const int32_t *v, *j, *vdel, *jdel;
@@ -92,12 +87,6 @@ __global__ __launch_bounds__(BLOCK) void clono_write_kernel(View G, Entries E, u
 
 enum { CS_PROD = 0, CS_PROD_READS, CS_NONPROD, CS_NONPROD_READS, CS_UNTRANS, CS_UNTRANS_READS, CS_READS, CS_MOTIF_LEFT, CS_WORDS };
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-  for (int d = warpSize / 2; d > 0; d >>= 1) x += __shfl_down(x, d);
-  return x;
-}
-
 // who is a member, and the statistics: the block's sums meet in LDS and ONE vector atomic per block (a lane per counter) adds
 // them to the totals
 __global__ __launch_bounds__(BLOCK) void clono_members_kernel(const dcrx_clono_row_t *__restrict__ rows,
@@ -137,20 +126,24 @@ __global__ __launch_bounds__(BLOCK) void clono_members_kernel(const dcrx_clono_r
   }
 }
 
-__global__ __launch_bounds__(BLOCK) void clono_list_kernel(const dcrx_clono_row_t *__restrict__ rows, const uint32_t *__restrict__ flag,
-                                                           const uint32_t *__restrict__ slot, uint32_t n, uint64_t mask,
-                                                           uint64_t *__restrict__ key, uint32_t *__restrict__ rank) {
-  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
-  if (e >= n || !flag[e]) return;
-  key[slot[e]] = rows[e].hash & mask;
-  rank[slot[e]] = e;
-}
+// what the compactions leave at a slot: a member's hash and rank; an active member of the last round
+struct PutMember {
+  const dcrx_clono_row_t *rows;
+  uint64_t mask, *key;
+  uint32_t *rank;
+  __device__ void operator()(uint32_t slot, uint32_t e) const { key[slot] = rows[e].hash & mask; rank[slot] = e; }
+};
+struct PutActive {
+  const uint32_t *src;
+  uint32_t *dst;
+  __device__ void operator()(uint32_t slot, uint32_t i) const { dst[slot] = src[i]; }
+};
 
 __global__ __launch_bounds__(BLOCK) void clono_runs_kernel(const uint64_t *__restrict__ key, uint32_t m, uint32_t *__restrict__ mark,
                                                            uint32_t *__restrict__ active) {
   const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
   if (s >= m) return;
-  mark[s] = (s == 0 || key[s] != key[s - 1]) ? s : 0u;
+  mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
   active[s] = s;
 }
 
@@ -159,7 +152,7 @@ __global__ __launch_bounds__(BLOCK) void clono_round_mark_kernel(const uint32_t 
                                                                  uint32_t a, uint32_t *__restrict__ mark) {
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= a) return;
-  mark[i] = (i == 0 || run[active[i]] != run[active[i - 1]]) ? i : 0u;
+  mark[i] = run_mark(i, [&](uint32_t k) { return run[active[k]]; });
 }
 
 // ... and every other active member against it, in full
@@ -179,15 +172,6 @@ __global__ __launch_bounds__(BLOCK) void clono_round_compare_kernel(View G, Entr
   }
   if (same) head_of[p] = h;
   keep[i] = same ? 0u : 1u;
-}
-
-__global__ __launch_bounds__(BLOCK) void clono_compact_kernel(const uint32_t *__restrict__ src, const uint32_t *__restrict__ keep,
-                                                              const uint32_t *__restrict__ slot, uint32_t a, uint32_t *__restrict__ dst,
-                                                              uint32_t *__restrict__ kept) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a) return;
-  if (keep[i]) dst[slot[i]] = src[i];
-  if (i == a - 1) *kept = slot[i] + keep[i];
 }
 
 __global__ __launch_bounds__(BLOCK) void clono_totals_kernel(const uint32_t *__restrict__ head_of, const uint32_t *__restrict__ rank,
@@ -212,26 +196,6 @@ __global__ __launch_bounds__(BLOCK) void clono_rep_kernel(const uint32_t *__rest
   if (s >= m) return;
   const uint32_t h = head_of[s], e = rank[s];
   if (count[e] == top[h]) atomicMin(&rep[h], e);
-}
-
-__global__ __launch_bounds__(BLOCK) void clono_heads_kernel(const uint32_t *__restrict__ is_head, const uint32_t *__restrict__ slot,
-                                                            uint32_t m, uint32_t *__restrict__ list, uint32_t *__restrict__ heads) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= m) return;
-  if (is_head[s]) list[slot[s]] = s;
-  if (s == m - 1) *heads = slot[s] + is_head[s];
-}
-
-__global__ __launch_bounds__(BLOCK) void clono_key_rep_kernel(const uint32_t *__restrict__ rep, const uint32_t *__restrict__ list,
-                                                              uint32_t c, uint64_t *__restrict__ key) {
-  const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
-  if (r < c) key[r] = rep[list[r]];
-}
-
-__global__ __launch_bounds__(BLOCK) void clono_key_total_kernel(const unsigned long long *__restrict__ total, const uint32_t *__restrict__ list,
-                                                                uint32_t c, uint64_t *__restrict__ key) {
-  const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
-  if (r < c) key[r] = ~(uint64_t)total[list[r]];
 }
 
 // the rows in their final order, and where the representatives' junctions lie
@@ -277,16 +241,15 @@ struct WorkPlan {
   uint64_t len, off, cub, cub_bytes, total;
 };
 
-int plan_work(uint64_t n, WorkPlan *W) {
+int plan_clono_work(uint64_t n, WorkPlan *W) {
   size_t sum_bytes = 0;
-  const int wn = (int)std::max<uint64_t>(n, 1);
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, wn));
-  uint64_t at = 0;
-  auto take = [&](uint64_t bytes) { const uint64_t here = at; at += aligned(std::max<uint64_t>(bytes, 1)); return here; };
-  W->len = take(n * 8); W->off = take(n * 8);
+  const int rc = exclusive_sum_bytes<uint64_t>(std::max<uint64_t>(n, 1), &sum_bytes);
+  if (rc) return rc;
+  Carver C;
+  W->len = C.take(n * 8); W->off = C.take(n * 8);
   W->cub_bytes = sum_bytes;
-  W->cub = take(sum_bytes);
-  W->total = at;
+  W->cub = C.take(sum_bytes);
+  W->total = C.at;
   return DCRX_OK;
 }
 
@@ -310,9 +273,7 @@ int run_lengths(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d
   uint64_t *len = reinterpret_cast<uint64_t *>(w + W.len), *off = reinterpret_cast<uint64_t *>(w + W.off);
   clono_calls_kernel<<<grid_for(n), BLOCK, 0, s>>>(G, E, (uint32_t)n, d_rows, len);
   HIP_TRY(hipGetLastError());
-  size_t tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w + W.cub, tb, len, off, (int)n, s));
-  return DCRX_OK;
+  return exclusive_sum(Scratch{w + W.cub, W.cub_bytes}, len, off, n, s);
 }
 int run_write(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d_rows, uint8_t *w, const WorkPlan &W, uint8_t *d_arena,
               uint64_t arena_cap, uint64_t *d_need, hipStream_t s) {
@@ -321,20 +282,6 @@ int run_write(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d_r
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
-
-struct Pool {      // one allocation carved into 256-byte aligned buffers (a first pass with no memory behind it adds up the size)
-  dcrx::DevBuf<uint8_t> base;
-  uint64_t at = 0;
-  template <class T> void get(T **p, uint64_t count) {
-    *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += aligned(std::max<uint64_t>(count, 1) * sizeof(T));
-  }
-  int allocate() {
-    const int rc = base.alloc(std::max<uint64_t>(at, 1));
-    at = 0;
-    return rc;
-  }
-};
 
 }  // namespace
 
@@ -375,7 +322,7 @@ int dcrx_clono_set_hash_bits(dcrx_clono_genes_t *g, uint32_t bits) {
 uint64_t dcrx_clono_work_bytes(uint64_t n, uint64_t text_bytes) {
   (void)text_bytes;      // (the work space holds per-entry lengths and offsets: the inserts' bytes do not enter it)
   WorkPlan W;
-  if (n >= MAX_ENTRIES || plan_work(n, &W) != DCRX_OK) return 0;
+  if (n >= MAX_ENTRIES || plan_clono_work(n, &W) != DCRX_OK) return 0;
   return W.total;
 }
 
@@ -394,7 +341,7 @@ int dcrx_cdr3_device(dcrx_clono_genes_t *g, uint64_t n, const int32_t *d_v, cons
     return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: null argument");
   if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: the work space is not 256-byte aligned");
   WorkPlan W;
-  int rc = plan_work(n, &W);
+  int rc = plan_clono_work(n, &W);
   if (rc) return rc;
   if (work_bytes < W.total) return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: the work space is smaller than dcrx_clono_work_bytes(n, text_bytes)");
   View G;
@@ -419,25 +366,15 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
     return set_err(DCRX_E_INVALID, "dcrx_clonotypes: null argument");
   for (uint64_t k = 0; k < n; k++)
     if (ins_off[k + 1] < ins_off[k]) return set_err(DCRX_E_INVALID, "dcrx_clonotypes: offsets go backwards");
-  const uint64_t text0 = ins_off[0], text_bytes = ins_off[n] - text0;
+  const uint64_t text_bytes = ins_off[n] - ins_off[0];
   if (text_bytes && !ins_text) return set_err(DCRX_E_INVALID, "dcrx_clonotypes: ins_text is null");
   const uint32_t n32 = (uint32_t)n;
   WorkPlan W;
-  int rc = plan_work(n, &W);
+  int rc = plan_clono_work(n, &W);
   if (rc) return rc;
   size_t cub_bytes = 0;
-  {
-    size_t b = 0;
-    const int wn = (int)n;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, wn, 0, 64));
-    cub_bytes = std::max(cub_bytes, b);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint32_t *)nullptr, (uint32_t *)nullptr, wn));
-    cub_bytes = std::max(cub_bytes, b);
-    HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, b, (uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), wn));
-    cub_bytes = std::max(cub_bytes, b);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t *)nullptr, (uint64_t *)nullptr, 2 * wn));
-    cub_bytes = std::max(cub_bytes, b);
-  }
+  if ((rc = sort_pairs_bytes<uint32_t>(n, 64, &cub_bytes)) || (rc = exclusive_sum_bytes<uint32_t>(n, &cub_bytes)) ||
+      (rc = run_heads_bytes(n, &cub_bytes)) || (rc = exclusive_sum_bytes<uint64_t>(2 * n, &cub_bytes))) return rc;
   View G;
   if ((rc = device_view(g, &G))) return rc;
 
@@ -460,15 +397,7 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
     P.get(&d_jlen, 2 * n); P.get(&d_joff, 2 * n); P.get(&d_kept, 1);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
-  std::vector<uint64_t> off(n + 1);
-  for (uint64_t k = 0; k <= n; k++) off[k] = ins_off[k] - text0;
-  HIP_TRY(hipMemcpy(d_v, v, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_j, j, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_vdel, vdel, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_jdel, jdel, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_count, count, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-  if (text_bytes) HIP_TRY(hipMemcpy(d_text, ins_text + text0, text_bytes, hipMemcpyHostToDevice));
+  if ((rc = upload_table(n, v, j, vdel, jdel, count, ins_off, ins_text, d_v, d_j, d_vdel, d_jdel, d_count, d_off, d_text))) return rc;
   const Entries E{d_v, d_j, d_vdel, d_jdel, d_off, d_text, text_bytes};
 
   // the calls, then an arena of exactly the bytes the junctions take
@@ -508,18 +437,14 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   const uint32_t m32 = (uint32_t)m;
 
   // the members in rank order, sorted (stably) by hash
-  size_t tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_cub, tb, d_flag, d_slot, (int)n));
+  const Scratch cub{d_cub, cub_bytes};
   const uint64_t mask = g->bits >= 64 ? ~0ull : ((1ull << g->bits) - 1);
-  clono_list_kernel<<<grid_for(n), BLOCK>>>(d_rows, d_flag, d_slot, n32, mask, d_key[0], d_rank[0]);
-  HIP_TRY(hipGetLastError());
-  tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_rank[0], d_rank[1], (int)m, 0, 64));
+  if ((rc = compact(cub, d_flag, d_slot, n32, PutMember{d_rows, mask, d_key[0], d_rank[0]}, nullptr, nullptr)) ||      // (their number is m)
+      (rc = sort_pairs(cub, d_key[0], d_key[1], d_rank[0], d_rank[1], m, 64, nullptr))) return rc;
   const uint32_t *d_sorted = d_rank[1];
   clono_runs_kernel<<<grid_for(m), BLOCK>>>(d_key[1], m32, d_mark, d_active[0]);
   HIP_TRY(hipGetLastError());
-  tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_cub, tb, d_mark, d_run, hipcub::Max(), (int)m));
+  if ((rc = run_heads(cub, d_mark, d_run, m, nullptr))) return rc;
 
   // rounds: every active member against the first active member of its run; what differs stays active
   uint32_t a = m32;
@@ -527,14 +452,10 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   while (a) {
     clono_round_mark_kernel<<<grid_for(a), BLOCK>>>(d_active[cur], d_run, a, d_mark);
     HIP_TRY(hipGetLastError());
-    tb = cub_bytes;
-    HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_cub, tb, d_mark, d_first, hipcub::Max(), (int)a));
+    if ((rc = run_heads(cub, d_mark, d_first, a, nullptr))) return rc;
     clono_round_compare_kernel<<<grid_for(a), BLOCK>>>(G, E, d_rows, d_arena, d_sorted, d_active[cur], d_first, a, d_head_of, d_keep);
     HIP_TRY(hipGetLastError());
-    tb = cub_bytes;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_cub, tb, d_keep, d_slot, (int)a));
-    clono_compact_kernel<<<grid_for(a), BLOCK>>>(d_active[cur], d_keep, d_slot, a, d_active[cur ^ 1], d_kept);
-    HIP_TRY(hipGetLastError());
+    if ((rc = compact(cub, d_keep, d_slot, a, PutActive{d_active[cur], d_active[cur ^ 1]}, d_kept, nullptr))) return rc;
     uint32_t left = 0;
     HIP_TRY(hipMemcpy(&left, d_kept, 4, hipMemcpyDeviceToHost));      // (the round's one synchronisation)
     if (left >= a) return set_err(DCRX_E_HIP, "dcrx_clonotypes: a round resolved nothing");      // (the first of every run always resolves)
@@ -551,29 +472,18 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   HIP_TRY(hipGetLastError());
   clono_rep_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, d_count, d_top, m32, d_rep);
   HIP_TRY(hipGetLastError());
-  tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_cub, tb, d_ishead, d_slot, (int)m));
-  clono_heads_kernel<<<grid_for(m), BLOCK>>>(d_ishead, d_slot, m32, d_list[0], d_kept);
-  HIP_TRY(hipGetLastError());
+  if ((rc = compact(cub, d_ishead, d_slot, m32, PutIndex{d_list[0]}, d_kept, nullptr))) return rc;
   uint32_t c = 0;
   HIP_TRY(hipMemcpy(&c, d_kept, 4, hipMemcpyDeviceToHost));
 
   // order: by the representative's rank, then (stably) by duplicate_count descending
-  clono_key_rep_kernel<<<grid_for(c), BLOCK>>>(d_rep, d_list[0], c, d_key[0]);
-  HIP_TRY(hipGetLastError());
-  tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_list[0], d_list[1], (int)c, 0, 32));
-  clono_key_total_kernel<<<grid_for(c), BLOCK>>>(d_total, d_list[1], c, d_key[0]);
-  HIP_TRY(hipGetLastError());
-  tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_list[1], d_list[0], (int)c, 0, 64));
+  if ((rc = most_common_order(cub, d_list, d_key, d_rep, 32, d_total, c, nullptr))) return rc;
   clono_rows_kernel<<<grid_for(c), BLOCK>>>(d_list[0], c, d_total, d_members, d_top, d_rep, d_rows, d_dup, d_nd, d_topo, d_repo, d_rowof, d_jlen);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(d_of, 0xFF, n * 4, nullptr));
   clono_of_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, d_rowof, m32, d_of);
   HIP_TRY(hipGetLastError());
-  tb = cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_cub, tb, d_jlen, d_joff, (int)(2 * c)));
+  if ((rc = exclusive_sum(cub, d_jlen, d_joff, 2 * (uint64_t)c, nullptr))) return rc;
   HIP_TRY(hipMemcpy(junc_off_out, d_joff, 2 * (uint64_t)c * 8, hipMemcpyDeviceToHost));
   uint64_t last_len = 0;
   HIP_TRY(hipMemcpy(&last_len, d_jlen + (2 * (uint64_t)c - 1), 8, hipMemcpyDeviceToHost));

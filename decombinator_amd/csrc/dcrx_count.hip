@@ -23,7 +23,6 @@
 // device) or the arena.  A step that still ran out of room would set a flag that every read-out reports as an error: a key
 // or a count is never dropped silently.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstdio>
@@ -34,15 +33,15 @@
 
 #include "../../include/dcrx.h"
 #include "dcrx_count_core.h"
-#include "dcrx_hip.h"
+#include "dcrx_group.h"
 
 using namespace dcrx;
 using namespace dcrx_count;
+using namespace dcrx_group;
 
 namespace {
 
 constexpr uint64_t TAG_EMPTY = 0, TAG_BUSY = 2;
-constexpr int BLOCK = 256;
 constexpr uint64_t MIN_SLOTS = 1u << 16;
 constexpr uint64_t MIN_ARENA = 16u << 20;
 
@@ -89,14 +88,14 @@ __global__ __launch_bounds__(BLOCK) void count_keys_kernel(const dcrx_record_t *
   hash[r] = key_hash(header(R.v, R.j, R.vdel, R.jdel, R.ins_len), out, R.ins_len) & hash_mask;
 }
 
-// head[i] = i where a run of equal hashes starts, 0 elsewhere (the max scan then gives every position its run's head)
+// the mark of a run of equal hashes (dcrx_group.h: run_heads then gives every position its run's head), and the run's state
 __global__ __launch_bounds__(BLOCK) void count_heads_kernel(const uint64_t *__restrict__ hash, const uint32_t *__restrict__ pos,
                                                             uint64_t n, uint64_t first_index, const uint32_t *__restrict__ index,
                                                             uint32_t *__restrict__ head, uint32_t *__restrict__ run_strag,
                                                             uint64_t *__restrict__ run_first, uint8_t *__restrict__ strag) {
   const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
-  head[i] = (i == 0 || hash[i] != hash[i - 1]) ? (uint32_t)i : 0u;
+  head[i] = run_mark(i, [&](uint64_t k) { return hash[k]; });
   strag[i] = 0;
   run_strag[i] = 0;
   run_first[i] = ordinal(first_index, index, pos[i]);
@@ -238,16 +237,6 @@ __global__ __launch_bounds__(BLOCK) void count_compact_kernel(const uint64_t *__
   if (live) list[base + __popcll(m & ((1ull << __lane_id()) - 1))] = i;
 }
 
-__global__ __launch_bounds__(BLOCK) void count_gather_kernel(const uint64_t *__restrict__ src, const uint64_t *__restrict__ slots,
-                                                             uint64_t n, int negate, uint64_t *__restrict__ dst) {
-  const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t x = src[slots[i]];
-  dst[i] = negate ? ~x : x;
-}
-
-inline unsigned grid_for(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-
 inline uint64_t digits(uint64_t x) { uint64_t d = 1; while (x >= 10) { x /= 10; d++; } return d; }
 inline char *put_u64(char *o, uint64_t x) {
   char t[20];
@@ -263,8 +252,7 @@ __global__ __launch_bounds__(BLOCK) void count_text_kernel(const uint64_t *__res
   unsigned long long sum = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < slots; i += (uint64_t)gridDim.x * BLOCK)
     if (tag[i] & 1u) sum += header_len(hdr[i]);
-#pragma unroll
-  for (int d = warpSize / 2; d > 0; d >>= 1) sum += __shfl_down(sum, d);
+  sum = wave_sum(sum);
   if (__lane_id() == 0 && sum) atomicAdd(total, sum);
 }
 
@@ -397,11 +385,8 @@ int ensure_work(dcrx_counts *c, hipStream_t s, uint64_t n, uint64_t slot) {
       (rc = dev_alloc(W.pos[0], wn)) || (rc = dev_alloc(W.pos[1], wn)) || (rc = dev_alloc(W.head, wn)) ||
       (rc = dev_alloc(W.head_of, wn)) || (rc = dev_alloc(W.run_len, wn)) || (rc = dev_alloc(W.run_strag, wn)) ||
       (rc = dev_alloc(W.run_first, wn)) || (rc = dev_alloc(W.strag, wn))) return rc;
-  size_t sort_bytes = 0, scan_bytes = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, W.hash[0].get(), W.hash[1].get(), W.pos[0].get(), W.pos[1].get(), (int)wn, 0, 64, s));
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, W.head.get(), W.head_of.get(), hipcub::Max(), (int)wn, s));
-  W.cub_bytes = std::max(sort_bytes, scan_bytes);
-  if ((rc = dev_alloc(W.cub, W.cub_bytes))) return rc;
+  if ((rc = sort_pairs_bytes<uint32_t>(wn, 64, &W.cub_bytes)) || (rc = run_heads_bytes(wn, &W.cub_bytes)) ||
+      (rc = dev_alloc(W.cub, W.cub_bytes))) return rc;
   W.n = wn; W.slot = ws;
   c->work = std::move(W);
   return DCRX_OK;
@@ -419,12 +404,11 @@ int count_step(dcrx_counts *c, const dcrx_record_t *d_records, const dcrx_batch_
   const unsigned g = grid_for(n);
   count_keys_kernel<<<g, BLOCK, 0, s>>>(d_records, *b, slot, c->hash_mask, W.scratch, W.hash[0], W.pos[0]);
   HIP_TRY(hipGetLastError());
-  size_t tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(W.cub.get(), tb, W.hash[0].get(), W.hash[1].get(), W.pos[0].get(), W.pos[1].get(), (int)n, 0, 64, s));
+  const Scratch cub{W.cub, W.cub_bytes};
+  if ((rc = sort_pairs<uint32_t>(cub, W.hash[0], W.hash[1], W.pos[0], W.pos[1], n, 64, s))) return rc;
   count_heads_kernel<<<g, BLOCK, 0, s>>>(W.hash[1], W.pos[1], n, first_index, d_index, W.head, W.run_strag, W.run_first, W.strag);
   HIP_TRY(hipGetLastError());
-  tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(W.cub.get(), tb, W.head.get(), W.head_of.get(), hipcub::Max(), (int)n, s));
+  if ((rc = run_heads(cub, W.head, W.head_of, n, s))) return rc;
   count_members_kernel<<<g, BLOCK, 0, s>>>(d_records, W.hash[1], W.pos[1], W.head_of, n, W.scratch, slot, first_index, d_index,
                                            W.run_len, W.run_strag, W.run_first, W.strag);
   HIP_TRY(hipGetLastError());
@@ -566,22 +550,13 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
     if (got != n) return set_err(DCRX_E_HIP, "dcrx_counts_read: the table's live slots differ from its key count");
     if (!n) return DCRX_OK;
     size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key[0], key[1], list[0], list[1], (int)n, 0, 64));
-    if ((r = dev_alloc(tmp, tb))) return r;
-    count_gather_kernel<<<grid_for(n), BLOCK>>>(c->T.first, list[0], n, 0, key[0]);
-    HIP_TRY(hipGetLastError());
-    size_t t1 = tb;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t1, key[0], key[1], list[0], list[1], (int)n, 0, 64));
-    count_gather_kernel<<<grid_for(n), BLOCK>>>(c->T.count, list[1], n, 1, key[0]);
-    HIP_TRY(hipGetLastError());
-    t1 = tb;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t1, key[0], key[1], list[1], list[0], (int)n, 0, 64));
+    if ((r = sort_pairs_bytes<uint64_t>(n, 64, &tb)) || (r = dev_alloc(tmp, tb)) ||
+        (r = most_common_order(Scratch{tmp, tb}, list, key, c->T.first.get(), 64, c->T.count.get(), (uint32_t)n, nullptr))) return r;
     // list[0]: the slots in most_common() order
     uint64_t *fields[4] = {c->T.hdr, c->T.off, c->T.count, c->T.first};
     std::vector<uint64_t> *host[4] = {&hdr, &off, &cnt, &fst};
     for (int f = 0; f < 4; f++) {
-      count_gather_kernel<<<grid_for(n), BLOCK>>>(fields[f], list[0], n, 0, key[1]);
-      HIP_TRY(hipGetLastError());
+      if ((r = gather(fields[f], list[0], (uint32_t)n, 0, key[1], nullptr))) return r;
       HIP_TRY(hipMemcpy(host[f]->data(), key[1], n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return DCRX_OK;

@@ -19,9 +19,8 @@
 //            lanes have.  Every child writes its own parent: no atomics.
 // The host entry (dcrx_merge_dcrs) adds: pointer jumping to the roots (with the depth of every entry), the trees' totals
 // (integer atomicAdd / atomicMin onto the roots, results unused), and the roots compacted in rank order (exclusive scan)
-// and ordered by the two stable radix sorts of the count's read-out.
+// and put in most_common() order.  The sorts, scans, run heads, compaction and order are dcrx_group.h's.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -29,7 +28,7 @@
 #include <vector>
 
 #include "../../include/dcrx.h"
-#include "dcrx_hip.h"
+#include "dcrx_group.h"
 #include "dcrx_merge_core.h"
 
 namespace dcrx {
@@ -38,15 +37,11 @@ int merge_windows(dcrx_tables_t *t, const uint32_t **d_rows, uint32_t *n_v, uint
 }
 using dcrx::set_err;
 using namespace dcrx_merge;
+using namespace dcrx_group;
 
 namespace {
 
-constexpr int BLOCK = 256;
 constexpr int TILE = 256;        // staged entries per step: 8 KB of junctions + 2 KB of counts
-constexpr uint64_t ALIGN = 256;
-
-inline unsigned grid_for(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
-inline uint64_t aligned(uint64_t bytes) { return (bytes + ALIGN - 1) & ~(ALIGN - 1); }
 
 struct Entries {
   const uint16_t *v, *j;
@@ -92,7 +87,7 @@ __global__ __launch_bounds__(BLOCK) void merge_gather_kernel(Entries E, uint32_t
   sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
   sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
   sc[s] = E.count[e];
-  head[s] = (s == 0 || key[s] != key[s - 1]) ? s : 0u;
+  head[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
 }
 
 __global__ __launch_bounds__(BLOCK) void merge_parents_kernel(const uint4 *__restrict__ sj, const uint64_t *__restrict__ sc,
@@ -173,12 +168,6 @@ __global__ __launch_bounds__(BLOCK) void merge_jump_kernel(const uint32_t *__res
 
 enum { MS_OUT_OF_REACH = 0, MS_MERGED = 1, MS_MOVED = 2, MS_CHAIN = 3, MS_WORDS = 4 };
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-  for (int d = warpSize / 2; d > 0; d >>= 1) x += __shfl_down(x, d);
-  return x;
-}
-
 __global__ __launch_bounds__(BLOCK) void merge_totals_kernel(const uint32_t *__restrict__ root, const uint32_t *__restrict__ depth,
                                                              const uint8_t *__restrict__ reach, const uint64_t *__restrict__ count,
                                                              const uint64_t *__restrict__ first, uint32_t n,
@@ -210,61 +199,27 @@ __global__ __launch_bounds__(BLOCK) void merge_totals_kernel(const uint32_t *__r
   }
 }
 
-__global__ __launch_bounds__(BLOCK) void merge_list_kernel(const uint32_t *__restrict__ is_root, const uint32_t *__restrict__ slot,
-                                                           uint32_t n, uint32_t *__restrict__ list) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i < n && is_root[i]) list[slot[i]] = i;
-}
-
-__global__ __launch_bounds__(BLOCK) void merge_pick_kernel(const unsigned long long *__restrict__ src, const uint32_t *__restrict__ list,
-                                                           uint32_t m, int negate, uint64_t *__restrict__ dst) {
-  const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
-  if (k >= m) return;
-  const uint64_t x = src[list[k]];
-  dst[k] = negate ? ~x : x;
-}
-
 struct WorkPlan {
   uint64_t key[2], idx[2], sj, sc, head, bstart, cub, cub_bytes, total;
 };
 
-int plan_work(uint64_t n, WorkPlan *W) {
+int plan_merge_work(uint64_t n, WorkPlan *W) {
   // (the largest of the primitive's sort and scan and of the host entry's scan and 64-bit sorts, which reuse the space)
-  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0, sort64_bytes = 0;
-  const int wn = (int)std::max<uint64_t>(n, 1);
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, wn, 0, (int)KEY_BITS));
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), wn));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, wn));
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort64_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                             (uint32_t *)nullptr, wn, 0, 64));
-  uint64_t at = 0;
-  auto take = [&](uint64_t bytes) { const uint64_t here = at; at += aligned(std::max<uint64_t>(bytes, 1)); return here; };
-  W->key[0] = take(n * 8); W->key[1] = take(n * 8);
-  W->idx[0] = take(n * 4); W->idx[1] = take(n * 4);
-  W->sj = take(n * WORDS * 4); W->sc = take(n * 8);
-  W->head = take(n * 4); W->bstart = take(n * 4);
-  W->cub_bytes = std::max(std::max(sort_bytes, scan_bytes), std::max(sum_bytes, sort64_bytes));
-  W->cub = take(W->cub_bytes);
-  W->total = at;
+  const uint64_t wn = std::max<uint64_t>(n, 1);
+  size_t cub_bytes = 0;
+  int rc;
+  if ((rc = sort_pairs_bytes<uint32_t>(wn, (int)KEY_BITS, &cub_bytes)) || (rc = run_heads_bytes(wn, &cub_bytes)) ||
+      (rc = exclusive_sum_bytes<uint32_t>(wn, &cub_bytes)) || (rc = sort_pairs_bytes<uint32_t>(wn, 64, &cub_bytes))) return rc;
+  Carver C;
+  W->key[0] = C.take(n * 8); W->key[1] = C.take(n * 8);
+  W->idx[0] = C.take(n * 4); W->idx[1] = C.take(n * 4);
+  W->sj = C.take(n * WORDS * 4); W->sc = C.take(n * 8);
+  W->head = C.take(n * 4); W->bstart = C.take(n * 4);
+  W->cub_bytes = cub_bytes;
+  W->cub = C.take(cub_bytes);
+  W->total = C.at;
   return DCRX_OK;
 }
-
-// device memory of one call of the host entry: ONE allocation, carved into 256-byte aligned buffers (a first pass over the
-// same requests, with no memory behind it, adds up the size)
-struct Pool {
-  dcrx::DevBuf<uint8_t> base;
-  uint64_t at = 0;
-  template <class T> void get(T **p, uint64_t count) {
-    *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += aligned(std::max<uint64_t>(count, 1) * sizeof(T));
-  }
-  int allocate() {
-    const int rc = base.alloc(std::max<uint64_t>(at, 1));
-    at = 0;
-    return rc;
-  }
-};
 
 }  // namespace
 
@@ -272,7 +227,7 @@ extern "C" {
 
 uint64_t dcrx_merge_work_bytes(uint64_t n) {
   WorkPlan W;
-  if (n >= (1ull << 31) || plan_work(n, &W) != DCRX_OK) return 0;
+  if (n >= (1ull << 31) || plan_merge_work(n, &W) != DCRX_OK) return 0;
   return W.total;
 }
 
@@ -290,7 +245,7 @@ int dcrx_merge_parents_device(dcrx_tables_t *tables, uint64_t n, const uint16_t 
     return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: null argument");
   if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is not 256-byte aligned");
   WorkPlan W;
-  int rc = plan_work(n, &W);
+  int rc = plan_merge_work(n, &W);
   if (rc) return rc;
   if (work_bytes < W.total) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is smaller than dcrx_merge_work_bytes(n)");
   Entries E{d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, reinterpret_cast<const uint8_t *>(d_ins_text), text_bytes, nullptr, 0, 0};
@@ -306,12 +261,11 @@ int dcrx_merge_parents_device(dcrx_tables_t *tables, uint64_t n, const uint16_t 
   const uint32_t n32 = (uint32_t)n;
   merge_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, key[0], idx[0]);
   HIP_TRY(hipGetLastError());
-  size_t tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(w + W.cub, tb, key[0], key[1], idx[0], idx[1], (int)n, 0, (int)KEY_BITS, s));
+  const Scratch cub{w + W.cub, W.cub_bytes};
+  if ((rc = sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, (int)KEY_BITS, s))) return rc;
   merge_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, key[1], idx[1], sj, sc, head);
   HIP_TRY(hipGetLastError());
-  tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(w + W.cub, tb, head, bstart, hipcub::Max(), (int)n, s));
+  if ((rc = run_heads(cub, head, bstart, n, s))) return rc;
   merge_parents_kernel<<<grid_for(n), BLOCK, 0, s>>>(sj, sc, key[1], idx[1], bstart, n32, distance, ratio, d_parent, d_reach);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
@@ -337,11 +291,11 @@ int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, co
     if (v[k] >= n_v || j[k] >= n_j) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: an entry names a v or j the tables do not have");
     if (ins_off[k + 1] < ins_off[k]) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: offsets go backwards");
   }
-  const uint64_t text0 = ins_off[0], text_bytes = ins_off[n] - text0;
+  const uint64_t text_bytes = ins_off[n] - ins_off[0];
   if (text_bytes && !ins_text) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: ins_text is null");
   const uint32_t n32 = (uint32_t)n;
   const uint64_t work_bytes = dcrx_merge_work_bytes(n);
-  if (!work_bytes) return DCRX_E_HIP;                      // (plan_work left the message)
+  if (!work_bytes) return DCRX_E_HIP;                      // (plan_merge_work left the message)
 
   Pool P;
   uint16_t *d_v, *d_j;
@@ -355,16 +309,8 @@ int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, co
     P.get(&d_r[0], n); P.get(&d_r[1], n); P.get(&d_d[0], n); P.get(&d_d[1], n); P.get(&d_changed, 1); P.get(&d_work, work_bytes);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
-  std::vector<uint64_t> off(n + 1);
-  for (uint64_t k = 0; k <= n; k++) off[k] = ins_off[k] - text0;
-  HIP_TRY(hipMemcpy(d_v, v, n * 2, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_j, j, n * 2, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_vdel, vdel, n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_jdel, jdel, n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_count, count, n * 8, hipMemcpyHostToDevice));
+  if ((rc = upload_table(n, v, j, vdel, jdel, count, ins_off, ins_text, d_v, d_j, d_vdel, d_jdel, d_count, d_off, d_text))) return rc;
   HIP_TRY(hipMemcpy(d_first, first, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-  if (text_bytes) HIP_TRY(hipMemcpy(d_text, ins_text + text0, text_bytes, hipMemcpyHostToDevice));
 
   rc = dcrx_merge_parents_device(tables, n, d_v, d_j, d_vdel, d_jdel, d_count, d_off, reinterpret_cast<const char *>(d_text),
                                  text_bytes, distance, ratio, d_r[0], d_reach, d_work, work_bytes, nullptr);
@@ -401,28 +347,16 @@ int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, co
 
   // the roots in rank order, then by first ordinal, then (stably) by count descending; the work space is free again
   WorkPlan W;
-  if ((rc = plan_work(n, &W))) return rc;
+  if ((rc = plan_merge_work(n, &W))) return rc;
   d_key[0] = reinterpret_cast<uint64_t *>(d_work + W.key[0]); d_key[1] = reinterpret_cast<uint64_t *>(d_work + W.key[1]);
   d_list[0] = reinterpret_cast<uint32_t *>(d_work + W.idx[0]); d_list[1] = reinterpret_cast<uint32_t *>(d_work + W.idx[1]);
-  void *d_cub = d_work + W.cub;
-  size_t tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_cub, tb, d_isroot, d_slot, (int)n));
-  merge_list_kernel<<<grid_for(n), BLOCK>>>(d_isroot, d_slot, n32, d_list[0]);
-  HIP_TRY(hipGetLastError());
-  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tf, d_list[0], m32, 0, d_key[0]);
-  HIP_TRY(hipGetLastError());
-  tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_list[0], d_list[1], (int)m, 0, 64));
-  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tc, d_list[1], m32, 1, d_key[0]);
-  HIP_TRY(hipGetLastError());
-  tb = W.cub_bytes;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_cub, tb, d_key[0], d_key[1], d_list[1], d_list[0], (int)m, 0, 64));
+  const Scratch cub{d_work + W.cub, W.cub_bytes};
+  if ((rc = compact(cub, d_isroot, d_slot, n32, PutIndex{d_list[0]}, nullptr, nullptr)) ||      // (their number is m)
+      (rc = most_common_order(cub, d_list, d_key, d_tf, 64, d_tc, m32, nullptr))) return rc;
   HIP_TRY(hipMemcpy(order_out, d_list[0], m * 4, hipMemcpyDeviceToHost));
-  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tc, d_list[0], m32, 0, d_key[1]);
-  HIP_TRY(hipGetLastError());
+  if ((rc = gather(d_tc, d_list[0], m32, 0, d_key[1], nullptr))) return rc;
   HIP_TRY(hipMemcpy(count_out, d_key[1], m * 8, hipMemcpyDeviceToHost));
-  merge_pick_kernel<<<grid_for(m), BLOCK>>>(d_tf, d_list[0], m32, 0, d_key[1]);
-  HIP_TRY(hipGetLastError());
+  if ((rc = gather(d_tf, d_list[0], m32, 0, d_key[1], nullptr))) return rc;
   HIP_TRY(hipMemcpy(first_out, d_key[1], m * 8, hipMemcpyDeviceToHost));
   if (stats_out) {
     stats_out->roots_out = m;

@@ -155,6 +155,53 @@ def test_degenerate_tables():
     assert len(got[0]["rep"]) == 0 and (got[2] == nat.NOT_A_MEMBER).all()
 
 
+def _synonymous_pairs(G, n, seed=31):
+    """n rows of equal count: every rank k with k % 3 == 1 is non-productive (a stop codon in frame), the others are pairs of
+    synonymous productive DCRs (one junction_aa, every codon spelt differently) whose two members lie half a table apart;
+    where that leaves an odd number of them, the last is non-productive too."""
+    import random
+    rnd = random.Random(seed + n)
+    syn = collections.defaultdict(list)
+    for c in cu._SENSE:
+        syn[translate.translate_nt(c)].append(c)
+    two = sorted(a for a in syn if len(syn[a]) > 1)
+    members = [k for k in range(n) if k % 3 != 1]
+    members = members[:len(members) // 2 * 2]
+    half = len(members) // 2
+    rows = [(k % 8, k % 5, 0, 0, cu.coding_insert(G, k % 8, k % 5, "TAA" + "GCA" * (k % 4)), 5) for k in range(n)]
+    seen = set()
+    for a, b in zip(members[:half], members[half:]):
+        while True:
+            v, j, aa = rnd.randrange(len(G.v_regions)), rnd.randrange(len(G.j_regions)), tuple(rnd.choice(two) for _ in range(4))
+            if (v, j, aa) not in seen:
+                break
+        seen.add((v, j, aa))
+        rows[a] = (v, j, 0, 0, cu.coding_insert(G, v, j, "".join(syn[x][0] for x in aa)), 5)
+        rows[b] = (v, j, 0, 0, cu.coding_insert(G, v, j, "".join(syn[x][1] for x in aa)), 5)
+    return cu.table(rows), half
+
+
+@pytest.mark.parametrize("n,bits", [(255, 64), (256, 64), (257, 64), (513, 64), (257, 0), (513, 0)])
+def test_tables_on_a_block_edge(n, bits):
+    """Tables that end on, one before and one behind a block of 256, and in a third block: the members' compaction, the
+    heads', the rounds' (with no hash bits a round resolves one clonotype: at 513 the active members go 342, 340, ... through
+    256; at 257 there are 170) and the order of clonotypes whose duplicate_count ties throughout."""
+    G = cu.coding_genes(3)
+    tab, pairs = _synonymous_pairs(G, n)
+    want = cu.expected_clonotypes(tab, G)
+    st, of = want[1], want[2]
+    assert st["clonotypes_out"] == st["convergent"] == pairs and st["largest_n_dcrs"] == 2 and st["productive"] == 2 * pairs
+    assert len(set(want[0]["duplicate_count"].tolist())) == 1
+    non = of == nat.NOT_A_MEMBER
+    assert non[:min(n, 256)].any() and (~non[:min(n, 256)]).any() and (n <= 256 or non[256:].any())
+    g = _genes(G)
+    g.set_hash_bits(bits)
+    try:
+        cu.assert_same(nat.clonotypes(g, tab), want)
+    finally:
+        g.set_hash_bits(64)
+
+
 def test_one_hot_clonotype_beside_singletons():
     """One clonotype of 5 000 synonymous DCRs (the codons of one junction rewritten) beside 20 000 others."""
     G = cu.coding_genes(3)

@@ -2,6 +2,7 @@
 built on the host from dcrx_decombine's records, the chains entry against the single entry on each handle, and the
 `-nbc --count-dcrs` stage on the TINY fixtures and on clonal synthetic reads."""
 import collections
+import functools
 
 import numpy as np
 import pytest
@@ -139,6 +140,30 @@ def test_colliding_hashes_stay_exact(bits):
         dc.set_hash_bits(63)
     dc.reset()
     dc.set_hash_bits(63)
+    nat.decombine_count(t, batch, dc, 0, None, "both")
+    assert _got(dc.read()) == want
+    dc.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_batch(n):
+    """(tables, batch, expected table) of n reads drawn from 40 clonal reads in either orientation."""
+    ts = synth.config_tagset(2)
+    t = _tables(ts)
+    batch = nat.pack_reads(nu.clonal_reads(ts, n, seed=71, n_pool=40, orientation="both"))
+    rec, _ = nat.decombine(t, batch, "both")
+    return t, batch, _expected(rec, batch)
+
+
+@pytest.mark.parametrize("bits", [0, 3, 63])
+@pytest.mark.parametrize("n", [255, 256, 257, 513])
+def test_batches_on_a_block_edge(n, bits):
+    """Batches that end on, one before and one behind a block of 256, and in a third block, of so few clones that runs of
+    equal hashes lie across the blocks' edges (with no hash bits the batch is one run and every other DCR a straggler)."""
+    t, batch, want = _edge_batch(n)
+    assert len(want) > 10 and want[0][5] > 1
+    dc = nat.DcrCounts()
+    dc.set_hash_bits(bits)
     nat.decombine_count(t, batch, dc, 0, None, "both")
     assert _got(dc.read()) == want
     dc.close()

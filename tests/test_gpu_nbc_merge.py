@@ -123,6 +123,65 @@ def test_degenerate_tables():
     assert stats["out_of_reach"] == 4 and stats["merged"] == 1
 
 
+def _paired_bucket(n, equal_totals, seed=21):
+    """n entries of one (v, j, length) bucket in rank order (nm.ranked), and the mask of the intended children: pairs of a parent
+    and a child one substitution from it with at least ten times fewer reads, the other inserts far apart, first ordinals a
+    permutation that has nothing to do with the ranks.  With equal_totals every root ends with the same total: the parents
+    (and, for an odd n, one entry that stands alone) fill the first ranks and every child stands behind every root — a child
+    has at most a tenth of its parent's reads, so equal totals and children between the roots exclude each other.  Without
+    it there are two totals (11 000 and 800: the lesser pairs' parents have as many reads as the greater pairs' children, so
+    roots and children alternate over the middle half of the table) and, for an odd n, a last entry of one read that stands
+    alone: the table's last rank is then a root, in a block of its own at 257 and 513."""
+    rng = np.random.default_rng(seed + n)
+    pairs = n // 2
+    greater = pairs if equal_totals else pairs // 2
+    first = rng.permutation(n).tolist()
+    entries, child_of, seen = [], {}, set()
+
+    def insert():
+        while True:
+            s = "".join(rng.choice(list("ACGT"), size=24))
+            if s not in seen:
+                seen.add(s)
+                return s
+    for k in range(pairs):
+        total, y = (11_000, int(rng.integers(730, 800))) if k < greater else (800, int(rng.integers(2, 72)))
+        src = insert()
+        p = int(rng.integers(0, 24))
+        sub = src[:p] + "ACGT"[("ACGT".index(src[p]) + int(rng.integers(1, 4))) % 4] + src[p + 1:]
+        seen.add(sub)
+        entries += [(1, 2, 4, 3, src, total - y, first.pop()), (1, 2, 4, 3, sub, y, first.pop())]
+        child_of[sub] = src
+    if n % 2:
+        entries.append((1, 2, 4, 3, insert(), 11_000 if equal_totals else 1, first.pop()))
+    counted = nm.ranked(entries)
+    return counted, np.array([x in child_of for x in nm.inserts(counted)])
+
+
+@pytest.mark.parametrize("equal_totals", [True, False], ids=["equal-totals", "interleaved"])
+@pytest.mark.parametrize("n", [255, 256, 257, 513])
+def test_tables_on_a_block_edge(n, equal_totals):
+    """Tables that end on, one before and one behind a block of 256, and in a third block: the roots' compaction, its count and
+    the order of roots whose totals tie (the first ordinal decides).  Equal totals and children between the roots exclude
+    each other (_paired_bucket), so each has a table of its own."""
+    ts = synth.config_tagset(2)
+    counted, child = _paired_bucket(n, equal_totals)
+    want, wstats, wroot = nm.expected_merge(counted, ts, 1, 10)
+    is_root = wroot == np.arange(n)
+    assert np.array_equal(~is_root, child) and wstats["merged"] == n // 2 and wstats["out_of_reach"] == 0
+    assert (np.bincount(wroot[child], minlength=n) <= 1).all()          # every parent has exactly one child
+    totals = set(want["count"].tolist())
+    assert totals == ({11_000} if equal_totals else {11_000, 800, 1} if n % 2 else {11_000, 800})
+    if not equal_totals:
+        edge = min(256, n - 1)          # (the last block's first entry; in a table of one block, its last)
+        assert child[:edge].any() and is_root[:edge].any() and is_root[n - 1] == n % 2
+        if n > 256:          # a root and a child on either side of index 256 (257 has one entry there: the root that stands alone)
+            assert is_root[256:].any() and (child[256:].any() or n == 257)
+        mixed = np.nonzero(child[:-1] != child[1:])[0]
+        assert len(mixed) > n // 8 and (n < 513 or (mixed.min() < 256 < mixed.max()))
+    _check(_tables(ts), ts, counted, 1, 10)
+
+
 def test_parents_device_on_a_stream_of_the_callers():
     ts = synth.config_tagset(2)
     t = _tables(ts)
