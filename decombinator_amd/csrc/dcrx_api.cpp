@@ -428,8 +428,7 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   if (b->n_reads && !d_records) return set_err(DCRX_E_INVALID, "d_records is null");
   if (cfg->orientation < 0 || cfg->orientation > 2) return set_err(DCRX_E_INVALID, "orientation must be 0, 1 or 2");
   if (cfg->flags & DCRX_F_PROFILE_MASK) {       // profiling switches: the records are then not results
-    static const bool debug_flags = getenv("DCRX_DEBUG_FLAGS") && getenv("DCRX_DEBUG_FLAGS")[0] == '1';
-    if (!debug_flags) return set_err(DCRX_E_INVALID, "cfg.flags holds a profiling switch (records would not be results): set DCRX_DEBUG_FLAGS=1 to allow it");
+    if (!dcrx_debug_flags_on()) return set_err(DCRX_E_INVALID, "cfg.flags holds a profiling switch (records would not be results): set DCRX_DEBUG_FLAGS=1 to allow it");
   }
   rc = ensure_device(t, b->n_reads, b->stride, (hipStream_t)stream);
   if (rc) return rc;
@@ -919,7 +918,9 @@ int dcrx_tune_state(const dcrx_tables_t *t, int orientation, uint64_t n_reads, d
   *out = dcrx_tune_state_t{0u, 0u, 0.f, 0.f, 0u, 0u};
   const V2Tune &F = t->state.tune[orientation == DCRX_ORIENT_FORWARD ? 0 : 1];
   out->launch_form = F.last_form;
-  out->candidates = n_reads >= V2Tune::BIG_BATCH ? (8192u | (4096u << 16)) : (4096u | (3072u << 16));
+  uint32_t first, second;
+  V2Tune::candidates(n_reads, first, second);
+  out->candidates = first | (second << 16);
   const int k = V2Tune::size_class(n_reads);
   if (k < 0) return DCRX_OK;
   const V2TuneSlot &U = F.slot[k];

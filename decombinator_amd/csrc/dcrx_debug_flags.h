@@ -32,3 +32,13 @@ static inline const char *dcrx_debug_env(const char *name) {
   static const bool on = [] { const char *e = std::getenv("DCRX_DEBUG_FLAGS"); return e && e[0] == '1'; }();
   return on ? std::getenv(name) : nullptr;
 }
+static inline bool dcrx_debug_flags_on() { return dcrx_debug_env("DCRX_DEBUG_FLAGS") != nullptr; }
+// A numeric knob: the variable's value where it starts with a number inside [lo, hi], else (unset, not a number, out of
+// range, or no DCRX_DEBUG_FLAGS=1) the fallback.  A caller keeps the result in a static: one reading per process.
+static inline int dcrx_debug_int(const char *name, const int lo, const int hi, const int fallback) {
+  const char *e = dcrx_debug_env(name);
+  if (!e) return fallback;
+  char *end = nullptr;
+  const long v = std::strtol(e, &end, 10);
+  return (end != e && v >= lo && v <= hi) ? (int)v : fallback;
+}

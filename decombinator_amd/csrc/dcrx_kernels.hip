@@ -617,9 +617,25 @@ bool first_use_on_device(bool (&seen)[64]) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
   return !seen[dev];
 }
-void attributes_set_on_device(bool (&seen)[64]) {
+static void attributes_set_on_device(bool (&seen)[64]) {
   int dev = 0;
   if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) seen[dev] = true;
+}
+// A launcher's kernels and their LDS ceilings, on the first use of each device
+hipError_t set_lds_ceilings(bool (&seen)[64], const KernelLds *list, const int n) {
+  if (!first_use_on_device(seen)) return hipSuccess;
+  for (int i = 0; i < n; i++) {
+    if (list[i].no_static_lds) {
+      hipFuncAttributes fa;
+      const hipError_t e = hipFuncGetAttributes(&fa, list[i].kernel);
+      if (e != hipSuccess) return e;
+      if (fa.sharedSizeBytes != 0) return hipErrorNotSupported;      // (dcrx_api.cpp: DCRX_E_HIP with the runtime's text; a toolchain that moves the LDS base)
+    }
+    const hipError_t e = hipFuncSetAttribute(list[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, list[i].bytes);
+    if (e != hipSuccess) return e;
+  }
+  attributes_set_on_device(seen);
+  return hipSuccess;
 }
 
 template <bool TABLE_LDS, bool UNIFORM, int NW, int ARITY>
@@ -635,13 +651,9 @@ static hipError_t launch_all(const LaunchPlan &P, const DevTables &T, const Batc
   // persistent grids: as many blocks as are resident at once for THIS table size (queried per
   // launch: a host-side call, and tables of different sizes share the kernel instantiations)
   static bool attr_seen[64];
-  if (first_use_on_device(attr_seen)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfast), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(klist), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attributes_set_on_device(attr_seen);
-  }
+  const KernelLds ceilings[] = {{reinterpret_cast<const void *>(kfast), 160 * 1024, false}, {reinterpret_cast<const void *>(klist), 160 * 1024, false}};
+  e = set_lds_ceilings(attr_seen, ceilings, 2);
+  if (e != hipSuccess) return e;
   int occ_fast = 0, occ_list = 0;
   e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_fast, kfast, FBLOCK, lds_fast);
   if (e != hipSuccess) return e;
@@ -748,11 +760,9 @@ static hipError_t launch_all(const LaunchPlan &P, const DevTables &T, const Batc
   if (rescue16 && !all_general) {
     auto kresc = decombine_rescue_kernel<UNIFORM, NW>;
     static bool rattr_seen[64];
-    if (first_use_on_device(rattr_seen)) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(kresc), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attributes_set_on_device(rattr_seen);
-    }
+    const KernelLds resc_lds = {reinterpret_cast<const void *>(kresc), 160 * 1024, false};
+    e = set_lds_ceilings(rattr_seen, &resc_lds, 1);
+    if (e != hipSuccess) return e;
     const uint32_t lds_resc = P.lds16_bytes + DCRX_RESCUE_LDS_EXTRA;
     hipExtLaunchKernelGGL(kresc, dim3(cus), dim3(DCRX_RBLOCK), lds_resc, s, nullptr, P.ev_step_stop, 0, T, B, cfg, rec, d_counters, queue, gqueue,
                           queue_count, qcap);
@@ -800,12 +810,10 @@ static hipError_t launch_long_as(const LaunchPlan &P, const DevTables &T, const 
   auto ku = decombine_long_kernel<true, TABLE_LDS, BLOCK>;
   auto kr = decombine_long_kernel<false, TABLE_LDS, BLOCK>;
   static bool attr_seen[64];
-  if (TABLE_LDS && first_use_on_device(attr_seen)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ku), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (TABLE_LDS) {
+    const KernelLds ceilings[] = {{reinterpret_cast<const void *>(ku), 160 * 1024, false}, {reinterpret_cast<const void *>(kr), 160 * 1024, false}};
+    const hipError_t e = set_lds_ceilings(attr_seen, ceilings, 2);
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attributes_set_on_device(attr_seen);
   }
   if (B.lens) hipExtLaunchKernelGGL(kr, dim3(grid), dim3(BLOCK), lds, s, nullptr, P.ev_step_stop, 0, T, B, cfg, rec, d_counters, slot_dwords);
   else hipExtLaunchKernelGGL(ku, dim3(grid), dim3(BLOCK), lds, s, nullptr, P.ev_step_stop, 0, T, B, cfg, rec, d_counters, slot_dwords);
@@ -828,7 +836,7 @@ static hipError_t launch_long(const LaunchPlan &P, const DevTables &T, const Bat
   static const bool no_lds = dcrx_debug_env("DCRX_DEBUG_LONG_GLOBAL_TABLES") != nullptr;      // (A/B)
   if (!no_lds && T.lds_image_bytes && slot_for(512, 1) && B.n_reads >= 4096u) {
     // (experiment, DCRX_DEBUG_LONG_BLOCK=768: three waves per SIMD with 170 registers each instead of four with 128)
-    static const int long_block = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_LONG_BLOCK"); return e ? atoi(e) : 0; }();
+    static const int long_block = dcrx_debug_int("DCRX_DEBUG_LONG_BLOCK", 768, 768, 0);
     if (long_block == 768) {
       if (const uint32_t sl = slot_for(768, 1)) {
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus, (B.n_reads + 767) / 768));

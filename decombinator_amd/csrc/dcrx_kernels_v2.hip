@@ -31,6 +31,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -44,9 +45,6 @@
 #include "dcrx_sink_device.h"
 
 namespace dcrx {
-
-bool first_use_on_device(bool (&seen)[64]);
-void attributes_set_on_device(bool (&seen)[64]);
 
 constexpr int DCRX_V2_BLOCK = 1024;
 #ifdef DCRX_SCAN_STAMPS
@@ -1753,454 +1751,470 @@ bool v2_applies(const LaunchPlan &P, const DevTables &T, const CfgDev &cfg, cons
   return fits(cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1);
 }
 
-template <bool UNIFORM, int NW, int RPL, bool NARROW, bool PREFETCH = true>
-static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
-                            uint32_t *queue, uint32_t *gqueue, uint32_t qcap, uint32_t *queue_count,
-                            unsigned long long *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t retry, V2SinkLaunch *sink) {
-  const int o = cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1;
-  // The fused form (the tail inside the scan kernel, through a ring in LDS: scan2_kernel, FUSE) for the 150-nt shape when the
-  // frame's pair table leaves room for the side tables, the buckets and a ring of at least four batches; the A/B forms and the
-  // profiling switches keep the tail a launch of its own.
-  constexpr bool CAN_FUSE = NW == 10 && ((RPL == 2 && PREFETCH) || (RPL == 3 && !PREFETCH));
-  uint32_t ring_batches = 0;
+// ---- the launcher's A/B and developer knobs (dcrx_debug_flags.h: honoured only under DCRX_DEBUG_FLAGS=1), read once per process
+struct V2Knobs {
   // (measured, profiles/r04: config 2's 57 KB table 0.413 ms per step fused against 0.429 with the tail as a role; the extended
   // beta set's 76 KB table 0.752 against 0.726 for config 3's two chains: pair tables of up to 64 KB fuse)
-  static const uint32_t fuse_limit = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_FUSE_LIMIT_KB"); const int v = e ? atoi(e) : 0; return v > 0 ? (uint32_t)v * 1024u : 64u * 1024u; }();      // (A/B)
-  if (CAN_FUSE && T.v2[o].trans_bytes <= fuse_limit && !(cfg.flags & (DCRX_F_V2_NO_FUSE | DCRX_F_V2_SIDE_STREAMS | DCRX_F_V2_LEAN_SERIAL | DCRX_F_V2_NO_LEAN_RESCUE | (DCRX_F_PROFILE_MASK & ~DCRX_F_PROFILE_TAIL_STREAM_ONLY)))) {
-    const uint32_t fixed = v2_scan_lds_bytes(T, o) + (T.lds_image_bytes - T.dfa_bytes) + T.v2[o].bk_bytes;
-    static const uint32_t nb_max = [] {      // (tests: DCRX_DEBUG_RING_BATCHES=4 forces the shortest ring)
-      const char *e = dcrx_debug_env("DCRX_DEBUG_RING_BATCHES");
-      const uint32_t v = e ? (uint32_t)atoi(e) : V2_RING_MAXBATCHES;
-      return (v == 4u || v == 8u || v == 16u) ? v : V2_RING_MAXBATCHES;
-    }();
-    // (the whole ring or none: with the extended alpha set's 119 KB table only four batches fit, the scanning waves wait for
-    // room, and config 3 took 7.26 ms per 100 M reads against 5.91 with the tail as a role of the finishing launch;
-    // tests force shorter rings through DCRX_DEBUG_RING_BATCHES)
-    // (round 5: a ring of 8 batches serves config 2 as well as one of 16 — 0.366 / 0.373 against 0.374 / 0.377 ms per step —, one
-    // of 4 does not: 0.447; profiles/r05/ring_batches_ab.log)
-    const uint32_t nb_min = dcrx_debug_env("DCRX_DEBUG_RING_BATCHES") ? 4u : 8u;
-    for (uint32_t nb = nb_max; nb >= nb_min; nb >>= 1)
-      if (fixed + nb * 64u * V2_RING_STRIDE * 4u <= 160u * 1024u) { ring_batches = nb; break; }
+  uint32_t fuse_limit = (uint32_t)dcrx_debug_int("DCRX_DEBUG_FUSE_LIMIT_KB", 1, INT_MAX, 64) * 1024u;      // (A/B)
+  // (the whole ring or none: with the extended alpha set's 119 KB table only four batches fit, the scanning waves wait for
+  // room, and config 3 took 7.26 ms per 100 M reads against 5.91 with the tail as a role of the finishing launch)
+  // (round 5: a ring of 8 batches serves config 2 as well as one of 16 — 0.366 / 0.373 against 0.374 / 0.377 ms per step —, one
+  // of 4 does not: 0.447; profiles/r05/ring_batches_ab.log)
+  // (tests: DCRX_DEBUG_RING_BATCHES=4 forces the shortest ring; whatever its value, the variable allows rings down to four batches)
+  uint32_t ring_max = [] { const int v = dcrx_debug_int("DCRX_DEBUG_RING_BATCHES", 4, 16, (int)V2_RING_MAXBATCHES); return (v == 4 || v == 8 || v == 16) ? (uint32_t)v : V2_RING_MAXBATCHES; }();
+  uint32_t ring_min = dcrx_debug_env("DCRX_DEBUG_RING_BATCHES") ? 4u : 8u;
+  int fuse_e = dcrx_debug_int("DCRX_DEBUG_FUSE_E", 0, INT_MAX, -1);      // 0 keeps list E a role of the finishing launch, another number puts it inside the scan where it fits (A/B); -1: the handle's choice
+  uint32_t fuse_e_waves = (uint32_t)dcrx_debug_int("DCRX_DEBUG_FUSE_E_WAVES", 1, 8, 3);      // the rescue waves of a scan block that finishes list E
+  uint32_t tail_waves = (uint32_t)dcrx_debug_int("DCRX_DEBUG_TAIL_WAVES", 2, 8, 0);      // (tests, A/B)
+  // (experiment, DCRX_DEBUG_SCAN_THREADS=768: three waves per SIMD in a scan block, so that a wave of another stream's finishing launch fits beside it)
+  uint32_t scan_threads = [] { const int v = dcrx_debug_int("DCRX_DEBUG_SCAN_THREADS", 512, DCRX_V2_BLOCK, DCRX_V2_BLOCK); return (uint32_t)(v % 64 == 0 ? v : DCRX_V2_BLOCK); }();
+  uint32_t rescue_waves = (uint32_t)dcrx_debug_int("DCRX_DEBUG_RESCUE_WAVES", 256, INT_MAX, 0);      // (A/B)
+  uint32_t rescue_waves_c = (uint32_t)dcrx_debug_int("DCRX_DEBUG_RESCUE_WAVES_C", 256, INT_MAX, 0);      // (A/B)
+  uint32_t tail_role_waves = (uint32_t)dcrx_debug_int("DCRX_DEBUG_TAIL_ROLE_WAVES", 256, INT_MAX, 0);      // (A/B)
+  uint32_t x_bsplit = (uint32_t)dcrx_debug_int("DCRX_DEBUG_X_BSPLIT", 1, 16, 0);      // (A/B)
+  bool no_tune = dcrx_debug_env("DCRX_DEBUG_NO_TUNE") != nullptr;      // (tests, A/B)
+  bool say_tune = dcrx_debug_env("DCRX_DEBUG_TUNE") != nullptr;
+  bool say_counts = dcrx_debug_env("DCRX_DEBUG_V2_COUNTS") != nullptr;
+};
+static const V2Knobs &v2_knobs() { static const V2Knobs K; return K; }
+
+// ---- what a call will launch ----
+// The fused form (the tail inside the scan kernel, through a ring in LDS: scan2_kernel, FUSE) for the 150-nt shape when the
+// frame's pair table leaves room for the side tables, the buckets and a ring of at least eight batches; the A/B forms and the
+// profiling switches keep the tail a launch of its own.  Batches of the tail ring, 0: the tail as a role (or a launch) of its own.
+static uint32_t v2_tail_ring(const bool can_fuse, const DevTables &T, const int o, const uint32_t flags) {
+  const V2Knobs &K = v2_knobs();
+  if (!can_fuse || T.v2[o].trans_bytes > K.fuse_limit ||
+      (flags & (DCRX_F_V2_NO_FUSE | DCRX_F_V2_SIDE_STREAMS | DCRX_F_V2_LEAN_SERIAL | DCRX_F_V2_NO_LEAN_RESCUE | (DCRX_F_PROFILE_MASK & ~DCRX_F_PROFILE_TAIL_STREAM_ONLY))))
+    return 0u;
+  const uint32_t fixed = v2_scan_lds_bytes(T, o) + (T.lds_image_bytes - T.dfa_bytes) + T.v2[o].bk_bytes;
+  for (uint32_t nb = K.ring_max; nb >= K.ring_min; nb >>= 1)
+    if (fixed + nb * 64u * V2_RING_STRIDE * 4u <= 160u * 1024u) return nb;
+  return 0u;
+}
+
+// One scan block per compute unit, each with a contiguous range of the reads — a multiple of 512: whole items of its waves and
+// whole 64-byte lines of the exception bitmap (v2_exc_slice) — and one region of every list, sized for the reads the block can
+// meet; a small batch takes fewer blocks, 16 items each at least.
+struct V2Regions {
+  uint32_t grid = 1, n_regions = 1;      // scan blocks; regions of every list (a block's own)
+  uint64_t per_block = 0;            // reads of a block
+  uint64_t pb128 = 0;                // ... rounded up to whole chunks
+  uint32_t tcap = 0, ecap = 0, scap = 0;      // entries of a region of the tail list (fused: of the ring's sequence, which stands in for it), of list E, of lists C and X together
+  // items of a region's slab of the tuple sink: a section per list (tail, E, C) and one for the late items
+  uint64_t sink_stride() const { return (uint64_t)tcap + ecap + scap / 2 + pb128; }
+};
+template <int NW, int RPL> static V2Regions v2_regions(const LaunchPlan &P, const BatchDev &B, const uint32_t ring_batches) {
+  V2Regions R;
+  const uint32_t cus = P.n_cu > P.reserved_cus ? P.n_cu - P.reserved_cus : 1u;
+  const uint64_t wt = 64ull * RPL;
+  const uint64_t n_items = (B.n_reads + wt - 1) / wt;
+  R.grid = R.n_regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cus, (n_items + 15) / 16));
+  R.per_block = (((B.n_reads + R.grid - 1) / R.grid + 511) / 512) * 512;
+  R.pb128 = (R.per_block + 255) & ~127ull;
+  // (the fused form: the ring's sequence stands in for the tail list — the tuple sink's tail section is as long)
+  R.tcap = ring_batches ? (uint32_t)R.pb128 & ~63u : (uint32_t)std::min<uint64_t>(R.pb128, P.v2_tail_rows / V2Rows<NW>::T / R.n_regions) & ~63u;      // (whole chunks of 64 slots)
+  R.ecap = (uint32_t)std::min<uint64_t>(R.pb128, P.v2_event_rows / V2Rows<NW>::E / R.n_regions) & ~127u;    // (region `sx`, of the same size, holds two lists of whole chunks)
+  R.scap = (uint32_t)std::min<uint64_t>(R.ecap, P.v2_slow_rows / V2Rows<NW>::E / R.n_regions) & ~127u;
+  return R;
+}
+
+// Launch order, all on the caller's stream: scan -> finish2 (the lean rescue over lists E and C, the lean tail and the general
+// form over list X as roles of one launch) -> (dcrx_kernels.hip) the list kernel.  A/B and tests: DCRX_F_V2_SIDE_STREAMS puts the
+// tail kernel and the X pass on two side streams of the handle beside the rescue kernel (round 3's shape: forked from the scan
+// dispatch's stop event, joined through the side kernels' own stop events), DCRX_F_V2_LEAN_SERIAL runs the three as launches of
+// their own one after the other.
+enum class V2Order { ROLES, SERIES, SIDE_STREAMS };
+struct V2Form {
+  uint32_t ring_batches = 0;         // the tail inside the scan, through a ring of so many batches (0: not)
+  bool fuse_e = false;               // list E inside the scan as well (FUSE_E) ...
+  uint32_t ring_batches_e = 0, scan_lds_e = 0;      // ... and then the tail ring's batches and the scan block's LDS
+  uint32_t scan_lds = 0;             // the scan block's LDS otherwise
+  bool finish = true;                // something runs behind the scan (not under the profiling switches that stop there)
+  V2Order order = V2Order::ROLES;
+  bool sink = false;                 // the call's tuple sink is served by these launches
+  uint32_t last_form = 2;            // what dcrx_tune_state reports for the call (V2Tune::last_form)
+  V2TuneSlot *eslot = nullptr;       // the size class's slot, where the handle keeps its list-E decision (null: the call has no part in it)
+  hipEvent_t e_start = nullptr, e_stop = nullptr;      // the slot's pair on the scan's / the finishing launch's dispatch, when this call is one of the timed samples
+};
+template <bool UNIFORM, int NW, int RPL, bool PREFETCH>
+static V2Form v2_form(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, const int o, const uint32_t ring_batches, const V2Regions &R,
+                      const uint32_t retry, const bool sink_asked, const bool caller_events) {
+  constexpr bool CAN_FUSE_E = NW == 10 && UNIFORM && RPL == 2 && PREFETCH, CAN_SINK = NW == 10;
+  V2Form F;
+  F.ring_batches = ring_batches;
+  F.scan_lds = v2_scan_lds_bytes(T, o) + (ring_batches ? (T.lds_image_bytes - T.dfa_bytes) + T.v2[o].bk_bytes + ring_batches * 64u * V2_RING_STRIDE * 4u : 0u);
+  F.finish = !(cfg.flags & (DCRX_F_PROFILE_SCAN_ONLY | DCRX_F_PROFILE_NO_FINISH));
+  if (cfg.flags & (DCRX_F_V2_SIDE_STREAMS | DCRX_F_V2_LEAN_SERIAL | DCRX_F_V2_NO_LEAN_RESCUE)) {
+    const bool side = F.finish && (cfg.flags & DCRX_F_V2_SIDE_STREAMS) && !(cfg.flags & DCRX_F_V2_LEAN_SERIAL) && P.v2_side && P.v2_side2 && P.v2_ev_fork &&
+                      P.v2_ev_join && P.v2_ev_join2;
+    F.order = side ? V2Order::SIDE_STREAMS : V2Order::SERIES;
   }
-  auto ks = scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH>;
-  if constexpr (CAN_FUSE) {
-    if (ring_batches) ks = o ? scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 1> : scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 0>;
-  }
+  // The call's tuple sink (dcrx_sink_device.h), when this launch serves it: the shipped shape (one finishing launch), one pass,
+  // no profiling switch, and room: a slab per region with a section per list and one for the late items, a region's bitmap and
+  // its ranks in the place kernel's LDS.
+  F.sink = CAN_SINK && sink_asked && F.finish && F.order == V2Order::ROLES && !retry && !(cfg.flags & DCRX_F_PROFILE_MASK) && R.n_regions <= P.sink.regions_cap &&
+           R.sink_stride() * R.n_regions <= P.sink.items_cap && R.sink_stride() < (1ull << 32) && R.per_block / 32 * 8 <= 144u * 1024u && R.per_block < 0xFFFFFFull;
   // FUSE_E: list E through an event ring inside the scan kernel as well (the two-reads-per-lane shape of uniform 150-nt batches,
-  // one pass, no tuple sink, no A/B or profiling switch), where the block's LDS holds the event ring beside a tail ring of eight
-  // batches or more; DCRX_DEBUG_FUSE_E=0 keeps list E a role of the finishing launch (A/B), DCRX_DEBUG_FUSE_E_WAVES the rescue waves
-  constexpr bool CAN_FUSE_E = CAN_FUSE && UNIFORM && RPL == 2;
-  auto ks_e = ks;
-  bool fuse_e = false;
-  uint32_t ring_batches_e = 0, scan_lds_e = 0;
-  static const int fuse_e_env = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_FUSE_E"); return e ? atoi(e) : -1; }();
-  static const uint32_t rescue_waves_fused = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_FUSE_E_WAVES"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= 8) ? (uint32_t)v : 3u; }();
-  V2TuneSlot *eslot = nullptr;      // (the size class's slot, where the handle keeps its decision)
-  hipEvent_t e_ev_start = nullptr, e_ev_stop = nullptr;      // this call's pair, when it is one of the two timed samples
+  // one pass, no tuple sink served — its items are placed by list position —, no A/B or profiling switch), where the block's LDS
+  // holds the event ring beside a tail ring of eight batches or more.  The handle decides per size class (dcrx_tune.h):
+  // the first launch's lists are counted, and list E's share of the reads decides whether the forms are timed at all (config 2:
+  // 10 % — inside the scan, three rescue waves per block, the step 0.316 ms whatever state the box is in against 0.31-0.35 as a
+  // role; config 5's mouse chains at 2 % substitutions: 30 % — a role: 0.609 against 0.691 ms).  What decides is not the share
+  // alone: config 5's mouse chains hold 10 % of list-E entries per chain as config 2 does and lose 13-28 % fused (their entries
+  // take a rescue wave half as long again), and on a box whose scan runs at its faster pace the two forms of config 2 are within
+  // 2 % of each other (profiles/r06/list_e_in_the_scan_ab.log): so three launches of each form are timed and the faster stays.
   if constexpr (CAN_FUSE_E) {
+    const V2Knobs &K = v2_knobs();
+    HipTuneClock clock;
     const int ec = V2Tune::size_class(B.n_reads);
-    if (P.tune && ec >= 0 && !retry && !cfg.flags && ring_batches) eslot = &P.tune[o].slot[ec];
-    if (eslot && eslot->fuse_e == -1 && eslot->e_sampling && hipEventQuery(eslot->ev_counts) == hipSuccess) {
-      // the first launch's lists have been counted: list E's share of the reads decides (config 2: 10 % — inside the scan, three
-      // rescue waves per block, the step 0.316 ms whatever state the box is in against 0.31-0.35 as a role; config 5's mouse chains
-      // at 2 % substitutions: 30 % — a role: 0.609 against 0.691 ms; profiles/r06/list_e_in_the_scan_ab.log)
-      uint64_t e_entries = 0;
-      for (uint32_t r = 0; r < eslot->e_regions; r++) e_entries += eslot->h_counts[(size_t)V2_L_COUNTS * r + V2_L_E];
-      eslot->e_share = eslot->e_reads ? (float)((double)e_entries / (double)eslot->e_reads) : 0.f;
-      eslot->fuse_e = eslot->e_share <= V2_FUSE_E_MAX_SHARE ? -2 : 0;
-      eslot->e_sampling = false;
-      static const bool say = dcrx_debug_env("DCRX_DEBUG_TUNE") != nullptr;
-      if (say) fprintf(stderr, "dcrx tune: list E holds %.1f %% of %llu reads, frame %d: %s\n", 100.0 * eslot->e_share, (unsigned long long)eslot->e_reads, o,
-                       eslot->fuse_e ? "both forms will be timed" : "stays a role of the finishing launch");
+    if (P.tune && ec >= 0 && !retry && !cfg.flags && ring_batches) F.eslot = &P.tune[o].slot[ec];
+    V2TuneSlot *U = F.eslot;
+    if (U && tune_e_share(*U, clock, V2_FUSE_E_MAX_SHARE, [&] {
+          uint64_t e_entries = 0;
+          for (uint32_t r = 0; r < U->e_regions; r++) e_entries += U->h_counts[(size_t)V2_L_COUNTS * r + V2_L_E];
+          return e_entries;
+        }) && K.say_tune)
+      fprintf(stderr, "dcrx tune: list E holds %.1f %% of %llu reads, frame %d: %s\n", 100.0 * U->e_share, (unsigned long long)U->e_reads, o,
+              U->fuse_e ? "both forms will be timed" : "stays a role of the finishing launch");
+    bool want = K.fuse_e > 0;
+    if (U && K.fuse_e < 0) {
+      const V2ListEStep<HipTuneClock> st = tune_list_e(*U, clock, !caller_events && !sink_asked);
+      want = st.fused;
+      if (st.start) { F.e_start = *st.start; F.e_stop = *st.stop; }
+      if (st.read && K.say_tune)
+        fprintf(stderr, "dcrx tune: scan + finishing launch of %llu reads, frame %d: %.1f us with list E a role, %.1f inside the scan -> %s\n",
+                (unsigned long long)B.n_reads, o, U->us_e[0], U->us_e[1], U->fuse_e ? "inside the scan" : "a role");
     }
-    (void)hipGetLastError();
-    bool want = fuse_e_env >= 0 ? fuse_e_env != 0 : (eslot && eslot->fuse_e == 1);
-    // The share allows it: three launches as a role and three fused under a pair of events each (start on the scan's dispatch, stop on
-    // the finishing launch's), from the class's ninth eligible launch on (the clocks have come up), once the handle's rescue waves
-    // are settled and on launches that carry no events of the caller's; the faster form stays.  What decides is not the share alone: config 5's mouse chains hold 10 % of list-E entries per chain as
-    // config 2 does and lose 13-28 % fused (their entries take a rescue wave half as long again), and on a box whose scan runs at
-    // its faster pace the two forms of config 2 are within 2 % of each other (profiles/r06/list_e_in_the_scan_ab.log).
-    if (fuse_e_env < 0 && eslot && eslot->fuse_e == -2 && eslot->choice != 0u && !ev_start && !ev_stop && !P.ev_step_start && !P.ev_step_stop && !(sink && P.sink.dev)) {
-      bool ok = true;
-      constexpr int NP = V2TuneSlot::E_PAIRS, FIRST = V2TuneSlot::E_FIRST;
-      if (!eslot->ev_e[0][0])
-        for (int a = 0; a < 2 * NP && ok; a++) for (int b = 0; b < 2 && ok; b++) ok = eslot->ev_e[a][b].create(true) == DCRX_OK;
-      const int k = eslot->e_phase - FIRST;      // index of this launch among the timed ones
-      if (!ok) { (void)hipGetLastError(); eslot->fuse_e = 0; }
-      else if (k < 0) eslot->e_phase++;
-      // NP launches with list E a role, one fused launch that is not timed (the other kernel's code is cold, the blocks' hints are the
-      // role form's), NP fused ones: timed in turns the two forms paid for each switch and read within 1 % of each other on a box
-      // where the fused form is 5 % faster in the steady state
-      else if (k < NP) { e_ev_start = eslot->ev_e[k][0]; e_ev_stop = eslot->ev_e[k][1]; want = false; eslot->e_phase++; }
-      else if (k == NP) { want = true; eslot->e_phase++; }
-      else if (k <= 2 * NP) { e_ev_start = eslot->ev_e[k - 1][0]; e_ev_stop = eslot->ev_e[k - 1][1]; want = true; eslot->e_phase++; }
-      else {
-        bool ready = true;
-        for (int a = 0; a < 2 * NP && ready; a++) ready = hipEventQuery(eslot->ev_e[a][1]) == hipSuccess;
-        want = true;      // (the fused form runs on while its samples are read: one switch fewer if it stays)
-        if (ready) {
-          float ms[2] = {0.f, 0.f};
-          for (int a = 0; a < 2 * NP && ok; a++) { float t = 0.f; ok = hipEventElapsedTime(&t, eslot->ev_e[a][0], eslot->ev_e[a][1]) == hipSuccess; ms[a < NP ? 0 : 1] += t; }
-          eslot->us_e[0] = 1e3f * ms[0] / NP; eslot->us_e[1] = 1e3f * ms[1] / NP;
-          eslot->fuse_e = (ok && ms[1] > 0.f && ms[1] < 0.985f * ms[0]) ? 1 : 0;
-          want = eslot->fuse_e == 1;
-          static const bool say = dcrx_debug_env("DCRX_DEBUG_TUNE") != nullptr;
-          if (say) fprintf(stderr, "dcrx tune: scan + finishing launch of %llu reads, frame %d: %.1f us with list E a role, %.1f inside the scan -> %s\n",
-                           (unsigned long long)B.n_reads, o, eslot->us_e[0], eslot->us_e[1], eslot->fuse_e ? "inside the scan" : "a role");
-        }
-      }
-      (void)hipGetLastError();
-    }
+    (void)hipGetLastError();      // (an event that had not completed left hipErrorNotReady behind)
     if (ring_batches && want && !retry && !(cfg.flags & ~(DCRX_F_V2_SHAPE(3)))) {
       const uint32_t fixed = v2_scan_lds_bytes(T, o) + (T.lds_image_bytes - T.dfa_bytes) + T.v2[o].bk_bytes + 64u * V2_ERING_BATCHES * (uint32_t)v2_ering_stride<NW>() * 4u +
                              DCRX_N_COUNTERS * 4u;
       for (uint32_t nb = ring_batches; nb >= 8u; nb >>= 1)
-        if (fixed + nb * 64u * V2_RING_STRIDE * 4u <= 160u * 1024u) { ring_batches_e = nb; scan_lds_e = fixed + nb * 64u * V2_RING_STRIDE * 4u; break; }
-      if (!ring_batches_e && eslot && fuse_e_env < 0) eslot->fuse_e = 0;      // (no room for the event ring beside this table: a role it stays)
-      if (ring_batches_e) {
-        fuse_e = true;
-        ks_e = o ? scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 1, false, true> : scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 0, false, true>;
-      }
+        if (fixed + nb * 64u * V2_RING_STRIDE * 4u <= 160u * 1024u) { F.ring_batches_e = nb; F.scan_lds_e = fixed + nb * 64u * V2_RING_STRIDE * 4u; break; }
+      if (!F.ring_batches_e && U && K.fuse_e < 0) tune_e_no_room(*U);
+      F.fuse_e = F.ring_batches_e && !F.sink;
     }
   }
-  if (P.tune && ring_batches) P.tune[o].last_form = 3u;      // (launch_decombine has said 2; 4 below where list E rides inside the scan as well)
-  const uint32_t scan_lds = v2_scan_lds_bytes(T, o) + (ring_batches ? (T.lds_image_bytes - T.dfa_bytes) + T.v2[o].bk_bytes + ring_batches * 64u * V2_RING_STRIDE * 4u : 0u);
-  auto ke = o ? events2_kernel<UNIFORM, NW, 1> : events2_kernel<UNIFORM, NW, 0>;
-  auto kt = o ? tail2_kernel<UNIFORM, NW, 1> : tail2_kernel<UNIFORM, NW, 0>;
-  auto kr = o ? rescue2_kernel<UNIFORM, NW, 1> : rescue2_kernel<UNIFORM, NW, 0>;
-  auto kf = o ? finish2_kernel<UNIFORM, NW, 1> : finish2_kernel<UNIFORM, NW, 0>;
-  auto kf0 = o ? finish2_kernel<UNIFORM, NW, 1, false> : finish2_kernel<UNIFORM, NW, 0, false>;      // ... without the tail role's code
-  // the kernels that also serve a tuple sink (the 150-nt shapes only; other shapes' calls compact their records)
-  constexpr bool CAN_SINK = NW == 10;
-  auto ks_sink = ks;
-  auto kf_sink = kf, kf0_sink = kf0;
-  if constexpr (CAN_SINK) {
-    kf_sink = o ? finish2_kernel<UNIFORM, NW, 1, true, true> : finish2_kernel<UNIFORM, NW, 0, true, true>;
-    kf0_sink = o ? finish2_kernel<UNIFORM, NW, 1, false, true> : finish2_kernel<UNIFORM, NW, 0, false, true>;
+  F.last_form = F.fuse_e ? 4u : (ring_batches ? 3u : 2u);
+  return F;
+}
+
+// Rescue waves of the finishing launch: as many as keep 4096 on each rescue list of a full-size launch
+// (measured, profiles/r04/rescue_waves_*.log, config3_finish_waves_*.log: where the launch also holds the tail role — the
+// extended sets — 4 096 tail waves and 3 072 rescue waves per list run config 3's step 6 % faster than 8 192 and 4 096: fewer
+// blocks wait for a slot; where the scan has taken the tail, config 2 would take 3 072 rescue waves (- 2 %) and config 5 loses
+// 4 % on them: the 4 096 stay there)
+// (batches of 2^25 reads and more, fused form: 8 192 — config 5 at 100 M reads per launch 18.4 against 17.4 G reads/s, config 2
+// 32.0 against 31.4; at 30 M + 2 % / none: profiles/r05/rescue_waves_by_batch_size.log)
+// (the tail as a role of this launch — the extended sets of config 3 —: 3 072, and 4 096 for big batches: 19.3 against 18.8 G reads/s
+// at 100 M reads, 16.3 against 16.6 at 10 M; profiles/r05/config3_waves_by_batch_size.log)
+// The fused form: the handle's own choice between the two candidates (dcrx_tune.h), timed on its first launches of this batch
+// size: `start` and `stop` ride on the finishing launch's dispatch when this call is one of the samples.
+struct V2Waves { uint32_t rescue; hipEvent_t start = nullptr, stop = nullptr; };
+static V2Waves v2_rescue_waves(const LaunchPlan &P, const BatchDev &B, const CfgDev &cfg, const int o, const V2Form &F, const uint32_t retry) {
+  const V2Knobs &K = v2_knobs();
+  const bool big = B.n_reads >= V2Tune::BIG_BATCH, separate = F.order != V2Order::ROLES;
+  uint32_t first = 4096u, second = 3072u;
+  if (F.ring_batches && !separate) V2Tune::candidates(B.n_reads, first, second);
+  V2Waves W{K.rescue_waves ? K.rescue_waves : ((F.ring_batches || separate) ? first : (big ? 4096u : 3072u))};
+  const int tune_class = V2Tune::size_class(B.n_reads);
+  if (!F.ring_batches || separate || K.rescue_waves || K.no_tune || !P.tune || retry || cfg.flags || tune_class < 0) return W;
+  V2TuneSlot &U = P.tune[o].slot[tune_class];      // (a size class of its own for every power of two: a short last batch does not unsettle the others')
+  HipTuneClock clock;
+  // (a big batch's samples may be waited for, once, where the caller has said so — dcrx_set_tune_wait —: a caller that queues
+  // such launches ahead of the device — each takes milliseconds — would otherwise never find them complete; without that
+  // permission the call keeps its contract of never waiting and the handle stays on the first setting until a query succeeds)
+  const int launch = U.launches;
+  const bool settled = U.choice != 0u;
+  const V2RescueStep<HipTuneClock> st = tune_rescue_waves(P.tune[o], clock, B.n_reads, P.tune_may_wait);
+  if (!settled) (void)hipGetLastError();      // (an event that had not completed left hipErrorNotReady behind)
+  W.rescue = st.waves;
+  if (st.start) { W.start = *st.start; W.stop = *st.stop; }
+  if (st.read && K.say_tune)
+    fprintf(stderr, "dcrx tune: finishing launches of %llu reads, frame %d: %.1f us on %u rescue waves, %.1f on %u -> %u (launch %d)\n",
+            (unsigned long long)B.n_reads, o, U.us[0], first, U.us[1], second, U.choice, launch);
+  return W;
+}
+
+// ---- the finishing launches' geometry: the regions, the waves and blocks of each role, the LDS of each kernel ----
+struct V2Geometry : V2Regions {
+  uint32_t tsplit = 1, rsplit = 1, csplit = 1;      // waves of the tail role, of the rescue over list E and over list C that share a region
+  uint32_t bsplit = 1;               // blocks of list X's pass that share a region
+  uint32_t fgrid = 0, egrid = 0, sgrid = 0, tgrid = 0;      // blocks of the rescue (lists E and C), of the general form over a whole event list (A/B), of list X's pass, of the tail kernel (A/B)
+  uint32_t llds = 0, tlds = 0, elds = 0, ext = 0;      // LDS of a lean block, of a tail-kernel block, of an event-kernel block (ext: with the germline regions in it)
+  static constexpr uint32_t slow_width = 4u;      // lanes of a wave that take entries of a short list (64 / 16 / 4 / 2 / 1: 97 / 62 / 57 / 65 / 79 us)
+  V2Roles roles(const bool fused) const {      // ... as the finishing launch takes them
+    V2Roles R;
+    R.xgrid = sgrid; R.rgrid = fgrid; R.tgrid = fused ? 0u : (n_regions * tsplit + DCRX_V2_FBLOCK / 64 - 1) / (DCRX_V2_FBLOCK / 64);      // (fused: the tail list is empty)
+    R.rsplit = rsplit | (csplit << 8); R.tsplit = tsplit; R.bsplit = bsplit; R.width = slow_width;
+    return R;
+  }
+};
+template <int NW> static V2Geometry v2_geometry(const DevTables &T, const int o, const V2Regions &R, const V2Form &F, const uint32_t rescue_waves) {
+  const V2Knobs &K = v2_knobs();
+  const bool separate = F.order != V2Order::ROLES;
+  V2Geometry G;
+  static_cast<V2Regions &>(G) = R;
+  const uint32_t n_regions = R.n_regions;
+  // waves of the finishing roles that share a region (a scan block's list): as many as keep 8192 waves on the tail list and
+  // `rescue_waves` on each rescue list of a full-size launch
+  const uint32_t tail_role_waves = K.tail_role_waves ? K.tail_role_waves : (separate ? 8192u : 4096u);
+  G.tsplit = std::max<uint32_t>(1u, std::min<uint32_t>(64u, tail_role_waves / n_regions));
+  const uint32_t rsplit_full = std::max<uint32_t>(1u, std::min<uint32_t>(64u, rescue_waves / n_regions));
+  G.rsplit = F.fuse_e ? 1u : rsplit_full;      // (FUSE_E: list E is empty — its entries went through the scan's event ring —: one wave per region looks)
+  G.csplit = K.rescue_waves_c ? std::max<uint32_t>(1u, std::min<uint32_t>(64u, K.rescue_waves_c / n_regions)) : rsplit_full;
+  // (list C's jobs behind list E's on the same waves — one round of blocks instead of two — were measured: the step 3 % longer
+  // on config 2, 8 % on config 5: list C's batches are the slow ones, two sweeps each, and want to start with the launch;
+  // profiles/r05/finish_list_c_folded_ab.log.  List C's jobs IN FRONT of list E's on the same waves: 1-2 % longer still
+  // than list E's blocks first and list C's in the second round, as shipped; finish_one_round_c_first_ab.log)
+  G.fgrid = (n_regions * (G.rsplit + G.csplit) + DCRX_V2_FBLOCK / 64 - 1) / (DCRX_V2_FBLOCK / 64);
+  G.egrid = (n_regions + DCRX_V2_FBLOCK / 64 - 1) / (DCRX_V2_FBLOCK / 64);      // the general form over a whole event list (A/B): a block takes four regions
+  // blocks of a short list's pass that share a region: as a pass of its own (A/B forms) the list's latency is the launch's, and
+  // four blocks per region halve it; as a role under the lean rescue one block per region does (its rounds run hidden)
+  // (FUSE_E: with list E gone the launch is as long as list X's chains of single reads: two blocks per region 46 us, one 57, four 65 —
+  // profiles/r06/list_e_in_the_scan_ab.log)
+  G.bsplit = K.x_bsplit ? K.x_bsplit : (separate ? std::max<uint32_t>(1u, std::min<uint32_t>(16u, 1024u / n_regions)) : (F.fuse_e ? 2u : 1u));
+  G.sgrid = n_regions * G.bsplit;
+  G.tgrid = (n_regions * G.tsplit + DCRX_V2_TBLOCK / 64 - 1) / (DCRX_V2_TBLOCK / 64);
+  const uint32_t flds = v2_finish_lds_bytes(T, o);
+  G.llds = v2_finish_block_lds<NW>(T, o, DCRX_V2_FBLOCK);      // the lean roles: + a strip per lane (+ the rescue's scratch counters)
+  G.tlds = v2_finish_block_lds<NW>(T, o, DCRX_V2_TBLOCK);
+  const uint32_t elds_ext = flds + (T.lds_image2_bytes - T.lds_image_bytes);
+  G.ext = elds_ext <= 64u * 1024u ? 1u : 0u;
+  G.elds = G.ext ? elds_ext : flds;
+  return G;
+}
+// the tuple sink's slabs as the kernels take them, and what the list kernel and the place kernel behind this launch need
+static V2SinkCall v2_sink_call(const LaunchPlan &P, const V2Regions &R, const bool fused, const uint32_t *counts, V2SinkLaunch *out) {
+  V2SinkCall S{};
+  S.dev = P.sink.dev; S.items = P.sink.items; S.hits = P.sink.hits; S.stride = (uint32_t)R.sink_stride(); S.e_off = R.tcap; S.c_off = R.tcap + R.ecap; S.late_off = R.tcap + R.ecap + R.scap / 2;
+  S.late_cap = (uint32_t)R.pb128; S.per_block = (uint32_t)R.per_block; S.wpack = P.sink.wpack;
+  out->S = S; out->n_regions = R.n_regions; out->tcap = R.tcap; out->ecap = R.ecap; out->ccap = R.scap / 2; out->fused = fused ? 1u : 0u;
+  out->counts = counts;
+  return S;
+}
+
+// ---- the kernels of one launch shape, and their LDS ceilings ----
+template <bool UNIFORM, int NW, int RPL, bool NARROW, bool PREFETCH> struct V2Kernels {
+  static constexpr bool CAN_FUSE = NW == 10 && ((RPL == 2 && PREFETCH) || (RPL == 3 && !PREFETCH));
+  static constexpr bool CAN_FUSE_E = CAN_FUSE && UNIFORM && RPL == 2;
+  static constexpr bool CAN_SINK = NW == 10;      // the kernels that also serve a tuple sink (the 150-nt shapes only; other shapes' calls compact their records)
+  using Scan = decltype(&scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH>);
+  template <int FUSE = -1, bool SINK = false, bool FUSE_E = false> static Scan scan_as() { return scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, FUSE, SINK, FUSE_E>; }
+  Scan scan = scan_as(), scan_e, scan_sink;      // the tail a role or, fused, inside the scan; ... with list E inside it as well; ... serving a sink
+  decltype(&events2_kernel<UNIFORM, NW, 0>) events;
+  decltype(&tail2_kernel<UNIFORM, NW, 0>) tail;
+  decltype(&rescue2_kernel<UNIFORM, NW, 0>) rescue;
+  decltype(&finish2_kernel<UNIFORM, NW, 0>) finish, finish0, finish_sink, finish0_sink;      // (0: without the tail role's code)
+  decltype(&left2_kernel<UNIFORM, NW, 0>) left;
+  V2Kernels(const int o, const bool fused) {
     if constexpr (CAN_FUSE) {
-      if (ring_batches) ks_sink = o ? scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 1, true> : scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 0, true>;
+      if (fused) scan = o ? scan_as<1>() : scan_as<0>();
     }
-  }
-  auto kl = o ? left2_kernel<UNIFORM, NW, 1> : left2_kernel<UNIFORM, NW, 0>;
-  static bool seen[64];
-  hipError_t e;
-  if (first_use_on_device(seen)) {
-    {      // the scan kernels address their pair table from LDS address 0: no static LDS may sit in front of the dynamic segment
-      const void *scans[] = {reinterpret_cast<const void *>(ks), reinterpret_cast<const void *>(ks_sink)};
-      for (const void *k : scans) {
-        hipFuncAttributes fa;
-        e = hipFuncGetAttributes(&fa, k);
-        if (e != hipSuccess) return e;
-        if (fa.sharedSizeBytes != 0) return hipErrorNotSupported;      // (dcrx_api.cpp: DCRX_E_HIP with the runtime's text; a toolchain that moves the LDS base)
-      }
-    }
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
+    scan_e = scan_sink = scan;
     if constexpr (CAN_FUSE_E) {
-      const void *ke2[] = {reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 0, false, true>),
-                           reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 1, false, true>)};
-      for (const void *k : ke2) {
-        hipFuncAttributes fa;
-        e = hipFuncGetAttributes(&fa, k);
-        if (e != hipSuccess) return e;
-        if (fa.sharedSizeBytes != 0) return hipErrorNotSupported;
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-      }
+      if (fused) scan_e = o ? scan_as<1, false, true>() : scan_as<0, false, true>();
     }
-    if constexpr (CAN_FUSE) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(ke), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kf0), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kl), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) return e;
+    events = o ? events2_kernel<UNIFORM, NW, 1> : events2_kernel<UNIFORM, NW, 0>;
+    tail = o ? tail2_kernel<UNIFORM, NW, 1> : tail2_kernel<UNIFORM, NW, 0>;
+    rescue = o ? rescue2_kernel<UNIFORM, NW, 1> : rescue2_kernel<UNIFORM, NW, 0>;
+    finish = o ? finish2_kernel<UNIFORM, NW, 1> : finish2_kernel<UNIFORM, NW, 0>;
+    finish0 = o ? finish2_kernel<UNIFORM, NW, 1, false> : finish2_kernel<UNIFORM, NW, 0, false>;
+    finish_sink = finish; finish0_sink = finish0;
     if constexpr (CAN_SINK) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(kf_sink), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(kf0_sink), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      if (e != hipSuccess) return e;
+      finish_sink = o ? finish2_kernel<UNIFORM, NW, 1, true, true> : finish2_kernel<UNIFORM, NW, 0, true, true>;
+      finish0_sink = o ? finish2_kernel<UNIFORM, NW, 1, false, true> : finish2_kernel<UNIFORM, NW, 0, false, true>;
       if constexpr (CAN_FUSE) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan2_kernel<UNIFORM, NW, RPL, NARROW, PREFETCH, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
+        if (fused) scan_sink = o ? scan_as<1, true>() : scan_as<0, true>();
       }
     }
-    attributes_set_on_device(seen);
+    left = o ? left2_kernel<UNIFORM, NW, 1> : left2_kernel<UNIFORM, NW, 0>;
   }
+  // (the scan kernels address their pair table from LDS address 0: no static LDS may sit in front of the dynamic segment)
+  hipError_t set_ceilings() const {
+    static bool seen[64];
+    if (!first_use_on_device(seen)) return hipSuccess;
+    KernelLds list[16];
+    int n = 0;
+    auto add = [&](auto kernel, const int kb, const bool scan) { list[n++] = KernelLds{reinterpret_cast<const void *>(kernel), kb * 1024, scan}; };
+    add(scan_as(), 160, true);
+    if constexpr (CAN_FUSE_E) { add(scan_as<0, false, true>(), 160, true); add(scan_as<1, false, true>(), 160, true); }
+    if constexpr (CAN_FUSE) { add(scan_as<0>(), 160, true); add(scan_as<1>(), 160, true); }
+    add(tail, 128, false); add(events, 64, false); add(rescue, 64, false); add(finish, 64, false); add(finish0, 64, false); add(left, 64, false);
+    if constexpr (CAN_SINK) {
+      add(finish_sink, 64, false); add(finish0_sink, 64, false);
+      if constexpr (CAN_FUSE) { add(scan_as<0, true>(), 160, true); add(scan_as<1, true>(), 160, true); }
+    }
+    return set_lds_ceilings(seen, list, n);
+  }
+};
+
+// ---- the A/B launch orders: the rescue, the tail and list X's pass as launches of their own, in series on the caller's stream
+// or the latter two on the handle's side streams (forked from `fork_ev`, which rides on the scan's dispatch), then what they left
+template <class Kernels>
+static hipError_t launch_v2_separate(const Kernels &K, const LaunchPlan &P, const V2FinishArgs &A, const V2Geometry &G, const bool side, hipStream_t s, hipEvent_t fork_ev) {
+  hipError_t e;
+  auto general = [&](hipStream_t st, const int which, const bool whole_list, hipEvent_t stop) -> hipError_t {
+    if (whole_list)
+      hipExtLaunchKernelGGL(K.events, dim3(G.egrid), dim3(DCRX_V2_FBLOCK), G.elds, st, nullptr, stop, 0, A.T0, A.B, A.cfg, A.records, A.counters, A.Q, which, (uint32_t)(DCRX_V2_FBLOCK / 64), 64u, 1u,
+                            G.ext, G.n_regions, A.queue, A.gqueue, A.qcap, A.queue_count);
+    else
+      hipExtLaunchKernelGGL(K.events, dim3(G.sgrid), dim3(DCRX_V2_FBLOCK), G.elds, st, nullptr, stop, 0, A.T0, A.B, A.cfg, A.records, A.counters, A.Q, which, 1u, G.slow_width, G.bsplit, G.ext,
+                            G.n_regions, A.queue, A.gqueue, A.qcap, A.queue_count);
+    return hipGetLastError();
+  };
+  if (side) {
+    e = hipStreamWaitEvent(P.v2_side, fork_ev, 0); if (e != hipSuccess) return e;
+    hipExtLaunchKernelGGL(K.tail, dim3(G.tgrid), dim3(DCRX_V2_TBLOCK), G.tlds, P.v2_side, nullptr, P.v2_ev_join, 0, A.T0, A.B, A.cfg, A.records, A.counters, A.Q, G.n_regions, G.tsplit, A.queue,
+                          A.gqueue, A.qcap, A.queue_count, A.Tmem);
+    e = hipGetLastError(); if (e != hipSuccess) return e;
+    e = hipStreamWaitEvent(P.v2_side2, fork_ev, 0); if (e != hipSuccess) return e;
+    e = general(P.v2_side2, V2_L_X, false, P.v2_ev_join2); if (e != hipSuccess) return e;
+  }
+  // the scan kernel's event lists E and C: the lean rescue, or — A/B — the general form at once
+  if (A.cfg.flags & DCRX_F_V2_NO_LEAN_RESCUE) {
+    for (int which = V2_L_E; which <= V2_L_C; which++) { e = general(s, which, true, nullptr); if (e != hipSuccess) return e; }
+  } else {
+    hipLaunchKernelGGL(K.rescue, dim3(G.fgrid), dim3(DCRX_V2_FBLOCK), G.llds, s, A.T0, A.B, A.cfg, A.records, A.counters, A.Q, G.n_regions, G.rsplit | (G.csplit << 8), A.queue, A.gqueue, A.qcap,
+                       A.queue_count, A.Tmem);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (side) {
+    e = hipStreamWaitEvent(s, P.v2_ev_join, 0); if (e != hipSuccess) return e;
+    e = hipStreamWaitEvent(s, P.v2_ev_join2, 0); if (e != hipSuccess) return e;
+  } else {
+    hipLaunchKernelGGL(K.tail, dim3(G.tgrid), dim3(DCRX_V2_TBLOCK), G.tlds, s, A.T0, A.B, A.cfg, A.records, A.counters, A.Q, G.n_regions, G.tsplit, A.queue, A.gqueue, A.qcap, A.queue_count, A.Tmem);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = general(s, V2_L_X, false, nullptr); if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(K.left, dim3(1), dim3(DCRX_V2_FBLOCK), G.llds, s, A);      // what the lean kernels left
+  return hipGetLastError();
+}
+
+// debugging aid (DCRX_DEBUG_V2_COUNTS): the lists' populations (synchronises)
+static void v2_dump_counts(const DevTables &T, const int o, const V2Lists &Q, const V2Geometry &G, const uint32_t scan_lds, hipStream_t s) {
+  std::vector<uint32_t> h((size_t)V2_L_COUNTS * G.n_regions);
+  (void)hipStreamSynchronize(s);
+  (void)hipMemcpy(h.data(), Q.counts, h.size() * 4, hipMemcpyDeviceToHost);
+  unsigned long long t[V2_L_COUNTS] = {0};
+  for (uint32_t r = 0; r < G.n_regions; r++) for (int k = 0; k < V2_L_COUNTS; k++) t[k] += h[(size_t)V2_L_COUNTS * r + k];
+  fprintf(stderr, "dcrx v2 lists: regions %u tail %llu E %llu C %llu X %llu; LDS of a finishing block %u bytes (side tables %u, buckets %u), of a scan block %u\n", G.n_regions,
+          t[V2_L_TAIL], t[V2_L_E], t[V2_L_C], t[V2_L_X], G.llds, T.lds_image_bytes - T.dfa_bytes, T.v2[o].bk_bytes, scan_lds);
+}
 #ifdef DCRX_SCAN_STAMPS
-  {
-    static uint32_t *stamps = nullptr;
-    if (!stamps) { (void)hipMalloc(&stamps, (size_t)4096 * 16 * 16); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_scan_stamps), &stamps, sizeof(stamps)); }
+// instrumented build (tools/): when do a scan block's waves start, leave their loops and end?
+static void v2_stamps_arm() {
+  static uint32_t *stamps = nullptr;
+  if (!stamps) { (void)hipMalloc(&stamps, (size_t)4096 * 16 * 16); (void)hipMemcpyToSymbol(HIP_SYMBOL(g_scan_stamps), &stamps, sizeof(stamps)); }
+}
+// (synchronises; launch DCRX_STAMPS_LAUNCH of the process, default 30)
+static void v2_stamps_dump(const uint32_t n_regions, const bool fused, hipStream_t s) {
+  static int launches = 0;
+  static const int want = dcrx_debug_int("DCRX_STAMPS_LAUNCH", INT_MIN, INT_MAX, 30);
+  if (launches++ != want) return;
+  const size_t nw = (size_t)n_regions * (DCRX_V2_BLOCK / 64);
+  std::vector<uint32_t> h(4 * nw);
+  (void)hipStreamSynchronize(s);
+  uint32_t *dptr = nullptr;
+  (void)hipMemcpyFromSymbol(&dptr, HIP_SYMBOL(g_scan_stamps), sizeof(dptr));
+  (void)hipMemcpy(h.data(), dptr, h.size() * 4, hipMemcpyDeviceToHost);
+  if (const char *dump = dcrx_debug_env("DCRX_STAMPS_DUMP")) { FILE *f = fopen(dump, "wb"); if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); } }
+  uint32_t t0 = 0xFFFFFFFFu;
+  for (size_t i = 0; i < nw; i++) t0 = std::min(t0, h[4 * i]);
+  auto pcs = [&](const char *what, std::vector<double> v) {
+    std::sort(v.begin(), v.end());
+    auto pc = [&](double q) { return v[(size_t)(q * (v.size() - 1))]; };
+    fprintf(stderr, "dcrx scan stamps: %-44s min %6.1f p10 %6.1f p50 %6.1f p90 %6.1f p99 %6.1f max %6.1f us\n", what, pc(0), pc(0.1), pc(0.5), pc(0.9), pc(0.99), pc(1.0));
+  };
+  std::vector<double> st, su, le_scan, le_tail, en, blk_scan_end, blk_end;
+  for (uint32_t r = 0; r < n_regions; r++) {
+    double last_scan = 0, last = 0;
+    for (int wv = 0; wv < DCRX_V2_BLOCK / 64; wv++) {
+      const uint32_t *c = &h[4 * ((size_t)r * (DCRX_V2_BLOCK / 64) + wv)];
+      st.push_back((c[0] - t0) / 100.0); su.push_back((c[1] - t0) / 100.0); en.push_back((c[3] - t0) / 100.0);
+      const bool tailw = fused && wv >= (DCRX_V2_BLOCK / 64) - 3;      // (a guess at three tail waves: the block's own choice is not known here)
+      (tailw ? le_tail : le_scan).push_back((c[2] - t0) / 100.0);
+      if (!tailw) last_scan = std::max(last_scan, (c[2] - t0) / 100.0);
+      last = std::max(last, (c[3] - t0) / 100.0);
+    }
+    blk_scan_end.push_back(last_scan); blk_end.push_back(last);
   }
+  pcs("wave start", st); pcs("wave set-up done (tables staged)", su); pcs("scanning wave leaves its loop", le_scan);
+  if (!le_tail.empty()) pcs("tail wave leaves its loop (last three waves)", le_tail);
+  pcs("wave end", en); pcs("per block: last scanning wave leaves", blk_scan_end); pcs("per block: end", blk_end);
+}
+#endif
+
+// One frame's pass over a batch: what to launch (v2_form), where (v2_regions, v2_geometry), the kernels' LDS ceilings on a
+// device's first use, the scan, the finishing launch.
+template <bool UNIFORM, int NW, int RPL, bool NARROW, bool PREFETCH = true>
+static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
+                            uint32_t *queue, uint32_t *gqueue, uint32_t qcap, uint32_t *queue_count,
+                            unsigned long long *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t retry, V2SinkLaunch *sink) {
+  using Kernels = V2Kernels<UNIFORM, NW, RPL, NARROW, PREFETCH>;
+  const V2Knobs &knobs = v2_knobs();
+  const int o = cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1;
+  const uint32_t ring_batches = v2_tail_ring(Kernels::CAN_FUSE, T, o, cfg.flags);
+  const V2Regions R = v2_regions<NW, RPL>(P, B, ring_batches);
+  const V2Form F = v2_form<UNIFORM, NW, RPL, PREFETCH>(P, T, B, cfg, o, ring_batches, R, retry, sink && P.sink.dev, ev_start || ev_stop || P.ev_step_start || P.ev_step_stop);
+  if (P.tune) P.tune[o].last_form = F.last_form;
+  const Kernels K(o, ring_batches != 0u);
+  hipError_t e = K.set_ceilings();
+  if (e != hipSuccess) return e;
+#ifdef DCRX_SCAN_STAMPS
+  v2_stamps_arm();
 #endif
   if (B.n_reads == 0) return hipSuccess;       // (the tallies stay zero; the list kernel hands them over)
-  const uint32_t cus = P.n_cu > P.reserved_cus ? P.n_cu - P.reserved_cus : 1u;
-  // One scan block per compute unit, each with a contiguous range of the reads — a multiple of 512: whole items of its waves and
-  // whole 64-byte lines of the exception bitmap (v2_exc_slice) — and one region of every list, sized for the reads the block can
-  // meet; a small batch takes fewer blocks, 16 items each at least.
-  const uint64_t wt = 64ull * RPL;
-  const uint64_t n_items = (B.n_reads + wt - 1) / wt;
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cus, (n_items + 15) / 16));
-  const uint64_t per_block = (((B.n_reads + grid - 1) / grid + 511) / 512) * 512;
-  V2Lists Q;
-  Q.tail = P.v2_tail; Q.ev = P.v2_events; Q.sx = P.v2_slow; Q.left = P.v2_left; Q.counts = P.v2_counts;
-  const uint32_t n_regions = grid;
-  const uint64_t pb128 = (per_block + 255) & ~127ull;           // (a block's reads, rounded up to whole chunks)
-  Q.tcap = (uint32_t)std::min<uint64_t>(pb128, P.v2_tail_rows / V2Rows<NW>::T / n_regions) & ~63u;      // (whole chunks of 64 slots)
-  Q.ecap = (uint32_t)std::min<uint64_t>(pb128, P.v2_event_rows / V2Rows<NW>::E / n_regions) & ~127u;    // (region `sx`, of the same size, holds two lists of whole chunks)
-  Q.scap = (uint32_t)std::min<uint64_t>(Q.ecap, P.v2_slow_rows / V2Rows<NW>::E / n_regions) & ~127u;
   // (a launch that keeps the tail a role of the finishing launch needs the tail list, which a handle that has fused so far does
   // not hold: hipErrorNotReady before anything is launched — dcrx_api.cpp allocates it and comes back)
-  if (!ring_batches && (!P.v2_tail || Q.tcap < 64)) return B.n_reads ? hipErrorNotReady : hipSuccess;
-  if (ring_batches) Q.tcap = (uint32_t)pb128 & ~63u;      // (the fused form: the ring's sequence stands in for the list — the tuple sink's tail section is as long)
-  if (Q.ecap < 128 || Q.scap < 128) return hipErrorInvalidValue;      // the workspace was not sized for this batch (dcrx_api.cpp sizes it)
-  // Launch order, all on the caller's stream: scan -> finish2 (the lean rescue over lists E and C, the lean tail and the general
-  // form over list X as roles of one launch) -> (dcrx_kernels.hip) the list kernel.  A/B and tests: DCRX_F_V2_SIDE_STREAMS puts the
-  // tail kernel and the X pass on two side streams of the handle beside the rescue kernel (round 3's shape: forked from the scan
-  // dispatch's stop event, joined through the side kernels' own stop events), DCRX_F_V2_LEAN_SERIAL runs the three as launches of
-  // their own one after the other.
-  const bool finish = !(cfg.flags & (DCRX_F_PROFILE_SCAN_ONLY | DCRX_F_PROFILE_NO_FINISH));
-  const bool separate = (cfg.flags & (DCRX_F_V2_SIDE_STREAMS | DCRX_F_V2_LEAN_SERIAL | DCRX_F_V2_NO_LEAN_RESCUE)) != 0u;
-  const bool side = finish && (cfg.flags & DCRX_F_V2_SIDE_STREAMS) && !(cfg.flags & DCRX_F_V2_LEAN_SERIAL) && P.v2_side && P.v2_side2 && P.v2_ev_fork &&
-                    P.v2_ev_join && P.v2_ev_join2;
+  if (!ring_batches && (!P.v2_tail || R.tcap < 64)) return hipErrorNotReady;
+  if (R.ecap < 128 || R.scap < 128) return hipErrorInvalidValue;      // the workspace was not sized for this batch (dcrx_api.cpp sizes it)
+  V2Lists Q;
+  Q.tail = P.v2_tail; Q.ev = P.v2_events; Q.sx = P.v2_slow; Q.left = P.v2_left; Q.counts = P.v2_counts;
+  Q.tcap = R.tcap; Q.ecap = R.ecap; Q.scap = R.scap;
+  const V2SinkCall S = F.sink ? v2_sink_call(P, R, ring_batches != 0u, Q.counts, sink) : V2SinkCall{};
   // (the caller's stop event for the scan, when there is one — timing, or a caller that orders other work behind the scan —
-  // serves as the fork event as well: one signal on the dispatch, no marker packet)
+  // serves as the fork event of the side streams as well: one signal on the dispatch, no marker packet)
+  const bool side = F.order == V2Order::SIDE_STREAMS;
   const hipEvent_t fork_ev = ev_stop ? ev_stop : P.v2_ev_fork;
-  static const uint32_t tail_waves_forced = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_TAIL_WAVES"); const int v = e ? atoi(e) : 0; return (v >= 2 && v <= 8) ? (uint32_t)v : 0u; }();      // (tests, A/B)
-  // The call's tuple sink (dcrx_sink_device.h), when this launch serves it: the shipped shape (one finishing launch), one pass,
-  // no profiling switch, and room: a slab per region with a section per list and one for the late items, a region's bitmap and
-  // its ranks in the place kernel's LDS.
-  V2SinkCall S{};
-  if (CAN_SINK && sink && P.sink.dev && finish && !separate && !retry && !(cfg.flags & DCRX_F_PROFILE_MASK)) {
-    const uint64_t stride = (uint64_t)Q.tcap + Q.ecap + Q.scap / 2 + pb128;
-    if (n_regions <= P.sink.regions_cap && stride * n_regions <= P.sink.items_cap && stride < (1ull << 32) && per_block / 32 * 8 <= 144u * 1024u &&
-        per_block < 0xFFFFFFull) {
-      S.dev = P.sink.dev; S.items = P.sink.items; S.hits = P.sink.hits; S.stride = (uint32_t)stride; S.e_off = Q.tcap; S.c_off = Q.tcap + Q.ecap; S.late_off = Q.tcap + Q.ecap + Q.scap / 2;
-      S.late_cap = (uint32_t)pb128; S.per_block = (uint32_t)per_block; S.wpack = P.sink.wpack;
-      sink->S = S; sink->n_regions = n_regions; sink->tcap = Q.tcap; sink->ecap = Q.ecap; sink->ccap = Q.scap / 2; sink->fused = ring_batches ? 1u : 0u;
-      sink->counts = Q.counts;
-    }
-  }
-  if (S.dev) fuse_e = false;      // (a call that leaves a tuple sink's message keeps list E a role: its items are placed by list position)
-  if (P.tune && fuse_e) P.tune[o].last_form = 4u;
-  // (experiment, DCRX_DEBUG_SCAN_THREADS=768: three waves per SIMD in a scan block, so that a wave of another stream's finishing launch fits beside it)
-  static const uint32_t scan_threads = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_SCAN_THREADS"); const int v = e ? atoi(e) : 0; return (v >= 512 && v <= DCRX_V2_BLOCK && v % 64 == 0) ? (uint32_t)v : (uint32_t)DCRX_V2_BLOCK; }();
-  hipExtLaunchKernelGGL(S.dev ? ks_sink : (fuse_e ? ks_e : ks), dim3(grid), dim3(scan_threads), fuse_e ? scan_lds_e : scan_lds, s, ev_start ? ev_start : e_ev_start, side ? fork_ev : ev_stop, 0, T, B, cfg, rec,
-                        d_counters, Q, queue, gqueue, qcap, queue_count, per_block, retry, P.dev_tables, fuse_e ? ring_batches_e : ring_batches, S, tail_waves_forced,
-                        fuse_e ? rescue_waves_fused : 0u);
+  hipExtLaunchKernelGGL(F.sink ? K.scan_sink : (F.fuse_e ? K.scan_e : K.scan), dim3(R.grid), dim3(knobs.scan_threads), F.fuse_e ? F.scan_lds_e : F.scan_lds, s, ev_start ? ev_start : F.e_start,
+                        side ? fork_ev : ev_stop, 0, T, B, cfg, rec, d_counters, Q, queue, gqueue, qcap, queue_count, R.per_block, retry, P.dev_tables,
+                        F.fuse_e ? F.ring_batches_e : ring_batches, S, knobs.tail_waves, F.fuse_e ? knobs.fuse_e_waves : 0u);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if constexpr (CAN_FUSE_E) {
-    if (eslot && eslot->fuse_e == -1 && !eslot->e_sampling && !fuse_e && fuse_e_env < 0 && !S.dev && finish) {
-      // the class's first launch: its regions' list counts to pinned memory behind the scan (once per handle, frame and size class)
-      bool ok = eslot->h_counts || eslot->h_counts.alloc((size_t)4096 * V2_L_COUNTS) == DCRX_OK;
-      ok = ok && (eslot->ev_counts || eslot->ev_counts.create(false) == DCRX_OK);
-      ok = ok && grid <= 4096u && hipMemcpyAsync(eslot->h_counts, Q.counts, (size_t)grid * V2_L_COUNTS * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
-           hipEventRecord(eslot->ev_counts, s) == hipSuccess;
-      if (ok) { eslot->e_sampling = true; eslot->e_regions = grid; eslot->e_reads = B.n_reads; }
-      else { (void)hipGetLastError(); eslot->fuse_e = 0; }
-    }
+  if (F.eslot && knobs.fuse_e < 0 && !F.sink) {
+    // the class's first launch: its regions' list counts to pinned memory behind the scan (once per handle, frame and size class)
+    V2TuneSlot &U = *F.eslot;
+    tune_e_first_launch(U, R.grid, B.n_reads, [&] {
+      bool ok = U.h_counts || U.h_counts.alloc((size_t)4096 * V2_L_COUNTS) == DCRX_OK;
+      ok = ok && (U.ev_counts || U.ev_counts.create(false) == DCRX_OK);
+      ok = ok && R.grid <= 4096u && hipMemcpyAsync(U.h_counts, Q.counts, (size_t)R.grid * V2_L_COUNTS * 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
+           hipEventRecord(U.ev_counts, s) == hipSuccess;
+      if (!ok) (void)hipGetLastError();
+      return ok;
+    });
   }
-  if (finish) {
-    // waves of the finishing roles that share a region (a scan block's list): as many as keep 8192 waves on the tail list and
-    // 4096 on each rescue list of a full-size launch
-    // (measured, profiles/r04/rescue_waves_*.log, config3_finish_waves_*.log: where the launch also holds the tail role — the
-    // extended sets — 4 096 tail waves and 3 072 rescue waves per list run config 3's step 6 % faster than 8 192 and 4 096: fewer
-    // blocks wait for a slot; where the scan has taken the tail, config 2 would take 3 072 rescue waves (- 2 %) and config 5 loses
-    // 4 % on them: the 4 096 stay there)
-    static const uint32_t rescue_waves_env = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_RESCUE_WAVES"); const int v = e ? atoi(e) : 0; return v >= 256 ? (uint32_t)v : 0u; }();      // (A/B)
-    // (batches of 2^25 reads and more, fused form: 8 192 — config 5 at 100 M reads per launch 18.4 against 17.4 G reads/s, config 2
-    // 32.0 against 31.4; at 30 M + 2 % / none: profiles/r05/rescue_waves_by_batch_size.log)
-    const bool big = B.n_reads >= V2Tune::BIG_BATCH;
-    const uint32_t waves_first = (ring_batches && !separate && big) ? 8192u : 4096u, waves_second = (ring_batches && !separate && big) ? 4096u : 3072u;
-    // (the tail as a role of this launch — the extended sets of config 3 —: 3 072, and 4 096 for big batches: 19.3 against 18.8 G reads/s
-    // at 100 M reads, 16.3 against 16.6 at 10 M; profiles/r05/config3_waves_by_batch_size.log)
-    uint32_t rescue_waves = rescue_waves_env ? rescue_waves_env : ((ring_batches || separate) ? waves_first : (big ? 4096u : 3072u));
-    // the fused form: the handle's own choice between 4 096 and 3 072 (V2Tune), timed on its first launches of this batch size
-    hipEvent_t tune_start = nullptr, tune_stop = nullptr;
-    static const bool tune_off = dcrx_debug_env("DCRX_DEBUG_NO_TUNE") != nullptr;      // (tests, A/B)
-    const int tune_class = V2Tune::size_class(B.n_reads);
-    if (ring_batches && !separate && !rescue_waves_env && !tune_off && P.tune && !retry && !cfg.flags && tune_class >= 0) {
-      V2TuneSlot &U = P.tune[o].slot[tune_class];      // (a size class of its own for every power of two: a short last batch does not unsettle the others')
-      if (U.choice) rescue_waves = U.choice;
-      else {
-        const int k = U.launches - 1;            // sample index of this launch (the first launch of a size is not timed)
-        if (k >= 0 && k < V2Tune::SAMPLES) {
-          if (!U.created) {
-            bool ok = true;
-            for (int i = 0; i < V2Tune::SAMPLES && ok; i++)
-              ok = U.ev[i][0].create(true) == DCRX_OK && U.ev[i][1].create(true) == DCRX_OK;
-            U.created = ok;
-            if (!ok) { (void)hipGetLastError(); U.choice = waves_first; }
-          }
-          if (U.created) { rescue_waves = (k & 1) ? waves_second : waves_first; tune_start = U.ev[k][0]; tune_stop = U.ev[k][1]; }
-        } else if (k >= V2Tune::SAMPLES && U.created) {
-          // (a big batch's samples may be waited for, once, where the caller has said so — dcrx_set_tune_wait —: a caller that queues
-          // such launches ahead of the device — each takes milliseconds — would otherwise never find them complete; without that
-          // permission the call keeps its contract of never waiting and the handle stays on the first setting until a query succeeds)
-          if (big && k == V2Tune::SAMPLES && P.tune_may_wait) (void)hipEventSynchronize(U.ev[V2Tune::SAMPLES - 1][1]);      // (only where the caller allowed it: dcrx_set_tune_wait)
-          bool ready = true;
-          for (int i = 0; i < V2Tune::SAMPLES && ready; i++) ready = hipEventQuery(U.ev[i][1]) == hipSuccess;
-          (void)hipGetLastError();
-          if (ready) {
-            float ms[2] = {0.f, 0.f};
-            bool ok = true;
-            for (int i = 0; i < V2Tune::SAMPLES && ok; i++) {
-              float t = 0.f;
-              ok = hipEventElapsedTime(&t, U.ev[i][0], U.ev[i][1]) == hipSuccess;
-              ms[i & 1] += t;
-            }
-            (void)hipGetLastError();
-            U.choice = (ok && ms[1] < 0.985f * ms[0]) ? waves_second : waves_first;
-            if (ok) { U.us[0] = 1e3f * ms[0] / (V2Tune::SAMPLES / 2); U.us[1] = 1e3f * ms[1] / (V2Tune::SAMPLES / 2); }
-            rescue_waves = U.choice;
-            static const bool say = dcrx_debug_env("DCRX_DEBUG_TUNE") != nullptr;
-            if (say) fprintf(stderr, "dcrx tune: finishing launches of %llu reads, frame %d: %.1f us on %u rescue waves, %.1f on %u -> %u (launch %d)\n",
-                             (unsigned long long)B.n_reads, o, 1e3f * ms[0] / (V2Tune::SAMPLES / 2), waves_first, 1e3f * ms[1] / (V2Tune::SAMPLES / 2), waves_second, U.choice, U.launches);
-          }
-        }
-        U.launches++;
-      }
-    }
-    static const uint32_t tail_role_waves_env = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_TAIL_ROLE_WAVES"); const int v = e ? atoi(e) : 0; return v >= 256 ? (uint32_t)v : 0u; }();      // (A/B)
-    const uint32_t tail_role_waves = tail_role_waves_env ? tail_role_waves_env : (separate ? 8192u : 4096u);
-    const uint32_t tsplit = std::max<uint32_t>(1u, std::min<uint32_t>(64u, tail_role_waves / n_regions));
-    const uint32_t rsplit_full = std::max<uint32_t>(1u, std::min<uint32_t>(64u, rescue_waves / n_regions));
-    const uint32_t rsplit = fuse_e ? 1u : rsplit_full;      // (FUSE_E: list E is empty — its entries went through the scan's event ring —: one wave per region looks)
-    static const uint32_t rescue_waves_c = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_RESCUE_WAVES_C"); const int v = e ? atoi(e) : 0; return v >= 256 ? (uint32_t)v : 0u; }();      // (A/B)
-    const uint32_t csplit = rescue_waves_c ? std::max<uint32_t>(1u, std::min<uint32_t>(64u, rescue_waves_c / n_regions)) : rsplit_full;
-    // (list C's jobs behind list E's on the same waves — one round of blocks instead of two — were measured: the step 3 % longer
-    // on config 2, 8 % on config 5: list C's batches are the slow ones, two sweeps each, and want to start with the launch;
-    // profiles/r05/finish_list_c_folded_ab.log.  List C's jobs IN FRONT of list E's on the same waves: 1-2 % longer still
-    // than list E's blocks first and list C's in the second round, as shipped; finish_one_round_c_first_ab.log)
-    const uint32_t fgrid = (n_regions * (rsplit + csplit) + DCRX_V2_FBLOCK / 64 - 1) / (DCRX_V2_FBLOCK / 64);
-    const uint32_t egrid = (n_regions + DCRX_V2_FBLOCK / 64 - 1) / (DCRX_V2_FBLOCK / 64);      // the general form over a whole event list (A/B): a block takes four regions
-    // blocks of a short list's pass that share a region: as a pass of its own (A/B forms) the list's latency is the launch's, and
-    // four blocks per region halve it; as a role under the lean rescue one block per region does (its rounds run hidden)
-    static const uint32_t bsplit_env = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_X_BSPLIT"); const int v = e ? atoi(e) : 0; return (v >= 1 && v <= 16) ? (uint32_t)v : 0u; }();      // (A/B)
-    // (FUSE_E: with list E gone the launch is as long as list X's chains of single reads: two blocks per region 46 us, one 57, four 65 —
-    // profiles/r06/list_e_in_the_scan_ab.log)
-    const uint32_t bsplit = bsplit_env ? bsplit_env : (separate ? std::max<uint32_t>(1u, std::min<uint32_t>(16u, 1024u / n_regions)) : (fuse_e ? 2u : 1u));
-    const uint32_t sgrid = n_regions * bsplit;
-    const uint32_t flds = v2_finish_lds_bytes(T, o);
-    const uint32_t llds = v2_finish_block_lds<NW>(T, o, DCRX_V2_FBLOCK);      // the lean roles: + a strip per lane (+ the rescue's scratch counters)
-    const uint32_t tlds = v2_finish_block_lds<NW>(T, o, DCRX_V2_TBLOCK);
-    const uint32_t elds_ext = flds + (T.lds_image2_bytes - T.lds_image_bytes);
-    const uint32_t ext = elds_ext <= 64u * 1024u ? 1u : 0u;      // the event kernel's LDS with the germline regions in it
-    const uint32_t elds = ext ? elds_ext : flds;
-    const uint32_t slow_width = 4u;        // lanes of a wave that take entries of a short list (64 / 16 / 4 / 2 / 1: 97 / 62 / 57 / 65 / 79 us)
-    const uint32_t tgrid = (n_regions * tsplit + DCRX_V2_TBLOCK / 64 - 1) / (DCRX_V2_TBLOCK / 64);
-    V2Roles R;
-    R.xgrid = sgrid; R.rgrid = fgrid; R.tgrid = ring_batches ? 0u : (n_regions * tsplit + DCRX_V2_FBLOCK / 64 - 1) / (DCRX_V2_FBLOCK / 64);      // (fused: the tail list is empty)
-    R.rsplit = rsplit | (csplit << 8); R.tsplit = tsplit; R.bsplit = bsplit; R.width = slow_width;
+  if (F.finish) {
+    const V2Waves W = v2_rescue_waves(P, B, cfg, o, F, retry);
+    const V2Geometry G = v2_geometry<NW>(T, o, R, F, W.rescue);
     V2FinishArgs A;
-    A.T0 = T; A.B = B; A.cfg = cfg; A.records = rec; A.counters = d_counters; A.Q = Q; A.n_regions = n_regions; A.R = R;
+    A.T0 = T; A.B = B; A.cfg = cfg; A.records = rec; A.counters = d_counters; A.Q = Q; A.n_regions = G.n_regions; A.R = G.roles(ring_batches != 0u);
     A.queue = queue; A.gqueue = gqueue; A.qcap = qcap; A.queue_count = queue_count; A.Tmem = P.dev_tables; A.S = S;
-    if (!separate) {
-      hipExtLaunchKernelGGL(S.dev ? (ring_batches ? kf0_sink : kf_sink) : (ring_batches ? kf0 : kf), dim3(R.xgrid + R.rgrid + R.tgrid), dim3(DCRX_V2_FBLOCK), llds, s, tune_start,
-                            tune_stop ? tune_stop : e_ev_stop, 0, A);
+    if (F.order == V2Order::ROLES) {
+      hipExtLaunchKernelGGL(F.sink ? (ring_batches ? K.finish0_sink : K.finish_sink) : (ring_batches ? K.finish0 : K.finish), dim3(A.R.xgrid + A.R.rgrid + A.R.tgrid), dim3(DCRX_V2_FBLOCK),
+                            G.llds, s, W.start, W.stop ? W.stop : F.e_stop, 0, A);
       e = hipGetLastError();
-      if (e != hipSuccess) return e;
     } else {
-      auto general = [&](hipStream_t st, const int which, const bool whole_list, hipEvent_t stop) -> hipError_t {
-        if (whole_list)
-          hipExtLaunchKernelGGL(ke, dim3(egrid), dim3(DCRX_V2_FBLOCK), elds, st, nullptr, stop, 0, T, B, cfg, rec, d_counters, Q, which, (uint32_t)(DCRX_V2_FBLOCK / 64), 64u, 1u, ext,
-                                n_regions, queue, gqueue, qcap, queue_count);
-        else
-          hipExtLaunchKernelGGL(ke, dim3(sgrid), dim3(DCRX_V2_FBLOCK), elds, st, nullptr, stop, 0, T, B, cfg, rec, d_counters, Q, which, 1u, slow_width, bsplit, ext, n_regions, queue,
-                                gqueue, qcap, queue_count);
-        return hipGetLastError();
-      };
-      if (side) {
-        e = hipStreamWaitEvent(P.v2_side, fork_ev, 0); if (e != hipSuccess) return e;
-        hipExtLaunchKernelGGL(kt, dim3(tgrid), dim3(DCRX_V2_TBLOCK), tlds, P.v2_side, nullptr, P.v2_ev_join, 0, T, B, cfg, rec, d_counters, Q, n_regions, tsplit, queue,
-                              gqueue, qcap, queue_count, P.dev_tables);
-        e = hipGetLastError(); if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(P.v2_side2, fork_ev, 0); if (e != hipSuccess) return e;
-        e = general(P.v2_side2, V2_L_X, false, P.v2_ev_join2); if (e != hipSuccess) return e;
-      }
-      // the scan kernel's event lists E and C: the lean rescue, or — A/B — the general form at once
-      if (cfg.flags & DCRX_F_V2_NO_LEAN_RESCUE) {
-        for (int which = V2_L_E; which <= V2_L_C; which++) { e = general(s, which, true, nullptr); if (e != hipSuccess) return e; }
-      } else {
-        hipLaunchKernelGGL(kr, dim3(fgrid), dim3(DCRX_V2_FBLOCK), llds, s, T, B, cfg, rec, d_counters, Q, n_regions, rsplit | (csplit << 8), queue, gqueue, qcap,
-                           queue_count, P.dev_tables);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-      }
-      if (side) {
-        e = hipStreamWaitEvent(s, P.v2_ev_join, 0); if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(s, P.v2_ev_join2, 0); if (e != hipSuccess) return e;
-      } else {
-        hipLaunchKernelGGL(kt, dim3(tgrid), dim3(DCRX_V2_TBLOCK), tlds, s, T, B, cfg, rec, d_counters, Q, n_regions, tsplit, queue, gqueue, qcap, queue_count, P.dev_tables);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        e = general(s, V2_L_X, false, nullptr); if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(kl, dim3(1), dim3(DCRX_V2_FBLOCK), llds, s, A);      // what the lean kernels left
-      e = hipGetLastError(); if (e != hipSuccess) return e;
+      e = launch_v2_separate(K, P, A, G, side, s, fork_ev);
     }
-    static const bool dbg = dcrx_debug_env("DCRX_DEBUG_V2_COUNTS") != nullptr;
-    if (dbg && e == hipSuccess) {          // debugging aid: the lists' populations (synchronises)
-      std::vector<uint32_t> h((size_t)V2_L_COUNTS * n_regions);
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(h.data(), Q.counts, h.size() * 4, hipMemcpyDeviceToHost);
-      unsigned long long t[V2_L_COUNTS] = {0};
-      for (uint32_t r = 0; r < n_regions; r++) for (int k = 0; k < V2_L_COUNTS; k++) t[k] += h[(size_t)V2_L_COUNTS * r + k];
-      fprintf(stderr, "dcrx v2 lists: regions %u tail %llu E %llu C %llu X %llu; LDS of a finishing block %u bytes (side tables %u, buckets %u), of a scan block %u\n", n_regions,
-              t[V2_L_TAIL], t[V2_L_E], t[V2_L_C], t[V2_L_X], llds, T.lds_image_bytes - T.dfa_bytes, T.v2[o].bk_bytes, scan_lds);
-    }
+    if (e != hipSuccess) return e;
+    if (knobs.say_counts) v2_dump_counts(T, o, Q, G, F.scan_lds, s);
   }
 #ifdef DCRX_SCAN_STAMPS
-  {      // instrumented build (tools/): when do a scan block's waves start, leave their loops and end?  (synchronises; launch DCRX_STAMPS_LAUNCH of the process, default 30)
-    static int launches = 0;
-    static const int want = [] { const char *e = dcrx_debug_env("DCRX_STAMPS_LAUNCH"); return e ? atoi(e) : 30; }();
-    if (launches++ == want && e == hipSuccess) {
-      const size_t nw = (size_t)n_regions * (DCRX_V2_BLOCK / 64);
-      std::vector<uint32_t> h(4 * nw);
-      (void)hipStreamSynchronize(s);
-      uint32_t *dptr = nullptr;
-      (void)hipMemcpyFromSymbol(&dptr, HIP_SYMBOL(g_scan_stamps), sizeof(dptr));
-      (void)hipMemcpy(h.data(), dptr, h.size() * 4, hipMemcpyDeviceToHost);
-      if (const char *dump = dcrx_debug_env("DCRX_STAMPS_DUMP")) { FILE *f = fopen(dump, "wb"); if (f) { fwrite(h.data(), 4, h.size(), f); fclose(f); } }
-      uint32_t t0 = 0xFFFFFFFFu;
-      for (size_t i = 0; i < nw; i++) t0 = std::min(t0, h[4 * i]);
-      auto pcs = [&](const char *what, std::vector<double> v) {
-        std::sort(v.begin(), v.end());
-        auto pc = [&](double q) { return v[(size_t)(q * (v.size() - 1))]; };
-        fprintf(stderr, "dcrx scan stamps: %-44s min %6.1f p10 %6.1f p50 %6.1f p90 %6.1f p99 %6.1f max %6.1f us\n", what, pc(0), pc(0.1), pc(0.5), pc(0.9), pc(0.99), pc(1.0));
-      };
-      std::vector<double> st, su, le_scan, le_tail, en, blk_scan_end, blk_end;
-      for (uint32_t r = 0; r < n_regions; r++) {
-        double last_scan = 0, last = 0;
-        for (int wv = 0; wv < DCRX_V2_BLOCK / 64; wv++) {
-          const uint32_t *c = &h[4 * ((size_t)r * (DCRX_V2_BLOCK / 64) + wv)];
-          st.push_back((c[0] - t0) / 100.0); su.push_back((c[1] - t0) / 100.0); en.push_back((c[3] - t0) / 100.0);
-          const bool tailw = ring_batches && wv >= (DCRX_V2_BLOCK / 64) - 3;      // (a guess at three tail waves: the block's own choice is not known here)
-          (tailw ? le_tail : le_scan).push_back((c[2] - t0) / 100.0);
-          if (!tailw) last_scan = std::max(last_scan, (c[2] - t0) / 100.0);
-          last = std::max(last, (c[3] - t0) / 100.0);
-        }
-        blk_scan_end.push_back(last_scan); blk_end.push_back(last);
-      }
-      pcs("wave start", st); pcs("wave set-up done (tables staged)", su); pcs("scanning wave leaves its loop", le_scan);
-      if (!le_tail.empty()) pcs("tail wave leaves its loop (last three waves)", le_tail);
-      pcs("wave end", en); pcs("per block: last scanning wave leaves", blk_scan_end); pcs("per block: end", blk_end);
-    }
-  }
+  v2_stamps_dump(R.n_regions, ring_batches != 0u, s);
 #endif
   return e;
 }
@@ -2208,14 +2222,12 @@ static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const Batch
 // the tuple sink's place kernel behind the list kernel (the call's last launch: its stop event rides here)
 hipError_t launch_v2_place(const LaunchPlan &P, const V2SinkLaunch &K, uint64_t n_reads, hipStream_t s, hipEvent_t ev_stop) {
   static bool seen[64];
-  if (first_use_on_device(seen)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(v2_place_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) return e;
-    attributes_set_on_device(seen);
-  }
+  const KernelLds place_lds = {reinterpret_cast<const void *>(v2_place_kernel), 150 * 1024, false};
+  const hipError_t e = set_lds_ceilings(seen, &place_lds, 1);
+  if (e != hipSuccess) return e;
   // LDS: the region's bitmap and its ranks, then room to stage its tuples (5 bytes each) for whole-line stores: as many as fit
   const uint32_t words = (K.S.per_block / 32u) * 2u;
-  static const int hcap_forced = [] { const char *e = dcrx_debug_env("DCRX_DEBUG_PLACE_HCAP"); return e ? atoi(e) : -1; }();      // (tests: the path of regions whose tuples do not fit)
+  static const int hcap_forced = dcrx_debug_int("DCRX_DEBUG_PLACE_HCAP", 0, INT_MAX, -1);      // (tests: the path of regions whose tuples do not fit)
   const uint32_t hcap = hcap_forced >= 0 ? ((uint32_t)hcap_forced & ~3u) : (std::min<uint32_t>(K.S.per_block, (150u * 1024u - words * 4u) / 5u) & ~3u);
   const uint32_t lds = words * 4u + hcap * 5u;
   hipExtLaunchKernelGGL(v2_place_kernel, dim3(K.n_regions), dim3(V2_PLACE_BLOCK), lds, s, nullptr, ev_stop, 0, K.S, K.counts, K.n_regions, K.tcap, K.ecap,
@@ -2223,7 +2235,7 @@ hipError_t launch_v2_place(const LaunchPlan &P, const V2SinkLaunch &K, uint64_t 
   return hipGetLastError();
 }
 // items of a sink's slabs for batches of up to max_reads reads: per region the three lists' capacities and as many late slots
-// as the region has reads (launch_v2: tcap, ecap, scap / 2 <= pb128 each)
+// as the region has reads (V2Regions::sink_stride: tcap, ecap, scap / 2 <= pb128 each)
 uint64_t v2_sink_items(uint64_t max_reads, uint32_t n_cu) { return 4 * (max_reads + (uint64_t)n_cu * 1024) + 4096; }
 
 hipError_t launch_v2_any(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,

@@ -10,6 +10,7 @@
 #include "dcrx_hip.h"
 
 #include "dcrx_launch_types.h"
+#include "dcrx_tune.h"
 
 namespace dcrx {
 
@@ -47,48 +48,27 @@ struct V2SinkJob {
   bool *done = nullptr;
 };
 
-// A handle's own choice of the waves that share a region's list E in the finishing launch of the fused form (launch_v2): 16 per
-// region suit some tag sets and 12 others by 1-4 % of the step, whatever the reads are, so a handle
-// times its own launches: behind its first launch of a batch size two finishing launches on 16 and two on 12 in turn carry
-// a pair of events on their dispatch (no marker packets), later launches look (hipEventQuery: no waiting) whether the pairs
-// have completed, and the setting whose launches were at least 1.5 % shorter on average stays; else 16.  One per frame.
-struct V2TuneSlot {
-  static constexpr int SAMPLES = 2;      // (one per setting — the two differ by a tenth of the launch, samples by a hundredth —: launches 1 and 2 of a size class, so that a caller's third or fourth launch finds them complete and runs on the choice)
-  uint32_t choice = 0;               // rescue waves once settled (0: not yet)
-  int launches = 0;                  // launches seen in this size class
-  Event ev[SAMPLES][2];              // (start, stop) of the finishing launch of sample k
-  bool created = false;              // all of them exist
-  // list E inside the scan kernel (FUSE_E) or a role of the finishing launch: decided once per size class from the share of the
-  // reads that were list-E entries in the class's first launch (the regions' counts copied to pinned memory behind that launch,
-  // read when the copy's event has passed: no wait)
-  int fuse_e = -1;                   // -1 not known yet, -2 the share allows it: the two forms are being timed, 0 a role, 1 inside the scan
-  static constexpr int E_PAIRS = 3, E_FIRST = 8;      // pairs of timed launches (a role, fused), from the class's E_FIRST-th eligible launch on (the clocks have come up by then)
-  int e_phase = 0;                   // (fuse_e == -2) eligible launches seen: E_FIRST + 2 k runs as a role under a pair of events, E_FIRST + 2 k + 1 fused; then the events are read
-  Event ev_e[2 * E_PAIRS][2];        // (start on the scan's dispatch, stop on the finishing launch's) per timed launch
-  float us_e[2] = {0.f, 0.f};        // what the samples said: mean of the launches with list E a role / inside the scan
-  bool e_sampling = false;
-  Event ev_counts;
-  PinnedBuf<uint32_t> h_counts;      // V2_L_COUNTS words per region
-  uint32_t e_regions = 0;
-  uint64_t e_reads = 0;
-  float e_share = -1.f;
-  float us[2] = {0.f, 0.f};          // what the samples said: a finishing launch on 4 096 / on 3 072 rescue waves (dcrx_tune_state)
+// The clock of a handle's own timing (dcrx_tune.h) in production: HIP events, read without waiting.  (A query that finds an
+// event not complete leaves hipErrorNotReady behind: launch_v2 clears it.)
+struct HipTuneClock {
+  using Event = dcrx::Event;
+  using Counts = PinnedBuf<uint32_t>;
+  bool create(Event &e, bool timing) { return e.create(timing) == DCRX_OK; }
+  bool done(const Event &e) { return hipEventQuery(e) == hipSuccess; }
+  bool elapsed_ms(const Event &a, const Event &b, float &ms) { return hipEventElapsedTime(&ms, a, b) == hipSuccess; }
+  void wait(const Event &e) { (void)hipEventSynchronize(e); }
 };
-// ... per size class (batches of 2^(20 + k) .. 2^(21 + k) - 1 reads share a slot): a short last chunk of a host call, or the
-// short last step of a shard, falls into another class and leaves the settled one alone.
-struct V2Tune {
-  static constexpr int SAMPLES = V2TuneSlot::SAMPLES;
-  static constexpr int CLASSES = 12;
-  static constexpr uint64_t BIG_BATCH = 1ull << 25;      // reads: from here a handle chooses between 8 192 and 4 096 rescue waves (below: 4 096 and 3 072)
-  V2TuneSlot slot[CLASSES];
-  uint32_t last_form = 0;            // the frame's last call: 0 none yet, 1 the three-launch form, 2 the v2 kernels (tail as a role), 3 v2 with the tail inside the scan
-  static int size_class(uint64_t n_reads) {      // -1: below a million reads (not tuned)
-    if (n_reads < (1ull << 20)) return -1;
-    int k = 0;
-    while (k + 1 < CLASSES && (n_reads >> (21 + k)) != 0) k++;
-    return k;
-  }
+using V2TuneSlot = V2TuneSlotT<HipTuneClock>;
+using V2Tune = V2TuneT<HipTuneClock>;
+
+// a kernel and the dynamic LDS its launches may ask for (set_lds_ceilings, dcrx_kernels.hip)
+struct KernelLds {
+  const void *kernel;
+  int bytes;
+  bool no_static_lds;      // the kernel addresses its table from LDS address 0: static LDS in front of the dynamic segment is refused (hipErrorNotSupported)
 };
+bool first_use_on_device(bool (&seen)[64]);
+hipError_t set_lds_ceilings(bool (&seen)[64], const KernelLds *list, int n);
 
 struct LaunchPlan {
   uint32_t n_cu;

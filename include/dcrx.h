@@ -796,7 +796,8 @@ int64_t dcrx_format_clonotypes(uint64_t m, const uint32_t *rep, const uint64_t *
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
  * 4096 from there (`candidates`: the first setting | the second << 16).  rescue_waves = the choice once settled, 0 before (a
- * launch then runs on the first setting or is one of the two samples); launches = calls seen in the class; us_first / us_second =
+ * launch then runs on the first setting or is one of the two samples); launches = the class's calls that took part, counted until
+ * the choice settled (calls with cfg flags, and the second pass of orientation `both`, take no part); us_first / us_second =
  * what the samples took (0 before).  The samples are read without waiting, so a caller that queues launches ahead of the device
  * keeps the first setting until they are complete — except, where the caller has allowed it with dcrx_set_tune_wait(tables, 1),
  * for batches of 2^25 reads and more: the fourth call of such a class then waits for the third's finishing launch, once
@@ -805,8 +806,10 @@ int64_t dcrx_format_clonotypes(uint64_t m, const uint32_t *rep, const uint64_t *
  * DCRX_E_INVALID for a null argument.
  * Round 6: where the scan kernel takes the tail, a handle also settles per size class whether list E's entries (one gene to rescue) are
  * finished inside the scan kernel as well (launch_form 4) or by the finishing launch (3): where list E held at most a quarter of the
- * reads of the class's first launch, three launches of each form are timed (events on the dispatches, read without waiting) from
- * the class's ninth launch on, and the faster form stays. */
+ * reads of the class's first launch, three launches of each form are timed (events on the dispatches, read without waiting) and
+ * the form inside the scan stays if it was at least 1.5 % shorter.  Only calls made once the first launch's lists have been
+ * counted and the rescue waves are settled, without events of the caller's (dcrx_set_step_events) and without a tuple sink, count
+ * for this: the ninth of them is the first timed one. */
 typedef struct dcrx_tune_state {
   uint32_t rescue_waves, launches;
   float us_first, us_second;

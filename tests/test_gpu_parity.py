@@ -981,3 +981,80 @@ def test_timed_launch_shapes_at_size(config, env):
         assert "tail and list E inside the scan" in p.stdout, p.stdout
     if env.get("DCRX_DEBUG_FUSE_E") == "0":
         assert "'launch_form': 'v2, tail inside the scan'" in p.stdout, p.stdout
+
+
+# ---- the launcher's geometry at its edges, and its forms one after the other on one handle ----
+
+_small = {}
+
+
+def _small_config2(n):
+    """A handle of config 2, n uniform 150-nt reads (made once per size), and orientation -> their oracle records and counters
+    (each computed once)."""
+    if "tables" not in _small:
+        _small["tables"] = _tables(synth.config_tagset(2))
+    t, ot = _small["tables"]
+    if n not in _small:
+        hb = nat.synth_reads_host(t, nat.synth_cfg(seed=41, sub_rate=0.01, n_rate=0.002), 0, n) if n else nat.pack_reads([])
+        reads = nat.unpack_reads(hb) if n else []
+        made = {}
+
+        def want(orientation):
+            if orientation not in made:
+                made[orientation] = pu.oracle_records(ot, reads, orientation, False, 130)
+            return made[orientation]
+        _small[n] = (hb, reads, want)
+    return (t,) + _small[n]
+
+
+@pytest.mark.parametrize("flags", [0, nat.F_V2_NO_FUSE], ids=["fused", "tail-as-a-role"])
+@pytest.mark.parametrize("n", [0, 1, 129, 2049, 5000])
+def test_launch_geometry_at_its_edge_sizes(n, flags):
+    """The scan's grid is min(CUs, ceil(ceil(n / 128) / 16)) blocks and a block's range a multiple of 512 reads: nothing to launch,
+    one read, two items in one block, seventeen items (two blocks, two regions), and a few blocks."""
+    t, hb, reads, want = _small_config2(n)
+    rec, cnt = nat.decombine(t, hb, flags=flags)
+    if n == 0:
+        assert len(rec) == 0 and int(cnt.sum()) == 0
+        return
+    assert hb.lens is None and len(rec) == n
+    pu.assert_records_equal(rec, want("reverse")[0], reads, f"n = {n}")
+    pu.assert_counters_equal(cnt, want("reverse")[1], f"n = {n}")
+
+
+FORM_SEQUENCE = [("reverse", 0), ("reverse", nat.F_V2_NO_FUSE), ("reverse", nat.F_V2_NO_LEAN_RESCUE), ("reverse", nat.F_V2_LEAN_SERIAL),
+                 ("reverse", nat.F_V2_SIDE_STREAMS), ("reverse", nat.F_V2_SHAPE(3)), ("reverse", nat.F_V1_KERNELS), ("reverse", 0),
+                 ("forward", 0), ("both", 0)]
+FORM_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_forms_in_sequence.json")
+
+
+def launch_forms_in_sequence(check=None):
+    """FORM_SEQUENCE on one fresh handle, 5000 reads per call: what dcrx_tune_state reports as the launch form of either frame
+    after each call."""
+    ts = synth.config_tagset(2)
+    t, _ = _tables(ts)
+    _, hb, reads, want = _small_config2(5000)
+    seen = []
+    for orientation, flags in FORM_SEQUENCE:
+        rec, cnt = nat.decombine(t, hb, orientation=orientation, flags=flags)
+        if check:
+            check(rec, cnt, reads, want(orientation), f"{orientation}, flags {flags}")
+        seen.append({"orientation": orientation, "flags": flags,
+                     "launch_form": {o: t.tune_state(5000, o)["launch_form"] for o in ("reverse", "forward")}})
+    return seen
+
+
+def test_launch_forms_in_sequence_on_one_handle():
+    """A handle that has fused so far holds no tail list: the second call goes through hipErrorNotReady, the allocation and the
+    relaunch in dcrx_decombine_device; then every A/B form, the three-launch form, the shipped form again and the other
+    orientations.  Records and counters against the oracle after each call, and the launch form the handle reports against
+    what the build before launch_v2 was split into steps reported for the same sequence (tests/golden)."""
+    import json
+
+    def check(rec, cnt, reads, want, what):
+        pu.assert_records_equal(rec, want[0], reads, what)
+        pu.assert_counters_equal(cnt, want[1], what)
+    seen = launch_forms_in_sequence(check)
+    golden = json.load(open(FORM_GOLDEN))
+    assert golden["n_reads"] == 5000 and len(golden["steps"]) == len(FORM_SEQUENCE)
+    assert seen == golden["steps"]
