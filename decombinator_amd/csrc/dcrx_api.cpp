@@ -103,9 +103,8 @@ struct dcrx_tables {
   uint32_t reserved_cus = 0;
   bool tune_may_wait = false;       // dcrx_set_tune_wait
   // the tail list (a third of the lists' bytes) exists only for handles whose calls keep the tail a role of the finishing launch:
-  // where the scan takes the tail through its ring in LDS nothing is ever stored in it.  Unknown: decided by the first use
-  // (table sizes), corrected by the first launch that turns out to need the list (dcrx_decombine_device allocates it and launches again)
-  int want_tail = -1;
+  // set by the first route that needs it (ensure_device), and stays set
+  bool want_tail = false;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;      // around the dominant kernel (the caller's: dcrx_set_timing_events)
   hipEvent_t ev_step_start = nullptr, ev_step_stop = nullptr;  // around every launch of a call (the caller's)
   // the tuple sink (dcrx_set_tuple_sink): where the next calls leave their message
@@ -270,17 +269,19 @@ static int first_use(const dcrx_tables *t, int dev, DeviceState *out) {
   return DCRX_OK;
 }
 
-// the handle's workspace on the current device holds batches of up to max_reads reads of this stride (sizes kept in the plan
-// say what is allocated; a list that failed to grow is gone and its size is zero)
-static int grow_workspace(dcrx_tables *t, uint64_t max_reads, uint32_t stride) {
+// the handle's tables and plan are on the caller's current device
+static int use_device(dcrx_tables *t) {
   int dev = -1;
   HIP_TRY(hipGetDevice(&dev));
-  if (t->state.device != dev) {
-    free_device_state(t);       // tables move with the caller's current device
-    // (built aside and committed whole: a first use that fails part-way leaves the handle empty, and what it had allocated is freed)
-    int rc = first_use(t, dev, &t->state);
-    if (rc) return rc;
-  }
+  if (t->state.device == dev) return DCRX_OK;
+  free_device_state(t);       // tables move with the caller's current device
+  // (built aside and committed whole: a first use that fails part-way leaves the handle empty, and what it had allocated is freed)
+  return first_use(t, dev, &t->state);
+}
+
+// the handle's workspace on its device holds batches of up to max_reads reads of this stride, and the tail list where
+// want_tail says so (sizes kept in the plan say what is allocated; a list that failed to grow is gone and its size is zero)
+static int grow_workspace(dcrx_tables *t, uint64_t max_reads, uint32_t stride) {
   DeviceState &S = t->state;
   LaunchPlan &P = S.plan;
   int rc;
@@ -298,9 +299,6 @@ static int grow_workspace(dcrx_tables *t, uint64_t max_reads, uint32_t stride) {
     // entries; an entry carries the read's packed words, so the size follows the stride
     uint64_t tr = 0, er = 0;
     v2_list_rows(max_reads, stride, P.n_cu, &tr, &er);
-    // (the fused form: 150-nt shapes, pair tables of up to 64 KB — launch_v2; either frame may be asked for)
-    if (t->want_tail < 0)
-      t->want_tail = (stride <= 40 && std::max(t->host.rel.v2[0].trans_bytes, t->host.rel.v2[1].trans_bytes) <= 64u * 1024u) ? 0 : 1;
     if (t->want_tail && tr > P.v2_tail_rows) {
       P.v2_tail_rows = 0;
       if ((rc = S.v2_tail.alloc(tr))) return rc;
@@ -346,8 +344,18 @@ static void fill_plan(DeviceState &S) {
   P.v2_ev_fork = S.v2_ev_fork; P.v2_ev_join = S.v2_ev_join; P.v2_ev_join2 = S.v2_ev_join2;
 }
 
-static int ensure_device(dcrx_tables *t, uint64_t max_reads, uint32_t stride = 40, hipStream_t stream = nullptr) {
-  int rc = grow_workspace(t, max_reads, stride);
+// cfg, uniform: the call the workspace is for, whose route (dcrx_route.h) comes back in *route; no call in hand
+// (dcrx_reserve_device, the host-buffer pipeline, entries that only need the tables): either frame might be asked for, no flags
+static int ensure_device(dcrx_tables *t, uint64_t max_reads, uint32_t stride = 40, hipStream_t stream = nullptr, const dcrx_cfg_t *cfg = nullptr,
+                         bool uniform = true, Route *route = nullptr) {
+  int rc = use_device(t);
+  if (!rc) {
+    auto ask = [&](int orientation, uint32_t flags) { return route_of(route_facts(t->state.plan, t->state.dev, stride, uniform, max_reads, orientation, flags)); };
+    const Route R = cfg ? ask(cfg->orientation, cfg->flags) : ask(DCRX_ORIENT_REVERSE, 0);
+    if (R.needs_tail_list || (!cfg && ask(DCRX_ORIENT_FORWARD, 0).needs_tail_list)) t->want_tail = true;
+    if (route) *route = R;
+    rc = grow_workspace(t, max_reads, stride);
+  }
   DeviceState &S = t->state;
   fill_plan(S);
   if (rc) return rc;
@@ -430,7 +438,8 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
   if (cfg->flags & DCRX_F_PROFILE_MASK) {       // profiling switches: the records are then not results
     if (!dcrx_debug_flags_on()) return set_err(DCRX_E_INVALID, "cfg.flags holds a profiling switch (records would not be results): set DCRX_DEBUG_FLAGS=1 to allow it");
   }
-  rc = ensure_device(t, b->n_reads, b->stride, (hipStream_t)stream);
+  Route route;      // what the call will launch, before anything is: the workspace is sized for it, and launch_decombine runs it
+  rc = ensure_device(t, b->n_reads, b->stride, (hipStream_t)stream, cfg, b->lens == nullptr, &route);
   if (rc) return rc;
   BatchDev B;
   B.packed = b->packed; B.stride = b->stride; B.read_len = b->read_len; B.lens = b->lens;
@@ -463,22 +472,9 @@ int dcrx_decombine_device(dcrx_tables_t *t, const dcrx_cfg_t *cfg, const dcrx_ba
       J.bytes = LD.bytes; J.msg = t->sink_msg; J.n_slots = t->sink_slots; J.d_total = t->sink_total; J.done = &sink_done;
     }
   }
-  hipError_t le = launch_decombine(t->state.plan, t->state.dev, B, C, d_records, t->state.queue + DCRX_QUEUE_HEADER,
-                                   t->state.queue + DCRX_QUEUE_HEADER + t->state.exc_flag_reads, t->state.queue, d_counters,
-                                   (hipStream_t)stream, t->ev_start, t->ev_stop);
-  if (le == hipErrorNotReady && !t->want_tail) {
-    // the launch keeps the tail a role of the finishing launch (a frame whose table does not fuse, an A/B switch) and the handle
-    // has no tail list yet: nothing was launched — the list is allocated and the call launched again
-    // (orientation `both`: the first pass may have run and tallied before the second found its frame without a tail list — the
-    // workspace is zeroed again, on the same stream behind whatever ran, before the call starts over)
-    (void)hipGetLastError();
-    t->want_tail = 1;
-    t->ws_dirty = true;
-    rc = ensure_device(t, b->n_reads, b->stride, (hipStream_t)stream);
-    if (rc) { t->state.plan.sink = V2SinkJob{}; return rc; }
-    le = launch_decombine(t->state.plan, t->state.dev, B, C, d_records, t->state.queue + DCRX_QUEUE_HEADER, t->state.queue + DCRX_QUEUE_HEADER + t->state.exc_flag_reads,
-                          t->state.queue, d_counters, (hipStream_t)stream, t->ev_start, t->ev_stop);
-  }
+  const hipError_t le = launch_decombine(route, t->state.plan, t->state.dev, B, C, d_records, t->state.queue + DCRX_QUEUE_HEADER,
+                                         t->state.queue + DCRX_QUEUE_HEADER + t->state.exc_flag_reads, t->state.queue, d_counters,
+                                         (hipStream_t)stream, t->ev_start, t->ev_stop);
   t->state.plan.sink = V2SinkJob{};
   if (le != hipSuccess) { t->ws_dirty = true; return hip_fail(le, "launch_decombine"); }
   if (t->sink_on && !sink_done) {

@@ -638,135 +638,136 @@ hipError_t set_lds_ceilings(bool (&seen)[64], const KernelLds *list, const int n
   return hipSuccess;
 }
 
+// A kernel's 160 KB ceiling before its first launch on a device (`seen`: the kernel's own mark) and, for a persistent grid, as
+// many blocks as are resident at once for THIS table size on the units the plan leaves free, `cap` at most (queried per
+// launch: a host-side call, and tables of different sizes share the kernel instantiations)
+template <class K> static hipError_t lds_ceiling(bool (&seen)[64], K kernel) {
+  const KernelLds one = {reinterpret_cast<const void *>(kernel), 160 * 1024, false};
+  return set_lds_ceilings(seen, &one, 1);
+}
+template <class K> static hipError_t persistent_grid(bool (&seen)[64], K kernel, const LaunchPlan &P, int block, uint32_t lds, uint32_t cap, uint32_t &grid) {
+  int occ = 0;
+  hipError_t e = lds_ceiling(seen, kernel);
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, lds);
+  grid = std::min<uint32_t>(cap, free_cus(P) * (uint32_t)std::max(occ, 1));
+  return e;
+}
+
+// Where the caller's events go.  The step's start rides on the call's first dispatch — for the v2 kernels the scan's, unless
+// the scan's own start event claims that place or an empty batch launches no scan: then it is recorded in front —, the step's
+// stop on the last one.  The pair around the dominant kernel rides on the v2 scan's dispatch and is recorded around the fast
+// kernel of the three-launch form; the long form has none.
+struct CallEvents {
+  hipEvent_t in_front = nullptr, first = nullptr;      // the step's start: recorded before anything is launched / on the first dispatch, where that is not the scan
+  hipEvent_t scan_start = nullptr, scan_stop = nullptr;
+  hipEvent_t last = nullptr;          // on the last dispatch
+};
+static CallEvents call_events(const Route &R, const LaunchPlan &P, const bool empty, hipEvent_t ev_start, hipEvent_t ev_stop) {
+  CallEvents E;
+  E.last = P.ev_step_stop;
+  if (R.form == RouteForm::LONG) { E.first = P.ev_step_start; return E; }
+  E.scan_start = ev_start; E.scan_stop = ev_stop;
+  if (!R.v2()) E.first = P.ev_step_start;
+  else if (!ev_start && !empty) E.scan_start = P.ev_step_start;
+  else E.in_front = P.ev_step_start;
+  return E;
+}
+
+// The list kernel of a call: everything the kernels in front of it did not finish.  Four instantiations share one signature.
+struct ListLaunch {
+  decltype(&decombine_list_kernel<true, true>) kernel = nullptr;
+  uint32_t lds = 0, grid = 0;
+};
+template <bool TABLE_LDS, bool UNIFORM> static hipError_t list_launch_as(const LaunchPlan &P, ListLaunch &L) {
+  static bool seen[64];
+  L.kernel = decombine_list_kernel<TABLE_LDS, UNIFORM>;
+  L.lds = P.lds_bytes + DCRX_QUEUE_LDS_EXTRA;
+  return persistent_grid(seen, L.kernel, P, DCRX_QBLOCK, L.lds, P.qgrid, L.grid);
+}
+
+// The three-launch form: the prologue zeroes the caller's counters (and marks / lists the reads with exception bytes), the
+// kernels add their tallies with one atomic per counter and block, and the last kernel — the rescue kernel when the pair
+// table serves it, else the list kernel — leaves the work counters and the exception bitmap zeroed for the next batch.
 template <bool TABLE_LDS, bool UNIFORM, int NW, int ARITY>
-static hipError_t launch_all(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
-                             dcrx_record_t *rec, uint32_t *queue, uint32_t *gqueue, uint32_t *queue_count,
-                             unsigned long long *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+static hipError_t launch_three(const Route &R, const CallEvents &E, const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
+                               dcrx_record_t *rec, uint32_t *queue, uint32_t *gqueue, uint32_t *queue_count, unsigned long long *d_counters, hipStream_t s) {
   auto kfast = decombine_kernel<TABLE_LDS, UNIFORM, NW, ARITY>;
-  constexpr uint32_t FBLOCK = ARITY == 16 ? DCRX_BLOCK16 : DCRX_BLOCK;
   auto klist = decombine_list_kernel<TABLE_LDS, UNIFORM>;
-  const uint32_t lds_fast = ARITY == 16 ? P.lds16_bytes + DCRX_FAST16_LDS_EXTRA : P.lds_bytes + DCRX_FAST_LDS_EXTRA;
-  const uint32_t lds_list = P.lds_bytes + DCRX_QUEUE_LDS_EXTRA;
+  auto kresc = decombine_rescue_kernel<UNIFORM, NW>;
+  constexpr uint32_t FBLOCK = ARITY == 16 ? DCRX_BLOCK16 : DCRX_BLOCK;
   hipError_t e;
-  // persistent grids: as many blocks as are resident at once for THIS table size (queried per
-  // launch: a host-side call, and tables of different sizes share the kernel instantiations)
-  static bool attr_seen[64];
-  const KernelLds ceilings[] = {{reinterpret_cast<const void *>(kfast), 160 * 1024, false}, {reinterpret_cast<const void *>(klist), 160 * 1024, false}};
-  e = set_lds_ceilings(attr_seen, ceilings, 2);
-  if (e != hipSuccess) return e;
-  int occ_fast = 0, occ_list = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_fast, kfast, FBLOCK, lds_fast);
-  if (e != hipSuccess) return e;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_list, klist, DCRX_QBLOCK, lds_list);
-  if (e != hipSuccess) return e;
-  occ_fast = std::max(occ_fast, 1); occ_list = std::max(occ_list, 1);
-  // (the three-launch form holds 320 nt in registers: longer reads all go through its list kernel; the v2 kernels hold 511)
-  // (the v2 condition: its entries keep two flags above a 30-bit read index)
-  const bool v2_ok_here = B.stride <= 4 * DCRX_V2_NWLONG && v2_applies(P, T, cfg, B.stride) && B.n_reads < (1ull << 30);
-  // (`both` as two v2 passes: 0.69 ms per 10 M reads of config 2 against 28 ms through the list kernel)
-  const bool v2_both = cfg.orientation == DCRX_ORIENT_BOTH && v2_ok_here;
-  const bool all_general = (cfg.orientation == DCRX_ORIENT_BOTH && !v2_both) || (cfg.flags & DCRX_F_FORCE_SLOW_READER) || (B.stride > 4 * DCRX_NWMAX && !v2_ok_here);
-  // reserved_cus: compute units left to other streams (an RCCL gather running beside the scan)
-  const uint32_t cus = P.n_cu > P.reserved_cus ? P.n_cu - P.reserved_cus : 1u;
-  const bool v2 = v2_ok_here && cfg.orientation != DCRX_ORIENT_BOTH;
-  const uint32_t grid = all_general ? 0 : std::min<uint32_t>(P.grid, cus * (uint32_t)occ_fast);
-  const uint32_t qgrid = std::min<uint32_t>(P.qgrid, cus * (uint32_t)occ_list);
-  const uint32_t qcap = (uint32_t)(gqueue - queue);      // capacity of the rescue queue, of the general
-                                                         // list behind it, and of the list of exception-list offsets behind that
-  // The three-launch form: the prologue zeroes the caller's counters (and marks / lists the reads with exception bytes), the
-  // kernels add their tallies with one atomic per counter and block, and the list kernel leaves the work counters and the
-  // exception bitmap zeroed for the next batch.  The v2 kernels need no prologue: the scan blocks mark the exception reads of
-  // their own ranges, every kernel tallies into the handle's accumulator (zero between calls), and the list kernel — the
-  // last launch — hands the counters to the caller and re-arms the accumulator.
-  // (which form this call's launches take, for whoever asks: dcrx_tune_state — a fallback to the three-launch form is then seen,
-  // not inferred from the clock)
-  if (P.tune) P.tune[cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1].last_form = (v2 || v2_both) ? 2u : 1u;
-  unsigned long long *acc = (v2 || v2_both) ? reinterpret_cast<unsigned long long *>(P.v2_acc) : d_counters;
-  if (!(v2 || v2_both)) {
-    const uint64_t items = std::max<uint64_t>(all_general ? B.n_reads : 0, std::max<uint64_t>(B.n_exc, 1));
-    // (the call's start event, when one is set, rides on this dispatch)
-    hipExtLaunchKernelGGL(prologue_kernel, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, s, P.ev_step_start, nullptr, 0, B.exc_read, B.n_exc,
-                          all_general ? 1 : 0, 1, B.n_reads, const_cast<uint32_t *>(B.exc_flag), gqueue, gqueue + qcap,
-                          queue_count + 1, d_counters);
-  }
-  // (v2: the call's start event rides on the scan's dispatch — the first launch — unless the scan's own start event claims that
-  // place, or nothing is launched for an empty batch: then it is recorded in front)
-  hipEvent_t scan_start = ev_start;
-  if ((v2 || v2_both) && P.ev_step_start) {
-    if (!ev_start && B.n_reads) scan_start = P.ev_step_start;
-    else { e = hipEventRecord(P.ev_step_start, s); if (e != hipSuccess) return e; }
-  }
-  if (v2_both) {
-    // `both` (decombine.py:1005-1010): the reverse frame for every read, then the forward frame for the reads it did not
-    // decombine (retry: the scan skips the reads whose record is OK); the failure counters of both attempts add up, as the
-    // reference's do.  After each frame the list kernel takes what the v2 kernels handed over (in that frame); the second one
-    // hands the counters over, with read_count set once.
-    const uint32_t lgrid = std::max<uint32_t>(1u, std::min<uint32_t>(qgrid, cus / 4));
-    CfgDev c1 = cfg, c2 = cfg;
-    c1.orientation = DCRX_ORIENT_REVERSE; c2.orientation = DCRX_ORIENT_FORWARD;
-    e = launch_v2_any(P, T, B, c1, rec, queue, gqueue, qcap, queue_count, acc, s, scan_start, ev_stop, 0u);
+  const uint32_t qcap = (uint32_t)(gqueue - queue);      // capacity of the rescue queue, of the general list behind it, and of the list of exception-list offsets behind that
+  // (which form this call's launches take, for whoever asks: dcrx_tune_state — a fallback to this form is then seen, not inferred from the clock)
+  if (P.tune) P.tune[route_frame(cfg.orientation)].last_form = R.last_form;
+  const uint64_t items = std::max<uint64_t>(R.all_general ? B.n_reads : 0, std::max<uint64_t>(B.n_exc, 1));
+  hipExtLaunchKernelGGL(prologue_kernel, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, s, E.first, nullptr, 0, B.exc_read, B.n_exc,
+                        R.all_general ? 1 : 0, 1, B.n_reads, const_cast<uint32_t *>(B.exc_flag), gqueue, gqueue + qcap, queue_count + 1, d_counters);
+  if (E.scan_start) { e = hipEventRecord(E.scan_start, s); if (e != hipSuccess) return e; }
+  if (!R.all_general) {
+    static bool seen[64];
+    const uint32_t lds_fast = ARITY == 16 ? P.lds16_bytes + DCRX_FAST16_LDS_EXTRA : P.lds_bytes + DCRX_FAST_LDS_EXTRA;
+    uint32_t grid = 0;
+    e = persistent_grid(seen, kfast, P, FBLOCK, lds_fast, P.grid, grid);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(klist, dim3(lgrid), dim3(DCRX_QBLOCK), lds_list, s, T, B, c1, rec, acc, queue, gqueue, queue_count, (unsigned long long *)nullptr, ~0ull, V2SinkCall{});
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = launch_v2_any(P, T, B, c2, rec, queue, gqueue, qcap, queue_count, acc, s, nullptr, nullptr, 1u);
-    if (e != hipSuccess) return e;
-    hipExtLaunchKernelGGL(klist, dim3(lgrid), dim3(DCRX_QBLOCK), lds_list, s, nullptr, P.ev_step_stop, 0, T, B, c2, rec, acc, queue, gqueue, queue_count, d_counters,
-                          (unsigned long long)B.n_reads, V2SinkCall{});
-    return hipGetLastError();
-  }
-  // (a tuple sink, when the call has one and the launch shape serves it: the kernels leave the tuples' items, the place
-  // kernel behind the list kernel puts the message together; else the caller compacts the records)
-  V2SinkLaunch K;
-  if (v2) {
-    e = launch_v2_any(P, T, B, cfg, rec, queue, gqueue, qcap, queue_count, acc, s, scan_start, ev_stop, 0u, P.sink.dev ? &K : nullptr);
-    if (e != hipSuccess) return e;
-  }
-  if (v2 && dcrx_debug_env("DCRX_DEBUG_HANDOVER")) {      // developer aid: how many reads the v2 kernels handed over
-    uint32_t qc[2] = {0, 0};
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(qc, queue_count, sizeof qc, hipMemcpyDeviceToHost);
-    fprintf(stderr, "dcrx: v2 handed over %u clean reads and %u reads with exception bytes\n", qc[0], qc[1]);
-  }
-  if (!v2 && ev_start) { e = hipEventRecord(ev_start, s); if (e != hipSuccess) return e; }
-  if (!v2 && grid) {
     hipLaunchKernelGGL(kfast, dim3(grid), dim3(FBLOCK), lds_fast, s, T, B, cfg, rec, d_counters, queue, queue_count);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  if (!v2 && ev_stop) { e = hipEventRecord(ev_stop, s); if (e != hipSuccess) return e; }
-  // What the fast kernel left: the general list (reads with exception bytes; every read for
-  // `both` / the forced slow reader) goes through the list kernel; the rescue queue through the
-  // rescue kernel when the pair table serves it, else through the list kernel as well.
-  // (behind the v2 kernels only the few reads they hand over are left: the list kernel, whose blocks
-  // leave at once when there is nothing to do)
-  const bool rescue16 = !v2 && ARITY == 16 && T.pair_rescue && !(cfg.flags & DCRX_F_LIST_RESCUE) &&
-                        P.lds16_bytes + DCRX_RESCUE_LDS_EXTRA <= 160u * 1024u;
-  if (!rescue16 || all_general) {
-    // (behind the v2 kernels a quarter of the grid: every block signs off with an atomic on one address, and that,
-    // not the handful of reads, is what the launch costs there)
-    const uint32_t lgrid = v2 ? std::max<uint32_t>(1u, std::min<uint32_t>(qgrid, cus / 4)) : qgrid;
-    const bool list_is_last = !(rescue16 && !all_general);
-    hipExtLaunchKernelGGL(klist, dim3(lgrid), dim3(DCRX_QBLOCK), lds_list, s, nullptr, list_is_last && !K.S.dev ? P.ev_step_stop : nullptr, 0, T, B, cfg, rec,
-                          acc, queue, gqueue, queue_count, v2 ? d_counters : (unsigned long long *)nullptr, ~0ull, K.S);
-    e = hipGetLastError();
+  if (E.scan_stop) { e = hipEventRecord(E.scan_stop, s); if (e != hipSuccess) return e; }
+  // What the fast kernel left: the general list (reads with exception bytes; every read where all are general) and the rescue queue
+  if (R.rescue_kernel) {
+    static bool seen[64];
+    e = lds_ceiling(seen, kresc);
     if (e != hipSuccess) return e;
-    if (K.S.dev) {
-      e = launch_v2_place(P, K, B.n_reads, s, P.ev_step_stop);
-      if (e != hipSuccess) return e;
-      if (P.sink.done) *P.sink.done = true;
-    }
+    hipExtLaunchKernelGGL(kresc, dim3(free_cus(P)), dim3(DCRX_RBLOCK), P.lds16_bytes + DCRX_RESCUE_LDS_EXTRA, s, nullptr, E.last, 0, T, B, cfg, rec, d_counters, queue, gqueue, queue_count, qcap);
+  } else {
+    ListLaunch L;
+    e = list_launch_as<TABLE_LDS, UNIFORM>(P, L);
+    if (e != hipSuccess) return e;
+    hipExtLaunchKernelGGL(klist, dim3(L.grid), dim3(DCRX_QBLOCK), L.lds, s, nullptr, E.last, 0, T, B, cfg, rec, d_counters, queue, gqueue, queue_count,
+                          (unsigned long long *)nullptr, ~0ull, V2SinkCall{});
   }
-  if (rescue16 && !all_general) {
-    auto kresc = decombine_rescue_kernel<UNIFORM, NW>;
-    static bool rattr_seen[64];
-    const KernelLds resc_lds = {reinterpret_cast<const void *>(kresc), 160 * 1024, false};
-    e = set_lds_ceilings(rattr_seen, &resc_lds, 1);
+  return hipGetLastError();
+}
+
+// The v2 kernels (dcrx_kernels_v2.hip), one pass per frame of the route: no prologue — the scan blocks mark the exception reads
+// of their own ranges —, every kernel tallies into the handle's accumulator (zero between calls), the list kernel behind each
+// pass takes the few reads it handed over, and the last one hands the counters to the caller and re-arms the accumulator.
+// `both` (decombine.py:1005-1010): the reverse frame for every read, then the forward frame for the reads it did not decombine
+// (the scan skips the reads whose record is OK); the failure counters of both attempts add up, as the reference's do, and
+// read_count is set once (0.69 ms per 10 M reads of config 2 against 28 ms through the list kernel).
+static hipError_t launch_v2_passes(const Route &R, const ListLaunch &L, const CallEvents &E, const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
+                                   dcrx_record_t *rec, uint32_t *queue, uint32_t *gqueue, uint32_t *queue_count, unsigned long long *d_counters, hipStream_t s) {
+  if (!P.v2_events || !P.v2_slow || !P.v2_acc || !P.v2_left) return hipErrorInvalidValue;      // the workspace was not sized (dcrx_api.cpp sizes it)
+  hipError_t e;
+  unsigned long long *acc = reinterpret_cast<unsigned long long *>(P.v2_acc);
+  const uint32_t qcap = (uint32_t)(gqueue - queue);
+  // (a quarter of the grid: every block signs off with an atomic on one address, and that, not the handful of reads, is what the launch costs here)
+  const uint32_t lgrid = std::max<uint32_t>(1u, std::min<uint32_t>(L.grid, free_cus(P) / 4));
+  const bool both = R.form == RouteForm::V2_BOTH;
+  if (E.in_front) { e = hipEventRecord(E.in_front, s); if (e != hipSuccess) return e; }
+  V2SinkLaunch K;      // (a tuple sink, when the call has one and the launch shape serves it: the place kernel behind the list kernel puts the message together; else the caller compacts the records)
+  for (int k = 0; k < R.n_passes; k++) {
+    const bool last = k + 1 == R.n_passes;
+    CfgDev c = cfg; c.orientation = R.pass[k].frame ? DCRX_ORIENT_REVERSE : DCRX_ORIENT_FORWARD;
+    e = launch_v2_any(P, T, B, c, rec, queue, gqueue, qcap, queue_count, acc, s, k ? nullptr : E.scan_start, k ? nullptr : E.scan_stop, R.pass[k], (uint32_t)k,
+                      !both && P.sink.dev ? &K : nullptr);
     if (e != hipSuccess) return e;
-    const uint32_t lds_resc = P.lds16_bytes + DCRX_RESCUE_LDS_EXTRA;
-    hipExtLaunchKernelGGL(kresc, dim3(cus), dim3(DCRX_RBLOCK), lds_resc, s, nullptr, P.ev_step_stop, 0, T, B, cfg, rec, d_counters, queue, gqueue,
-                          queue_count, qcap);
+    if (!both && dcrx_debug_env("DCRX_DEBUG_HANDOVER")) {      // developer aid: how many reads the v2 kernels handed over
+      uint32_t qc[2] = {0, 0};
+      (void)hipStreamSynchronize(s);
+      (void)hipMemcpy(qc, queue_count, sizeof qc, hipMemcpyDeviceToHost);
+      fprintf(stderr, "dcrx: v2 handed over %u clean reads and %u reads with exception bytes\n", qc[0], qc[1]);
+    }
+    hipExtLaunchKernelGGL(L.kernel, dim3(lgrid), dim3(DCRX_QBLOCK), L.lds, s, nullptr, last && !K.S.dev ? E.last : nullptr, 0, T, B, c, rec, acc, queue, gqueue,
+                          queue_count, last ? d_counters : (unsigned long long *)nullptr, both && last ? (unsigned long long)B.n_reads : ~0ull, K.S);
     e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (K.S.dev) {
+    e = launch_v2_place(P, K, B.n_reads, s, E.last);
+    if (e != hipSuccess) return e;
+    if (P.sink.done) *P.sink.done = true;
   }
   return e;
 }
@@ -806,7 +807,7 @@ __global__ __launch_bounds__(BLOCK) void decombine_long_kernel(DevTables T0, Bat
 }
 template <bool TABLE_LDS, int BLOCK>
 static hipError_t launch_long_as(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
-                                 unsigned long long *d_counters, hipStream_t s, const uint32_t grid, const uint32_t lds, const uint32_t slot_dwords) {
+                                 unsigned long long *d_counters, hipStream_t s, hipEvent_t ev_last, const uint32_t grid, const uint32_t lds, const uint32_t slot_dwords) {
   auto ku = decombine_long_kernel<true, TABLE_LDS, BLOCK>;
   auto kr = decombine_long_kernel<false, TABLE_LDS, BLOCK>;
   static bool attr_seen[64];
@@ -815,14 +816,14 @@ static hipError_t launch_long_as(const LaunchPlan &P, const DevTables &T, const 
     const hipError_t e = set_lds_ceilings(attr_seen, ceilings, 2);
     if (e != hipSuccess) return e;
   }
-  if (B.lens) hipExtLaunchKernelGGL(kr, dim3(grid), dim3(BLOCK), lds, s, nullptr, P.ev_step_stop, 0, T, B, cfg, rec, d_counters, slot_dwords);
-  else hipExtLaunchKernelGGL(ku, dim3(grid), dim3(BLOCK), lds, s, nullptr, P.ev_step_stop, 0, T, B, cfg, rec, d_counters, slot_dwords);
+  if (B.lens) hipExtLaunchKernelGGL(kr, dim3(grid), dim3(BLOCK), lds, s, nullptr, ev_last, 0, T, B, cfg, rec, d_counters, slot_dwords);
+  else hipExtLaunchKernelGGL(ku, dim3(grid), dim3(BLOCK), lds, s, nullptr, ev_last, 0, T, B, cfg, rec, d_counters, slot_dwords);
   return hipGetLastError();
 }
 static hipError_t launch_long(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
-                              unsigned long long *d_counters, hipStream_t s) {
-  hipExtLaunchKernelGGL(zero_counters_kernel, dim3(1), dim3(64), 0, s, P.ev_step_start, nullptr, 0, d_counters);
-  const uint32_t cus = P.n_cu > P.reserved_cus ? P.n_cu - P.reserved_cus : 1u;
+                              unsigned long long *d_counters, hipStream_t s, const CallEvents &E) {
+  hipExtLaunchKernelGGL(zero_counters_kernel, dim3(1), dim3(64), 0, s, E.first, nullptr, 0, d_counters);
+  const uint32_t cus = free_cus(P);
   // the tables in LDS where a block's image and its lanes' slots leave room for a block of 1 024 threads per compute unit (long dependent
   // chains: the waves of a unit hide one another's look-ups; 4 waves per SIMD is what the kernel's registers allow), else one of 512;
   // a batch of a few reads keeps the form without staging
@@ -840,44 +841,55 @@ static hipError_t launch_long(const LaunchPlan &P, const DevTables &T, const Bat
     if (long_block == 768) {
       if (const uint32_t sl = slot_for(768, 1)) {
         const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus, (B.n_reads + 767) / 768));
-        return launch_long_as<true, 768>(P, T, B, cfg, rec, d_counters, s, grid, lds_of(768, true, sl), sl);
+        return launch_long_as<true, 768>(P, T, B, cfg, rec, d_counters, s, E.last, grid, lds_of(768, true, sl), sl);
       }
     }
     if (const uint32_t sl = slot_for(1024, 1)) {
       const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus, (B.n_reads + 1023) / 1024));
-      return launch_long_as<true, 1024>(P, T, B, cfg, rec, d_counters, s, grid, lds_of(1024, true, sl), sl);
+      return launch_long_as<true, 1024>(P, T, B, cfg, rec, d_counters, s, E.last, grid, lds_of(1024, true, sl), sl);
     }
     const uint32_t sl = slot_for(512, 1);
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus, (B.n_reads + 511) / 512));
-    return launch_long_as<true, 512>(P, T, B, cfg, rec, d_counters, s, grid, lds_of(512, true, sl), sl);
+    return launch_long_as<true, 512>(P, T, B, cfg, rec, d_counters, s, E.last, grid, lds_of(512, true, sl), sl);
   }
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 8, (B.n_reads + 63) / 64));      // (a wave per block where the batch is small: long chains, few reads)
-  if (B.n_reads > (uint64_t)grid * 64) return launch_long_as<false, 256>(P, T, B, cfg, rec, d_counters, s, grid, lds_of(256, false, DCRX_LONG_SLOT_MAX), DCRX_LONG_SLOT_MAX);
-  return launch_long_as<false, 64>(P, T, B, cfg, rec, d_counters, s, grid, lds_of(64, false, DCRX_LONG_SLOT_MAX), DCRX_LONG_SLOT_MAX);
+  if (B.n_reads > (uint64_t)grid * 64) return launch_long_as<false, 256>(P, T, B, cfg, rec, d_counters, s, E.last, grid, lds_of(256, false, DCRX_LONG_SLOT_MAX), DCRX_LONG_SLOT_MAX);
+  return launch_long_as<false, 64>(P, T, B, cfg, rec, d_counters, s, E.last, grid, lds_of(64, false, DCRX_LONG_SLOT_MAX), DCRX_LONG_SLOT_MAX);
 }
 
-hipError_t launch_decombine(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
+// The route's facts as the handle's plan, its tables, the batch and the cfg give them (the v2 kernels' share: v2_route_facts)
+RouteFacts route_facts(const LaunchPlan &P, const DevTables &T, const uint32_t stride, const bool uniform, const uint64_t n_reads, const int orientation,
+                       const uint32_t flags) {
+  RouteFacts F;
+  F.stride = stride; F.uniform = uniform; F.n_reads = n_reads; F.orientation = orientation; F.flags = flags;
+  F.table_in_lds = P.table_in_lds; F.table16_in_lds = P.table16_in_lds; F.lds16_bytes = P.lds16_bytes; F.rescue_lds_extra = DCRX_RESCUE_LDS_EXTRA;
+  F.pair_rescue = T.pair_rescue != 0;
+  v2_route_facts(T, stride, F);
+  return F;
+}
+
+// The launches of route R (what route_of said of this call's route_facts)
+hipError_t launch_decombine(const Route &R, const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
                             dcrx_record_t *rec, uint32_t *queue, uint32_t *gqueue, uint32_t *queue_count,
                             uint64_t *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
-  hipError_t e;
   unsigned long long *ctr = reinterpret_cast<unsigned long long *>(d_counters);
-  if (B.stride > DCRX_FAST_MAX_STRIDE) return launch_long(P, T, B, cfg, rec, ctr, s);      // reads of 512 nt and more
+  const CallEvents E = call_events(R, P, B.n_reads == 0, ev_start, ev_stop);
+  if (R.form == RouteForm::LONG) return launch_long(P, T, B, cfg, rec, ctr, s, E);
   const bool uniform = B.lens == nullptr;
-  const bool nw10 = B.stride <= 40;  // 150-nt reads: ten words in registers instead of DCRX_NWMAX
-#define DCRX_LAUNCH(TL, UN, NW_, AR_) launch_all<TL, UN, NW_, AR_>(P, T, B, cfg, rec, queue, gqueue, queue_count, ctr, s, ev_start, ev_stop)
-  const bool pair_scan = P.table16_in_lds && !(cfg.flags & DCRX_F_ONE_BASE_SCAN);
-  if (P.table_in_lds && pair_scan) {
-    if (nw10) e = uniform ? DCRX_LAUNCH(true, true, 10, 16) : DCRX_LAUNCH(true, false, 10, 16);
-    else e = uniform ? DCRX_LAUNCH(true, true, DCRX_NWMAX, 16) : DCRX_LAUNCH(true, false, DCRX_NWMAX, 16);
-  } else if (P.table_in_lds) {
-    if (nw10) e = uniform ? DCRX_LAUNCH(true, true, 10, 4) : DCRX_LAUNCH(true, false, 10, 4);
-    else e = uniform ? DCRX_LAUNCH(true, true, DCRX_NWMAX, 4) : DCRX_LAUNCH(true, false, DCRX_NWMAX, 4);
-  } else {
-    if (nw10) e = uniform ? DCRX_LAUNCH(false, true, 10, 4) : DCRX_LAUNCH(false, false, 10, 4);
-    else e = uniform ? DCRX_LAUNCH(false, true, DCRX_NWMAX, 4) : DCRX_LAUNCH(false, false, DCRX_NWMAX, 4);
-  }
+  if (R.form == RouteForm::THREE_LAUNCH) {
+#define DCRX_LAUNCH(TL, NW_, AR_) \
+  (uniform ? launch_three<TL, true, NW_, AR_>(R, E, P, T, B, cfg, rec, queue, gqueue, queue_count, ctr, s) : launch_three<TL, false, NW_, AR_>(R, E, P, T, B, cfg, rec, queue, gqueue, queue_count, ctr, s))
+    if (R.pair_scan) return R.nw == 10 ? DCRX_LAUNCH(true, 10, 16) : DCRX_LAUNCH(true, DCRX_NWMAX, 16);
+    if (P.table_in_lds) return R.nw == 10 ? DCRX_LAUNCH(true, 10, 4) : DCRX_LAUNCH(true, DCRX_NWMAX, 4);
+    return R.nw == 10 ? DCRX_LAUNCH(false, 10, 4) : DCRX_LAUNCH(false, DCRX_NWMAX, 4);
 #undef DCRX_LAUNCH
-  return e;
+  }
+  // the v2 kernels: their passes need the list kernel only, one of its four instantiations
+  ListLaunch L;
+  const hipError_t e = P.table_in_lds ? (uniform ? list_launch_as<true, true>(P, L) : list_launch_as<true, false>(P, L))
+                                      : (uniform ? list_launch_as<false, true>(P, L) : list_launch_as<false, false>(P, L));
+  if (e != hipSuccess) return e;
+  return launch_v2_passes(R, L, E, P, T, B, cfg, rec, queue, gqueue, queue_count, ctr, s);
 }
 
 hipError_t launch_compact(const dcrx_record_t *rec, uint64_t n, uint64_t first_index, dcrx_record_t *hits,

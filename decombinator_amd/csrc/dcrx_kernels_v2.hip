@@ -1733,24 +1733,6 @@ __global__ __launch_bounds__(V2_PLACE_BLOCK) void v2_place_kernel(const V2SinkCa
 // LDS the scan kernel needs for frame o: the pair table and the block's counters
 static uint32_t v2_scan_lds_bytes(const DevTables &T, int o) { return T.v2[o].trans_bytes + DCRX_N_COUNTERS * 4 + V2_WK_WORDS * 4; }
 
-// The v2 kernels serve one frame; the A/B switches of the three-launch form, the forced slow
-// reader and orientation `both` keep that form.
-// The v2 kernels serve one frame per pass: `reverse` and `forward` are one pass, `both` (decombine.py:1005-1010) the reverse
-// frame and then the forward frame for the reads it did not decombine (both frames' tables must fit).
-bool v2_applies(const LaunchPlan &P, const DevTables &T, const CfgDev &cfg, const uint32_t stride) {
-  if (!T.v2_ok || !P.v2_events || !P.v2_slow || !P.v2_acc || !P.v2_left) return false;      // (the tail list: only where a launch needs it, launch_v2)
-  if (cfg.flags & (DCRX_F_V1_KERNELS | DCRX_F_FORCE_SLOW_READER | DCRX_F_ONE_BASE_SCAN | DCRX_F_LIST_RESCUE | DCRX_F_PROFILE_LIST_SCAN_ONLY)) return false;
-  // (the lean kernels add a strip of LDS per lane: priced at the register shape the batch's stride takes — at the long reads'
-  // shape whatever the batch, the extended alpha set's larger keyword tables sent its 150-nt batches to the three-launch form)
-  auto fits = [&](int o) {
-    const uint32_t fin = stride <= 40 ? v2_finish_block_lds<10>(T, o, DCRX_V2_FBLOCK)
-                                      : (stride <= 4 * DCRX_NWMAX ? v2_finish_block_lds<DCRX_NWMAX>(T, o, DCRX_V2_FBLOCK) : v2_finish_block_lds<DCRX_V2_NWLONG>(T, o, DCRX_V2_FBLOCK));
-    return v2_scan_lds_bytes(T, o) <= 160u * 1024u && fin <= 64u * 1024u;
-  };
-  if (cfg.orientation == DCRX_ORIENT_BOTH) return fits(0) && fits(1) && !(cfg.flags & DCRX_F_PROFILE_MASK);
-  return fits(cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1);
-}
-
 // ---- the launcher's A/B and developer knobs (dcrx_debug_flags.h: honoured only under DCRX_DEBUG_FLAGS=1), read once per process
 struct V2Knobs {
   // (measured, profiles/r04: config 2's 57 KB table 0.413 ms per step fused against 0.429 with the tail as a role; the extended
@@ -1778,19 +1760,24 @@ struct V2Knobs {
 };
 static const V2Knobs &v2_knobs() { static const V2Knobs K; return K; }
 
-// ---- what a call will launch ----
-// The fused form (the tail inside the scan kernel, through a ring in LDS: scan2_kernel, FUSE) for the 150-nt shape when the
-// frame's pair table leaves room for the side tables, the buckets and a ring of at least eight batches; the A/B forms and the
-// profiling switches keep the tail a launch of its own.  Batches of the tail ring, 0: the tail as a role (or a launch) of its own.
-static uint32_t v2_tail_ring(const bool can_fuse, const DevTables &T, const int o, const uint32_t flags) {
+// ---- what a call will launch: the v2 kernels' share of the route's facts (dcrx_route.h) ----
+// A frame's finishing block is priced at the register shape the batch's stride takes (at the long reads' shape whatever the
+// batch, the extended alpha set's larger keyword tables sent its 150-nt batches to the three-launch form).
+void v2_route_facts(const DevTables &T, const uint32_t stride, RouteFacts &F) {
   const V2Knobs &K = v2_knobs();
-  if (!can_fuse || T.v2[o].trans_bytes > K.fuse_limit ||
-      (flags & (DCRX_F_V2_NO_FUSE | DCRX_F_V2_SIDE_STREAMS | DCRX_F_V2_LEAN_SERIAL | DCRX_F_V2_NO_LEAN_RESCUE | (DCRX_F_PROFILE_MASK & ~DCRX_F_PROFILE_TAIL_STREAM_ONLY))))
-    return 0u;
-  const uint32_t fixed = v2_scan_lds_bytes(T, o) + (T.lds_image_bytes - T.dfa_bytes) + T.v2[o].bk_bytes;
-  for (uint32_t nb = K.ring_max; nb >= K.ring_min; nb >>= 1)
-    if (fixed + nb * 64u * V2_RING_STRIDE * 4u <= 160u * 1024u) return nb;
-  return 0u;
+  F.v2_ok = T.v2_ok != 0;
+  for (int o = 0; o < 2; o++) {
+    RouteFacts::Frame &f = F.frame[o];
+    f.trans_bytes = T.v2[o].trans_bytes;
+    f.scan_lds = v2_scan_lds_bytes(T, o);
+    f.finish_lds = stride <= 40 ? v2_finish_block_lds<10>(T, o, DCRX_V2_FBLOCK)
+                                : (stride <= 4 * DCRX_NWMAX ? v2_finish_block_lds<DCRX_NWMAX>(T, o, DCRX_V2_FBLOCK) : v2_finish_block_lds<DCRX_V2_NWLONG>(T, o, DCRX_V2_FBLOCK));
+    f.bucket_bytes = T.v2[o].bk_bytes;
+    f.narrow = T.v2[o].narrow != 0;
+  }
+  F.side_bytes = T.lds_image_bytes - T.dfa_bytes;
+  F.ring_batch_bytes = 64u * V2_RING_STRIDE * 4u;
+  F.fuse_limit = K.fuse_limit; F.ring_max = K.ring_max; F.ring_min = K.ring_min;
 }
 
 // One scan block per compute unit, each with a contiguous range of the reads — a multiple of 512: whole items of its waves and
@@ -1806,7 +1793,7 @@ struct V2Regions {
 };
 template <int NW, int RPL> static V2Regions v2_regions(const LaunchPlan &P, const BatchDev &B, const uint32_t ring_batches) {
   V2Regions R;
-  const uint32_t cus = P.n_cu > P.reserved_cus ? P.n_cu - P.reserved_cus : 1u;
+  const uint32_t cus = free_cus(P);
   const uint64_t wt = 64ull * RPL;
   const uint64_t n_items = (B.n_reads + wt - 1) / wt;
   R.grid = R.n_regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cus, (n_items + 15) / 16));
@@ -2153,11 +2140,12 @@ static void v2_stamps_dump(const uint32_t n_regions, const bool fused, hipStream
 template <bool UNIFORM, int NW, int RPL, bool NARROW, bool PREFETCH = true>
 static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
                             uint32_t *queue, uint32_t *gqueue, uint32_t qcap, uint32_t *queue_count,
-                            unsigned long long *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t retry, V2SinkLaunch *sink) {
+                            unsigned long long *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t retry, V2SinkLaunch *sink,
+                            const uint32_t ring_batches) {
   using Kernels = V2Kernels<UNIFORM, NW, RPL, NARROW, PREFETCH>;
   const V2Knobs &knobs = v2_knobs();
-  const int o = cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1;
-  const uint32_t ring_batches = v2_tail_ring(Kernels::CAN_FUSE, T, o, cfg.flags);
+  const int o = route_frame(cfg.orientation);
+  if (ring_batches && !Kernels::CAN_FUSE) return hipErrorInvalidValue;      // (the route and the kernels agree on the shapes that fuse: dcrx_route.h)
   const V2Regions R = v2_regions<NW, RPL>(P, B, ring_batches);
   const V2Form F = v2_form<UNIFORM, NW, RPL, PREFETCH>(P, T, B, cfg, o, ring_batches, R, retry, sink && P.sink.dev, ev_start || ev_stop || P.ev_step_start || P.ev_step_stop);
   if (P.tune) P.tune[o].last_form = F.last_form;
@@ -2168,10 +2156,8 @@ static hipError_t launch_v2(const LaunchPlan &P, const DevTables &T, const Batch
   v2_stamps_arm();
 #endif
   if (B.n_reads == 0) return hipSuccess;       // (the tallies stay zero; the list kernel hands them over)
-  // (a launch that keeps the tail a role of the finishing launch needs the tail list, which a handle that has fused so far does
-  // not hold: hipErrorNotReady before anything is launched — dcrx_api.cpp allocates it and comes back)
-  if (!ring_batches && (!P.v2_tail || R.tcap < 64)) return hipErrorNotReady;
-  if (R.ecap < 128 || R.scap < 128) return hipErrorInvalidValue;      // the workspace was not sized for this batch (dcrx_api.cpp sizes it)
+  // the workspace was not sized for this batch (dcrx_api.cpp sizes it, the tail list where the call's route keeps the tail out of the scan)
+  if ((!ring_batches && (!P.v2_tail || R.tcap < 64)) || R.ecap < 128 || R.scap < 128) return hipErrorInvalidValue;
   V2Lists Q;
   Q.tail = P.v2_tail; Q.ev = P.v2_events; Q.sx = P.v2_slow; Q.left = P.v2_left; Q.counts = P.v2_counts;
   Q.tcap = R.tcap; Q.ecap = R.ecap; Q.scap = R.scap;
@@ -2240,16 +2226,14 @@ uint64_t v2_sink_items(uint64_t max_reads, uint32_t n_cu) { return 4 * (max_read
 
 hipError_t launch_v2_any(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
                          uint32_t *queue, uint32_t *gqueue, uint32_t qcap, uint32_t *queue_count, unsigned long long *d_counters,
-                         hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t retry, V2SinkLaunch *sink) {
-  const int o = cfg.orientation == DCRX_ORIENT_FORWARD ? 0 : 1;
-  const bool uniform = B.lens == nullptr, nw10 = B.stride <= 40, narrow = T.v2[o].narrow != 0;
-  int shape = (int)((cfg.flags >> 8) & 3u);
-  if (shape == 0) shape = nw10 ? 2 : 3;      // two reads per lane (two independent chains per wave) where the registers allow: measured faster than one
-#define DCRX_V2A(UN, NW_, RP, NA) launch_v2<UN, NW_, RP, NA>(P, T, B, cfg, rec, queue, gqueue, qcap, queue_count, d_counters, s, ev_start, ev_stop, retry, sink)
-#define DCRX_V2X(UN, NW_, RP, NA, PF) launch_v2<UN, NW_, RP, NA, PF>(P, T, B, cfg, rec, queue, gqueue, qcap, queue_count, d_counters, s, ev_start, ev_stop, retry, sink)
-#define DCRX_V2(UN, NW_, NA) (shape == 3 ? DCRX_V2A(UN, NW_, 1, NA) : (shape == 1 && UN && NW_ == 10 && NA) ? DCRX_V2X(true, 10, 4, true, false) : DCRX_V2A(UN, NW_, 2, NA))
+                         hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, const Route::Pass &pass, uint32_t retry, V2SinkLaunch *sink) {
+  const bool uniform = B.lens == nullptr, nw10 = B.stride <= 40, narrow = T.v2[pass.frame].narrow != 0;
+  const int rpl = pass.reads_per_lane;      // (two independent chains per wave where the registers allow: measured faster than one)
+#define DCRX_V2A(UN, NW_, RP, NA) launch_v2<UN, NW_, RP, NA>(P, T, B, cfg, rec, queue, gqueue, qcap, queue_count, d_counters, s, ev_start, ev_stop, retry, sink, pass.ring_batches)
+#define DCRX_V2X(UN, NW_, RP, NA, PF) launch_v2<UN, NW_, RP, NA, PF>(P, T, B, cfg, rec, queue, gqueue, qcap, queue_count, d_counters, s, ev_start, ev_stop, retry, sink, pass.ring_batches)
+#define DCRX_V2(UN, NW_, NA) (rpl == 1 ? DCRX_V2A(UN, NW_, 1, NA) : (rpl == 4 && UN && NW_ == 10 && NA) ? DCRX_V2X(true, 10, 4, true, false) : DCRX_V2A(UN, NW_, 2, NA))
 #ifdef DCRX_FAST_BUILD      // (experiment builds, tools/build_variant.sh: the benchmark's launch shape only)
-  if (nw10 && uniform && shape == 2) return narrow ? DCRX_V2A(true, 10, 2, true) : DCRX_V2A(true, 10, 2, false);
+  if (nw10 && uniform && rpl == 2) return narrow ? DCRX_V2A(true, 10, 2, true) : DCRX_V2A(true, 10, 2, false);
   return hipErrorNotSupported;
 #else
   if (nw10) {

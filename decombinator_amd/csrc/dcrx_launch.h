@@ -10,6 +10,7 @@
 #include "dcrx_hip.h"
 
 #include "dcrx_launch_types.h"
+#include "dcrx_route.h"
 #include "dcrx_tune.h"
 
 namespace dcrx {
@@ -96,18 +97,24 @@ struct LaunchPlan {
   bool tune_may_wait = false;  // dcrx_set_tune_wait: the fourth call of a big-batch size class may wait for the third's finishing launch, once
 };
 
-hipError_t launch_decombine(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
+// compute units the persistent grids may fill (reserved_cus: left to other streams — an RCCL gather running beside the scan)
+inline uint32_t free_cus(const LaunchPlan &P) { return P.n_cu > P.reserved_cus ? P.n_cu - P.reserved_cus : 1u; }
+
+// The facts a call's route follows from (dcrx_route.h), and the launches of that route: what route_of() said of these facts
+// is what launch_decombine runs — dcrx_api.cpp asks first and sizes the workspace by the answer.
+RouteFacts route_facts(const LaunchPlan &P, const DevTables &T, uint32_t stride, bool uniform, uint64_t n_reads, int orientation, uint32_t flags);
+hipError_t launch_decombine(const Route &R, const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg,
                             dcrx_record_t *rec, uint32_t *queue, uint32_t *gqueue, uint32_t *queue_count,
                             uint64_t *d_counters, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop);
 // dcrx_kernels_v2.hip
 void v2_list_rows(uint64_t max_reads, uint32_t stride, uint32_t n_cu, uint64_t *tail_rows, uint64_t *event_rows);
 uint64_t v2_slow_rows(uint64_t max_reads, uint32_t stride, uint32_t n_cu);
-bool v2_applies(const LaunchPlan &P, const DevTables &T, const CfgDev &cfg, uint32_t stride);
+void v2_route_facts(const DevTables &T, uint32_t stride, RouteFacts &F);      // the v2 kernels' share of route_facts
 // what a v2 launch that serves the call's tuple sink leaves for the list kernel and the place kernel behind it
 struct V2SinkLaunch { V2SinkCall S{}; uint32_t n_regions = 0, tcap = 0, ecap = 0, ccap = 0, fused = 0; const uint32_t *counts = nullptr; };
 hipError_t launch_v2_any(const LaunchPlan &P, const DevTables &T, const BatchDev &B, const CfgDev &cfg, dcrx_record_t *rec,
                          uint32_t *queue, uint32_t *gqueue, uint32_t qcap, uint32_t *queue_count, unsigned long long *d_counters,
-                         hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t retry = 0, V2SinkLaunch *sink = nullptr);
+                         hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, const Route::Pass &pass, uint32_t retry = 0, V2SinkLaunch *sink = nullptr);
 hipError_t launch_v2_place(const LaunchPlan &P, const V2SinkLaunch &K, uint64_t n_reads, hipStream_t s, hipEvent_t ev_stop);
 uint64_t v2_sink_items(uint64_t max_reads, uint32_t n_cu);      // items a handle's sink needs for batches of up to max_reads reads
 hipError_t launch_compact(const dcrx_record_t *rec, uint64_t n, uint64_t first_index, dcrx_record_t *hits,

@@ -225,7 +225,7 @@ extern "C" int emul_decombine(const dcrx_tagset_t *ts, const dcrx_cfg_t *cfg, co
     }
     const bool pair_scan = T.dfa16_bytes != 0 && !(C.flags & DCRX_F_ONE_BASE_SCAN);
     const bool pair_rescue = pair_scan && T.pair_rescue && !(C.flags & DCRX_F_LIST_RESCUE);
-    // the launch's choice of kernels (dcrx_kernels.hip, v2_applies); reads beyond the three-launch form's 320 nt stay on the
+    // the launch's choice of kernels (dcrx_route.h, route_of); reads beyond the three-launch form's 320 nt stay on the
     // v2 functions (32 words per read) where those apply, and all take the general list form otherwise
     const bool v2_able = T.v2_ok && !(C.flags & (DCRX_F_V1_KERNELS | DCRX_F_ONE_BASE_SCAN | DCRX_F_LIST_RESCUE | DCRX_F_PROFILE_LIST_SCAN_ONLY |
                                                   DCRX_F_PROFILE_RESCUE_HITS_ONLY | DCRX_F_FORCE_SLOW_READER));

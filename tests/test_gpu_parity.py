@@ -1045,10 +1045,10 @@ def launch_forms_in_sequence(check=None):
 
 
 def test_launch_forms_in_sequence_on_one_handle():
-    """A handle that has fused so far holds no tail list: the second call goes through hipErrorNotReady, the allocation and the
-    relaunch in dcrx_decombine_device; then every A/B form, the three-launch form, the shipped form again and the other
-    orientations.  Records and counters against the oracle after each call, and the launch form the handle reports against
-    what the build before launch_v2 was split into steps reported for the same sequence (tests/golden)."""
+    """A handle that has fused so far holds no tail list: the second call's route (dcrx_route.h) says it needs one, and
+    dcrx_decombine_device allocates it before that call's first launch; then every A/B form, the three-launch form, the shipped
+    form again and the other orientations.  Records and counters against the oracle after each call, and the launch form the
+    handle reports against what the build before launch_v2 was split into steps reported for the same sequence (tests/golden)."""
     import json
 
     def check(rec, cnt, reads, want, what):
@@ -1058,3 +1058,99 @@ def test_launch_forms_in_sequence_on_one_handle():
     golden = json.load(open(FORM_GOLDEN))
     assert golden["n_reads"] == 5000 and len(golden["steps"]) == len(FORM_SEQUENCE)
     assert seen == golden["steps"]
+
+
+# ---- the route of a call (dcrx_route.h): the same launches as the build before the route was decided in one place ----
+
+ROUTE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_routes.json")
+ROUTE_N = 5000
+_ROUTE_FLAGS = [0, nat.F_V2_NO_FUSE, nat.F_V2_NO_LEAN_RESCUE, nat.F_V2_LEAN_SERIAL, nat.F_V2_SIDE_STREAMS, nat.F_V2_SHAPE(3), nat.F_V1_KERNELS,
+                nat.F_ONE_BASE_SCAN, nat.F_FORCE_SLOW_READER, nat.F_LIST_RESCUE]
+# (tag set, read shape, orientation, flags)
+ROUTE_CALLS = [("config2", "150", "reverse", f) for f in _ROUTE_FLAGS] + \
+              [(ts, "150", o, 0) for ts in ("config2", "config3-alpha", "config3-beta", "config5-gamma") for o in ("reverse", "forward", "both")] + \
+              [("config2", shape, o, 0) for shape in ("150-ragged", "300", "500", "600") for o in ("reverse", "both")]
+_route = {}
+
+
+def _route_tagset(name):
+    return {"config2": lambda: synth.config_tagset(2), "config3-alpha": lambda: synth.config3_tagsets()[0],
+            "config3-beta": lambda: synth.config3_tagsets()[1], "config5-gamma": lambda: synth.config5_tagsets()[0]}[name]()
+
+
+def _route_batch(name, shape):
+    """(tag set, oracle tables, packed batch, reads, orientation -> oracle records and counters), made once per tag set and
+    shape: ROUTE_N synthetic 150-nt reads as they are (uniform lengths), cut to 100 .. 150 nt (per-read lengths), or inside
+    random flanks of 300, 500 (strides 80, 128) and 600 nt (the long form), three in ten of those on the other strand."""
+    if (name, shape) not in _route:
+        if name not in _route:
+            _route[name] = (_route_tagset(name),) + _tables(_route_tagset(name))
+        ts, t, ot = _route[name]
+        reads = nat.unpack_reads(nat.synth_reads_host(t, nat.synth_cfg(seed=61, sub_rate=0.01, n_rate=0.002), 0, ROUTE_N))
+        rng = np.random.default_rng(62)
+        if shape == "150-ragged":
+            reads = [r[:int(c)] if i % 2 else r[len(r) - int(c):] for i, (r, c) in enumerate(zip(reads, rng.integers(100, 151, size=ROUTE_N)))]
+        elif shape != "150":
+            n = int(shape)
+            out = []
+            for r in reads:
+                left = int(rng.integers(0, n - len(r) + 1))
+                fl = "".join("ACGT"[k] for k in rng.integers(0, 4, size=n - len(r)))
+                row = fl[:left] + r + fl[left:]
+                out.append(orc.revcomp(row) if rng.random() < 0.3 else row)
+            reads = out
+        hb = nat.pack_reads(reads, stride=40) if shape.startswith("150") else nat.pack_reads(reads)
+        assert hb.stride == {"150": 40, "150-ragged": 40, "300": 80, "500": 128, "600": 152}[shape] and (hb.lens is None) == (shape != "150-ragged")
+        made = {}
+
+        def want(orientation):
+            if orientation not in made:
+                made[orientation] = pu.oracle_records(ot, reads, orientation, False, 130)
+            return made[orientation]
+        _route[(name, shape)] = (ts, hb, reads, want)
+    return _route[(name, shape)]
+
+
+def launch_routes(check=None):
+    """ROUTE_CALLS, each on a fresh handle: what dcrx_tune_state reports as the launch form of either frame after the call."""
+    seen = []
+    for name, shape, orientation, flags in ROUTE_CALLS:
+        ts, hb, reads, want = _route_batch(name, shape)
+        t, _ = _tables(ts)
+        rec, cnt = nat.decombine(t, hb, orientation=orientation, flags=flags)
+        if check:
+            check(rec, cnt, reads, want(orientation), f"{name}, {shape} nt, {orientation}, flags {flags}")
+        seen.append({"tagset": name, "reads": shape, "orientation": orientation, "flags": flags,
+                     "launch_form": {o: t.tune_state(ROUTE_N, o)["launch_form"] for o in ("reverse", "forward")}})
+        t.close()
+    return seen
+
+
+def test_launch_routes_equal_the_parents():
+    """Every kind of call — the flags that choose a form, the tag sets whose pair tables fuse and do not (the extended beta set
+    needs the tail list on its first call), the three orientations, the four read shapes — on a fresh handle: records and
+    counters against the oracle, and the launch forms the handle reports against what the build before the call's route was
+    decided in one place (dcrx_route.h) reported for the same calls (tests/golden/launch_routes.json)."""
+    import json
+
+    def check(rec, cnt, reads, want, what):
+        pu.assert_records_equal(rec, want[0], reads, what)
+        pu.assert_counters_equal(cnt, want[1], what)
+    seen = launch_routes(check)
+    golden = json.load(open(ROUTE_GOLDEN))
+    assert golden["n_reads"] == ROUTE_N and len(golden["calls"]) == len(ROUTE_CALLS) == 30
+    assert seen == golden["calls"]
+
+
+def test_first_call_both_with_one_frame_fused_and_one_not():
+    """Config 2's pair tables are 56 608 bytes (forward) and 53 152 bytes (reverse): under DCRX_DEBUG_FUSE_LIMIT_KB=54 the reverse
+    frame takes the tail inside the scan and the forward frame keeps it a role, which needs the handle's tail list.  A fresh
+    handle's first call is orientation `both` through the device entry; then the same call again; then, on another fresh
+    handle, reverse with no flags followed by reverse with DCRX_F_V2_NO_FUSE.  The worker (the knobs are read once per process)
+    checks records and counters against the oracle after every call and the launch forms after each."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, DCRX_DEBUG_FLAGS="1", DCRX_DEBUG_FUSE_LIMIT_KB="54", PYTHONPATH=root)
+    p = subprocess.run([sys.executable, os.path.join(root, "tests", "route_worker.py")], env=env, cwd=root, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "ROUTE_OK" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
