@@ -402,6 +402,18 @@ class ClonotypeStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CLONOTYPE_STATS]
 
 
+CDR3_NETWORK_STATS = ("nodes_in", "out_of_reach", "edges", "clusters_out", "singletons", "largest_cluster", "largest_degree")
+CDR3_CLUSTER_COLUMNS = ["clonotype", "v_call", "j_call", "junction_aa", "duplicate_count", "cluster", "cluster_size",
+                        "cluster_duplicate_count", "degree"]
+CDR3_EDGE_COLUMNS = ["a", "b", "distance"]
+CDR3NET_MAX_LEN = 32           # DCRX_CDR3NET_MAX_LEN
+CDR3NET_MAX_NODES = 1 << 30    # dcrx_cdr3_network / dcrx_cdr3_neighbours_device: DCRX_E_UNSUPPORTED from here on
+
+
+class Cdr3NetworkStatsC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in CDR3_NETWORK_STATS]
+
+
 # dcrx_clono_row_t: what dcrx_cdr3_device leaves of an entry (flags: productive, in_frame, stop, conserved_c, conserved_f from bit 0)
 CLONO_ROW_DTYPE = np.dtype([("hash", "<u8"), ("arena_off", "<u8"), ("start_cdr3", "<i4"), ("end_cdr3", "<i4"), ("seq_len", "<u4"),
                             ("status", "u1"), ("flags", "u1"), ("pad", "<u2")])
@@ -429,6 +441,8 @@ EXPORTS = [
     "dcrx_merge_work_bytes", "dcrx_merge_parents_device", "dcrx_merge_dcrs", "dcrx_merge_gather",
     "dcrx_clono_genes_create", "dcrx_clono_genes_destroy", "dcrx_clono_set_hash_bits", "dcrx_clono_work_bytes", "dcrx_cdr3_device",
     "dcrx_clonotypes", "dcrx_clonotypes_text", "dcrx_format_clonotypes",
+    "dcrx_cdr3net_work_bytes", "dcrx_cdr3_neighbours_device", "dcrx_cdr3_network", "dcrx_format_cdr3_clusters",
+    "dcrx_format_cdr3_edges",
 ]
 
 _lib = None
@@ -561,6 +575,11 @@ def lib():
         "dcrx_clonotypes": (C.c_int64, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(ClonotypeStatsC)]),
         "dcrx_clonotypes_text": (C.c_int64, [vp, vp, u64]),
         "dcrx_format_clonotypes": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u64]),
+        "dcrx_cdr3net_work_bytes": (u64, [u64, u64]),
+        "dcrx_cdr3_neighbours_device": (i32, [u64, vp, vp, vp, u64, u32, vp, vp, vp, u64, vp, vp, u64, vp]),
+        "dcrx_cdr3_network": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, C.POINTER(Cdr3NetworkStatsC)]),
+        "dcrx_format_cdr3_clusters": (C.c_int64, [u64, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64]),
+        "dcrx_format_cdr3_edges": (C.c_int64, [u64, vp, vp, vp, vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1278,6 +1297,100 @@ def format_clonotypes(genes: ClonoGenes, table: dict, counted: dict) -> bytes:
     need = check(int(lib().dcrx_format_clonotypes(*args, None, 0)))
     out = _uninitialised_bytes(max(1, need))
     check(int(lib().dcrx_format_clonotypes(*args, _bytes_address(out), need)))
+    return bytes(out[:need])
+
+
+# ---- the CDR3 network (--cdr3-network): include/dcrx.h "the CDR3 network" ----
+
+def cdr3net_work_bytes(m: int, text_bytes: int) -> int:
+    return int(lib().dcrx_cdr3net_work_bytes(int(m), int(text_bytes)))
+
+
+def cdr3_neighbours_device(m: int, d_class, d_off, d_text, text_bytes: int, distance: int, d_degree, d_adj_off, d_adj, adj_cap: int,
+                           d_adj_need, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_neighbours_device: degree and adjacency of every node of a table in HBM (DeviceBuffers), asynchronous on
+    `stream`."""
+    check(lib().dcrx_cdr3_neighbours_device(int(m), d_class.ptr, d_off.ptr, d_text.ptr if d_text is not None else None,
+                                            int(text_bytes), int(distance), d_degree.ptr, d_adj_off.ptr,
+                                            d_adj.ptr if d_adj is not None else None, int(adj_cap),
+                                            d_adj_need.ptr if d_adj_need is not None else None, d_work.ptr, int(work_bytes), stream))
+
+
+def _node_arrays(aa_off, aa_text):
+    off = np.ascontiguousarray(aa_off, dtype=np.uint64)
+    text = np.frombuffer(aa_text, np.uint8) if len(aa_text) else np.zeros(1, np.uint8)
+    return off, text
+
+
+def cdr3_network(classes, aa_off, aa_text: bytes, weights, distance: int, want_edges: bool = False):
+    """dcrx_cdr3_network on the current device: m nodes (class, string = aa_text[aa_off[i]:aa_off[i + 1]], weight) linked where
+    class and length agree and at most `distance` (1 or 2) bytes differ — (result, statistics dict over CDR3_NETWORK_STATS).
+    result: degree and cluster_of per node; cluster_head, cluster_size and cluster_weight per cluster row (rows by head
+    ascending); with want_edges the CSR adjacency adj_off (m + 1) and adj (a second call, once the first has sized it)."""
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    off, text = _node_arrays(aa_off, aa_text)
+    m = len(cls)
+    if len(off) != m + 1 or len(w) != m:
+        raise ValueError("cdr3_network: one class and one weight per node, m + 1 offsets")
+    if m >= CDR3NET_MAX_NODES:
+        raise ValueError(f"the CDR3 network takes fewer than {CDR3NET_MAX_NODES:,} nodes, not {m:,}")
+    deg, of, head, nn = (np.zeros(max(m, 1), np.uint32) for _ in range(4))
+    cw = np.zeros(max(m, 1), np.uint64)
+    adj_off = np.zeros(m + 1, np.uint64) if want_edges else None
+    need = C.c_uint64(0)
+    st = Cdr3NetworkStatsC()
+
+    def call(adj, cap):
+        return check(int(lib().dcrx_cdr3_network(m, cls.ctypes.data, off.ctypes.data, text.ctypes.data, w.ctypes.data, int(distance),
+                                                 deg.ctypes.data, of.ctypes.data, head.ctypes.data, nn.ctypes.data, cw.ctypes.data,
+                                                 adj_off.ctypes.data if want_edges else None,
+                                                 adj.ctypes.data if adj is not None else None, cap, C.byref(need), C.byref(st))))
+    c = call(None, 0)
+    result = {"degree": deg[:m].copy(), "cluster_of": of[:m].copy(), "cluster_head": head[:c].copy(), "cluster_size": nn[:c].copy(),
+              "cluster_weight": cw[:c].copy()}
+    if want_edges:
+        adj = np.zeros(max(1, need.value), np.uint32)
+        if need.value:
+            call(adj, need.value)
+        result["adj_off"], result["adj"] = adj_off, adj[:need.value]
+    return result, {k: int(getattr(st, k)) for k in CDR3_NETWORK_STATS}
+
+
+def _calls_blob(strings):
+    bs = [x.encode("latin-1") for x in strings]
+    o = np.zeros(len(bs) + 1, dtype=np.uint32)
+    o[1:] = np.cumsum([len(b) for b in bs])
+    return np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy(), o
+
+
+def format_cdr3_clusters(v_idx, j_idx, v_calls, j_calls, aa_off, aa_text: bytes, weights, result: dict) -> bytes:
+    """dcrx_format_cdr3_clusters: the `.cdr3_clusters.tsv` text — per node its rank, the calls v_calls[v_idx[i]] and
+    j_calls[j_idx[i]], its string and weight, and its cluster's row, size and weight out of a cdr3_network result."""
+    vi, ji = (np.ascontiguousarray(a, dtype=np.uint32) for a in (v_idx, j_idx))
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    off, text = _node_arrays(aa_off, aa_text)
+    (vc, vo), (jc, jo) = _calls_blob(v_calls), _calls_blob(j_calls)
+    cols = [np.ascontiguousarray(result[k], dtype=t) for k, t in (("cluster_of", np.uint32), ("cluster_size", np.uint32),
+                                                                 ("cluster_weight", np.uint64), ("degree", np.uint32))]
+    args = [len(vi), vi.ctypes.data, ji.ctypes.data, len(v_calls), vc.ctypes.data, vo.ctypes.data, len(j_calls), jc.ctypes.data,
+            jo.ctypes.data, off.ctypes.data, text.ctypes.data, w.ctypes.data, cols[0].ctypes.data, len(cols[1]), cols[1].ctypes.data,
+            cols[2].ctypes.data, cols[3].ctypes.data]
+    need = check(int(lib().dcrx_format_cdr3_clusters(*args, None, 0)))
+    out = _uninitialised_bytes(max(1, need))
+    check(int(lib().dcrx_format_cdr3_clusters(*args, _bytes_address(out), need)))
+    return bytes(out[:need])
+
+
+def format_cdr3_edges(aa_off, aa_text: bytes, result: dict) -> bytes:
+    """dcrx_format_cdr3_edges: the `.cdr3_edges.tsv` text of a cdr3_network result with edges."""
+    off, text = _node_arrays(aa_off, aa_text)
+    adj_off = np.ascontiguousarray(result["adj_off"], dtype=np.uint64)
+    adj = np.ascontiguousarray(result["adj"], dtype=np.uint32) if len(result["adj"]) else np.zeros(1, np.uint32)
+    args = [len(off) - 1, adj_off.ctypes.data, adj.ctypes.data, off.ctypes.data, text.ctypes.data]
+    need = check(int(lib().dcrx_format_cdr3_edges(*args, None, 0)))
+    out = _uninitialised_bytes(max(1, need))
+    check(int(lib().dcrx_format_cdr3_edges(*args, _bytes_address(out), need)))
     return bytes(out[:need])
 
 

@@ -28,14 +28,18 @@ def create_args_dict(
     writeclusters: bool = False, UMIhistogram: bool = False, nonproductivefilter: bool = False,
     outpath: str = None, dontsave: bool = False, command: str = None, sampling_analysis: bool = False,
     cluster: bool = False, count_dcrs: bool = False, merge_errors: bool = False, merge_distance: int = 1,
-    merge_ratio: int = 10, write_merges: bool = False, clonotypes: bool = False,
+    merge_ratio: int = 10, write_merges: bool = False, clonotypes: bool = False, cdr3_network: bool = False,
+    cdr3_distance: int = 1, cdr3_class: str = "v", write_cdr3_edges: bool = False,
 ) -> dict:
     """The function-argument dictionary threaded through the stages (the reference's 33 keys, `cluster`: run the
     grouping / clustering half of collapse, writing the `.freq`, and `count_dcrs`: with nobarcoding, count the DCRs on the
     GPU and write the `.nbc`; `merge_errors`: fold the counted DCRs within `merge_distance` substitutions of a DCR at least
     `merge_ratio` times as abundant into it before the `.nbc` is written, `write_merges`: list what was folded in a
     `.merges` file.  The defaults 1 and 10 are a design choice, not a measured optimum.  `clonotypes`: translate also groups the
-    counted DCRs by (v_call, j_call, junction_aa) on the GPU and writes `<the .tsv's stem>.clonotypes.tsv`)."""
+    counted DCRs by (v_call, j_call, junction_aa) on the GPU and writes `<the .tsv's stem>.clonotypes.tsv`; `cdr3_network`:
+    with clonotypes, link the clonotypes of one `cdr3_class` (none, v or vj) whose junction_aa have one length and differ in at
+    most `cdr3_distance` (1 or 2) residues, on the GPU, and write `.cdr3_clusters.tsv`, with `write_cdr3_edges` also
+    `.cdr3_edges.tsv`.  The defaults v and 1 are a design choice, not a measured optimum)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -47,7 +51,8 @@ def create_args_dict(
         UMIhistogram=UMIhistogram, nonproductivefilter=nonproductivefilter, outpath=outpath,
         dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster,
         count_dcrs=count_dcrs, merge_errors=merge_errors, merge_distance=merge_distance, merge_ratio=merge_ratio,
-        write_merges=write_merges, clonotypes=clonotypes)
+        write_merges=write_merges, clonotypes=clonotypes, cdr3_network=cdr3_network, cdr3_distance=cdr3_distance,
+        cdr3_class=cdr3_class, write_cdr3_edges=write_cdr3_edges)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -112,6 +117,20 @@ def _clonotypes_flag(p: argparse.ArgumentParser):
                    help="translate, pipeline --cluster / --count-dcrs: group the counted DCRs by V call, J call and CDR3 amino "
                         "acids on the GPU and write <the .tsv's stem>.clonotypes.tsv beside the .tsv (one row per clonotype: its "
                         "reads, its DCRs, its most abundant DCR)")
+    p.add_argument("--cdr3-network", dest="cdr3_network", action="store_true",
+                   help="With --clonotypes: link the clonotypes of one class (--cdr3-class) whose CDR3 amino acids have one length "
+                        "and differ in at most --cdr3-distance residues, find the clusters they form (GPU) and write <the .tsv's "
+                        "stem>.cdr3_clusters.tsv (one row per clonotype, in the order of the .clonotypes.tsv: its cluster, the "
+                        "cluster's clonotypes and reads, its neighbours)")
+    p.add_argument("--cdr3-distance", dest="cdr3_distance", type=int, default=None,
+                   help="Residues in which two linked CDR3s may differ: 1 (default) or 2.  The default is a design choice, not a "
+                        "measured optimum")
+    p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default=None,
+                   help="What two linked clonotypes must share beside the CDR3's length: nothing (none), the V call (v, the "
+                        "default) or the V and the J call (vj).  The default is a design choice, not a measured optimum")
+    p.add_argument("--write-cdr3-edges", dest="write_cdr3_edges", action="store_true",
+                   help="With --cdr3-network: write <same stem>.cdr3_edges.tsv, one line per linked pair a < b (rows of the "
+                        ".clonotypes.tsv, 0-based) with its distance")
 
 
 def _merge_flags(p: argparse.ArgumentParser):
@@ -169,6 +188,12 @@ def cli_args(argv=None) -> dict:
                                       if inp[k] is not None]
         inp["merge_distance"] = 1 if inp["merge_distance"] is None else inp["merge_distance"]
         inp["merge_ratio"] = 10 if inp["merge_ratio"] is None else inp["merge_ratio"]
+    if "cdr3_network" in inp:
+        # which of the network's options the command line named (they are refused without --cdr3-network), then the defaults
+        inp["cdr3_options_given"] = [f for f, k in (("--cdr3-distance", "cdr3_distance"), ("--cdr3-class", "cdr3_class"))
+                                     if inp[k] is not None]
+        inp["cdr3_distance"] = 1 if inp["cdr3_distance"] is None else inp["cdr3_distance"]
+        inp["cdr3_class"] = "v" if inp["cdr3_class"] is None else inp["cdr3_class"]
     return inp
 
 
@@ -284,6 +309,35 @@ def write_out_clonotypes(clonotypes, inputargs: dict):
             fh.write(text)
     sort_permissions(outfilename)
     return outfilename
+
+
+def _write_beside_tsv(text: bytes, suffix: str, what: str, inputargs: dict):
+    """`<the .tsv's stem><suffix>` with write_out_clonotypes' rules: gzipped unless dontgzip, mode 666.  Returns the name."""
+    outfilename = _translated_stem(inputargs) + suffix
+    if not inputargs["dontgzip"]:
+        from . import _native as nat
+        print(f"Compressing {what} output file to", outfilename + ".gz")
+        with nat.GzipWriter(outfilename + ".gz", level=int(os.environ.get("DCRX_GZIP_LEVEL", "6"))) as gz:
+            gz.write(text)
+        outfilename += ".gz"
+    else:
+        with open(outfilename, "wb") as fh:
+            fh.write(text)
+    sort_permissions(outfilename)
+    return outfilename
+
+
+def write_out_cdr3_clusters(network, inputargs: dict):
+    """The cluster table of --cdr3-network beside the `.tsv`: `<the .tsv's stem>.cdr3_clusters.tsv`, tab separated with a
+    header line, one row per clonotype in the clonotype table's order (clonotype = the 0-based row of the `.clonotypes.tsv`).
+    `network`: translate.Cdr3Network (or anything with text() -> bytes).  Returns the file's name."""
+    return _write_beside_tsv(network.text(), ".cdr3_clusters.tsv", "CDR3 cluster", inputargs)
+
+
+def write_out_cdr3_edges(network, inputargs: dict):
+    """The edges of --cdr3-network --write-cdr3-edges: `<the .tsv's stem>.cdr3_edges.tsv`, header `a b distance`, one line
+    per linked pair a < b, ascending by (a, b).  `network`: anything with edges_text() -> bytes.  Returns the file's name."""
+    return _write_beside_tsv(network.edges_text(), ".cdr3_edges.tsv", "CDR3 edge", inputargs)
 
 
 def write_out_translated(rows, headers, inputargs: dict):

@@ -31,15 +31,38 @@ def clonotype_refusal(inp: dict):
     return None
 
 
+def cdr3_network_refusal(inp: dict):
+    """Why the --cdr3-network flags cannot run with these arguments, or None: the network is made of the clonotype table."""
+    others = list(inp.get("cdr3_options_given") or []) + (["--write-cdr3-edges"] if inp.get("write_cdr3_edges") else [])
+    if not inp.get("cdr3_network"):
+        return f"{', '.join(others)} belong{'s' if len(others) == 1 else ''} to --cdr3-network" if others else None
+    if not inp.get("clonotypes"):
+        return "--cdr3-network links the rows of the clonotype table: it needs --clonotypes"
+    if inp.get("cdr3_distance", 1) not in (1, 2):
+        return f"--cdr3-distance is 1 or 2, not {inp['cdr3_distance']}"
+    if inp.get("cdr3_class", "v") not in ("none", "v", "vj"):
+        return f"--cdr3-class is none, v or vj, not {inp['cdr3_class']}"
+    return None
+
+
 def _clonotypes_step(inp: dict):
-    """--clonotypes behind cdr3translator: the table (statistics printed and kept), and its file unless dontsave."""
+    """--clonotypes behind cdr3translator: the table (statistics printed and kept), and its file unless dontsave; with
+    --cdr3-network the network of its rows behind it, and its files."""
     from . import translate
-    from .io import write_out_clonotypes
+    from .io import write_out_cdr3_clusters, write_out_cdr3_edges, write_out_clonotypes
     table = translate.clonotypes(inp)
     if inp.get("chain"):
         translate.chain_clonotype_stats[str(inp["chain"]).lower()] = dict(translate.clonotype_stats)
     if not inp.get("dontsave"):
         write_out_clonotypes(table, inp)
+    if inp.get("cdr3_network"):
+        network = translate.cdr3_network(inp, table)
+        if inp.get("chain"):
+            translate.chain_cdr3_network_stats[str(inp["chain"]).lower()] = dict(translate.cdr3_network_stats)
+        if not inp.get("dontsave"):
+            write_out_cdr3_clusters(network, inp)
+            if inp.get("write_cdr3_edges"):
+                write_out_cdr3_edges(network, inp)
     return table
 
 
@@ -64,6 +87,9 @@ def _opener(path):
 def run(args: Optional[dict[str, Any]] = None, cli_args: Optional[dict[str, Any]] = None):
     inp = cli_args if cli_args else args
     why = clonotype_refusal(dict(inp, command=inp.get("command") or "pipeline"))
+    if why:
+        raise ValueError(why)
+    why = cdr3_network_refusal(inp)
     if why:
         raise ValueError(why)
     if dec.chain_list(inp.get("chain")) is not None:
@@ -139,6 +165,10 @@ def main(argv=None):
         if why:
             from .io import create_parser
             create_parser().error(why)
+    why = cdr3_network_refusal(inp)     # refused before anything is read
+    if why:
+        from .io import create_parser
+        create_parser().error(why)
     if inp.get("merge_errors") or inp.get("write_merges") or inp.get("merge_options_given"):
         from .io import create_parser          # (decombine and pipeline alone take these flags)
         try:

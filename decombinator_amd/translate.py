@@ -386,3 +386,83 @@ def clonotypes(inputargs: dict, counted: dict | None = None, genes: GeneInfo | N
           f"{stats['untranslatable']:,} untranslatable ({stats['untranslatable_reads']:,}); {stats['clonotypes_out']:,} clonotypes, "
           f"{stats['convergent']:,} of them with several DCRs (at most {stats['largest_n_dcrs']:,})")
     return ClonotypeTable(cg, table, counted, stats, of)
+
+
+# ---- the CDR3 network (--cdr3-network): the clonotypes one or two CDR3 residues apart, and their clusters, on the GPU;
+# include/dcrx.h holds the contract ----
+cdr3_network_stats: dict = {}          # the statistics of the last cdr3_network() (_native.CDR3_NETWORK_STATS)
+chain_cdr3_network_stats: dict = {}    # ... per chain, for `pipeline -c a,b`
+CDR3_CLASSES = ("none", "v", "vj")
+
+
+class Cdr3Network:
+    """What cdr3_network() returns: the nodes it made of a ClonotypeTable (classes, aa_off / aa_text, weights, and the
+    representatives' V and J genes), the result of _native.cdr3_network and its statistics; text() is the
+    `.cdr3_clusters.tsv`'s and edges_text() the `.cdr3_edges.tsv`'s, formatted by libdcrx in one pass."""
+
+    def __init__(self, genes, nodes: dict, result: dict, stats: dict):
+        self.genes, self.nodes, self.result, self.stats = genes, nodes, result, stats
+
+    def __len__(self):
+        return len(self.nodes["classes"])
+
+    def text(self) -> bytes:
+        from . import _native as nat
+        n = self.nodes
+        return nat.format_cdr3_clusters(n["v"], n["j"], self.genes.v_calls, self.genes.j_calls, n["aa_off"], n["aa_text"], n["weights"],
+                                        self.result)
+
+    def edges_text(self) -> bytes:
+        from . import _native as nat
+        return nat.format_cdr3_edges(self.nodes["aa_off"], self.nodes["aa_text"], self.result)
+
+
+def cdr3_nodes(clonotypes: ClonotypeTable, cdr3_class: str = "v") -> dict:
+    """The nodes of a clonotype table, in its order: the string is junction_aa, the weight duplicate_count, and the class what
+    `cdr3_class` says of the representative's genes — none: 0 throughout; v: the V gene's call group (the numbering of
+    ClonoGenes); vj: the V and the J call group as one number."""
+    import numpy as np
+    if cdr3_class not in CDR3_CLASSES:
+        raise ValueError(f"--cdr3-class is one of {', '.join(CDR3_CLASSES)}, not {cdr3_class!r}")
+    t, g = clonotypes.table, clonotypes.genes
+    m = len(t["rep"])
+    rep = np.asarray(t["rep"], dtype=np.int64)
+    v = np.asarray(clonotypes.counted["v"], dtype=np.int64)[rep] % max(1, len(g.v_group))      # (a negative gene counts from the end)
+    j = np.asarray(clonotypes.counted["j"], dtype=np.int64)[rep] % max(1, len(g.j_group))
+    joff = np.asarray(t["junc_off"], dtype=np.int64)
+    start, end = joff[0:2 * m:2], joff[1:2 * m:2]
+    length = end - start
+    aa_off = np.zeros(m + 1, dtype=np.uint64)
+    aa_off[1:] = np.cumsum(length)
+    # the bytes of the junction_aa halves of junc_text, back to back
+    take = np.repeat(start - aa_off[:m].astype(np.int64), length) + np.arange(int(aa_off[m]), dtype=np.int64)
+    aa_text = np.frombuffer(t["junc_text"], np.uint8)[take].tobytes() if m and int(aa_off[m]) else b""
+    if cdr3_class == "none" or not m:
+        classes = np.zeros(m, dtype=np.uint32)
+    else:
+        vg, jg = np.asarray(g.v_group, dtype=np.int64)[v], np.asarray(g.j_group, dtype=np.int64)[j]
+        classes = (vg if cdr3_class == "v" else vg * (int(np.max(g.j_group)) + 1) + jg).astype(np.uint32)
+    return {"classes": classes, "aa_off": aa_off, "aa_text": aa_text, "weights": np.asarray(t["duplicate_count"], dtype=np.uint64),
+            "v": v.astype(np.uint32), "j": j.astype(np.uint32)}
+
+
+def cdr3_network(inputargs: dict, clonotypes: ClonotypeTable) -> Cdr3Network:
+    """The CDR3 network of a clonotype table: its rows as nodes (cdr3_nodes, inputargs["cdr3_class"], default v), linked within
+    inputargs["cdr3_distance"] (1 or 2, default 1) substitutions: one call of _native.cdr3_network, with the edges when
+    inputargs["write_cdr3_edges"] is set.  Prints the statistics and keeps them in cdr3_network_stats."""
+    from . import _native as nat
+    global cdr3_network_stats
+    distance = inputargs.get("cdr3_distance")
+    distance = 1 if distance is None else int(distance)
+    if distance not in (1, 2):
+        raise ValueError(f"--cdr3-distance is 1 or 2, not {distance}")
+    nodes = cdr3_nodes(clonotypes, inputargs.get("cdr3_class") or "v")
+    if len(nodes["classes"]) >= nat.CDR3NET_MAX_NODES:
+        raise ValueError(f"--cdr3-network takes fewer than {nat.CDR3NET_MAX_NODES:,} clonotypes, not {len(nodes['classes']):,}")
+    result, stats = nat.cdr3_network(nodes["classes"], nodes["aa_off"], nodes["aa_text"], nodes["weights"], distance,
+                                     want_edges=bool(inputargs.get("write_cdr3_edges")))
+    cdr3_network_stats = stats
+    print(f"CDR3 network: {stats['nodes_in']:,} clonotypes in ({stats['out_of_reach']:,} out of reach); {stats['edges']:,} pairs "
+          f"within {distance}; {stats['clusters_out']:,} clusters, {stats['singletons']:,} of them single (the largest holds "
+          f"{stats['largest_cluster']:,}; at most {stats['largest_degree']:,} neighbours)")
+    return Cdr3Network(clonotypes.genes, nodes, result, stats)

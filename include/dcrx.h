@@ -792,6 +792,89 @@ int64_t dcrx_format_clonotypes(uint64_t m, const uint32_t *rep, const uint64_t *
                                uint32_t n_v, const char *v_calls, const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
                                const uint32_t *j_call_off, char *out, uint64_t out_cap);
 
+/* ---- the CDR3 network (`--clonotypes --cdr3-network`): which clonotypes lie one or two CDR3 residues apart, and the
+ * clusters they form, on the GPU.  The reference has no counterpart: the contract below is this library's own.  The entries
+ * only ADD to ABI 5 (nothing that existed changes) ----
+ *
+ * This layer knows nothing about genes: it works on NODES, which the caller makes out of a clonotype table.
+ * Input: m nodes — node i has rank i — with, per node, a class c_i (uint32), a string s_i (bytes, given as m + 1 offsets
+ *   into one text) and a weight w_i (uint64); and a distance D, 1 or 2.
+ * In reach: 1 <= len(s_i) <= DCRX_CDR3NET_MAX_LEN (32).  A node out of reach (empty, or longer) has no neighbours: it is a
+ *   cluster of its own, and it is counted.  The limit is a design choice: 32 bytes are eight dwords of registers per lane,
+ *   as the error merge keeps its junction; real CDR3 junctions have 8 to 25 residues.
+ * Edge: {i, j}, i != j, where both nodes are in reach, c_i == c_j, len(s_i) == len(s_j) and the Hamming distance of the
+ *   bytes is <= D.  Bytes are compared as they are: upper case, lower case, 'X', '*' and bytes >= 0x80 are each equal to
+ *   themselves alone.  Distance 0 is an edge (two clonotypes of one CDR3 that the classes do not separate).
+ * Output: degree[i]; the adjacency in CSR form, adj_off[m + 1] (uint64) and adj[] with every node's neighbours' ranks
+ *   ascending; cluster_of[i] = the row of i's connected component; per cluster row head = its smallest rank, n_nodes, and
+ *   weight = the sum of its nodes' weights.  Cluster rows are ordered by head ascending (a clonotype table is ordered by
+ *   abundance: clusters come in the order of their most abundant clonotype).
+ * The result is a function of the input alone: no tile size, launch shape or order of arrival enters it (integer adds, min
+ *   and max, and atomics whose results are not read). */
+#define DCRX_CDR3NET_MAX_LEN 32
+
+/* Bytes of device work space dcrx_cdr3_neighbours_device needs for m nodes whose strings take text_bytes bytes; 0 for
+ * m >= 2^30. */
+uint64_t dcrx_cdr3net_work_bytes(uint64_t m, uint64_t text_bytes);
+
+/* The primitive: degree and adjacency of every node, asynchronously on `hip_stream`, all arrays in device memory.  d_class:
+ * m classes; d_off: m + 1 offsets into d_text (text_bytes bytes; a node whose offsets go backwards or leave the text is out
+ * of reach).  Writes d_degree (m) and d_adj_off (m + 1: the exclusive sum of the degrees in rank order).  *d_adj_need
+ * (device, uint64) always receives the entries the adjacency takes (= d_adj_off[m], twice the number of edges); d_adj
+ * (adj_cap entries) is written when the need fits adj_cap and is never written past otherwise (an entry beyond adj_cap is
+ * dropped), so a caller that finds *d_adj_need > adj_cap calls again with a larger one (d_adj may be NULL with adj_cap 0 to
+ * size it).  The steps: keys, a stable radix sort of (key, rank) — a bucket stays in rank order —, the packed strings
+ * gathered in sorted order, a degree pass in which a block of 256 sorted nodes walks the entries of its buckets in LDS
+ * tiles of 256 (every node counts its own neighbours over its whole bucket: no atomics, neighbours in ascending rank), the
+ * exclusive sum, and a write pass that repeats the walk.  d_work: dcrx_cdr3net_work_bytes(m, text_bytes) bytes, 256-byte
+ * aligned; a smaller one is DCRX_E_INVALID, not a launch.  distance other than 1 or 2: DCRX_E_INVALID.  m < 2^30
+ * (DCRX_E_UNSUPPORTED beyond). */
+int dcrx_cdr3_neighbours_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text,
+                                uint64_t text_bytes, uint32_t distance, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj,
+                                uint64_t adj_cap, uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* Nothing that depends on the algorithm is in here (the number of component rounds is not). */
+typedef struct dcrx_cdr3_network_stats {
+  uint64_t nodes_in;
+  uint64_t out_of_reach;
+  uint64_t edges;                 /* unordered pairs */
+  uint64_t clusters_out;
+  uint64_t singletons;            /* clusters of one node */
+  uint64_t largest_cluster;       /* the largest n_nodes */
+  uint64_t largest_degree;
+} dcrx_cdr3_network_stats_t;
+
+/* The whole step on host arrays, synchronous on the current device: uploads the nodes, runs the primitive's two halves
+ * (the degree pass sizes the adjacency, which is then allocated — DCRX_E_NOMEM when it cannot be — and filled), then the
+ * connected components — label[i] = i, rounds of "the smallest label among my neighbours and me" followed by pointer
+ * jumping until a round changes nothing (one 4-byte copy back per round): the label is then the component's smallest rank —
+ * and the totals: integer adds of weights and node counts onto the heads, whose results are not read, the heads compacted in
+ * rank order.  degree_out, cluster_of_out: m entries; head_out, n_nodes_out, weight_out: m entries, of which the return value
+ * are rows.  The adjacency is copied back only where it is asked for: adj_off_out (m + 1) may be NULL, and adj_out
+ * (adj_cap entries) is filled when adj_off_out is given and the need fits adj_cap; *adj_need_out (may be NULL) receives the
+ * need either way, so a caller that wants the edges calls once to size them.  stats_out may be NULL.  Returns the number of
+ * clusters or a negative dcrx_error: DCRX_E_UNSUPPORTED for m >= 2^30, DCRX_E_INVALID for a distance other than 1 or 2 and
+ * for offsets that go backwards, DCRX_E_NOMEM (after the degree pass) for an adjacency that cannot be allocated. */
+int64_t dcrx_cdr3_network(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                          uint32_t distance, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
+                          uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap,
+                          uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out);
+
+/* The `.cdr3_clusters.tsv` text of m nodes in one pass: a header line, then per node, in rank order,
+ * "clonotype v_call j_call junction_aa duplicate_count cluster cluster_size cluster_duplicate_count degree", tab separated:
+ * clonotype = the rank, v_call / j_call = the calls of v_idx[i] / j_idx[i] (calls: one text, n + 1 offsets), junction_aa =
+ * the node's string, duplicate_count = its weight, cluster = cluster_of[i], and that row's n_nodes and weight.  Returns the
+ * bytes the text takes; writes it when out != NULL and it fits out_cap.  Host only. */
+int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint32_t *j_idx, uint32_t n_v, const char *v_calls,
+                                  const uint32_t *v_call_off, uint32_t n_j, const char *j_calls, const uint32_t *j_call_off,
+                                  const uint64_t *off, const char *text, const uint64_t *weight, const uint32_t *cluster_of,
+                                  uint64_t n_clusters, const uint32_t *n_nodes, const uint64_t *cluster_weight,
+                                  const uint32_t *degree, char *out, uint64_t out_cap);
+/* The `.cdr3_edges.tsv` text of a CSR adjacency in one pass: the header "a b distance", then one line per edge with a < b,
+ * ascending by (a, b); the distance is computed here from the two strings.  Same return rule.  Host only. */
+int64_t dcrx_format_cdr3_edges(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
+                               char *out, uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
