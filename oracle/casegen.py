@@ -278,3 +278,100 @@ def engineered_cases(ts, rng, n: int = 150):
         add("both_antisense", revcomp(r0), orientation="both")
         add("both_random", rand_seq(rng, n), orientation="both")
     return cases
+
+
+def family_cases(ts, rng, n: int = 150):
+    """(label, sense-frame read, kwargs) triples for a tag set of gene families (oracle/family.py): windows within
+    Hamming 1 of two tags, where the reference's candidate order decides (decombine.py:292-394, :420-531: hits in
+    findall order, the genes sharing the half in index order, the first that passes Hamming <= 1 and whose walk
+    succeeds; verr*/jerr* counted per candidate that passes Hamming).  Every read in `reverse`, `forward` and `both`
+    (either strand), and with an N inside the contested window with allowNs off and on."""
+    from oracle import family as fam
+    cases = []
+    nv, nj = len(ts.v_tags), len(ts.j_tags)
+    vsplit, jsplit = ts.half_splits
+
+    def variants(label, read, n_pos=None):
+        cases.append((label, read, {}))
+        cases.append((label, read, {"orientation": "forward"}))
+        cases.append((label, read, {"orientation": "both"}))
+        cases.append((label, revcomp(read), {"orientation": "both"}))
+        if n_pos is not None and 0 <= n_pos < len(read):
+            rn = read[:n_pos] + "N" + read[n_pos + 1:]
+            cases.append((label + "_N", rn, {}))
+            cases.append((label + "_N_allowed", rn, {"allow_ns": True}))
+
+    def rr(v=None, j=None, vts=None, nn=n):
+        v = int(rng.integers(0, nv)) if v is None else v
+        j = int(rng.integers(0, nj)) if j is None else j
+        vts = int(rng.integers(22, 37)) if vts is None else vts
+        r, info = rearranged(ts, rng, v, j, int(rng.integers(0, 5)), int(rng.integers(0, 7)), int(rng.integers(2, 9)), vts, nn)
+        return r, info, v, j
+
+    def put(read, pos, s):
+        return read[:pos] + s + read[pos + len(s):]
+
+    sides = (("v", ts.v_tags, vsplit, "v_tag_pos"), ("j", ts.j_tags, jsplit, "j_tag_pos"))
+    # 1. every pair at distance 2: both midpoints on a clean rearrangement of either gene
+    for side, tags, split, key in sides:
+        for a, b in fam.pairs_at(tags, 2):
+            diff = [i for i in range(len(tags[a])) if tags[a][i] != tags[b][i]]
+            for g in (a, b):
+                for k, m in enumerate(fam.midpoints(tags[a], tags[b])):
+                    if m in tags:
+                        continue
+                    r0, info, _, _ = rr(**{side: g})
+                    variants(f"{side}_midpoint", put(r0, info[key], m), info[key] + diff[k])
+    # 2. every pair at distance 1: each tag with one substitution in the shared half and one at the differing position
+    for side, tags, split, key in sides:
+        for a, b in fam.pairs_at(tags, 1):
+            p = [i for i in range(len(tags[a])) if tags[a][i] != tags[b][i]][0]
+            shared = range(0, split) if p >= split else range(split, len(tags[a]))
+            for g, o in ((a, b), (b, a)):
+                r0, info, _, _ = rr(**{side: g})
+                w = substitute(rng, tags[g], int(rng.choice(list(shared))))
+                variants(f"{side}_near1_to_other", put(r0, info[key], w[:p] + tags[o][p] + w[p + 1:]), info[key] + p)
+                third = [x for x in "ACGT" if x not in (tags[a][p], tags[b][p])][int(rng.integers(0, 2))]
+                variants(f"{side}_near1_to_neither", put(r0, info[key], w[:p] + third + w[p + 1:]))
+    # 3. a midpoint whose first candidate's walk gives up at the read's end (get_v_deletions, decombine.py:760-762): the
+    #    reference goes on to the next candidate and counts verr* twice
+    for a, b in fam.pairs_at(ts.v_tags, 2):
+        if ts.v_jumps[a] > ts.v_jumps[b]:
+            m = [x for x in fam.midpoints(ts.v_tags[a], ts.v_tags[b]) if x not in ts.v_tags]
+            if not m:
+                continue
+            r0, info, _, _ = rr(v=b)
+            for room in (0, ts.v_jumps[a] - ts.v_jumps[b] - 1):
+                variants("v_midpoint_first_walk_fails", put(r0, info["v_tag_pos"], m[0])[:info["v_tag_pos"] + ts.v_jumps[b] + room])
+    # 4. two hits of one kind of half: a bare half tag that fails Hamming before the tag's own hit, and after it
+    for side, tags, split, key in sides:
+        for g in [int(x) for x in rng.choice(len(tags), size=3 if side == "v" else 2, replace=False)]:
+            for kind in (1, 2):
+                halves = fam._halves(tags, split, kind)
+                decoy = str(rng.choice(sorted({h for h in halves if h != halves[g]})))
+                r0, info, _, _ = rr(**{side: g}, vts=34)
+                pos = info[key]
+                r0 = substitute(rng, r0, pos + (split + 2 if kind == 1 else 2))        # the tag keeps half `kind` only
+                first = put(r0, pos - len(decoy) - 4, decoy) if side == "v" else put(r0, 2, decoy)
+                variants(f"{side}_half{kind}_decoy_first", first)
+                variants(f"{side}_half{kind}_decoy_last", put(r0, len(r0) - len(decoy), decoy))
+    # 5. a half-2 hit of one gene upstream of a half-1 hit of another: half 1 is consulted first (decombine.py:292-339)
+    for _ in range(3):
+        y = int(rng.integers(0, nv))
+        xs = [x for x in range(nv) if ts.v_tags[x][:vsplit] != ts.v_tags[y][:vsplit] and ts.v_tags[x][vsplit:] != ts.v_tags[y][vsplit:]]
+        x = int(rng.choice(xs))
+        r0, info, _, _ = rr(v=y, vts=36)
+        pos = info["v_tag_pos"]
+        r0 = substitute(rng, r0, pos + vsplit + 3)
+        variants("v_half2_upstream_of_half1", put(r0, pos - len(ts.v_tags[x]) - 4, substitute(rng, ts.v_tags[x], 3)))
+    # 6. the decoy ladder on either side of the kernels' list limits
+    for k in (4, 5, 8, 9):
+        for kind in (1, 2):
+            v, j = int(rng.integers(0, nv)), int(rng.integers(0, nj))
+            variants(f"v_ladder_{k}", fam.ladder_read(ts, rng, v, j, k, 0, kind, 3 - kind, ins=int(rng.integers(0, 7))))
+            variants(f"j_ladder_{k}", fam.ladder_read(ts, rng, v, j, 0, k, 1, 2, kind, 3 - kind, ins=int(rng.integers(0, 7))))
+    for k in (5, 9):     # the rungs are all the half-1 hits there are: found...1not...2
+        v, j = int(rng.integers(0, nv)), int(rng.integers(0, nj))
+        variants(f"v_ladder_{k}_gives_up", fam.ladder_read(ts, rng, v, j, k, 0, 1, 1))
+        variants(f"j_ladder_{k}_gives_up", fam.ladder_read(ts, rng, v, j, 0, k, 1, 2, 1, 1))
+    return cases

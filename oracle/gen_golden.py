@@ -10,6 +10,7 @@ oracle and the HIP path against them.
     python oracle/gen_golden.py --bulk N   # additionally cross-checks the C oracle
                                            # against the reference on N random reads
                                            # per tag set (not committed)
+    python oracle/gen_golden.py --only NAME   # writes that one fixture and nothing else
 
 Each fixture: {"tagset": {...}, "cases": [{"label", "read" (FASTQ frame),
 "orientation", "allowNs", "lenthreshold", "expect" (dcr()'s 7-list or null),
@@ -18,6 +19,7 @@ Each fixture: {"tagset": {...}, "cases": [{"label", "read" (FASTQ frame),
 from __future__ import annotations
 
 import argparse
+import gzip
 import json
 import os
 import sys
@@ -29,9 +31,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from decombinator_amd import synth  # noqa: E402
-from oracle import casegen, ref_driver  # noqa: E402
+from oracle import casegen, family, ref_driver  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+GZIPPED = ("family_original_b",)      # written as dcr_NAME.json.gz; tests/golden_util.py reads either
 
 
 def tagset_dict(ts: synth.TagSet) -> dict:
@@ -59,10 +62,13 @@ def run_cases(ts: synth.TagSet, cases, tagdir: str):
     return out
 
 
-def build_cases(ts, seed: int, n_mix: int, read_len: int = 150, sub_rate: float = 0.005):
+def build_cases(ts, seed: int, n_mix: int, read_len: int = 150, sub_rate: float = 0.005, with_family_cases: bool = False):
     rng = np.random.default_rng(seed)
     cases = []
-    for label, read, kw in casegen.engineered_cases(ts, rng, read_len):
+    engineered = casegen.engineered_cases(ts, rng, read_len)
+    if with_family_cases:
+        engineered += casegen.family_cases(ts, rng, read_len)
+    for label, read, kw in engineered:
         orientation = kw.get("orientation", "reverse")
         fq = casegen.revcomp(read) if "orientation" not in kw else read
         cases.append((label, fq, orientation, kw.get("allow_ns", False), kw.get("lenthreshold", 130)))
@@ -83,8 +89,9 @@ def summarize(name, cases):
     print(f"{name}: {len(cases)} cases, {ok} decombined; counters: {dict(sorted(c.items()))}")
 
 
-def bulk_crosscheck(ts, tagdir, n, seed):
-    """Reference (Python) vs the C oracle on n random mixture reads."""
+def bulk_crosscheck(ts, tagdir, n, seed, family_reads: bool = False):
+    """Reference (Python) vs the C oracle on n random mixture reads; on a family set n contested reads and n ladder
+    reads (oracle/family.py) on top."""
     from oracle import oracle as orc
     ts.write(tagdir)
     ref = ref_driver.RefChain(tagdir, ts.species, ts.tags, ts.chain)
@@ -95,8 +102,10 @@ def bulk_crosscheck(ts, tagdir, n, seed):
     bad = 0
     tot = np.zeros(orc.N_COUNTERS, dtype=np.uint64)
     ref.reload()
-    for i in range(n):
-        sense = casegen.mixture_read(ts, rng, 150, sub_rate=0.01, n_rate=0.01)
+    senses = [casegen.mixture_read(ts, rng, 150, sub_rate=0.01, n_rate=0.01) for _ in range(n)]
+    if family_reads:
+        senses += family.contested_reads(ts, rng, n)[0] + family.decoy_ladder(ts, rng, n)[0]
+    for sense in senses:
         fq = casegen.revcomp(sense)
         recom, frame, _ = ref.decombine_read(fq, "reverse")
         ok, res = ot.decombine_read(fq, 0, counts=tot)
@@ -114,7 +123,7 @@ def bulk_crosscheck(ts, tagdir, n, seed):
         if int(tot[idx]) != int(refc.get(nm, 0)) and nm != "frame_forward":
             bad += 1
             print("COUNTER MISMATCH", nm, int(tot[idx]), refc.get(nm, 0))
-    print(f"bulk {ts.species}/{ts.tags}/{ts.chain}: {n} reads, {bad} mismatches")
+    print(f"bulk {ts.species}/{ts.tags}/{ts.chain}: {len(senses)} reads, {bad} mismatches")
     return bad
 
 
@@ -163,6 +172,12 @@ def make_edge_tagset(seed: int = 14) -> synth.TagSet:
             reg = reg[:jump + len(t) + 3]     # J region ends 3 nt after the tag
         ts.j_tags.append(t); ts.j_jumps.append(jump); ts.j_names.append(f"EDGEJ{i}"); ts.j_regions.append(reg)
     return ts
+
+
+def make_family_tagset() -> synth.TagSet:
+    """The family set of the fifth fixture (oracle/family.py)."""
+    return family.make_family_tagset(seed=15, tags="original", chain="b", n_v=24, n_j=10, v_families=3, j_families=2,
+                                     related_regions=True, decoys=True)
 
 
 def gen_stage_fixture(out_path: str, seed: int = 77, n_pairs: int = 700):
@@ -222,6 +237,7 @@ def gen_stage_fixture(out_path: str, seed: int = 77, n_pairs: int = 700):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bulk", type=int, default=0)
+    ap.add_argument("--only", metavar="NAME", help="write the fixture of that name only")
     args = ap.parse_args()
     if not ref_driver.available():
         sys.exit("reference tree not present: golden vectors can only be generated in the build container")
@@ -235,20 +251,34 @@ def main():
         "mouse_original_g": (synth.make_tagset("mouse", "original", "g", n_v=12, n_j=4, seed=13,
                                                n_shared_groups=2), 103, 800),
         "edge_extended_b": (make_edge_tagset(), 104, 600),
+        # gene families: tags 1 and 2 substitutions apart that share a half, related regions, decoy half tags upstream
+        "family_original_b": (make_family_tagset(), 105, 300),
     }
+    if args.only:
+        if args.only not in sets:
+            sys.exit(f"--only: no such fixture (one of {', '.join(sets)})")
+        sets = {args.only: sets[args.only]}
     bad = 0
     for name, (ts, seed, n_mix) in sets.items():
         with tempfile.TemporaryDirectory() as td:
-            cases = build_cases(ts, seed, n_mix, sub_rate=0.02 if "mouse" in name else 0.005)
+            cases = build_cases(ts, seed, n_mix, sub_rate=0.02 if "mouse" in name else 0.005,
+                                with_family_cases=name.startswith("family"))
             res = run_cases(ts, cases, td)
             summarize(name, res)
-            with open(os.path.join(GOLDEN, f"dcr_{name}.json"), "w") as f:
-                json.dump({"generator": "oracle/gen_golden.py", "source":
-                           "reference src/decombinator/decombine.py (unmodified) + oracle/refshim stand-ins",
-                           "tagset": tagset_dict(ts), "cases": res}, f, separators=(",", ":"))
+            text = json.dumps({"generator": "oracle/gen_golden.py", "source":
+                               "reference src/decombinator/decombine.py (unmodified) + oracle/refshim stand-ins",
+                               "tagset": tagset_dict(ts), "cases": res}, separators=(",", ":"))
+            if name in GZIPPED:      # (mtime 0, no file name inside: the same bytes on every run)
+                with open(os.path.join(GOLDEN, f"dcr_{name}.json.gz"), "wb") as f, \
+                        gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=f, mtime=0) as z:
+                    z.write(text.encode("ascii"))
+            else:
+                with open(os.path.join(GOLDEN, f"dcr_{name}.json"), "w") as f:
+                    f.write(text)
             if args.bulk:
-                bad += bulk_crosscheck(ts, td, args.bulk, seed + 1000)
-    gen_stage_fixture(os.path.join(GOLDEN, "stage_human_extended_b.json"))
+                bad += bulk_crosscheck(ts, td, args.bulk, seed + 1000, family_reads=name.startswith("family"))
+    if not args.only:
+        gen_stage_fixture(os.path.join(GOLDEN, "stage_human_extended_b.json"))
     if args.bulk:
         print("bulk cross-check mismatches:", bad)
         sys.exit(1 if bad else 0)

@@ -2,7 +2,8 @@
 reads its A/B switches (DCRX_DEBUG_RESCUE_WAVES, DCRX_DEBUG_TAIL_WAVES, DCRX_DEBUG_NO_TUNE) once per process.  Decombines
 N device-resident reads of a BASELINE config in one launch (the fused form at a batch size the handle tunes itself on:
 >= 2^20 reads), CALLS times on one handle — the handle's own choice of rescue waves settles on the sixth call — and compares
-every record and every counter of every call with the threaded oracle.  usage: forced_shape_worker.py CONFIG N CALLS"""
+every record and every counter of every call with the threaded oracle.  usage: forced_shape_worker.py CONFIG N CALLS
+CONFIG `family`: N uniform 150-nt contested reads of a gene-family tag set (oracle/family.py) instead of the generator's."""
 import os
 import sys
 
@@ -15,7 +16,34 @@ from oracle import oracle as orc                     # noqa: E402
 from tests import parity_util as pu                  # noqa: E402
 
 
+def family_main(n, calls):
+    """Contested reads (windows within Hamming 1 of two tags) in one uniform batch, as the forms that need one length for
+    all reads take them; the conditions on the workload from the oracle's side, then every record and counter."""
+    from oracle import family
+    from tests import family_util as fu
+    ts = fu.tagset("original")
+    sense, marks = family.contested_reads(ts, np.random.default_rng(n), n, p_cut=0.0, lengths=(150,), length_p=(1.0,))
+    w = fu.Workload(ts, sense, marks)
+    family.assert_contest_conditions(w.report, scale=n / 60_000)
+    t = pu.native_tables(w.d)
+    (_, hb), = w.batches("reverse")
+    assert hb.lens is None and hb.read_len == 150
+    orec, ocnt = w.want("reverse")
+    db = nat.DeviceBatch.from_host(hb)
+    d_rec = nat.DeviceBuffer(n * 16)
+    d_cnt = nat.DeviceBuffer(nat.N_COUNTERS * 8)
+    for k in range(calls):
+        nat.check(nat.lib().dcrx_memset_device(d_rec.ptr, 0xEE, n * 16))
+        nat.decombine_device(t, db, d_rec, d_cnt)
+        nat.synchronize()
+        pu.assert_records_equal(d_rec.to_host(nat.RECORD_DTYPE, n), orec, w.reads("reverse"), f"call {k}")
+        pu.assert_counters_equal(d_cnt.to_host(np.uint64, nat.N_COUNTERS), ocnt, f"call {k}")
+    print("SHAPE_OK", "family", n, calls, t.tune_state(n), w.report)
+
+
 def main():
+    if sys.argv[1] == "family":
+        return family_main(int(sys.argv[2]), int(sys.argv[3]))
     config, n, calls = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
     ts = synth.config_tagset(2) if config == 2 else list(synth.config5_tagsets())[0]
     vs, js = ts.half_splits

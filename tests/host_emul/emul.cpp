@@ -232,6 +232,10 @@ extern "C" int emul_decombine(const dcrx_tagset_t *ts, const dcrx_cfg_t *cfg, co
     const bool all_general = C.orientation == DCRX_ORIENT_BOTH || (C.flags & DCRX_F_FORCE_SLOW_READER) || (B.stride > 4 * DCRX_NWMAX && !v2_able);
     const bool general = all_general || ((flag[r >> 5] >> (r & 31)) & 1u);
     const bool v2 = v2_able && !all_general;
+    // what the v2 kernels hand over (more flagged pairs or exception bytes than an entry holds) goes to the LIST kernel behind
+    // them, whatever the three-launch form would do with its rescue queue: the rescue kernel's forms hold 320 nt, the v2
+    // kernels' longest shape 511
+    const bool pair_handover = pair_rescue && !v2;
     // the v2 kernels take every read of the batch, those with exception bytes included (with their slice of the list)
     int x0 = 0, x1 = 0;
     if (v2 && general) {
@@ -243,15 +247,15 @@ extern "C" int emul_decombine(const dcrx_tagset_t *ts, const dcrx_cfg_t *cfg, co
       int what = FAST_TO_GENERAL;
       if (v2) what = B.stride <= 40 ? v2_one<false, 10>(T, B, C, r, x0, x1, CC, records) : B.stride <= 4 * DCRX_NWMAX ? v2_one<false, DCRX_NWMAX>(T, B, C, r, x0, x1, CC, records) : v2_one<false, DCRX_V2_NWLONG>(T, B, C, r, x0, x1, CC, records);
       else if (!general) what = fast_one<false>(pair_scan, T, B, C, r, nw, CC, records);
-      if (what == FAST_TO_GENERAL) general_one<false>(pair_rescue && !all_general, T, B, C, r, nw, CC, records, slot);
-      else if (what == FAST_TO_RESCUE) rescue_one<false>(pair_rescue, T, B, C, r, nw, CC, records, slot);
+      if (what == FAST_TO_GENERAL) general_one<false>(pair_handover && !all_general, T, B, C, r, nw, CC, records, slot);
+      else if (what == FAST_TO_RESCUE) rescue_one<false>(pair_handover, T, B, C, r, nw, CC, records, slot);
       else if (what != FAST_DONE) return -100;
     } else {
       int what = FAST_TO_GENERAL;
       if (v2) what = B.stride <= 40 ? v2_one<true, 10>(T, B, C, r, x0, x1, CC, records) : B.stride <= 4 * DCRX_NWMAX ? v2_one<true, DCRX_NWMAX>(T, B, C, r, x0, x1, CC, records) : v2_one<true, DCRX_V2_NWLONG>(T, B, C, r, x0, x1, CC, records);
       else if (!general) what = fast_one<true>(pair_scan, T, B, C, r, nw, CC, records);
-      if (what == FAST_TO_GENERAL) general_one<true>(pair_rescue && !all_general, T, B, C, r, nw, CC, records, slot);
-      else if (what == FAST_TO_RESCUE) rescue_one<true>(pair_rescue, T, B, C, r, nw, CC, records, slot);
+      if (what == FAST_TO_GENERAL) general_one<true>(pair_handover && !all_general, T, B, C, r, nw, CC, records, slot);
+      else if (what == FAST_TO_RESCUE) rescue_one<true>(pair_handover, T, B, C, r, nw, CC, records, slot);
       else if (what != FAST_DONE) return -100;
     }
     for (int c = 0; c < DCRX_N_COUNTERS; c++) { counters[c] += counts[c]; counts[c] = 0; }
