@@ -408,6 +408,7 @@ CDR3_CLUSTER_COLUMNS = ["clonotype", "v_call", "j_call", "junction_aa", "duplica
 CDR3_EDGE_COLUMNS = ["a", "b", "distance"]
 CDR3NET_MAX_LEN = 32           # DCRX_CDR3NET_MAX_LEN
 CDR3NET_MAX_NODES = 1 << 30    # dcrx_cdr3_network / dcrx_cdr3_neighbours_device: DCRX_E_UNSUPPORTED from here on
+CDR3_METRICS = {"hamming": 0, "levenshtein": 1}      # DCRX_CDR3NET_HAMMING, DCRX_CDR3NET_LEVENSHTEIN
 
 
 class Cdr3NetworkStatsC(C.Structure):
@@ -443,6 +444,7 @@ EXPORTS = [
     "dcrx_clonotypes", "dcrx_clonotypes_text", "dcrx_format_clonotypes",
     "dcrx_cdr3net_work_bytes", "dcrx_cdr3_neighbours_device", "dcrx_cdr3_network", "dcrx_format_cdr3_clusters",
     "dcrx_format_cdr3_edges",
+    "dcrx_cdr3net_metric_work_bytes", "dcrx_cdr3_neighbours_metric_device", "dcrx_cdr3_network_metric", "dcrx_format_cdr3_edges_metric",
 ]
 
 _lib = None
@@ -580,6 +582,11 @@ def lib():
         "dcrx_cdr3_network": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp, C.POINTER(Cdr3NetworkStatsC)]),
         "dcrx_format_cdr3_clusters": (C.c_int64, [u64, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64]),
         "dcrx_format_cdr3_edges": (C.c_int64, [u64, vp, vp, vp, vp, vp, u64]),
+        "dcrx_cdr3net_metric_work_bytes": (u64, [u64, u64, u32]),
+        "dcrx_cdr3_neighbours_metric_device": (i32, [u64, vp, vp, vp, u64, u32, u32, vp, vp, vp, u64, vp, vp, u64, vp]),
+        "dcrx_cdr3_network_metric": (C.c_int64, [u64, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp,
+                                                 C.POINTER(Cdr3NetworkStatsC)]),
+        "dcrx_format_cdr3_edges_metric": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1302,18 +1309,36 @@ def format_clonotypes(genes: ClonoGenes, table: dict, counted: dict) -> bytes:
 
 # ---- the CDR3 network (--cdr3-network): include/dcrx.h "the CDR3 network" ----
 
-def cdr3net_work_bytes(m: int, text_bytes: int) -> int:
-    return int(lib().dcrx_cdr3net_work_bytes(int(m), int(text_bytes)))
+def cdr3_metric_code(metric) -> int:
+    """DCRX_CDR3NET_HAMMING / _LEVENSHTEIN for a metric's name (None: hamming); a number is passed on as it is (the library
+    refuses the ones it does not know)."""
+    if metric is None:
+        return 0
+    if isinstance(metric, str):
+        if metric not in CDR3_METRICS:
+            raise ValueError(f"the CDR3 network's metric is one of {', '.join(CDR3_METRICS)}, not {metric!r}")
+        return CDR3_METRICS[metric]
+    return int(metric)
+
+
+def cdr3net_work_bytes(m: int, text_bytes: int, metric=None) -> int:
+    """dcrx_cdr3net_work_bytes, or with a metric dcrx_cdr3net_metric_work_bytes."""
+    if metric is None:
+        return int(lib().dcrx_cdr3net_work_bytes(int(m), int(text_bytes)))
+    return int(lib().dcrx_cdr3net_metric_work_bytes(int(m), int(text_bytes), cdr3_metric_code(metric)))
 
 
 def cdr3_neighbours_device(m: int, d_class, d_off, d_text, text_bytes: int, distance: int, d_degree, d_adj_off, d_adj, adj_cap: int,
-                           d_adj_need, d_work, work_bytes: int, stream=None):
-    """dcrx_cdr3_neighbours_device: degree and adjacency of every node of a table in HBM (DeviceBuffers), asynchronous on
-    `stream`."""
-    check(lib().dcrx_cdr3_neighbours_device(int(m), d_class.ptr, d_off.ptr, d_text.ptr if d_text is not None else None,
-                                            int(text_bytes), int(distance), d_degree.ptr, d_adj_off.ptr,
-                                            d_adj.ptr if d_adj is not None else None, int(adj_cap),
-                                            d_adj_need.ptr if d_adj_need is not None else None, d_work.ptr, int(work_bytes), stream))
+                           d_adj_need, d_work, work_bytes: int, stream=None, metric=None):
+    """dcrx_cdr3_neighbours_device (with a metric: dcrx_cdr3_neighbours_metric_device): degree and adjacency of every node of a
+    table in HBM (DeviceBuffers), asynchronous on `stream`."""
+    head = [int(m), d_class.ptr, d_off.ptr, d_text.ptr if d_text is not None else None, int(text_bytes), int(distance)]
+    tail = [d_degree.ptr, d_adj_off.ptr, d_adj.ptr if d_adj is not None else None, int(adj_cap),
+            d_adj_need.ptr if d_adj_need is not None else None, d_work.ptr, int(work_bytes), stream]
+    if metric is None:
+        check(lib().dcrx_cdr3_neighbours_device(*head, *tail))
+    else:
+        check(lib().dcrx_cdr3_neighbours_metric_device(*head, cdr3_metric_code(metric), *tail))
 
 
 def _node_arrays(aa_off, aa_text):
@@ -1322,9 +1347,11 @@ def _node_arrays(aa_off, aa_text):
     return off, text
 
 
-def cdr3_network(classes, aa_off, aa_text: bytes, weights, distance: int, want_edges: bool = False):
+def cdr3_network(classes, aa_off, aa_text: bytes, weights, distance: int, want_edges: bool = False, metric="hamming"):
     """dcrx_cdr3_network on the current device: m nodes (class, string = aa_text[aa_off[i]:aa_off[i + 1]], weight) linked where
-    class and length agree and at most `distance` (1 or 2) bytes differ — (result, statistics dict over CDR3_NETWORK_STATS).
+    class and length agree and at most `distance` (1 or 2) bytes differ — or, with metric "levenshtein"
+    (dcrx_cdr3_network_metric), where the class agrees and the strings are at most `distance` substitutions, insertions and
+    deletions apart — (result, statistics dict over CDR3_NETWORK_STATS).
     result: degree and cluster_of per node; cluster_head, cluster_size and cluster_weight per cluster row (rows by head
     ascending); with want_edges the CSR adjacency adj_off (m + 1) and adj (a second call, once the first has sized it)."""
     cls = np.ascontiguousarray(classes, dtype=np.uint32)
@@ -1340,12 +1367,16 @@ def cdr3_network(classes, aa_off, aa_text: bytes, weights, distance: int, want_e
     adj_off = np.zeros(m + 1, np.uint64) if want_edges else None
     need = C.c_uint64(0)
     st = Cdr3NetworkStatsC()
+    code = cdr3_metric_code(metric)
 
     def call(adj, cap):
-        return check(int(lib().dcrx_cdr3_network(m, cls.ctypes.data, off.ctypes.data, text.ctypes.data, w.ctypes.data, int(distance),
-                                                 deg.ctypes.data, of.ctypes.data, head.ctypes.data, nn.ctypes.data, cw.ctypes.data,
-                                                 adj_off.ctypes.data if want_edges else None,
-                                                 adj.ctypes.data if adj is not None else None, cap, C.byref(need), C.byref(st))))
+        head_args = [m, cls.ctypes.data, off.ctypes.data, text.ctypes.data, w.ctypes.data, int(distance)]
+        tail_args = [deg.ctypes.data, of.ctypes.data, head.ctypes.data, nn.ctypes.data, cw.ctypes.data,
+                     adj_off.ctypes.data if want_edges else None, adj.ctypes.data if adj is not None else None, cap, C.byref(need),
+                     C.byref(st)]
+        if code == 0:
+            return check(int(lib().dcrx_cdr3_network(*head_args, *tail_args)))
+        return check(int(lib().dcrx_cdr3_network_metric(*head_args, code, *tail_args)))
     c = call(None, 0)
     result = {"degree": deg[:m].copy(), "cluster_of": of[:m].copy(), "cluster_head": head[:c].copy(), "cluster_size": nn[:c].copy(),
               "cluster_weight": cw[:c].copy()}
@@ -1382,15 +1413,21 @@ def format_cdr3_clusters(v_idx, j_idx, v_calls, j_calls, aa_off, aa_text: bytes,
     return bytes(out[:need])
 
 
-def format_cdr3_edges(aa_off, aa_text: bytes, result: dict) -> bytes:
-    """dcrx_format_cdr3_edges: the `.cdr3_edges.tsv` text of a cdr3_network result with edges."""
+def format_cdr3_edges(aa_off, aa_text: bytes, result: dict, metric="hamming") -> bytes:
+    """dcrx_format_cdr3_edges: the `.cdr3_edges.tsv` text of a cdr3_network result with edges; with metric "levenshtein"
+    (dcrx_format_cdr3_edges_metric) the distance column is the Levenshtein distance and edges may join two lengths."""
     off, text = _node_arrays(aa_off, aa_text)
     adj_off = np.ascontiguousarray(result["adj_off"], dtype=np.uint64)
     adj = np.ascontiguousarray(result["adj"], dtype=np.uint32) if len(result["adj"]) else np.zeros(1, np.uint32)
     args = [len(off) - 1, adj_off.ctypes.data, adj.ctypes.data, off.ctypes.data, text.ctypes.data]
-    need = check(int(lib().dcrx_format_cdr3_edges(*args, None, 0)))
+    code = cdr3_metric_code(metric)
+    if code == 0:
+        fmt = lib().dcrx_format_cdr3_edges
+    else:
+        fmt, args = lib().dcrx_format_cdr3_edges_metric, args + [code]
+    need = check(int(fmt(*args, None, 0)))
     out = _uninitialised_bytes(max(1, need))
-    check(int(lib().dcrx_format_cdr3_edges(*args, _bytes_address(out), need)))
+    check(int(fmt(*args, _bytes_address(out), need)))
     return bytes(out[:need])
 
 

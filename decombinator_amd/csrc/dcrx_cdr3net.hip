@@ -18,11 +18,19 @@
 // "the smallest label among my neighbours and me" and pointer jumping, double buffered, until a round changes nothing) and
 // the totals (integer atomics onto the heads, results unused; the heads compacted in rank order).
 // The sorts, scans, run heads and compaction are dcrx_group.h's.
+//
+// Under the Levenshtein metric (the *_metric entries, DCRX_CDR3NET_LEVENSHTEIN) the bucket is the class alone: the same keys
+// are sorted over their class bits and the out-of-reach bit only — stable, so a class stays in rank order and the sorted keys
+// keep every node's length —, the gather also leaves a letter-presence mask per node, and the walk (the LEV forms of the same
+// kernels) tests a pair by class, length difference, presence masks and then lev_within (on the entry a lane has waiting,
+// once some lane of the wave meets its next one).  A node still walks its whole bucket, now its class: the extra pairs fall
+// at one length compare, and the neighbours still come in ascending rank.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/dcrx.h"
@@ -37,6 +45,7 @@ namespace {
 
 constexpr uint64_t MAX_NODES = 1ull << 30;
 constexpr int TILE = 256;        // staged entries per step
+constexpr uint32_t NO_ENTRY = 0xFFFFFFFFu;
 
 struct Nodes {
   const uint32_t *cls;
@@ -60,9 +69,14 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_keys_kernel(Nodes N, uint32_t n
   idx[e] = e;
 }
 
+// the key a bucket is made of: the whole key, or under the Levenshtein metric its class (and out-of-reach) bits
+template <bool LEV> __device__ __forceinline__ uint64_t bucket_of(uint64_t key) { return LEV ? key_class(key) : key; }
+
+// LEV: the run marks are the classes', and every node's letter-presence mask goes beside its string
+template <bool LEV>
 __global__ __launch_bounds__(BLOCK) void cdr3net_gather_kernel(Nodes N, uint32_t n, const uint64_t *__restrict__ key,
                                                                const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
-                                                               uint32_t *__restrict__ mark) {
+                                                               uint32_t *__restrict__ mark, uint32_t *__restrict__ pres) {
   const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
   if (s >= n) return;
   const uint32_t e = idx[s];
@@ -72,24 +86,31 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_gather_kernel(Nodes N, uint32_t
   pack(N.text + (in_reach(len) ? at : 0), len, w);
   sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
   sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-  mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
+  mark[s] = run_mark(s, [&](uint32_t k) { return bucket_of<LEV>(key[k]); });
+  if (LEV) pres[s] = presence(w, in_reach(len) ? (uint32_t)len : 0u);
 }
 
 // The walk.  WRITE false: degree[rank] (and the same as 64 bits, for the scan); true: the neighbours' ranks at adj_off[rank].
-template <bool WRITE>
+// LEV: the buckets are the classes (the staged keys still hold the lengths), the presence masks are staged with the strings,
+// and a pair is tested by length difference, presence masks and lev_within instead of the Hamming distance.
+template <bool WRITE, bool LEV>
 __global__ __launch_bounds__(BLOCK) void cdr3net_walk_kernel(const uint4 *__restrict__ sj, const uint64_t *__restrict__ key,
                                                              const uint32_t *__restrict__ idx, const uint32_t *__restrict__ bstart,
                                                              uint32_t n, uint32_t limit, uint32_t *__restrict__ degree,
                                                              uint64_t *__restrict__ deg64, const uint64_t *__restrict__ adj_off,
-                                                             uint32_t *__restrict__ adj, uint64_t adj_cap) {
+                                                             uint32_t *__restrict__ adj, uint64_t adj_cap,
+                                                             const uint32_t *__restrict__ pres) {
   __shared__ uint4 lds_j[TILE * 2];
   __shared__ uint64_t lds_k[TILE];
   __shared__ uint32_t lds_r[TILE];
+  __shared__ uint32_t lds_p[LEV ? TILE : 1];
   const uint32_t s0 = blockIdx.x * BLOCK;
   const uint32_t s = s0 + threadIdx.x;
   const bool valid = s < n;
-  const uint64_t k_own = valid ? key[s] : KEY_OUT_OF_REACH;
-  const bool reach = k_own != KEY_OUT_OF_REACH;
+  const uint64_t key_own = valid ? key[s] : KEY_OUT_OF_REACH;
+  const bool reach = key_own != KEY_OUT_OF_REACH;
+  const uint64_t k_own = bucket_of<LEV>(key_own);
+  const uint32_t len_own = key_length(key_own), pres_own = LEV && valid ? pres[s] : 0u;
   uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t e = 0, count = 0;
   uint64_t at = 0;
@@ -104,9 +125,9 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_walk_kernel(const uint4 *__rest
   // the wave's keys (sorted along s; lanes behind the table hold the largest key)
   const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
   // the block's entries: from its first node's bucket start to its last node's bucket end, nodes out of reach left out
-  const uint64_t k_max = min(key[min(n, s0 + (uint32_t)BLOCK) - 1], KEY_OUT_OF_REACH - 1);
+  const uint64_t k_max = min(bucket_of<LEV>(key[min(n, s0 + (uint32_t)BLOCK) - 1]), bucket_of<LEV>(KEY_OUT_OF_REACH) - 1);
   for (uint32_t t = bstart[s0]; t < n; t += TILE) {
-    if (key[t] > k_max) break;                              // (the same for every lane of the block)
+    if (bucket_of<LEV>(key[t]) > k_max) break;              // (the same for every lane of the block)
     __syncthreads();                                        // the previous tile is no longer read
     const uint32_t tile_n = min((uint32_t)TILE, n - t);
     if (threadIdx.x < tile_n) {
@@ -115,19 +136,47 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_walk_kernel(const uint4 *__rest
       lds_j[2 * threadIdx.x + 1] = sj[2 * (size_t)p + 1];
       lds_k[threadIdx.x] = key[p];
       if (WRITE) lds_r[threadIdx.x] = idx[p];
+      if (LEV) lds_p[threadIdx.x] = pres[p];
     }
     __syncthreads();
-    if (lds_k[tile_n - 1] < w_lo || lds_k[0] > w_hi) continue;      // the tile holds nothing of this wave's buckets
+    if (bucket_of<LEV>(lds_k[tile_n - 1]) < w_lo || bucket_of<LEV>(lds_k[0]) > w_hi) continue;      // the tile holds nothing of this wave's buckets
     const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
+    if (!LEV) {
+      for (uint32_t q = 0; q < tile_n; q++) {
+        const uint64_t kq = lds_k[q];
+        if (kq < w_lo) continue;
+        if (kq > w_hi) break;
+        if (reach && kq == k_own && t + q != s && distance(own, lj + q * WORDS, limit) <= limit) {
+          if (WRITE && at + count < adj_cap) adj[at + count] = lds_r[q];
+          count++;
+        }
+      }
+      continue;
+    }
+    // LEV: an entry that passes the cheap tests waits in `pending` (one per lane), and lev_within runs — for every lane that
+    // has one waiting, each on its own entry — only once some lane meets its next one, and at the tile's end: the few lanes
+    // of a wave that pass at one entry would otherwise run it nearly alone.  A lane still takes its entries in order.
+    uint32_t pending = NO_ENTRY;
+    auto settle = [&]() {
+      if (pending != NO_ENTRY) {
+        if (lev_within(own, len_own, lj + pending * WORDS, key_length(lds_k[pending]), limit) <= limit) {
+          if (WRITE && at + count < adj_cap) adj[at + count] = lds_r[pending];
+          count++;
+        }
+        pending = NO_ENTRY;
+      }
+    };
     for (uint32_t q = 0; q < tile_n; q++) {
-      const uint64_t kq = lds_k[q];
+      const uint64_t key_q = lds_k[q], kq = key_class(key_q);
       if (kq < w_lo) continue;
       if (kq > w_hi) break;
-      if (reach && kq == k_own && t + q != s && distance(own, lj + q * WORDS, limit) <= limit) {
-        if (WRITE && at + count < adj_cap) adj[at + count] = lds_r[q];
-        count++;
-      }
+      const uint32_t len_q = key_length(key_q);
+      const bool passes = reach && kq == k_own && t + q != s && len_q + limit >= len_own && len_own + limit >= len_q &&
+                          presence_allows(pres_own, lds_p[q], limit);
+      if (__any(passes && pending != NO_ENTRY)) settle();      // (the same for every lane of the wave)
+      if (passes) pending = q;
     }
+    settle();      // (the next tile overwrites the staged entries)
   }
   if (valid && !WRITE) {
     degree[e] = count;
@@ -207,10 +256,13 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_cluster_of_kernel(const uint32_
 
 // ---- work space of the primitive ----
 struct WorkPlan {
-  uint64_t key[2], idx[2], mark, bstart, sj, deg64, cub, cub_bytes, total;
+  uint64_t key[2], idx[2], mark, bstart, sj, deg64, pres, cub, cub_bytes, total;
 };
 
-int plan_work(uint64_t n, WorkPlan *W) {
+bool metric_exists(uint32_t metric) { return metric == METRIC_HAMMING || metric == METRIC_LEVENSHTEIN; }
+
+// (the Hamming plan is what it was: the presence masks of the Levenshtein walk come behind it)
+int plan_work(uint64_t n, uint32_t metric, WorkPlan *W) {
   size_t cub_bytes = 0;
   const uint64_t k = std::max<uint64_t>(n, 1);
   int rc;
@@ -224,6 +276,7 @@ int plan_work(uint64_t n, WorkPlan *W) {
   W->deg64 = C.take(n * 8);
   W->cub_bytes = cub_bytes;
   W->cub = C.take(cub_bytes);
+  W->pres = metric == METRIC_LEVENSHTEIN ? C.take(n * 4) : 0;
   W->total = C.at;
   return DCRX_OK;
 }
@@ -233,16 +286,18 @@ struct Sorted {      // what the degree pass leaves in the work space for the wr
   const uint64_t *key;
   const uint32_t *idx, *bstart;
   uint64_t *deg64;
+  uint32_t *pres;      // (the Levenshtein walk's)
 };
 Sorted sorted_view(uint8_t *w, const WorkPlan &W) {
   return Sorted{reinterpret_cast<const uint4 *>(w + W.sj), reinterpret_cast<const uint64_t *>(w + W.key[1]),
                 reinterpret_cast<const uint32_t *>(w + W.idx[1]), reinterpret_cast<const uint32_t *>(w + W.bstart),
-                reinterpret_cast<uint64_t *>(w + W.deg64)};
+                reinterpret_cast<uint64_t *>(w + W.deg64), reinterpret_cast<uint32_t *>(w + W.pres)};
 }
 
 // keys, sort, gather, the degree pass, the scan and the need
-int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t *d_degree, uint64_t *d_adj_off, uint64_t *d_need, uint8_t *w,
-                const WorkPlan &W, hipStream_t s) {
+int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint64_t *d_need,
+                uint8_t *w, const WorkPlan &W, hipStream_t s) {
+  const bool lev = metric == METRIC_LEVENSHTEIN;
   const uint32_t n32 = (uint32_t)n;
   uint64_t *key[2] = {reinterpret_cast<uint64_t *>(w + W.key[0]), reinterpret_cast<uint64_t *>(w + W.key[1])};
   uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(w + W.idx[0]), reinterpret_cast<uint32_t *>(w + W.idx[1])};
@@ -251,12 +306,19 @@ int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t *d_degree, 
   int rc;
   cdr3net_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[0], idx[0]);
   HIP_TRY(hipGetLastError());
-  if ((rc = sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, KEY_BITS, s))) return rc;
-  cdr3net_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[1], idx[1], reinterpret_cast<uint4 *>(w + W.sj), mark);
+  const Sorted S = sorted_view(w, W);
+  uint4 *sj = reinterpret_cast<uint4 *>(w + W.sj);
+  if ((rc = sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, KEY_BITS, s, lev ? (int)LEN_BITS : 0))) return rc;
+  if (lev) cdr3net_gather_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[1], idx[1], sj, mark, S.pres);
+  else cdr3net_gather_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[1], idx[1], sj, mark, nullptr);
   HIP_TRY(hipGetLastError());
   if ((rc = run_heads(cub, mark, bstart, n, s))) return rc;
-  const Sorted S = sorted_view(w, W);
-  cdr3net_walk_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, n32, limit, d_degree, S.deg64, nullptr, nullptr, 0);
+  if (lev)
+    cdr3net_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, n32, limit, d_degree, S.deg64, nullptr,
+                                                                   nullptr, 0, S.pres);
+  else
+    cdr3net_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, n32, limit, d_degree, S.deg64, nullptr,
+                                                                    nullptr, 0, nullptr);
   HIP_TRY(hipGetLastError());
   if ((rc = exclusive_sum(cub, S.deg64, d_adj_off, n, s))) return rc;
   cdr3net_need_kernel<<<1, 64, 0, s>>>(S.deg64, d_adj_off, n32, d_need);
@@ -264,31 +326,28 @@ int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t *d_degree, 
   return DCRX_OK;
 }
 
-int run_write(uint64_t n, uint32_t limit, const uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, uint8_t *w, const WorkPlan &W,
-              hipStream_t s) {
+int run_write(uint64_t n, uint32_t limit, uint32_t metric, const uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, uint8_t *w,
+              const WorkPlan &W, hipStream_t s) {
   const Sorted S = sorted_view(w, W);
-  cdr3net_walk_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, (uint32_t)n, limit, nullptr, nullptr, d_adj_off,
-                                                          d_adj, adj_cap);
+  if (metric == METRIC_LEVENSHTEIN)
+    cdr3net_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, (uint32_t)n, limit, nullptr, nullptr,
+                                                                  d_adj_off, d_adj, adj_cap, S.pres);
+  else
+    cdr3net_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, (uint32_t)n, limit, nullptr, nullptr,
+                                                                   d_adj_off, d_adj, adj_cap, nullptr);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
 
-}  // namespace
+// an error of the entry `who` (the plain entries and their *_metric forms share one body and name themselves)
+int fail(int code, const char *who, const char *what) { return set_err(code, (std::string(who) + ": " + what).c_str()); }
 
-extern "C" {
-
-uint64_t dcrx_cdr3net_work_bytes(uint64_t m, uint64_t text_bytes) {
-  (void)text_bytes;      // (the work space holds per-node keys, ranks and packed strings: the text's bytes do not enter it)
-  WorkPlan W;
-  if (m >= MAX_NODES || plan_work(m, &W) != DCRX_OK) return 0;
-  return W.total;
-}
-
-int dcrx_cdr3_neighbours_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
-                                uint32_t distance, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap,
-                                uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
-  if (m >= MAX_NODES) return set_err(DCRX_E_UNSUPPORTED, "dcrx_cdr3_neighbours_device: 2^30 or more nodes");
-  if (distance != 1 && distance != 2) return set_err(DCRX_E_INVALID, "dcrx_cdr3_neighbours_device: the distance is 1 or 2");
+int neighbours_device(const char *who, uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
+                      uint32_t distance, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap,
+                      uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
+  if (m >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, who, "2^30 or more nodes");
+  if (distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
+  if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
   hipStream_t s = (hipStream_t)hip_stream;
   if (!m) {
     if (d_adj_need) HIP_TRY(hipMemsetAsync(d_adj_need, 0, sizeof(uint64_t), s));
@@ -296,42 +355,44 @@ int dcrx_cdr3_neighbours_device(uint64_t m, const uint32_t *d_class, const uint6
     return DCRX_OK;
   }
   if (!d_class || !d_off || !d_degree || !d_adj_off || !d_work || (text_bytes && !d_text) || (adj_cap && !d_adj))
-    return set_err(DCRX_E_INVALID, "dcrx_cdr3_neighbours_device: null argument");
-  if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_neighbours_device: the work space is not 256-byte aligned");
+    return fail(DCRX_E_INVALID, who, "null argument");
+  if ((uintptr_t)d_work % ALIGN) return fail(DCRX_E_INVALID, who, "the work space is not 256-byte aligned");
   WorkPlan W;
-  int rc = plan_work(m, &W);
+  int rc = plan_work(m, metric, &W);
   if (rc) return rc;
   if (work_bytes < W.total)
-    return set_err(DCRX_E_INVALID, "dcrx_cdr3_neighbours_device: the work space is smaller than dcrx_cdr3net_work_bytes(m, text_bytes)");
+    return fail(DCRX_E_INVALID, who, metric == METRIC_HAMMING ? "the work space is smaller than dcrx_cdr3net_work_bytes(m, text_bytes)"
+                                                              : "the work space is smaller than dcrx_cdr3net_metric_work_bytes(m, text_bytes, metric)");
   const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
   uint8_t *w = static_cast<uint8_t *>(d_work);
-  if ((rc = run_degrees(N, m, distance, d_degree, d_adj_off, d_adj_need, w, W, s))) return rc;
+  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_adj_need, w, W, s))) return rc;
   if (!d_adj || !adj_cap) return DCRX_OK;
-  return run_write(m, distance, d_adj_off, d_adj, adj_cap, w, W, s);
+  return run_write(m, distance, metric, d_adj_off, d_adj, adj_cap, w, W, s);
 }
 
-int64_t dcrx_cdr3_network(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
-                          uint32_t distance, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out, uint32_t *n_nodes_out,
-                          uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap, uint64_t *adj_need_out,
-                          dcrx_cdr3_network_stats_t *stats_out) {
-  if (m >= MAX_NODES) return set_err(DCRX_E_UNSUPPORTED, "dcrx_cdr3_network: 2^30 or more nodes");
-  if (distance != 1 && distance != 2) return set_err(DCRX_E_INVALID, "dcrx_cdr3_network: the distance is 1 or 2");
+int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                uint32_t distance, uint32_t metric, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
+                uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap,
+                uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) {
+  if (m >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, who, "2^30 or more nodes");
+  if (distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
+  if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
   if (stats_out) { *stats_out = dcrx_cdr3_network_stats_t{}; stats_out->nodes_in = m; }
   if (adj_need_out) *adj_need_out = 0;
   if (adj_off_out) adj_off_out[0] = 0;
   if (!m) return 0;
   if (!cls || !off || !weight || !degree_out || !cluster_of_out || !head_out || !n_nodes_out || !weight_out || (adj_cap && !adj_out))
-    return set_err(DCRX_E_INVALID, "dcrx_cdr3_network: null argument");
+    return fail(DCRX_E_INVALID, who, "null argument");
   uint64_t out_of_reach = 0;
   for (uint64_t k = 0; k < m; k++) {
-    if (off[k + 1] < off[k]) return set_err(DCRX_E_INVALID, "dcrx_cdr3_network: offsets go backwards");
+    if (off[k + 1] < off[k]) return fail(DCRX_E_INVALID, who, "offsets go backwards");
     if (!in_reach(off[k + 1] - off[k])) out_of_reach++;
   }
   const uint64_t text0 = off[0], text_bytes = off[m] - text0;
-  if (text_bytes && !text) return set_err(DCRX_E_INVALID, "dcrx_cdr3_network: text is null");
+  if (text_bytes && !text) return fail(DCRX_E_INVALID, who, "text is null");
   const uint32_t m32 = (uint32_t)m;
   WorkPlan W;
-  int rc = plan_work(m, &W);
+  int rc = plan_work(m, metric, &W);
   if (rc) return rc;
   size_t cub_bytes = 0;
   if ((rc = exclusive_sum_bytes<uint32_t>(m, &cub_bytes))) return rc;
@@ -361,13 +422,13 @@ int64_t dcrx_cdr3_network(uint64_t m, const uint32_t *cls, const uint64_t *off, 
   const Nodes N{d_cls, d_off, d_text, text_bytes};
 
   // the degree pass, then an adjacency of exactly the entries it takes
-  if ((rc = run_degrees(N, m, distance, d_degree, d_adj_off, d_need, d_work, W, nullptr))) return rc;
+  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_need, d_work, W, nullptr))) return rc;
   uint64_t need = 0;
   HIP_TRY(hipMemcpy(&need, d_need, sizeof need, hipMemcpyDeviceToHost));
   if (adj_need_out) *adj_need_out = need;
   dcrx::DevBuf<uint32_t> d_adj;
-  if (d_adj.alloc(std::max<uint64_t>(need, 1))) return set_err(DCRX_E_NOMEM, "dcrx_cdr3_network: the adjacency does not fit the device's memory");
-  if (need && (rc = run_write(m, distance, d_adj_off, d_adj, need, d_work, W, nullptr))) return rc;
+  if (d_adj.alloc(std::max<uint64_t>(need, 1))) return fail(DCRX_E_NOMEM, who, "the adjacency does not fit the device's memory");
+  if (need && (rc = run_write(m, distance, metric, d_adj_off, d_adj, need, d_work, W, nullptr))) return rc;
 
   // components: rounds of the neighbourhood's smallest label, then the labels followed to their ends
   cdr3net_label_init_kernel<<<grid_for(m), BLOCK>>>(m32, d_label[0]);
@@ -417,7 +478,18 @@ int64_t dcrx_cdr3_network(uint64_t m, const uint32_t *cls, const uint64_t *off, 
   return (int64_t)c;
 }
 
-namespace {
+// the Levenshtein distance of two byte strings of any length (the edge file's column): a plain two-row table
+uint64_t host_levenshtein(const char *a, uint64_t la, const char *b, uint64_t lb) {
+  std::vector<uint64_t> prev(lb + 1), cur(lb + 1);
+  for (uint64_t j = 0; j <= lb; j++) prev[j] = j;
+  for (uint64_t i = 1; i <= la; i++) {
+    cur[0] = i;
+    for (uint64_t j = 1; j <= lb; j++) cur[j] = std::min({prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (a[i - 1] != b[j - 1] ? 1u : 0u)});
+    prev.swap(cur);
+  }
+  return prev[lb];
+}
+
 struct TextOut {
   char *out;
   uint64_t cap, at = 0;
@@ -430,7 +502,76 @@ struct TextOut {
     put(buf, (uint64_t)snprintf(buf, sizeof buf, "%llu", x));
   }
 };
+
+int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
+                     uint32_t metric, char *out, uint64_t out_cap) {
+  static const char header[] = "a\tb\tdistance\n";
+  if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
+  if (m && (!adj_off || !off || (adj_off[m] && !adj))) return fail(DCRX_E_INVALID, who, "null argument");
+  TextOut T{out, out_cap};
+  T.put(header, sizeof header - 1);
+  for (uint64_t a = 0; a < m; a++) {
+    if (adj_off[a + 1] < adj_off[a]) return fail(DCRX_E_INVALID, who, "adjacency offsets go backwards");
+    for (uint64_t k = adj_off[a]; k < adj_off[a + 1]; k++) {
+      const uint64_t b = adj[k];
+      if (b >= m) return fail(DCRX_E_INVALID, who, "a neighbour outside the nodes");
+      if (b <= a) continue;
+      const uint64_t la = off[a + 1] - off[a], lb = off[b + 1] - off[b];
+      unsigned long long d = 0;
+      if (metric == METRIC_LEVENSHTEIN) {
+        d = host_levenshtein(text + off[a], la, text + off[b], lb);
+      } else {
+        if (la != lb) return fail(DCRX_E_INVALID, who, "an edge between strings of two lengths");
+        for (uint64_t p = 0; p < la; p++) d += text[off[a] + p] != text[off[b] + p];
+      }
+      T.unum(a); T.put("\t", 1); T.unum(b); T.put("\t", 1); T.unum(d); T.put("\n", 1);
+    }
+  }
+  return (int64_t)T.at;
+}
+
 }  // namespace
+
+extern "C" {
+
+uint64_t dcrx_cdr3net_metric_work_bytes(uint64_t m, uint64_t text_bytes, uint32_t metric) {
+  (void)text_bytes;      // (the work space holds per-node keys, ranks and packed strings: the text's bytes do not enter it)
+  WorkPlan W;
+  if (m >= MAX_NODES || !metric_exists(metric) || plan_work(m, metric, &W) != DCRX_OK) return 0;
+  return W.total;
+}
+
+uint64_t dcrx_cdr3net_work_bytes(uint64_t m, uint64_t text_bytes) { return dcrx_cdr3net_metric_work_bytes(m, text_bytes, METRIC_HAMMING); }
+
+int dcrx_cdr3_neighbours_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
+                                uint32_t distance, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap,
+                                uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
+  return neighbours_device("dcrx_cdr3_neighbours_device", m, d_class, d_off, d_text, text_bytes, distance, METRIC_HAMMING, d_degree,
+                           d_adj_off, d_adj, adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
+}
+
+int dcrx_cdr3_neighbours_metric_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
+                                       uint32_t distance, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj,
+                                       uint64_t adj_cap, uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
+  return neighbours_device("dcrx_cdr3_neighbours_metric_device", m, d_class, d_off, d_text, text_bytes, distance, metric, d_degree,
+                           d_adj_off, d_adj, adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
+}
+
+int64_t dcrx_cdr3_network(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                          uint32_t distance, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out, uint32_t *n_nodes_out,
+                          uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap, uint64_t *adj_need_out,
+                          dcrx_cdr3_network_stats_t *stats_out) {
+  return network("dcrx_cdr3_network", m, cls, off, text, weight, distance, METRIC_HAMMING, degree_out, cluster_of_out, head_out,
+                 n_nodes_out, weight_out, adj_off_out, adj_out, adj_cap, adj_need_out, stats_out);
+}
+
+int64_t dcrx_cdr3_network_metric(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                                 uint32_t distance, uint32_t metric, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
+                                 uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap,
+                                 uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) {
+  return network("dcrx_cdr3_network_metric", m, cls, off, text, weight, distance, metric, degree_out, cluster_of_out, head_out,
+                 n_nodes_out, weight_out, adj_off_out, adj_out, adj_cap, adj_need_out, stats_out);
+}
 
 int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint32_t *j_idx, uint32_t n_v, const char *v_calls,
                                   const uint32_t *v_call_off, uint32_t n_j, const char *j_calls, const uint32_t *j_call_off,
@@ -463,24 +604,13 @@ int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint3
 
 int64_t dcrx_format_cdr3_edges(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
                                char *out, uint64_t out_cap) {
-  static const char header[] = "a\tb\tdistance\n";
-  if (m && (!adj_off || !off || (adj_off[m] && !adj))) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_edges: null argument");
-  TextOut T{out, out_cap};
-  T.put(header, sizeof header - 1);
-  for (uint64_t a = 0; a < m; a++) {
-    if (adj_off[a + 1] < adj_off[a]) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_edges: adjacency offsets go backwards");
-    for (uint64_t k = adj_off[a]; k < adj_off[a + 1]; k++) {
-      const uint64_t b = adj[k];
-      if (b >= m) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_edges: a neighbour outside the nodes");
-      if (b <= a) continue;
-      const uint64_t la = off[a + 1] - off[a], lb = off[b + 1] - off[b];
-      if (la != lb) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_edges: an edge between strings of two lengths");
-      unsigned long long d = 0;
-      for (uint64_t p = 0; p < la; p++) d += text[off[a] + p] != text[off[b] + p];
-      T.unum(a); T.put("\t", 1); T.unum(b); T.put("\t", 1); T.unum(d); T.put("\n", 1);
-    }
-  }
-  return (int64_t)T.at;
+  return format_edges("dcrx_format_cdr3_edges", m, adj_off, adj, off, text, METRIC_HAMMING, out, out_cap);
+}
+
+int64_t dcrx_format_cdr3_edges_metric(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
+                                      uint32_t metric, char *out, uint64_t out_cap) {
+  return format_edges("dcrx_format_cdr3_edges_metric", m, adj_off, adj, off, text, metric, out, out_cap);
 }
 
 }  // extern "C"
+

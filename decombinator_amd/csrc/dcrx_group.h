@@ -55,7 +55,8 @@ struct Carver {
 
 // ---- hipCUB: the four calls in use.  A *_bytes query folds the scratch a call over n items wants into `most` (a plan
 // asks for every call it will make and holds the largest); the call itself takes its scratch BY VALUE, as hipCUB
-// overwrites the size it is handed.  Sorts are stable and ascending over the key's bits [0, end_bit); results are in *_out.
+// overwrites the size it is handed.  Sorts are stable and ascending over the key's bits [begin_bit, end_bit), begin_bit 0
+// unless given; results are in *_out.
 // (The scans hand hipCUB plain pointers for input too: it makes its kernels per iterator type, and one set is enough.)
 struct Scratch {
   void *p;
@@ -69,8 +70,8 @@ template <class V> int sort_pairs_bytes(uint64_t n, int end_bit, size_t *most) {
   return DCRX_OK;
 }
 template <class V> int sort_pairs(Scratch t, const uint64_t *key_in, uint64_t *key_out, const V *val_in, V *val_out, uint64_t n,
-                                  int end_bit, hipStream_t s) {
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(t.p, t.bytes, key_in, key_out, val_in, val_out, (int)n, 0, end_bit, s));
+                                  int end_bit, hipStream_t s, int begin_bit = 0) {
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(t.p, t.bytes, key_in, key_out, val_in, val_out, (int)n, begin_bit, end_bit, s));
   return DCRX_OK;
 }
 

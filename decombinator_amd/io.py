@@ -29,7 +29,7 @@ def create_args_dict(
     outpath: str = None, dontsave: bool = False, command: str = None, sampling_analysis: bool = False,
     cluster: bool = False, count_dcrs: bool = False, merge_errors: bool = False, merge_distance: int = 1,
     merge_ratio: int = 10, write_merges: bool = False, clonotypes: bool = False, cdr3_network: bool = False,
-    cdr3_distance: int = 1, cdr3_class: str = "v", write_cdr3_edges: bool = False,
+    cdr3_distance: int = 1, cdr3_class: str = "v", write_cdr3_edges: bool = False, cdr3_metric: str = None,
 ) -> dict:
     """The function-argument dictionary threaded through the stages (the reference's 33 keys, `cluster`: run the
     grouping / clustering half of collapse, writing the `.freq`, and `count_dcrs`: with nobarcoding, count the DCRs on the
@@ -39,7 +39,9 @@ def create_args_dict(
     counted DCRs by (v_call, j_call, junction_aa) on the GPU and writes `<the .tsv's stem>.clonotypes.tsv`; `cdr3_network`:
     with clonotypes, link the clonotypes of one `cdr3_class` (none, v or vj) whose junction_aa have one length and differ in at
     most `cdr3_distance` (1 or 2) residues, on the GPU, and write `.cdr3_clusters.tsv`, with `write_cdr3_edges` also
-    `.cdr3_edges.tsv`.  The defaults v and 1 are a design choice, not a measured optimum)."""
+    `.cdr3_edges.tsv`; `cdr3_metric` levenshtein (None: hamming) also links junction_aa of two lengths, at most
+    `cdr3_distance` substitutions, insertions and deletions apart.  The defaults v and 1 are a design choice, not a measured
+    optimum)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -52,7 +54,7 @@ def create_args_dict(
         dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster,
         count_dcrs=count_dcrs, merge_errors=merge_errors, merge_distance=merge_distance, merge_ratio=merge_ratio,
         write_merges=write_merges, clonotypes=clonotypes, cdr3_network=cdr3_network, cdr3_distance=cdr3_distance,
-        cdr3_class=cdr3_class, write_cdr3_edges=write_cdr3_edges)
+        cdr3_class=cdr3_class, write_cdr3_edges=write_cdr3_edges, cdr3_metric=cdr3_metric)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -125,6 +127,10 @@ def _clonotypes_flag(p: argparse.ArgumentParser):
     p.add_argument("--cdr3-distance", dest="cdr3_distance", type=int, default=None,
                    help="Residues in which two linked CDR3s may differ: 1 (default) or 2.  The default is a design choice, not a "
                         "measured optimum")
+    p.add_argument("--cdr3-metric", dest="cdr3_metric", choices=["hamming", "levenshtein"], default=None,
+                   help="How the residues between two linked CDR3s are counted: hamming (default; substitutions between CDR3s of "
+                        "one length) or levenshtein (substitutions, insertions and deletions: the lengths may differ by up to "
+                        "--cdr3-distance)")
     p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default=None,
                    help="What two linked clonotypes must share beside the CDR3's length: nothing (none), the V call (v, the "
                         "default) or the V and the J call (vj).  The default is a design choice, not a measured optimum")
@@ -190,8 +196,8 @@ def cli_args(argv=None) -> dict:
         inp["merge_ratio"] = 10 if inp["merge_ratio"] is None else inp["merge_ratio"]
     if "cdr3_network" in inp:
         # which of the network's options the command line named (they are refused without --cdr3-network), then the defaults
-        inp["cdr3_options_given"] = [f for f, k in (("--cdr3-distance", "cdr3_distance"), ("--cdr3-class", "cdr3_class"))
-                                     if inp[k] is not None]
+        inp["cdr3_options_given"] = [f for f, k in (("--cdr3-distance", "cdr3_distance"), ("--cdr3-class", "cdr3_class"),
+                                                    ("--cdr3-metric", "cdr3_metric")) if inp[k] is not None]
         inp["cdr3_distance"] = 1 if inp["cdr3_distance"] is None else inp["cdr3_distance"]
         inp["cdr3_class"] = "v" if inp["cdr3_class"] is None else inp["cdr3_class"]
     return inp

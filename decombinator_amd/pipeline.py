@@ -42,6 +42,8 @@ def cdr3_network_refusal(inp: dict):
         return f"--cdr3-distance is 1 or 2, not {inp['cdr3_distance']}"
     if inp.get("cdr3_class", "v") not in ("none", "v", "vj"):
         return f"--cdr3-class is none, v or vj, not {inp['cdr3_class']}"
+    if (inp.get("cdr3_metric") or "hamming") not in ("hamming", "levenshtein"):
+        return f"--cdr3-metric is hamming or levenshtein, not {inp['cdr3_metric']}"
     return None
 
 

@@ -393,6 +393,7 @@ def clonotypes(inputargs: dict, counted: dict | None = None, genes: GeneInfo | N
 cdr3_network_stats: dict = {}          # the statistics of the last cdr3_network() (_native.CDR3_NETWORK_STATS)
 chain_cdr3_network_stats: dict = {}    # ... per chain, for `pipeline -c a,b`
 CDR3_CLASSES = ("none", "v", "vj")
+CDR3_METRICS = ("hamming", "levenshtein")
 
 
 class Cdr3Network:
@@ -400,8 +401,8 @@ class Cdr3Network:
     representatives' V and J genes), the result of _native.cdr3_network and its statistics; text() is the
     `.cdr3_clusters.tsv`'s and edges_text() the `.cdr3_edges.tsv`'s, formatted by libdcrx in one pass."""
 
-    def __init__(self, genes, nodes: dict, result: dict, stats: dict):
-        self.genes, self.nodes, self.result, self.stats = genes, nodes, result, stats
+    def __init__(self, genes, nodes: dict, result: dict, stats: dict, metric: str = "hamming"):
+        self.genes, self.nodes, self.result, self.stats, self.metric = genes, nodes, result, stats, metric
 
     def __len__(self):
         return len(self.nodes["classes"])
@@ -414,7 +415,9 @@ class Cdr3Network:
 
     def edges_text(self) -> bytes:
         from . import _native as nat
-        return nat.format_cdr3_edges(self.nodes["aa_off"], self.nodes["aa_text"], self.result)
+        if self.metric == "hamming":
+            return nat.format_cdr3_edges(self.nodes["aa_off"], self.nodes["aa_text"], self.result)
+        return nat.format_cdr3_edges(self.nodes["aa_off"], self.nodes["aa_text"], self.result, metric=self.metric)
 
 
 def cdr3_nodes(clonotypes: ClonotypeTable, cdr3_class: str = "v") -> dict:
@@ -448,7 +451,8 @@ def cdr3_nodes(clonotypes: ClonotypeTable, cdr3_class: str = "v") -> dict:
 
 def cdr3_network(inputargs: dict, clonotypes: ClonotypeTable) -> Cdr3Network:
     """The CDR3 network of a clonotype table: its rows as nodes (cdr3_nodes, inputargs["cdr3_class"], default v), linked within
-    inputargs["cdr3_distance"] (1 or 2, default 1) substitutions: one call of _native.cdr3_network, with the edges when
+    inputargs["cdr3_distance"] (1 or 2, default 1) substitutions — under inputargs["cdr3_metric"] "levenshtein" (default
+    hamming) substitutions, insertions and deletions —: one call of _native.cdr3_network, with the edges when
     inputargs["write_cdr3_edges"] is set.  Prints the statistics and keeps them in cdr3_network_stats."""
     from . import _native as nat
     global cdr3_network_stats
@@ -456,13 +460,20 @@ def cdr3_network(inputargs: dict, clonotypes: ClonotypeTable) -> Cdr3Network:
     distance = 1 if distance is None else int(distance)
     if distance not in (1, 2):
         raise ValueError(f"--cdr3-distance is 1 or 2, not {distance}")
+    metric = inputargs.get("cdr3_metric") or "hamming"
+    if metric not in CDR3_METRICS:
+        raise ValueError(f"--cdr3-metric is {' or '.join(CDR3_METRICS)}, not {metric}")
     nodes = cdr3_nodes(clonotypes, inputargs.get("cdr3_class") or "v")
     if len(nodes["classes"]) >= nat.CDR3NET_MAX_NODES:
         raise ValueError(f"--cdr3-network takes fewer than {nat.CDR3NET_MAX_NODES:,} clonotypes, not {len(nodes['classes']):,}")
+    # (the keyword goes along only where it says something: what stands in for the native function need not know it)
+    more = {} if metric == "hamming" else {"metric": metric}
     result, stats = nat.cdr3_network(nodes["classes"], nodes["aa_off"], nodes["aa_text"], nodes["weights"], distance,
-                                     want_edges=bool(inputargs.get("write_cdr3_edges")))
+                                     want_edges=bool(inputargs.get("write_cdr3_edges")), **more)
     cdr3_network_stats = stats
+    if metric != "hamming":
+        print(f"CDR3 network metric: {metric} (substitutions, insertions and deletions; linked CDR3s may differ in length)")
     print(f"CDR3 network: {stats['nodes_in']:,} clonotypes in ({stats['out_of_reach']:,} out of reach); {stats['edges']:,} pairs "
           f"within {distance}; {stats['clusters_out']:,} clusters, {stats['singletons']:,} of them single (the largest holds "
           f"{stats['largest_cluster']:,}; at most {stats['largest_degree']:,} neighbours)")
-    return Cdr3Network(clonotypes.genes, nodes, result, stats)
+    return Cdr3Network(clonotypes.genes, nodes, result, stats, metric)

@@ -875,6 +875,53 @@ int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint3
 int64_t dcrx_format_cdr3_edges(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
                                char *out, uint64_t out_cap);
 
+/* ---- the CDR3 network's metric (`--cdr3-metric`): the contract above with a METRIC beside the distance.  The entries only
+ * ADD to ABI 5; the four entries above keep their signatures and behaviour ----
+ *
+ * DCRX_CDR3NET_HAMMING (0): the contract above, and the default.  Every *_metric entry below then gives bit for bit what
+ *   its counterpart above gives.
+ * DCRX_CDR3NET_LEVENSHTEIN (1): CDR3 junctions are made by deleting germline ends and inserting nucleotides, so two related
+ *   clonotypes differ by a gained or lost residue as often as by a substituted one.  Under this metric:
+ * In reach: unchanged, 1 <= len(s_i) <= DCRX_CDR3NET_MAX_LEN (32).  A node out of reach has no neighbours.
+ * Edge: {i, j}, i != j, where both nodes are in reach, c_i == c_j, |len(s_i) - len(s_j)| <= D and the Levenshtein distance
+ *   of the bytes is <= D (D = 1 or 2).  Substitution, insertion and deletion cost 1 each.  Bytes are compared as they are:
+ *   a real 0x00 byte is a symbol like any other and never matches the padding behind a shorter string.  Distance 0 is an
+ *   edge.
+ * Output, statistics, limits and error codes: unchanged — degree, the CSR with every node's neighbours' ranks ascending,
+ *   cluster_of, cluster rows by head ascending, dcrx_cdr3_network_stats_t.  The result is a function of the input alone.
+ * Any other metric is DCRX_E_INVALID.
+ * The steps under DCRX_CDR3NET_LEVENSHTEIN: the bucket is the class alone — the stable sort of (key, rank) runs over the
+ *   key's class bits and its out-of-reach bit only, so a class stays in rank order and the sorted keys keep every node's
+ *   length —, a 32-bit letter-presence mask (bit byte & 31) is gathered beside every packed string, and the walk's pair test
+ *   is: equal class, lengths at most D apart, presence masks at most 2 D bits apart (a filter: one substitution moves two of
+ *   those bits at most, one insertion or deletion one), then an exact register-only edit-distance test (furthest-reaching
+ *   rows on the 2 D + 1 diagonals, csrc/dcrx_cdr3net_core.h), which a lane runs on the entry it has waiting once some lane
+ *   of its wave meets its next one, so that many lanes run it together. */
+#define DCRX_CDR3NET_HAMMING 0
+#define DCRX_CDR3NET_LEVENSHTEIN 1
+
+/* dcrx_cdr3net_work_bytes for a metric (the Levenshtein walk keeps a presence mask per node beside what the Hamming walk
+ * keeps); 0 for m >= 2^30 and for a metric that does not exist. */
+uint64_t dcrx_cdr3net_metric_work_bytes(uint64_t m, uint64_t text_bytes, uint32_t metric);
+
+/* dcrx_cdr3_neighbours_device under `metric`: the same arguments, rules and errors; d_work takes
+ * dcrx_cdr3net_metric_work_bytes(m, text_bytes, metric) bytes. */
+int dcrx_cdr3_neighbours_metric_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text,
+                                       uint64_t text_bytes, uint32_t distance, uint32_t metric, uint32_t *d_degree,
+                                       uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, uint64_t *d_adj_need, void *d_work,
+                                       uint64_t work_bytes, void *hip_stream);
+
+/* dcrx_cdr3_network under `metric`: the same arguments, rules and errors. */
+int64_t dcrx_cdr3_network_metric(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                                 uint32_t distance, uint32_t metric, uint32_t *degree_out, uint32_t *cluster_of_out,
+                                 uint32_t *head_out, uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out,
+                                 uint32_t *adj_out, uint64_t adj_cap, uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out);
+
+/* dcrx_format_cdr3_edges under `metric`: with DCRX_CDR3NET_LEVENSHTEIN the distance column is the Levenshtein distance of the
+ * two strings, computed here on the host (a plain two-row table), and an edge between strings of two lengths is not refused. */
+int64_t dcrx_format_cdr3_edges_metric(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off,
+                                      const char *text, uint32_t metric, char *out, uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
