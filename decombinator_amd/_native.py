@@ -415,6 +415,21 @@ class Cdr3NetworkStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CDR3_NETWORK_STATS]
 
 
+OVERLAP_MAX_SAMPLES = 64       # DCRX_OVERLAP_MAX_SAMPLES
+OVERLAP_MAX_ROWS = 1 << 30     # dcrx_overlap_run: DCRX_E_UNSUPPORTED from here on
+OVERLAP_PLANES = ("shared", "shared_weight", "min_weight", "prod_lo", "prod_hi")      # enum dcrx_overlap_plane
+OVERLAP_STATS = ("rows_in", "groups", "private_groups", "shared_groups", "in_all_samples", "largest_n_samples", "public_rows",
+                 "public_cells")
+OVERLAP_PUBLIC_COLUMNS = ["v_call", "j_call", "junction_aa", "n_samples", "duplicate_count"]      # then one column per sample
+OVERLAP_PAIR_COLUMNS = ["sample_a", "sample_b", "clonotypes_a", "clonotypes_b", "shared_clonotypes", "reads_a", "reads_b",
+                        "shared_reads_a", "shared_reads_b", "min_reads", "jaccard", "overlap_coefficient", "bray_curtis",
+                        "morisita_horn"]
+
+
+class OverlapStatsC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in OVERLAP_STATS]
+
+
 # dcrx_clono_row_t: what dcrx_cdr3_device leaves of an entry (flags: productive, in_frame, stop, conserved_c, conserved_f from bit 0)
 CLONO_ROW_DTYPE = np.dtype([("hash", "<u8"), ("arena_off", "<u8"), ("start_cdr3", "<i4"), ("end_cdr3", "<i4"), ("seq_len", "<u4"),
                             ("status", "u1"), ("flags", "u1"), ("pad", "<u2")])
@@ -445,6 +460,8 @@ EXPORTS = [
     "dcrx_cdr3net_work_bytes", "dcrx_cdr3_neighbours_device", "dcrx_cdr3_network", "dcrx_format_cdr3_clusters",
     "dcrx_format_cdr3_edges",
     "dcrx_cdr3net_metric_work_bytes", "dcrx_cdr3_neighbours_metric_device", "dcrx_cdr3_network_metric", "dcrx_format_cdr3_edges_metric",
+    "dcrx_overlap_set_hash_bits", "dcrx_overlap_run", "dcrx_overlap_destroy", "dcrx_overlap_info", "dcrx_overlap_export",
+    "dcrx_overlap_pairs_device", "dcrx_format_overlap_public",
 ]
 
 _lib = None
@@ -587,6 +604,14 @@ def lib():
         "dcrx_cdr3_network_metric": (C.c_int64, [u64, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, u64, vp,
                                                  C.POINTER(Cdr3NetworkStatsC)]),
         "dcrx_format_cdr3_edges_metric": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, u64]),
+        "dcrx_overlap_set_hash_bits": (i32, [u32]),
+        "dcrx_overlap_run": (vp, [u32, u64, vp, vp, vp, vp, vp, u32, C.POINTER(i32)]),
+        "dcrx_overlap_destroy": (None, [vp]),
+        "dcrx_overlap_info": (i32, [vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(OverlapStatsC)]),
+        "dcrx_overlap_export": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dcrx_overlap_pairs_device": (i32, [u64, vp, vp, vp, u32, vp, vp]),
+        "dcrx_format_overlap_public": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, u32, vp, vp, u32, vp, vp, vp,
+                                                   vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1428,6 +1453,84 @@ def format_cdr3_edges(aa_off, aa_text: bytes, result: dict, metric="hamming") ->
     need = check(int(fmt(*args, None, 0)))
     out = _uninitialised_bytes(max(1, need))
     check(int(fmt(*args, _bytes_address(out), need)))
+    return bytes(out[:need])
+
+
+# ---- overlap (the `overlap` sub-command): include/dcrx.h "overlap" ----
+
+def overlap_set_hash_bits(bits: int):
+    """dcrx_overlap_set_hash_bits: the bits of the key hash the grouping sorts by (tests; the result does not depend on it)."""
+    check(lib().dcrx_overlap_set_hash_bits(int(bits)))
+
+
+def overlap(samples, classes, off, text: bytes, weights, n_samples: int, min_samples: int = 2):
+    """dcrx_overlap_run on the current device, and everything it exports: m rows (sample, class, string =
+    text[off[i]:off[i + 1]], weight) of n_samples samples grouped by (class, string) -> (result, statistics dict over
+    OVERLAP_STATS, with "rows_per_sample" beside them).
+    result: per plane of OVERLAP_PLANES an (n_samples, n_samples) uint64 array; group_of per row (groups numbered by their
+    first row); per public row (n_samples >= min_samples; n_samples descending, weight descending, head ascending) head,
+    n_samples and weight, and the rows' cells as CSR: cell_off, cell_sample (ascending in a row), cell_weight."""
+    smp = np.ascontiguousarray(samples, dtype=np.uint32)
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    o, t = _node_arrays(off, text)
+    m, S = len(smp), int(n_samples)
+    if len(cls) != m or len(w) != m or len(o) != m + 1:
+        raise ValueError("overlap: one sample, one class and one weight per row, m + 1 offsets")
+    err = C.c_int(0)
+    h = lib().dcrx_overlap_run(S, m, smp.ctypes.data, cls.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data, int(min_samples),
+                               C.byref(err))
+    if not h:
+        check(err.value if err.value < 0 else -1)
+    try:
+        n_pub, n_cells, st = C.c_uint64(0), C.c_uint64(0), OverlapStatsC()
+        check(lib().dcrx_overlap_info(h, None, None, C.byref(n_pub), C.byref(n_cells), C.byref(st)))
+        P, Q = n_pub.value, n_cells.value
+        planes = np.zeros((len(OVERLAP_PLANES), S, S), np.uint64)
+        group_of, per_sample = np.zeros(max(m, 1), np.uint32), np.zeros(S, np.uint64)
+        head, ns, cs = np.zeros(max(P, 1), np.uint32), np.zeros(max(P, 1), np.uint32), np.zeros(max(Q, 1), np.uint32)
+        wt, coff, cw = np.zeros(max(P, 1), np.uint64), np.zeros(P + 1, np.uint64), np.zeros(max(Q, 1), np.uint64)
+        check(lib().dcrx_overlap_export(h, planes.ctypes.data, group_of.ctypes.data, per_sample.ctypes.data, head.ctypes.data,
+                                        ns.ctypes.data, wt.ctypes.data, coff.ctypes.data, cs.ctypes.data, cw.ctypes.data))
+    finally:
+        lib().dcrx_overlap_destroy(h)
+    result = {name: planes[k] for k, name in enumerate(OVERLAP_PLANES)}
+    result.update(group_of=group_of[:m], head=head[:P], n_samples=ns[:P], weight=wt[:P], cell_off=coff, cell_sample=cs[:Q],
+                  cell_weight=cw[:Q])
+    stats = {k: int(getattr(st, k)) for k in OVERLAP_STATS}
+    stats["rows_per_sample"] = [int(x) for x in per_sample]
+    return result, stats
+
+
+def overlap_pairs_device(n_groups: int, d_cell_off, d_cell_sample, d_cell_weight, n_samples: int, d_planes, stream=None):
+    """dcrx_overlap_pairs_device: the pair accumulation alone over cells in HBM (DeviceBuffers: n_groups + 1 uint32 offsets,
+    uint32 samples and weights), ADDED onto d_planes (len(OVERLAP_PLANES) x S x S uint64), asynchronous on `stream`."""
+    check(lib().dcrx_overlap_pairs_device(int(n_groups), d_cell_off.ptr, d_cell_sample.ptr, d_cell_weight.ptr, int(n_samples),
+                                          d_planes.ptr, stream))
+
+
+def format_overlap_public(result: dict, sample_names, v_idx, j_idx, v_calls, j_calls, off, text: bytes) -> bytes:
+    """dcrx_format_overlap_public: the `overlap_public.tsv` text of an overlap result — per public row the calls
+    v_calls[v_idx[head]] and j_calls[j_idx[head]], the head row's string, n_samples, weight, and per sample its cell's weight
+    or 0."""
+    vi, ji = (np.ascontiguousarray(a, dtype=np.uint32) if len(a) else np.zeros(1, np.uint32) for a in (v_idx, j_idx))
+    o, t = _node_arrays(off, text)
+    (vc, vo), (jc, jo) = _calls_blob(v_calls), _calls_blob(j_calls)
+    names = [x.encode("utf-8", "surrogateescape") for x in sample_names]      # (file names: whatever the file system holds)
+    so = np.zeros(len(names) + 1, dtype=np.uint32)
+    so[1:] = np.cumsum([len(b) for b in names])
+    sc = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
+    P = len(result["head"])
+    u32 = [np.ascontiguousarray(result[k], dtype=np.uint32) if len(result[k]) else np.zeros(1, np.uint32)
+           for k in ("head", "n_samples", "cell_sample")]
+    u64 = [np.ascontiguousarray(result[k], dtype=np.uint64) if len(result[k]) else np.zeros(1, np.uint64)
+           for k in ("weight", "cell_off", "cell_weight")]
+    args = [P, u32[0].ctypes.data, u32[1].ctypes.data, u64[0].ctypes.data, u64[1].ctypes.data, u32[2].ctypes.data, u64[2].ctypes.data,
+            len(sample_names), sc.ctypes.data, so.ctypes.data, len(o) - 1, vi.ctypes.data, ji.ctypes.data, len(v_calls), vc.ctypes.data,
+            vo.ctypes.data, len(j_calls), jc.ctypes.data, jo.ctypes.data, o.ctypes.data, t.ctypes.data]
+    need = check(int(lib().dcrx_format_overlap_public(*args, None, 0)))
+    out = _uninitialised_bytes(max(1, need))
+    check(int(lib().dcrx_format_overlap_public(*args, _bytes_address(out), need)))
     return bytes(out[:need])
 
 

@@ -155,6 +155,21 @@ def _merge_flags(p: argparse.ArgumentParser):
                         "count, its root's key")
 
 
+def _overlap(p: argparse.ArgumentParser):
+    p.add_argument("-in", "--infile", type=str, nargs="+", required=True,
+                   help="1 to 64 .clonotypes.tsv files (plain or .gz), one per sample; a sample is named by its file name "
+                        "without .clonotypes.tsv[.gz]")
+    p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
+    p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
+    p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
+    p.add_argument("--overlap-key", dest="overlap_key", choices=["vj", "v", "none"], default="vj",
+                   help="What two rows must share beside the CDR3 amino acids to be one clonotype: the V and the J call (vj, "
+                        "the default), the V call (v) or nothing (none)")
+    p.add_argument("--min-samples", dest="min_samples", type=int, default=2,
+                   help="A clonotype is written to overlap_public.tsv when at least this many samples hold it (1 .. the number "
+                        "of files; default 2)")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -183,6 +198,9 @@ def create_parser() -> argparse.ArgumentParser:
     tr.add_argument("-tfdir", "--tagfastadir", type=str, default="Decombinator-Tags-FASTAs")
     tr.add_argument("-nbc", "--nobarcoding", action="store_true")
     _count_flag(tr); _clonotypes_flag(tr)
+    ov = sub.add_parser("overlap", help="clonotype sharing between samples (GPU): per pair of .clonotypes.tsv files what they "
+                                        "share (overlap_pairs.tsv), and the clonotypes several samples hold (overlap_public.tsv)")
+    _overlap(ov)
     return parser
 
 
@@ -323,6 +341,23 @@ def _write_beside_tsv(text: bytes, suffix: str, what: str, inputargs: dict):
     if not inputargs["dontgzip"]:
         from . import _native as nat
         print(f"Compressing {what} output file to", outfilename + ".gz")
+        with nat.GzipWriter(outfilename + ".gz", level=int(os.environ.get("DCRX_GZIP_LEVEL", "6"))) as gz:
+            gz.write(text)
+        outfilename += ".gz"
+    else:
+        with open(outfilename, "wb") as fh:
+            fh.write(text)
+    sort_permissions(outfilename)
+    return outfilename
+
+
+def write_out_overlap(text: bytes, name: str, inputargs: dict):
+    """A file of the `overlap` sub-command: `<outpath><prefix><name>` (overlap_pairs.tsv, overlap_public.tsv), with
+    write_out_clonotypes' rules: gzipped unless dontgzip, mode 666.  Returns the file's name."""
+    outfilename = (inputargs.get("outpath") or "") + (inputargs.get("prefix") or "") + name
+    if not inputargs.get("dontgzip"):
+        from . import _native as nat
+        print("Compressing overlap output file to", outfilename + ".gz")
         with nat.GzipWriter(outfilename + ".gz", level=int(os.environ.get("DCRX_GZIP_LEVEL", "6"))) as gz:
             gz.write(text)
         outfilename += ".gz"

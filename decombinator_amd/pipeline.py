@@ -162,6 +162,14 @@ def _after_decombine(data, inp, start):
 
 def main(argv=None):
     inp = cli_args(argv)
+    if inp["command"] == "overlap":     # a stage of its own: it reads clonotype tables, not reads
+        from . import overlap
+        try:
+            overlap.run(inp)
+        except ValueError as e:
+            from .io import create_parser
+            create_parser().error(str(e))
+        return
     if inp.get("clonotypes"):           # refused before anything is read
         why = clonotype_refusal(inp)
         if why:

@@ -922,6 +922,111 @@ int64_t dcrx_cdr3_network_metric(uint64_t m, const uint32_t *cls, const uint64_t
 int64_t dcrx_format_cdr3_edges_metric(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off,
                                       const char *text, uint32_t metric, char *out, uint64_t out_cap);
 
+/* ---- overlap (`overlap`): which clonotypes several samples share, and how alike two repertoires are, on the GPU.  The
+ * reference has no counterpart: the contract below is this library's own.  The entries only ADD to ABI 5 ----
+ *
+ * This layer knows nothing about genes or files: it works on ROWS, which the caller makes out of clonotype tables.
+ * Input: S samples, 1 <= S <= DCRX_OVERLAP_MAX_SAMPLES (64: a design choice — a group's cells then take six key bits, a
+ *   lane walks at most 63 later cells, and the pair kernel's per-block planes fit 64 KB of LDS); m rows, m < 2^30 — row i has
+ *   rank i — with, per row, a sample (uint32 < S), a class (uint32), a string (bytes of any length, 0 included, given as
+ *   m + 1 offsets into one text) and a weight (uint64).  A sample may have no row.
+ * Key: (class, bytes), compared in full.  Bytes are compared as they are, and the length is part of the key ("CASS" is not
+ *   "CASSL").  A 64-bit hash only puts candidates next to each other; dcrx_overlap_set_hash_bits is the test knob, and the
+ *   result does not depend on it.
+ * Group: the rows with one key.  Its head is its row of the smallest rank; groups are numbered by head ascending, and
+ *   group_of[i] is row i's group.
+ * Cell: (group, sample), with weight = the sum of that sample's rows in the group (several rows of one sample may share a
+ *   key; they add).  Every row weight and every cell weight must be < 2^32 (DCRX_E_UNSUPPORTED otherwise; a cell sum that
+ *   crosses the limit is found on the device by a flag that travels with the copy-back of the number of cells).  A group's
+ *   n_samples is its number of cells.
+ * Matrices: DCRX_OVERLAP_PLANES planes of S x S uint64, plane p's value at (a, b) at planes[(p * S + a) * S + b].  Every
+ *   value is an exact integer and a function of the input alone.  For a != b the sums run over the groups that have a cell in
+ *   both a (weight w_a) and b (weight w_b):
+ *     DCRX_OVERLAP_SHARED         the number of such groups            (a, a): the sample's groups
+ *     DCRX_OVERLAP_SHARED_WEIGHT  sum of w_a (not symmetric)           (a, a): the sample's reads X_a
+ *     DCRX_OVERLAP_MIN_WEIGHT     sum of min(w_a, w_b)                 (a, a): X_a
+ *     DCRX_OVERLAP_PROD_LO        sum of (w_a w_b mod 2^32)            (a, a): the same of w_a^2
+ *     DCRX_OVERLAP_PROD_HI        sum of (w_a w_b >> 32)               (a, a): the same of w_a^2
+ *   A product fits 64 bits because cells are < 2^32, and each half-sum stays < 2^62 because there are fewer than 2^30 groups:
+ *   the caller composes prod_hi * 2^32 + prod_lo as a big integer (it may pass 2^64).
+ * Public rows: the groups with n_samples >= min_samples (>= 1), ordered by three stable sorts from the least to the most
+ *   significant key: head ascending, total weight descending, n_samples descending.  Each row carries head, n_samples,
+ *   weight (the sum of its cells) and its cells as CSR: cell_off (rows + 1), cell_sample ascending, cell_weight.
+ * Statistics: dcrx_overlap_stats_t and the rows per sample; nothing that depends on the algorithm is in there. */
+#define DCRX_OVERLAP_MAX_SAMPLES 64
+enum dcrx_overlap_plane {
+  DCRX_OVERLAP_SHARED = 0,
+  DCRX_OVERLAP_SHARED_WEIGHT = 1,
+  DCRX_OVERLAP_MIN_WEIGHT = 2,
+  DCRX_OVERLAP_PROD_LO = 3,
+  DCRX_OVERLAP_PROD_HI = 4,
+  DCRX_OVERLAP_PLANES = 5
+};
+typedef struct dcrx_overlap_stats {
+  uint64_t rows_in;
+  uint64_t groups;
+  uint64_t private_groups;        /* groups of one sample */
+  uint64_t shared_groups;         /* groups of two samples or more */
+  uint64_t in_all_samples;        /* groups with a cell in every one of the S samples */
+  uint64_t largest_n_samples;
+  uint64_t public_rows;
+  uint64_t public_cells;
+} dcrx_overlap_stats_t;
+typedef struct dcrx_overlap dcrx_overlap_t;
+
+/* How many bits of the 64-bit key hash the grouping sorts by, 0 .. 64 (default 64; process wide, for tests: with 0 bits
+ * every row is a candidate of every other and there are as many rounds of full compares as distinct keys).  DCRX_E_INVALID
+ * above 64. */
+int dcrx_overlap_set_hash_bits(uint32_t bits);
+
+/* The whole step on host arrays, synchronous on the current device, run ONCE whatever is exported afterwards: the rows are
+ * uploaded; overlap_keys_kernel hashes (class, bytes); a stable radix sort of (hash, rank), run heads, and rounds of full-key
+ * compares against the first active row of every run (one round in practice) give the groups; a stable sort of
+ * (group, sample) over at most 36 bits, run heads and integer atomics whose results are not read give the cells, compacted in
+ * order; dcrx_overlap_pairs_device gives the planes; flag, compaction, the stable sorts and a gather give the public rows.
+ * Returns the result, to be released with dcrx_overlap_destroy, or NULL with the dcrx_error in *error_out (may be NULL) and
+ * its text in dcrx_last_error(): DCRX_E_INVALID for S of 0 or above DCRX_OVERLAP_MAX_SAMPLES, a sample id >= S, offsets that
+ * go backwards, min_samples of 0 or a null argument; DCRX_E_UNSUPPORTED for m >= 2^30 and for a row or cell weight >= 2^32;
+ * DCRX_E_NOMEM as elsewhere.  m == 0 is a result without groups (and touches no device). */
+dcrx_overlap_t *dcrx_overlap_run(uint32_t n_samples, uint64_t m, const uint32_t *sample, const uint32_t *cls,
+                                 const uint64_t *off, const char *text, const uint64_t *weight, uint32_t min_samples,
+                                 int *error_out);
+void dcrx_overlap_destroy(dcrx_overlap_t *overlap);
+/* Sizes (samples, rows, public rows, public cells) and statistics; any pointer may be NULL. */
+int dcrx_overlap_info(const dcrx_overlap_t *overlap, uint32_t *n_samples, uint64_t *n_rows, uint64_t *n_public,
+                      uint64_t *n_public_cells, dcrx_overlap_stats_t *stats);
+/* Into the caller's arrays, any of which may be NULL: planes (DCRX_OVERLAP_PLANES x S x S), group_of (rows),
+ * rows_per_sample (S), the public rows' head, n_samples and weight (public rows each), cell_off (public rows + 1),
+ * cell_sample and cell_weight (public cells each). */
+int dcrx_overlap_export(const dcrx_overlap_t *overlap, uint64_t *planes, uint32_t *group_of, uint64_t *rows_per_sample,
+                        uint32_t *head, uint32_t *n_samples, uint64_t *weight, uint64_t *cell_off, uint32_t *cell_sample,
+                        uint64_t *cell_weight);
+
+/* The primitive — the pair accumulation alone —, asynchronous on `hip_stream`, all arrays in device memory: cells in group
+ * order (group g's are d_cell_off[g] .. d_cell_off[g + 1]; n_groups + 1 offsets, fewer than 2^30 cells), samples ascending
+ * inside a group and < n_samples, weights < 2^32.  ADDS onto d_planes (DCRX_OVERLAP_PLANES x S x S uint64), which the caller
+ * has zeroed (or not: what is there stays under the sums).  One lane per cell adds its diagonal terms and walks the later
+ * cells of its own group (adjacent, at most 63; a group may straddle a block boundary: the walk reads global memory), adding
+ * the five terms of each pair to the block's planes in LDS; one flush per block follows, by global 64-bit atomic adds whose
+ * results are not read.  The planes are taken in two launches (shared + shared_weight + min_weight, then the two product
+ * planes), the symmetric ones kept as triangles, so that a block's LDS stays under 64 KB at 64 samples; a group of one cell
+ * costs its diagonal update and no walk.  DCRX_E_INVALID for n_samples of 0 or above DCRX_OVERLAP_MAX_SAMPLES or a null
+ * argument, DCRX_E_UNSUPPORTED for 2^30 groups or more. */
+int dcrx_overlap_pairs_device(uint64_t n_groups, const uint32_t *d_cell_off, const uint32_t *d_cell_sample,
+                              const uint32_t *d_cell_weight, uint32_t n_samples, uint64_t *d_planes, void *hip_stream);
+
+/* The `overlap_public.tsv` text of n_public rows in one pass: the header "v_call j_call junction_aa n_samples
+ * duplicate_count" followed by one column per sample (its name), then per row the calls of its head row (v_idx / j_idx of
+ * the m input rows into calls tables: one text, n + 1 offsets), the head row's string, n_samples, weight and per sample the
+ * cell's weight or 0, tab separated.  Returns the bytes the text takes; writes it when out != NULL and it fits out_cap.
+ * Host only. */
+int64_t dcrx_format_overlap_public(uint64_t n_public, const uint32_t *head, const uint32_t *n_samples, const uint64_t *weight,
+                                   const uint64_t *cell_off, const uint32_t *cell_sample, const uint64_t *cell_weight,
+                                   uint32_t n_sample_names, const char *sample_names, const uint32_t *sample_name_off,
+                                   uint64_t m, const uint32_t *v_idx, const uint32_t *j_idx, uint32_t n_v, const char *v_calls,
+                                   const uint32_t *v_call_off, uint32_t n_j, const char *j_calls, const uint32_t *j_call_off,
+                                   const uint64_t *off, const char *text, char *out, uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
