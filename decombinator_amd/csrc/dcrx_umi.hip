@@ -29,23 +29,7 @@ namespace {
 constexpr int TILE = DCRX_UMI_TILE;
 constexpr int RW = DCRX_UMI_REC_WORDS;
 static_assert(RW == 16, "a record is four 16-byte loads");
-
-// Whole-tile lower bound: the smallest distance any pair of the two tiles can have by length and composition.
-__device__ __forceinline__ bool tiles_may_match(const uint32_t *ta, const uint32_t *tb, int32_t k) {
-  const int32_t gap_len = max((int32_t)tb[0] - (int32_t)ta[1], (int32_t)ta[0] - (int32_t)tb[1]);
-  if (gap_len > k) return false;
-  int32_t gap = 0;
-#pragma unroll
-  for (int w = 0; w < 2; w++) {
-    const uint32_t amin = ta[2 + w], amax = ta[4 + w], bmin = tb[2 + w], bmax = tb[4 + w];
-#pragma unroll
-    for (int s = 0; s < 32; s += 8) {
-      const int32_t a0 = (amin >> s) & 255, a1 = (amax >> s) & 255, b0 = (bmin >> s) & 255, b1 = (bmax >> s) & 255;
-      gap += max(0, max(b0 - a1, a0 - b1));
-    }
-  }
-  return gap <= 2 * k;
-}
+static_assert(UMI_MAX_LEN == DCRX_UMI_MAX_LEN, "clamp_k clamps to the longest UMI");
 
 __global__ __launch_bounds__(TILE) void umi_pairs_kernel(const uint32_t *__restrict__ recs, const uint32_t *__restrict__ tiles,
                                                          uint32_t n_tiles, int32_t k, unsigned long long *__restrict__ pairs,
@@ -184,6 +168,7 @@ extern "C" int64_t dcrx_umi_encode(const char *ascii, const uint64_t *offsets, u
 extern "C" int dcrx_umi_neighbours_device(const uint32_t *d_recs, const uint32_t *d_tiles, uint64_t n_tiles, int32_t k,
                                           uint64_t *d_pairs, uint64_t pair_cap, uint64_t *d_total, void *hip_stream) {
   if (k < 0) return set_err(DCRX_E_INVALID, "dcrx_umi_neighbours_device: k < 0");
+  k = clamp_k(k);                                                             // the same pairs, and 2 * k stays an int32
   if (!d_total || (n_tiles && (!d_recs || !d_tiles)) || (pair_cap && !d_pairs))
     return set_err(DCRX_E_INVALID, "dcrx_umi_neighbours_device: null argument");
   if (n_tiles > 0xffffffffull / TILE) return set_err(DCRX_E_UNSUPPORTED, "dcrx_umi_neighbours_device: too many tiles");
@@ -201,6 +186,7 @@ extern "C" int dcrx_umi_neighbours_device(const uint32_t *d_recs, const uint32_t
 extern "C" int64_t dcrx_umi_neighbours(const char *ascii, const uint64_t *offsets, uint64_t n, int32_t k, uint64_t *pairs,
                                        uint64_t pair_cap) {
   if (k < 0) return set_err(DCRX_E_INVALID, "dcrx_umi_neighbours: k < 0");
+  k = clamp_k(k);
   if (pair_cap && !pairs) return set_err(DCRX_E_INVALID, "dcrx_umi_neighbours: pairs is null");
   const int64_t n_tiles = dcrx_umi_encode(ascii, offsets, n, nullptr, nullptr);
   if (n_tiles < 0) return n_tiles;

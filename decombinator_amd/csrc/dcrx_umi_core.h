@@ -1,5 +1,6 @@
-// dcrx_umi_core.h — the per-pair decision of the UMI neighbour search (dcrx_umi.hip), shared by the kernel and a plain
-// host build (tests/host_umi): is levenshtein(a, b) <= k for two UMIs of at most DCRX_UMI_MAX_LEN symbols?
+// dcrx_umi_core.h — the decisions of the UMI neighbour search (dcrx_umi.hip), shared by the kernel and a plain host build
+// (tests/host_umi): can two tiles hold a pair within k (tiles_may_match), and is levenshtein(a, b) <= k for two UMIs of at
+// most DCRX_UMI_MAX_LEN symbols (pair_distance)?
 //
 // A record (DCRX_UMI_REC_WORDS words) holds one UMI as the kernel needs it on both sides of a pair:
 //   [0..7]   Peq: bit p of word s is set when symbol p is s (the pattern side of Myers' algorithm)
@@ -66,6 +67,35 @@ DCRX_UMI_HD int32_t myers(const uint32_t *peq, uint32_t m, uint32_t c0, uint32_t
     if (score - (int32_t)(n - 1 - t) > k) return k + 1;
   }
   return score;
+}
+
+// No two UMIs are farther apart than UMI_MAX_LEN edits, so a larger k asks for the same pairs: both entries of the search
+// clamp k on the way in, and every int32 expression in k below (2 * k, k + 1) stays in range.
+enum { UMI_MAX_LEN = 24 };
+DCRX_UMI_HD int32_t clamp_k(int32_t k) { return k > UMI_MAX_LEN ? (int32_t)UMI_MAX_LEN : k; }
+
+DCRX_UMI_HD int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
+
+// Whole-tile lower bound: the smallest distance any pair of the two tiles can have by length and composition.  ta, tb: tile
+// summaries (min length, max length, composition minima[2], maxima[2]).  k <= UMI_MAX_LEN (clamp_k).
+DCRX_UMI_HD bool tiles_may_match(const uint32_t *ta, const uint32_t *tb, int32_t k) {
+  const int32_t gap_len = imax((int32_t)tb[0] - (int32_t)ta[1], (int32_t)ta[0] - (int32_t)tb[1]);
+  if (gap_len > k) return false;
+  int32_t gap = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int w = 0; w < 2; w++) {
+    const uint32_t amin = ta[2 + w], amax = ta[4 + w], bmin = tb[2 + w], bmax = tb[4 + w];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int s = 0; s < 32; s += 8) {
+      const int32_t a0 = (amin >> s) & 255, a1 = (amax >> s) & 255, b0 = (bmin >> s) & 255, b1 = (bmax >> s) & 255;
+      gap += imax(0, imax(b0 - a1, a0 - b1));
+    }
+  }
+  return gap <= 2 * k;
 }
 
 // The whole decision on two records, as the kernel takes it (b is the pattern, a the text).

@@ -587,7 +587,8 @@ int dcrx_gzip_close(void *writer);
  *
  * Limits: a UMI is at most DCRX_UMI_MAX_LEN bytes (what dcrx_collapse_row_t.barcode holds) and one call sees at most
  * DCRX_UMI_MAX_SYMBOLS distinct byte values (A, C, G, T, N, and the S / L of set_barcode fit); beyond either the call
- * returns DCRX_E_UNSUPPORTED.  Any k >= 0. */
+ * returns DCRX_E_UNSUPPORTED.  Any k >= 0: a k above DCRX_UMI_MAX_LEN is taken as DCRX_UMI_MAX_LEN on entry (no two UMIs
+ * are farther apart, so the pairs are the same), which keeps the search's int32 arithmetic in k in range. */
 #define DCRX_UMI_MAX_LEN 24
 #define DCRX_UMI_MAX_SYMBOLS 8
 #define DCRX_UMI_TILE 256

@@ -1,6 +1,7 @@
 """Helpers of the stage-2 collapse tests (test_collapse_cluster.py, test_gpu_collapse_cluster.py): an independent neighbour
 search (plain Levenshtein DP, no code shared with the kernel) and the fixture cases of tests/golden/collapse_cluster.json
 (made by tests/golden_gen/gen_collapse_cluster.py from the reference's own collapsinator)."""
+import functools
 import gzip
 import hashlib
 import json
@@ -67,8 +68,8 @@ def brute_neighbours(umis, k):
     if n < 2:
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
     alphabet = sorted(set("".join(umis))) or ["A"]
-    comp = np.array([[u.count(c) for c in alphabet] for u in umis], dtype=np.int32).reshape(n, len(alphabet))
-    lens = np.array([len(u) for u in umis], dtype=np.int32)
+    comp = np.array([[u.count(c) for c in alphabet] for u in umis], dtype=np.int64).reshape(n, len(alphabet))
+    lens = np.array([len(u) for u in umis], dtype=np.int64)
     ci, cj = [], []
     for i in range(n - 1):
         j = np.arange(i + 1, n)
@@ -220,3 +221,124 @@ def symdel_neighbours(umis, k):
         e = min(len(cand), s + 200000)
         keep[s:e] = lev_many([umis[x] for x in ci[s:e].tolist()], [umis[x] for x in cj[s:e].tolist()]) <= k
     return ci[keep], cj[keep]
+
+
+# ---- constructed UMI lists for the neighbour search (dcrx_umi.hip): each one puts a mechanism of the kernel's tile walk on
+# the spot (test_collapse_cluster.py on the host, test_gpu_collapse_cluster.py on the device).  Every list comes shuffled
+# with a fixed seed, so original indices differ from sorted positions. ----
+
+UMI_SYMBOLS = "ACGTNSL\xff"
+UMI_TILE = 256
+K_HUGE = (2 ** 30, 2 ** 31 - 1)
+
+
+def _shuffled(umis, seed):
+    umis = list(umis)
+    random.Random(seed).shuffle(umis)
+    return umis
+
+
+@functools.lru_cache(maxsize=None)
+def umi_all_pairs_list():
+    """600 distinct UMIs of lengths 0-24 (the empty one among them) over eight byte values: three tiles (256, 256, 88); at
+    k = 24 every pair is a neighbour, so every ballot of a full wave has 64 hits."""
+    rng = random.Random(600)
+    seen = {"": None}
+    while len(seen) < 600:
+        seen["".join(rng.choice(UMI_SYMBOLS) for _ in range(rng.randrange(1, 25)))] = None
+    return tuple(_shuffled(seen, 601))
+
+
+@functools.lru_cache(maxsize=None)
+def umi_ball_list():
+    """A 24-mer over the eight symbols and its 168 single substitutions: at k = 2 all 14 196 pairs, at k = 1 the 168 with
+    the centre and the 24 * 21 that share a position."""
+    rng = random.Random(24)
+    centre = list(UMI_SYMBOLS * 3)
+    rng.shuffle(centre)
+    out = ["".join(centre)]
+    for p in range(24):
+        out += ["".join(centre[:p] + [c] + centre[p + 1:]) for c in UMI_SYMBOLS if c != centre[p]]
+    return tuple(_shuffled(out, 25))
+
+
+@functools.lru_cache(maxsize=None)
+def umi_family_list(n=1300, seed=9):
+    """Families with the length limits in them: base lengths from {0, 1, 2, 11, 12, 13, 23, 24}, members by substitutions
+    (N included), insertions, deletions and exact repeats; not distinct.  The first n of the generator's list, shuffled."""
+    rng = random.Random(seed)
+    out = []
+    while len(out) < n:
+        base = "".join(rng.choice("ACGT") for _ in range(rng.choice([0, 1, 2, 11, 11, 12, 12, 12, 13, 13, 23, 23, 24, 24, 24])))
+        fam = [base]
+        for _ in range(rng.choice([0, 1, 2, 4, 6])):
+            s = list(rng.choice(fam))
+            for _ in range(rng.randrange(0, 3)):                    # no edit at all: an exact repeat
+                op = rng.randrange(4)
+                if op < 2 and s:
+                    s[rng.randrange(len(s))] = rng.choice("ACGTN")
+                elif op == 2 and len(s) < 24:
+                    s.insert(rng.randrange(len(s) + 1), rng.choice("ACGT"))
+                elif s:
+                    del s[rng.randrange(len(s))]
+            fam.append("".join(s))
+        out += fam
+    return tuple(_shuffled(out[:n], seed + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def umi_reach_len_list(k):
+    """256 distinct 10-mers, the same with k symbols appended, and 256 unrelated 24-mers: tiles 0 and 1 are k apart in length
+    and 256 pairs at distance k cross them."""
+    rng = random.Random(100 + k)
+    short = {}
+    while len(short) < 256:
+        short[rnd(rng, 10)] = None
+    far = {}
+    while len(far) < 256:
+        far[rnd(rng, 24)] = None
+    return tuple(_shuffled(list(short) + [u + rnd(rng, k) for u in short] + list(far), 110 + k))
+
+
+@functools.lru_cache(maxsize=None)
+def umi_reach_comp_list(k):
+    """256 distinct 12-mers of one composition (3 each of A, C, G, T) and the same with their first k A's turned into N, a
+    symbol the first group lacks: two tiles of one length, 2k apart in composition (k fewer A, k more N), and 256 pairs at
+    distance k cross them.  The first element is fixed (symbol codes follow first appearance: A, C, G, T, then N)."""
+    rng = random.Random(200 + k)
+    first = "AAACCCGGGTTT"
+    plain = {first: None}
+    while len(plain) < 256:
+        s = list(first)
+        rng.shuffle(s)
+        plain["".join(s)] = None
+    rest = _shuffled(list(plain)[1:] + [u.replace("A", "N", k) for u in plain], 210 + k)
+    return tuple([first] + rest)
+
+
+TILE_EDGE_N = (2, 255, 256, 257, 511, 512, 513)
+TILE_EDGE_SEED = 9
+
+
+def umi_constructed_cases():
+    """(name, list, the k values its GPU test runs) of every constructed list."""
+    cases = [("all_pairs", umi_all_pairs_list(), (24,) + K_HUGE), ("ball", umi_ball_list(), (1, 2)),
+             ("families", umi_family_list(), (0, 1, 2, 3))]
+    cases += [(f"families_{n}", umi_family_list(n, TILE_EDGE_SEED), (2,)) for n in TILE_EDGE_N]
+    cases += [(f"reach_len_{k}", umi_reach_len_list(k), (k,)) for k in (1, 2)]
+    cases += [(f"reach_comp_{k}", umi_reach_comp_list(k), (k,)) for k in (1, 2)]
+    return cases
+
+
+@functools.lru_cache(maxsize=None)
+def brute_keys(umis, k):
+    """brute_neighbours of a constructed list (a tuple) as sorted uint64 keys (i << 32 | j); computed once per (list, k).
+    No two strings of at most 24 symbols are more than 24 edits apart, so a k above 24 has the pairs of k = 24."""
+    assert max(len(u) for u in umis) <= 24
+    if k > 24:
+        return brute_keys(umis, 24)
+    r, c = brute_neighbours(list(umis), k)
+    keys = (r.astype(np.uint64) << np.uint64(32)) | c.astype(np.uint64)
+    keys.sort()
+    keys.setflags(write=False)
+    return keys

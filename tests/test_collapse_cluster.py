@@ -1,7 +1,9 @@
 """Stage 2 of `collapse` (--cluster) on the CPU: grouping, the protoseq test, the components and the counting are libdcrx's
 host code and Python; the UMI neighbour search (a HIP kernel) is replaced by an independent brute force here
 (tests/collapse_cluster_util.py), the pattern of test_host_stage.py's _oracle_device.  Expected outputs come from the
-reference's own collapsinator (tests/golden/collapse_cluster.json) and its TINY `.freq` files (tests/golden/tiny_freq.json)."""
+reference's own collapsinator (tests/golden/collapse_cluster.json) and its TINY `.freq` files (tests/golden/tiny_freq.json).
+The search itself is checked here as far as a host can: dcrx_umi_encode's layout, and the kernel's tile rule, walk order and
+pair function (dcrx_umi_core.h built by g++, tests/host_umi) against the brute force on constructed UMI lists."""
 import json
 import os
 import random
@@ -150,6 +152,10 @@ def _host_umi_lib():
     L = C.CDLL(os.path.join(d, "build", "libumi_host.so"))
     L.umi_host_pair_distance.restype = C.c_int32
     L.umi_host_pair_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.umi_host_tiles_may_match.restype = C.c_int
+    L.umi_host_tiles_may_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.umi_host_walk.restype = C.c_uint64
+    L.umi_host_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64]
     return L
 
 
@@ -189,6 +195,185 @@ def test_kernel_pair_function_on_host_matches_dp():
             assert d == want
         n_checked += 1
     assert n_checked == 100000
+
+
+def test_kernel_pair_function_at_the_length_limits():
+    """The same check where the lengths end: an empty UMI on either side, 24 symbols on both, and eight distinct byte values
+    with \\x00 and \\xff among them (bit 23 of Myers' word, symbol code 7)."""
+    L = _host_umi_lib()
+    rng = random.Random(13)
+    syms = "\x00ACGTN\xffS"
+    full = ["".join(rng.choice(syms) for _ in range(24)) for _ in range(150)]
+    umis = [""]
+    for base in full:
+        umis.append(base)
+        for _ in range(3):                                            # still 24 long: substitutions only
+            s = list(base)
+            for _ in range(rng.randrange(1, 5)):
+                s[rng.randrange(24)] = rng.choice(syms)
+            umis.append("".join(s))
+        s = list(base)                                                # and a shifted one: a deletion and an insertion
+        del s[rng.randrange(24)]
+        s.insert(rng.randrange(24), rng.choice(syms))
+        umis.append("".join(s))
+    umis += ["".join(rng.choice(syms) for _ in range(n)) for n in (1, 1, 2, 2, 3, 4, 23, 23) for _ in range(4)]
+    assert len(set("".join(umis))) == 8
+    recs, _ = nat.umi_encode(umis)
+    where = {}
+    for r in recs[:len(umis)]:
+        where[int(r[14])] = np.ascontiguousarray(r)
+    empty = umis.index("")
+    pairs = [(empty, j) for j in range(len(umis))] + [(j, empty) for j in range(len(umis))]
+    n24 = [i for i, u in enumerate(umis) if len(u) == 24]
+    pairs += [(rng.choice(n24), rng.choice(n24)) for _ in range(4000)]
+    pairs += [(i, min(len(umis) - 1, i + d)) for i in n24 for d in range(5)]               # family members
+    seen = {"empty": 0, "full": 0, "full_near": 0}
+    for i, j in pairs:
+        want = cu.lev(umis[i], umis[j])
+        for k in (0, 1, 2, 3, 4, 23, 24, 25):
+            d = L.umi_host_pair_distance(where[i].ctypes.data, where[j].ctypes.data, k)
+            assert (d <= k) == (want <= k), (umis[i], umis[j], k, d, want)
+            if want <= k:
+                assert d == want
+        seen["empty"] += not (umis[i] and umis[j])
+        seen["full"] += len(umis[i]) == 24 == len(umis[j])
+        seen["full_near"] += len(umis[i]) == 24 == len(umis[j]) and 0 < want <= 4
+    assert seen["empty"] > 1000 and seen["full"] > 4000 and seen["full_near"] > 300
+
+
+# ---- the search around the pair function: dcrx_umi_encode's layout, the whole-tile skip rule and the upper-triangle walk,
+# on the constructed lists of collapse_cluster_util (the lists the GPU tests give the kernel) ----
+
+UMI_CASES = cu.umi_constructed_cases()
+UMI_IDS = [c[0] for c in UMI_CASES]
+
+
+def _check_encode_layout(umis):
+    n = len(umis)
+    recs, tiles = nat.umi_encode(list(umis))
+    n_tiles = (n + 255) // 256
+    assert recs.shape == (n_tiles * 256, 16) and tiles.shape == (n_tiles, 8)
+    assert sorted(recs[:n, 14].tolist()) == list(range(n))                                 # every index once
+    comp = recs[:, 12:14].copy().view(np.uint8).reshape(-1, 8).astype(np.int64)          # byte s = count of symbol s
+    lens = recs[:, 11].astype(np.int64)
+    for s in range(n):                                                                      # each record is its UMI
+        u = umis[int(recs[s, 14])]
+        assert lens[s] == len(u) and comp[s].sum() == len(u)
+        assert sorted(c for c in comp[s].tolist() if c) == sorted(u.count(c) for c in set(u))
+    order = [(int(lens[s]),) + tuple(comp[s].tolist()) for s in range(n)]
+    assert order == sorted(order)                                                           # (length, composition)
+    assert not recs[n:].any()                                                               # padding of the last tile
+    for t in range(n_tiles):
+        lo, hi = t * 256, min(n, t * 256 + 256)
+        assert tiles[t, 6] == hi - lo and tiles[t, 7] == 0
+        assert tiles[t, 0] == lens[lo:hi].min() and tiles[t, 1] == lens[lo:hi].max()
+        assert tiles[t, 2:4].copy().view(np.uint8).tolist() == comp[lo:hi].min(axis=0).tolist()
+        assert tiles[t, 4:6].copy().view(np.uint8).tolist() == comp[lo:hi].max(axis=0).tolist()
+
+
+@pytest.mark.parametrize("name,umis,ks", UMI_CASES, ids=UMI_IDS)
+def test_umi_encode_layout_on_constructed_lists(name, umis, ks):
+    _check_encode_layout(umis)
+
+
+@pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 511, 512, 513])
+def test_umi_encode_layout_on_random_lists(n):
+    rng = random.Random(n)
+    _check_encode_layout(["".join(rng.choice(cu.UMI_SYMBOLS) for _ in range(rng.randrange(0, 25))) for _ in range(n)])
+
+
+def _tile_of_index(recs, n):
+    tile_of = np.zeros(n, dtype=np.int64)
+    tile_of[recs[:n, 14]] = np.arange(n) // 256
+    return tile_of
+
+
+def _rejected(L, tiles, k):
+    t = np.ascontiguousarray(tiles)
+    return {(a, b) for a in range(len(t)) for b in range(a, len(t))
+            if not L.umi_host_tiles_may_match(t[a].ctypes.data, t[b].ctypes.data, k)}
+
+
+@pytest.mark.parametrize("name,umis,ks", UMI_CASES, ids=UMI_IDS)
+def test_tile_skip_rule_is_sound(name, umis, ks):
+    """No tile pair the rule rejects holds a pair of the brute force (one UMI in each tile), at k = 0, 1, 2, 3, 24."""
+    L = _host_umi_lib()
+    recs, tiles = nat.umi_encode(list(umis))
+    tile_of = _tile_of_index(recs, len(umis))
+    for k in (0, 1, 2, 3, 24):
+        rejected = _rejected(L, tiles, k)
+        if name in ("all_pairs", "families") and k <= 2:
+            assert rejected                        # lengths 0 to 24 in one list: the first and the last tile are out of reach
+        if not rejected:
+            continue                               # (nothing to be wrong about; at k = 24 that is every list)
+        keys = cu.brute_keys(umis, k)
+        ti, tj = tile_of[(keys >> np.uint64(32)).astype(np.int64)], tile_of[(keys & np.uint64(0xFFFFFFFF)).astype(np.int64)]
+        crossed = set(zip(np.minimum(ti, tj).tolist(), np.maximum(ti, tj).tolist()))
+        assert not (crossed & rejected), (k, sorted(crossed & rejected))
+
+
+def _reach_len_layout(umis, k):
+    """What the by-length list is for, from the encode output and the brute force: tiles 0 and 1 each of one length, exactly k
+    apart, and at least 256 expected pairs with one UMI in each."""
+    recs, tiles = nat.umi_encode(list(umis))
+    assert tiles[0, 0] == tiles[0, 1] == 10 and tiles[1, 0] == tiles[1, 1] == 10 + k and tiles[0, 6] == tiles[1, 6] == 256
+    _crossing(umis, k, recs, 256)
+    return tiles
+
+
+def _reach_comp_layout(umis, k):
+    """The by-composition list: the first element fixes the symbol codes (A, C, G, T = 0..3, N = 4), both tiles hold 12-mers
+    only, their composition summaries are 2k apart in L1 (k in A, k in N), and at least 256 expected pairs cross them."""
+    assert umis[0] == "AAACCCGGGTTT"
+    recs, tiles = nat.umi_encode(list(umis))
+    assert len(tiles) == 2 and (tiles[:, 0:2] == 12).all() and (tiles[:, 6] == 256).all()
+    mn, mx = tiles[:, 2:4].copy().view(np.uint8).reshape(2, 8).astype(int), tiles[:, 4:6].copy().view(np.uint8).reshape(2, 8).astype(int)
+    assert (mn == mx).all()                                                                 # one composition per tile
+    assert mn[0].tolist() == [3 - k, 3, 3, 3, k, 0, 0, 0] and mn[1].tolist() == [3, 3, 3, 3, 0, 0, 0, 0]
+    assert np.abs(mn[0] - mn[1]).sum() == 2 * k
+    _crossing(umis, k, recs, 256)
+    return tiles
+
+
+def _crossing(umis, k, recs, at_least):
+    tile_of = _tile_of_index(recs, len(umis))
+    keys = cu.brute_keys(umis, k)
+    ti, tj = tile_of[(keys >> np.uint64(32)).astype(np.int64)], tile_of[(keys & np.uint64(0xFFFFFFFF)).astype(np.int64)]
+    assert int(((np.minimum(ti, tj) == 0) & (np.maximum(ti, tj) == 1)).sum()) >= at_least
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_tile_skip_rule_accepts_tiles_exactly_at_reach(k):
+    """Length gap = k, composition gap = 2k: in reach, and out of reach at k - 1."""
+    L = _host_umi_lib()
+    for tiles in (_reach_len_layout(cu.umi_reach_len_list(k), k), _reach_comp_layout(cu.umi_reach_comp_list(k), k)):
+        t = np.ascontiguousarray(tiles)
+        assert L.umi_host_tiles_may_match(t[0].ctypes.data, t[1].ctypes.data, k)
+        assert L.umi_host_tiles_may_match(t[1].ctypes.data, t[0].ctypes.data, k)
+        assert not L.umi_host_tiles_may_match(t[0].ctypes.data, t[1].ctypes.data, k - 1)
+
+
+@pytest.mark.parametrize("name,umis,ks", UMI_CASES, ids=UMI_IDS)
+def test_host_walk_equals_brute_force(name, umis, ks):
+    """dcrx_umi_encode, the tile rule, the upper-triangle walk and the pair function together (tests/host_umi's plain loop
+    over the kernel's iteration space) against the brute force, key for key.  k = 2^30 and 2^31 - 1 ask for every pair, as
+    k = 24 does: 2 * k must not wrap."""
+    L = _host_umi_lib()
+    recs, tiles = nat.umi_encode(list(umis))
+    recs, tiles = np.ascontiguousarray(recs), np.ascontiguousarray(tiles)
+    for k in ks:
+        want = cu.brute_keys(umis, k)
+        if k in cu.K_HUGE:
+            assert len(want) == len(umis) * (len(umis) - 1) // 2
+        out = np.zeros(len(want) + 8, dtype=np.uint64)
+        total = L.umi_host_walk(recs.ctypes.data, tiles.ctypes.data, len(tiles), k, out.ctypes.data, len(out))
+        assert total == len(want), (k, total, len(want))
+        got = np.sort(out[:total])
+        assert (got == want).all(), k
+        # too little room: the count is the same and nothing is written past it
+        small = np.full(7 + 4, 0xDEAD, dtype=np.uint64)
+        assert L.umi_host_walk(recs.ctypes.data, tiles.ctypes.data, len(tiles), k, small.ctypes.data, 7) == total
+        assert (small[7:] == 0xDEAD).all()
 
 
 def test_umi_limits_are_errors_not_aborts():

@@ -72,6 +72,105 @@ def test_kernel_small_inputs():
     assert keys.tolist() == [(i << 32) | j for i in range(4) for j in range(i + 1, 4)]
 
 
+# ---- constructed lists (collapse_cluster_util): each compared in full with the brute force ----
+
+def _check_keys(umis, k, **kw):
+    want = cu.brute_keys(umis, k)
+    got = nat.umi_neighbours_keys(list(umis), k, **kw)
+    assert len(got) == len(want), (k, len(got), len(want))
+    assert (got == want).all()
+    return want
+
+
+@pytest.mark.parametrize("k", [24, 2 ** 30, 2 ** 31 - 1])
+def test_all_pairs_full_ballots(k):
+    """Every pair is a hit: 64-lane ballots, four waves of a diagonal tile, three tiles, and more pairs than the first
+    call's room.  A k far beyond every length asks for the same pairs."""
+    umis = cu.umi_all_pairs_list()
+    assert len(umis) == 600 and "" in umis and len(set(umis)) == 600 and set("".join(umis)) == set(cu.UMI_SYMBOLS)
+    assert {len(u) for u in umis} == set(range(25))
+    want = _check_keys(umis, k)
+    assert len(want) == 600 * 599 // 2 == 179700 > 4 * 600 + 1024
+
+
+@pytest.mark.parametrize("k,n_pairs", [(2, 14196), (1, 168 + 24 * 21)])
+def test_one_substitution_ball(k, n_pairs):
+    umis = cu.umi_ball_list()
+    assert len(set(umis)) == 169 and {len(u) for u in umis} == {24} and set("".join(umis)) == set(cu.UMI_SYMBOLS)
+    assert len(_check_keys(umis, k)) == n_pairs
+
+
+@pytest.mark.parametrize("k", [0, 1, 2, 3])
+def test_families_with_repeats_and_length_limits(k):
+    umis = cu.umi_family_list()
+    assert len(umis) == 1300 and {0, 1, 2, 11, 12, 13, 23, 24} <= {len(u) for u in umis} and "N" in "".join(umis)
+    want = _check_keys(umis, k)
+    if k == 0:                                    # exactly the repeated strings
+        by_text = {}
+        for i, u in enumerate(umis):
+            by_text.setdefault(u, []).append(i)
+        repeats = sorted((a << 32) | b for g in by_text.values() for x, a in enumerate(g) for b in g[x + 1:])
+        assert want.tolist() == repeats
+        assert 0 < len(want) < len(cu.brute_keys(umis, 1))
+
+
+@pytest.mark.parametrize("n", cu.TILE_EDGE_N)
+def test_tile_edges(n):
+    umis = cu.umi_family_list(n, cu.TILE_EDGE_SEED)
+    assert len(umis) == n
+    want = _check_keys(umis, 2)
+    if n % 256 == 1:                              # the last tile holds one record, and an expected pair ends in it
+        recs, tiles = nat.umi_encode(list(umis))
+        assert tiles[-1, 6] == 1
+        alone = int(recs[(len(tiles) - 1) * 256, 14])
+        assert ((want >> np.uint64(32)) == alone).any() or ((want & np.uint64(0xFFFFFFFF)) == alone).any()
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_tiles_exactly_at_reach_by_length(k):
+    umis = cu.umi_reach_len_list(k)
+    tcc._reach_len_layout(umis, k)
+    _check_keys(umis, k)
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_tiles_exactly_at_reach_by_composition(k):
+    umis = cu.umi_reach_comp_list(k)
+    tcc._reach_comp_layout(umis, k)
+    _check_keys(umis, k)
+
+
+SENTINEL = 0xA5A5A5A5A5A5A5A5
+
+
+@pytest.mark.parametrize("cap", [0, 7, 14196, None], ids=["cap0", "cap7", "cap14196", "null"])
+def test_neighbours_device_on_a_stream_of_the_callers_with_too_little_room(cap):
+    """dcrx_umi_neighbours_device on a stream of the caller's: *d_total is the number found whatever the room, the first
+    min(cap, total) words are distinct expected keys, nothing is written from word `cap` on, and a second call on the same
+    buffers counts from zero again.  cap None: pair_cap = 0 with a null d_pairs.  The buffer has room for every pair and 64
+    words more, all holding a sentinel; the words checked are all of those from `cap` on, the 64 past it among them."""
+    umis = cu.umi_ball_list()
+    want = cu.brute_keys(umis, 2)
+    total = len(want)
+    assert total == 14196
+    recs, tiles = nat.umi_encode(list(umis))
+    d_recs, d_tiles = nat.DeviceBuffer.from_host(recs), nat.DeviceBuffer.from_host(tiles)
+    d_total = nat.DeviceBuffer.from_host(np.full(1, 12345, dtype=np.uint64))            # not zero: the call zeroes it
+    room = total + 64
+    d_pairs = nat.DeviceBuffer.from_host(np.full(room, SENTINEL, dtype=np.uint64))
+    s = nat.Stream()
+    for _ in range(2):
+        nat.check(nat.lib().dcrx_umi_neighbours_device(d_recs.ptr, d_tiles.ptr, len(tiles), 2, None if cap is None else d_pairs.ptr,
+                                                       cap or 0, d_total.ptr, s.ptr))
+        s.synchronize()
+        assert int(d_total.to_host(np.uint64, 1)[0]) == total
+        words = d_pairs.to_host(np.uint64, room)
+        n_written = min(cap or 0, total)
+        assert (words[n_written:] == SENTINEL).all()
+        got = words[:n_written]
+        assert len(np.unique(got)) == n_written and np.isin(got, want).all()
+
+
 @pytest.mark.parametrize("case", cu.cases(), ids=[c["params"]["name"] for c in cu.cases()])
 def test_fixture_case_on_device(case, tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
