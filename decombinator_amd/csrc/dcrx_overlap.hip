@@ -206,16 +206,7 @@ __global__ __launch_bounds__(BLOCK) void overlap_public_cells_kernel(const uint3
 
 // ---- the pair kernel ----
 
-// the smallest g in [lo, hi] with off[g] > c (off ascending; off[hi] > c is the caller's)
-__device__ __forceinline__ uint32_t first_above(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t c) {
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (off[mid] > c) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
+// (first_above and group_end, a lane's look-ups, are dcrx_overlap_core.h's: the host walk of tests/host_overlap shares them)
 template <int SMAX, int PART>
 __global__ __launch_bounds__(BLOCK) void overlap_pairs_kernel(const uint32_t *__restrict__ cell_off, uint32_t n_groups,
                                                               const uint32_t *__restrict__ cell_sample,
@@ -244,14 +235,7 @@ __global__ __launch_bounds__(BLOCK) void overlap_pairs_kernel(const uint32_t *__
     ends[t] = cell_off[min(g_first + 1 + t, n_groups)];
     __syncthreads();
     if (c >= n_cells) continue;
-    uint32_t k = 0;      // the first staged end above c
-    for (uint32_t hi = BLOCK; k < hi;) {
-      const uint32_t mid = k + (hi - k) / 2;
-      if (ends[mid] > c) hi = mid;
-      else k = mid + 1;
-    }
-    uint32_t end = k < (uint32_t)BLOCK ? ends[k] : cell_off[first_above(cell_off, min(g_first + 1 + (uint32_t)BLOCK, n_groups), n_groups, c)];
-    end = min(min(end, n_cells), c + MAX_SAMPLES);      // (a group has at most 64 cells: a walk never runs away on bad offsets)
+    const uint32_t end = group_end(ends, BLOCK, cell_off, g_first, n_groups, n_cells, c);
     const uint32_t a = cell_sample[c];
     if (a >= S) continue;                               // (outside the contract: never outside the planes)
     const unsigned long long wa = cell_weight[c];

@@ -5,6 +5,7 @@
 // and the full compare of two keys (class, length, then every byte as it is).
 // Per pair of cells: the 32/32 split of the product of two weights < 2^32, and where a pair of samples lies in a plane:
 // a full S x S plane is row major, a symmetric plane is kept as a triangle with its diagonal.
+// Per cell of the pair kernel: the lane's look-ups of where its group ends.
 #pragma once
 #include <stdint.h>
 
@@ -64,5 +65,35 @@ DCRX_OVERLAP_HD uint32_t tri_size(uint32_t S) { return S * (S + 1) / 2; }
 
 // the sort key of a row's cell: (group, sample), 36 bits at most
 DCRX_OVERLAP_HD uint64_t cell_key(uint32_t group, uint32_t sample) { return ((uint64_t)group << SAMPLE_BITS) | sample; }
+
+// ---- the pair kernel's look-ups (a lane's; tests/host_overlap walks the cells with them) ----
+
+DCRX_OVERLAP_HD uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+// the smallest g in [lo, hi] with off[g] > c (off ascending; off[hi] > c is the caller's)
+DCRX_OVERLAP_HD uint32_t first_above(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t c) {
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (off[mid] > c) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+// where the walk of cell c stops: the end of c's group.  ends[k] = cell_off[min(g_first + 1 + k, n_groups)], k < n_ends, are
+// the tile's staged ends (g_first: the group of the tile's first cell); a lane whose group's end is not among them — behind
+// empty groups — searches cell_off from the first group that is not staged.  Never past n_cells nor past c + MAX_SAMPLES (a
+// group has at most 64 cells: a walk never runs away on bad offsets).
+DCRX_OVERLAP_HD uint32_t group_end(const uint32_t *ends, uint32_t n_ends, const uint32_t *__restrict__ cell_off, uint32_t g_first,
+                                   uint32_t n_groups, uint32_t n_cells, uint32_t c) {
+  uint32_t k = 0;      // the first staged end above c
+  for (uint32_t hi = n_ends; k < hi;) {
+    const uint32_t mid = k + (hi - k) / 2;
+    if (ends[mid] > c) hi = mid;
+    else k = mid + 1;
+  }
+  const uint32_t end = k < n_ends ? ends[k] : cell_off[first_above(cell_off, min_u32(g_first + 1 + n_ends, n_groups), n_groups, c)];
+  return min_u32(min_u32(end, n_cells), c + MAX_SAMPLES);
+}
 
 }  // namespace dcrx_ovl

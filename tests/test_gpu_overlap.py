@@ -2,7 +2,10 @@
 (ou.expected_overlap) — the five planes, group_of, the public rows with their cells and the statistics, exactly, and the
 invariants on every case — on degenerate sizes, two-sample extremes, duplicates in a sample, key identity, every setting of the
 hash knob, limits, weights that need both product halves, the public rows' order and random tables; the pairs primitive on
-crafted cells across the block boundary; and the sub-command end to end."""
+crafted cells across the block boundary and on constructed cells (every plane size, blocks of several tiles, the group-end
+look-up behind empty groups, full groups across tile edges, weights at the limit, a stream of the caller's, many blocks onto
+one entry); the host entry on constructed tables (block edges, larger random tables, three hash bits at scale, a cell summed
+over a thousand rows); and the sub-command end to end."""
 import gzip
 import os
 import random
@@ -20,12 +23,13 @@ pytestmark = pytest.mark.gpu
 E_INVALID, E_UNSUPPORTED = -1, -2
 
 
-def _check(samples, classes, strings, S, weights=None, min_samples=2):
-    """The native result against the contract (and the invariants on both); returns the expected (result, stats)."""
+def _check(samples, classes, strings, S, weights=None, min_samples=2, want=None):
+    """The native result against the contract (and the invariants on both); returns the expected (result, stats).
+    want: ou.expected_overlap of the same arguments, where the caller has asserted a premise on it already."""
     w = [1 + (7 * k) % 13 for k in range(len(strings))] if weights is None else weights
     off, text = ou.row_text(strings)
     got = nat.overlap(samples, classes, off, text, w, S, min_samples)
-    want = ou.expected_overlap(samples, classes, strings, w, S, min_samples)
+    want = ou.expected_overlap(samples, classes, strings, w, S, min_samples) if want is None else want
     ou.assert_same(got, want, w)
     return want
 
@@ -114,19 +118,27 @@ def test_hash_bits_do_not_enter_the_result():
 
 # ---- 6. the pairs primitive on crafted cells ----
 
-def _pairs(groups, S, start=None):
+def _pairs(groups, S, start=None, stream=None, times=1, want=None):
+    """The primitive over crafted cells against ou.expected_planes, every entry: `times` calls in a row on `stream` (a
+    nat.Stream; None: the null stream) with ONE synchronisation after the last, onto `start`.  want: expected_planes(groups, S)
+    where the caller has it already."""
     off, smp, wt = ou.cells_of_groups(groups)
     planes = np.zeros((5, S, S), np.uint64) if start is None else np.array(start, dtype=np.uint64)
     bufs = [nat.DeviceBuffer.from_host(a) for a in (off, smp, wt, planes)]
     try:
-        nat.overlap_pairs_device(len(groups), bufs[0], bufs[1], bufs[2], S, bufs[3])
-        nat.synchronize()
+        for _ in range(times):
+            nat.overlap_pairs_device(len(groups), bufs[0], bufs[1], bufs[2], S, bufs[3], None if stream is None else stream.ptr)
+        if stream is None:
+            nat.synchronize()
+        else:
+            stream.synchronize()
         got = bufs[3].to_host(np.uint64, 5 * S * S).reshape(5, S, S)
     finally:
         for b in bufs:
             b.free()
-    want = ou.expected_planes(groups, S, None if start is None else [[[int(x) for x in r] for r in p] for p in start])
-    assert [int(x) for x in got.reshape(-1)] == [x for p in want for r in p for x in r]
+    want = ou.expected_planes(groups, S) if want is None else want
+    onto = [0] * (5 * S * S) if start is None else [int(x) for x in np.asarray(start).reshape(-1)]
+    assert [int(x) for x in got.reshape(-1)] == [o + times * x for o, x in zip(onto, (x for p in want for r in p for x in r))]
     return got
 
 
@@ -153,6 +165,123 @@ def test_pairs_add_onto_what_is_there_and_skip_empty_groups():
         with pytest.raises(nat.DcrxError) as e:
             nat.check(nat.lib().dcrx_overlap_pairs_device(1, None, None, None, S, None, None))
         assert e.value.code == E_INVALID
+
+
+# ---- 6b. the pairs primitive on constructed cells (tests/overlap_util.py: the lists, and the premise each list is for —
+# asserted on the list and the Python reference before the device call; tests/test_overlap.py walks the same lists on the
+# host).  The kernel's tile is ou.PAIR_BLOCK = 256 cells and its grid ou.PAIR_GRID = 2048 blocks at most. ----
+
+@pytest.mark.parametrize("S", ou.PLANE_SIZES)
+def test_pairs_every_plane_size(S):
+    """Both sides of 8 | 9, 16 | 17 and 32 | 33 and the ends 1, 63, 64: every SMAX, PART 0 and PART 1, with the last sample in
+    the triangle's last row and the full plane's last row and column."""
+    groups, _, want = ou.constructed(f"plane_size_{S}")
+    ou.premise_plane_size(groups, S, want)
+    _pairs(groups, S, want=want)
+
+
+def test_pairs_blocks_that_take_several_tiles():
+    """More than PAIR_GRID tiles: blocks 0, 1 and 2 take a second tile, stage its ends again and go on adding to their planes."""
+    groups, S, want = ou.constructed("several_tiles")
+    ou.premise_several_tiles(groups, S, want)
+    _pairs(groups, S, want=want)
+
+
+@pytest.mark.parametrize("name", ou.LOOKUP_NAMES)
+def test_pairs_group_end_look_up(name):
+    """A group's end in the last staged slot (254 empty groups), behind it (255, 256: the search over cell_off), the same in a
+    third tile (g_first > 0), empty groups that lead and that trail, and a tile of 256 single-cell groups."""
+    groups, S, want = ou.constructed("lookup_" + name)
+    ou.premise_lookup(name, groups)
+    _pairs(groups, S, want=want)
+
+
+@pytest.mark.parametrize("front", ou.TILE_EDGE_FRONTS)
+def test_pairs_full_group_across_a_tile_edge(front):
+    groups, S, want = ou.constructed(f"tile_edge_{front}")
+    ou.premise_tile_edge(front, groups)
+    _pairs(groups, S, want=want)
+
+
+def test_pairs_full_groups_across_many_tile_edges():
+    groups, S, want = ou.constructed("tile_edge_long")
+    ou.premise_tile_edge_long(groups)
+    _pairs(groups, S, want=want)
+
+
+def test_pairs_weights_at_the_limit_in_full_groups():
+    groups, S, want = ou.constructed("limit_weights")
+    ou.premise_limit_weights(groups, want)
+    _pairs(groups, S, want=want)
+
+
+def test_pairs_on_a_stream_of_the_callers_twice_in_a_row():
+    """Two calls on a stream of the caller's with no synchronisation between them, onto planes that are not zero."""
+    groups, S, want = ou.constructed("plane_size_17")
+    ou.premise_plane_size(groups, S, want)
+    start = (np.arange(5 * S * S, dtype=np.uint64) * 1000 + 17).reshape(5, S, S)
+    _pairs(groups, S, start, stream=nat.Stream(), times=2, want=want)
+
+
+def test_pairs_many_blocks_onto_one_entry():
+    """S = 1: 782 blocks flush onto the same four entries."""
+    groups, S, want = ou.constructed("one_entry")
+    ou.premise_one_entry(groups, want)
+    _pairs(groups, S, want=want)
+
+
+# ---- 6c. the host entry on constructed tables ----
+
+@pytest.mark.parametrize("bits", [64, 0])
+@pytest.mark.parametrize("m", [255, 256, 257, 513])
+def test_tables_on_a_block_edge(m, bits):
+    table = ou.block_edge_table(m)
+    samples, classes, strings, w = table
+    want = ou.expected_overlap(samples, classes, strings, w, 3, 1)
+    ou.premise_block_edge(m, table, want)
+    assert want[1]["groups"] == len(set(zip(classes, strings))) > 80      # at 0 bits: one run, and as many rounds as keys
+    try:
+        nat.overlap_set_hash_bits(bits)
+        _check(samples, classes, strings, 3, w, min_samples=1, want=want)
+    finally:
+        nat.overlap_set_hash_bits(64)
+
+
+@pytest.mark.parametrize("S,rows,pool,mode", [(8, 25000, 60000, "vj"), (8, 25000, 60000, "none"), (20, 5000, 30000, "vj")])
+def test_larger_random_tables(S, rows, pool, mode):
+    """S = 8: SMAX 8 at its edge; S = 20: SMAX 32 through the host entry."""
+    samples, v, j, s, w = ou.random_tables(S, rows, pool, 7)
+    classes = ou.call_classes(v, j, mode)
+    want = ou.expected_overlap(samples, classes, s, w, S)
+    st = want[1]
+    assert st["shared_groups"] > 100 and st["private_groups"] > 100 and st["in_all_samples"] > 0 and st["largest_n_samples"] == S
+    assert st["rows_in"] == S * rows
+    _check(samples, classes, s, S, w, want=want)
+
+
+def test_three_hash_bits_at_scale():
+    samples, classes, strings, w = ou.hash_bits_table()
+    want = ou.expected_overlap(samples, classes, strings, w, 4, 1)
+    assert len(strings) == 6000 and want[1]["groups"] > 1800      # eight runs of more than 200 keys each: hundreds of rounds
+    try:
+        nat.overlap_set_hash_bits(3)
+        _check(samples, classes, strings, 4, w, min_samples=1, want=want)
+    finally:
+        nat.overlap_set_hash_bits(64)
+
+
+def test_a_cell_summed_over_many_rows():
+    """1 000 rows of one cell — four blocks of the cell sort — add up to exactly 2^32 - 1; one unit more is refused."""
+    table = ou.long_cell_table()
+    samples, classes, strings, w = table
+    want = ou.expected_overlap(samples, classes, strings, w, 3, 1)
+    ou.premise_long_cell(table, want)
+    _check(samples, classes, strings, 3, w, min_samples=1, want=want)
+    samples, classes, strings, over = ou.long_cell_table(extra=1)
+    assert sum(over) == sum(w) + 1 and max(over) < ou.LIMIT
+    with pytest.raises(ou.Unsupported):
+        ou.expected_overlap(samples, classes, strings, over, 3, 1)
+    _refused(E_UNSUPPORTED, samples, classes, strings, 3, over)
 
 
 # ---- 7. limits ----

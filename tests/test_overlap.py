@@ -85,6 +85,51 @@ def test_equal_keys_hash_equal():
     assert h.overlap_host_hash(0, b"CASS", 4) != h.overlap_host_hash(0, b"CASSL", 5)
 
 
+# ---- the pair kernel's walk on the host: the look-ups the kernel's lanes make (first_above, group_end), around them the
+# tiles, the staged ends, the per-block planes and the flush as plain loops (tests/host_overlap: overlap_host_pairs) ----
+
+def _flat(planes):
+    return [x for p in planes for r in p for x in r]
+
+
+def test_the_constructed_lists_meet_their_premises():
+    """What tests/test_gpu_overlap.py asserts before every device call, here where no device is needed."""
+    for S in ou.PLANE_SIZES:
+        groups, _, want = ou.constructed(f"plane_size_{S}")
+        ou.premise_plane_size(groups, S, want)
+    ou.premise_several_tiles(*ou.constructed("several_tiles"))
+    for name in ou.LOOKUP_NAMES:
+        ou.premise_lookup(name, ou.constructed("lookup_" + name)[0])
+    for front in ou.TILE_EDGE_FRONTS:
+        ou.premise_tile_edge(front, ou.constructed(f"tile_edge_{front}")[0])
+    ou.premise_tile_edge_long(ou.constructed("tile_edge_long")[0])
+    groups, _, want = ou.constructed("limit_weights")
+    ou.premise_limit_weights(groups, want)
+    groups, _, want = ou.constructed("one_entry")
+    ou.premise_one_entry(groups, want)
+    assert [ou.pairs_smax(S) for S in ou.PLANE_SIZES] == [8, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64]
+
+
+@pytest.mark.parametrize("name", list(ou.CONSTRUCTED))
+def test_host_walk_on_constructed_cells(name):
+    groups, S, want = ou.constructed(name)
+    smax = ou.pairs_smax(S)
+    for grid in (1, 3, ou.PAIR_GRID):
+        assert _flat(ou.host_pairs(groups, S, smax, grid)) == _flat(want), grid
+    for larger in {x for x in (16, 64) if x > smax}:      # planes larger than the call needs: S, not SMAX, places an entry
+        assert _flat(ou.host_pairs(groups, S, larger, 3)) == _flat(want), larger
+    if smax == 64:
+        assert ou.host_lib().overlap_host_pairs(len(groups), None, None, None, S, 32, 1, None) == -1      # smaller ones are refused
+
+
+def test_host_walk_adds_onto_what_is_there():
+    groups, S, _ = ou.constructed("plane_size_17")
+    start = [[[1000 * (p * S * S + a * S + b) + 17 for b in range(S)] for a in range(S)] for p in range(5)]
+    want = ou.expected_planes(groups, S, ou.expected_planes(groups, S, start))
+    got = ou.host_pairs(groups, S, 32, 3, ou.host_pairs(groups, S, 32, 3, start))
+    assert _flat(got) == _flat(want)
+
+
 # ---- the stage, with the brute force in _native.overlap's place ----
 
 A_ROWS = [("TRBV1", "TRBJ1", "CASSA", 10), ("TRBV1", "TRBJ1", "CASSB", 5), ("TRBV2", "TRBJ1", "CASSA", 1)]
