@@ -36,6 +36,7 @@
 #include "../../include/dcrx.h"
 #include "dcrx_cdr3net_core.h"
 #include "dcrx_group.h"
+#include "dcrx_text.h"
 
 using dcrx::set_err;
 using namespace dcrx_cdr3net;
@@ -344,7 +345,7 @@ int fail(int code, const char *who, const char *what) { return set_err(code, (st
 
 int neighbours_device(const char *who, uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
                       uint32_t distance, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap,
-                      uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
+                      uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) try {
   if (m >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, who, "2^30 or more nodes");
   if (distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
   if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
@@ -368,12 +369,14 @@ int neighbours_device(const char *who, uint64_t m, const uint32_t *d_class, cons
   if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_adj_need, w, W, s))) return rc;
   if (!d_adj || !adj_cap) return DCRX_OK;
   return run_write(m, distance, metric, d_adj_off, d_adj, adj_cap, w, W, s);
+} catch (const std::exception &e) {      // (a message that could not be built)
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
                 uint32_t distance, uint32_t metric, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
                 uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap,
-                uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) {
+                uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) try {
   if (m >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, who, "2^30 or more nodes");
   if (distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
   if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
@@ -388,7 +391,7 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
     if (off[k + 1] < off[k]) return fail(DCRX_E_INVALID, who, "offsets go backwards");
     if (!in_reach(off[k + 1] - off[k])) out_of_reach++;
   }
-  const uint64_t text0 = off[0], text_bytes = off[m] - text0;
+  const uint64_t text_bytes = off[m] - off[0];
   if (text_bytes && !text) return fail(DCRX_E_INVALID, who, "text is null");
   const uint32_t m32 = (uint32_t)m;
   WorkPlan W;
@@ -409,16 +412,9 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
     P.get(&d_heads, m); P.get(&d_kept, 1); P.get(&d_nn, m); P.get(&d_wout, m); P.get(&d_of, m);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
-  try {
-    std::vector<uint64_t> rebased(m + 1);
-    for (uint64_t k = 0; k <= m; k++) rebased[k] = off[k] - text0;
-    HIP_TRY(hipMemcpy(d_off, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice));
-  } catch (const std::exception &e) {
-    return set_err(DCRX_E_NOMEM, e.what());
-  }
+  if ((rc = upload_spans(m, off, text, d_off, d_text))) return rc;
   HIP_TRY(hipMemcpy(d_cls, cls, m * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_weight, weight, m * 8, hipMemcpyHostToDevice));
-  if (text_bytes) HIP_TRY(hipMemcpy(d_text, text + text0, text_bytes, hipMemcpyHostToDevice));
   const Nodes N{d_cls, d_off, d_text, text_bytes};
 
   // the degree pass, then an adjacency of exactly the entries it takes
@@ -476,6 +472,8 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
     for (uint64_t k = 0; k < m; k++) stats_out->largest_degree = std::max<uint64_t>(stats_out->largest_degree, degree_out[k]);
   }
   return (int64_t)c;
+} catch (const std::exception &e) {      // (a message that could not be built)
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 // the Levenshtein distance of two byte strings of any length (the edge file's column): a plain two-row table
@@ -490,25 +488,12 @@ uint64_t host_levenshtein(const char *a, uint64_t la, const char *b, uint64_t lb
   return prev[lb];
 }
 
-struct TextOut {
-  char *out;
-  uint64_t cap, at = 0;
-  void put(const char *p, uint64_t bytes) {
-    if (out && at + bytes <= cap && bytes) std::memcpy(out + at, p, bytes);
-    at += bytes;
-  }
-  void unum(unsigned long long x) {
-    char buf[24];
-    put(buf, (uint64_t)snprintf(buf, sizeof buf, "%llu", x));
-  }
-};
-
 int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
-                     uint32_t metric, char *out, uint64_t out_cap) {
+                     uint32_t metric, char *out, uint64_t out_cap) try {
   static const char header[] = "a\tb\tdistance\n";
   if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
   if (m && (!adj_off || !off || (adj_off[m] && !adj))) return fail(DCRX_E_INVALID, who, "null argument");
-  TextOut T{out, out_cap};
+  dcrx::TextOut T{out, out_cap};
   T.put(header, sizeof header - 1);
   for (uint64_t a = 0; a < m; a++) {
     if (adj_off[a + 1] < adj_off[a]) return fail(DCRX_E_INVALID, who, "adjacency offsets go backwards");
@@ -528,6 +513,8 @@ int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const
     }
   }
   return (int64_t)T.at;
+} catch (const std::exception &e) {      // (host_levenshtein's rows, a message)
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 }  // namespace
@@ -582,7 +569,7 @@ int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint3
   if (m && (!v_idx || !j_idx || !v_calls || !v_call_off || !j_calls || !j_call_off || !off || !weight || !cluster_of || !n_nodes ||
             !cluster_weight || !degree))
     return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_clusters: null argument");
-  TextOut T{out, out_cap};
+  dcrx::TextOut T{out, out_cap};
   T.put(header, sizeof header - 1);
   for (uint64_t i = 0; i < m; i++) {
     const uint32_t vi = v_idx[i], ji = j_idx[i], c = cluster_of[i];
@@ -590,9 +577,9 @@ int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint3
     if (c >= n_clusters) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_clusters: a cluster outside the rows");
     if (off[i + 1] < off[i]) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_clusters: offsets go backwards");
     T.unum(i); T.put("\t", 1);
-    T.put(v_calls + v_call_off[vi], v_call_off[vi + 1] - v_call_off[vi]); T.put("\t", 1);
-    T.put(j_calls + j_call_off[ji], j_call_off[ji + 1] - j_call_off[ji]); T.put("\t", 1);
-    T.put(text + off[i], off[i + 1] - off[i]); T.put("\t", 1);
+    T.put_span(v_calls, v_call_off, vi); T.put("\t", 1);
+    T.put_span(j_calls, j_call_off, ji); T.put("\t", 1);
+    T.put_span(text, off, i); T.put("\t", 1);
     T.unum(weight[i]); T.put("\t", 1);
     T.unum(c); T.put("\t", 1);
     T.unum(n_nodes[c]); T.put("\t", 1);

@@ -8,11 +8,11 @@
 //   write    clono_write_kernel, one lane per entry: junction_aa, then junction, at that offset
 // The gene tables are one blob in global memory, read through the caches: every lane of a wave reads the same few KB (the
 // tail of its V gene, its J gene), and staging the blob in LDS per block has not been measured against that.
-// The host entry (dcrx_clonotypes) adds: the members compacted in rank order, a stable radix sort of (hash, rank), run
-// heads by a max scan, the full-key compare of every member with its run's head — in rounds: what differs from the head
-// stays, and the first of what stays in a run is the next head —, totals onto the heads by integer atomics whose results
-// are not read (add, max, then min of the rank among the members that hold the max), and the rows in most_common() order.
-// The sorts, scans, run heads, compactions and that order are dcrx_group.h's.
+// The host entry (dcrx_clonotypes) adds: the members compacted in rank order, a stable radix sort of (hash, rank), the
+// exact groups under the hash (dcrx_group.h's rounds, with SameKey below as the full-key test), totals onto the heads by
+// integer atomics whose results are not read (add, max, then min of the rank among the members that hold the max), and
+// the rows in most_common() order.
+// The sorts, scans, run heads, compactions, those rounds and that order are dcrx_group.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +23,7 @@
 #include "../../include/dcrx.h"
 #include "dcrx_clono_core.h"
 #include "dcrx_group.h"
+#include "dcrx_text.h"
 
 using dcrx::set_err;
 using namespace dcrx_clono;
@@ -126,53 +127,26 @@ __global__ __launch_bounds__(BLOCK) void clono_members_kernel(const dcrx_clono_r
   }
 }
 
-// what the compactions leave at a slot: a member's hash and rank; an active member of the last round
+// what the compaction leaves at a slot: a member's hash and rank
 struct PutMember {
   const dcrx_clono_row_t *rows;
   uint64_t mask, *key;
   uint32_t *rank;
   __device__ void operator()(uint32_t slot, uint32_t e) const { key[slot] = rows[e].hash & mask; rank[slot] = e; }
 };
-struct PutActive {
-  const uint32_t *src;
-  uint32_t *dst;
-  __device__ void operator()(uint32_t slot, uint32_t i) const { dst[slot] = src[i]; }
-};
 
-__global__ __launch_bounds__(BLOCK) void clono_runs_kernel(const uint64_t *__restrict__ key, uint32_t m, uint32_t *__restrict__ mark,
-                                                           uint32_t *__restrict__ active) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= m) return;
-  mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
-  active[s] = s;
-}
-
-// a round: the first active member of every run (a: the active members in sorted order, run: a member's run)
-__global__ __launch_bounds__(BLOCK) void clono_round_mark_kernel(const uint32_t *__restrict__ active, const uint32_t *__restrict__ run,
-                                                                 uint32_t a, uint32_t *__restrict__ mark) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a) return;
-  mark[i] = run_mark(i, [&](uint32_t k) { return run[active[k]]; });
-}
-
-// ... and every other active member against it, in full
-__global__ __launch_bounds__(BLOCK) void clono_round_compare_kernel(View G, Entries E, const dcrx_clono_row_t *__restrict__ rows,
-                                                                    const uint8_t *__restrict__ arena, const uint32_t *__restrict__ rank,
-                                                                    const uint32_t *__restrict__ active, const uint32_t *__restrict__ first,
-                                                                    uint32_t a, uint32_t *__restrict__ head_of, uint32_t *__restrict__ keep) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a) return;
-  const uint32_t p = active[i], h = active[first[i]];
-  bool same = p == h;
-  if (!same) {
-    const uint32_t ep = rank[p], eh = rank[h];
-    const dcrx_clono_row_t Rp = rows[ep], Rh = rows[eh];
-    same = key_equal(G, E.v[ep], E.j[ep], junction_aa_len(Rp), arena + Rp.arena_off, E.v[eh], E.j[eh], junction_aa_len(Rh),
-                     arena + Rh.arena_off);
+// the full-key test of the rounds: two members' (V call group, J call group, junction_aa)
+struct SameKey {
+  View G;
+  Entries E;
+  const dcrx_clono_row_t *rows;
+  const uint8_t *arena;
+  __device__ bool operator()(uint32_t ea, uint32_t eb) const {
+    const dcrx_clono_row_t Ra = rows[ea], Rb = rows[eb];
+    return key_equal(G, E.v[ea], E.j[ea], junction_aa_len(Ra), arena + Ra.arena_off, E.v[eb], E.j[eb], junction_aa_len(Rb),
+                     arena + Rb.arena_off);
   }
-  if (same) head_of[p] = h;
-  keep[i] = same ? 0u : 1u;
-}
+};
 
 __global__ __launch_bounds__(BLOCK) void clono_totals_kernel(const uint32_t *__restrict__ head_of, const uint32_t *__restrict__ rank,
                                                              const uint64_t *__restrict__ count, uint32_t m,
@@ -355,7 +329,7 @@ int dcrx_cdr3_device(dcrx_clono_genes_t *g, uint64_t n, const int32_t *d_v, cons
 int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, const int32_t *j, const int32_t *vdel,
                         const int32_t *jdel, const uint64_t *count, const uint64_t *ins_off, const char *ins_text,
                         uint32_t *rep_out, uint64_t *dup_out, uint32_t *ndcrs_out, uint64_t *top_out, uint64_t *junc_off_out,
-                        uint32_t *clonotype_of_out, dcrx_clonotype_stats_t *stats_out) {
+                        uint32_t *clonotype_of_out, dcrx_clonotype_stats_t *stats_out) try {
   if (!g) return set_err(DCRX_E_INVALID, "dcrx_clonotypes: the gene set is null");
   if (n >= MAX_ENTRIES) return set_err(DCRX_E_UNSUPPORTED, "dcrx_clonotypes: 2^30 or more entries");
   if (stats_out) { *stats_out = dcrx_clonotype_stats_t{}; stats_out->entries_in = n; }
@@ -384,17 +358,15 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   uint8_t *d_text, *d_work, *d_cub;
   dcrx_clono_row_t *d_rows;
   unsigned long long *d_stats, *d_total, *d_top;
-  uint32_t *d_flag, *d_slot, *d_rank[2], *d_run, *d_mark, *d_first, *d_active[2], *d_keep, *d_head_of, *d_members, *d_rep, *d_ishead,
-      *d_list[2], *d_nd, *d_repo, *d_rowof, *d_of, *d_kept;
+  uint32_t *d_flag, *d_rank[2], *d_head_of, *d_members, *d_rep, *d_ishead, *d_list[2], *d_nd, *d_repo, *d_rowof, *d_of;
+  GroupWork R;      // (its slot and kept serve the other compactions too)
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_v, n); P.get(&d_j, n); P.get(&d_vdel, n); P.get(&d_jdel, n); P.get(&d_count, n); P.get(&d_off, n + 1);
     P.get(&d_text, text_bytes); P.get(&d_rows, n); P.get(&d_work, W.total); P.get(&d_need, 1); P.get(&d_stats, CS_WORDS);
-    P.get(&d_cub, cub_bytes); P.get(&d_flag, n); P.get(&d_slot, n); P.get(&d_key[0], n); P.get(&d_key[1], n);
-    P.get(&d_rank[0], n); P.get(&d_rank[1], n); P.get(&d_run, n); P.get(&d_mark, n); P.get(&d_first, n);
-    P.get(&d_active[0], n); P.get(&d_active[1], n); P.get(&d_keep, n); P.get(&d_head_of, n); P.get(&d_total, n);
-    P.get(&d_members, n); P.get(&d_top, n); P.get(&d_rep, n); P.get(&d_ishead, n); P.get(&d_list[0], n); P.get(&d_list[1], n);
-    P.get(&d_dup, n); P.get(&d_topo, n); P.get(&d_nd, n); P.get(&d_repo, n); P.get(&d_rowof, n); P.get(&d_of, n);
-    P.get(&d_jlen, 2 * n); P.get(&d_joff, 2 * n); P.get(&d_kept, 1);
+    P.get(&d_cub, cub_bytes); P.get(&d_flag, n); P.get(&d_key[0], n); P.get(&d_key[1], n); P.get(&d_rank[0], n);
+    P.get(&d_rank[1], n); R.get(P, n); P.get(&d_head_of, n); P.get(&d_total, n); P.get(&d_members, n); P.get(&d_top, n);
+    P.get(&d_rep, n); P.get(&d_ishead, n); P.get(&d_list[0], n); P.get(&d_list[1], n); P.get(&d_dup, n); P.get(&d_topo, n);
+    P.get(&d_nd, n); P.get(&d_repo, n); P.get(&d_rowof, n); P.get(&d_of, n); P.get(&d_jlen, 2 * n); P.get(&d_joff, 2 * n);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
   if ((rc = upload_table(n, v, j, vdel, jdel, count, ins_off, ins_text, d_v, d_j, d_vdel, d_jdel, d_count, d_off, d_text))) return rc;
@@ -436,32 +408,13 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   if (!m) return 0;
   const uint32_t m32 = (uint32_t)m;
 
-  // the members in rank order, sorted (stably) by hash
+  // the members in rank order, sorted (stably) by hash; then the rounds: head_of
   const Scratch cub{d_cub, cub_bytes};
-  const uint64_t mask = g->bits >= 64 ? ~0ull : ((1ull << g->bits) - 1);
-  if ((rc = compact(cub, d_flag, d_slot, n32, PutMember{d_rows, mask, d_key[0], d_rank[0]}, nullptr, nullptr)) ||      // (their number is m)
+  if ((rc = compact(cub, d_flag, R.slot, n32, PutMember{d_rows, low_bits(g->bits), d_key[0], d_rank[0]}, nullptr, nullptr)) ||      // (their number is m)
       (rc = sort_pairs(cub, d_key[0], d_key[1], d_rank[0], d_rank[1], m, 64, nullptr))) return rc;
   const uint32_t *d_sorted = d_rank[1];
-  clono_runs_kernel<<<grid_for(m), BLOCK>>>(d_key[1], m32, d_mark, d_active[0]);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, d_mark, d_run, m, nullptr))) return rc;
-
-  // rounds: every active member against the first active member of its run; what differs stays active
-  uint32_t a = m32;
-  int cur = 0;
-  while (a) {
-    clono_round_mark_kernel<<<grid_for(a), BLOCK>>>(d_active[cur], d_run, a, d_mark);
-    HIP_TRY(hipGetLastError());
-    if ((rc = run_heads(cub, d_mark, d_first, a, nullptr))) return rc;
-    clono_round_compare_kernel<<<grid_for(a), BLOCK>>>(G, E, d_rows, d_arena, d_sorted, d_active[cur], d_first, a, d_head_of, d_keep);
-    HIP_TRY(hipGetLastError());
-    if ((rc = compact(cub, d_keep, d_slot, a, PutActive{d_active[cur], d_active[cur ^ 1]}, d_kept, nullptr))) return rc;
-    uint32_t left = 0;
-    HIP_TRY(hipMemcpy(&left, d_kept, 4, hipMemcpyDeviceToHost));      // (the round's one synchronisation)
-    if (left >= a) return set_err(DCRX_E_HIP, "dcrx_clonotypes: a round resolved nothing");      // (the first of every run always resolves)
-    a = left;
-    cur ^= 1;
-  }
+  if ((rc = exact_groups(cub, d_key[1], d_sorted, m32, SameKey{G, E, d_rows, d_arena}, R, d_head_of,
+                         "dcrx_clonotypes: a round resolved nothing", nullptr))) return rc;
 
   // totals onto the heads, the representatives
   HIP_TRY(hipMemsetAsync(d_total, 0, m * 8, nullptr));
@@ -472,9 +425,9 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   HIP_TRY(hipGetLastError());
   clono_rep_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, d_count, d_top, m32, d_rep);
   HIP_TRY(hipGetLastError());
-  if ((rc = compact(cub, d_ishead, d_slot, m32, PutIndex{d_list[0]}, d_kept, nullptr))) return rc;
+  if ((rc = compact(cub, d_ishead, R.slot, m32, PutIndex{d_list[0]}, R.kept, nullptr))) return rc;
   uint32_t c = 0;
-  HIP_TRY(hipMemcpy(&c, d_kept, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&c, R.kept, 4, hipMemcpyDeviceToHost));
 
   // order: by the representative's rank, then (stably) by duplicate_count descending
   if ((rc = most_common_order(cub, d_list, d_key, d_rep, 32, d_total, c, nullptr))) return rc;
@@ -493,11 +446,7 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   if ((rc = d_out.alloc(std::max<uint64_t>(out_bytes, 1)))) return rc;
   clono_gather_kernel<<<grid_for(c), BLOCK>>>(d_repo, d_rows, d_arena, d_jlen, d_joff, c, d_out);
   HIP_TRY(hipGetLastError());
-  try {
-    g->text.resize(out_bytes);
-  } catch (const std::exception &e) {
-    return set_err(DCRX_E_NOMEM, e.what());
-  }
+  g->text.resize(out_bytes);
   if (out_bytes) HIP_TRY(hipMemcpy(g->text.data(), d_out, out_bytes, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(rep_out, d_repo, (uint64_t)c * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(dup_out, d_dup, (uint64_t)c * 8, hipMemcpyDeviceToHost));
@@ -512,6 +461,8 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
     }
   }
   return (int64_t)c;
+} catch (const std::exception &e) {      // (the entry's one guard: the junction text, a message)
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 int64_t dcrx_clonotypes_text(dcrx_clono_genes_t *g, char *out, uint64_t cap) {
@@ -528,38 +479,24 @@ int64_t dcrx_format_clonotypes(uint64_t m, const uint32_t *rep, const uint64_t *
   static const char header[] = "v_call\tj_call\tjunction_aa\tduplicate_count\tn_dcrs\tjunction\tdecombinator_id\ttop_dcr_count\n";
   if (m && (!rep || !dup || !ndcrs || !top || !junc_off || !v || !j || !vdel || !jdel || !ins_off || !v_call_off || !j_call_off))
     return set_err(DCRX_E_INVALID, "dcrx_format_clonotypes: null argument");
-  uint64_t at = 0;
-  auto put = [&](const char *p, uint64_t bytes) {
-    if (out && at + bytes <= out_cap && bytes) std::memcpy(out + at, p, bytes);
-    at += bytes;
-  };
-  auto num = [&](long long x) {
-    char buf[24];
-    const int k = snprintf(buf, sizeof buf, "%lld", x);
-    put(buf, (uint64_t)k);
-  };
-  auto unum = [&](unsigned long long x) {
-    char buf[24];
-    const int k = snprintf(buf, sizeof buf, "%llu", x);
-    put(buf, (uint64_t)k);
-  };
-  put(header, sizeof header - 1);
+  dcrx::TextOut T{out, out_cap};
+  T.put(header, sizeof header - 1);
   for (uint64_t r = 0; r < m; r++) {
     const uint64_t e = rep[r];
     if (e >= n) return set_err(DCRX_E_INVALID, "dcrx_format_clonotypes: a representative outside the table");
     const int64_t vi = v[e] < 0 ? (int64_t)v[e] + n_v : (int64_t)v[e], ji = j[e] < 0 ? (int64_t)j[e] + n_j : (int64_t)j[e];
     if (vi < 0 || vi >= (int64_t)n_v || ji < 0 || ji >= (int64_t)n_j) return set_err(DCRX_E_INVALID, "dcrx_format_clonotypes: a gene outside its table");
-    put(v_calls + v_call_off[vi], v_call_off[vi + 1] - v_call_off[vi]); put("\t", 1);
-    put(j_calls + j_call_off[ji], j_call_off[ji + 1] - j_call_off[ji]); put("\t", 1);
-    put(junc_text + junc_off[2 * r], junc_off[2 * r + 1] - junc_off[2 * r]); put("\t", 1);
-    unum(dup[r]); put("\t", 1);
-    unum(ndcrs[r]); put("\t", 1);
-    put(junc_text + junc_off[2 * r + 1], junc_off[2 * r + 2] - junc_off[2 * r + 1]); put("\t", 1);
-    num(v[e]); put(", ", 2); num(j[e]); put(", ", 2); num(vdel[e]); put(", ", 2); num(jdel[e]); put(", ", 2);
-    put(ins_text + ins_off[e], ins_off[e + 1] - ins_off[e]); put("\t", 1);
-    unum(top[r]); put("\n", 1);
+    T.put_span(v_calls, v_call_off, vi); T.put("\t", 1);
+    T.put_span(j_calls, j_call_off, ji); T.put("\t", 1);
+    T.put_span(junc_text, junc_off, 2 * r); T.put("\t", 1);
+    T.unum(dup[r]); T.put("\t", 1);
+    T.unum(ndcrs[r]); T.put("\t", 1);
+    T.put_span(junc_text, junc_off, 2 * r + 1); T.put("\t", 1);
+    T.num(v[e]); T.put(", ", 2); T.num(j[e]); T.put(", ", 2); T.num(vdel[e]); T.put(", ", 2); T.num(jdel[e]); T.put(", ", 2);
+    T.put_span(ins_text, ins_off, e); T.put("\t", 1);
+    T.unum(top[r]); T.put("\n", 1);
   }
-  return (int64_t)at;
+  return (int64_t)T.at;
 }
 
 }  // extern "C"

@@ -502,7 +502,7 @@ int dcrx_count_device(dcrx_counts_t *c, const dcrx_record_t *d_records, const dc
 
 int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vdel, uint8_t *jdel, uint64_t *count,
                          uint64_t *first, uint64_t *ins_off, char *ins_text, uint64_t cap, uint64_t text_cap,
-                         uint64_t *text_bytes) {
+                         uint64_t *text_bytes) try {
   if (!c || !text_bytes) return set_err(DCRX_E_INVALID, "null argument");
   *text_bytes = 0;
   if (c->device < 0 || !c->slots) {
@@ -583,6 +583,8 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
   }
   ins_off[n] = at;
   return (int64_t)n;
+} catch (const std::exception &e) {      // (the entry's one guard: the host copies of the table's columns and of the arena)
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 int64_t dcrx_format_counts(uint64_t n, const uint16_t *v, const uint16_t *j, const uint8_t *vdel, const uint8_t *jdel,

@@ -1,16 +1,20 @@
-// dcrx_group.h — what the count (dcrx_count.hip), the error merge (dcrx_merge.hip) and the clonotype step (dcrx_clono.hip)
-// share to group, compact and order a table on the device, each written once: the launch geometry, the 64-bit wave sum,
-// the one-allocation pool and the offset carver, hipCUB's four calls with their scratch, run heads, the ordered compaction,
-// the most_common() order and the upload of a counted table.  Private to those translation units (HIP only, as dcrx_hip.h).
-// Nothing here synchronises or allocates behind the caller's back (Pool::allocate is the caller's one allocation); every
-// launch and hipCUB call goes to the stream it is handed.  Everything has internal linkage, as the kernels of those units
-// have: a unit's instances of the templated kernels are its own.
+// dcrx_group.h — what the count (dcrx_count.hip), the error merge (dcrx_merge.hip), the clonotype step (dcrx_clono.hip), the
+// CDR3 network (dcrx_cdr3net.hip) and the overlap step (dcrx_overlap.hip) share to group, compact and order a table on the
+// device, each written once: the launch geometry, the 64-bit wave sum, the one-allocation pool and the offset carver,
+// hipCUB's four calls with their scratch, run heads, the ordered compaction, exact groups under a hash (the rounds of the
+// clonotype and overlap steps), the most_common() order and the upload of offsets with their text and of a counted table.
+// Private to those translation units (HIP only, as dcrx_hip.h).
+// Nothing here allocates behind the caller's back (Pool::allocate is the caller's one allocation), and nothing synchronises
+// but exact_groups, once per round, and the uploads, which are blocking copies; every launch and hipCUB call goes to the
+// stream it is handed.  Everything has internal linkage, as the kernels of those units have: a unit's instances of the
+// templated kernels are its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <exception>
 #include <vector>
 
 #include "dcrx_hip.h"
@@ -23,6 +27,7 @@ constexpr uint64_t ALIGN = 256;
 
 inline unsigned grid_for(uint64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 inline uint64_t aligned(uint64_t bytes) { return (bytes + ALIGN - 1) & ~(ALIGN - 1); }
+inline uint64_t low_bits(uint32_t bits) { return bits >= 64 ? ~0ull : (1ull << bits) - 1; }      // the mask of a hash cut to `bits`
 
 // the wave's sum, in lane 0
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
@@ -127,6 +132,78 @@ struct PutIndex {      // the position itself
   __device__ void operator()(uint32_t slot, uint32_t i) const { list[slot] = i; }
 };
 
+// ---- exact groups under a hash.  The rows come sorted stably by hash: key[s] is the hash at sorted position s, rank[s] the
+// row there, so a run of one hash is in rank order.  Rounds: every active position is compared in full, by same(rank, rank),
+// with the first active position of its run; what differs stays active, and the first of what stays in a run is the next
+// round's head.  head_of[s] ends as the sorted position of the first row whose full key equals that of position s.
+// A round synchronises once: the 4 bytes that say how many positions stay, by a blocking copy on the stream (an asynchronous
+// copy and a stream wait in its place measured 1 ms slower per call).  `stalled` is the caller's message for a
+// round that resolved nothing (the first active position of every run always resolves).
+// The work buffers, over n >= m positions; between calls they are the caller's to use.
+struct GroupWork {
+  uint32_t *run, *mark, *first, *active[2], *keep, *slot, *kept;
+  void get(Pool &P, uint64_t n) {
+    P.get(&run, n); P.get(&mark, n); P.get(&first, n); P.get(&active[0], n); P.get(&active[1], n); P.get(&keep, n); P.get(&slot, n);
+    P.get(&kept, 1);
+  }
+};
+
+__global__ __launch_bounds__(BLOCK) void group_runs_kernel(const uint64_t *__restrict__ key, uint32_t m, uint32_t *__restrict__ mark,
+                                                           uint32_t *__restrict__ active) {
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= m) return;
+  mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
+  active[s] = s;
+}
+
+// a round: the first active position of every run (active: the active positions in sorted order, run: a position's run)
+__global__ __launch_bounds__(BLOCK) void group_round_mark_kernel(const uint32_t *__restrict__ active, const uint32_t *__restrict__ run,
+                                                                 uint32_t a, uint32_t *__restrict__ mark) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a) return;
+  mark[i] = run_mark(i, [&](uint32_t k) { return run[active[k]]; });
+}
+
+// ... and every other active position against it, in full
+template <class Same>
+__global__ __launch_bounds__(BLOCK) void group_round_compare_kernel(Same same, const uint32_t *__restrict__ rank,
+                                                                    const uint32_t *__restrict__ active, const uint32_t *__restrict__ first,
+                                                                    uint32_t a, uint32_t *__restrict__ head_of, uint32_t *__restrict__ keep) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a) return;
+  const uint32_t p = active[i], h = active[first[i]];
+  const bool eq = p == h || same(rank[p], rank[h]);
+  if (eq) head_of[p] = h;
+  keep[i] = eq ? 0u : 1u;
+}
+
+struct PutActive {      // an active position of the last round
+  const uint32_t *src;
+  uint32_t *dst;
+  __device__ void operator()(uint32_t slot, uint32_t i) const { dst[slot] = src[i]; }
+};
+
+template <class Same> int exact_groups(Scratch t, const uint64_t *key, const uint32_t *rank, uint32_t m, Same same, const GroupWork &W,
+                                       uint32_t *head_of, const char *stalled, hipStream_t s) {
+  if (!m) return DCRX_OK;
+  int rc;
+  group_runs_kernel<<<grid_for(m), BLOCK, 0, s>>>(key, m, W.mark, W.active[0]);
+  HIP_TRY(hipGetLastError());
+  if ((rc = run_heads(t, W.mark, W.run, m, s))) return rc;
+  int cur = 0;
+  for (uint32_t a = m, left = 0; a; a = left, cur ^= 1) {
+    group_round_mark_kernel<<<grid_for(a), BLOCK, 0, s>>>(W.active[cur], W.run, a, W.mark);
+    HIP_TRY(hipGetLastError());
+    if ((rc = run_heads(t, W.mark, W.first, a, s))) return rc;
+    group_round_compare_kernel<<<grid_for(a), BLOCK, 0, s>>>(same, rank, W.active[cur], W.first, a, head_of, W.keep);
+    HIP_TRY(hipGetLastError());
+    if ((rc = compact(t, W.keep, W.slot, a, PutActive{W.active[cur], W.active[cur ^ 1]}, W.kept, s))) return rc;
+    HIP_TRY(hipMemcpyWithStream(&left, W.kept, 4, hipMemcpyDeviceToHost, s));      // (blocking: the round's one synchronisation)
+    if (left >= a) return dcrx::set_err(DCRX_E_HIP, stalled);
+  }
+  return DCRX_OK;
+}
+
 // ---- collections.Counter.most_common() order
 // dst[k] = src[list[k]] as 64 bits, or its complement (an ascending sort of the complements is a descending one)
 template <class S, class L> __global__ __launch_bounds__(BLOCK) void gather_kernel(const S *__restrict__ src, const L *__restrict__ list, uint32_t m,
@@ -153,22 +230,31 @@ template <class L, class T, class C> int most_common_order(Scratch t, L *const l
   return DCRX_OK;
 }
 
-// ---- a counted table from the host (blocking copies): genes, deletions, counts, the offsets rebased to ins_off[0] and the
-// text they span
+// ---- from the host (blocking copies): the offsets off[0 .. n] rebased to off[0] and the text they span; DCRX_E_NOMEM,
+// not an exception, where the host has no room for the rebased offsets
+inline int upload_spans(uint64_t n, const uint64_t *off, const char *text, uint64_t *d_off, uint8_t *d_text) {
+  const uint64_t text0 = off[0], text_bytes = off[n] - text0;
+  std::vector<uint64_t> rebased;
+  try {
+    rebased.resize(n + 1);
+  } catch (const std::exception &e) {
+    return dcrx::set_err(DCRX_E_NOMEM, e.what());
+  }
+  for (uint64_t k = 0; k <= n; k++) rebased[k] = off[k] - text0;
+  HIP_TRY(hipMemcpy(d_off, rebased.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+  if (text_bytes) HIP_TRY(hipMemcpy(d_text, text + text0, text_bytes, hipMemcpyHostToDevice));
+  return DCRX_OK;
+}
+// ... and a counted table: genes, deletions, counts, and its inserts that way
 template <class G, class D> int upload_table(uint64_t n, const G *v, const G *j, const D *vdel, const D *jdel, const uint64_t *count,
                                              const uint64_t *ins_off, const char *ins_text, G *d_v, G *d_j, D *d_vdel, D *d_jdel,
                                              uint64_t *d_count, uint64_t *d_off, uint8_t *d_text) {
-  const uint64_t text0 = ins_off[0], text_bytes = ins_off[n] - text0;
-  std::vector<uint64_t> off(n + 1);
-  for (uint64_t k = 0; k <= n; k++) off[k] = ins_off[k] - text0;
   HIP_TRY(hipMemcpy(d_v, v, n * sizeof(G), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_j, j, n * sizeof(G), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_vdel, vdel, n * sizeof(D), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_jdel, jdel, n * sizeof(D), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_count, count, n * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-  if (text_bytes) HIP_TRY(hipMemcpy(d_text, ins_text + text0, text_bytes, hipMemcpyHostToDevice));
-  return DCRX_OK;
+  return upload_spans(n, ins_off, ins_text, d_off, d_text);
 }
 
 }  // namespace

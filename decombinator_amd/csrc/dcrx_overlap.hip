@@ -4,11 +4,9 @@
 //
 // The host entry (dcrx_overlap_run), on the null stream:
 //   keys     overlap_keys_kernel, one lane per row: the hash of (class, bytes)
-//   group    a stable radix sort of (hash, rank), run heads by a max scan, then rounds: every active row against the first
-//            active row of its run, in full; what differs stays active.  A run is in rank order, so a group's first row is
-//            its head.  (The round loop is dcrx_clono.hip's step 5 written again: lifting that one into dcrx_group.h means
-//            handing its compare kernel the key test as a functor argument, which changes the clonotype kernels' argument
-//            layout and so their instructions.)  The heads flagged in rank order and scanned number the groups.
+//   group    a stable radix sort of (hash, rank), then the exact groups under the hash (dcrx_group.h's rounds, with SameKey
+//            below as the full-key test).  A run is in rank order, so a group's first row is its head.  The heads flagged in
+//            rank order and scanned number the groups.
 //   cells    a stable sort of (group, sample) over the bits in use (36 at most), run heads, the rows' weights added onto
 //            their run's head by 64-bit atomics whose results are not read, the heads compacted in order; a cell sum of
 //            2^32 or more raises a flag that comes back with the number of cells.  n_samples and the group's weight by
@@ -24,7 +22,7 @@
 // is not zero to the planes in global memory.  PART 0 holds shared (a triangle of uint32), shared_weight (full, uint64) and
 // min_weight (a triangle of uint64); PART 1 the two product planes (triangles of uint64).  SMAX (8, 16, 32, 64) sizes the
 // planes in LDS for the call's number of samples.
-// The sorts, scans, run heads and compactions are dcrx_group.h's.
+// The sorts, scans, run heads, compactions and those rounds are dcrx_group.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +35,7 @@
 #include "../../include/dcrx.h"
 #include "dcrx_group.h"
 #include "dcrx_overlap_core.h"
+#include "dcrx_text.h"
 
 using dcrx::set_err;
 using namespace dcrx_ovl;
@@ -72,43 +71,13 @@ __global__ __launch_bounds__(BLOCK) void overlap_keys_kernel(Rows R, uint32_t m,
   rank[i] = i;
 }
 
-__global__ __launch_bounds__(BLOCK) void overlap_runs_kernel(const uint64_t *__restrict__ key, uint32_t m, uint32_t *__restrict__ mark,
-                                                             uint32_t *__restrict__ active) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= m) return;
-  mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
-  active[s] = s;
-}
-
-// a round: the first active row of every run (active: the active rows in sorted order, run: a row's run)
-__global__ __launch_bounds__(BLOCK) void overlap_round_mark_kernel(const uint32_t *__restrict__ active, const uint32_t *__restrict__ run,
-                                                                   uint32_t a, uint32_t *__restrict__ mark) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a) return;
-  mark[i] = run_mark(i, [&](uint32_t k) { return run[active[k]]; });
-}
-
-// ... and every other active row against it, in full
-__global__ __launch_bounds__(BLOCK) void overlap_round_compare_kernel(Rows R, const uint32_t *__restrict__ rank,
-                                                                      const uint32_t *__restrict__ active, const uint32_t *__restrict__ first,
-                                                                      uint32_t a, uint32_t *__restrict__ head_of, uint32_t *__restrict__ keep) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a) return;
-  const uint32_t p = active[i], h = active[first[i]];
-  bool same = p == h;
-  if (!same) {
-    const uint32_t ep = rank[p], eh = rank[h];
-    const uint64_t ap = R.off[ep], ah = R.off[eh];
-    same = key_equal(R.cls[ep], R.text + ap, R.off[ep + 1] - ap, R.cls[eh], R.text + ah, R.off[eh + 1] - ah);
+// the full-key test of the rounds: two rows' (class, bytes)
+struct SameKey {
+  Rows R;
+  __device__ bool operator()(uint32_t ea, uint32_t eb) const {
+    const uint64_t aa = R.off[ea], ab = R.off[eb];
+    return key_equal(R.cls[ea], R.text + aa, R.off[ea + 1] - aa, R.cls[eb], R.text + ab, R.off[eb + 1] - ab);
   }
-  if (same) head_of[p] = h;
-  keep[i] = same ? 0u : 1u;
-}
-
-struct PutActive {      // an active row of the last round
-  const uint32_t *src;
-  uint32_t *dst;
-  __device__ void operator()(uint32_t slot, uint32_t i) const { dst[slot] = src[i]; }
 };
 
 // the heads, flagged at their rank: their exclusive sum numbers the groups by head ascending
@@ -315,23 +284,22 @@ int bits_for(uint64_t values) {      // the bits that hold 0 .. values - 1
 int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
         uint32_t min_samples, dcrx_overlap &O) {
   const uint32_t m32 = (uint32_t)m, SS = S * S;
-  const uint64_t text0 = off[0], text_bytes = off[m] - text0;
+  const uint64_t text_bytes = off[m] - off[0];
   size_t cub_bytes = 0;
   int rc;
   if ((rc = sort_pairs_bytes<uint32_t>(m, 64, &cub_bytes)) || (rc = exclusive_sum_bytes<uint32_t>(m + 1, &cub_bytes)) ||
       (rc = run_heads_bytes(m, &cub_bytes))) return rc;
 
   Pool P;
-  uint32_t *d_sample, *d_cls, *d_rank[2], *d_run, *d_mark, *d_first, *d_active[2], *d_keep, *d_slot, *d_head_of, *d_flag, *d_group_of,
-      *d_head_rank, *d_cell_sample, *d_cell_weight, *d_ns, *d_cell_off, *d_list[2], *d_kept, *d_pub_head, *d_pub_ns, *d_pub_off,
-      *d_pub_sample, *d_pub_cw;
+  uint32_t *d_sample, *d_cls, *d_rank[2], *d_head_of, *d_flag, *d_group_of, *d_head_rank, *d_cell_sample, *d_cell_weight, *d_ns,
+      *d_cell_off, *d_list[2], *d_kept, *d_pub_head, *d_pub_ns, *d_pub_off, *d_pub_sample, *d_pub_cw;
+  GroupWork W;      // (its mark, first and slot serve the cells and the public rows too)
   uint64_t *d_off, *d_weight, *d_key[2], *d_pub_weight;
   unsigned long long *d_sum, *d_gweight, *d_planes;
   uint8_t *d_text, *d_cub;
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_sample, m); P.get(&d_cls, m); P.get(&d_off, m + 1); P.get(&d_text, text_bytes); P.get(&d_weight, m);
-    P.get(&d_key[0], m); P.get(&d_key[1], m); P.get(&d_rank[0], m); P.get(&d_rank[1], m); P.get(&d_run, m); P.get(&d_mark, m);
-    P.get(&d_first, m); P.get(&d_active[0], m); P.get(&d_active[1], m); P.get(&d_keep, m); P.get(&d_slot, m + 1);
+    P.get(&d_key[0], m); P.get(&d_key[1], m); P.get(&d_rank[0], m); P.get(&d_rank[1], m); W.get(P, m);
     P.get(&d_head_of, m); P.get(&d_flag, m + 1); P.get(&d_group_of, m); P.get(&d_head_rank, m); P.get(&d_sum, m);
     P.get(&d_cell_sample, m); P.get(&d_cell_weight, m); P.get(&d_ns, m + 1); P.get(&d_gweight, m); P.get(&d_cell_off, m + 1);
     P.get(&d_list[0], m); P.get(&d_list[1], m); P.get(&d_kept, 2); P.get(&d_planes, (uint64_t)PLANES * SS); P.get(&d_pub_head, m);
@@ -339,54 +307,29 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
     P.get(&d_cub, cub_bytes);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
-  {
-    std::vector<uint64_t> rebased(m + 1);
-    for (uint64_t k = 0; k <= m; k++) rebased[k] = off[k] - text0;
-    HIP_TRY(hipMemcpy(d_off, rebased.data(), (m + 1) * 8, hipMemcpyHostToDevice));
-  }
+  if ((rc = upload_spans(m, off, text, d_off, d_text))) return rc;
   HIP_TRY(hipMemcpy(d_sample, sample, m * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_cls, cls, m * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_weight, weight, m * 8, hipMemcpyHostToDevice));
-  if (text_bytes) HIP_TRY(hipMemcpy(d_text, text + text0, text_bytes, hipMemcpyHostToDevice));
   const Rows R{d_cls, d_off, d_text};
   const Scratch cub{d_cub, cub_bytes};
 
-  // keys, the sort by hash, the runs
-  const uint32_t bits = g_hash_bits.load();
-  const uint64_t mask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
-  overlap_keys_kernel<<<grid_for(m), BLOCK>>>(R, m32, mask, d_key[0], d_rank[0]);
+  // keys, the sort by hash, the rounds: head_of
+  overlap_keys_kernel<<<grid_for(m), BLOCK>>>(R, m32, low_bits(g_hash_bits.load()), d_key[0], d_rank[0]);
   HIP_TRY(hipGetLastError());
   if ((rc = sort_pairs(cub, d_key[0], d_key[1], d_rank[0], d_rank[1], m, 64, nullptr))) return rc;
   const uint32_t *d_sorted = d_rank[1];
-  overlap_runs_kernel<<<grid_for(m), BLOCK>>>(d_key[1], m32, d_mark, d_active[0]);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, d_mark, d_run, m, nullptr))) return rc;
-
-  // rounds: every active row against the first active row of its run; what differs stays active
-  uint32_t a = m32;
-  int cur = 0;
-  while (a) {
-    overlap_round_mark_kernel<<<grid_for(a), BLOCK>>>(d_active[cur], d_run, a, d_mark);
-    HIP_TRY(hipGetLastError());
-    if ((rc = run_heads(cub, d_mark, d_first, a, nullptr))) return rc;
-    overlap_round_compare_kernel<<<grid_for(a), BLOCK>>>(R, d_sorted, d_active[cur], d_first, a, d_head_of, d_keep);
-    HIP_TRY(hipGetLastError());
-    if ((rc = compact(cub, d_keep, d_slot, a, PutActive{d_active[cur], d_active[cur ^ 1]}, d_kept, nullptr))) return rc;
-    uint32_t left = 0;
-    HIP_TRY(hipMemcpy(&left, d_kept, 4, hipMemcpyDeviceToHost));      // (the round's one synchronisation)
-    if (left >= a) return set_err(DCRX_E_HIP, "dcrx_overlap_run: a round resolved nothing");      // (the first of every run always resolves)
-    a = left;
-    cur ^= 1;
-  }
+  if ((rc = exact_groups(cub, d_key[1], d_sorted, m32, SameKey{R}, W, d_head_of, "dcrx_overlap_run: a round resolved nothing", nullptr)))
+    return rc;
 
   // the groups, numbered by head ascending
   overlap_heads_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, m32, d_flag);
   HIP_TRY(hipGetLastError());
-  if ((rc = exclusive_sum(cub, d_flag, d_slot, m, nullptr))) return rc;
-  overlap_group_of_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, d_slot, m32, d_group_of, d_head_rank);
+  if ((rc = exclusive_sum(cub, d_flag, W.slot, m, nullptr))) return rc;
+  overlap_group_of_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, W.slot, m32, d_group_of, d_head_rank);
   HIP_TRY(hipGetLastError());
   uint32_t last[2] = {0, 0};
-  HIP_TRY(hipMemcpy(&last[0], d_slot + (m - 1), 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&last[0], W.slot + (m - 1), 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(&last[1], d_flag + (m - 1), 4, hipMemcpyDeviceToHost));
   const uint32_t n_groups = last[0] + last[1];
 
@@ -394,16 +337,16 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
   overlap_cell_keys_kernel<<<grid_for(m), BLOCK>>>(d_group_of, d_sample, m32, d_key[0], d_rank[0]);
   HIP_TRY(hipGetLastError());
   if ((rc = sort_pairs(cub, d_key[0], d_key[1], d_rank[0], d_rank[1], m, bits_for(n_groups) + (int)SAMPLE_BITS, nullptr))) return rc;
-  overlap_cell_marks_kernel<<<grid_for(m), BLOCK>>>(d_key[1], m32, d_mark);
+  overlap_cell_marks_kernel<<<grid_for(m), BLOCK>>>(d_key[1], m32, W.mark);
   HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, d_mark, d_first, m, nullptr))) return rc;
+  if ((rc = run_heads(cub, W.mark, W.first, m, nullptr))) return rc;
   HIP_TRY(hipMemsetAsync(d_sum, 0, m * 8, nullptr));
   HIP_TRY(hipMemsetAsync(d_ns, 0, ((uint64_t)n_groups + 1) * 4, nullptr));
   HIP_TRY(hipMemsetAsync(d_gweight, 0, (uint64_t)n_groups * 8, nullptr));
   HIP_TRY(hipMemsetAsync(d_kept, 0, 8, nullptr));
-  overlap_cell_sums_kernel<<<grid_for(m), BLOCK>>>(d_first, d_rank[1], d_weight, m32, d_sum, d_flag);
+  overlap_cell_sums_kernel<<<grid_for(m), BLOCK>>>(W.first, d_rank[1], d_weight, m32, d_sum, d_flag);
   HIP_TRY(hipGetLastError());
-  if ((rc = compact(cub, d_flag, d_slot, m32, PutCell{d_key[1], d_sum, d_cell_sample, d_cell_weight, d_ns, d_kept + 1, d_gweight}, d_kept,
+  if ((rc = compact(cub, d_flag, W.slot, m32, PutCell{d_key[1], d_sum, d_cell_sample, d_cell_weight, d_ns, d_kept + 1, d_gweight}, d_kept,
                     nullptr))) return rc;
   uint32_t kept[2] = {0, 0};      // the number of cells, and with it the flag of a cell that passed 2^32
   HIP_TRY(hipMemcpy(kept, d_kept, 8, hipMemcpyDeviceToHost));
@@ -418,7 +361,7 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
   // public rows: flag, compact (group order is head order), weight descending, n_samples descending
   overlap_public_flag_kernel<<<grid_for(n_groups), BLOCK>>>(d_ns, n_groups, min_samples, d_flag);
   HIP_TRY(hipGetLastError());
-  if ((rc = compact(cub, d_flag, d_slot, n_groups, PutIndex{d_list[0]}, d_kept, nullptr))) return rc;
+  if ((rc = compact(cub, d_flag, W.slot, n_groups, PutIndex{d_list[0]}, d_kept, nullptr))) return rc;
   uint32_t rows = 0;
   HIP_TRY(hipMemcpy(&rows, d_kept, 4, hipMemcpyDeviceToHost));
   if ((rc = most_common_order(cub, d_list, d_key, d_head_rank, 32, d_gweight, rows, nullptr))) return rc;
@@ -471,19 +414,6 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
   (void)n_cells;
   return DCRX_OK;
 }
-
-struct TextOut {
-  char *out;
-  uint64_t cap, at = 0;
-  void put(const char *p, uint64_t bytes) {
-    if (out && at + bytes <= cap && bytes) std::memcpy(out + at, p, bytes);
-    at += bytes;
-  }
-  void unum(unsigned long long x) {
-    char buf[24];
-    put(buf, (uint64_t)snprintf(buf, sizeof buf, "%llu", x));
-  }
-};
 
 }  // namespace
 
@@ -592,11 +522,11 @@ int64_t dcrx_format_overlap_public(uint64_t n_public, const uint32_t *head, cons
       (n_public && (!head || !n_samples || !weight || !cell_off || !cell_sample || !cell_weight || !v_idx || !j_idx || !v_calls ||
                     !v_call_off || !j_calls || !j_call_off || !off)))
     return set_err(DCRX_E_INVALID, "dcrx_format_overlap_public: null argument");
-  TextOut T{out, out_cap};
+  dcrx::TextOut T{out, out_cap};
   T.put(header, sizeof header - 1);
   for (uint32_t s = 0; s < S; s++) {
     T.put("\t", 1);
-    T.put(sample_names + sample_name_off[s], sample_name_off[s + 1] - sample_name_off[s]);
+    T.put_span(sample_names, sample_name_off, s);
   }
   T.put("\n", 1);
   for (uint64_t r = 0; r < n_public; r++) {
@@ -605,9 +535,9 @@ int64_t dcrx_format_overlap_public(uint64_t n_public, const uint32_t *head, cons
     const uint32_t vi = v_idx[e], ji = j_idx[e];
     if (vi >= n_v || ji >= n_j) return set_err(DCRX_E_INVALID, "dcrx_format_overlap_public: a gene outside its table");
     if (off[e + 1] < off[e] || cell_off[r + 1] < cell_off[r]) return set_err(DCRX_E_INVALID, "dcrx_format_overlap_public: offsets go backwards");
-    T.put(v_calls + v_call_off[vi], v_call_off[vi + 1] - v_call_off[vi]); T.put("\t", 1);
-    T.put(j_calls + j_call_off[ji], j_call_off[ji + 1] - j_call_off[ji]); T.put("\t", 1);
-    T.put(text + off[e], off[e + 1] - off[e]); T.put("\t", 1);
+    T.put_span(v_calls, v_call_off, vi); T.put("\t", 1);
+    T.put_span(j_calls, j_call_off, ji); T.put("\t", 1);
+    T.put_span(text, off, e); T.put("\t", 1);
     T.unum(n_samples[r]); T.put("\t", 1);
     T.unum(weight[r]);
     uint64_t k = cell_off[r];
