@@ -430,6 +430,14 @@ class OverlapStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in OVERLAP_STATS]
 
 
+DOWNSAMPLE_MAX_SAMPLES = 4096      # DCRX_DOWNSAMPLE_MAX_SAMPLES
+DOWNSAMPLE_MAX_ROWS = 1 << 30      # dcrx_downsample: DCRX_E_UNSUPPORTED from here on
+DOWNSAMPLE_MAX_READS = 1 << 40     # ... and for this many reads in all
+DOWNSAMPLE_OUTPUTS = ("kept", "reads", "depth_used", "threshold")
+OVERLAP_DIVERSITY_COLUMNS = ["sample", "reads_in", "reads", "clonotypes", "singletons", "doubletons", "max_reads", "d50", "chao1",
+                             "simpson", "inverse_simpson", "gini", "shannon", "clonality"]
+
+
 # dcrx_clono_row_t: what dcrx_cdr3_device leaves of an entry (flags: productive, in_frame, stop, conserved_c, conserved_f from bit 0)
 CLONO_ROW_DTYPE = np.dtype([("hash", "<u8"), ("arena_off", "<u8"), ("start_cdr3", "<i4"), ("end_cdr3", "<i4"), ("seq_len", "<u4"),
                             ("status", "u1"), ("flags", "u1"), ("pad", "<u2")])
@@ -462,6 +470,7 @@ EXPORTS = [
     "dcrx_cdr3net_metric_work_bytes", "dcrx_cdr3_neighbours_metric_device", "dcrx_cdr3_network_metric", "dcrx_format_cdr3_edges_metric",
     "dcrx_overlap_set_hash_bits", "dcrx_overlap_run", "dcrx_overlap_destroy", "dcrx_overlap_info", "dcrx_overlap_export",
     "dcrx_overlap_pairs_device", "dcrx_format_overlap_public",
+    "dcrx_downsample_work_bytes", "dcrx_downsample_device", "dcrx_downsample", "dcrx_abundance_classes",
 ]
 
 _lib = None
@@ -610,6 +619,10 @@ def lib():
         "dcrx_overlap_info": (i32, [vp, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(OverlapStatsC)]),
         "dcrx_overlap_export": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dcrx_overlap_pairs_device": (i32, [u64, vp, vp, vp, u32, vp, vp]),
+        "dcrx_downsample_work_bytes": (u64, [u64, u32]),
+        "dcrx_downsample_device": (i32, [u32, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
+        "dcrx_downsample": (i32, [u32, u64, vp, vp, vp, u64, vp, vp, vp, vp]),
+        "dcrx_abundance_classes": (C.c_int64, [u32, u64, vp, vp, vp, vp, vp, vp]),
         "dcrx_format_overlap_public": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, u32, vp, vp, u32, vp, vp, vp,
                                                    vp, vp, u64]),
     }
@@ -1532,6 +1545,57 @@ def format_overlap_public(result: dict, sample_names, v_idx, j_idx, v_calls, j_c
     out = _uninitialised_bytes(max(1, need))
     check(int(lib().dcrx_format_overlap_public(*args, _bytes_address(out), need)))
     return bytes(out[:need])
+
+
+# ---- downsample and the abundance classes (`overlap --downsample`, `overlap --diversity`): include/dcrx.h "downsample" ----
+
+def downsample(samples, weights, n_samples: int, depths, seed: int) -> dict:
+    """dcrx_downsample on the current device: m rows (sample, weight), the sample ids non-decreasing, a depth per sample and
+    one 64-bit seed -> {"kept": per row the reads of the subsample, "reads": X_s, "depth_used": min(depth_s, X_s),
+    "threshold": T_s}, uint64 arrays."""
+    smp = np.ascontiguousarray(samples, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    d = np.ascontiguousarray(depths, dtype=np.uint64)
+    m, S = len(smp), int(n_samples)
+    if len(w) != m or len(d) != S:
+        raise ValueError("downsample: one sample and one weight per row, one depth per sample")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("downsample: the seed is 0 .. 2^64 - 1")
+    kept = np.zeros(max(m, 1), np.uint64)
+    reads, used, thr = (np.zeros(max(S, 1), np.uint64) for _ in range(3))
+    check(lib().dcrx_downsample(S, m, smp.ctypes.data, w.ctypes.data, d.ctypes.data if S else None, int(seed), kept.ctypes.data,
+                                reads.ctypes.data, used.ctypes.data, thr.ctypes.data))
+    return {"kept": kept[:m], "reads": reads[:S], "depth_used": used[:S], "threshold": thr[:S]}
+
+
+def downsample_work_bytes(m: int, n_samples: int) -> int:
+    """dcrx_downsample_work_bytes: the work space dcrx_downsample_device takes (0: refused)."""
+    return int(lib().dcrx_downsample_work_bytes(int(m), int(n_samples)))
+
+
+def downsample_device(n_samples: int, m: int, d_sample, d_weight, d_depth, seed: int, d_kept, d_reads, d_depth_used, d_threshold,
+                      d_work, work_bytes: int, stream=None):
+    """dcrx_downsample_device: the subsample over rows in HBM (DeviceBuffers), asynchronous on `stream`; nothing is copied
+    back."""
+    check(lib().dcrx_downsample_device(int(n_samples), int(m), d_sample.ptr, d_weight.ptr, d_depth.ptr, int(seed), d_kept.ptr,
+                                       d_reads.ptr, d_depth_used.ptr, d_threshold.ptr, d_work.ptr, int(work_bytes), stream))
+
+
+def abundance_classes(samples, groups, weights, n_samples: int) -> dict:
+    """dcrx_abundance_classes on the current device: n items (sample, group, weight) add into cells (sample, group); per
+    sample the distinct cell weights ascending with the number of cells of each, as CSR -> {"class_off": n_samples + 1
+    offsets, "class_count": the weights, "class_mult": the cells}.  A cell of weight 0 is in no class."""
+    smp = np.ascontiguousarray(samples, dtype=np.uint32)
+    grp = np.ascontiguousarray(groups, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    n, S = len(smp), int(n_samples)
+    if len(grp) != n or len(w) != n:
+        raise ValueError("abundance_classes: one sample, one group and one weight per item")
+    off = np.zeros(max(S, 0) + 1, np.uint64)
+    count, mult = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64)
+    k = check(int(lib().dcrx_abundance_classes(S, n, smp.ctypes.data, grp.ctypes.data, w.ctypes.data, off.ctypes.data, count.ctypes.data,
+                                               mult.ctypes.data)))
+    return {"class_off": off, "class_count": count[:k].copy(), "class_mult": mult[:k].copy()}
 
 
 def merge_parents_device(tables: "Tables", n: int, d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, d_ins_text, text_bytes: int,

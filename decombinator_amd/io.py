@@ -168,6 +168,15 @@ def _overlap(p: argparse.ArgumentParser):
     p.add_argument("--min-samples", dest="min_samples", type=int, default=2,
                    help="A clonotype is written to overlap_public.tsv when at least this many samples hold it (1 .. the number "
                         "of files; default 2)")
+    p.add_argument("--downsample", dest="downsample", type=str, default=None, metavar="N|min",
+                   help="Subsample every sample's reads without replacement to one depth before anything is compared (GPU): N "
+                        "reads (1 or more), or min for the reads of the smallest sample that has any.  A sample with fewer reads "
+                        "is kept whole")
+    p.add_argument("--seed", dest="seed", type=int, default=None,
+                   help="The seed of --downsample's subsample, 0 .. 2^64 - 1 (default 1); the same seed gives the same files")
+    p.add_argument("--diversity", dest="diversity", action="store_true",
+                   help="Also write overlap_diversity.tsv: per sample its reads, clonotypes, singletons, doubletons, largest "
+                        "clonotype, D50, Chao1, Simpson, inverse Simpson, Gini, Shannon entropy and clonality")
 
 
 def create_parser() -> argparse.ArgumentParser:
@@ -352,7 +361,8 @@ def _write_beside_tsv(text: bytes, suffix: str, what: str, inputargs: dict):
 
 
 def write_out_overlap(text: bytes, name: str, inputargs: dict):
-    """A file of the `overlap` sub-command: `<outpath><prefix><name>` (overlap_pairs.tsv, overlap_public.tsv), with
+    """A file of the `overlap` sub-command: `<outpath><prefix><name>` (overlap_pairs.tsv, overlap_public.tsv,
+    overlap_diversity.tsv), with
     write_out_clonotypes' rules: gzipped unless dontgzip, mode 666.  Returns the file's name."""
     outfilename = (inputargs.get("outpath") or "") + (inputargs.get("prefix") or "") + name
     if not inputargs.get("dontgzip"):

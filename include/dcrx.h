@@ -1028,6 +1028,72 @@ int64_t dcrx_format_overlap_public(uint64_t n_public, const uint32_t *head, cons
                                    const uint32_t *v_call_off, uint32_t n_j, const char *j_calls, const uint32_t *j_call_off,
                                    const uint64_t *off, const char *text, char *out, uint64_t out_cap);
 
+/* ---- downsample (`overlap --downsample`, `overlap --diversity`): a subsample of every sample's reads without replacement,
+ * to one depth, and the abundance classes a diversity table is computed from, on the GPU.  The reference has no counterpart:
+ * the contract below is this library's own.  The entries only ADD to ABI 5 ----
+ *
+ * Input: S samples, 1 <= S <= DCRX_DOWNSAMPLE_MAX_SAMPLES (4096: a design choice — a sample keeps a histogram of 32 KB and as
+ *   many bytes of candidate keys in the work space); m rows, m < 2^30, each a (sample uint32 < S, weight uint64) pair, the
+ *   sample ids non-decreasing (DCRX_E_INVALID otherwise); a depth per sample (uint64); one 64-bit seed.
+ * Reads: X_s is the sum of sample s's weights; the sum of X_s over all samples is below 2^40 (DCRX_E_UNSUPPORTED otherwise).
+ *   The reads of sample s are numbered r = 0 .. X_s - 1 in row order: row i owns [P_i, P_i + w_i), P the exclusive sum of the
+ *   weights inside the sample.
+ * Key of a read, all arithmetic mod 2^64:
+ *     fin(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *     key(s, r) = fin( fin(seed + (s + 1) * 0xD1B54A32D192ED03) + (r + 1) * 0x9E3779B97F4A7C15 )
+ *   fin is a bijection (xor-shifts and odd multipliers are), and the multiplier of r + 1 is odd, so the keys of one sample are
+ *   pairwise distinct: there are no ties and no tie rule.  A counter-based hash and not a cryptographic generator is a design
+ *   choice: every read's key is computed where it is needed, in any order, by any number of lanes; nobody is to be kept from
+ *   predicting a subsample.
+ * Kept: n_s = min(depth_s, X_s).  If n_s = X_s every read of the sample is kept and threshold[s] = 2^64 - 1.  Otherwise T_s is
+ *   the (n_s + 1)-th smallest key of the sample and the kept reads are those with key < T_s: exactly n_s of them.
+ * Output, each a function of the input alone (integer arithmetic only; no tile size, launch shape or order of arrival enters
+ *   it): kept[i] = the kept reads of row i; reads[s] = X_s; depth_used[s] = n_s; threshold[s] = T_s.
+ * A sample without rows, a row of weight 0 and a depth of 0 are valid. */
+#define DCRX_DOWNSAMPLE_MAX_SAMPLES 4096
+
+/* Bytes of device work space dcrx_downsample_device needs for m rows of n_samples samples; 0 for m >= 2^30 and for a number of
+ * samples outside 1 .. DCRX_DOWNSAMPLE_MAX_SAMPLES. */
+uint64_t dcrx_downsample_work_bytes(uint64_t m, uint32_t n_samples);
+
+/* The primitive, asynchronous on `hip_stream`, all arrays in device memory: d_sample and d_weight m entries, d_depth,
+ * d_reads, d_depth_used and d_threshold n_samples entries, d_kept m entries.  Nothing is copied back and nothing waits.
+ * The steps: an exclusive sum of the weights gives the offsets of one index space over the reads of all samples; the space is
+ * cut into tiles of 2048 consecutive reads, a block takes a run of tiles, finds a tile's first row by a search over the
+ * offsets and stages the 512 offsets behind it in LDS (the work is split by reads, never by rows: a row of any weight costs
+ * what its reads cost).  Selection: a histogram pass over the keys' top 12 bits (LDS histograms, flushed by integer atomics
+ * whose results are not read) finds the bin of every sample's threshold; while a bin holds more than 4096 keys a further pass
+ * on the next 12 bits follows for the samples concerned (none for samples below 16 million reads or so; the launches of a
+ * level nobody needs return at once); the keys of the bin are written out, and the threshold is the one with the wanted
+ * number of smaller keys.  A count pass evaluates the keys once more and adds, per run of a wave's lanes that fall in one
+ * row, one number onto kept[row].  Keys are never stored for all reads.
+ * d_work: dcrx_downsample_work_bytes(m, n_samples) bytes, 256-byte aligned; a smaller one is DCRX_E_INVALID, not a launch.
+ * DCRX_E_INVALID for a number of samples outside 1 .. DCRX_DOWNSAMPLE_MAX_SAMPLES or a null argument, DCRX_E_UNSUPPORTED
+ * for m >= 2^30.  What only the device can see: sample ids that are not non-decreasing below n_samples are outside the
+ * contract (nothing is read or written outside the arrays); a sum of the weights of 2^40 or more leaves reads[] as summed and
+ * kept, depth_used and threshold 0. */
+int dcrx_downsample_device(uint32_t n_samples, uint64_t m, const uint32_t *d_sample, const uint64_t *d_weight,
+                           const uint64_t *d_depth, uint64_t seed, uint64_t *d_kept, uint64_t *d_reads, uint64_t *d_depth_used,
+                           uint64_t *d_threshold, void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* The host entry, synchronous on the current device, on host arrays of the same shapes: checks the arguments (all of the
+ * contract's refusals, before any device call), uploads, runs the primitive on the null stream, copies back.  m == 0 is
+ * answered on the host (every sample: 0 reads, depth_used 0, threshold 2^64 - 1) and touches no device. */
+int dcrx_downsample(uint32_t n_samples, uint64_t m, const uint32_t *sample, const uint64_t *weight, const uint64_t *depth,
+                    uint64_t seed, uint64_t *kept_out, uint64_t *reads_out, uint64_t *depth_used_out, uint64_t *threshold_out);
+
+/* The abundance classes of samples (count of counts): n items, n < 2^30, each (sample < n_samples, group uint32, weight
+ * uint64), 1 <= n_samples <= DCRX_OVERLAP_MAX_SAMPLES.  The items of one (sample, group) add into a cell; a cell sum of 2^32
+ * or more is DCRX_E_UNSUPPORTED; a cell of weight 0 is dropped.  Per sample the distinct cell weights ascending, each with the
+ * number of cells that have it, as CSR: sample s's classes are class_off_out[s] .. class_off_out[s + 1] (n_samples + 1
+ * entries) of class_count_out (the weight) and class_mult_out (the cells), which hold n entries each.  Returns the number
+ * of classes or a negative dcrx_error.  Synchronous on the current device, host arrays: a stable radix sort by
+ * (sample, group), run heads and integer adds onto the heads whose results are not read give the cells; a sort by (sample,
+ * weight), run heads and an ordered compaction give the classes.  n == 0 touches no device. */
+int64_t dcrx_abundance_classes(uint32_t n_samples, uint64_t n, const uint32_t *sample, const uint32_t *group,
+                               const uint64_t *weight, uint64_t *class_off_out, uint32_t *class_count_out,
+                               uint64_t *class_mult_out);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
