@@ -255,86 +255,64 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_cluster_of_kernel(const uint32_
   if (i < n) cluster_of[i] = slot[label[i]];
 }
 
-// ---- work space of the primitive ----
-struct WorkPlan {
-  uint64_t key[2], idx[2], mark, bstart, sj, deg64, pres, cub, cub_bytes, total;
-};
-
 bool metric_exists(uint32_t metric) { return metric == METRIC_HAMMING || metric == METRIC_LEVENSHTEIN; }
 
-// (the Hamming plan is what it was: the presence masks of the Levenshtein walk come behind it)
-int plan_work(uint64_t n, uint32_t metric, WorkPlan *W) {
-  size_t cub_bytes = 0;
-  const uint64_t k = std::max<uint64_t>(n, 1);
-  int rc;
-  if ((rc = sort_pairs_bytes<uint32_t>(k, KEY_BITS, &cub_bytes)) || (rc = run_heads_bytes(k, &cub_bytes)) ||
-      (rc = exclusive_sum_bytes<uint64_t>(k, &cub_bytes))) return rc;
-  Carver C;
-  W->key[0] = C.take(n * 8); W->key[1] = C.take(n * 8);
-  W->idx[0] = C.take(n * 4); W->idx[1] = C.take(n * 4);
-  W->mark = C.take(n * 4); W->bstart = C.take(n * 4);
-  W->sj = C.take(n * 32);
-  W->deg64 = C.take(n * 8);
-  W->cub_bytes = cub_bytes;
-  W->cub = C.take(cub_bytes);
-  W->pres = metric == METRIC_LEVENSHTEIN ? C.take(n * 4) : 0;
-  W->total = C.at;
-  return DCRX_OK;
-}
-
-struct Sorted {      // what the degree pass leaves in the work space for the write pass
-  const uint4 *sj;
-  const uint64_t *key;
-  const uint32_t *idx, *bstart;
+// ---- work space of the primitive: the degree pass leaves the sorted keys and ranks (key[1], idx[1]), the bucket starts, the
+// packed strings and the presence masks there for the write pass
+struct Work {
+  uint64_t *key[2];
+  uint32_t *idx[2], *mark, *bstart;
+  uint4 *sj;
   uint64_t *deg64;
-  uint32_t *pres;      // (the Levenshtein walk's)
+  Scratch cub;
+  uint32_t *pres;      // (the Levenshtein walk's; null under Hamming, whose work space is what it was: the masks come behind it)
+  int carve(Pool &P, uint64_t n, uint32_t metric) {
+    size_t cub_bytes = 0;
+    const uint64_t k = std::max<uint64_t>(n, 1);
+    int rc;
+    if ((rc = sort_pairs_bytes<uint32_t>(k, KEY_BITS, &cub_bytes)) || (rc = run_heads_bytes(k, &cub_bytes)) ||
+        (rc = exclusive_sum_bytes<uint64_t>(k, &cub_bytes))) return rc;
+    P.get(&key[0], n); P.get(&key[1], n); P.get(&idx[0], n); P.get(&idx[1], n); P.get(&mark, n); P.get(&bstart, n);
+    P.get(&sj, 2 * n); P.get(&deg64, n); P.get(&cub, cub_bytes);
+    pres = nullptr;
+    if (metric == METRIC_LEVENSHTEIN) P.get(&pres, n);
+    return DCRX_OK;
+  }
 };
-Sorted sorted_view(uint8_t *w, const WorkPlan &W) {
-  return Sorted{reinterpret_cast<const uint4 *>(w + W.sj), reinterpret_cast<const uint64_t *>(w + W.key[1]),
-                reinterpret_cast<const uint32_t *>(w + W.idx[1]), reinterpret_cast<const uint32_t *>(w + W.bstart),
-                reinterpret_cast<uint64_t *>(w + W.deg64), reinterpret_cast<uint32_t *>(w + W.pres)};
-}
 
 // keys, sort, gather, the degree pass, the scan and the need
 int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint64_t *d_need,
-                uint8_t *w, const WorkPlan &W, hipStream_t s) {
+                const Work &W, hipStream_t s) {
   const bool lev = metric == METRIC_LEVENSHTEIN;
   const uint32_t n32 = (uint32_t)n;
-  uint64_t *key[2] = {reinterpret_cast<uint64_t *>(w + W.key[0]), reinterpret_cast<uint64_t *>(w + W.key[1])};
-  uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(w + W.idx[0]), reinterpret_cast<uint32_t *>(w + W.idx[1])};
-  uint32_t *mark = reinterpret_cast<uint32_t *>(w + W.mark), *bstart = reinterpret_cast<uint32_t *>(w + W.bstart);
-  const Scratch cub{w + W.cub, W.cub_bytes};
   int rc;
-  cdr3net_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[0], idx[0]);
+  cdr3net_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[0], W.idx[0]);
   HIP_TRY(hipGetLastError());
-  const Sorted S = sorted_view(w, W);
-  uint4 *sj = reinterpret_cast<uint4 *>(w + W.sj);
-  if ((rc = sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, KEY_BITS, s, lev ? (int)LEN_BITS : 0))) return rc;
-  if (lev) cdr3net_gather_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[1], idx[1], sj, mark, S.pres);
-  else cdr3net_gather_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(N, n32, key[1], idx[1], sj, mark, nullptr);
+  if ((rc = sort_pairs(W.cub, W.key[0], W.key[1], W.idx[0], W.idx[1], n, KEY_BITS, s, lev ? (int)LEN_BITS : 0))) return rc;
+  if (lev) cdr3net_gather_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, W.pres);
+  else cdr3net_gather_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, nullptr);
   HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, mark, bstart, n, s))) return rc;
+  if ((rc = run_heads(W.cub, W.mark, W.bstart, n, s))) return rc;
   if (lev)
-    cdr3net_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, n32, limit, d_degree, S.deg64, nullptr,
-                                                                   nullptr, 0, S.pres);
+    cdr3net_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, n32, limit, d_degree, W.deg64, nullptr,
+                                                                   nullptr, 0, W.pres);
   else
-    cdr3net_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, n32, limit, d_degree, S.deg64, nullptr,
+    cdr3net_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, n32, limit, d_degree, W.deg64, nullptr,
                                                                     nullptr, 0, nullptr);
   HIP_TRY(hipGetLastError());
-  if ((rc = exclusive_sum(cub, S.deg64, d_adj_off, n, s))) return rc;
-  cdr3net_need_kernel<<<1, 64, 0, s>>>(S.deg64, d_adj_off, n32, d_need);
+  if ((rc = exclusive_sum(W.cub, W.deg64, d_adj_off, n, s))) return rc;
+  cdr3net_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_adj_off, n32, d_need);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
 
-int run_write(uint64_t n, uint32_t limit, uint32_t metric, const uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, uint8_t *w,
-              const WorkPlan &W, hipStream_t s) {
-  const Sorted S = sorted_view(w, W);
+int run_write(uint64_t n, uint32_t limit, uint32_t metric, const uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, const Work &W,
+              hipStream_t s) {
   if (metric == METRIC_LEVENSHTEIN)
-    cdr3net_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, (uint32_t)n, limit, nullptr, nullptr,
-                                                                  d_adj_off, d_adj, adj_cap, S.pres);
+    cdr3net_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, (uint32_t)n, limit, nullptr, nullptr,
+                                                                  d_adj_off, d_adj, adj_cap, W.pres);
   else
-    cdr3net_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(S.sj, S.key, S.idx, S.bstart, (uint32_t)n, limit, nullptr, nullptr,
+    cdr3net_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, (uint32_t)n, limit, nullptr, nullptr,
                                                                    d_adj_off, d_adj, adj_cap, nullptr);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
@@ -358,17 +336,17 @@ int neighbours_device(const char *who, uint64_t m, const uint32_t *d_class, cons
   if (!d_class || !d_off || !d_degree || !d_adj_off || !d_work || (text_bytes && !d_text) || (adj_cap && !d_adj))
     return fail(DCRX_E_INVALID, who, "null argument");
   if ((uintptr_t)d_work % ALIGN) return fail(DCRX_E_INVALID, who, "the work space is not 256-byte aligned");
-  WorkPlan W;
-  int rc = plan_work(m, metric, &W);
+  Pool P(d_work);
+  Work W;
+  int rc = W.carve(P, m, metric);
   if (rc) return rc;
-  if (work_bytes < W.total)
+  if (work_bytes < P.bytes())
     return fail(DCRX_E_INVALID, who, metric == METRIC_HAMMING ? "the work space is smaller than dcrx_cdr3net_work_bytes(m, text_bytes)"
                                                               : "the work space is smaller than dcrx_cdr3net_metric_work_bytes(m, text_bytes, metric)");
   const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
-  uint8_t *w = static_cast<uint8_t *>(d_work);
-  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_adj_need, w, W, s))) return rc;
+  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_adj_need, W, s))) return rc;
   if (!d_adj || !adj_cap) return DCRX_OK;
-  return run_write(m, distance, metric, d_adj_off, d_adj, adj_cap, w, W, s);
+  return run_write(m, distance, metric, d_adj_off, d_adj, adj_cap, W, s);
 } catch (const std::exception &e) {      // (a message that could not be built)
   return set_err(DCRX_E_NOMEM, e.what());
 }
@@ -394,37 +372,34 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
   const uint64_t text_bytes = off[m] - off[0];
   if (text_bytes && !text) return fail(DCRX_E_INVALID, who, "text is null");
   const uint32_t m32 = (uint32_t)m;
-  WorkPlan W;
-  int rc = plan_work(m, metric, &W);
-  if (rc) return rc;
+  int rc;
   size_t cub_bytes = 0;
   if ((rc = exclusive_sum_bytes<uint32_t>(m, &cub_bytes))) return rc;
 
   Pool P;
+  Work W;
   uint32_t *d_cls, *d_degree, *d_label[2], *d_changed, *d_members, *d_ishead, *d_slot, *d_heads, *d_kept, *d_nn, *d_of;
   uint64_t *d_off, *d_weight, *d_adj_off, *d_need, *d_wout;
   unsigned long long *d_total;
-  uint8_t *d_text, *d_work, *d_cub;
+  uint8_t *d_text, *d_cub;
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_cls, m); P.get(&d_off, m + 1); P.get(&d_text, text_bytes); P.get(&d_weight, m); P.get(&d_degree, m);
-    P.get(&d_adj_off, m + 1); P.get(&d_need, 1); P.get(&d_work, W.total); P.get(&d_cub, cub_bytes); P.get(&d_label[0], m);
+    P.get(&d_adj_off, m + 1); P.get(&d_need, 1); P.get(&d_cub, cub_bytes); P.get(&d_label[0], m);
     P.get(&d_label[1], m); P.get(&d_changed, 1); P.get(&d_total, m); P.get(&d_members, m); P.get(&d_ishead, m); P.get(&d_slot, m);
     P.get(&d_heads, m); P.get(&d_kept, 1); P.get(&d_nn, m); P.get(&d_wout, m); P.get(&d_of, m);
-    if (pass == 0 && (rc = P.allocate())) return rc;
+    if ((rc = W.carve(P, m, metric)) || (pass == 0 && (rc = P.allocate()))) return rc;
   }
-  if ((rc = upload_spans(m, off, text, d_off, d_text))) return rc;
-  HIP_TRY(hipMemcpy(d_cls, cls, m * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_weight, weight, m * 8, hipMemcpyHostToDevice));
+  if ((rc = upload_spans(m, off, text, d_off, d_text)) || (rc = to_device(d_cls, cls, m)) || (rc = to_device(d_weight, weight, m))) return rc;
   const Nodes N{d_cls, d_off, d_text, text_bytes};
 
   // the degree pass, then an adjacency of exactly the entries it takes
-  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_need, d_work, W, nullptr))) return rc;
+  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_need, W, nullptr))) return rc;
   uint64_t need = 0;
-  HIP_TRY(hipMemcpy(&need, d_need, sizeof need, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&need, d_need, 1))) return rc;
   if (adj_need_out) *adj_need_out = need;
   dcrx::DevBuf<uint32_t> d_adj;
   if (d_adj.alloc(std::max<uint64_t>(need, 1))) return fail(DCRX_E_NOMEM, who, "the adjacency does not fit the device's memory");
-  if (need && (rc = run_write(m, distance, metric, d_adj_off, d_adj, need, d_work, W, nullptr))) return rc;
+  if (need && (rc = run_write(m, distance, metric, d_adj_off, d_adj.get(), need, W, nullptr))) return rc;
 
   // components: rounds of the neighbourhood's smallest label, then the labels followed to their ends
   cdr3net_label_init_kernel<<<grid_for(m), BLOCK>>>(m32, d_label[0]);
@@ -435,7 +410,7 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
     HIP_TRY(hipGetLastError());
     cdr3net_jump_kernel<<<grid_for(m), BLOCK>>>(d_label[1], m32, d_label[0]);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&changed, d_changed, 4, hipMemcpyDeviceToHost));      // (the round's one synchronisation)
+    if ((rc = to_host(&changed, d_changed, 1))) return rc;      // (the round's one synchronisation)
   }
 
   // totals onto the heads; the heads in rank order are the rows
@@ -446,20 +421,17 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
   HIP_TRY(hipGetLastError());
   if ((rc = compact(cub, d_ishead, d_slot, m32, PutIndex{d_heads}, d_kept, nullptr))) return rc;
   uint32_t c = 0;
-  HIP_TRY(hipMemcpy(&c, d_kept, 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&c, d_kept, 1))) return rc;
   cdr3net_rows_kernel<<<grid_for(c), BLOCK>>>(d_heads, c, d_total, d_members, d_nn, d_wout);
   HIP_TRY(hipGetLastError());
   cdr3net_cluster_of_kernel<<<grid_for(m), BLOCK>>>(d_label[0], d_slot, m32, d_of);
   HIP_TRY(hipGetLastError());
 
-  HIP_TRY(hipMemcpy(degree_out, d_degree, m * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(cluster_of_out, d_of, m * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(head_out, d_heads, (uint64_t)c * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(n_nodes_out, d_nn, (uint64_t)c * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(weight_out, d_wout, (uint64_t)c * 8, hipMemcpyDeviceToHost));
+  if ((rc = to_host(degree_out, d_degree, m)) || (rc = to_host(cluster_of_out, d_of, m)) || (rc = to_host(head_out, d_heads, c)) ||
+      (rc = to_host(n_nodes_out, d_nn, c)) || (rc = to_host(weight_out, d_wout, c))) return rc;
   if (adj_off_out) {
-    HIP_TRY(hipMemcpy(adj_off_out, d_adj_off, (m + 1) * 8, hipMemcpyDeviceToHost));
-    if (adj_out && need && need <= adj_cap) HIP_TRY(hipMemcpy(adj_out, d_adj, need * 4, hipMemcpyDeviceToHost));
+    if ((rc = to_host(adj_off_out, d_adj_off, m + 1))) return rc;
+    if (adj_out && need <= adj_cap && (rc = to_host(adj_out, d_adj.get(), need))) return rc;
   }
   if (stats_out) {
     stats_out->out_of_reach = out_of_reach;
@@ -523,9 +495,10 @@ extern "C" {
 
 uint64_t dcrx_cdr3net_metric_work_bytes(uint64_t m, uint64_t text_bytes, uint32_t metric) {
   (void)text_bytes;      // (the work space holds per-node keys, ranks and packed strings: the text's bytes do not enter it)
-  WorkPlan W;
-  if (m >= MAX_NODES || !metric_exists(metric) || plan_work(m, metric, &W) != DCRX_OK) return 0;
-  return W.total;
+  Pool P;
+  Work W;
+  if (m >= MAX_NODES || !metric_exists(metric) || W.carve(P, m, metric) != DCRX_OK) return 0;
+  return P.bytes();
 }
 
 uint64_t dcrx_cdr3net_work_bytes(uint64_t m, uint64_t text_bytes) { return dcrx_cdr3net_metric_work_bytes(m, text_bytes, METRIC_HAMMING); }

@@ -211,21 +211,17 @@ __global__ __launch_bounds__(BLOCK) void clono_gather_kernel(const uint32_t *__r
 }
 
 // ---- work space of the primitive ----
-struct WorkPlan {
-  uint64_t len, off, cub, cub_bytes, total;
+struct Work {
+  uint64_t *len, *off;
+  Scratch cub;
+  int carve(Pool &P, uint64_t n) {
+    size_t sum_bytes = 0;
+    const int rc = exclusive_sum_bytes<uint64_t>(std::max<uint64_t>(n, 1), &sum_bytes);
+    if (rc) return rc;
+    P.get(&len, n); P.get(&off, n); P.get(&cub, sum_bytes);
+    return DCRX_OK;
+  }
 };
-
-int plan_clono_work(uint64_t n, WorkPlan *W) {
-  size_t sum_bytes = 0;
-  const int rc = exclusive_sum_bytes<uint64_t>(std::max<uint64_t>(n, 1), &sum_bytes);
-  if (rc) return rc;
-  Carver C;
-  W->len = C.take(n * 8); W->off = C.take(n * 8);
-  W->cub_bytes = sum_bytes;
-  W->cub = C.take(sum_bytes);
-  W->total = C.at;
-  return DCRX_OK;
-}
 
 int device_view(dcrx_clono_genes_t *g, View *G) {
   int dev = -1;
@@ -233,9 +229,8 @@ int device_view(dcrx_clono_genes_t *g, View *G) {
   if (g->device >= 0 && g->device != dev)
     return set_err(DCRX_E_INVALID, "the gene set lives on the device of its first use: create another handle for another device");
   if (!g->d_blob) {
-    int rc = g->d_blob.alloc(g->blob.size());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(g->d_blob, g->blob.data(), g->blob.size(), hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = g->d_blob.alloc(g->blob.size())) || (rc = to_device(g->d_blob.get(), g->blob.data(), g->blob.size()))) return rc;
     g->device = dev;
   }
   *G = make_view(g->h, g->d_blob);
@@ -243,16 +238,14 @@ int device_view(dcrx_clono_genes_t *g, View *G) {
 }
 
 // the lengths pass and the scan; then the write pass
-int run_lengths(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d_rows, uint8_t *w, const WorkPlan &W, hipStream_t s) {
-  uint64_t *len = reinterpret_cast<uint64_t *>(w + W.len), *off = reinterpret_cast<uint64_t *>(w + W.off);
-  clono_calls_kernel<<<grid_for(n), BLOCK, 0, s>>>(G, E, (uint32_t)n, d_rows, len);
+int run_lengths(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d_rows, const Work &W, hipStream_t s) {
+  clono_calls_kernel<<<grid_for(n), BLOCK, 0, s>>>(G, E, (uint32_t)n, d_rows, W.len);
   HIP_TRY(hipGetLastError());
-  return exclusive_sum(Scratch{w + W.cub, W.cub_bytes}, len, off, n, s);
+  return exclusive_sum(W.cub, W.len, W.off, n, s);
 }
-int run_write(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d_rows, uint8_t *w, const WorkPlan &W, uint8_t *d_arena,
-              uint64_t arena_cap, uint64_t *d_need, hipStream_t s) {
-  clono_write_kernel<<<grid_for(n), BLOCK, 0, s>>>(G, E, (uint32_t)n, d_rows, reinterpret_cast<const uint64_t *>(w + W.len),
-                                                    reinterpret_cast<const uint64_t *>(w + W.off), d_arena, arena_cap, d_need);
+int run_write(const View &G, const Entries &E, uint64_t n, dcrx_clono_row_t *d_rows, const Work &W, uint8_t *d_arena, uint64_t arena_cap,
+              uint64_t *d_need, hipStream_t s) {
+  clono_write_kernel<<<grid_for(n), BLOCK, 0, s>>>(G, E, (uint32_t)n, d_rows, W.len, W.off, d_arena, arena_cap, d_need);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
@@ -295,9 +288,10 @@ int dcrx_clono_set_hash_bits(dcrx_clono_genes_t *g, uint32_t bits) {
 
 uint64_t dcrx_clono_work_bytes(uint64_t n, uint64_t text_bytes) {
   (void)text_bytes;      // (the work space holds per-entry lengths and offsets: the inserts' bytes do not enter it)
-  WorkPlan W;
-  if (n >= MAX_ENTRIES || plan_clono_work(n, &W) != DCRX_OK) return 0;
-  return W.total;
+  Pool P;
+  Work W;
+  if (n >= MAX_ENTRIES || W.carve(P, n) != DCRX_OK) return 0;
+  return P.bytes();
 }
 
 int dcrx_cdr3_device(dcrx_clono_genes_t *g, uint64_t n, const int32_t *d_v, const int32_t *d_j, const int32_t *d_vdel,
@@ -314,16 +308,16 @@ int dcrx_cdr3_device(dcrx_clono_genes_t *g, uint64_t n, const int32_t *d_v, cons
   if (!d_v || !d_j || !d_vdel || !d_jdel || !d_ins_off || !d_rows || !d_work || (text_bytes && !d_ins_text) || (arena_cap && !d_arena))
     return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: null argument");
   if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: the work space is not 256-byte aligned");
-  WorkPlan W;
-  int rc = plan_clono_work(n, &W);
+  Pool P(d_work);
+  Work W;
+  int rc = W.carve(P, n);
   if (rc) return rc;
-  if (work_bytes < W.total) return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: the work space is smaller than dcrx_clono_work_bytes(n, text_bytes)");
+  if (work_bytes < P.bytes()) return set_err(DCRX_E_INVALID, "dcrx_cdr3_device: the work space is smaller than dcrx_clono_work_bytes(n, text_bytes)");
   View G;
   if ((rc = device_view(g, &G))) return rc;
   const Entries E{d_v, d_j, d_vdel, d_jdel, d_ins_off, reinterpret_cast<const uint8_t *>(d_ins_text), text_bytes};
-  uint8_t *w = static_cast<uint8_t *>(d_work);
-  if ((rc = run_lengths(G, E, n, d_rows, w, W, s))) return rc;
-  return run_write(G, E, n, d_rows, w, W, reinterpret_cast<uint8_t *>(d_arena), arena_cap, d_arena_need, s);
+  if ((rc = run_lengths(G, E, n, d_rows, W, s))) return rc;
+  return run_write(G, E, n, d_rows, W, reinterpret_cast<uint8_t *>(d_arena), arena_cap, d_arena_need, s);
 }
 
 int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, const int32_t *j, const int32_t *vdel,
@@ -343,9 +337,7 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   const uint64_t text_bytes = ins_off[n] - ins_off[0];
   if (text_bytes && !ins_text) return set_err(DCRX_E_INVALID, "dcrx_clonotypes: ins_text is null");
   const uint32_t n32 = (uint32_t)n;
-  WorkPlan W;
-  int rc = plan_clono_work(n, &W);
-  if (rc) return rc;
+  int rc;
   size_t cub_bytes = 0;
   if ((rc = sort_pairs_bytes<uint32_t>(n, 64, &cub_bytes)) || (rc = exclusive_sum_bytes<uint32_t>(n, &cub_bytes)) ||
       (rc = run_heads_bytes(n, &cub_bytes)) || (rc = exclusive_sum_bytes<uint64_t>(2 * n, &cub_bytes))) return rc;
@@ -353,42 +345,43 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   if ((rc = device_view(g, &G))) return rc;
 
   Pool P;
+  Work W;
   int32_t *d_v, *d_j, *d_vdel, *d_jdel;
   uint64_t *d_count, *d_off, *d_need, *d_key[2], *d_dup, *d_topo, *d_jlen, *d_joff;
-  uint8_t *d_text, *d_work, *d_cub;
+  uint8_t *d_text, *d_cub;
   dcrx_clono_row_t *d_rows;
   unsigned long long *d_stats, *d_total, *d_top;
   uint32_t *d_flag, *d_rank[2], *d_head_of, *d_members, *d_rep, *d_ishead, *d_list[2], *d_nd, *d_repo, *d_rowof, *d_of;
   GroupWork R;      // (its slot and kept serve the other compactions too)
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_v, n); P.get(&d_j, n); P.get(&d_vdel, n); P.get(&d_jdel, n); P.get(&d_count, n); P.get(&d_off, n + 1);
-    P.get(&d_text, text_bytes); P.get(&d_rows, n); P.get(&d_work, W.total); P.get(&d_need, 1); P.get(&d_stats, CS_WORDS);
+    P.get(&d_text, text_bytes); P.get(&d_rows, n); P.get(&d_need, 1); P.get(&d_stats, CS_WORDS);
     P.get(&d_cub, cub_bytes); P.get(&d_flag, n); P.get(&d_key[0], n); P.get(&d_key[1], n); P.get(&d_rank[0], n);
     P.get(&d_rank[1], n); R.get(P, n); P.get(&d_head_of, n); P.get(&d_total, n); P.get(&d_members, n); P.get(&d_top, n);
     P.get(&d_rep, n); P.get(&d_ishead, n); P.get(&d_list[0], n); P.get(&d_list[1], n); P.get(&d_dup, n); P.get(&d_topo, n);
     P.get(&d_nd, n); P.get(&d_repo, n); P.get(&d_rowof, n); P.get(&d_of, n); P.get(&d_jlen, 2 * n); P.get(&d_joff, 2 * n);
-    if (pass == 0 && (rc = P.allocate())) return rc;
+    if ((rc = W.carve(P, n)) || (pass == 0 && (rc = P.allocate()))) return rc;
   }
   if ((rc = upload_table(n, v, j, vdel, jdel, count, ins_off, ins_text, d_v, d_j, d_vdel, d_jdel, d_count, d_off, d_text))) return rc;
   const Entries E{d_v, d_j, d_vdel, d_jdel, d_off, d_text, text_bytes};
 
   // the calls, then an arena of exactly the bytes the junctions take
-  if ((rc = run_lengths(G, E, n, d_rows, d_work, W, nullptr))) return rc;
-  if ((rc = run_write(G, E, n, d_rows, d_work, W, nullptr, 0, d_need, nullptr))) return rc;
+  if ((rc = run_lengths(G, E, n, d_rows, W, nullptr))) return rc;
+  if ((rc = run_write(G, E, n, d_rows, W, nullptr, 0, d_need, nullptr))) return rc;
   uint64_t need = 0;
-  HIP_TRY(hipMemcpy(&need, d_need, sizeof need, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&need, d_need, 1))) return rc;
   dcrx::DevBuf<uint8_t> d_arena;
   if ((rc = d_arena.alloc(std::max<uint64_t>(need, 1)))) return rc;
-  if ((rc = run_write(G, E, n, d_rows, d_work, W, d_arena, need, nullptr, nullptr))) return rc;
+  if ((rc = run_write(G, E, n, d_rows, W, d_arena, need, nullptr, nullptr))) return rc;
 
   // members and statistics
   unsigned long long st[CS_WORDS];
   std::memset(st, 0, sizeof st);
   st[CS_MOTIF_LEFT] = ~0ull;
-  HIP_TRY(hipMemcpy(d_stats, st, sizeof st, hipMemcpyHostToDevice));
+  if ((rc = to_device(d_stats, st, CS_WORDS))) return rc;
   clono_members_kernel<<<grid_for(n), BLOCK>>>(d_rows, d_count, n32, d_flag, d_stats);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
+  if ((rc = to_host(st, d_stats, CS_WORDS))) return rc;
   if (st[CS_MOTIF_LEFT] != ~0ull) {
     const uint64_t e = st[CS_MOTIF_LEFT];
     const int64_t ji = j[e] < 0 ? (int64_t)j[e] + g->h.n_j : (int64_t)j[e];
@@ -427,7 +420,7 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   HIP_TRY(hipGetLastError());
   if ((rc = compact(cub, d_ishead, R.slot, m32, PutIndex{d_list[0]}, R.kept, nullptr))) return rc;
   uint32_t c = 0;
-  HIP_TRY(hipMemcpy(&c, R.kept, 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&c, R.kept, 1))) return rc;
 
   // order: by the representative's rank, then (stably) by duplicate_count descending
   if ((rc = most_common_order(cub, d_list, d_key, d_rep, 32, d_total, c, nullptr))) return rc;
@@ -437,9 +430,8 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   clono_of_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, d_rowof, m32, d_of);
   HIP_TRY(hipGetLastError());
   if ((rc = exclusive_sum(cub, d_jlen, d_joff, 2 * (uint64_t)c, nullptr))) return rc;
-  HIP_TRY(hipMemcpy(junc_off_out, d_joff, 2 * (uint64_t)c * 8, hipMemcpyDeviceToHost));
   uint64_t last_len = 0;
-  HIP_TRY(hipMemcpy(&last_len, d_jlen + (2 * (uint64_t)c - 1), 8, hipMemcpyDeviceToHost));
+  if ((rc = to_host(junc_off_out, d_joff, 2 * (uint64_t)c)) || (rc = to_host(&last_len, d_jlen + (2 * (uint64_t)c - 1), 1))) return rc;
   const uint64_t out_bytes = junc_off_out[2 * (uint64_t)c - 1] + last_len;
   junc_off_out[2 * (uint64_t)c] = out_bytes;
   dcrx::DevBuf<uint8_t> d_out;
@@ -447,12 +439,9 @@ int64_t dcrx_clonotypes(dcrx_clono_genes_t *g, uint64_t n, const int32_t *v, con
   clono_gather_kernel<<<grid_for(c), BLOCK>>>(d_repo, d_rows, d_arena, d_jlen, d_joff, c, d_out);
   HIP_TRY(hipGetLastError());
   g->text.resize(out_bytes);
-  if (out_bytes) HIP_TRY(hipMemcpy(g->text.data(), d_out, out_bytes, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(rep_out, d_repo, (uint64_t)c * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(dup_out, d_dup, (uint64_t)c * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(ndcrs_out, d_nd, (uint64_t)c * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(top_out, d_topo, (uint64_t)c * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(clonotype_of_out, d_of, n * 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(reinterpret_cast<uint8_t *>(g->text.data()), d_out.get(), out_bytes)) || (rc = to_host(rep_out, d_repo, c)) ||
+      (rc = to_host(dup_out, d_dup, c)) || (rc = to_host(ndcrs_out, d_nd, c)) || (rc = to_host(top_out, d_topo, c)) ||
+      (rc = to_host(clonotype_of_out, d_of, n))) return rc;
   if (stats_out) {
     stats_out->clonotypes_out = c;
     for (uint32_t r = 0; r < c; r++) {

@@ -323,7 +323,8 @@ int ensure_stats(dcrx_counts *c, hipStream_t s) {
 // the true figures of the table (synchronises the stream): bounds come down to them
 int read_stats(dcrx_counts *c, hipStream_t s, uint64_t st[ST_WORDS]) {
   HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(st, c->stats, ST_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  const int rc = to_host(st, c->stats.get(), ST_WORDS);
+  if (rc) return rc;
   if (st[ST_OVERFLOW]) return set_err(DCRX_E_HIP, "dcrx_counts: the arena ran out of room during a count step (counts are incomplete)");
   c->bound_keys = st[ST_KEYS];
   c->bound_bytes = st[ST_ARENA];
@@ -523,13 +524,10 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
     rc = dev_alloc(d_total, 1);
     if (rc) return rc;
     unsigned long long total = 0;
-    hipError_t e = hipMemset(d_total, 0, sizeof(total));
-    if (e == hipSuccess) {
-      count_text_kernel<<<(unsigned)std::min<uint64_t>(grid_for(c->slots), 2048), BLOCK>>>(c->T.tag, c->T.hdr, c->slots, d_total);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(&total, d_total, sizeof(total), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "dcrx_counts_read (sizes)");
+    HIP_TRY(hipMemset(d_total, 0, sizeof(total)));
+    count_text_kernel<<<(unsigned)std::min<uint64_t>(grid_for(c->slots), 2048), BLOCK>>>(c->T.tag, c->T.hdr, c->slots, d_total);
+    HIP_TRY(hipGetLastError());
+    if ((rc = to_host(&total, d_total.get(), 1))) return rc;
     *text_bytes = total;
     return (int64_t)n;
   }
@@ -546,7 +544,7 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
     count_compact_kernel<<<grid_for(c->slots), BLOCK>>>(c->T.tag, c->slots, list[0], n_list);
     HIP_TRY(hipGetLastError());
     uint64_t got = 0;
-    HIP_TRY(hipMemcpy(&got, n_list, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if ((r = to_host(&got, n_list.get(), 1))) return r;
     if (got != n) return set_err(DCRX_E_HIP, "dcrx_counts_read: the table's live slots differ from its key count");
     if (!n) return DCRX_OK;
     size_t tb = 0;
@@ -556,8 +554,7 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
     uint64_t *fields[4] = {c->T.hdr, c->T.off, c->T.count, c->T.first};
     std::vector<uint64_t> *host[4] = {&hdr, &off, &cnt, &fst};
     for (int f = 0; f < 4; f++) {
-      if ((r = gather(fields[f], list[0], (uint32_t)n, 0, key[1], nullptr))) return r;
-      HIP_TRY(hipMemcpy(host[f]->data(), key[1], n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      if ((r = gather(fields[f], list[0], (uint32_t)n, 0, key[1], nullptr)) || (r = to_host(host[f]->data(), key[1], n))) return r;
     }
     return DCRX_OK;
   };
@@ -569,7 +566,7 @@ int64_t dcrx_counts_read(dcrx_counts_t *c, uint16_t *v, uint16_t *j, uint8_t *vd
   if (cap < n || text_cap < bytes || !v || !j || !vdel || !jdel || !count || !first || !ins_off || (bytes && !ins_text))
     return (int64_t)n;                                // (sizes only)
   std::vector<uint8_t> arena(st[ST_ARENA]);
-  if (!arena.empty()) HIP_TRY(hipMemcpy(arena.data(), c->arena, arena.size(), hipMemcpyDeviceToHost));
+  if ((rc = to_host(arena.data(), c->arena.get(), arena.size()))) return rc;
   uint64_t at = 0;
   for (uint64_t k = 0; k < n; k++) {
     const uint64_t h = hdr[k];

@@ -1,13 +1,14 @@
 // dcrx_group.h — what the count (dcrx_count.hip), the error merge (dcrx_merge.hip), the clonotype step (dcrx_clono.hip), the
-// CDR3 network (dcrx_cdr3net.hip) and the overlap step (dcrx_overlap.hip) share to group, compact and order a table on the
-// device, each written once: the launch geometry, the 64-bit wave sum, the one-allocation pool and the offset carver,
-// hipCUB's four calls with their scratch, run heads, the ordered compaction, exact groups under a hash (the rounds of the
-// clonotype and overlap steps), the most_common() order and the upload of offsets with their text and of a counted table.
+// CDR3 network (dcrx_cdr3net.hip), the overlap step (dcrx_overlap.hip) and the downsampling step (dcrx_rarefy.hip) share to
+// group, compact and order a table on the device, each written once: the launch geometry, the 64-bit wave sum, the pool
+// that carves a work space, the typed blocking copies, hipCUB's four calls with their scratch, run heads, the ordered
+// compaction, cells (the sums of runs of one key), exact groups under a hash (the rounds of the clonotype and overlap steps),
+// the most_common() order and the upload of offsets with their text and of a counted table.
 // Private to those translation units (HIP only, as dcrx_hip.h).
 // Nothing here allocates behind the caller's back (Pool::allocate is the caller's one allocation), and nothing synchronises
-// but exact_groups, once per round, and the uploads, which are blocking copies; every launch and hipCUB call goes to the
-// stream it is handed.  Everything has internal linkage, as the kernels of those units have: a unit's instances of the
-// templated kernels are its own.
+// but exact_groups, once per round, and to_device, to_host and the uploads, which are blocking copies; every launch and
+// hipCUB call goes to the stream it is handed.  Everything has internal linkage, as the kernels of those units have: a unit's
+// instances of the templated kernels are its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,37 +37,55 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
   return x;
 }
 
-// device memory of one call of a host entry: ONE allocation, carved into 256-byte aligned buffers (a first pass over the
-// same requests, with no memory behind it, adds up the size)
-struct Pool {
-  dcrx::DevBuf<uint8_t> base;
-  uint64_t at = 0;
-  template <class T> void get(T **p, uint64_t count) {
-    *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += aligned(std::max<uint64_t>(count, 1) * sizeof(T));
-  }
-  int allocate() {
-    const int rc = base.alloc(std::max<uint64_t>(at, 1));
-    at = 0;
-    return rc;
-  }
-};
-
-// the offsets of a caller's work space, carved the same way
-struct Carver {
-  uint64_t at = 0;
-  uint64_t take(uint64_t bytes) { const uint64_t here = at; at += aligned(std::max<uint64_t>(bytes, 1)); return here; }
-};
-
-// ---- hipCUB: the four calls in use.  A *_bytes query folds the scratch a call over n items wants into `most` (a plan
-// asks for every call it will make and holds the largest); the call itself takes its scratch BY VALUE, as hipCUB
-// overwrites the size it is handed.  Sorts are stable and ascending over the key's bits [begin_bit, end_bit), begin_bit 0
-// unless given; results are in *_out.
-// (The scans hand hipCUB plain pointers for input too: it makes its kernels per iterator type, and one set is enough.)
+// hipCUB's scratch: a call takes it BY VALUE, as hipCUB overwrites the size it is handed
 struct Scratch {
   void *p;
   size_t bytes;
 };
+
+// A work space carved into 256-byte aligned buffers.  One list of typed requests serves three ways: over no memory it adds
+// up the size (bytes()); over memory of the caller's (a device entry's d_work) it hands out the pointers; and a host entry
+// runs it twice, the second time over its ONE allocation of what the first added up (allocate()).
+struct Pool {
+  Pool() = default;
+  explicit Pool(void *mem) : base(static_cast<uint8_t *>(mem)) {}
+  template <class T> void get(T **p, uint64_t count) {
+    *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+    at += aligned(std::max<uint64_t>(count, 1) * sizeof(T));
+  }
+  void get(Scratch *t, size_t bytes) {
+    uint8_t *p;
+    get(&p, bytes);
+    *t = Scratch{p, bytes};
+  }
+  uint64_t bytes() const { return at; }      // asked for so far
+  int allocate() {
+    const int rc = own.alloc(std::max<uint64_t>(at, 1));
+    base = own;
+    at = 0;
+    return rc;
+  }
+
+ private:
+  dcrx::DevBuf<uint8_t> own;
+  uint8_t *base = nullptr;
+  uint64_t at = 0;
+};
+
+// ---- blocking copies of n elements (none: nothing is copied)
+template <class T> int to_device(T *d, const T *h, uint64_t n) {
+  if (n) HIP_TRY(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
+  return DCRX_OK;
+}
+template <class T> int to_host(T *h, const T *d, uint64_t n) {
+  if (n) HIP_TRY(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  return DCRX_OK;
+}
+
+// ---- hipCUB: the four calls in use.  A *_bytes query folds the scratch a call over n items wants into `most` (a carve
+// asks for every call it will make and holds the largest).  Sorts are stable and ascending over the key's bits
+// [begin_bit, end_bit), begin_bit 0 unless given; results are in *_out.
+// (The scans hand hipCUB plain pointers for input too: it makes its kernels per iterator type, and one set is enough.)
 
 template <class V> int sort_pairs_bytes(uint64_t n, int end_bit, size_t *most) {
   size_t b = 0;
@@ -131,6 +150,40 @@ struct PutIndex {      // the position itself
   uint32_t *list;
   __device__ void operator()(uint32_t slot, uint32_t i) const { list[slot] = i; }
 };
+
+// ---- cells: a cell is a run of equal 64-bit keys in sorted order, its members' weights summed onto the run's first position
+__global__ __launch_bounds__(BLOCK) void run_marks_kernel(const uint64_t *__restrict__ key, uint32_t n, uint32_t *__restrict__ mark) {
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s < n) mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
+}
+inline int run_marks(const uint64_t *key, uint32_t n, uint32_t *mark, hipStream_t s) {
+  run_marks_kernel<<<grid_for(n), BLOCK, 0, s>>>(key, n, mark);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
+// every position's weight onto its cell's first position (64-bit atomics whose results are not read)
+__global__ __launch_bounds__(BLOCK) void cell_sums_kernel(const uint32_t *__restrict__ head, const uint32_t *__restrict__ idx,
+                                                          const uint64_t *__restrict__ weight, uint32_t n,
+                                                          unsigned long long *__restrict__ sum, uint32_t *__restrict__ is_head) {
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= n) return;
+  const uint32_t h = head[s];
+  atomicAdd(&sum[h], (unsigned long long)weight[idx[s]]);
+  is_head[s] = h == s ? 1u : 0u;
+}
+
+// over n >= 1 sorted keys, idx[s] the source position of sorted position s: head[s] is where the cell of s starts,
+// sum[head] the cell's weight[idx[.]] added up (zero elsewhere), is_head[s] whether s starts a cell; mark is overwritten
+inline int cell_sums(Scratch t, const uint64_t *key, const uint32_t *idx, const uint64_t *weight, uint32_t n, uint32_t *mark,
+                     uint32_t *head, unsigned long long *sum, uint32_t *is_head, hipStream_t s) {
+  int rc;
+  if ((rc = run_marks(key, n, mark, s)) || (rc = run_heads(t, mark, head, n, s))) return rc;
+  HIP_TRY(hipMemsetAsync(sum, 0, (uint64_t)n * sizeof *sum, s));
+  cell_sums_kernel<<<grid_for(n), BLOCK, 0, s>>>(head, idx, weight, n, sum, is_head);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
 
 // ---- exact groups under a hash.  The rows come sorted stably by hash: key[s] is the hash at sorted position s, rank[s] the
 // row there, so a run of one hash is in rank order.  Rounds: every active position is compared in full, by same(rank, rank),
@@ -241,19 +294,17 @@ inline int upload_spans(uint64_t n, const uint64_t *off, const char *text, uint6
     return dcrx::set_err(DCRX_E_NOMEM, e.what());
   }
   for (uint64_t k = 0; k <= n; k++) rebased[k] = off[k] - text0;
-  HIP_TRY(hipMemcpy(d_off, rebased.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-  if (text_bytes) HIP_TRY(hipMemcpy(d_text, text + text0, text_bytes, hipMemcpyHostToDevice));
-  return DCRX_OK;
+  const int rc = to_device(d_off, rebased.data(), n + 1);
+  if (rc || !text_bytes) return rc;      // (no text: `text` may be null)
+  return to_device(d_text, reinterpret_cast<const uint8_t *>(text + text0), text_bytes);
 }
 // ... and a counted table: genes, deletions, counts, and its inserts that way
 template <class G, class D> int upload_table(uint64_t n, const G *v, const G *j, const D *vdel, const D *jdel, const uint64_t *count,
                                              const uint64_t *ins_off, const char *ins_text, G *d_v, G *d_j, D *d_vdel, D *d_jdel,
                                              uint64_t *d_count, uint64_t *d_off, uint8_t *d_text) {
-  HIP_TRY(hipMemcpy(d_v, v, n * sizeof(G), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_j, j, n * sizeof(G), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_vdel, vdel, n * sizeof(D), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_jdel, jdel, n * sizeof(D), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_count, count, n * 8, hipMemcpyHostToDevice));
+  int rc;
+  if ((rc = to_device(d_v, v, n)) || (rc = to_device(d_j, j, n)) || (rc = to_device(d_vdel, vdel, n)) || (rc = to_device(d_jdel, jdel, n)) ||
+      (rc = to_device(d_count, count, n))) return rc;
   return upload_spans(n, ins_off, ins_text, d_off, d_text);
 }
 

@@ -199,25 +199,40 @@ __global__ __launch_bounds__(BLOCK) void merge_totals_kernel(const uint32_t *__r
   }
 }
 
-struct WorkPlan {
-  uint64_t key[2], idx[2], sj, sc, head, bstart, cub, cub_bytes, total;
+// ---- work space of the primitive; when it is done the host entry's compaction and order reuse key, idx and cub
+struct Work {
+  uint64_t *key[2];
+  uint32_t *idx[2];
+  uint4 *sj;
+  uint64_t *sc;
+  uint32_t *head, *bstart;
+  Scratch cub;
+  int carve(Pool &P, uint64_t n) {
+    // (the largest of the primitive's sort and scan and of the host entry's scan and 64-bit sorts)
+    const uint64_t wn = std::max<uint64_t>(n, 1);
+    size_t cub_bytes = 0;
+    int rc;
+    if ((rc = sort_pairs_bytes<uint32_t>(wn, (int)KEY_BITS, &cub_bytes)) || (rc = run_heads_bytes(wn, &cub_bytes)) ||
+        (rc = exclusive_sum_bytes<uint32_t>(wn, &cub_bytes)) || (rc = sort_pairs_bytes<uint32_t>(wn, 64, &cub_bytes))) return rc;
+    P.get(&key[0], n); P.get(&key[1], n); P.get(&idx[0], n); P.get(&idx[1], n); P.get(&sj, 2 * n); P.get(&sc, n);
+    P.get(&head, n); P.get(&bstart, n); P.get(&cub, cub_bytes);
+    return DCRX_OK;
+  }
 };
 
-int plan_merge_work(uint64_t n, WorkPlan *W) {
-  // (the largest of the primitive's sort and scan and of the host entry's scan and 64-bit sorts, which reuse the space)
-  const uint64_t wn = std::max<uint64_t>(n, 1);
-  size_t cub_bytes = 0;
+// keys, sort, gather, bucket starts, parents (E.rows are the tables' windows)
+int run_parents(const Entries &E, uint64_t n, uint32_t distance, uint64_t ratio, uint32_t *d_parent, uint8_t *d_reach, const Work &W,
+                hipStream_t s) {
+  const uint32_t n32 = (uint32_t)n;
   int rc;
-  if ((rc = sort_pairs_bytes<uint32_t>(wn, (int)KEY_BITS, &cub_bytes)) || (rc = run_heads_bytes(wn, &cub_bytes)) ||
-      (rc = exclusive_sum_bytes<uint32_t>(wn, &cub_bytes)) || (rc = sort_pairs_bytes<uint32_t>(wn, 64, &cub_bytes))) return rc;
-  Carver C;
-  W->key[0] = C.take(n * 8); W->key[1] = C.take(n * 8);
-  W->idx[0] = C.take(n * 4); W->idx[1] = C.take(n * 4);
-  W->sj = C.take(n * WORDS * 4); W->sc = C.take(n * 8);
-  W->head = C.take(n * 4); W->bstart = C.take(n * 4);
-  W->cub_bytes = cub_bytes;
-  W->cub = C.take(cub_bytes);
-  W->total = C.at;
+  merge_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, W.key[0], W.idx[0]);
+  HIP_TRY(hipGetLastError());
+  if ((rc = sort_pairs(W.cub, W.key[0], W.key[1], W.idx[0], W.idx[1], n, (int)KEY_BITS, s))) return rc;
+  merge_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, W.key[1], W.idx[1], W.sj, W.sc, W.head);
+  HIP_TRY(hipGetLastError());
+  if ((rc = run_heads(W.cub, W.head, W.bstart, n, s))) return rc;
+  merge_parents_kernel<<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.sc, W.key[1], W.idx[1], W.bstart, n32, distance, ratio, d_parent, d_reach);
+  HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
 
@@ -226,9 +241,10 @@ int plan_merge_work(uint64_t n, WorkPlan *W) {
 extern "C" {
 
 uint64_t dcrx_merge_work_bytes(uint64_t n) {
-  WorkPlan W;
-  if (n >= (1ull << 31) || plan_merge_work(n, &W) != DCRX_OK) return 0;
-  return W.total;
+  Pool P;
+  Work W;
+  if (n >= (1ull << 31) || W.carve(P, n) != DCRX_OK) return 0;
+  return P.bytes();
 }
 
 int dcrx_merge_parents_device(dcrx_tables_t *tables, uint64_t n, const uint16_t *d_v, const uint16_t *d_j,
@@ -244,31 +260,14 @@ int dcrx_merge_parents_device(dcrx_tables_t *tables, uint64_t n, const uint16_t 
   if (!d_v || !d_j || !d_vdel || !d_jdel || !d_count || !d_ins_off || !d_parent || !d_work || (text_bytes && !d_ins_text))
     return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: null argument");
   if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is not 256-byte aligned");
-  WorkPlan W;
-  int rc = plan_merge_work(n, &W);
+  Pool P(d_work);
+  Work W;
+  int rc = W.carve(P, n);
   if (rc) return rc;
-  if (work_bytes < W.total) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is smaller than dcrx_merge_work_bytes(n)");
+  if (work_bytes < P.bytes()) return set_err(DCRX_E_INVALID, "dcrx_merge_parents_device: the work space is smaller than dcrx_merge_work_bytes(n)");
   Entries E{d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, reinterpret_cast<const uint8_t *>(d_ins_text), text_bytes, nullptr, 0, 0};
-  rc = dcrx::merge_windows(tables, &E.rows, &E.n_v, &E.n_j);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)hip_stream;
-  uint8_t *w = static_cast<uint8_t *>(d_work);
-  uint64_t *key[2] = {reinterpret_cast<uint64_t *>(w + W.key[0]), reinterpret_cast<uint64_t *>(w + W.key[1])};
-  uint32_t *idx[2] = {reinterpret_cast<uint32_t *>(w + W.idx[0]), reinterpret_cast<uint32_t *>(w + W.idx[1])};
-  uint4 *sj = reinterpret_cast<uint4 *>(w + W.sj);
-  uint64_t *sc = reinterpret_cast<uint64_t *>(w + W.sc);
-  uint32_t *head = reinterpret_cast<uint32_t *>(w + W.head), *bstart = reinterpret_cast<uint32_t *>(w + W.bstart);
-  const uint32_t n32 = (uint32_t)n;
-  merge_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, key[0], idx[0]);
-  HIP_TRY(hipGetLastError());
-  const Scratch cub{w + W.cub, W.cub_bytes};
-  if ((rc = sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, (int)KEY_BITS, s))) return rc;
-  merge_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(E, n32, key[1], idx[1], sj, sc, head);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, head, bstart, n, s))) return rc;
-  merge_parents_kernel<<<grid_for(n), BLOCK, 0, s>>>(sj, sc, key[1], idx[1], bstart, n32, distance, ratio, d_parent, d_reach);
-  HIP_TRY(hipGetLastError());
-  return DCRX_OK;
+  if ((rc = dcrx::merge_windows(tables, &E.rows, &E.n_v, &E.n_j))) return rc;
+  return run_parents(E, n, distance, ratio, d_parent, d_reach, W, (hipStream_t)hip_stream);
 }
 
 int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, const uint16_t *j, const uint8_t *vdel,
@@ -283,38 +282,35 @@ int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, co
   if (!n) return 0;
   if (!v || !j || !vdel || !jdel || !count || !first || !ins_off || !root_of_out || !order_out || !count_out || !first_out)
     return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: null argument");
-  const uint32_t *rows = nullptr;
-  uint32_t n_v = 0, n_j = 0;
-  int rc = dcrx::merge_windows(tables, &rows, &n_v, &n_j);
+  Entries E{};
+  int rc = dcrx::merge_windows(tables, &E.rows, &E.n_v, &E.n_j);
   if (rc) return rc;
   for (uint64_t k = 0; k < n; k++) {
-    if (v[k] >= n_v || j[k] >= n_j) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: an entry names a v or j the tables do not have");
+    if (v[k] >= E.n_v || j[k] >= E.n_j) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: an entry names a v or j the tables do not have");
     if (ins_off[k + 1] < ins_off[k]) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: offsets go backwards");
   }
   const uint64_t text_bytes = ins_off[n] - ins_off[0];
   if (text_bytes && !ins_text) return set_err(DCRX_E_INVALID, "dcrx_merge_dcrs: ins_text is null");
   const uint32_t n32 = (uint32_t)n;
-  const uint64_t work_bytes = dcrx_merge_work_bytes(n);
-  if (!work_bytes) return DCRX_E_HIP;                      // (plan_merge_work left the message)
 
   Pool P;
+  Work W;
   uint16_t *d_v, *d_j;
-  uint8_t *d_vdel, *d_jdel, *d_reach, *d_text, *d_work;
-  uint64_t *d_count, *d_first, *d_off, *d_key[2];
+  uint8_t *d_vdel, *d_jdel, *d_reach, *d_text;
+  uint64_t *d_count, *d_first, *d_off;
   unsigned long long *d_tc, *d_tf, *d_stats;
-  uint32_t *d_r[2], *d_d[2], *d_changed, *d_isroot, *d_slot, *d_list[2];
+  uint32_t *d_r[2], *d_d[2], *d_changed, *d_isroot, *d_slot;
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_v, n); P.get(&d_j, n); P.get(&d_vdel, n); P.get(&d_jdel, n); P.get(&d_reach, n); P.get(&d_text, text_bytes);
     P.get(&d_count, n); P.get(&d_first, n); P.get(&d_off, n + 1); P.get(&d_tc, n); P.get(&d_tf, n); P.get(&d_stats, MS_WORDS);
-    P.get(&d_r[0], n); P.get(&d_r[1], n); P.get(&d_d[0], n); P.get(&d_d[1], n); P.get(&d_changed, 1); P.get(&d_work, work_bytes);
-    if (pass == 0 && (rc = P.allocate())) return rc;
+    P.get(&d_r[0], n); P.get(&d_r[1], n); P.get(&d_d[0], n); P.get(&d_d[1], n); P.get(&d_changed, 1);
+    if ((rc = W.carve(P, n)) || (pass == 0 && (rc = P.allocate()))) return rc;
   }
   if ((rc = upload_table(n, v, j, vdel, jdel, count, ins_off, ins_text, d_v, d_j, d_vdel, d_jdel, d_count, d_off, d_text))) return rc;
-  HIP_TRY(hipMemcpy(d_first, first, n * 8, hipMemcpyHostToDevice));
+  if ((rc = to_device(d_first, first, n))) return rc;
 
-  rc = dcrx_merge_parents_device(tables, n, d_v, d_j, d_vdel, d_jdel, d_count, d_off, reinterpret_cast<const char *>(d_text),
-                                 text_bytes, distance, ratio, d_r[0], d_reach, d_work, work_bytes, nullptr);
-  if (rc) return rc;
+  E.v = d_v; E.j = d_j; E.vdel = d_vdel; E.jdel = d_jdel; E.count = d_count; E.ins_off = d_off; E.ins_text = d_text; E.text_bytes = text_bytes;
+  if ((rc = run_parents(E, n, distance, ratio, d_r[0], d_reach, W, nullptr))) return rc;
 
   // roots: pointer jumping until no pointer moves (a round halves every entry's way to its root)
   merge_depth_init_kernel<<<grid_for(n), BLOCK>>>(d_r[0], n32, d_d[0]);
@@ -325,7 +321,7 @@ int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, co
     HIP_TRY(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), nullptr));
     merge_jump_kernel<<<grid_for(n), BLOCK>>>(d_r[cur], d_d[cur], n32, d_r[cur ^ 1], d_d[cur ^ 1], d_changed);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&changed, d_changed, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if ((rc = to_host(&changed, d_changed, 1))) return rc;
     if (!changed) break;                                    // (both buffers hold the same roots and depths now)
     cur ^= 1;
   }
@@ -340,24 +336,15 @@ int64_t dcrx_merge_dcrs(dcrx_tables_t *tables, uint64_t n, const uint16_t *v, co
   merge_totals_kernel<<<grid_for(n), BLOCK>>>(d_root, d_depth, d_reach, d_count, d_first, n32, d_tc, d_tf, d_isroot, d_stats);
   HIP_TRY(hipGetLastError());
   unsigned long long st[MS_WORDS];
-  HIP_TRY(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(root_of_out, d_root, n * 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(st, d_stats, MS_WORDS)) || (rc = to_host(root_of_out, d_root, n))) return rc;
   const uint64_t m = n - st[MS_MERGED];
   const uint32_t m32 = (uint32_t)m;
 
   // the roots in rank order, then by first ordinal, then (stably) by count descending; the work space is free again
-  WorkPlan W;
-  if ((rc = plan_merge_work(n, &W))) return rc;
-  d_key[0] = reinterpret_cast<uint64_t *>(d_work + W.key[0]); d_key[1] = reinterpret_cast<uint64_t *>(d_work + W.key[1]);
-  d_list[0] = reinterpret_cast<uint32_t *>(d_work + W.idx[0]); d_list[1] = reinterpret_cast<uint32_t *>(d_work + W.idx[1]);
-  const Scratch cub{d_work + W.cub, W.cub_bytes};
-  if ((rc = compact(cub, d_isroot, d_slot, n32, PutIndex{d_list[0]}, nullptr, nullptr)) ||      // (their number is m)
-      (rc = most_common_order(cub, d_list, d_key, d_tf, 64, d_tc, m32, nullptr))) return rc;
-  HIP_TRY(hipMemcpy(order_out, d_list[0], m * 4, hipMemcpyDeviceToHost));
-  if ((rc = gather(d_tc, d_list[0], m32, 0, d_key[1], nullptr))) return rc;
-  HIP_TRY(hipMemcpy(count_out, d_key[1], m * 8, hipMemcpyDeviceToHost));
-  if ((rc = gather(d_tf, d_list[0], m32, 0, d_key[1], nullptr))) return rc;
-  HIP_TRY(hipMemcpy(first_out, d_key[1], m * 8, hipMemcpyDeviceToHost));
+  if ((rc = compact(W.cub, d_isroot, d_slot, n32, PutIndex{W.idx[0]}, nullptr, nullptr)) ||      // (their number is m)
+      (rc = most_common_order(W.cub, W.idx, W.key, d_tf, 64, d_tc, m32, nullptr)) || (rc = to_host(order_out, W.idx[0], m)) ||
+      (rc = gather(d_tc, W.idx[0], m32, 0, W.key[1], nullptr)) || (rc = to_host(count_out, W.key[1], m)) ||
+      (rc = gather(d_tf, W.idx[0], m32, 0, W.key[1], nullptr)) || (rc = to_host(first_out, W.key[1], m))) return rc;
   if (stats_out) {
     stats_out->roots_out = m;
     stats_out->out_of_reach = st[MS_OUT_OF_REACH];

@@ -105,22 +105,6 @@ __global__ __launch_bounds__(BLOCK) void overlap_cell_keys_kernel(const uint32_t
   idx[i] = i;
 }
 
-__global__ __launch_bounds__(BLOCK) void overlap_cell_marks_kernel(const uint64_t *__restrict__ key, uint32_t m, uint32_t *__restrict__ mark) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s < m) mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
-}
-
-// every row's weight onto its cell's first position
-__global__ __launch_bounds__(BLOCK) void overlap_cell_sums_kernel(const uint32_t *__restrict__ cell_head, const uint32_t *__restrict__ idx,
-                                                                  const uint64_t *__restrict__ weight, uint32_t m,
-                                                                  unsigned long long *__restrict__ sum, uint32_t *__restrict__ is_head) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= m) return;
-  const uint32_t h = cell_head[s];
-  atomicAdd(&sum[h], (unsigned long long)weight[idx[s]]);
-  is_head[s] = h == s ? 1u : 0u;
-}
-
 // what the compaction leaves of a cell, and what the cell adds to its group
 struct PutCell {
   const uint64_t *key;
@@ -307,10 +291,8 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
     P.get(&d_cub, cub_bytes);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
-  if ((rc = upload_spans(m, off, text, d_off, d_text))) return rc;
-  HIP_TRY(hipMemcpy(d_sample, sample, m * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_cls, cls, m * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_weight, weight, m * 8, hipMemcpyHostToDevice));
+  if ((rc = upload_spans(m, off, text, d_off, d_text)) || (rc = to_device(d_sample, sample, m)) || (rc = to_device(d_cls, cls, m)) ||
+      (rc = to_device(d_weight, weight, m))) return rc;
   const Rows R{d_cls, d_off, d_text};
   const Scratch cub{d_cub, cub_bytes};
 
@@ -329,27 +311,21 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
   overlap_group_of_kernel<<<grid_for(m), BLOCK>>>(d_head_of, d_sorted, W.slot, m32, d_group_of, d_head_rank);
   HIP_TRY(hipGetLastError());
   uint32_t last[2] = {0, 0};
-  HIP_TRY(hipMemcpy(&last[0], W.slot + (m - 1), 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&last[1], d_flag + (m - 1), 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&last[0], W.slot + (m - 1), 1)) || (rc = to_host(&last[1], d_flag + (m - 1), 1))) return rc;
   const uint32_t n_groups = last[0] + last[1];
 
   // cells: the rows sorted (stably) by (group, sample); a run is a cell
   overlap_cell_keys_kernel<<<grid_for(m), BLOCK>>>(d_group_of, d_sample, m32, d_key[0], d_rank[0]);
   HIP_TRY(hipGetLastError());
   if ((rc = sort_pairs(cub, d_key[0], d_key[1], d_rank[0], d_rank[1], m, bits_for(n_groups) + (int)SAMPLE_BITS, nullptr))) return rc;
-  overlap_cell_marks_kernel<<<grid_for(m), BLOCK>>>(d_key[1], m32, W.mark);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, W.mark, W.first, m, nullptr))) return rc;
-  HIP_TRY(hipMemsetAsync(d_sum, 0, m * 8, nullptr));
   HIP_TRY(hipMemsetAsync(d_ns, 0, ((uint64_t)n_groups + 1) * 4, nullptr));
   HIP_TRY(hipMemsetAsync(d_gweight, 0, (uint64_t)n_groups * 8, nullptr));
   HIP_TRY(hipMemsetAsync(d_kept, 0, 8, nullptr));
-  overlap_cell_sums_kernel<<<grid_for(m), BLOCK>>>(W.first, d_rank[1], d_weight, m32, d_sum, d_flag);
-  HIP_TRY(hipGetLastError());
+  if ((rc = cell_sums(cub, d_key[1], d_rank[1], d_weight, m32, W.mark, W.first, d_sum, d_flag, nullptr))) return rc;
   if ((rc = compact(cub, d_flag, W.slot, m32, PutCell{d_key[1], d_sum, d_cell_sample, d_cell_weight, d_ns, d_kept + 1, d_gweight}, d_kept,
                     nullptr))) return rc;
   uint32_t kept[2] = {0, 0};      // the number of cells, and with it the flag of a cell that passed 2^32
-  HIP_TRY(hipMemcpy(kept, d_kept, 8, hipMemcpyDeviceToHost));
+  if ((rc = to_host(kept, d_kept, 2))) return rc;
   if (kept[1]) return set_err(DCRX_E_UNSUPPORTED, "dcrx_overlap_run: a cell's weight (the sum of one sample's rows under one key) is 2^32 or more");
   const uint32_t n_cells = kept[0];
   if ((rc = exclusive_sum(cub, d_ns, d_cell_off, (uint64_t)n_groups + 1, nullptr))) return rc;
@@ -363,7 +339,7 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
   HIP_TRY(hipGetLastError());
   if ((rc = compact(cub, d_flag, W.slot, n_groups, PutIndex{d_list[0]}, d_kept, nullptr))) return rc;
   uint32_t rows = 0;
-  HIP_TRY(hipMemcpy(&rows, d_kept, 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&rows, d_kept, 1))) return rc;
   if ((rc = most_common_order(cub, d_list, d_key, d_head_rank, 32, d_gweight, rows, nullptr))) return rc;
   const uint32_t *d_order = d_list[0];
   if (rows) {
@@ -383,24 +359,17 @@ int run(uint32_t S, uint64_t m, const uint32_t *sample, const uint32_t *cls, con
 
   // back to the host
   std::vector<uint32_t> ns(n_groups), off32((size_t)rows + 1), cw32;
-  HIP_TRY(hipMemcpy(O.planes.data(), d_planes, (uint64_t)PLANES * SS * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(O.group_of.data(), d_group_of, m * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(ns.data(), d_ns, (uint64_t)n_groups * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(off32.data(), d_pub_off, ((uint64_t)rows + 1) * 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(O.planes.data(), reinterpret_cast<const uint64_t *>(d_planes), (uint64_t)PLANES * SS)) ||
+      (rc = to_host(O.group_of.data(), d_group_of, m)) || (rc = to_host(ns.data(), d_ns, n_groups)) ||
+      (rc = to_host(off32.data(), d_pub_off, (uint64_t)rows + 1))) return rc;
   const uint32_t pub_cells = off32[rows];
   O.head.resize(rows); O.n_samples.resize(rows); O.weight.resize(rows);
   O.cell_off.assign(off32.begin(), off32.end());
   O.cell_sample.resize(pub_cells); O.cell_weight.resize(pub_cells); cw32.resize(pub_cells);
-  if (rows) {
-    HIP_TRY(hipMemcpy(O.head.data(), d_pub_head, (uint64_t)rows * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(O.n_samples.data(), d_pub_ns, (uint64_t)rows * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(O.weight.data(), d_pub_weight, (uint64_t)rows * 8, hipMemcpyDeviceToHost));
-  }
-  if (pub_cells) {
-    HIP_TRY(hipMemcpy(O.cell_sample.data(), d_pub_sample, (uint64_t)pub_cells * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cw32.data(), d_pub_cw, (uint64_t)pub_cells * 4, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < pub_cells; k++) O.cell_weight[k] = cw32[k];
-  }
+  if ((rc = to_host(O.head.data(), d_pub_head, rows)) || (rc = to_host(O.n_samples.data(), d_pub_ns, rows)) ||
+      (rc = to_host(O.weight.data(), d_pub_weight, rows)) || (rc = to_host(O.cell_sample.data(), d_pub_sample, pub_cells)) ||
+      (rc = to_host(cw32.data(), d_pub_cw, pub_cells))) return rc;
+  for (uint32_t k = 0; k < pub_cells; k++) O.cell_weight[k] = cw32[k];
   dcrx_overlap_stats_t &T = O.stats;
   T.groups = n_groups;
   for (uint32_t g = 0; g < n_groups; g++) {

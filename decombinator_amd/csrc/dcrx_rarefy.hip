@@ -234,39 +234,25 @@ __global__ __launch_bounds__(BLOCK) void rarefy_threshold_kernel(State Q) {
   }
 }
 
-struct Plan {
-  uint64_t G, base, s_seed, rank, prefix, levels, active, all, cand_n, hist, cand, ctl, cub, total;
-  size_t cub_bytes;
+// ---- work space of the primitive: what of a State lies there, and hipCUB's scratch
+struct Work {
+  State Q{};
+  Scratch cub;
+  int carve(Pool &P, uint64_t m, uint32_t S) {
+    size_t b = 0;
+    const int rc = exclusive_sum_bytes<uint64_t>(std::max<uint64_t>(m, 1), &b);
+    if (rc) return rc;
+    P.get(&Q.G, m + 1); P.get(&Q.base, (uint64_t)S + 1); P.get(&Q.s_seed, S); P.get(&Q.rank, S); P.get(&Q.prefix, S);
+    P.get(&Q.levels, S); P.get(&Q.active, S); P.get(&Q.all, S); P.get(&Q.cand_n, S); P.get(&Q.hist, (uint64_t)S * BINS);
+    P.get(&Q.cand, (uint64_t)S * CANDIDATES); P.get(&Q.ctl, 1); P.get(&cub, b);
+    return DCRX_OK;
+  }
 };
 
-int plan_work(uint64_t m, uint32_t S, Plan *W) {
-  size_t b = 0;
-  const int rc = exclusive_sum_bytes<uint64_t>(std::max<uint64_t>(m, 1), &b);
-  if (rc) return rc;
-  Carver C;
-  W->G = C.take((m + 1) * 8); W->base = C.take(((uint64_t)S + 1) * 8);
-  W->s_seed = C.take((uint64_t)S * 8); W->rank = C.take((uint64_t)S * 8); W->prefix = C.take((uint64_t)S * 8);
-  W->levels = C.take((uint64_t)S * 4); W->active = C.take((uint64_t)S * 4); W->all = C.take((uint64_t)S * 4);
-  W->cand_n = C.take((uint64_t)S * 4);
-  W->hist = C.take((uint64_t)S * BINS * 8); W->cand = C.take((uint64_t)S * CANDIDATES * 8);
-  W->ctl = C.take(sizeof(Control));
-  W->cub_bytes = b;
-  W->cub = C.take(b);
-  W->total = C.at;
-  return DCRX_OK;
-}
-
 int run_downsample(uint32_t S, uint64_t m, const uint32_t *d_sample, const uint64_t *d_weight, const uint64_t *d_depth, uint64_t seed,
-                   uint64_t *d_kept, uint64_t *d_reads, uint64_t *d_depth_used, uint64_t *d_threshold, uint8_t *w, const Plan &W,
-                   hipStream_t s) {
-  State Q;
+                   uint64_t *d_kept, uint64_t *d_reads, uint64_t *d_depth_used, uint64_t *d_threshold, const Work &W, hipStream_t s) {
+  State Q = W.Q;
   Q.sample = d_sample; Q.weight = d_weight;
-  Q.G = reinterpret_cast<uint64_t *>(w + W.G); Q.base = reinterpret_cast<uint64_t *>(w + W.base);
-  Q.s_seed = reinterpret_cast<uint64_t *>(w + W.s_seed); Q.rank = reinterpret_cast<uint64_t *>(w + W.rank);
-  Q.prefix = reinterpret_cast<uint64_t *>(w + W.prefix); Q.levels = reinterpret_cast<uint32_t *>(w + W.levels);
-  Q.active = reinterpret_cast<uint32_t *>(w + W.active); Q.all = reinterpret_cast<uint32_t *>(w + W.all);
-  Q.cand_n = reinterpret_cast<uint32_t *>(w + W.cand_n); Q.hist = reinterpret_cast<unsigned long long *>(w + W.hist);
-  Q.cand = reinterpret_cast<uint64_t *>(w + W.cand); Q.ctl = reinterpret_cast<Control *>(w + W.ctl);
   Q.threshold = d_threshold; Q.kept = reinterpret_cast<unsigned long long *>(d_kept);
   Q.m = (uint32_t)m; Q.S = S;
   int rc;
@@ -274,7 +260,7 @@ int run_downsample(uint32_t S, uint64_t m, const uint32_t *d_sample, const uint6
   if (m) {
     HIP_TRY(hipMemsetAsync(Q.hist, 0, (uint64_t)S * BINS * 8, s));
     HIP_TRY(hipMemsetAsync(d_kept, 0, m * 8, s));
-    if ((rc = exclusive_sum(Scratch{w + W.cub, W.cub_bytes}, d_weight, Q.G, m, s))) return rc;
+    if ((rc = exclusive_sum(W.cub, d_weight, Q.G, m, s))) return rc;
   }
   rarefy_samples_kernel<<<grid_for((uint64_t)S + 1), BLOCK, 0, s>>>(Q, d_depth, seed, d_reads, d_depth_used);
   HIP_TRY(hipGetLastError());
@@ -305,19 +291,6 @@ __global__ __launch_bounds__(BLOCK) void classes_cell_keys_kernel(const uint32_t
   if (i >= n) return;
   key[i] = ((uint64_t)sample[i] << 32) | group[i];
   idx[i] = i;
-}
-
-__global__ __launch_bounds__(BLOCK) void classes_marks_kernel(const uint64_t *__restrict__ key, uint32_t n, uint32_t *__restrict__ mark) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s < n) mark[s] = run_mark(s, [&](uint32_t k) { return key[k]; });
-}
-
-// every item's weight onto its cell's first position
-__global__ __launch_bounds__(BLOCK) void classes_cell_sums_kernel(const uint32_t *__restrict__ head, const uint32_t *__restrict__ idx,
-                                                                  const uint64_t *__restrict__ weight, uint32_t n,
-                                                                  unsigned long long *__restrict__ sum) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s < n) atomicAdd(&sum[head[s]], (unsigned long long)weight[idx[s]]);
 }
 
 // the cells that stay: the heads whose sum is not zero
@@ -363,27 +336,20 @@ int run_classes(uint32_t S, uint64_t n, const uint32_t *sample, const uint32_t *
     P.get(&d_list, n); P.get(&d_sum, n); P.get(&d_cub, cub_bytes);
     if (pass == 0 && (rc = P.allocate())) return rc;
   }
-  HIP_TRY(hipMemcpy(d_sample, sample, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_group, group, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_weight, weight, n * 8, hipMemcpyHostToDevice));
+  if ((rc = to_device(d_sample, sample, n)) || (rc = to_device(d_group, group, n)) || (rc = to_device(d_weight, weight, n))) return rc;
   const Scratch cub{d_cub, cub_bytes};
 
   // cells: the items sorted (stably) by (sample, group); a run is a cell
   classes_cell_keys_kernel<<<grid_for(n), BLOCK>>>(d_sample, d_group, n32, d_key[0], d_idx[0]);
   HIP_TRY(hipGetLastError());
   if ((rc = sort_pairs(cub, d_key[0], d_key[1], d_idx[0], d_idx[1], n, 32 + (int)dcrx_ovl::SAMPLE_BITS, nullptr))) return rc;
-  classes_marks_kernel<<<grid_for(n), BLOCK>>>(d_key[1], n32, d_mark);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, d_mark, d_head, n, nullptr))) return rc;
-  HIP_TRY(hipMemsetAsync(d_sum, 0, n * 8, nullptr));
-  HIP_TRY(hipMemsetAsync(d_kept, 0, 8, nullptr));
-  classes_cell_sums_kernel<<<grid_for(n), BLOCK>>>(d_head, d_idx[1], d_weight, n32, d_sum);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(d_kept, 0, 2 * sizeof *d_kept, nullptr));
+  if ((rc = cell_sums(cub, d_key[1], d_idx[1], d_weight, n32, d_mark, d_head, d_sum, d_flag, nullptr))) return rc;
   classes_cell_flags_kernel<<<grid_for(n), BLOCK>>>(d_head, d_sum, n32, d_flag);
   HIP_TRY(hipGetLastError());
   if ((rc = compact(cub, d_flag, d_slot, n32, PutClassKey{d_key[1], d_sum, d_key[0], d_idx[0], d_kept + 1}, d_kept, nullptr))) return rc;
   uint32_t kept[2] = {0, 0};      // the number of cells, and with it the flag of a cell that passed 2^32
-  HIP_TRY(hipMemcpy(kept, d_kept, 8, hipMemcpyDeviceToHost));
+  if ((rc = to_host(kept, d_kept, 2))) return rc;
   if (kept[1]) return set_err(DCRX_E_UNSUPPORTED, "dcrx_abundance_classes: a cell's weight (the sum of one sample's items of one group) is 2^32 or more");
   const uint32_t n_cells = kept[0];
   *n_cells_out = n_cells;
@@ -392,20 +358,16 @@ int run_classes(uint32_t S, uint64_t n, const uint32_t *sample, const uint32_t *
 
   // classes: the cells sorted by (sample, weight); a run is a class, and its head's position tells where it starts
   if ((rc = sort_pairs(cub, d_key[0], d_key[1], d_idx[0], d_idx[1], n_cells, 32 + (int)dcrx_ovl::SAMPLE_BITS, nullptr))) return rc;
-  classes_marks_kernel<<<grid_for(n_cells), BLOCK>>>(d_key[1], n_cells, d_mark);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(cub, d_mark, d_head, n_cells, nullptr))) return rc;
+  if ((rc = run_marks(d_key[1], n_cells, d_mark, nullptr)) || (rc = run_heads(cub, d_mark, d_head, n_cells, nullptr))) return rc;
   classes_head_flags_kernel<<<grid_for(n_cells), BLOCK>>>(d_head, n_cells, d_flag);
   HIP_TRY(hipGetLastError());
   if ((rc = compact(cub, d_flag, d_slot, n_cells, PutIndex{d_list}, d_kept, nullptr))) return rc;
   uint32_t n_classes = 0;
-  HIP_TRY(hipMemcpy(&n_classes, d_kept, 4, hipMemcpyDeviceToHost));
+  if ((rc = to_host(&n_classes, d_kept, 1))) return rc;
   starts.resize(n_classes);
   keys.resize(n_classes);
-  HIP_TRY(hipMemcpy(starts.data(), d_list, (uint64_t)n_classes * 4, hipMemcpyDeviceToHost));
-  if ((rc = gather(d_key[1], d_list, n_classes, 0, d_key[0], nullptr))) return rc;
-  HIP_TRY(hipMemcpy(keys.data(), d_key[0], (uint64_t)n_classes * 8, hipMemcpyDeviceToHost));
-  return DCRX_OK;
+  if ((rc = to_host(starts.data(), d_list, n_classes)) || (rc = gather(d_key[1], d_list, n_classes, 0, d_key[0], nullptr))) return rc;
+  return to_host(keys.data(), d_key[0], n_classes);
 }
 
 int check_device_args(const char *who, uint32_t S, uint64_t m) {
@@ -426,9 +388,10 @@ int check_device_args(const char *who, uint32_t S, uint64_t m) {
 extern "C" {
 
 uint64_t dcrx_downsample_work_bytes(uint64_t m, uint32_t n_samples) {
-  Plan W;
-  if (n_samples < 1 || n_samples > MAX_SAMPLES || m >= MAX_ROWS || plan_work(m, n_samples, &W) != DCRX_OK) return 0;
-  return W.total;
+  Pool P;
+  Work W;
+  if (n_samples < 1 || n_samples > MAX_SAMPLES || m >= MAX_ROWS || W.carve(P, m, n_samples) != DCRX_OK) return 0;
+  return P.bytes();
 }
 
 int dcrx_downsample_device(uint32_t n_samples, uint64_t m, const uint32_t *d_sample, const uint64_t *d_weight, const uint64_t *d_depth,
@@ -438,11 +401,12 @@ int dcrx_downsample_device(uint32_t n_samples, uint64_t m, const uint32_t *d_sam
   if ((rc = check_device_args("dcrx_downsample_device", n_samples, m))) return rc;
   if (!d_depth || !d_reads || !d_depth_used || !d_threshold || !d_work || (m && (!d_sample || !d_weight || !d_kept)))
     return set_err(DCRX_E_INVALID, "dcrx_downsample_device: null argument");
-  Plan W;
-  if ((rc = plan_work(m, n_samples, &W))) return rc;
-  if (work_bytes < W.total) return set_err(DCRX_E_INVALID, "dcrx_downsample_device: the work space is smaller than dcrx_downsample_work_bytes(m, n_samples)");
-  return run_downsample(n_samples, m, d_sample, d_weight, d_depth, seed, d_kept, d_reads, d_depth_used, d_threshold,
-                        static_cast<uint8_t *>(d_work), W, (hipStream_t)hip_stream);
+  Pool P(d_work);
+  Work W;
+  if ((rc = W.carve(P, m, n_samples))) return rc;
+  if (work_bytes < P.bytes()) return set_err(DCRX_E_INVALID, "dcrx_downsample_device: the work space is smaller than dcrx_downsample_work_bytes(m, n_samples)");
+  return run_downsample(n_samples, m, d_sample, d_weight, d_depth, seed, d_kept, d_reads, d_depth_used, d_threshold, W,
+                        (hipStream_t)hip_stream);
 }
 
 int dcrx_downsample(uint32_t n_samples, uint64_t m, const uint32_t *sample, const uint64_t *weight, const uint64_t *depth, uint64_t seed,
@@ -463,26 +427,20 @@ int dcrx_downsample(uint32_t n_samples, uint64_t m, const uint32_t *sample, cons
     for (uint32_t s = 0; s < S; s++) { reads_out[s] = 0; depth_used_out[s] = 0; threshold_out[s] = ~0ull; }
     return DCRX_OK;
   }
-  Plan W;
-  if ((rc = plan_work(m, S, &W))) return rc;
   Pool P;
+  Work W;
   uint32_t *d_sample;
   uint64_t *d_weight, *d_depth, *d_kept, *d_reads, *d_used, *d_thr;
-  uint8_t *d_work;
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_sample, m); P.get(&d_weight, m); P.get(&d_depth, S); P.get(&d_kept, m); P.get(&d_reads, S); P.get(&d_used, S);
-    P.get(&d_thr, S); P.get(&d_work, W.total);
-    if (pass == 0 && (rc = P.allocate())) return rc;
+    P.get(&d_thr, S);
+    if ((rc = W.carve(P, m, S)) || (pass == 0 && (rc = P.allocate()))) return rc;
   }
-  HIP_TRY(hipMemcpy(d_sample, sample, m * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_weight, weight, m * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_depth, depth, (uint64_t)S * 8, hipMemcpyHostToDevice));
-  if ((rc = run_downsample(S, m, d_sample, d_weight, d_depth, seed, d_kept, d_reads, d_used, d_thr, d_work, W, nullptr))) return rc;
-  HIP_TRY(hipMemcpy(kept_out, d_kept, m * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(reads_out, d_reads, (uint64_t)S * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(depth_used_out, d_used, (uint64_t)S * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(threshold_out, d_thr, (uint64_t)S * 8, hipMemcpyDeviceToHost));
-  return DCRX_OK;
+  if ((rc = to_device(d_sample, sample, m)) || (rc = to_device(d_weight, weight, m)) || (rc = to_device(d_depth, depth, S)) ||
+      (rc = run_downsample(S, m, d_sample, d_weight, d_depth, seed, d_kept, d_reads, d_used, d_thr, W, nullptr)) ||
+      (rc = to_host(kept_out, d_kept, m)) || (rc = to_host(reads_out, d_reads, S)) || (rc = to_host(depth_used_out, d_used, S)))
+    return rc;
+  return to_host(threshold_out, d_thr, S);
 }
 
 int64_t dcrx_abundance_classes(uint32_t n_samples, uint64_t n, const uint32_t *sample, const uint32_t *group, const uint64_t *weight,
