@@ -228,6 +228,43 @@ def star(k: int, length: int = 20, centre_rank=None):
     return leaves[:at] + [centre] + leaves[at:]
 
 
+# ---- decoys of the walk: strings whose packed words are equal, classes that differ in their high bits ----
+
+ZERO_RUN = (b"CASSF", b"CASSF\x00", b"CASSF\x00\x00")
+ZERO_RUN_FRONT = 254          # nodes of a smaller class in front: the run's buckets then straddle sorted position 256
+
+
+def zero_byte_run(front_strings):
+    """(classes, strings, the rank of ZERO_RUN[0]): the front strings under class 0, then under class 1 a run of strings that a
+    zero byte lengthens — the packed words are equal, the lengths are not —, a pair of 31 and 32 bytes of the same kind, and one
+    substitution of the run's head.  By (class, length) the run stands at sorted positions 254 (with its substitution at 255),
+    256 and 257; by class alone, in rank order, at 254, 255 and 256."""
+    assert len(front_strings) == ZERO_RUN_FRONT
+    long = bytes(range(65, 65 + 31))
+    tail = list(ZERO_RUN) + [long, long + b"\x00", b"CASSY"]
+    packed = [host_pack(x).tolist() for x in tail]
+    assert packed[0] == packed[1] == packed[2] and packed[3] == packed[4] and [len(x) for x in tail] == [5, 6, 7, 31, 32, 5]
+    return [0] * ZERO_RUN_FRONT + [1] * len(tail), as_bytes(front_strings) + tail, ZERO_RUN_FRONT
+
+
+CLASS_BIT_PAIRS = ((0, 1 << 31), (5, 5 | 1 << 26), (0xFFFFFFFE, 0xFFFFFFFF))
+
+
+def class_bit_nodes(strings, pair, n_out=0, seed=3):
+    """(classes, strings, the same classes as 0 and 1): every string once under either class of `pair`, ranks shuffled, with n_out
+    nodes out of reach (under the pair's larger class) among them.  The strings of one class are those of the other: across the
+    classes every node has a twin at distance 0."""
+    rnd = random.Random(seed)
+    nodes = [(c, s) for s in as_bytes(strings) for c in (0, 1)] + [(1, b"" if k % 2 else b"A" * (MAX_LEN + 1)) for k in range(n_out)]
+    rnd.shuffle(nodes)
+    return [pair[c] for c, _ in nodes], [s for _, s in nodes], [c for c, _ in nodes]
+
+
+def no_edge_across(classes, result) -> bool:
+    off, adj = result["adj_off"], result["adj"]
+    return all(classes[a] == classes[int(b)] for a in range(len(classes)) for b in adj[int(off[a]):int(off[a + 1])])
+
+
 # ---- the per-node and per-pair code on the host (tests/host_cdr3net) ----
 
 _host = None

@@ -1,6 +1,7 @@
 """Helpers of the error-merge tests (test_nbc_merge.py on CPU, test_gpu_nbc_merge.py on the GPU): the contract of
 `--merge-errors` written directly in Python (expected_merge: strings, a dict of buckets, all pairs), noisy clonal reads that
-remember where they were substituted, hand-made counted tables, and the brute force as a stand-in for nat.merge_dcrs."""
+remember where they were substituted, hand-made counted tables, the brute force as a stand-in for nat.merge_dcrs, and the
+constructed lists that pin the kernel's walk (each builder asserts its own premise on the contract; no GPU, no library)."""
 import collections
 import ctypes as C
 import os
@@ -39,11 +40,11 @@ def junction_of(ts, v, j, vdel, jdel, ins):
     return junction, True
 
 
-def expected_merge(counted, ts, D, R):
-    """The contract, directly: (merged table, statistics, root_of) of a counted table (entry k = rank k)."""
+def expected_parents(counted, ts, D, R):
+    """The contract's parents step, directly: (parent, reach) of a counted table (entry k = rank k)."""
     n = len(counted["v"])
     v, j, vdel, jdel = (counted[f].tolist() for f in ("v", "j", "vdel", "jdel"))
-    count, first = [int(x) for x in counted["count"]], [int(x) for x in counted["first"]]
+    count = [int(x) for x in counted["count"]]
     ins = inserts(counted)
     reach = [False] * n
     buckets = collections.defaultdict(list)
@@ -68,6 +69,16 @@ def expected_merge(counted, ts, D, R):
             hit = np.nonzero(ham <= D)[0]
             if len(hit):
                 parent[members[i]] = members[int(ok[hit[0]])]
+    return parent, reach
+
+
+def expected_merge(counted, ts, D, R):
+    """The contract, directly: (merged table, statistics, root_of) of a counted table (entry k = rank k)."""
+    n = len(counted["v"])
+    v, j, vdel, jdel = (counted[f].tolist() for f in ("v", "j", "vdel", "jdel"))
+    count, first = [int(x) for x in counted["count"]], [int(x) for x in counted["first"]]
+    ins = inserts(counted)
+    parent, reach = expected_parents(counted, ts, D, R)
     root_of, depth = list(range(n)), [0] * n
     for k in range(n):          # a parent's rank is smaller: its root is known
         if parent[k] != k:
@@ -94,6 +105,14 @@ def table(entries):
             "vdel": np.array([e[2] for e in entries], np.uint8), "jdel": np.array([e[3] for e in entries], np.uint8),
             "count": np.array([e[5] for e in entries], np.uint64), "first": np.array([e[6] for e in entries], np.uint64),
             "ins_off": off, "ins_text": b"".join(ins)}
+
+
+def take(counted, n):
+    """The first n entries of a counted table."""
+    out = {f: counted[f][:n].copy() for f in ("v", "j", "vdel", "jdel", "count", "first")}
+    out["ins_off"] = counted["ins_off"][:n + 1].copy()
+    out["ins_text"] = counted["ins_text"][:int(counted["ins_off"][n])]
+    return out
 
 
 def ranked(entries):
@@ -225,3 +244,399 @@ def roots_of(parent):
         if parent[k] != k:
             root[k] = root[parent[k]]
     return root.astype(np.uint32)
+
+
+# ---- constructed lists: merge_parents_kernel's walk, the counts and the primitive's rules.  Every builder asserts its own
+# premise on the contract above (expected_parents / expected_merge) before it returns, so a list that stopped being the edge
+# it was written for fails without a GPU.  With vdel = jdel = ANCHOR and windows of ANCHOR clean bases the junction is the
+# insert alone (bare). ----
+
+BASES = "ACGT"
+TILE = 256          # merge_parents_kernel stages this many sorted entries per step, and a block holds this many children
+
+
+def sub(s, p, step=1):
+    """s with the base at p replaced by another one."""
+    return s[:p] + BASES[(BASES.index(s[p]) + step) % 4] + s[p + 1:]
+
+
+def subs(s, places):
+    for p in places:
+        s = sub(s, p)
+    return s
+
+
+def pack(s):
+    """A junction as the kernels hold it: eight dwords of 2-bit bases, A = 0, zero beyond the length."""
+    w = [0] * (MAX_JUNCTION // 16)
+    for p, c in enumerate(s):
+        w[p // 16] |= BASES.index(c) << (2 * (p % 16))
+    return w
+
+
+def packed_distance(a, b):
+    """Bases at which two packed junctions differ, over all MAX_JUNCTION places (what the walk sees without the lengths)."""
+    return sum(((x ^ y) >> (2 * p)) & 3 != 0 for x, y in zip(pack(a), pack(b)) for p in range(16))
+
+
+def full_anchors(ts):
+    """Whether every window of the tag set is ANCHOR clean bases (then bare() entries have the insert for a junction)."""
+    return all(len(r) >= ANCHOR and set(r.upper()[-ANCHOR:]) <= ACGT for r in ts.v_regions) and \
+        all(len(r) >= ANCHOR and set(r.upper()[:ANCHOR]) <= ACGT for r in ts.j_regions)
+
+
+def bare(v, j, ins, count, first):
+    return (v, j, ANCHOR, ANCHOR, ins, count, first)
+
+
+def random_bases(rng, length):
+    return "".join(rng.choice(list(BASES), size=length)) if length else ""
+
+
+def junctions(counted, ts):
+    """Per entry its junction, None where it is out of reach."""
+    ins = inserts(counted)
+    return [junction_of(ts, int(counted["v"][k]), int(counted["j"][k]), int(counted["vdel"][k]), int(counted["jdel"][k]), ins[k])[0]
+            for k in range(len(ins))]
+
+
+def sorted_order(counted, ts):
+    """The ranks in the order the device puts them: by (v, j, junction length), stable, entries out of reach behind all."""
+    junc = junctions(counted, ts)
+    return sorted(range(len(junc)), key=lambda k: (1, 0, 0, 0) if junc[k] is None else
+                  (0, int(counted["v"][k]), int(counted["j"][k]), len(junc[k])))
+
+
+def _fillers(rng, n, count_from=9000):
+    """One bucket (v 0, j 0, 30 bases) of n entries that are far apart, in front of every other bucket in sorted order; their
+    counts are larger than any count behind them, so a walk that wrongly starts among them is not stopped by the ratio."""
+    return [bare(0, 0, random_bases(rng, 30), count_from + n - k, k) for k in range(n)]
+
+
+DECOY_LENGTHS = (15, 16, 31, 63, 64, 127)
+DECOY_FILLERS = (1, 255, 256, 257, 300)          # the decoy buckets start at this sorted position
+
+
+def padding_decoys(ts, length, n_fill, with_children):
+    """List 1a.  X of `length` bases (its last one not A) and X[:-1], X + "A", X + "AA": four neighbouring buckets of one (v, j)
+    whose packed junctions are equal (or one base apart) although the lengths differ.  Without children every bucket is a far
+    head and the decoy behind it, and nothing merges; with children every bucket is the decoy and one substitution of it, and
+    every bucket has exactly one merge.  n_fill entries of another bucket stand in front.  Returns (table, merges)."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(1000 * length + n_fill)
+    X = random_bases(rng, length - 1) + str(rng.choice(list("CGT")))
+    group, counts = [X[:-1], X, X + "A", X + "AA"], [40, 1000, 30, 20]
+    assert all(pack(s) == pack(X) for s in group[1:] if len(s) <= MAX_JUNCTION) and packed_distance(X, X[:-1]) == 1
+    entries = _fillers(rng, n_fill)
+    first = n_fill
+    for s, c in zip(group, counts):
+        if with_children:
+            entries += [bare(1, 0, s, c, first), bare(1, 0, sub(s, 0), 1, first + 1)]
+        else:
+            entries += [bare(1, 0, random_bases(rng, len(s)), 5000, first), bare(1, 0, s, c, first + 1)]
+        first += 2
+    counted = ranked(entries)
+    junc = junctions(counted, ts)
+    order = sorted_order(counted, ts)
+    in_reach = [len(s) for s in group if len(s) <= MAX_JUNCTION]
+    # the decoy buckets stand next to each other, in length order, from sorted position n_fill on
+    assert [len(junc[k]) for k in order[:n_fill]] == [30] * n_fill
+    assert [len(junc[k]) for k in order[n_fill:n_fill + 2 * len(in_reach)]] == [x for x in in_reach for _ in range(2)]
+    for D in (1, 2):
+        _, stats, root = expected_merge(counted, ts, D, 1)
+        assert stats["out_of_reach"] == 2 * (len(group) - len(in_reach))
+        assert stats["merged"] == (len(in_reach) if with_children else 0)
+        if with_children:          # every child's root is its own bucket's head
+            where = {s: k for k, s in enumerate(junc) if s is not None}
+            assert all(root[where[sub(s, 0)]] == where[s] for s in group if len(s) <= MAX_JUNCTION)
+    return counted, (len(in_reach) if with_children else 0)
+
+
+def gene_pair_decoys(ts, axis):
+    """List 1b.  One insert under two V genes and one J gene (axis "v"), or two J genes and one V gene (axis "j"): identical
+    junctions in two neighbouring buckets.  The first bucket is H and its child; the second is a far head G, H again, a
+    substitution of H and G's child.  The children merge inside their buckets (at R = 1 the substitution of H joins the H of
+    its own bucket); nothing crosses, and the second H stays a root."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(77 + (axis == "j"))
+    H, G = random_bases(rng, 40), random_bases(rng, 40)
+    (va, ja), (vb, jb) = ((3, 2), (4, 2)) if axis == "v" else ((3, 2), (3, 3))
+    counted = ranked([bare(va, ja, H, 1000, 0), bare(va, ja, sub(H, 5), 2, 1), bare(vb, jb, G, 900, 2), bare(vb, jb, H, 5, 3),
+                      bare(vb, jb, sub(H, 9), 3, 4), bare(vb, jb, sub(G, 7), 1, 5)])
+    assert inserts(counted) == [H, G, H, sub(H, 9), sub(H, 5), sub(G, 7)]
+    assert sorted_order(counted, ts) == [0, 4, 1, 2, 3, 5]          # the two buckets stand next to each other
+    for D, R in ((1, 10), (2, 1)):
+        _, stats, root = expected_merge(counted, ts, D, R)
+        assert root.tolist() == [0, 1, 2, 3 if R == 10 else 2, 0, 1] and stats["out_of_reach"] == 0
+    return counted
+
+
+PREFIX_PLACES = ((0, 3), (7, 3), (8, 3), (255, 3), (256, 3), (0, 0), (255, 0), (299, 0))          # (offset, entries up to the child)
+
+
+def prefix_end(ts, R, k, gap, eligible):
+    """List 1c.  One bucket that starts at sorted position 0, so bucket offsets are tile offsets.  Offsets 0 .. k-1 are far
+    heads above R * c; offset k is one substitution from the child and has exactly R * c reads (eligible) or R * c - 1 (not);
+    `gap` entries of R * c - 1 follow, the first of them one substitution from the child as well, with a first ordinal below
+    the parent's; then the child of c reads.  Returns (table, the child's rank, its parent's rank or the child's own)."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(31 * k + 7 * gap + R)
+    c = 7
+    need = R * c
+    child = random_bases(rng, 40)
+    parent, decoy = sub(child, 3), sub(child, 20)
+    entries = [bare(1, 2, random_bases(rng, 40), need + (k - i), i) for i in range(k)]
+    entries.append(bare(1, 2, parent, need if eligible else need - 1, 1000))
+    entries += [bare(1, 2, decoy if g == 0 else random_bases(rng, 40), need - 1, 999 if g == 0 else 1000 + g) for g in range(gap)]
+    entries.append(bare(1, 2, child, c, 2000))
+    counted = ranked(entries)
+    at = {s: i for i, s in enumerate(inserts(counted))}
+    count = [int(x) for x in counted["count"]]
+    assert sorted_order(counted, ts) == list(range(len(entries)))          # one bucket, in rank order
+    want = at[parent] if eligible else at[child]
+    for D in (1, 2):
+        assert expected_parents(counted, ts, D, R)[0][at[child]] == want
+    if eligible:
+        assert at[parent] == k and count[k] == need and (k == 0 or count[k - 1] > need)
+        if k == 0:
+            assert count[0] == need          # the early-out's edge: the bucket's largest count is exactly the need
+        if R > 1:          # the prefix is cut at offset k + 1 (or the child stands there)
+            assert at[child] == k + 1 + gap and (gap == 0 or count[k + 1] == need - 1)
+    else:
+        assert all(x != need for x in count[:at[child]]) and (k > 0 or R == 1 or count[0] == need - 1)
+    if gap:
+        # the decoy asks for a place in front of the parent (a smaller first ordinal); the rank order puts it behind
+        assert at[decoy] > at[parent] or not eligible
+        assert R == 1 or at[decoy] < at[child]
+    return counted, at[child], want
+
+
+BALL_PLACES = (0, 15, 16, 31, 32, 39)
+
+
+def equal_counts_ball(ts, n=600):
+    """List 1d.  One bucket of n entries of 5 reads each: strings that differ from one seed of 40 bases in at most three of six
+    places (at the word edges), first ordinals a permutation.  With R = 1 every entry in front is eligible by count, so the
+    parent is the smallest rank within distance, later candidates lose, and entries behind the child never count."""
+    import itertools
+    assert full_anchors(ts)
+    rng = np.random.default_rng(1234)
+    seed = random_bases(rng, 40)
+    ball = sorted({subs_steps(seed, BALL_PLACES, steps) for steps in itertools.product(range(4), repeat=len(BALL_PLACES))
+                   if sum(1 for x in steps if x) <= 3})
+    assert len(ball) == 694 and n <= len(ball)
+    picks = [ball[i] for i in rng.permutation(len(ball))[:n]]
+    firsts = rng.permutation(n).tolist()
+    counted = ranked([bare(1, 2, s, 5, f) for s, f in zip(picks, firsts)])
+    M = np.frombuffer("".join(inserts(counted)).encode(), np.uint8).reshape(n, 40)
+    ham = (M[:, None, :] != M[None, :, :]).sum(axis=2)
+    for D in (1, 2):
+        parent = expected_parents(counted, ts, D, 1)[0]
+        near = ham <= D
+        np.fill_diagonal(near, False)
+        front = [np.nonzero(near[i, :i])[0] for i in range(n)]
+        assert all(parent[i] == (int(front[i][0]) if len(front[i]) else i) for i in range(n))
+        assert sum(1 for f in front if len(f) >= 2) >= n // 4          # a later candidate that must lose
+        assert sum(1 for i in range(n) if near[i, i + 1:].any()) >= n // 4          # an entry behind that never is a parent
+    return counted
+
+
+def subs_steps(s, places, steps):
+    for p, step in zip(places, steps):
+        if step:
+            s = sub(s, p, step)
+    return s
+
+
+CHAIN_LINKS = 384
+
+
+def deep_chain(ts, n_out=0):
+    """List 1e.  "A" * 128, then one place per entry turned A -> C from left to right, then C -> G, then G -> T: 385 entries of
+    7 reads in rank order (by first ordinal), each one substitution from the one before and two from the one before that.
+    n_out entries out of reach (an N in the insert) stand between them in rank order."""
+    assert full_anchors(ts)
+    s, chain = ["A"] * MAX_JUNCTION, ["A" * MAX_JUNCTION]
+    for b in "CGT":
+        for p in range(MAX_JUNCTION):
+            s[p] = b
+            chain.append("".join(s))
+    assert len(chain) == CHAIN_LINKS + 1
+    entries = []
+    for i, x in enumerate(chain):
+        entries.append(bare(1, 2, x, 7, len(entries)))
+        if (i * n_out) // len(chain) < ((i + 1) * n_out) // len(chain):
+            entries.append(bare(1, 2, "ACGTN", 7, len(entries)))
+    counted = table(entries)
+    assert len(entries) == len(chain) + n_out
+    for D in (1, 2):
+        _, stats, root = expected_merge(counted, ts, D, 1)
+        assert stats == {"entries_in": len(entries), "roots_out": 1 + n_out, "out_of_reach": n_out, "merged": CHAIN_LINKS,
+                         "reads_moved": 7 * CHAIN_LINKS, "longest_chain": CHAIN_LINKS // D}
+    return counted
+
+
+EDGE_PLACES = ((0,), (15,), (16,), (63,), (64,), (127,), (63, 64), (0, 127), (0, 1, 64), (62, 63, 64))
+
+
+def lengths_and_word_edges(ts):
+    """List 1f.  One (v, j) with junctions of 0, 1, 16, 17, 64, 65, 128 and 129 bases.  The buckets of 65 and 128 hold a base
+    and children substituted at EDGE_PLACES (a place beyond the end stands for the last one): the first and last base of a
+    dword, both sides of the half split at base 63/64, alone, in pairs and in threes.  The 17- and 65-base heads are the 16-
+    and 64-base heads with an A behind them.  With R = 10 and children of 1 .. 9 reads only a head can be a parent.  Returns
+    (table, {rank of a child: (rank of its head, substitutions)})."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(65)
+    b16, b64, b128, b129 = (random_bases(rng, n) for n in (16, 64, 128, 129))
+    entries, kids = [], []
+
+    def bucket(head, count, places):
+        entries.append(bare(2, 1, head, count, len(entries)))
+        seen = set()
+        for pl in places:
+            pl = tuple(sorted({min(p, len(head) - 1) for p in pl}))
+            if pl in seen:
+                continue
+            seen.add(pl)
+            entries.append(bare(2, 1, subs(head, pl), 1 + len(kids) % 9, len(entries)))
+            kids.append((subs(head, pl), head, len(pl)))
+    entries += [bare(2, 1, "", 50, 0), bare(2, 1, "", 4, 1)]
+    bucket("C", 1000, [(0,)])
+    bucket(b16, 1000, [(0,), (15,), (0, 15)])
+    bucket(b16 + "A", 900, [(0,), (16,), (15, 16)])
+    bucket(b64, 1000, [(0,), (63,), (0, 63), (0, 1, 63)])
+    bucket(b64 + "A", 900, EDGE_PLACES)
+    bucket(b128, 800, EDGE_PLACES)
+    bucket(b129, 700, [(5,)])
+    counted = ranked(entries)
+    at = {}
+    for k, s in enumerate(inserts(counted)):
+        at.setdefault(s, k)
+    assert {len(s) for s in at} == {0, 1, 16, 17, 64, 65, 128, 129}
+    empty = [k for k, s in enumerate(inserts(counted)) if s == ""]
+    assert len(empty) == 2
+    expect = {at[c]: (at[h], nsub) for c, h, nsub in kids if len(h) <= MAX_JUNCTION}
+    for D in (1, 2):
+        _, stats, root = expected_merge(counted, ts, D, 10)
+        assert stats["out_of_reach"] == 2
+        assert all(root[c] == (h if nsub <= D else c) for c, (h, nsub) in expect.items())
+        assert sum(1 for _, nsub in expect.values() if nsub == 3) >= 5
+        for R in (1, 10):          # two entries of an empty junction are distance 0 apart
+            assert expected_merge(counted, ts, D, R)[2][empty[1]] == empty[0]
+    assert int(root[at[sub(b129, 5)]]) == at[sub(b129, 5)]
+    return counted, expect
+
+
+U64 = (1 << 64) - 1
+
+
+def big_counts(ts):
+    """List 2h: [(name, table, D, R, expected root_of or None)] with counts and ratios up to 2^64 - 1."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(64)
+    X = random_bases(rng, 40)
+    cases = []
+    # three entries one substitution apart (the same place) with 2^64 - 11, 1 and 2 reads, as given and in rank order
+    three = table([bare(1, 2, X, U64 - 10, 0), bare(1, 2, sub(X, 9, 1), 1, 1), bare(1, 2, sub(X, 9, 2), 2, 2)])
+    in_rank = ranked([bare(1, 2, X, U64 - 10, 0), bare(1, 2, sub(X, 9, 1), 1, 1), bare(1, 2, sub(X, 9, 2), 2, 2)])
+    for R, roots in ((U64 - 10, [0, 0, 2]), (U64 - 9, [0, 1, 2]), (1 << 63, [0, 0, 2]), (1 << 62, [0, 0, 0])):
+        cases.append((f"three-R{R}", three, 1, R, roots))
+        cases.append((f"ranked-R{R}", in_rank, 1, R, [0, 0 if roots[2] == 0 else 1, 0 if roots[1] == 0 else 2]))
+    # a tree whose total is exactly 2^64 - 1
+    full = ranked([bare(1, 2, X, U64 - 10, 0), bare(1, 2, sub(X, 3), 7, 1), bare(1, 2, sub(X, 30), 3, 2)])
+    assert int(expected_merge(full, ts, 1, 10)[0]["count"][0]) == U64
+    cases.append(("total-2^64-1", full, 1, 10, [0, 0, 0]))
+    # 2^40 and 2^32 +- 1 in one bucket at R = 10: the ratio's edge in 64 bits, and more than 2^32 reads moved
+    A, B, E = (random_bases(rng, 40) for _ in range(3))
+    p32, m32 = (1 << 32) + 1, (1 << 32) - 1
+    wide = ranked([bare(1, 2, E, 1 << 40, 0), bare(1, 2, A, 10 * p32, 1), bare(1, 2, B, 10 * p32 - 1, 2), bare(1, 2, sub(A, 4), p32, 3),
+                   bare(1, 2, sub(B, 4), p32, 4), bare(1, 2, sub(E, 4), m32, 5)])
+    out, stats, root = expected_merge(wide, ts, 1, 10)
+    assert root.tolist() == [0, 1, 2, 1, 4, 0] and stats["reads_moved"] == 1 << 33
+    assert out["count"].tolist() == [(1 << 40) + m32, 11 * p32, 10 * p32 - 1, p32]
+    cases.append(("wide", wide, 1, 10, root.tolist()))
+    # two roots whose totals tie above 2^32: the tree's first ordinal decides, against the input's rank order
+    tie = ranked([bare(1, 2, A, (1 << 33) + 5, 4), bare(1, 2, B, 1 << 33, 9), bare(1, 2, sub(B, 11), 5, 3)])
+    out, stats, root = expected_merge(tie, ts, 1, 10)
+    assert root.tolist() == [0, 1, 1] and out["count"].tolist() == [(1 << 33) + 5] * 2 and out["first"].tolist() == [3, 4]
+    assert inserts(out) == [B, A]
+    cases.append(("tie", tie, 1, 10, root.tolist()))
+    for name, counted, D, R, roots in cases:
+        assert expected_merge(counted, ts, D, R)[2].tolist() == roots, name
+    return cases
+
+
+def zero_counts(ts):
+    """List 2i.  count_c = 0 makes an entry the child of any entry within distance (0 <= count_p / R): a head, a zero-count
+    entry one substitution from it and one far from everything."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(9)
+    X = random_bases(rng, 40)
+    counted = ranked([bare(1, 2, X, 100, 0), bare(1, 2, sub(X, 17), 0, 1), bare(1, 2, random_bases(rng, 40), 0, 2)])
+    for D, R in ((1, 10), (2, 1), (1, U64)):
+        _, stats, root = expected_merge(counted, ts, D, R)
+        assert root.tolist() == [0, 0, 2] and stats["reads_moved"] == 0 and stats["merged"] == 1
+    return counted
+
+
+def primitive_defects(ts, pairs=300):
+    """List 2j.  2 * pairs entries (a parent of 2000 .. reads and its child of 1 .. 9, one substitution apart, 30-base inserts,
+    over three gene pairs) in which a few entries carry what dcrx_merge_parents_device's rules call out of reach.  Returns
+    (what the device gets: the table, with `text_bytes`; the same table with those entries' inserts turned to N, for the
+    contract; the defect ranks)."""
+    assert full_anchors(ts)
+    rng = np.random.default_rng(606)
+    n_v, n_j = len(ts.v_regions), len(ts.j_regions)
+    entries = []
+    for k in range(pairs):
+        s = random_bases(rng, 30)
+        v, j = 1 + k % 3, 2
+        entries += [bare(v, j, s, 2000 + pairs - k, 2 * k), bare(v, j, sub(s, int(rng.integers(0, 30))), 1 + k % 9, 2 * k + 1)]
+    clean = ranked(entries)
+    n = len(entries)
+    dev = {f: np.array(x, copy=True) if isinstance(x, np.ndarray) else x for f, x in clean.items()}
+    text_bytes = len(clean["ins_text"]) - 1          # the last entry's insert leaves the text by one byte
+    dev["v"][5], dev["v"][100], dev["j"][255] = n_v, 65535, n_j
+    dev["ins_off"][257] = text_bytes + 5          # entry 256 runs past the text, entry 257 goes backwards
+    dev["ins_off"][451] = 0          # entry 450 goes backwards; entry 451 is then [0, 452 * 30): longer than any junction
+    dev["text_bytes"] = text_bytes
+    bad = [5, 100, 255, 256, 257, 450, 451, n - 1]
+    text = bytearray(clean["ins_text"])
+    for k in bad:
+        text[30 * k:30 * k + 30] = b"N" * 30
+    contract = dict(clean, ins_text=bytes(text))
+    for D, R in ((1, 10), (2, 1)):
+        parent, reach = expected_parents(contract, ts, D, R)
+        assert [k for k in range(n) if not reach[k]] == bad and all(parent[k] == k for k in bad)
+        assert sum(1 for k in range(n) if parent[k] != k) >= pairs - len(bad)
+        # defects stand among parents and among children: a child of a defect parent stays alone
+        was = expected_parents(clean, ts, D, R)[0]
+        assert sum(1 for k in range(n) if was[k] in bad and was[k] != k) >= 3 and sum(1 for k in bad if was[k] != k) >= 2
+    return dev, contract, bad
+
+
+def short_window_mix(ts):
+    """List 1g, for a tag set whose V 1 is 20 bases, whose J 1 is 17 bases and whose V 2 has an unclean window: deletions up
+    to and one beyond either short window, a chain, the substitution the deletion walk turned into a longer insert, and
+    entries on the unclean V."""
+    assert len(ts.v_regions[1]) == 20 and len(ts.j_regions[1]) == 17 and not set(ts.v_regions[2].upper()[-ANCHOR:]) <= ACGT
+    A = "ACGTTGCAAGGT"
+    Vr = ts.v_regions[3].upper()
+    vend = Vr[len(Vr) - 3 - 1]          # the germline base a child with vdel 4 gave up
+    rows = [(1, 1, 20, 17, A, 500), (1, 1, 20, 17, sub(A, 4), 5),          # both windows deleted whole: the insert alone
+            (1, 1, 21, 17, A, 4), (1, 1, 20, 18, A, 3),          # one beyond either window: out of reach
+            (1, 1, 3, 2, A, 400), (1, 1, 3, 2, sub(A, 0), 4), (1, 0, 20, 0, A, 300), (1, 0, 20, 0, sub(A, 11), 3),
+            (0, 1, 0, 17, A, 200), (0, 1, 0, 17, sub(A, 5), 2), (0, 1, 0, 16, sub(A, 5), 2),
+            (2, 0, 3, 2, A, 100), (2, 0, 3, 2, sub(A, 1), 1),          # the unclean V: out of reach
+            (0, 0, 3, 2, A, 1000), (0, 0, 3, 2, sub(A, 4), 50), (0, 0, 3, 2, subs(A, (4, 7)), 2),          # a chain
+            (3, 0, 3, 0, A, 600), (3, 0, 4, 0, BASES[(BASES.index(vend) + 1) % 4] + A, 6)]
+    counted = ranked([r + (k,) for k, r in enumerate(rows)])
+    key = [tuple(x) for x in zip(counted["v"].tolist(), counted["j"].tolist(), counted["vdel"].tolist(), counted["jdel"].tolist(),
+                                 inserts(counted))]
+    at = {k: i for i, k in enumerate(key)}
+    _, stats, root = expected_merge(counted, ts, 1, 10)
+    assert stats["out_of_reach"] == 4 and stats["merged"] == 7 and stats["longest_chain"] == 2
+    for child, head in ((1, 0), (5, 4), (7, 6), (9, 8), (14, 13), (15, 13), (17, 16)):
+        assert root[at[rows[child][:5]]] == at[rows[head][:5]]
+    assert root[at[rows[10][:5]]] == at[rows[10][:5]]          # one J base more: another length
+    return counted

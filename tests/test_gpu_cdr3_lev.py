@@ -159,6 +159,30 @@ def test_a_class_that_starts_at_the_last_lane_of_a_block():
     _check([0] * 50 + classes, [""] * 25 + ["A" * 33] * 25 + strings, 1)
 
 
+# ---- decoys: equal packed words at neighbouring lengths, classes that differ in their high bits ----
+
+@pytest.mark.parametrize("D", [1, 2])
+def test_a_zero_byte_is_one_insertion(D):
+    """b"CASSF", b"CASSF\\0" and b"CASSF\\0\\0" (and a pair of 31 and 32 bytes) pack to the same dwords: the edges are exactly the
+    length steps, one apart at D = 1 and also two apart at D = 2.  The run straddles sorted position 256."""
+    classes, strings, at = cnu.zero_byte_run(clu.families_indel(cnu.ZERO_RUN_FRONT, seed=41, length=6))
+    r, st = _check(classes, strings, D)
+    near = [sorted(int(x) - at for x in r["adj"][int(r["adj_off"][k]):int(r["adj_off"][k + 1])]) for k in range(at, at + 6)]
+    assert near == ([[1, 5], [0, 2], [1], [4], [3], [0]] if D == 1 else [[1, 2, 5], [0, 2, 5], [0, 1], [4], [3], [0, 1]])
+    assert cnu.no_edge_across(classes, r)
+
+
+@pytest.mark.parametrize("pair", cnu.CLASS_BIT_PAIRS, ids=["bit31", "bit26", "all-ones"])
+def test_classes_that_differ_in_their_high_bits(pair):
+    """As in test_gpu_cdr3_network.py, under the Levenshtein metric (the bucket is the class alone)."""
+    classes, strings, plain = cnu.class_bit_nodes(clu.families_indel(150, seed=43, length=12), pair, n_out=40 if pair[1] == 0xFFFFFFFF else 0)
+    w = [1 + (7 * k) % 13 for k in range(len(strings))]
+    for D in (1, 2):
+        want = _check(classes, strings, D)
+        cnu.assert_same(want, clu.expected_lev_network(plain, strings, w, D))
+        assert want[1]["edges"] > 100 and cnu.no_edge_across(classes, want[0])
+
+
 # ---- component rounds ----
 
 def test_a_shuffled_path_grown_letter_by_letter():

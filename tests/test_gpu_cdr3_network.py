@@ -93,6 +93,29 @@ def test_a_bucket_that_starts_at_the_last_lane_of_a_block():
     _check([0] * 50 + classes, [""] * 25 + ["A" * 33] * 25 + strings, 1)
 
 
+# ---- decoys: equal packed words in neighbouring buckets, classes that differ in their high bits ----
+
+@pytest.mark.parametrize("D", [1, 2])
+def test_a_zero_byte_lengthens_a_string_into_the_next_bucket(D):
+    """b"CASSF", b"CASSF\\0" and b"CASSF\\0\\0" (and a pair of 31 and 32 bytes) pack to the same dwords; only the key keeps them
+    apart.  The three buckets straddle sorted position 256."""
+    classes, strings, at = cnu.zero_byte_run(cnu.families(cnu.ZERO_RUN_FRONT, seed=41, length=6))
+    r, st = _check(classes, strings, D)
+    assert r["degree"][at:].tolist() == [1, 0, 0, 0, 0, 1] and cnu.no_edge_across(classes, r)
+
+
+@pytest.mark.parametrize("pair", cnu.CLASS_BIT_PAIRS, ids=["bit31", "bit26", "all-ones"])
+def test_classes_that_differ_in_their_high_bits(pair):
+    """The same strings under two classes that differ in bit 31, in bit 26 (the key's bit 32) and in bit 0 of 0xFFFFFFFF (with
+    nodes out of reach, which sort directly behind that class): the edges are those under classes 0 and 1."""
+    classes, strings, plain = cnu.class_bit_nodes(cnu.families(150, seed=43, length=12), pair, n_out=40 if pair[1] == 0xFFFFFFFF else 0)
+    w = [1 + (7 * k) % 13 for k in range(len(strings))]
+    for D in (1, 2):
+        want = _check(classes, strings, D)
+        cnu.assert_same(want, cnu.expected_network(plain, strings, w, D))
+        assert want[1]["edges"] > 100 and cnu.no_edge_across(classes, want[0])
+
+
 # ---- lengths and difference positions ----
 
 @pytest.mark.parametrize("D", [1, 2])

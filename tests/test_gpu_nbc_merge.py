@@ -1,7 +1,9 @@
 """The error merge (`--merge-errors`) through the HIP path: dcrx_merge_dcrs and dcrx_merge_parents_device against the contract
 written in Python (nm.expected_merge) — every array of the result, root_of and the statistics, exactly — on tables counted on
-the GPU from noisy clonal reads, on one hot bucket, on degenerate tables, and the stage end to end against the oracle's DCRs put
-through a Counter and expected_merge."""
+the GPU from noisy clonal reads, on one hot bucket, on degenerate tables, on lists constructed for the walk's decisions (decoys in
+the bucket in front, both ends of the ratio prefix, tile and word edges, a chain of 384 links, 64-bit counts and ratios, the
+primitive's out-of-reach rules and two calls on one work space), and the stage end to end against the oracle's DCRs put through
+a Counter and expected_merge."""
 import gzip
 
 import numpy as np
@@ -208,6 +210,180 @@ def test_parents_device_on_a_stream_of_the_callers():
     # too small a work space is an error, not a launch
     with pytest.raises(nat.DcrxError, match="work space"):
         nat.merge_parents_device(t, n, *bufs, d_text, len(text), 1, 10, d_parent, d_reach, d_work, work_bytes - 256, s.ptr)
+
+
+# ---- constructed lists (tests/nbc_merge_util.py builds them and asserts each one's premise on the contract; their CPU twins
+# are in test_nbc_merge.py): merge_parents_kernel's walk, the 64-bit counts, the primitive's rules.  What each list is there to
+# fail: a walk that ignores `start` (1a, 1b) or stops after its first tile (1c at offset 256, 1e); `<=` for `<` at the prefix's
+# end and `>` for `>=` at the early-out (1c); a distance that skips the second half (1f); needed_count without its overflow
+# guard (2h); fewer than nine rounds of pointer jumping (1e); a bucket key without v (1b). ----
+
+@pytest.fixture(scope="module")
+def config2():
+    ts = synth.config_tagset(2)
+    return ts, _tables(ts)
+
+
+@pytest.mark.parametrize("n_fill", nm.DECOY_FILLERS)
+def test_padding_decoys_across_bucket_edges(config2, n_fill):
+    """List 1a: X, X[:-1], X + "A" and X + "AA" pack to (nearly) the same dwords and stand in neighbouring buckets, which
+    start at sorted position n_fill; only `p >= start` keeps a lane out of the bucket in front."""
+    ts, t = config2
+    for length in nm.DECOY_LENGTHS:
+        for with_children in (False, True):
+            counted, merges = nm.padding_decoys(ts, length, n_fill, with_children)
+            assert _check(t, ts, counted, 2, 1)["merged"] == merges, (length, with_children)
+
+
+@pytest.mark.parametrize("axis", ["v", "j"])
+def test_identical_junction_under_another_gene_pair(config2, axis):
+    """List 1b."""
+    ts, t = config2
+    counted = nm.gene_pair_decoys(ts, axis)
+    for D, R in ((1, 10), (2, 1)):
+        assert _check(t, ts, counted, D, R)["merged"] == (2 if R == 10 else 3)
+
+
+@pytest.mark.parametrize("R", [1, 2, 10])
+def test_prefix_ends(config2, R):
+    """List 1c: the last eligible parent has exactly R * c reads (or one less, and then is none) at bucket offsets on and
+    around a tile's edge and right in front of the child; offset 0 is the early-out's edge."""
+    ts, t = config2
+    for k, gap in nm.PREFIX_PLACES:
+        for eligible in (True, False):
+            counted, child, want = nm.prefix_end(ts, R, k, gap, eligible)
+            for D in (1, 2):
+                assert _check(t, ts, counted, D, R)["merged"] >= int(eligible), (k, gap, eligible, D)
+
+
+@pytest.mark.parametrize("D", [1, 2])
+def test_equal_counts_at_ratio_one(config2, D):
+    """List 1d."""
+    ts, t = config2
+    assert _check(t, ts, nm.equal_counts_ball(ts), D, 1)["merged"] > 300
+
+
+@pytest.mark.parametrize("n_out", [0, 200])
+def test_deep_chain(config2, n_out):
+    """List 1e: 384 links over two blocks; nine rounds of pointer jumping, and the depths add up."""
+    ts, t = config2
+    counted = nm.deep_chain(ts, n_out)
+    for D in (1, 2):
+        stats = _check(t, ts, counted, D, 1)
+        assert stats["longest_chain"] == nm.CHAIN_LINKS // D and stats["roots_out"] == 1 + n_out and stats["reads_moved"] == 2688
+
+
+def test_lengths_and_word_edges(config2):
+    """List 1f."""
+    ts, t = config2
+    counted, expect = nm.lengths_and_word_edges(ts)
+    for D in (1, 2):
+        stats = _check(t, ts, counted, D, 10)
+        assert stats["merged"] == 1 + sum(1 for _, nsub in expect.values() if nsub <= D) and stats["out_of_reach"] == 2
+        _check(t, ts, counted, D, 1)
+
+
+def test_short_and_unclean_windows():
+    """List 1g: windows shorter than the anchor and an unclean one, through the device build of the tables."""
+    from tests.test_nbc_merge import _short_region_tagset
+    ts = _short_region_tagset()
+    stats = _check(_tables(ts), ts, nm.short_window_mix(ts), 1, 10)
+    assert stats["out_of_reach"] == 4 and stats["merged"] == 7
+
+
+def test_counts_and_ratios_up_to_64_bits(config2):
+    """List 2h."""
+    ts, t = config2
+    for name, counted, D, R, roots in nm.big_counts(ts):
+        got, stats, root_of = nat.merge_dcrs(t, counted, D, R)
+        assert root_of.tolist() == roots, name
+        _check(t, ts, counted, D, R)
+
+
+def test_a_count_of_zero_is_a_child(config2):
+    """List 2i."""
+    ts, t = config2
+    for D, R in ((1, 10), (2, 1), (1, nm.U64)):
+        assert _check(t, ts, nm.zero_counts(ts), D, R)["merged"] == 1
+
+
+class _DeviceTable:
+    """A counted table in device memory, as dcrx_merge_parents_device takes it."""
+
+    def __init__(self, counted, text_bytes=None):
+        self.n = len(counted["v"])
+        self.bufs = [nat.DeviceBuffer.from_host(np.ascontiguousarray(counted[f], dtype=ty))
+                     for f, ty in (("v", np.uint16), ("j", np.uint16), ("vdel", np.uint8), ("jdel", np.uint8), ("count", np.uint64),
+                                   ("ins_off", np.uint64))]
+        text = np.frombuffer(counted["ins_text"], np.uint8)
+        self.text = nat.DeviceBuffer.from_host(text)
+        self.text_bytes = len(text) if text_bytes is None else text_bytes
+        self.parent, self.reach = nat.DeviceBuffer(4 * self.n), nat.DeviceBuffer.from_host(np.full(self.n, 7, np.uint8))
+
+    def launch(self, t, D, R, work, work_bytes, stream, parent=None, with_reach=True):
+        nat.merge_parents_device(t, self.n, *self.bufs, self.text, self.text_bytes, D, R, parent or self.parent,
+                                 self.reach if with_reach else None, work, work_bytes, stream.ptr)
+
+
+def test_primitive_out_of_reach_rules(config2):
+    """List 2j: a v or j the tables do not have and inserts that leave the text or go backwards are out of reach, nothing
+    more: reach is 0 exactly there, such an entry is its own parent and no one else's, the rest is the contract's."""
+    ts, t = config2
+    dev, contract, bad = nm.primitive_defects(ts)
+    d = _DeviceTable(dev, dev["text_bytes"])
+    wb = int(nat.lib().dcrx_merge_work_bytes(d.n))
+    work, s = nat.DeviceBuffer(wb), nat.Stream()
+    for D, R in ((1, 10), (2, 1)):
+        d.launch(t, D, R, work, wb, s)
+        s.synchronize()
+        want_parent, want_reach = nm.expected_parents(contract, ts, D, R)
+        reach = d.reach.to_host(np.uint8, d.n)
+        assert np.nonzero(reach == 0)[0].tolist() == bad and set(reach.tolist()) == {0, 1}
+        assert reach.astype(bool).tolist() == want_reach
+        parent = d.parent.to_host(np.uint32, d.n)
+        assert parent.tolist() == want_parent and all(parent[k] == k for k in bad)
+
+
+def test_two_calls_in_a_row_share_a_work_space(config2):
+    """List 2k: calls back to back on one stream of the caller's, one work space, no synchronisation in between, each into
+    its own parent buffer; one of them without reach flags."""
+    ts, t = config2
+    a = nm.padding_decoys(ts, 64, 255, True)[0]
+    b = nm.equal_counts_ball(ts)
+    da, db = _DeviceTable(a), _DeviceTable(b)
+    wb = max(int(nat.lib().dcrx_merge_work_bytes(x.n)) for x in (da, db))
+    work, s = nat.DeviceBuffer(wb), nat.Stream()
+    calls = [(da, 2, 1, True), (db, 1, 1, False), (da, 1, 1, False), (db, 2, 1, True)]
+    single = []
+    for d, D, R, with_reach in calls:          # one call at a time
+        d.launch(t, D, R, work, wb, s, with_reach=with_reach)
+        s.synchronize()
+        single.append(d.parent.to_host(np.uint32, d.n))
+        want_parent, want_reach = nm.expected_parents(a if d is da else b, ts, D, R)
+        assert single[-1].tolist() == want_parent
+        assert d.reach.to_host(np.uint8, d.n).tolist() == ([int(x) for x in want_reach] if with_reach else [7] * d.n)
+        d.reach = nat.DeviceBuffer.from_host(np.full(d.n, 7, np.uint8))
+    outs = [nat.DeviceBuffer.from_host(np.full(d.n, 0xFFFFFFFF, np.uint32)) for d, _, _, _ in calls]
+    for (d, D, R, with_reach), out in zip(calls, outs):          # all four in a row
+        d.launch(t, D, R, work, wb, s, parent=out, with_reach=with_reach)
+    s.synchronize()
+    for (d, _, _, _), out, want in zip(calls, outs, single):
+        assert np.array_equal(out.to_host(np.uint32, d.n), want)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_work_space_of_exactly_the_bytes_asked_for(config2, n):
+    ts, t = config2
+    counted = nm.take(nm.equal_counts_ball(ts), n)
+    d = _DeviceTable(counted)
+    wb = int(nat.lib().dcrx_merge_work_bytes(n))
+    assert wb > 256
+    work, s = nat.DeviceBuffer(wb), nat.Stream()
+    d.launch(t, 2, 1, work, wb, s)
+    s.synchronize()
+    assert d.parent.to_host(np.uint32, n).tolist() == nm.expected_parents(counted, ts, 2, 1)[0]
+    with pytest.raises(nat.DcrxError, match="work space"):
+        d.launch(t, 2, 1, work, wb - 256, s)
 
 
 def _merges_text(counted, root_of):

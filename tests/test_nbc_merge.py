@@ -1,7 +1,8 @@
 """The error merge of the barcode-free count (`--merge-errors`) on the CPU: the kernels' per-entry and per-pair code built by
-g++ (tests/host_merge) against Python, hand-made tables through the contract written in Python (nm.expected_merge) and through
-the host build, what the junction's definition is for on oracle-decombined noisy clonal reads, and the stage with the oracle
-standing in for the count (nu.OracleCountDevice) and the brute force for nat.merge_dcrs (nm.BruteMerge)."""
+g++ (tests/host_merge) against Python, hand-made tables and the constructed lists of nbc_merge_util through the contract
+written in Python (nm.expected_merge) and through the host build, what the junction's definition is for on oracle-decombined
+noisy clonal reads, and the stage with the oracle standing in for the count (nu.OracleCountDevice) and the brute force for
+nat.merge_dcrs (nm.BruteMerge)."""
 import gzip
 import os
 
@@ -174,6 +175,67 @@ def test_hand_made_tables():
     # nothing at all
     out, stats, root = nm.expected_merge(nm.table([]), ts, 1, 10)
     assert len(out["v"]) == 0 and stats["roots_out"] == 0 and len(root) == 0
+
+
+# ---- the constructed lists of nbc_merge_util (the builders assert each list's premise; here the host build agrees with the
+# contract on them, before a GPU sees them in test_gpu_nbc_merge.py) ----
+
+def _twin(ts, counted, D, R):
+    """_check_table, and the host build's parents and reach flags against the contract's, entry by entry."""
+    out, stats, root_of = _check_table(ts, counted, D, R)
+    parent, reach = nm.host_parents(nm.host_merge_lib(), ts, counted, D, R)
+    want_parent, want_reach = nm.expected_parents(counted, ts, D, R)
+    assert parent.tolist() == want_parent and reach.astype(bool).tolist() == want_reach
+    return out, stats, root_of
+
+
+@pytest.mark.parametrize("n_fill", nm.DECOY_FILLERS)
+def test_list_padding_decoys(n_fill):
+    ts = synth.config_tagset(2)
+    for length in nm.DECOY_LENGTHS:
+        for with_children in (False, True):
+            counted, merges = nm.padding_decoys(ts, length, n_fill, with_children)
+            assert _twin(ts, counted, 2, 1)[1]["merged"] == merges
+
+
+def test_list_gene_pair_decoys():
+    ts = synth.config_tagset(2)
+    for axis in "vj":
+        for D, R in ((1, 10), (2, 1)):
+            _twin(ts, nm.gene_pair_decoys(ts, axis), D, R)
+
+
+@pytest.mark.parametrize("R", [1, 2, 10])
+def test_list_prefix_ends(R):
+    ts = synth.config_tagset(2)
+    for k, gap in nm.PREFIX_PLACES:
+        for eligible in (True, False):
+            counted, child, want = nm.prefix_end(ts, R, k, gap, eligible)
+            for D in (1, 2):
+                assert nm.host_parents(nm.host_merge_lib(), ts, counted, D, R)[0][child] == want
+                _twin(ts, counted, D, R)
+
+
+def test_list_equal_counts_deep_chain_and_lengths():
+    ts = synth.config_tagset(2)
+    ball = nm.equal_counts_ball(ts)
+    edges, _ = nm.lengths_and_word_edges(ts)
+    for D in (1, 2):
+        _twin(ts, ball, D, 1)
+        for n_out in (0, 200):
+            assert _twin(ts, nm.deep_chain(ts, n_out), D, 1)[1]["longest_chain"] == nm.CHAIN_LINKS // D
+        for R in (10, 1):
+            _twin(ts, edges, D, R)
+    _twin(_short_region_tagset(), nm.short_window_mix(_short_region_tagset()), 1, 10)
+
+
+def test_list_big_and_zero_counts():
+    ts = synth.config_tagset(2)
+    for name, counted, D, R, roots in nm.big_counts(ts):
+        assert _twin(ts, counted, D, R)[2].tolist() == roots, name
+    for D, R in ((1, 10), (2, 1), (1, nm.U64)):
+        _twin(ts, nm.zero_counts(ts), D, R)
+    nm.primitive_defects(ts)          # (its premises; the defects themselves are the device primitive's rules)
 
 
 def test_substituted_reads_join_their_clone():
