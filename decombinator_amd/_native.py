@@ -415,6 +415,16 @@ class Cdr3NetworkStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CDR3_NETWORK_STATS]
 
 
+CDR3_MATCH_STATS = ("queries", "targets", "queries_out_of_reach", "targets_out_of_reach", "hits", "queries_hit", "queries_hit_weight",
+                    "targets_hit", "largest_degree")
+CDR3_MATCH_MAX_SAMPLES = 64         # files of one `match` call
+CDR3_MATCH_COLUMNS = ["clonotype", "v_call", "j_call", "junction_aa", "duplicate_count", "target", "distance"]      # then db_<column> ...
+
+
+class Cdr3MatchStatsC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in CDR3_MATCH_STATS]
+
+
 OVERLAP_MAX_SAMPLES = 64       # DCRX_OVERLAP_MAX_SAMPLES
 OVERLAP_MAX_ROWS = 1 << 30     # dcrx_overlap_run: DCRX_E_UNSUPPORTED from here on
 OVERLAP_PLANES = ("shared", "shared_weight", "min_weight", "prod_lo", "prod_hi")      # enum dcrx_overlap_plane
@@ -471,6 +481,8 @@ EXPORTS = [
     "dcrx_overlap_set_hash_bits", "dcrx_overlap_run", "dcrx_overlap_destroy", "dcrx_overlap_info", "dcrx_overlap_export",
     "dcrx_overlap_pairs_device", "dcrx_format_overlap_public",
     "dcrx_downsample_work_bytes", "dcrx_downsample_device", "dcrx_downsample", "dcrx_abundance_classes",
+    "dcrx_cdr3_index_create", "dcrx_cdr3_index_destroy", "dcrx_cdr3_index_info", "dcrx_cdr3_match_work_bytes", "dcrx_cdr3_match_device",
+    "dcrx_cdr3_match_run", "dcrx_cdr3_match_destroy", "dcrx_cdr3_match_info", "dcrx_cdr3_match_export", "dcrx_format_cdr3_matches",
 ]
 
 _lib = None
@@ -625,6 +637,17 @@ def lib():
         "dcrx_abundance_classes": (C.c_int64, [u32, u64, vp, vp, vp, vp, vp, vp]),
         "dcrx_format_overlap_public": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, u32, vp, vp, u32, vp, vp, vp,
                                                    vp, vp, u64]),
+        "dcrx_cdr3_index_create": (i32, [u64, vp, vp, vp, C.POINTER(vp)]),
+        "dcrx_cdr3_index_destroy": (None, [vp]),
+        "dcrx_cdr3_index_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "dcrx_cdr3_match_work_bytes": (u64, [u64, u64, u32]),
+        "dcrx_cdr3_match_device": (i32, [vp, u64, vp, vp, vp, u64, u32, u32, vp, vp, vp, u64, vp, vp, u64, vp]),
+        "dcrx_cdr3_match_run": (i32, [vp, u64, vp, vp, vp, vp, u32, u32, C.POINTER(vp)]),
+        "dcrx_cdr3_match_destroy": (None, [vp]),
+        "dcrx_cdr3_match_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(Cdr3MatchStatsC)]),
+        "dcrx_cdr3_match_export": (i32, [vp, vp, vp, vp, vp, vp]),
+        "dcrx_format_cdr3_matches": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp,
+                                                 u32, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1466,6 +1489,109 @@ def format_cdr3_edges(aa_off, aa_text: bytes, result: dict, metric="hamming") ->
     need = check(int(fmt(*args, None, 0)))
     out = _uninitialised_bytes(max(1, need))
     check(int(fmt(*args, _bytes_address(out), need)))
+    return bytes(out[:need])
+
+
+# ---- match (the `match` sub-command): include/dcrx.h "match" ----
+
+class Cdr3Index:
+    """dcrx_cdr3_index_t: the targets (class, string = text[off[j]:off[j + 1]]) of a database, built on the current device once
+    and kept there for any number of cdr3_match / cdr3_match_device calls, under either metric and every distance."""
+
+    def __init__(self, classes, off, text: bytes):
+        cls = np.ascontiguousarray(classes, dtype=np.uint32)
+        o, t = _node_arrays(off, text)
+        if len(o) != len(cls) + 1:
+            raise ValueError("Cdr3Index: one class per target, m + 1 offsets")
+        h = C.c_void_p()
+        check(lib().dcrx_cdr3_index_create(len(cls), cls.ctypes.data, o.ctypes.data, t.ctypes.data, C.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    def info(self) -> dict:
+        n, out, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().dcrx_cdr3_index_info(self._h, C.byref(n), C.byref(out), C.byref(b)))
+        return {"targets": n.value, "out_of_reach": out.value, "device_bytes": b.value}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dcrx_cdr3_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cdr3_match_work_bytes(m_q: int, text_bytes: int, metric="hamming") -> int:
+    """dcrx_cdr3_match_work_bytes."""
+    return int(lib().dcrx_cdr3_match_work_bytes(int(m_q), int(text_bytes), cdr3_metric_code(metric)))
+
+
+def cdr3_match_device(index: Cdr3Index, m_q: int, d_class, d_off, d_text, text_bytes: int, distance: int, d_degree, d_hit_off, d_hit,
+                      hit_cap: int, d_hit_need, d_work, work_bytes: int, stream=None, metric="hamming"):
+    """dcrx_cdr3_match_device: degree and hits of every query of a table in HBM (DeviceBuffers) against an index, asynchronous on
+    `stream`."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    check(lib().dcrx_cdr3_match_device(index.handle, int(m_q), ptr(d_class), ptr(d_off), ptr(d_text), int(text_bytes), int(distance),
+                                       cdr3_metric_code(metric), ptr(d_degree), ptr(d_hit_off), ptr(d_hit), int(hit_cap), ptr(d_hit_need),
+                                       ptr(d_work), int(work_bytes), stream))
+
+
+def cdr3_match(index: Cdr3Index, classes, off, text: bytes, weights, distance: int, metric="hamming") -> dict:
+    """dcrx_cdr3_match_run on the index's device, and everything it exports: m_q queries (class, string = text[off[i]:off[i + 1]],
+    weight) against the index's targets; a hit is a query and a target of one class within `distance` (0, 1 or 2) under `metric`
+    -> {"degree" per query, "hit_off" (m_q + 1) and "hit" (every query's targets ascending), "t_queries" and "t_weight" per
+    target, "stats": dict over CDR3_MATCH_STATS}."""
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    o, t = _node_arrays(off, text)
+    m = len(cls)
+    if len(o) != m + 1 or len(w) != m:
+        raise ValueError("cdr3_match: one class and one weight per query, m + 1 offsets")
+    h = C.c_void_p()
+    check(lib().dcrx_cdr3_match_run(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data, int(distance),
+                                    cdr3_metric_code(metric), C.byref(h)))
+    try:
+        n_t, n_hits, st = C.c_uint64(0), C.c_uint64(0), Cdr3MatchStatsC()
+        check(lib().dcrx_cdr3_match_info(h, None, C.byref(n_t), C.byref(n_hits), C.byref(st)))
+        T, H = n_t.value, n_hits.value
+        degree, hit, tq = np.zeros(max(m, 1), np.uint32), np.zeros(max(H, 1), np.uint32), np.zeros(max(T, 1), np.uint32)
+        hit_off, tw = np.zeros(m + 1, np.uint64), np.zeros(max(T, 1), np.uint64)
+        check(lib().dcrx_cdr3_match_export(h, degree.ctypes.data, hit_off.ctypes.data, hit.ctypes.data, tq.ctypes.data, tw.ctypes.data))
+    finally:
+        lib().dcrx_cdr3_match_destroy(h)
+    return {"degree": degree[:m], "hit_off": hit_off, "hit": hit[:H], "t_queries": tq[:T], "t_weight": tw[:T],
+            "stats": {k: int(getattr(st, k)) for k in CDR3_MATCH_STATS}}
+
+
+def format_cdr3_matches(result: dict, v_idx, j_idx, v_calls, j_calls, off, text: bytes, weights, t_off, t_text: bytes, db_header: bytes,
+                        db_lines, metric="hamming") -> bytes:
+    """dcrx_format_cdr3_matches: the `.cdr3_matches.tsv` text of a cdr3_match result — per hit the query's rank, calls, string
+    and weight, the target's rank, the distance, and the target's database line db_lines[j] (bytes) under db_header."""
+    vi, ji = (np.ascontiguousarray(a, dtype=np.uint32) if len(a) else np.zeros(1, np.uint32) for a in (v_idx, j_idx))
+    w = np.ascontiguousarray(weights, dtype=np.uint64) if len(weights) else np.zeros(1, np.uint64)
+    (o, t), (to, tt) = _node_arrays(off, text), _node_arrays(t_off, t_text)
+    (vc, vo), (jc, jo) = _calls_blob(v_calls), _calls_blob(j_calls)
+    lo = np.zeros(len(db_lines) + 1, dtype=np.uint64)
+    if len(db_lines):
+        lo[1:] = np.cumsum([len(b) for b in db_lines])
+    lt = np.frombuffer(b"".join(db_lines) + b"\0", dtype=np.uint8)
+    hdr = np.frombuffer(bytes(db_header) + b"\0", dtype=np.uint8)
+    hit_off = np.ascontiguousarray(result["hit_off"], dtype=np.uint64)
+    hit = np.ascontiguousarray(result["hit"], dtype=np.uint32) if len(result["hit"]) else np.zeros(1, np.uint32)
+    args = [len(o) - 1, hit_off.ctypes.data, hit.ctypes.data, vi.ctypes.data, ji.ctypes.data, len(v_calls), vc.ctypes.data, vo.ctypes.data,
+            len(j_calls), jc.ctypes.data, jo.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data, len(to) - 1, to.ctypes.data,
+            tt.ctypes.data, hdr.ctypes.data, len(db_header), lo.ctypes.data, lt.ctypes.data, cdr3_metric_code(metric)]
+    need = check(int(lib().dcrx_format_cdr3_matches(*args, None, 0)))
+    out = _uninitialised_bytes(max(1, need))
+    check(int(lib().dcrx_format_cdr3_matches(*args, _bytes_address(out), need)))
     return bytes(out[:need])
 
 

@@ -1,0 +1,594 @@
+// dcrx_cdr3match.hip — match (`match`): which queries (a sample's clonotypes) are the same as, or one or two residues from, a
+// target (an entry of a database, or of another sample); include/dcrx.h "match" holds the contract, dcrx_cdr3net_core.h the
+// per-node and per-pair code (the CDR3 network's), dcrx_cdr3match_core.h the walk's look-ups.
+//
+// The index (dcrx_cdr3_index_create), once per database: keys, then per bucket order — (class, length) for the Hamming walk,
+// class alone for the Levenshtein walk — a stable radix sort of (key, rank) and the gather of the packed strings (and, in the
+// class order, of the presence masks).  It stays on the device.
+// The primitive (dcrx_cdr3_match_device), all on the caller's stream and in the caller's work space:
+//   keys, sort, gather   the queries, as the network prepares its nodes (cdr3match_keys_kernel, cdr3match_gather_kernel)
+//   degrees  cdr3match_walk_kernel<false>: a block of 256 consecutive sorted queries, one per lane and in registers, finds the
+//            first target at or above its first query's bucket (a binary search over the index's sorted keys, the same for
+//            every lane) and stages the targets from there in LDS tiles of 256 (8 KB of strings, 2 KB of keys, 1 KB of ranks,
+//            1 KB of masks) until a tile starts behind its last query's bucket; every lane of a wave reads the same staged
+//            target (a broadcast), and a wave skips a tile whose buckets miss its own.  A bucket's targets are in rank order:
+//            a query's hits come in ascending rank, with no atomics
+//   scan     an exclusive sum of the degrees in rank order: hit_off, whose end is the need
+//   write    cdr3match_walk_kernel<true>: the same walk writes every hit's rank at its exact offset
+// The host entry (dcrx_cdr3_match_run) runs those two halves around the hits' allocation, then the totals: a lane per query
+// adds its row's hits onto the targets (integer atomics, results unused).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dcrx.h"
+#include "dcrx_cdr3match_core.h"
+#include "dcrx_group.h"
+#include "dcrx_text.h"
+
+using dcrx::set_err;
+using namespace dcrx_cdr3match;
+using namespace dcrx_group;
+
+namespace {
+
+constexpr uint64_t MAX_NODES = 1ull << 30;
+constexpr uint32_t NO_ENTRY = 0xFFFFFFFFu;
+static_assert(BLOCK == (int)QUERIES && BLOCK == (int)TILE, "a lane holds one query and stages one target");
+
+struct Nodes {
+  const uint32_t *cls;
+  const uint64_t *off;
+  const uint8_t *text;
+  uint64_t text_bytes;
+};
+
+// one side in one bucket order: the sorted keys, the ranks, the packed strings and (class order) the presence masks
+struct Sorted {
+  const uint64_t *key;
+  const uint32_t *idx;
+  const uint4 *sj;
+  const uint32_t *pres;
+  uint32_t n;
+};
+
+// the length of node e's string; one past the reach for offsets that go backwards or leave the text
+__device__ __forceinline__ uint64_t node_len(const Nodes &N, uint32_t e, uint64_t *at) {
+  const uint64_t a = N.off[e], b = N.off[e + 1];
+  *at = a;
+  return (b < a || b > N.text_bytes) ? (uint64_t)MAX_LEN + 1 : b - a;
+}
+
+__global__ __launch_bounds__(BLOCK) void cdr3match_keys_kernel(Nodes N, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
+  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= n) return;
+  uint64_t at;
+  key[e] = node_key(N.cls[e], node_len(N, e, &at));
+  idx[e] = e;
+}
+
+// per sorted position the packed string, and (pres != null) its letter-presence mask
+__global__ __launch_bounds__(BLOCK) void cdr3match_gather_kernel(Nodes N, uint32_t n, const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
+                                                                 uint32_t *__restrict__ pres) {
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= n) return;
+  uint64_t at;
+  const uint64_t len = node_len(N, idx[s], &at);
+  uint32_t w[WORDS];
+  pack(N.text + (in_reach(len) ? at : 0), len, w);
+  sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
+  sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+  if (pres) pres[s] = presence(w, in_reach(len) ? (uint32_t)len : 0u);
+}
+
+// The walk.  q_*: the queries, t_*: the targets, both sorted in the walk's bucket order.  WRITE false: degree[rank] (and the same
+// as 64 bits, for the scan); true: the hits' ranks at hit_off[rank].  LEV: the buckets are the classes (the keys still hold the
+// lengths), the presence masks are staged with the strings, and a pair is tested by length difference, presence masks and
+// lev_within instead of the Hamming distance.
+template <bool WRITE, bool LEV>
+__global__ __launch_bounds__(BLOCK) void cdr3match_walk_kernel(const uint4 *__restrict__ q_sj, const uint64_t *__restrict__ q_key,
+                                                               const uint32_t *__restrict__ q_idx, const uint32_t *__restrict__ q_pres,
+                                                               uint32_t n_q, const uint4 *__restrict__ t_sj, const uint64_t *__restrict__ t_key,
+                                                               const uint32_t *__restrict__ t_idx, const uint32_t *__restrict__ t_pres,
+                                                               uint32_t n_t, uint32_t limit, uint32_t *__restrict__ degree,
+                                                               uint64_t *__restrict__ deg64, const uint64_t *__restrict__ hit_off,
+                                                               uint32_t *__restrict__ hit, uint64_t hit_cap) {
+  __shared__ uint4 lds_j[TILE * 2];
+  __shared__ uint64_t lds_k[TILE];
+  __shared__ uint32_t lds_r[WRITE ? TILE : 1];
+  __shared__ uint32_t lds_p[LEV ? TILE : 1];
+  const uint32_t s0 = blockIdx.x * BLOCK;
+  const uint32_t s = s0 + threadIdx.x;
+  const bool valid = s < n_q;
+  const uint64_t key_own = valid ? q_key[s] : KEY_OUT_OF_REACH;
+  const bool reach = key_own != KEY_OUT_OF_REACH;
+  const uint64_t k_own = bucket_of<LEV>(key_own);
+  const uint32_t len_own = key_length(key_own), pres_own = LEV && valid ? q_pres[s] : 0u;
+  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t e = 0, count = 0;
+  uint64_t at = 0;
+  if (valid) {
+    e = q_idx[s];
+    if (WRITE) at = hit_off[e];
+    if (reach) {
+      const uint4 a = q_sj[2 * (size_t)s], b = q_sj[2 * (size_t)s + 1];
+      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
+    }
+  }
+  // the wave's buckets (sorted along s; lanes behind the table hold the largest)
+  const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
+  const Range R = block_range<LEV>(q_key, n_q, s0, t_key, n_t);      // (the same for every lane of the block)
+  for (uint32_t t = R.first; t < n_t; t += TILE) {
+    if (!goes_on<LEV>(R, t_key[t])) break;
+    __syncthreads();                                        // the previous tile is no longer read
+    const uint32_t tile_n = min((uint32_t)TILE, n_t - t);
+    if (threadIdx.x < tile_n) {
+      const uint32_t p = t + threadIdx.x;
+      lds_j[2 * threadIdx.x] = t_sj[2 * (size_t)p];
+      lds_j[2 * threadIdx.x + 1] = t_sj[2 * (size_t)p + 1];
+      lds_k[threadIdx.x] = t_key[p];
+      if (WRITE) lds_r[threadIdx.x] = t_idx[p];
+      if (LEV) lds_p[threadIdx.x] = t_pres[p];
+    }
+    __syncthreads();
+    if (wave_skips(bucket_of<LEV>(lds_k[0]), bucket_of<LEV>(lds_k[tile_n - 1]), w_lo, w_hi)) continue;
+    const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
+    if (!LEV) {
+      for (uint32_t q = 0; q < tile_n; q++) {
+        const uint64_t kq = lds_k[q];
+        if (kq < w_lo) continue;
+        if (kq > w_hi) break;
+        if (reach && kq == k_own && distance(own, lj + q * WORDS, limit) <= limit) {
+          if (WRITE && at + count < hit_cap) hit[at + count] = lds_r[q];
+          count++;
+        }
+      }
+      continue;
+    }
+    // LEV: a target that passes the cheap tests waits in `pending` (one per lane), and lev_within runs — for every lane that
+    // has one waiting, each on its own — only once some lane meets its next one, and at the tile's end, as in the network's
+    // walk: the few lanes of a wave that pass at one target would otherwise run it nearly alone.  A lane takes its targets
+    // in order.
+    uint32_t pending = NO_ENTRY;
+    auto settle = [&]() {
+      if (pending != NO_ENTRY) {
+        if (lev_within(own, len_own, lj + pending * WORDS, key_length(lds_k[pending]), limit) <= limit) {
+          if (WRITE && at + count < hit_cap) hit[at + count] = lds_r[pending];
+          count++;
+        }
+        pending = NO_ENTRY;
+      }
+    };
+    for (uint32_t q = 0; q < tile_n; q++) {
+      const uint64_t key_q = lds_k[q], kq = key_class(key_q);
+      if (kq < w_lo) continue;
+      if (kq > w_hi) break;
+      const uint32_t len_q = key_length(key_q);
+      const bool passes = reach && kq == k_own && len_q + limit >= len_own && len_own + limit >= len_q &&
+                          presence_allows(pres_own, lds_p[q], limit);
+      if (__any(passes && pending != NO_ENTRY)) settle();      // (the same for every lane of the wave)
+      if (passes) pending = q;
+    }
+    settle();      // (the next tile overwrites the staged targets)
+  }
+  if (valid && !WRITE) {
+    degree[e] = count;
+    deg64[e] = count;
+  }
+}
+
+// hit_off[m] and the need behind the scan
+__global__ void cdr3match_need_kernel(const uint64_t *__restrict__ deg64, uint64_t *__restrict__ hit_off, uint32_t n,
+                                      uint64_t *__restrict__ need) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint64_t total = hit_off[n - 1] + deg64[n - 1];
+    hit_off[n] = total;
+    if (need) *need = total;
+  }
+}
+
+// the host entry's: every hit of query i onto its target (the results of the atomics are not read)
+__global__ __launch_bounds__(BLOCK) void cdr3match_totals_kernel(const uint64_t *__restrict__ hit_off, const uint32_t *__restrict__ hit,
+                                                                 const uint64_t *__restrict__ weight, uint32_t n_q,
+                                                                 uint32_t *__restrict__ t_queries, unsigned long long *__restrict__ t_weight) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n_q) return;
+  const unsigned long long w = weight[i];
+  for (uint64_t k = hit_off[i], end = hit_off[i + 1]; k < end; k++) {
+    const uint32_t j = hit[k];
+    atomicAdd(&t_queries[j], 1u);
+    atomicAdd(&t_weight[j], w);
+  }
+}
+
+bool metric_exists(uint32_t metric) { return metric == METRIC_HAMMING || metric == METRIC_LEVENSHTEIN; }
+// D = 0 is byte equality: the (class, length) buckets and the Hamming test serve it under either metric
+bool walks_lev(uint32_t distance, uint32_t metric) { return metric == METRIC_LEVENSHTEIN && distance > 0; }
+
+// keys of n nodes, then their stable sort over the key's bits from begin_bit: (key[1], idx[1])
+int sorted_keys(const Nodes &N, uint64_t n, uint64_t *const key[2], uint32_t *const idx[2], Scratch cub, int begin_bit, bool make_keys,
+                hipStream_t s) {
+  if (make_keys) {
+    cdr3match_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, key[0], idx[0]);
+    HIP_TRY(hipGetLastError());
+  }
+  return sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, KEY_BITS, s, begin_bit);
+}
+
+int gather(const Nodes &N, uint64_t n, const uint32_t *idx, uint4 *sj, uint32_t *pres, hipStream_t s) {
+  cdr3match_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, idx, sj, pres);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
+// ---- work space of the primitive: the degree pass leaves the sorted queries there for the write pass
+struct Work {
+  uint64_t *key[2];
+  uint32_t *idx[2];
+  uint4 *sj;
+  uint64_t *deg64;
+  Scratch cub;
+  uint32_t *pres;      // (the Levenshtein walk's; null under Hamming)
+  int carve(Pool &P, uint64_t n, uint32_t metric) {
+    size_t cub_bytes = 0;
+    const uint64_t k = std::max<uint64_t>(n, 1);
+    int rc;
+    if ((rc = sort_pairs_bytes<uint32_t>(k, KEY_BITS, &cub_bytes)) || (rc = exclusive_sum_bytes<uint64_t>(k, &cub_bytes))) return rc;
+    P.get(&key[0], n); P.get(&key[1], n); P.get(&idx[0], n); P.get(&idx[1], n); P.get(&sj, 2 * n); P.get(&deg64, n); P.get(&cub, cub_bytes);
+    pres = nullptr;
+    if (metric == METRIC_LEVENSHTEIN) P.get(&pres, n);
+    return DCRX_OK;
+  }
+  Sorted queries(uint64_t n, bool lev) const { return Sorted{key[1], idx[1], sj, lev ? pres : nullptr, (uint32_t)n}; }
+};
+
+}  // namespace
+
+// the targets in both bucket orders, in one allocation
+struct dcrx_cdr3_index {
+  uint64_t m = 0, out_of_reach = 0, bytes = 0;
+  int device = -1;
+  Pool mem;
+  uint64_t *key[2] = {nullptr, nullptr};      // [0]: by (class, length); [1]: by class
+  uint32_t *idx[2] = {nullptr, nullptr};
+  uint4 *sj[2] = {nullptr, nullptr};
+  uint32_t *pres = nullptr;                   // of the class order
+  void carve() {
+    for (int o = 0; o < 2; o++) { mem.get(&key[o], m); mem.get(&idx[o], m); mem.get(&sj[o], 2 * m); }
+    mem.get(&pres, m);
+  }
+  Sorted targets(bool lev) const { return Sorted{key[lev], idx[lev], sj[lev], lev ? pres : nullptr, (uint32_t)m}; }
+};
+
+struct dcrx_cdr3_match {
+  dcrx_cdr3_match_stats_t stats{};
+  std::vector<uint32_t> degree, hit, t_queries;
+  std::vector<uint64_t> hit_off, t_weight;
+};
+
+namespace {
+
+int build_index(dcrx_cdr3_index &I, const uint32_t *cls, const uint64_t *off, const char *text) {
+  const uint64_t m = I.m, text_bytes = off[m] - off[0];
+  int rc;
+  I.carve();
+  I.bytes = I.mem.bytes();
+  if ((rc = I.mem.allocate())) return rc;
+  I.carve();
+  // what only the build needs: the nodes, the unsorted keys and ranks, hipCUB's scratch
+  Pool P;
+  uint32_t *d_cls, *d_idx;
+  uint64_t *d_off, *d_key;
+  uint8_t *d_text;
+  Scratch cub;
+  size_t cub_bytes = 0;
+  if ((rc = sort_pairs_bytes<uint32_t>(m, KEY_BITS, &cub_bytes))) return rc;
+  for (int pass = 0; pass < 2; pass++) {
+    P.get(&d_cls, m); P.get(&d_off, m + 1); P.get(&d_text, text_bytes); P.get(&d_key, m); P.get(&d_idx, m); P.get(&cub, cub_bytes);
+    if (pass == 0 && (rc = P.allocate())) return rc;
+  }
+  if ((rc = upload_spans(m, off, text, d_off, d_text)) || (rc = to_device(d_cls, cls, m))) return rc;
+  const Nodes N{d_cls, d_off, d_text, text_bytes};
+  for (int o = 0; o < 2; o++) {
+    uint64_t *const key[2] = {d_key, I.key[o]};
+    uint32_t *const idx[2] = {d_idx, I.idx[o]};
+    if ((rc = sorted_keys(N, m, key, idx, cub, o ? (int)LEN_BITS : 0, o == 0, nullptr)) ||
+        (rc = gather(N, m, I.idx[o], I.sj[o], o ? I.pres : nullptr, nullptr))) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(nullptr));      // (the build's buffers go out of scope)
+  return DCRX_OK;
+}
+
+// keys, sort, gather of the queries, the degree pass, the scan and the need
+int run_degrees(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, uint32_t limit, bool lev, uint32_t *d_degree, uint64_t *d_hit_off,
+                uint64_t *d_need, const Work &W, hipStream_t s) {
+  int rc;
+  if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, lev ? (int)LEN_BITS : 0, true, s)) ||
+      (rc = gather(N, n, W.idx[1], W.sj, lev ? W.pres : nullptr, s))) return rc;
+  const Sorted Q = W.queries(n, lev), T = I.targets(lev);
+  if (lev) cdr3match_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
+  else cdr3match_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
+  HIP_TRY(hipGetLastError());
+  if ((rc = exclusive_sum(W.cub, W.deg64, d_hit_off, n, s))) return rc;
+  cdr3match_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_hit_off, (uint32_t)n, d_need);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
+int run_write(const dcrx_cdr3_index &I, uint64_t n, uint32_t limit, bool lev, const uint64_t *d_hit_off, uint32_t *d_hit, uint64_t hit_cap,
+              const Work &W, hipStream_t s) {
+  const Sorted Q = W.queries(n, lev), T = I.targets(lev);
+  if (lev) cdr3match_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
+  else cdr3match_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
+// what every entry refuses of (index, m_q, distance, metric)
+int refuse(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, uint32_t distance, uint32_t metric) {
+  auto fail = [&](int code, const char *what) { return set_err(code, (std::string(who) + ": " + what).c_str()); };
+  if (!I) return fail(DCRX_E_INVALID, "null index");
+  if (m_q >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, "2^30 or more queries");
+  if (distance > 2) return fail(DCRX_E_INVALID, "the distance is 0, 1 or 2");
+  if (!metric_exists(metric)) return fail(DCRX_E_INVALID, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
+  return DCRX_OK;
+}
+
+int run_match(const dcrx_cdr3_index &I, uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+              uint32_t distance, uint32_t metric, dcrx_cdr3_match &M) {
+  const uint64_t text_bytes = off[m] - off[0], mt = I.m;
+  const bool lev = walks_lev(distance, metric);
+  int rc;
+  Pool P;
+  Work W;
+  uint32_t *d_cls, *d_degree, *d_tq;
+  uint64_t *d_off, *d_weight, *d_hit_off, *d_need;
+  unsigned long long *d_tw;
+  uint8_t *d_text;
+  for (int pass = 0; pass < 2; pass++) {
+    P.get(&d_cls, m); P.get(&d_off, m + 1); P.get(&d_text, text_bytes); P.get(&d_weight, m); P.get(&d_degree, m);
+    P.get(&d_hit_off, m + 1); P.get(&d_need, 1); P.get(&d_tq, mt); P.get(&d_tw, mt);
+    if ((rc = W.carve(P, m, metric)) || (pass == 0 && (rc = P.allocate()))) return rc;
+  }
+  if ((rc = upload_spans(m, off, text, d_off, d_text)) || (rc = to_device(d_cls, cls, m)) || (rc = to_device(d_weight, weight, m))) return rc;
+  const Nodes N{d_cls, d_off, d_text, text_bytes};
+
+  // the degree pass, then exactly the hits it sized
+  if ((rc = run_degrees(I, N, m, distance, lev, d_degree, d_hit_off, d_need, W, nullptr))) return rc;
+  uint64_t need = 0;
+  if ((rc = to_host(&need, d_need, 1))) return rc;
+  dcrx::DevBuf<uint32_t> d_hit;
+  if (d_hit.alloc(std::max<uint64_t>(need, 1))) return set_err(DCRX_E_NOMEM, "dcrx_cdr3_match_run: the hits do not fit the device's memory");
+  M.hit.resize(need);
+  HIP_TRY(hipMemsetAsync(d_tq, 0, mt * sizeof *d_tq, nullptr));
+  HIP_TRY(hipMemsetAsync(d_tw, 0, mt * sizeof *d_tw, nullptr));
+  if (need) {
+    if ((rc = run_write(I, m, distance, lev, d_hit_off, d_hit.get(), need, W, nullptr))) return rc;
+    cdr3match_totals_kernel<<<grid_for(m), BLOCK>>>(d_hit_off, d_hit.get(), d_weight, (uint32_t)m, d_tq, d_tw);
+    HIP_TRY(hipGetLastError());
+  }
+  if ((rc = to_host(M.degree.data(), d_degree, m)) || (rc = to_host(M.hit_off.data(), d_hit_off, m + 1)) ||
+      (rc = to_host(M.hit.data(), d_hit.get(), need)) || (rc = to_host(M.t_queries.data(), d_tq, mt)) ||
+      (rc = to_host(M.t_weight.data(), reinterpret_cast<const uint64_t *>(d_tw), mt))) return rc;
+  return DCRX_OK;
+}
+
+// the Levenshtein distance of two byte strings of any length (the matches file's column): a plain two-row table
+uint64_t host_levenshtein(const char *a, uint64_t la, const char *b, uint64_t lb) {
+  std::vector<uint64_t> prev(lb + 1), cur(lb + 1);
+  for (uint64_t j = 0; j <= lb; j++) prev[j] = j;
+  for (uint64_t i = 1; i <= la; i++) {
+    cur[0] = i;
+    for (uint64_t j = 1; j <= lb; j++) cur[j] = std::min({prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (a[i - 1] != b[j - 1] ? 1u : 0u)});
+    prev.swap(cur);
+  }
+  return prev[lb];
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcrx_cdr3_index_create(uint64_t m_t, const uint32_t *cls, const uint64_t *off, const char *text, dcrx_cdr3_index_t **index_out) try {
+  if (!index_out) return set_err(DCRX_E_INVALID, "dcrx_cdr3_index_create: null argument");
+  *index_out = nullptr;
+  if (m_t >= MAX_NODES) return set_err(DCRX_E_UNSUPPORTED, "dcrx_cdr3_index_create: 2^30 or more targets");
+  if (m_t && (!cls || !off)) return set_err(DCRX_E_INVALID, "dcrx_cdr3_index_create: null argument");
+  uint64_t out_of_reach = 0;
+  for (uint64_t k = 0; k < m_t; k++) {
+    if (off[k + 1] < off[k]) return set_err(DCRX_E_INVALID, "dcrx_cdr3_index_create: offsets go backwards");
+    if (!in_reach(off[k + 1] - off[k])) out_of_reach++;
+  }
+  if (m_t && off[m_t] > off[0] && !text) return set_err(DCRX_E_INVALID, "dcrx_cdr3_index_create: text is null");
+  dcrx_cdr3_index *I = new dcrx_cdr3_index();
+  I->m = m_t;
+  I->out_of_reach = out_of_reach;
+  if (m_t) {
+    int rc = DCRX_OK;
+    if (hipGetDevice(&I->device) != hipSuccess) rc = set_err(DCRX_E_NOGPU, "dcrx_cdr3_index_create: no current device");
+    if (!rc) rc = build_index(*I, cls, off, text);
+    if (rc) { delete I; return rc; }
+  }
+  *index_out = I;
+  return DCRX_OK;
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+void dcrx_cdr3_index_destroy(dcrx_cdr3_index_t *I) {
+  if (!I) return;
+  dcrx::DeviceGuard on(I->device);      // (what belongs to a device is released with that device current)
+  delete I;
+}
+
+int dcrx_cdr3_index_info(const dcrx_cdr3_index_t *I, uint64_t *targets, uint64_t *out_of_reach, uint64_t *device_bytes) {
+  if (!I) return set_err(DCRX_E_INVALID, "dcrx_cdr3_index_info: null handle");
+  if (targets) *targets = I->m;
+  if (out_of_reach) *out_of_reach = I->out_of_reach;
+  if (device_bytes) *device_bytes = I->m ? I->bytes : 0;
+  return DCRX_OK;
+}
+
+uint64_t dcrx_cdr3_match_work_bytes(uint64_t m_q, uint64_t text_bytes, uint32_t metric) {
+  (void)text_bytes;      // (the work space holds per-query keys, ranks and packed strings: the text's bytes do not enter it)
+  Pool P;
+  Work W;
+  if (m_q >= MAX_NODES || !metric_exists(metric) || W.carve(P, m_q, metric) != DCRX_OK) return 0;
+  return P.bytes();
+}
+
+int dcrx_cdr3_match_device(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off, const char *d_text,
+                           uint64_t text_bytes, uint32_t distance, uint32_t metric, uint32_t *d_degree, uint64_t *d_hit_off, uint32_t *d_hit,
+                           uint64_t hit_cap, uint64_t *d_hit_need, void *d_work, uint64_t work_bytes, void *hip_stream) try {
+  static const char who[] = "dcrx_cdr3_match_device";
+  int rc = refuse(who, I, m_q, distance, metric);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (m_q && (!d_class || !d_off || !d_degree || !d_hit_off || !d_work || (text_bytes && !d_text) || (hit_cap && !d_hit)))
+    return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: null argument");
+  dcrx::DeviceGuard on(I->device);      // (the index's device for the launches, the caller's again behind them; no index memory: neither)
+  if (!m_q || !I->m) {      // nothing can hit: no launch
+    if (d_hit_need) HIP_TRY(hipMemsetAsync(d_hit_need, 0, sizeof(uint64_t), s));
+    if (d_hit_off) HIP_TRY(hipMemsetAsync(d_hit_off, 0, (m_q + 1) * sizeof(uint64_t), s));
+    if (m_q) HIP_TRY(hipMemsetAsync(d_degree, 0, m_q * sizeof(uint32_t), s));
+    return DCRX_OK;
+  }
+  if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: the work space is not 256-byte aligned");
+  Pool P(d_work);
+  Work W;
+  if ((rc = W.carve(P, m_q, metric))) return rc;
+  if (work_bytes < P.bytes())
+    return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: the work space is smaller than dcrx_cdr3_match_work_bytes(m_q, text_bytes, metric)");
+  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
+  const bool lev = walks_lev(distance, metric);
+  if ((rc = run_degrees(*I, N, m_q, distance, lev, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
+  if (!d_hit || !hit_cap) return DCRX_OK;
+  return run_write(*I, m_q, distance, lev, d_hit_off, d_hit, hit_cap, W, s);
+} catch (const std::exception &e) {      // (a message that could not be built)
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int dcrx_cdr3_match_run(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *cls, const uint64_t *off, const char *text,
+                        const uint64_t *weight, uint32_t distance, uint32_t metric, dcrx_cdr3_match_t **match_out) try {
+  static const char who[] = "dcrx_cdr3_match_run";
+  if (!match_out) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: null argument");
+  *match_out = nullptr;
+  int rc = refuse(who, I, m_q, distance, metric);
+  if (rc) return rc;
+  if (m_q && (!cls || !off || !weight)) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: null argument");
+  uint64_t out_of_reach = 0, total = 0;
+  for (uint64_t k = 0; k < m_q; k++) {
+    if (off[k + 1] < off[k]) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: offsets go backwards");
+    if (!in_reach(off[k + 1] - off[k])) out_of_reach++;
+    if (__builtin_add_overflow(total, weight[k], &total))
+      return set_err(DCRX_E_UNSUPPORTED, "dcrx_cdr3_match_run: the sum of the query weights is 2^64 or more");
+  }
+  if (m_q && off[m_q] > off[0] && !text) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: text is null");
+  dcrx_cdr3_match *M = new dcrx_cdr3_match();
+  struct Drop {      // (released on every path that does not hand it over)
+    dcrx_cdr3_match *p;
+    ~Drop() { delete p; }
+  } drop{M};
+  M->stats.queries = m_q;
+  M->stats.targets = I->m;
+  M->stats.queries_out_of_reach = out_of_reach;
+  M->stats.targets_out_of_reach = I->out_of_reach;
+  M->degree.assign(m_q, 0);
+  M->hit_off.assign(m_q + 1, 0);
+  M->t_queries.assign(I->m, 0);
+  M->t_weight.assign(I->m, 0);
+  if (m_q && I->m) {
+    dcrx::DeviceGuard on(I->device);
+    if ((rc = run_match(*I, m_q, cls, off, text, weight, distance, metric, *M))) return rc;
+  }
+  M->stats.hits = M->hit.size();
+  for (uint64_t k = 0; k < m_q; k++) {
+    if (!M->degree[k]) continue;
+    M->stats.queries_hit++;
+    M->stats.queries_hit_weight += weight[k];
+    M->stats.largest_degree = std::max<uint64_t>(M->stats.largest_degree, M->degree[k]);
+  }
+  for (uint32_t q : M->t_queries) M->stats.targets_hit += q != 0;
+  drop.p = nullptr;
+  *match_out = M;
+  return DCRX_OK;
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+void dcrx_cdr3_match_destroy(dcrx_cdr3_match_t *M) { delete M; }
+
+int dcrx_cdr3_match_info(const dcrx_cdr3_match_t *M, uint64_t *queries, uint64_t *targets, uint64_t *hits, dcrx_cdr3_match_stats_t *stats) {
+  if (!M) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_info: null handle");
+  if (queries) *queries = M->degree.size();
+  if (targets) *targets = M->t_queries.size();
+  if (hits) *hits = M->hit.size();
+  if (stats) *stats = M->stats;
+  return DCRX_OK;
+}
+
+int dcrx_cdr3_match_export(const dcrx_cdr3_match_t *M, uint32_t *degree, uint64_t *hit_off, uint32_t *hit, uint32_t *t_queries,
+                           uint64_t *t_weight) {
+  if (!M) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_export: null handle");
+  auto copy = [](auto *dst, const auto &src) {
+    if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(src[0]));
+  };
+  copy(degree, M->degree); copy(hit_off, M->hit_off); copy(hit, M->hit); copy(t_queries, M->t_queries); copy(t_weight, M->t_weight);
+  return DCRX_OK;
+}
+
+int64_t dcrx_format_cdr3_matches(uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx, const uint32_t *j_idx,
+                                 uint32_t n_v, const char *v_calls, const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
+                                 const uint32_t *j_call_off, const uint64_t *q_off, const char *q_text, const uint64_t *weight, uint64_t m_t,
+                                 const uint64_t *t_off, const char *t_text, const char *db_header, uint64_t db_header_bytes,
+                                 const uint64_t *db_line_off, const char *db_lines, uint32_t metric, char *out, uint64_t out_cap) try {
+  static const char header[] = "clonotype\tv_call\tj_call\tjunction_aa\tduplicate_count\ttarget\tdistance\t";
+  if (!metric_exists(metric))
+    return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
+  if ((db_header_bytes && !db_header) ||
+      (m_q && (!hit_off || !v_idx || !j_idx || !v_calls || !v_call_off || !j_calls || !j_call_off || !q_off || !weight)) ||
+      (m_q && hit_off[m_q] && (!hit || !t_off || !db_line_off || !q_text || !t_text || !db_lines)))
+    return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: null argument");
+  dcrx::TextOut T{out, out_cap};
+  T.put(header, sizeof header - 1);
+  T.put(db_header, db_header_bytes);
+  T.put("\n", 1);
+  for (uint64_t i = 0; i < m_q; i++) {
+    if (hit_off[i + 1] < hit_off[i]) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: hit offsets go backwards");
+    if (hit_off[i + 1] == hit_off[i]) continue;
+    const uint32_t vi = v_idx[i], ji = j_idx[i];
+    if (vi >= n_v || ji >= n_j) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: a gene outside its table");
+    if (q_off[i + 1] < q_off[i]) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: offsets go backwards");
+    const uint64_t lq = q_off[i + 1] - q_off[i];
+    for (uint64_t k = hit_off[i]; k < hit_off[i + 1]; k++) {
+      const uint64_t j = hit[k];
+      if (j >= m_t) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: a hit outside the targets");
+      if (t_off[j + 1] < t_off[j] || db_line_off[j + 1] < db_line_off[j])
+        return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: offsets go backwards");
+      const uint64_t lt = t_off[j + 1] - t_off[j];
+      unsigned long long d = 0;
+      if (metric == METRIC_LEVENSHTEIN) {
+        d = host_levenshtein(q_text + q_off[i], lq, t_text + t_off[j], lt);
+      } else {
+        if (lq != lt) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: a hit between strings of two lengths");
+        for (uint64_t p = 0; p < lq; p++) d += q_text[q_off[i] + p] != t_text[t_off[j] + p];
+      }
+      T.unum(i); T.put("\t", 1);
+      T.put_span(v_calls, v_call_off, vi); T.put("\t", 1);
+      T.put_span(j_calls, j_call_off, ji); T.put("\t", 1);
+      T.put_span(q_text, q_off, i); T.put("\t", 1);
+      T.unum(weight[i]); T.put("\t", 1);
+      T.unum(j); T.put("\t", 1);
+      T.unum(d); T.put("\t", 1);
+      T.put_span(db_lines, db_line_off, j); T.put("\n", 1);
+    }
+  }
+  return (int64_t)T.at;
+} catch (const std::exception &e) {      // (host_levenshtein's rows)
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+}  // extern "C"

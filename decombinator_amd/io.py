@@ -13,6 +13,7 @@ from __future__ import annotations
 import argparse
 import gzip
 import os
+import sys
 
 from .decombine import __version__, sort_permissions
 
@@ -179,6 +180,36 @@ def _overlap(p: argparse.ArgumentParser):
                         "clonotype, D50, Chao1, Simpson, inverse Simpson, Gini, Shannon entropy and clonality")
 
 
+def _match(p: argparse.ArgumentParser):
+    p.add_argument("-in", "--infile", type=str, nargs="+", required=True,
+                   help="1 to 64 .clonotypes.tsv files (plain or .gz), one per sample; a sample is named by its file name "
+                        "without .clonotypes.tsv[.gz]")
+    p.add_argument("-db", "--database", type=str, required=True,
+                   help="The database: a tab-separated table (plain or .gz) with a header line, its columns found by name; a "
+                        ".clonotypes.tsv is one as it stands")
+    p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
+    p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
+    p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
+    p.add_argument("--cdr3-distance", dest="cdr3_distance", type=int, default=1,
+                   help="Residues in which a clonotype's CDR3 and a database entry's may differ: 0, 1 (default) or 2.  The default "
+                        "is a design choice, not a measured optimum")
+    p.add_argument("--cdr3-metric", dest="cdr3_metric", choices=["hamming", "levenshtein"], default="hamming",
+                   help="How those residues are counted: hamming (default; substitutions between CDR3s of one length) or "
+                        "levenshtein (substitutions, insertions and deletions)")
+    p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default="v",
+                   help="What a clonotype and a database entry must share beside the CDR3: nothing (none), the V call (v, the "
+                        "default) or the V and the J call (vj).  The default is the network's: a design choice, not a measured "
+                        "optimum")
+    p.add_argument("--strip-alleles", dest="strip_alleles", action="store_true",
+                   help="Compare a call up to its first * on both sides (TRBV7-9*01 and TRBV7-9*03 are then one V)")
+    p.add_argument("--db-cdr3-column", dest="db_cdr3_column", type=str, default="junction_aa",
+                   help="The database column that holds the CDR3 amino acids (default junction_aa; a VDJdb export: CDR3)")
+    p.add_argument("--db-v-column", dest="db_v_column", type=str, default="v_call",
+                   help="The database column that holds the V call (default v_call; a VDJdb export: V); read when the class needs it")
+    p.add_argument("--db-j-column", dest="db_j_column", type=str, default="j_call",
+                   help="The database column that holds the J call (default j_call; a VDJdb export: J); read when the class needs it")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -186,6 +217,8 @@ def create_parser() -> argparse.ArgumentParser:
                     "Sub-commands as in the reference; the grouping / clustering half of `collapse` (UMI clustering, the "
                     ".freq) runs with --cluster.")
     parser.add_argument("-v", "--version", action="version", version=__version__)
+    parser.epilog = ("A further command has a parser of its own: `match` (clonotypes near a database's CDR3s, GPU); see "
+                     "`python -m decombinator_amd match --help`.")
     sub = parser.add_subparsers(dest="command", help="Available commands")
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
@@ -213,7 +246,22 @@ def create_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def create_match_parser() -> argparse.ArgumentParser:
+    """The parser of `match`, a sub-command with a parser of its own: cli_args hands it what follows the word `match` (the
+    list of create_parser()'s sub-commands stays what it was; its epilog names this one)."""
+    parser = argparse.ArgumentParser(
+        prog="python -m decombinator_amd match",
+        description="Near matches between samples and a database (GPU): which clonotypes of .clonotypes.tsv files are the same "
+                    "as, or one or two CDR3 residues from, an entry of a second table (a list of CDR3s of known specificity, or "
+                    "another sample's .clonotypes.tsv); writes <sample>.cdr3_matches.tsv per sample and match_targets.tsv.")
+    _match(parser)
+    return parser
+
+
 def cli_args(argv=None) -> dict:
+    words = sys.argv[1:] if argv is None else list(argv)
+    if words and words[0] == "match":
+        return dict(vars(create_match_parser().parse_args(words[1:])), command="match")
     inp = vars(create_parser().parse_args(argv))
     if "merge_errors" in inp:
         # which of the merge options the command line named (they are refused without --merge-errors), then the defaults
@@ -360,14 +408,14 @@ def _write_beside_tsv(text: bytes, suffix: str, what: str, inputargs: dict):
     return outfilename
 
 
-def write_out_overlap(text: bytes, name: str, inputargs: dict):
+def write_out_overlap(text: bytes, name: str, inputargs: dict, what: str = "overlap"):
     """A file of the `overlap` sub-command: `<outpath><prefix><name>` (overlap_pairs.tsv, overlap_public.tsv,
     overlap_diversity.tsv), with
     write_out_clonotypes' rules: gzipped unless dontgzip, mode 666.  Returns the file's name."""
     outfilename = (inputargs.get("outpath") or "") + (inputargs.get("prefix") or "") + name
     if not inputargs.get("dontgzip"):
         from . import _native as nat
-        print("Compressing overlap output file to", outfilename + ".gz")
+        print(f"Compressing {what} output file to", outfilename + ".gz")
         with nat.GzipWriter(outfilename + ".gz", level=int(os.environ.get("DCRX_GZIP_LEVEL", "6"))) as gz:
             gz.write(text)
         outfilename += ".gz"
@@ -376,6 +424,12 @@ def write_out_overlap(text: bytes, name: str, inputargs: dict):
             fh.write(text)
     sort_permissions(outfilename)
     return outfilename
+
+
+def write_out_match(text: bytes, name: str, inputargs: dict):
+    """A file of the `match` sub-command: `<outpath><prefix><name>` (<sample>.cdr3_matches.tsv, match_targets.tsv), with
+    write_out_overlap's rules.  Returns the file's name."""
+    return write_out_overlap(text, name, inputargs, what="match")
 
 
 def write_out_cdr3_clusters(network, inputargs: dict):

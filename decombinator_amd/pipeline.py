@@ -170,6 +170,14 @@ def main(argv=None):
             from .io import create_parser
             create_parser().error(str(e))
         return
+    if inp["command"] == "match":       # ... and so is this one: clonotype tables against a database
+        from . import match
+        try:
+            match.run(inp)
+        except ValueError as e:
+            from .io import create_match_parser
+            create_match_parser().error(str(e))
+        return
     if inp.get("clonotypes"):           # refused before anything is read
         why = clonotype_refusal(inp)
         if why:

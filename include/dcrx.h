@@ -1094,6 +1094,116 @@ int64_t dcrx_abundance_classes(uint32_t n_samples, uint64_t n, const uint32_t *s
                                const uint64_t *weight, uint64_t *class_off_out, uint32_t *class_count_out,
                                uint64_t *class_mult_out);
 
+/* ---- match (`match`): which nodes of one table (the QUERIES: a sample's clonotypes) are the same as, or one or two residues
+ * from, a node of a second table (the TARGETS: a database of CDR3s of known specificity, or another sample), on the GPU.  The
+ * reference has no counterpart: the contract below is this library's own.  The entries only ADD to ABI 5 ----
+ *
+ * This layer knows nothing about genes or files, as the CDR3 network's.
+ * Input: m_t targets — target j has rank j — with, per target, a class c_j (uint32) and a string s_j (bytes, given as
+ *   m_t + 1 offsets into one text); m_q queries — query i has rank i — with a class, a string and a weight w_i (uint64);
+ *   a distance D, 0, 1 or 2; a metric, DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN.  m_q, m_t < 2^30
+ *   (DCRX_E_UNSUPPORTED beyond).  The sum of the query weights is below 2^64 (DCRX_E_UNSUPPORTED otherwise, decided on the
+ *   host before any device call: no t_weight can wrap).
+ * In reach: the network's rule, 1 <= len <= DCRX_CDR3NET_MAX_LEN (32), on either side.  A node out of reach takes part in
+ *   no hit, and is counted.
+ * Hit: (i, j) where query i and target j are both in reach, c_i == c_j, and the network's edge rule holds between the two
+ *   strings: under DCRX_CDR3NET_HAMMING equal lengths and at most D differing bytes; under DCRX_CDR3NET_LEVENSHTEIN lengths
+ *   at most D apart and a Levenshtein distance (substitution, insertion, deletion cost 1 each) of at most D.  Bytes are
+ *   compared as they are; a real 0x00 byte is a symbol like any other and never matches the padding behind a shorter
+ *   string.  D = 0 is byte equality under either metric.  A query and a target of the same bytes are a hit: the two sides
+ *   are different sets, there is no "i != j".
+ * Output: degree[i] = the hits of query i; the hits in CSR form, hit_off[m_q + 1] (uint64) and hit[] with every query's
+ *   targets' ranks ascending; per target t_queries[j] = the queries that hit it (uint32) and t_weight[j] = the sum of their
+ *   weights (uint64).  Statistics: dcrx_cdr3_match_stats_t, which holds nothing of the algorithm.
+ * Everything is a function of the input alone (integer adds, and atomics whose results are not read).
+ * D above 2, a metric that does not exist and offsets that go backwards are DCRX_E_INVALID. */
+typedef struct dcrx_cdr3_index dcrx_cdr3_index_t;
+typedef struct dcrx_cdr3_match dcrx_cdr3_match_t;
+typedef struct dcrx_cdr3_match_stats {
+  uint64_t queries;
+  uint64_t targets;
+  uint64_t queries_out_of_reach;
+  uint64_t targets_out_of_reach;
+  uint64_t hits;                  /* (query, target) pairs */
+  uint64_t queries_hit;           /* queries with a hit ... */
+  uint64_t queries_hit_weight;    /* ... and the sum of their weights */
+  uint64_t targets_hit;           /* targets with a hit */
+  uint64_t largest_degree;
+} dcrx_cdr3_match_stats_t;
+
+/* The targets, built on the current device ONCE and kept there for any number of dcrx_cdr3_match_run / _device calls (host
+ * arrays; synchronous).  The index holds the targets in both bucket orders — by (class, length) for the Hamming walk and by
+ * class alone for the Levenshtein walk, each a stable radix sort of (key, rank), so a bucket stays in rank order —: per
+ * order the sorted keys, the ranks and the packed strings (32 bytes each), and for the class order the letter-presence
+ * masks, which are always built: one index serves both metrics and every D, at 92 bytes per target.  m_t == 0 is a valid
+ * index (and touches no device).  DCRX_E_UNSUPPORTED for m_t >= 2^30, DCRX_E_INVALID for offsets that go backwards or a
+ * null argument, DCRX_E_NOMEM as elsewhere. */
+int dcrx_cdr3_index_create(uint64_t m_t, const uint32_t *cls, const uint64_t *off, const char *text,
+                           dcrx_cdr3_index_t **index_out);
+void dcrx_cdr3_index_destroy(dcrx_cdr3_index_t *index);
+/* The targets, how many of them are out of reach, and the index's bytes of device memory; any pointer may be NULL. */
+int dcrx_cdr3_index_info(const dcrx_cdr3_index_t *index, uint64_t *targets, uint64_t *out_of_reach, uint64_t *device_bytes);
+
+/* Bytes of device work space dcrx_cdr3_match_device needs for m_q queries whose strings take text_bytes bytes under `metric`
+ * (it does not depend on the index); 0 for m_q >= 2^30 and for a metric that does not exist. */
+uint64_t dcrx_cdr3_match_work_bytes(uint64_t m_q, uint64_t text_bytes, uint32_t metric);
+
+/* The primitive: degree and hits of every query against an index, asynchronously on `hip_stream`, the queries' arrays in
+ * device memory of the device the index was built on, and `hip_stream` a stream of that device: the call makes that device
+ * current for its launches and puts the caller's back before it returns (as dcrx_cdr3_match_run does).  d_class: m_q classes; d_off: m_q + 1 offsets into d_text (text_bytes
+ * bytes; a query whose offsets go backwards or leave the text is out of reach).  Writes d_degree (m_q) and d_hit_off
+ * (m_q + 1: the exclusive sum of the degrees in rank order).  *d_hit_need (device, uint64) always receives the entries the
+ * hits take (= d_hit_off[m_q]); d_hit (hit_cap entries) is written when the need fits hit_cap and is never written past
+ * otherwise (an entry beyond hit_cap is dropped), so a caller that finds *d_hit_need > hit_cap calls again with a larger one
+ * (d_hit may be NULL with hit_cap 0 to size it).
+ * The steps: the queries are prepared as the network prepares its nodes (keys, a stable radix sort of (key, rank), the
+ * packed strings gathered in sorted order, presence masks under Levenshtein); then cdr3match_walk_kernel: a block holds 256
+ * sorted queries in registers, finds the first target at or above its first query's bucket by a binary search over the
+ * index's sorted keys, and stages the targets from there in LDS tiles of 256 until the staged bucket passes its last query's
+ * bucket; a wave skips a tile that holds none of its buckets; the targets of a bucket are in rank order, so a query's hits
+ * come out ascending with no atomics.  The pair test is the network's (csrc/dcrx_cdr3net_core.h).  A degree pass, an
+ * exclusive sum, and a write pass that repeats the walk.  Under DCRX_CDR3NET_LEVENSHTEIN with D = 0 the Hamming walk runs.
+ * d_work: dcrx_cdr3_match_work_bytes(m_q, text_bytes, metric) bytes, 256-byte aligned; a smaller one is DCRX_E_INVALID, not
+ * a launch.  m_q == 0, and an index of 0 targets, launch no kernel (the outputs are zeroed on the stream). */
+int dcrx_cdr3_match_device(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off,
+                           const char *d_text, uint64_t text_bytes, uint32_t distance, uint32_t metric, uint32_t *d_degree,
+                           uint64_t *d_hit_off, uint32_t *d_hit, uint64_t hit_cap, uint64_t *d_hit_need, void *d_work,
+                           uint64_t work_bytes, void *hip_stream);
+
+/* The whole step on host arrays, synchronous on the current device, run ONCE whatever is exported afterwards: checks the
+ * arguments (all of the contract's refusals, before any device call), uploads the queries, runs the primitive's degree half,
+ * allocates exactly the hits it sized (DCRX_E_NOMEM when it cannot) and fills them, then cdr3match_totals_kernel — a lane
+ * per query over its CSR row — adds every hit onto its target's t_queries and t_weight by atomics whose results are not
+ * read.  *match_out: the result, to be released with dcrx_cdr3_match_destroy (NULL on an error).  m_q == 0, and an index of
+ * 0 targets, are answered without a launch. */
+int dcrx_cdr3_match_run(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *cls, const uint64_t *off,
+                        const char *text, const uint64_t *weight, uint32_t distance, uint32_t metric,
+                        dcrx_cdr3_match_t **match_out);
+void dcrx_cdr3_match_destroy(dcrx_cdr3_match_t *match);
+/* Sizes (queries, targets, hits) and statistics; any pointer may be NULL. */
+int dcrx_cdr3_match_info(const dcrx_cdr3_match_t *match, uint64_t *queries, uint64_t *targets, uint64_t *hits,
+                         dcrx_cdr3_match_stats_t *stats);
+/* Into the caller's arrays, any of which may be NULL: degree (queries), hit_off (queries + 1), hit (hits), t_queries and
+ * t_weight (targets each). */
+int dcrx_cdr3_match_export(const dcrx_cdr3_match_t *match, uint32_t *degree, uint64_t *hit_off, uint32_t *hit,
+                           uint32_t *t_queries, uint64_t *t_weight);
+
+/* The `.cdr3_matches.tsv` text of a CSR of hits in one pass: the header "clonotype v_call j_call junction_aa duplicate_count
+ * target distance" followed by a tab and db_header (db_header_bytes bytes: the database's column names, as the caller
+ * wants them shown), then one line per hit ordered by (query, target): the query's rank, the calls of v_idx[i] / j_idx[i]
+ * (calls: one text, n + 1 offsets), its string and weight, the target's rank, the distance of the two strings under `metric`,
+ * computed here on the host (as dcrx_format_cdr3_edges_metric computes it), a tab and the target's line db_lines[db_line_off[j]
+ * .. db_line_off[j + 1]) verbatim.  Returns the bytes the text takes; writes it when out != NULL and it fits out_cap.
+ * DCRX_E_INVALID for a hit outside the targets, offsets that go backwards, a gene outside its table, a metric that does
+ * not exist or, under DCRX_CDR3NET_HAMMING, a hit between strings of two lengths.  Host only. */
+int64_t dcrx_format_cdr3_matches(uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx,
+                                 const uint32_t *j_idx, uint32_t n_v, const char *v_calls, const uint32_t *v_call_off,
+                                 uint32_t n_j, const char *j_calls, const uint32_t *j_call_off, const uint64_t *q_off,
+                                 const char *q_text, const uint64_t *weight, uint64_t m_t, const uint64_t *t_off,
+                                 const char *t_text, const char *db_header, uint64_t db_header_bytes,
+                                 const uint64_t *db_line_off, const char *db_lines, uint32_t metric, char *out,
+                                 uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
