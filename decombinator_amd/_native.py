@@ -419,10 +419,25 @@ CDR3_MATCH_STATS = ("queries", "targets", "queries_out_of_reach", "targets_out_o
                     "targets_hit", "largest_degree")
 CDR3_MATCH_MAX_SAMPLES = 64         # files of one `match` call
 CDR3_MATCH_COLUMNS = ["clonotype", "v_call", "j_call", "junction_aa", "duplicate_count", "target", "distance"]      # then db_<column> ...
+CDR3_METRIC_WEIGHTED = 2            # DCRX_CDR3NET_WEIGHTED: the weighted entries' own (the *_metric entries refuse it)
+CDR3_COST_MAX_GAP, CDR3_COST_MAX_TRIM, CDR3_MAX_RADIUS = 255, 16, 65535
+AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"
+# The default substitution costs, after TCRdist: 3 * min(4, 4 - BLOSUM62) off the diagonal, which is 12 for every pair of
+# letters but the pairs BLOSUM62 scores above zero, spelt out here by score (B, J, O, U, X and Z cost 12 against everything).
+CDR3_COST_FAR = 12
+CDR3_COST_NEAR = {
+    9: ("AS", "RQ", "ND", "NH", "NS", "QK", "EK", "IM", "LV", "MV", "FW", "ST"),      # BLOSUM62 score 1
+    6: ("RK", "DE", "QE", "HY", "IL", "LM", "WY"),                                    # score 2
+    3: ("IV", "FY"),                                                                  # score 3
+}
 
 
 class Cdr3MatchStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CDR3_MATCH_STATS]
+
+
+class Cdr3CostC(C.Structure):      # dcrx_cdr3_cost_t
+    _fields_ = [("sub", (C.c_uint8 * 32) * 32), ("gap", C.c_uint32), ("ntrim", C.c_uint32), ("ctrim", C.c_uint32)]
 
 
 OVERLAP_MAX_SAMPLES = 64       # DCRX_OVERLAP_MAX_SAMPLES
@@ -483,6 +498,8 @@ EXPORTS = [
     "dcrx_downsample_work_bytes", "dcrx_downsample_device", "dcrx_downsample", "dcrx_abundance_classes",
     "dcrx_cdr3_index_create", "dcrx_cdr3_index_destroy", "dcrx_cdr3_index_info", "dcrx_cdr3_match_work_bytes", "dcrx_cdr3_match_device",
     "dcrx_cdr3_match_run", "dcrx_cdr3_match_destroy", "dcrx_cdr3_match_info", "dcrx_cdr3_match_export", "dcrx_format_cdr3_matches",
+    "dcrx_cdr3_match_weighted_work_bytes", "dcrx_cdr3_match_weighted_device", "dcrx_cdr3_match_weighted_run", "dcrx_cdr3_match_export_dist",
+    "dcrx_format_cdr3_matches_weighted",
 ]
 
 _lib = None
@@ -648,6 +665,12 @@ def lib():
         "dcrx_cdr3_match_export": (i32, [vp, vp, vp, vp, vp, vp]),
         "dcrx_format_cdr3_matches": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp,
                                                  u32, vp, u64]),
+        "dcrx_cdr3_match_weighted_work_bytes": (u64, [u64, u64]),
+        "dcrx_cdr3_match_weighted_device": (i32, [vp, u64, vp, vp, vp, u64, vp, u32, vp, vp, vp, vp, u64, vp, vp, u64, vp]),
+        "dcrx_cdr3_match_weighted_run": (i32, [vp, u64, vp, vp, vp, vp, vp, u32, C.POINTER(vp)]),
+        "dcrx_cdr3_match_export_dist": (i32, [vp, vp]),
+        "dcrx_format_cdr3_matches_weighted": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp,
+                                                          vp, vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1558,6 +1581,11 @@ def cdr3_match(index: Cdr3Index, classes, off, text: bytes, weights, distance: i
     h = C.c_void_p()
     check(lib().dcrx_cdr3_match_run(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data, int(distance),
                                     cdr3_metric_code(metric), C.byref(h)))
+    return _cdr3_match_take(h, m, False)
+
+
+def _cdr3_match_take(h, m: int, with_dist: bool) -> dict:
+    """Everything a dcrx_cdr3_match_t exports, as cdr3_match returns it (with_dist: and "hit_dist"); releases the handle."""
     try:
         n_t, n_hits, st = C.c_uint64(0), C.c_uint64(0), Cdr3MatchStatsC()
         check(lib().dcrx_cdr3_match_info(h, None, C.byref(n_t), C.byref(n_hits), C.byref(st)))
@@ -1565,16 +1593,153 @@ def cdr3_match(index: Cdr3Index, classes, off, text: bytes, weights, distance: i
         degree, hit, tq = np.zeros(max(m, 1), np.uint32), np.zeros(max(H, 1), np.uint32), np.zeros(max(T, 1), np.uint32)
         hit_off, tw = np.zeros(m + 1, np.uint64), np.zeros(max(T, 1), np.uint64)
         check(lib().dcrx_cdr3_match_export(h, degree.ctypes.data, hit_off.ctypes.data, hit.ctypes.data, tq.ctypes.data, tw.ctypes.data))
+        dist = np.zeros(max(H, 1), np.uint32)
+        if with_dist:
+            check(lib().dcrx_cdr3_match_export_dist(h, dist.ctypes.data))
     finally:
         lib().dcrx_cdr3_match_destroy(h)
-    return {"degree": degree[:m], "hit_off": hit_off, "hit": hit[:H], "t_queries": tq[:T], "t_weight": tw[:T],
-            "stats": {k: int(getattr(st, k)) for k in CDR3_MATCH_STATS}}
+    out = {"degree": degree[:m], "hit_off": hit_off, "hit": hit[:H], "t_queries": tq[:T], "t_weight": tw[:T],
+           "stats": {k: int(getattr(st, k)) for k in CDR3_MATCH_STATS}}
+    if with_dist:
+        out["hit_dist"] = dist[:H]
+    return out
+
+
+class Cdr3Cost:
+    """dcrx_cdr3_cost_t: the weighted metric's cost — sub, a 32 x 32 uint8 table indexed by (byte & 31) of the two letters
+    (symmetric, zero on the diagonal), gap (1 .. 255) and the trims (0 .. 16 each).  The constructor checks nothing: the
+    library refuses what the contract refuses."""
+
+    def __init__(self, sub, gap: int = 12, ntrim: int = 3, ctrim: int = 2):
+        self.sub = np.ascontiguousarray(sub, dtype=np.uint8).reshape(32, 32).copy()
+        self.gap, self.ntrim, self.ctrim = int(gap), int(ntrim), int(ctrim)
+
+    @staticmethod
+    def default_table() -> np.ndarray:
+        """CDR3_COST_FAR between any two letters of A .. Z, CDR3_COST_NEAR's pairs below it, zero on the diagonal."""
+        sub = np.zeros((32, 32), dtype=np.uint8)
+        sub[1:27, 1:27] = CDR3_COST_FAR
+        for cost, pairs in CDR3_COST_NEAR.items():
+            for x, y in pairs:
+                sub[ord(x) & 31, ord(y) & 31] = sub[ord(y) & 31, ord(x) & 31] = cost
+        sub[np.arange(32), np.arange(32)] = 0
+        return sub
+
+    @classmethod
+    def default(cls, gap: int = 12, ntrim: int = 3, ctrim: int = 2) -> "Cdr3Cost":
+        return cls(cls.default_table(), gap, ntrim, ctrim)
+
+    @classmethod
+    def from_file(cls, path, gap: int = 12, ntrim: int = 3, ctrim: int = 2) -> "Cdr3Cost":
+        """A tab-separated square table: the first row and the first column are single letters of A .. Z (the same letters in
+        the same order; the corner cell is ignored), the cells integers 0 .. 255.  It covers the twenty amino acids, is
+        symmetric and zero on its diagonal; a letter of A .. Z it lacks costs the file's largest cell against every other
+        letter.  ValueError by line number for anything else."""
+        with open(path, "rb") as fh:
+            lines = fh.read().split(b"\n")
+        if lines and lines[-1] == b"":
+            lines.pop()
+        lines = [x[:-1] if x.endswith(b"\r") else x for x in lines]
+        if not lines:
+            raise ValueError(f"{path}, line 1: no header row")
+
+        def letter(cell: bytes, n: int) -> int:
+            if len(cell) != 1 or not b"A" <= cell <= b"Z":
+                raise ValueError(f"{path}, line {n}: {cell.decode('latin-1')!r} is not a single letter A..Z")
+            return cell[0] & 31
+        cols = [letter(c, 1) for c in lines[0].split(b"\t")[1:]]
+        if len(set(cols)) != len(cols):
+            raise ValueError(f"{path}, line 1: a letter stands twice")
+        missing = sorted(set(AMINO_ACIDS) - {chr(64 + c) for c in cols})
+        if missing:
+            raise ValueError(f"{path}, line 1: no column for {', '.join(missing)}")
+        if len(lines) - 1 != len(cols):
+            raise ValueError(f"{path}, line {len(lines)}: {len(lines) - 1} rows under {len(cols)} columns")
+        cells = np.zeros((len(cols), len(cols)), dtype=np.int64)
+        for r, line in enumerate(lines[1:]):
+            n = r + 2
+            f = line.split(b"\t")
+            if len(f) != len(cols) + 1:
+                raise ValueError(f"{path}, line {n}: {len(f)} fields, not {len(cols) + 1}")
+            if letter(f[0], n) != cols[r]:
+                raise ValueError(f"{path}, line {n}: row {f[0].decode('latin-1')} where the header has {chr(64 + cols[r])}")
+            for k, cell in enumerate(f[1:]):
+                if not cell.isdigit() or int(cell) > 255:
+                    raise ValueError(f"{path}, line {n}: {cell.decode('latin-1')!r} is not an integer 0..255")
+                cells[r, k] = int(cell)
+        for r in range(len(cols)):
+            if cells[r, r]:
+                raise ValueError(f"{path}, line {r + 2}: the diagonal cell is {cells[r, r]}, not 0")
+            for k in range(r):
+                if cells[r, k] != cells[k, r]:
+                    raise ValueError(f"{path}, line {r + 2}: {chr(64 + cols[r])}-{chr(64 + cols[k])} is {cells[r, k]} "
+                                     f"but {chr(64 + cols[k])}-{chr(64 + cols[r])} is {cells[k, r]}")
+        sub = np.zeros((32, 32), dtype=np.uint8)
+        sub[1:27, 1:27] = cells.max()
+        sub[np.ix_(cols, cols)] = cells
+        sub[np.arange(32), np.arange(32)] = 0
+        return cls(sub, gap, ntrim, ctrim)
+
+    def as_c(self) -> Cdr3CostC:
+        c = Cdr3CostC()
+        C.memmove(c.sub, self.sub.ctypes.data, 1024)
+        c.gap, c.ntrim, c.ctrim = (v & 0xFFFFFFFF for v in (self.gap, self.ntrim, self.ctrim))
+        return c
+
+
+def cdr3_match_weighted_work_bytes(m_q: int, text_bytes: int) -> int:
+    """dcrx_cdr3_match_weighted_work_bytes."""
+    return int(lib().dcrx_cdr3_match_weighted_work_bytes(int(m_q), int(text_bytes)))
+
+
+def _radius(radius) -> int:
+    if not 0 <= int(radius) < 1 << 32:
+        raise ValueError(f"the radius is 0 .. {CDR3_MAX_RADIUS}, not {radius}")
+    return int(radius)
+
+
+def cdr3_match_weighted_device(index: Cdr3Index, m_q: int, d_class, d_off, d_text, text_bytes: int, cost: Cdr3Cost, radius: int, d_degree,
+                               d_hit_off, d_hit, d_hit_dist, hit_cap: int, d_hit_need, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_match_weighted_device: cdr3_match_device under the weighted metric; d_hit_dist (may be None) receives the
+    hits' distances."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    c = cost.as_c() if cost is not None else None      # (alive across the call, which copies it)
+    check(lib().dcrx_cdr3_match_weighted_device(index.handle, int(m_q), ptr(d_class), ptr(d_off), ptr(d_text), int(text_bytes),
+                                                C.addressof(c) if c is not None else None, _radius(radius), ptr(d_degree),
+                                                ptr(d_hit_off), ptr(d_hit), ptr(d_hit_dist), int(hit_cap), ptr(d_hit_need), ptr(d_work),
+                                                int(work_bytes), stream))
+
+
+def cdr3_match_weighted(index: Cdr3Index, classes, off, text: bytes, weights, cost: Cdr3Cost, radius: int) -> dict:
+    """dcrx_cdr3_match_weighted_run: cdr3_match under the weighted metric — a hit is a query and a target of one class, both of
+    1 .. 32 letters A .. Z, whose weighted distance under `cost` is at most `radius` -> cdr3_match's dict and "hit_dist", the
+    distance of every hit as the device computed it."""
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    o, t = _node_arrays(off, text)
+    m = len(cls)
+    if len(o) != m + 1 or len(w) != m:
+        raise ValueError("cdr3_match_weighted: one class and one weight per query, m + 1 offsets")
+    h = C.c_void_p()
+    c = cost.as_c() if cost is not None else None
+    check(lib().dcrx_cdr3_match_weighted_run(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data,
+                                             C.addressof(c) if c is not None else None, _radius(radius), C.byref(h)))
+    return _cdr3_match_take(h, m, True)
+
+
+def format_cdr3_matches_weighted(result: dict, v_idx, j_idx, v_calls, j_calls, off, text: bytes, weights, t_off, t_text: bytes,
+                                 db_header: bytes, db_lines, cost: Cdr3Cost) -> bytes:
+    """dcrx_format_cdr3_matches_weighted: format_cdr3_matches with the weighted distance, computed on the host, in the distance
+    column."""
+    return format_cdr3_matches(result, v_idx, j_idx, v_calls, j_calls, off, text, weights, t_off, t_text, db_header, db_lines, cost)
 
 
 def format_cdr3_matches(result: dict, v_idx, j_idx, v_calls, j_calls, off, text: bytes, weights, t_off, t_text: bytes, db_header: bytes,
                         db_lines, metric="hamming") -> bytes:
     """dcrx_format_cdr3_matches: the `.cdr3_matches.tsv` text of a cdr3_match result — per hit the query's rank, calls, string
-    and weight, the target's rank, the distance, and the target's database line db_lines[j] (bytes) under db_header."""
+    and weight, the target's rank, the distance, and the target's database line db_lines[j] (bytes) under db_header.  (metric a
+    Cdr3Cost: dcrx_format_cdr3_matches_weighted.)"""
     vi, ji = (np.ascontiguousarray(a, dtype=np.uint32) if len(a) else np.zeros(1, np.uint32) for a in (v_idx, j_idx))
     w = np.ascontiguousarray(weights, dtype=np.uint64) if len(weights) else np.zeros(1, np.uint64)
     (o, t), (to, tt) = _node_arrays(off, text), _node_arrays(t_off, t_text)
@@ -1588,10 +1753,15 @@ def format_cdr3_matches(result: dict, v_idx, j_idx, v_calls, j_calls, off, text:
     hit = np.ascontiguousarray(result["hit"], dtype=np.uint32) if len(result["hit"]) else np.zeros(1, np.uint32)
     args = [len(o) - 1, hit_off.ctypes.data, hit.ctypes.data, vi.ctypes.data, ji.ctypes.data, len(v_calls), vc.ctypes.data, vo.ctypes.data,
             len(j_calls), jc.ctypes.data, jo.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data, len(to) - 1, to.ctypes.data,
-            tt.ctypes.data, hdr.ctypes.data, len(db_header), lo.ctypes.data, lt.ctypes.data, cdr3_metric_code(metric)]
-    need = check(int(lib().dcrx_format_cdr3_matches(*args, None, 0)))
+            tt.ctypes.data, hdr.ctypes.data, len(db_header), lo.ctypes.data, lt.ctypes.data]
+    if isinstance(metric, Cdr3Cost):
+        c = metric.as_c()
+        fmt, args = lib().dcrx_format_cdr3_matches_weighted, args + [C.addressof(c)]
+    else:
+        fmt, args = lib().dcrx_format_cdr3_matches, args + [cdr3_metric_code(metric)]
+    need = check(int(fmt(*args, None, 0)))
     out = _uninitialised_bytes(max(1, need))
-    check(int(lib().dcrx_format_cdr3_matches(*args, _bytes_address(out), need)))
+    check(int(fmt(*args, _bytes_address(out), need)))
     return bytes(out[:need])
 
 

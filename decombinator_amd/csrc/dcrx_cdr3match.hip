@@ -17,6 +17,9 @@
 //   write    cdr3match_walk_kernel<true>: the same walk writes every hit's rank at its exact offset
 // The host entry (dcrx_cdr3_match_run) runs those two halves around the hits' allocation, then the totals: a lane per query
 // adds its row's hits onto the targets (integer atomics, results unused).
+// The weighted metric (dcrx_cdr3_match_weighted_*; include/dcrx.h "match, weighted"): cdr3match_wwalk_kernel is the
+// Levenshtein walk over the same class-order arrays with weighted_within (dcrx_cdr3w_core.h) as its pair test; it lives in
+// this file because the index, the work space, the handle and the two halves around the walk are this file's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,11 +29,13 @@
 
 #include "../../include/dcrx.h"
 #include "dcrx_cdr3match_core.h"
+#include "dcrx_cdr3w_core.h"
 #include "dcrx_group.h"
 #include "dcrx_text.h"
 
 using dcrx::set_err;
 using namespace dcrx_cdr3match;
+using namespace dcrx_cdr3w;
 using namespace dcrx_group;
 
 namespace {
@@ -180,6 +185,95 @@ __global__ __launch_bounds__(BLOCK) void cdr3match_walk_kernel(const uint4 *__re
   }
 }
 
+// the cost as the weighted walk's launch argument: the table as the 256 dwords the block's lanes copy into LDS, one each
+struct CostArg {
+  uint32_t sub[SUB_BYTES / 4];
+  uint32_t gap, ntrim, ctrim;
+};
+static_assert(SUB_BYTES / 4 == BLOCK, "a lane stages one dword of the cost table");
+
+// The weighted walk: the Levenshtein walk's blocks, tiles and wave skip (the bucket is the class) with another predicate: the
+// class, the length window |la - lb| * gap <= radius, then weighted_within.  The cost table is staged in LDS once per block.
+// The lane that stages a target tests it for letters and stages a key of length 0 for one that fails, which no lane tests;
+// a query that fails takes part in nothing.  The presence masks are not read.  A pair is tested where it is met: at such
+// radii most pairs of a class pass the window, so there is nothing for a pending / settle scheme to collect.  WRITE true
+// also stores the hit's distance (hit_dist may be null).
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK) void cdr3match_wwalk_kernel(const uint4 *__restrict__ q_sj, const uint64_t *__restrict__ q_key,
+                                                                const uint32_t *__restrict__ q_idx, uint32_t n_q,
+                                                                const uint4 *__restrict__ t_sj, const uint64_t *__restrict__ t_key,
+                                                                const uint32_t *__restrict__ t_idx, uint32_t n_t, const CostArg cost,
+                                                                uint32_t radius, uint32_t *__restrict__ degree, uint64_t *__restrict__ deg64,
+                                                                const uint64_t *__restrict__ hit_off, uint32_t *__restrict__ hit,
+                                                                uint32_t *__restrict__ hit_dist, uint64_t hit_cap) {
+  __shared__ uint4 lds_j[TILE * 2];
+  __shared__ uint64_t lds_k[TILE];
+  __shared__ uint32_t lds_r[WRITE ? TILE : 1];
+  __shared__ uint32_t lds_sub[SUB_BYTES / 4];
+  lds_sub[threadIdx.x] = cost.sub[threadIdx.x];      // (the walk's first barrier stands before its first read)
+  const Cost C{reinterpret_cast<const uint8_t *>(lds_sub), cost.gap, cost.ntrim, cost.ctrim};
+  const uint32_t s0 = blockIdx.x * BLOCK;
+  const uint32_t s = s0 + threadIdx.x;
+  const bool valid = s < n_q;
+  const uint64_t key_own = valid ? q_key[s] : KEY_OUT_OF_REACH;
+  bool reach = key_own != KEY_OUT_OF_REACH;
+  const uint64_t k_own = key_class(key_own);
+  const uint32_t len_own = key_length(key_own);
+  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t e = 0, count = 0;
+  uint64_t at = 0;
+  if (valid) {
+    e = q_idx[s];
+    if (WRITE) at = hit_off[e];
+    if (reach) {
+      const uint4 a = q_sj[2 * (size_t)s], b = q_sj[2 * (size_t)s + 1];
+      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
+      reach = letters_only(own, len_own);
+    }
+  }
+  const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
+  const Range R = block_range<true>(q_key, n_q, s0, t_key, n_t);      // (the same for every lane of the block)
+  for (uint32_t t = R.first; t < n_t; t += TILE) {
+    if (!goes_on<true>(R, t_key[t])) break;
+    __syncthreads();                                        // the previous tile is no longer read
+    const uint32_t tile_n = min((uint32_t)TILE, n_t - t);
+    if (threadIdx.x < tile_n) {
+      const uint32_t p = t + threadIdx.x;
+      const uint4 a = t_sj[2 * (size_t)p], b = t_sj[2 * (size_t)p + 1];
+      const uint32_t w[WORDS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      const uint64_t key = t_key[p];
+      lds_j[2 * threadIdx.x] = a;
+      lds_j[2 * threadIdx.x + 1] = b;
+      lds_k[threadIdx.x] = letters_only(w, key_length(key)) ? key : key & ~LEN_MASK;      // (the class stays: the tile stays sorted)
+      if (WRITE) lds_r[threadIdx.x] = t_idx[p];
+    }
+    __syncthreads();
+    if (wave_skips(key_class(lds_k[0]), key_class(lds_k[tile_n - 1]), w_lo, w_hi)) continue;
+    const uint8_t *lj = reinterpret_cast<const uint8_t *>(lds_j);
+    for (uint32_t q = 0; q < tile_n; q++) {
+      const uint64_t key_q = lds_k[q], kq = key_class(key_q);
+      if (kq < w_lo) continue;
+      if (kq > w_hi) break;
+      const uint32_t len_q = key_length(key_q);      // (0: a target with a non-letter, or out of reach)
+      const uint32_t apart = len_q > len_own ? len_q - len_own : len_own - len_q;
+      if (reach && kq == k_own && len_q != 0 && apart * C.gap <= radius) {
+        const uint32_t dist = weighted_within(own, len_own, lj + q * (WORDS * 4), len_q, C, radius);
+        if (dist <= radius) {
+          if (WRITE && at + count < hit_cap) {
+            hit[at + count] = lds_r[q];
+            if (hit_dist) hit_dist[at + count] = dist;
+          }
+          count++;
+        }
+      }
+    }
+  }
+  if (valid && !WRITE) {
+    degree[e] = count;
+    deg64[e] = count;
+  }
+}
+
 // hit_off[m] and the need behind the scan
 __global__ void cdr3match_need_kernel(const uint64_t *__restrict__ deg64, uint64_t *__restrict__ hit_off, uint32_t n,
                                       uint64_t *__restrict__ need) {
@@ -267,6 +361,8 @@ struct dcrx_cdr3_match {
   dcrx_cdr3_match_stats_t stats{};
   std::vector<uint32_t> degree, hit, t_queries;
   std::vector<uint64_t> hit_off, t_weight;
+  bool weighted = false;
+  std::vector<uint32_t> hit_dist;      // (a weighted handle's)
 };
 
 namespace {
@@ -303,13 +399,15 @@ int build_index(dcrx_cdr3_index &I, const uint32_t *cls, const uint64_t *off, co
 }
 
 // keys, sort, gather of the queries, the degree pass, the scan and the need
-int run_degrees(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, uint32_t limit, bool lev, uint32_t *d_degree, uint64_t *d_hit_off,
-                uint64_t *d_need, const Work &W, hipStream_t s) {
+// (wc: the weighted walk's cost, and then `limit` is the radius and `lev` is set: the class order, without the presence masks)
+int run_degrees(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, uint32_t limit, bool lev, const CostArg *wc, uint32_t *d_degree,
+                uint64_t *d_hit_off, uint64_t *d_need, const Work &W, hipStream_t s) {
   int rc;
   if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, lev ? (int)LEN_BITS : 0, true, s)) ||
       (rc = gather(N, n, W.idx[1], W.sj, lev ? W.pres : nullptr, s))) return rc;
   const Sorted Q = W.queries(n, lev), T = I.targets(lev);
-  if (lev) cdr3match_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
+  if (wc) cdr3match_wwalk_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.n, T.sj, T.key, T.idx, T.n, *wc, limit, d_degree, W.deg64, nullptr, nullptr, nullptr, 0);
+  else if (lev) cdr3match_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
   else cdr3match_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
   HIP_TRY(hipGetLastError());
   if ((rc = exclusive_sum(W.cub, W.deg64, d_hit_off, n, s))) return rc;
@@ -318,10 +416,11 @@ int run_degrees(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, uint32_t l
   return DCRX_OK;
 }
 
-int run_write(const dcrx_cdr3_index &I, uint64_t n, uint32_t limit, bool lev, const uint64_t *d_hit_off, uint32_t *d_hit, uint64_t hit_cap,
-              const Work &W, hipStream_t s) {
+int run_write(const dcrx_cdr3_index &I, uint64_t n, uint32_t limit, bool lev, const CostArg *wc, const uint64_t *d_hit_off, uint32_t *d_hit,
+              uint32_t *d_hit_dist, uint64_t hit_cap, const Work &W, hipStream_t s) {
   const Sorted Q = W.queries(n, lev), T = I.targets(lev);
-  if (lev) cdr3match_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
+  if (wc) cdr3match_wwalk_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.n, T.sj, T.key, T.idx, T.n, *wc, limit, nullptr, nullptr, d_hit_off, d_hit, d_hit_dist, hit_cap);
+  else if (lev) cdr3match_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
   else cdr3match_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
@@ -338,9 +437,9 @@ int refuse(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, uint32_t d
 }
 
 int run_match(const dcrx_cdr3_index &I, uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
-              uint32_t distance, uint32_t metric, dcrx_cdr3_match &M) {
+              uint32_t distance, uint32_t metric, const CostArg *wc, dcrx_cdr3_match &M) {
   const uint64_t text_bytes = off[m] - off[0], mt = I.m;
-  const bool lev = walks_lev(distance, metric);
+  const bool lev = wc || walks_lev(distance, metric);
   int rc;
   Pool P;
   Work W;
@@ -357,22 +456,24 @@ int run_match(const dcrx_cdr3_index &I, uint64_t m, const uint32_t *cls, const u
   const Nodes N{d_cls, d_off, d_text, text_bytes};
 
   // the degree pass, then exactly the hits it sized
-  if ((rc = run_degrees(I, N, m, distance, lev, d_degree, d_hit_off, d_need, W, nullptr))) return rc;
+  if ((rc = run_degrees(I, N, m, distance, lev, wc, d_degree, d_hit_off, d_need, W, nullptr))) return rc;
   uint64_t need = 0;
   if ((rc = to_host(&need, d_need, 1))) return rc;
-  dcrx::DevBuf<uint32_t> d_hit;
-  if (d_hit.alloc(std::max<uint64_t>(need, 1))) return set_err(DCRX_E_NOMEM, "dcrx_cdr3_match_run: the hits do not fit the device's memory");
+  dcrx::DevBuf<uint32_t> d_hit, d_dist;
+  if (d_hit.alloc(std::max<uint64_t>(need, 1)) || (wc && d_dist.alloc(std::max<uint64_t>(need, 1)))) return set_err(DCRX_E_NOMEM, "dcrx_cdr3_match_run: the hits do not fit the device's memory");
   M.hit.resize(need);
+  if (wc) M.hit_dist.resize(need);
   HIP_TRY(hipMemsetAsync(d_tq, 0, mt * sizeof *d_tq, nullptr));
   HIP_TRY(hipMemsetAsync(d_tw, 0, mt * sizeof *d_tw, nullptr));
   if (need) {
-    if ((rc = run_write(I, m, distance, lev, d_hit_off, d_hit.get(), need, W, nullptr))) return rc;
+    if ((rc = run_write(I, m, distance, lev, wc, d_hit_off, d_hit.get(), wc ? d_dist.get() : nullptr, need, W, nullptr))) return rc;
     cdr3match_totals_kernel<<<grid_for(m), BLOCK>>>(d_hit_off, d_hit.get(), d_weight, (uint32_t)m, d_tq, d_tw);
     HIP_TRY(hipGetLastError());
   }
   if ((rc = to_host(M.degree.data(), d_degree, m)) || (rc = to_host(M.hit_off.data(), d_hit_off, m + 1)) ||
       (rc = to_host(M.hit.data(), d_hit.get(), need)) || (rc = to_host(M.t_queries.data(), d_tq, mt)) ||
       (rc = to_host(M.t_weight.data(), reinterpret_cast<const uint64_t *>(d_tw), mt))) return rc;
+  if (wc && (rc = to_host(M.hit_dist.data(), d_dist.get(), need))) return rc;
   return DCRX_OK;
 }
 
@@ -386,6 +487,147 @@ uint64_t host_levenshtein(const char *a, uint64_t la, const char *b, uint64_t lb
     prev.swap(cur);
   }
   return prev[lb];
+}
+
+// what every weighted entry refuses of (cost, radius), on the host; the cost as the walk's launch argument
+int refuse_cost(const char *who, const dcrx_cdr3_cost_t *cost, uint32_t radius, CostArg *arg) {
+  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  if (!cost) return fail("null cost");
+  if (radius > MAX_RADIUS) return fail("the radius is 0 .. 65535");
+  if (cost->gap < 1 || cost->gap > MAX_GAP) return fail("the gap cost is 1 .. 255");
+  if (cost->ntrim > MAX_TRIM || cost->ctrim > MAX_TRIM) return fail("a trim is 0 .. 16");
+  for (uint32_t x = 1; x <= 26; x++) {
+    if (cost->sub[x][x]) return fail("the substitution table is not zero on its diagonal");
+    for (uint32_t y = 1; y < x; y++)
+      if (cost->sub[x][y] != cost->sub[y][x]) return fail("the substitution table is not symmetric");
+  }
+  if (arg) {
+    static_assert(sizeof cost->sub == sizeof arg->sub, "one table");
+    std::memcpy(arg->sub, cost->sub, sizeof arg->sub);
+    arg->gap = cost->gap; arg->ntrim = cost->ntrim; arg->ctrim = cost->ctrim;
+  }
+  return DCRX_OK;
+}
+
+bool host_letters(const char *a, uint64_t la) {
+  for (uint64_t i = 0; i < la; i++)
+    if (a[i] < 'A' || a[i] > 'Z') return false;
+  return true;
+}
+
+// the weighted distance of two strings of letters (the matches file's column): the contract read out, the literal minimum
+// over every gap position p in 0 .. la of the sum over the counted positions
+uint64_t host_weighted(const char *a, uint64_t la, const char *b, uint64_t lb, const dcrx_cdr3_cost_t &cost) {
+  if (la > lb) { std::swap(a, b); std::swap(la, lb); }
+  const uint64_t d = lb - la;
+  uint64_t best = UINT64_MAX;
+  for (uint64_t p = 0; p <= (d ? la : 0); p++) {
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < la; i++) {
+      if (i < cost.ntrim || i + cost.ctrim >= la) continue;
+      sum += cost.sub[a[i] & 31][b[i < p ? i : i + d] & 31];
+    }
+    best = std::min(best, sum);
+  }
+  return d * cost.gap + best;
+}
+
+// the host entry under any metric, behind the entry's own refusals (wc: the weighted walk's cost, `distance` its radius)
+int run_entry(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *cls, const uint64_t *off, const char *text,
+              const uint64_t *weight, uint32_t distance, uint32_t metric, const CostArg *wc, dcrx_cdr3_match_t **match_out) {
+  auto fail = [&](int code, const char *what) { return set_err(code, (std::string(who) + ": " + what).c_str()); };
+  int rc;
+  if (m_q && (!cls || !off || !weight)) return fail(DCRX_E_INVALID, "null argument");
+  uint64_t out_of_reach = 0, total = 0;
+  for (uint64_t k = 0; k < m_q; k++) {
+    if (off[k + 1] < off[k]) return fail(DCRX_E_INVALID, "offsets go backwards");
+    if (!in_reach(off[k + 1] - off[k])) out_of_reach++;
+    if (__builtin_add_overflow(total, weight[k], &total))
+      return fail(DCRX_E_UNSUPPORTED, "the sum of the query weights is 2^64 or more");
+  }
+  if (m_q && off[m_q] > off[0] && !text) return fail(DCRX_E_INVALID, "text is null");
+  dcrx_cdr3_match *M = new dcrx_cdr3_match();
+  struct Drop {      // (released on every path that does not hand it over)
+    dcrx_cdr3_match *p;
+    ~Drop() { delete p; }
+  } drop{M};
+  M->weighted = wc != nullptr;
+  M->stats.queries = m_q;
+  M->stats.targets = I->m;
+  M->stats.queries_out_of_reach = out_of_reach;
+  M->stats.targets_out_of_reach = I->out_of_reach;
+  M->degree.assign(m_q, 0);
+  M->hit_off.assign(m_q + 1, 0);
+  M->t_queries.assign(I->m, 0);
+  M->t_weight.assign(I->m, 0);
+  if (m_q && I->m) {
+    dcrx::DeviceGuard on(I->device);
+    if ((rc = run_match(*I, m_q, cls, off, text, weight, distance, metric, wc, *M))) return rc;
+  }
+  M->stats.hits = M->hit.size();
+  for (uint64_t k = 0; k < m_q; k++) {
+    if (!M->degree[k]) continue;
+    M->stats.queries_hit++;
+    M->stats.queries_hit_weight += weight[k];
+    M->stats.largest_degree = std::max<uint64_t>(M->stats.largest_degree, M->degree[k]);
+  }
+  for (uint32_t q : M->t_queries) M->stats.targets_hit += q != 0;
+  drop.p = nullptr;
+  *match_out = M;
+  return DCRX_OK;
+}
+
+// the matches text under any metric (cost: the weighted metric's, null otherwise)
+int64_t format_matches(const char *who, uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx, const uint32_t *j_idx,
+                                 uint32_t n_v, const char *v_calls, const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
+                                 const uint32_t *j_call_off, const uint64_t *q_off, const char *q_text, const uint64_t *weight, uint64_t m_t,
+                                 const uint64_t *t_off, const char *t_text, const char *db_header, uint64_t db_header_bytes,
+                                 const uint64_t *db_line_off, const char *db_lines, uint32_t metric, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap) {
+  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  static const char header[] = "clonotype\tv_call\tj_call\tjunction_aa\tduplicate_count\ttarget\tdistance\t";
+  if ((db_header_bytes && !db_header) ||
+      (m_q && (!hit_off || !v_idx || !j_idx || !v_calls || !v_call_off || !j_calls || !j_call_off || !q_off || !weight)) ||
+      (m_q && hit_off[m_q] && (!hit || !t_off || !db_line_off || !q_text || !t_text || !db_lines)))
+    return fail("null argument");
+  dcrx::TextOut T{out, out_cap};
+  T.put(header, sizeof header - 1);
+  T.put(db_header, db_header_bytes);
+  T.put("\n", 1);
+  for (uint64_t i = 0; i < m_q; i++) {
+    if (hit_off[i + 1] < hit_off[i]) return fail("hit offsets go backwards");
+    if (hit_off[i + 1] == hit_off[i]) continue;
+    const uint32_t vi = v_idx[i], ji = j_idx[i];
+    if (vi >= n_v || ji >= n_j) return fail("a gene outside its table");
+    if (q_off[i + 1] < q_off[i]) return fail("offsets go backwards");
+    const uint64_t lq = q_off[i + 1] - q_off[i];
+    for (uint64_t k = hit_off[i]; k < hit_off[i + 1]; k++) {
+      const uint64_t j = hit[k];
+      if (j >= m_t) return fail("a hit outside the targets");
+      if (t_off[j + 1] < t_off[j] || db_line_off[j + 1] < db_line_off[j])
+        return fail("offsets go backwards");
+      const uint64_t lt = t_off[j + 1] - t_off[j];
+      unsigned long long d = 0;
+      if (cost) {
+        if (!in_reach(lq) || !in_reach(lt) || !host_letters(q_text + q_off[i], lq) || !host_letters(t_text + t_off[j], lt))
+          return fail("a hit between strings out of the weighted metric's reach");
+        d = host_weighted(q_text + q_off[i], lq, t_text + t_off[j], lt, *cost);
+      } else if (metric == METRIC_LEVENSHTEIN) {
+        d = host_levenshtein(q_text + q_off[i], lq, t_text + t_off[j], lt);
+      } else {
+        if (lq != lt) return fail("a hit between strings of two lengths");
+        for (uint64_t p = 0; p < lq; p++) d += q_text[q_off[i] + p] != t_text[t_off[j] + p];
+      }
+      T.unum(i); T.put("\t", 1);
+      T.put_span(v_calls, v_call_off, vi); T.put("\t", 1);
+      T.put_span(j_calls, j_call_off, ji); T.put("\t", 1);
+      T.put_span(q_text, q_off, i); T.put("\t", 1);
+      T.unum(weight[i]); T.put("\t", 1);
+      T.unum(j); T.put("\t", 1);
+      T.unum(d); T.put("\t", 1);
+      T.put_span(db_lines, db_line_off, j); T.put("\n", 1);
+    }
+  }
+  return (int64_t)T.at;
 }
 
 }  // namespace
@@ -464,9 +706,9 @@ int dcrx_cdr3_match_device(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint3
     return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: the work space is smaller than dcrx_cdr3_match_work_bytes(m_q, text_bytes, metric)");
   const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
   const bool lev = walks_lev(distance, metric);
-  if ((rc = run_degrees(*I, N, m_q, distance, lev, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
+  if ((rc = run_degrees(*I, N, m_q, distance, lev, nullptr, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
   if (!d_hit || !hit_cap) return DCRX_OK;
-  return run_write(*I, m_q, distance, lev, d_hit_off, d_hit, hit_cap, W, s);
+  return run_write(*I, m_q, distance, lev, nullptr, d_hit_off, d_hit, nullptr, hit_cap, W, s);
 } catch (const std::exception &e) {      // (a message that could not be built)
   return set_err(DCRX_E_NOMEM, e.what());
 }
@@ -478,43 +720,7 @@ int dcrx_cdr3_match_run(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t
   *match_out = nullptr;
   int rc = refuse(who, I, m_q, distance, metric);
   if (rc) return rc;
-  if (m_q && (!cls || !off || !weight)) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: null argument");
-  uint64_t out_of_reach = 0, total = 0;
-  for (uint64_t k = 0; k < m_q; k++) {
-    if (off[k + 1] < off[k]) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: offsets go backwards");
-    if (!in_reach(off[k + 1] - off[k])) out_of_reach++;
-    if (__builtin_add_overflow(total, weight[k], &total))
-      return set_err(DCRX_E_UNSUPPORTED, "dcrx_cdr3_match_run: the sum of the query weights is 2^64 or more");
-  }
-  if (m_q && off[m_q] > off[0] && !text) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_run: text is null");
-  dcrx_cdr3_match *M = new dcrx_cdr3_match();
-  struct Drop {      // (released on every path that does not hand it over)
-    dcrx_cdr3_match *p;
-    ~Drop() { delete p; }
-  } drop{M};
-  M->stats.queries = m_q;
-  M->stats.targets = I->m;
-  M->stats.queries_out_of_reach = out_of_reach;
-  M->stats.targets_out_of_reach = I->out_of_reach;
-  M->degree.assign(m_q, 0);
-  M->hit_off.assign(m_q + 1, 0);
-  M->t_queries.assign(I->m, 0);
-  M->t_weight.assign(I->m, 0);
-  if (m_q && I->m) {
-    dcrx::DeviceGuard on(I->device);
-    if ((rc = run_match(*I, m_q, cls, off, text, weight, distance, metric, *M))) return rc;
-  }
-  M->stats.hits = M->hit.size();
-  for (uint64_t k = 0; k < m_q; k++) {
-    if (!M->degree[k]) continue;
-    M->stats.queries_hit++;
-    M->stats.queries_hit_weight += weight[k];
-    M->stats.largest_degree = std::max<uint64_t>(M->stats.largest_degree, M->degree[k]);
-  }
-  for (uint32_t q : M->t_queries) M->stats.targets_hit += q != 0;
-  drop.p = nullptr;
-  *match_out = M;
-  return DCRX_OK;
+  return run_entry(who, I, m_q, cls, off, text, weight, distance, metric, nullptr, match_out);
 } catch (const std::exception &e) {
   return set_err(DCRX_E_NOMEM, e.what());
 }
@@ -545,50 +751,86 @@ int64_t dcrx_format_cdr3_matches(uint64_t m_q, const uint64_t *hit_off, const ui
                                  const uint32_t *j_call_off, const uint64_t *q_off, const char *q_text, const uint64_t *weight, uint64_t m_t,
                                  const uint64_t *t_off, const char *t_text, const char *db_header, uint64_t db_header_bytes,
                                  const uint64_t *db_line_off, const char *db_lines, uint32_t metric, char *out, uint64_t out_cap) try {
-  static const char header[] = "clonotype\tv_call\tj_call\tjunction_aa\tduplicate_count\ttarget\tdistance\t";
   if (!metric_exists(metric))
     return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
-  if ((db_header_bytes && !db_header) ||
-      (m_q && (!hit_off || !v_idx || !j_idx || !v_calls || !v_call_off || !j_calls || !j_call_off || !q_off || !weight)) ||
-      (m_q && hit_off[m_q] && (!hit || !t_off || !db_line_off || !q_text || !t_text || !db_lines)))
-    return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: null argument");
-  dcrx::TextOut T{out, out_cap};
-  T.put(header, sizeof header - 1);
-  T.put(db_header, db_header_bytes);
-  T.put("\n", 1);
-  for (uint64_t i = 0; i < m_q; i++) {
-    if (hit_off[i + 1] < hit_off[i]) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: hit offsets go backwards");
-    if (hit_off[i + 1] == hit_off[i]) continue;
-    const uint32_t vi = v_idx[i], ji = j_idx[i];
-    if (vi >= n_v || ji >= n_j) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: a gene outside its table");
-    if (q_off[i + 1] < q_off[i]) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: offsets go backwards");
-    const uint64_t lq = q_off[i + 1] - q_off[i];
-    for (uint64_t k = hit_off[i]; k < hit_off[i + 1]; k++) {
-      const uint64_t j = hit[k];
-      if (j >= m_t) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: a hit outside the targets");
-      if (t_off[j + 1] < t_off[j] || db_line_off[j + 1] < db_line_off[j])
-        return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: offsets go backwards");
-      const uint64_t lt = t_off[j + 1] - t_off[j];
-      unsigned long long d = 0;
-      if (metric == METRIC_LEVENSHTEIN) {
-        d = host_levenshtein(q_text + q_off[i], lq, t_text + t_off[j], lt);
-      } else {
-        if (lq != lt) return set_err(DCRX_E_INVALID, "dcrx_format_cdr3_matches: a hit between strings of two lengths");
-        for (uint64_t p = 0; p < lq; p++) d += q_text[q_off[i] + p] != t_text[t_off[j] + p];
-      }
-      T.unum(i); T.put("\t", 1);
-      T.put_span(v_calls, v_call_off, vi); T.put("\t", 1);
-      T.put_span(j_calls, j_call_off, ji); T.put("\t", 1);
-      T.put_span(q_text, q_off, i); T.put("\t", 1);
-      T.unum(weight[i]); T.put("\t", 1);
-      T.unum(j); T.put("\t", 1);
-      T.unum(d); T.put("\t", 1);
-      T.put_span(db_lines, db_line_off, j); T.put("\n", 1);
-    }
-  }
-  return (int64_t)T.at;
+  return format_matches("dcrx_format_cdr3_matches", m_q, hit_off, hit, v_idx, j_idx, n_v, v_calls, v_call_off, n_j, j_calls, j_call_off, q_off, q_text, weight, m_t, t_off,
+                        t_text, db_header, db_header_bytes, db_line_off, db_lines, metric, nullptr, out, out_cap);
 } catch (const std::exception &e) {      // (host_levenshtein's rows)
   return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int64_t dcrx_format_cdr3_matches_weighted(uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx,
+                                          const uint32_t *j_idx, uint32_t n_v, const char *v_calls, const uint32_t *v_call_off,
+                                          uint32_t n_j, const char *j_calls, const uint32_t *j_call_off, const uint64_t *q_off,
+                                          const char *q_text, const uint64_t *weight, uint64_t m_t, const uint64_t *t_off,
+                                          const char *t_text, const char *db_header, uint64_t db_header_bytes, const uint64_t *db_line_off,
+                                          const char *db_lines, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap) try {
+  static const char who[] = "dcrx_format_cdr3_matches_weighted";
+  const int rc = refuse_cost(who, cost, 0, nullptr);
+  if (rc) return rc;
+  return format_matches(who, m_q, hit_off, hit, v_idx, j_idx, n_v, v_calls, v_call_off, n_j, j_calls, j_call_off, q_off, q_text, weight, m_t, t_off,
+                        t_text, db_header, db_header_bytes, db_line_off, db_lines, METRIC_WEIGHTED, cost, out, out_cap);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+// ---- the weighted metric's entries (include/dcrx.h "match, weighted")
+
+uint64_t dcrx_cdr3_match_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes) {
+  return dcrx_cdr3_match_work_bytes(m_q, text_bytes, METRIC_HAMMING);      // (the same carve: no presence masks)
+}
+
+int dcrx_cdr3_match_weighted_device(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off,
+                                    const char *d_text, uint64_t text_bytes, const dcrx_cdr3_cost_t *cost, uint32_t radius,
+                                    uint32_t *d_degree, uint64_t *d_hit_off, uint32_t *d_hit, uint32_t *d_hit_dist, uint64_t hit_cap,
+                                    uint64_t *d_hit_need, void *d_work, uint64_t work_bytes, void *hip_stream) try {
+  static const char who[] = "dcrx_cdr3_match_weighted_device";
+  CostArg wc;
+  int rc = refuse(who, I, m_q, 0, METRIC_HAMMING);
+  if (rc || (rc = refuse_cost(who, cost, radius, &wc))) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  if (m_q && (!d_class || !d_off || !d_degree || !d_hit_off || !d_work || (text_bytes && !d_text) || (hit_cap && !d_hit)))
+    return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_weighted_device: null argument");
+  dcrx::DeviceGuard on(I->device);
+  if (!m_q || !I->m) {      // nothing can hit: no launch
+    if (d_hit_need) HIP_TRY(hipMemsetAsync(d_hit_need, 0, sizeof(uint64_t), s));
+    if (d_hit_off) HIP_TRY(hipMemsetAsync(d_hit_off, 0, (m_q + 1) * sizeof(uint64_t), s));
+    if (m_q) HIP_TRY(hipMemsetAsync(d_degree, 0, m_q * sizeof(uint32_t), s));
+    return DCRX_OK;
+  }
+  if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_weighted_device: the work space is not 256-byte aligned");
+  Pool P(d_work);
+  Work W;
+  if ((rc = W.carve(P, m_q, METRIC_HAMMING))) return rc;
+  if (work_bytes < P.bytes())
+    return set_err(DCRX_E_INVALID,
+                   "dcrx_cdr3_match_weighted_device: the work space is smaller than dcrx_cdr3_match_weighted_work_bytes(m_q, text_bytes)");
+  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
+  if ((rc = run_degrees(*I, N, m_q, radius, true, &wc, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
+  if (!d_hit || !hit_cap) return DCRX_OK;
+  return run_write(*I, m_q, radius, true, &wc, d_hit_off, d_hit, d_hit_dist, hit_cap, W, s);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int dcrx_cdr3_match_weighted_run(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *cls, const uint64_t *off, const char *text,
+                                 const uint64_t *weight, const dcrx_cdr3_cost_t *cost, uint32_t radius, dcrx_cdr3_match_t **match_out) try {
+  static const char who[] = "dcrx_cdr3_match_weighted_run";
+  if (!match_out) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_weighted_run: null argument");
+  *match_out = nullptr;
+  CostArg wc;
+  int rc = refuse(who, I, m_q, 0, METRIC_HAMMING);
+  if (rc || (rc = refuse_cost(who, cost, radius, &wc))) return rc;
+  return run_entry(who, I, m_q, cls, off, text, weight, radius, METRIC_HAMMING, &wc, match_out);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int dcrx_cdr3_match_export_dist(const dcrx_cdr3_match_t *M, uint32_t *hit_dist) {
+  if (!M) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_export_dist: null handle");
+  if (!M->weighted) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_export_dist: the handle is not of dcrx_cdr3_match_weighted_run");
+  if (hit_dist && !M->hit_dist.empty()) std::memcpy(hit_dist, M->hit_dist.data(), M->hit_dist.size() * sizeof(uint32_t));
+  return DCRX_OK;
 }
 
 }  // extern "C"

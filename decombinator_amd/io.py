@@ -193,9 +193,25 @@ def _match(p: argparse.ArgumentParser):
     p.add_argument("--cdr3-distance", dest="cdr3_distance", type=int, default=1,
                    help="Residues in which a clonotype's CDR3 and a database entry's may differ: 0, 1 (default) or 2.  The default "
                         "is a design choice, not a measured optimum")
-    p.add_argument("--cdr3-metric", dest="cdr3_metric", choices=["hamming", "levenshtein"], default="hamming",
-                   help="How those residues are counted: hamming (default; substitutions between CDR3s of one length) or "
-                        "levenshtein (substitutions, insertions and deletions)")
+    p.add_argument("--cdr3-metric", dest="cdr3_metric", choices=["hamming", "levenshtein", "weighted"], default="hamming",
+                   help="How those residues are counted: hamming (default; substitutions between CDR3s of one length), "
+                        "levenshtein (substitutions, insertions and deletions) or weighted (a TCRdist-style distance with a "
+                        "radius: a substitution costs what --cdr3-cost-matrix says, a length difference is one gap of "
+                        "--cdr3-gap-cost per position, the ends given by --cdr3-trim do not count, and a hit lies within "
+                        "--cdr3-radius; --cdr3-distance does not apply; CDR3s with a byte outside A..Z take no part)")
+    p.add_argument("--cdr3-radius", dest="cdr3_radius", type=int, default=None,
+                   help="With --cdr3-metric weighted: the largest weighted distance of a hit, 0 to 65535 (default 24: two radical "
+                        "substitutions, or one gapped position and one radical substitution).  The defaults 24, 12 and 3,2 "
+                        "follow TCRdist's CDR3 settings: a design choice, not a measured optimum")
+    p.add_argument("--cdr3-gap-cost", dest="cdr3_gap_cost", type=int, default=None,
+                   help="With --cdr3-metric weighted: the price of one gapped position, 1 to 255 (default 12)")
+    p.add_argument("--cdr3-trim", dest="cdr3_trim", type=str, default=None,
+                   help="With --cdr3-metric weighted: N,C - the first N and the last C residues of the shorter CDR3 do not count, "
+                        "0 to 16 each (default 3,2)")
+    p.add_argument("--cdr3-cost-matrix", dest="cdr3_cost_matrix", type=str, default=None,
+                   help="With --cdr3-metric weighted: a tab-separated square table of substitution costs 0..255 (first row and "
+                        "first column: single letters; symmetric, zero diagonal, covering the twenty amino acids).  Default: "
+                        "3 * min(4, 4 - BLOSUM62), as TCRdist's")
     p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default="v",
                    help="What a clonotype and a database entry must share beside the CDR3: nothing (none), the V call (v, the "
                         "default) or the V and the J call (vj).  The default is the network's: a design choice, not a measured "

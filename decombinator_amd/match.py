@@ -3,6 +3,7 @@ second table — a list of CDR3s of known specificity (a VDJdb or McPAS export, 
 
     python -m decombinator_amd match -in A.clonotypes.tsv [B.clonotypes.tsv.gz ...] -db known.tsv[.gz] [-op DIR] [-pf dcr_] [-dz]
            [--cdr3-distance 0|1|2] [--cdr3-metric hamming|levenshtein] [--cdr3-class none|v|vj] [--strip-alleles]
+           [--cdr3-metric weighted [--cdr3-radius N] [--cdr3-gap-cost N] [--cdr3-trim N,C] [--cdr3-cost-matrix FILE]]
            [--db-cdr3-column NAME] [--db-v-column NAME] [--db-j-column NAME]
 
 The samples are 1 to 64 `.clonotypes.tsv` files (overlap.read_table; a sample is named as `overlap` names it).  The database is
@@ -15,6 +16,13 @@ A hit joins a clonotype and a database entry of one class (--cdr3-class: nothing
 or the V and the J call; numbered from the call STRINGS over the database and all samples, with --strip-alleles up to the
 first `*` on both sides: no gene set and no -tfdir are needed) whose CDR3s are at most --cdr3-distance (default 1) apart under
 --cdr3-metric (hamming, the default: substitutions between CDR3s of one length; levenshtein: insertions and deletions too).
+
+--cdr3-metric weighted asks the field's usual question instead (include/dcrx.h "match, weighted"; _native.cdr3_match_weighted):
+a TCRdist-style distance with a radius.  A substitution costs what the table says (--cdr3-cost-matrix; by default 3 * min(4, 4 -
+BLOSUM62): 12 for most pairs, 3 for I-V), a length difference is ONE gap at the best place at --cdr3-gap-cost (12) a position, the
+first N and last C residues of the shorter CDR3 (--cdr3-trim, 3,2) do not count, and a hit lies within --cdr3-radius (24).  Those
+defaults follow TCRdist's CDR3 settings: a design choice, not a measured optimum.  --cdr3-distance does not apply.  A CDR3 with a
+byte outside A..Z takes no part, and the stage prints how many it left out; the files' distance column holds the weighted distance.
 
 Per sample `<prefix><sample>.cdr3_matches.tsv[.gz]`: one line per hit, ordered by (clonotype, target): clonotype (the 0-based
 row of the sample's table), v_call, j_call, junction_aa, duplicate_count, target (the 0-based row of the database), distance,
@@ -50,11 +58,62 @@ def refusal(inp: dict):
     distance = inp.get("cdr3_distance", 1)
     if isinstance(distance, bool) or not isinstance(distance, int) or not 0 <= distance <= 2:
         return f"--cdr3-distance is 0, 1 or 2, not {distance!r}"
-    if inp.get("cdr3_metric", "hamming") not in nat.CDR3_METRICS:
-        return f"--cdr3-metric is one of {', '.join(nat.CDR3_METRICS)}, not {inp['cdr3_metric']}"
+    if inp.get("cdr3_metric", "hamming") not in tuple(nat.CDR3_METRICS) + (WEIGHTED,):
+        return f"--cdr3-metric is one of {', '.join(tuple(nat.CDR3_METRICS) + (WEIGHTED,))}, not {inp['cdr3_metric']}"
+    why = weighted_refusal(inp)
+    if why:
+        return why
     if inp.get("cdr3_class", "v") not in CLASSES:
         return f"--cdr3-class is none, v or vj, not {inp['cdr3_class']}"
     return None
+
+
+WEIGHTED = "weighted"
+WEIGHTED_OPTIONS = {"cdr3_radius": "--cdr3-radius", "cdr3_gap_cost": "--cdr3-gap-cost", "cdr3_trim": "--cdr3-trim",
+                    "cdr3_cost_matrix": "--cdr3-cost-matrix"}
+WEIGHTED_DEFAULTS = {"cdr3_radius": 24, "cdr3_gap_cost": 12, "cdr3_trim": "3,2"}      # after TCRdist's CDR3 settings: a design choice
+
+
+def parse_trim(text):
+    """(N, C) of "N,C", or None."""
+    parts = str(text).split(",")
+    if len(parts) != 2 or not all(x.strip().isdigit() for x in parts):
+        return None
+    return int(parts[0]), int(parts[1])
+
+
+def weighted_refusal(inp: dict):
+    """What refusal() adds for the weighted metric and its options — decided before any file is opened."""
+    given = [flag for key, flag in WEIGHTED_OPTIONS.items() if inp.get(key) is not None]
+    if inp.get("cdr3_metric", "hamming") != WEIGHTED:
+        return f"{given[0]} goes with --cdr3-metric weighted" if given else None
+    if inp.get("cdr3_distance", 1) != 1:
+        return "--cdr3-distance does not apply to --cdr3-metric weighted: the radius is --cdr3-radius"
+    radius = inp.get("cdr3_radius") if inp.get("cdr3_radius") is not None else WEIGHTED_DEFAULTS["cdr3_radius"]
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= nat.CDR3_MAX_RADIUS:
+        return f"--cdr3-radius is 0 to {nat.CDR3_MAX_RADIUS}, not {radius!r}"
+    gap = inp.get("cdr3_gap_cost") if inp.get("cdr3_gap_cost") is not None else WEIGHTED_DEFAULTS["cdr3_gap_cost"]
+    if isinstance(gap, bool) or not isinstance(gap, int) or not 1 <= gap <= nat.CDR3_COST_MAX_GAP:
+        return f"--cdr3-gap-cost is 1 to {nat.CDR3_COST_MAX_GAP}, not {gap!r}"
+    trim = parse_trim(inp.get("cdr3_trim") if inp.get("cdr3_trim") is not None else WEIGHTED_DEFAULTS["cdr3_trim"])
+    if trim is None or max(trim) > nat.CDR3_COST_MAX_TRIM:
+        return f"--cdr3-trim is N,C with 0 to {nat.CDR3_COST_MAX_TRIM} each, not {inp.get('cdr3_trim')!r}"
+    return None
+
+
+def weighted_settings(inp: dict):
+    """(cost, radius) of arguments weighted_refusal() let pass; reads --cdr3-cost-matrix (ValueError by line for a bad one)."""
+    get = lambda key: inp.get(key) if inp.get(key) is not None else WEIGHTED_DEFAULTS[key]
+    ntrim, ctrim = parse_trim(get("cdr3_trim"))
+    if inp.get("cdr3_cost_matrix"):
+        cost = nat.Cdr3Cost.from_file(inp["cdr3_cost_matrix"], get("cdr3_gap_cost"), ntrim, ctrim)
+    else:
+        cost = nat.Cdr3Cost.default(get("cdr3_gap_cost"), ntrim, ctrim)
+    return cost, get("cdr3_radius")
+
+
+def letters_only(s: bytes) -> bool:
+    return all(65 <= b <= 90 for b in s)
 
 
 def call_key(call: str, strip_alleles: bool) -> str:
@@ -145,6 +204,7 @@ def run(inp: dict) -> dict:
     names = [sample_name(f) for f in files]
     mode, strip = inp.get("cdr3_class", "v"), bool(inp.get("strip_alleles"))
     distance, metric = int(inp.get("cdr3_distance", 1)), inp.get("cdr3_metric", "hamming")
+    cost, radius = weighted_settings(inp) if metric == WEIGHTED else (None, None)      # (the matrix file: before the database)
     db = read_database(inp["database"], inp)
     class_no = {}
     t_classes = [class_no.setdefault(class_key(mode, v, j, strip), len(class_no)) for v, j in zip(db["v"], db["j"])]
@@ -165,14 +225,23 @@ def run(inp: dict) -> dict:
             if sum(dup) >= 1 << 64:      # (before the sample's device call; the library refuses the same)
                 raise ValueError(f"{path}: the duplicate counts add up to 2^64 or more")
             weights = np.array(dup, dtype=np.uint64)
-            result = nat.cdr3_match(index, np.array(classes, dtype=np.uint32), off, text, weights, distance, metric)
-            st = result["stats"]
+            cls_arr = np.array(classes, dtype=np.uint32)
+            if cost is not None:
+                result = nat.cdr3_match_weighted(index, cls_arr, off, text, weights, cost, radius)
+                not_letters = lambda strings: sum(1 <= len(s) <= nat.CDR3NET_MAX_LEN and not letters_only(s) for s in strings)
+                st = dict(result["stats"], queries_not_letters=not_letters(aa), targets_not_letters=not_letters(db["cdr3"]))
+                how = f"weighted, radius {radius}, gap {cost.gap}, trim {cost.ntrim},{cost.ctrim}"
+                left_out = (f", {st['queries_not_letters']:,} clonotypes and {st['targets_not_letters']:,} entries left out for a byte "
+                            "outside A..Z")
+            else:
+                result = nat.cdr3_match(index, cls_arr, off, text, weights, distance, metric)
+                st, how, left_out = result["stats"], f"{metric} {distance}", ""
             stats[name] = st
-            print(f"Match of {name} against {st['targets']:,} database entries ({metric} {distance}, class {mode}): {st['queries']:,} "
+            print(f"Match of {name} against {st['targets']:,} database entries ({how}, class {mode}): {st['queries']:,} "
                   f"clonotypes, {st['queries_hit']:,} with a hit ({st['queries_hit_weight']:,} reads), {st['hits']:,} hits, "
-                  f"{st['queries_out_of_reach']:,} clonotypes and {st['targets_out_of_reach']:,} entries out of reach")
+                  f"{st['queries_out_of_reach']:,} clonotypes and {st['targets_out_of_reach']:,} entries out of reach{left_out}")
             text_out = nat.format_cdr3_matches(result, v_idx, j_idx, list(v_no), list(j_no), off, text, weights, t_off, t_text, db_header,
-                                               db["lines"], metric)
+                                               db["lines"], metric if cost is None else cost)
             out["matches"].append(write_out_match(text_out, name + ".cdr3_matches.tsv", inp))
             out["results"].append(result)
             out["stats"].append(st)

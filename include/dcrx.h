@@ -1204,6 +1204,76 @@ int64_t dcrx_format_cdr3_matches(uint64_t m_q, const uint64_t *hit_off, const ui
                                  const uint64_t *db_line_off, const char *db_lines, uint32_t metric, char *out,
                                  uint64_t out_cap);
 
+/* ---- match, weighted (`match --cdr3-metric weighted`): the same question under a weighted, TCRdist-style distance with a
+ * radius — a conservative substitution costs little, a radical one a lot, a length difference is one gap with a price, and
+ * the conserved ends of the CDR3 do not count.  The reference has no counterpart: the contract below is this library's own.
+ * The entries only ADD to ABI 5; the entries above keep their signatures and behaviour, and go on refusing metric 2 ----
+ *
+ * A cost, dcrx_cdr3_cost_t: sub[x][y] the price of letter x against letter y, a letter's index being byte & 31 ('A' 1 ..
+ *   'Z' 26; rows and columns 0 and 27 .. 31 are never read); gap, the price of one gapped position, 1 .. 255; ntrim and ctrim,
+ *   0 .. 16 each: the first ntrim and the last ctrim positions of the SHORTER string are not counted.  sub is symmetric and
+ *   zero on its diagonal over 1 .. 26.  A radius R, 0 .. 65535.  Anything else (an asymmetric entry, a non-zero diagonal,
+ *   gap 0 or above 255, a trim above 16, a radius above 65535) is DCRX_E_INVALID, refused on the host before any device call.
+ * In reach: the network's rule, 1 <= len <= DCRX_CDR3NET_MAX_LEN (32), and under this metric every byte in 'A' .. 'Z'.  A
+ *   node with any other byte (lower case, '*', '_', 0x00, 0x80 and above) takes part in no hit.  The statistics'
+ *   *_out_of_reach count the network's rule alone, as under the other metrics; the stage counts the non-letter nodes.
+ * The distance of a (la bytes) and b (lb >= la bytes; swapped otherwise), d = lb - la: the gap is ONE block of d positions
+ *   put into a behind its first p residues, so a[i] stands against b[i] for i < p and against b[i + d] for i >= p; position i
+ *   of a is counted when ntrim <= i < la - ctrim; dist(a, b) = d * gap + min over p in 0 .. la of the sum over the counted i
+ *   of sub[a[i]][the byte of b it stands against].  With d = 0 there is no gap and no minimum; with la <= ntrim + ctrim
+ *   nothing is counted and dist = d * gap.  (Every p below ntrim costs what p = ntrim costs and every p above la - ctrim what
+ *   p = la - ctrim costs; moving the gap from p to p + 1 changes the sum by sub[a[p]][b[p]] - sub[a[p]][b[p + d]].)
+ * Hit: (i, j) both in reach, c_i == c_j, dist <= R.  The same bytes on both sides are a hit; two strings that differ in
+ *   uncounted positions alone are at distance 0.
+ * Output: as dcrx_cdr3_match_run, and hit_dist: per hit the distance the device computed (uint32).  Everything is a function
+ *   of the input alone.  m_q, m_t < 2^30 and the weight sum below 2^64, as above. */
+#define DCRX_CDR3NET_WEIGHTED 2
+typedef struct dcrx_cdr3_cost {
+  uint8_t sub[32][32];
+  uint32_t gap;
+  uint32_t ntrim;
+  uint32_t ctrim;
+} dcrx_cdr3_cost_t;
+
+/* Bytes of device work space dcrx_cdr3_match_weighted_device needs for m_q queries; 0 for m_q >= 2^30. */
+uint64_t dcrx_cdr3_match_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes);
+
+/* The primitive under the weighted metric, with the arguments, the hit_cap / d_hit_need rules and the work-space rules of
+ * dcrx_cdr3_match_device (one and the same index serves all three metrics).  `cost` is a HOST pointer: the call checks it
+ * and copies it (it travels to the kernels as a launch argument), so the caller may release it on return.  d_hit_dist
+ * (hit_cap entries, device) receives every written hit's distance beside d_hit; it may be NULL.
+ * The steps: keys, the stable sort by class and the gather of the queries as under Levenshtein (no presence masks: a
+ * substitution may cost anything from 0 to 255, so they filter nothing), then cdr3match_wwalk_kernel: the Levenshtein walk's
+ * blocks, tiles and wave skip over the index's class-order arrays; the block stages the 1 KB cost table in LDS once; the
+ * lane that stages a target tests it for letters and marks the staged key (length 0) so that no lane tests it; a lane
+ * tests the class, then the length window |la - lb| * gap <= R, then weighted_within (csrc/dcrx_cdr3w_core.h), pair by pair
+ * as it meets them.  A degree pass, an exclusive sum, and a write pass that stores rank and distance. */
+int dcrx_cdr3_match_weighted_device(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *d_class,
+                                    const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
+                                    const dcrx_cdr3_cost_t *cost, uint32_t radius, uint32_t *d_degree, uint64_t *d_hit_off,
+                                    uint32_t *d_hit, uint32_t *d_hit_dist, uint64_t hit_cap, uint64_t *d_hit_need,
+                                    void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* dcrx_cdr3_match_run under the weighted metric: the same handle (dcrx_cdr3_match_info, _export and _destroy serve it),
+ * which also keeps the hits' distances. */
+int dcrx_cdr3_match_weighted_run(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *cls, const uint64_t *off,
+                                 const char *text, const uint64_t *weight, const dcrx_cdr3_cost_t *cost, uint32_t radius,
+                                 dcrx_cdr3_match_t **match_out);
+/* The distances of a weighted handle's hits, in the order of `hit` (hits entries; may be NULL).  DCRX_E_INVALID for a handle
+ * of dcrx_cdr3_match_run, which has none. */
+int dcrx_cdr3_match_export_dist(const dcrx_cdr3_match_t *match, uint32_t *hit_dist);
+
+/* dcrx_format_cdr3_matches with the weighted distance in the distance column, computed here on the host from the two
+ * strings as the literal minimum over every p in 0 .. la (not the device's one-pass form).  DCRX_E_INVALID in addition for a
+ * cost the contract refuses, and for a hit between strings out of reach or with a byte outside 'A' .. 'Z'. */
+int64_t dcrx_format_cdr3_matches_weighted(uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx,
+                                          const uint32_t *j_idx, uint32_t n_v, const char *v_calls,
+                                          const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
+                                          const uint32_t *j_call_off, const uint64_t *q_off, const char *q_text,
+                                          const uint64_t *weight, uint64_t m_t, const uint64_t *t_off, const char *t_text,
+                                          const char *db_header, uint64_t db_header_bytes, const uint64_t *db_line_off,
+                                          const char *db_lines, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or

@@ -14,8 +14,14 @@ beside two baselines that give the same hits:
   - at 10^5 queries against 10^4 targets only, a Python search on one thread: the targets entered under their strings with D
     positions masked (Hamming) or up to D bytes deleted (Levenshtein, candidates verified by the edit-distance table).
 Every side's hit count is compared: they must agree.  --out FILE rewrites the result so far after every table.
-Usage: tools/bench_cdr3_match.py [--queries 100000,1000000] [--targets 10000,100000] [--classes none,60] [--metrics hamming,levenshtein]
-                                 [--distance 1] [--repeats 5] [--no-baselines] [--slow-s 20] [--skip-above-s 120] [--out FILE]"""
+--metrics may also name `weighted` (include/dcrx.h "match, weighted"): the same seeded tables under the default cost at R = 12
+and at R = 24 (keys .../weighted12 and .../weighted24), the primitive and the host entry timed likewise; the network route does
+not exist for it, and its only baseline is --python-util: tests/cdr3_wmatch_util.expected_numpy (the literal minimum over every
+gap position, as array operations, on one thread) at 10^5 queries against 10^4 targets where the classes are not `none` (all
+pairs of 10^9 are not run).  --python-util needs no GPU when given with --no-gpu.
+Usage: tools/bench_cdr3_match.py [--queries 100000,1000000] [--targets 10000,100000] [--classes none,60]
+                                 [--metrics hamming,levenshtein,weighted] [--distance 1] [--repeats 5] [--no-baselines] [--slow-s 20]
+                                 [--skip-above-s 120] [--python-util] [--no-gpu] [--out FILE]"""
 import argparse
 import itertools
 import json
@@ -31,8 +37,10 @@ sys.path.insert(0, ROOT)
 from decombinator_amd import _native as nat  # noqa: E402
 from tests import cdr3_match_util as mu  # noqa: E402
 from tests import cdr3_network_util as cnu  # noqa: E402
+from tests import cdr3_wmatch_util as wu  # noqa: E402
 
 PYTHON_AT = (100_000, 10_000)
+WEIGHTED_RADII = (12, 24)
 WIDTH = 18
 
 
@@ -101,6 +109,41 @@ def time_primitive(index, q, D, metric, repeats):
             "work_bytes": wb}
 
 
+def time_weighted_primitive(index, q, cost, R, repeats):
+    """time_primitive for dcrx_cdr3_match_weighted_device, the hits' distances written too."""
+    cls, off, text, _ = q
+    m = len(cls)
+    d_cls, d_off = nat.DeviceBuffer.from_host(cls), nat.DeviceBuffer.from_host(off)
+    d_text = nat.DeviceBuffer.from_host(np.frombuffer(text + b"\0", np.uint8))
+    d_deg, d_hit_off, d_need = nat.DeviceBuffer(m * 4), nat.DeviceBuffer((m + 1) * 8), nat.DeviceBuffer(16)
+    wb = nat.cdr3_match_weighted_work_bytes(m, len(text))
+    d_work = nat.DeviceBuffer(wb)
+    args = (index, m, d_cls, d_off, d_text, len(text), cost, R, d_deg, d_hit_off)
+    nat.cdr3_match_weighted_device(*args, None, None, 0, d_need, d_work, wb, None)
+    nat.check(nat.lib().dcrx_synchronize())
+    need = int(d_need.to_host(np.uint64, 1)[0])
+    d_hit, d_dist = nat.DeviceBuffer(max(16, need * 4)), nat.DeviceBuffer(max(16, need * 4))
+    e0, e1, ms = nat.Event(), nat.Event(), []
+    for k in range(repeats + 1):
+        e0.record()
+        nat.cdr3_match_weighted_device(*args, d_hit, d_dist, need, d_need, d_work, wb, None)
+        e1.record()
+        e1.synchronize()
+        if k:
+            ms.append(e0.elapsed_ms(e1))
+    return {"match_device_ms": round(statistics.median(ms), 3), "match_device_ms_all": [round(x, 3) for x in ms], "hits": need,
+            "work_bytes": wb}
+
+
+def python_util(t, q, cost, R):
+    """(hits, seconds) of the Python contract in its numpy form, on one thread."""
+    (t_cls, t_off, t_text), (q_cls, q_off, q_text, w) = t, q
+    case = mu.Case(t_cls.tolist(), cnu.node_strings(t_off, t_text), q_cls.tolist(), cnu.node_strings(q_off, q_text), w.tolist())
+    t0 = time.perf_counter()
+    hits = wu.expected_numpy(case, cost, R)["stats"]["hits"]
+    return hits, time.perf_counter() - t0
+
+
 def network_route(t, q, D, metric):
     """The hits by the route there was before: the network over queries + targets, the cross edges kept."""
     (t_cls, t_off, t_text), (q_cls, q_off, q_text, w) = t, q
@@ -149,16 +192,41 @@ def main():
     ap.add_argument("--no-baselines", action="store_true")
     ap.add_argument("--slow-s", type=float, default=20.0)
     ap.add_argument("--skip-above-s", type=float, default=120.0)
+    ap.add_argument("--python-util", action="store_true")
+    ap.add_argument("--no-gpu", action="store_true")
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     D = a.distance
-    res = {"device": nat.device_name(), "distance": D, "repeats": a.repeats,
+    res = {"device": None if a.no_gpu else nat.device_name(), "distance": D, "repeats": a.repeats,
            "table": "11-18 residues; a fifth of the queries planted 0-2 edits from a target; seed = queries + targets", "tables": {}}
     seen = {}      # (classes, metric) -> (nodes, seconds) of the slowest network route run so far
     for n_q, n_t, cls in itertools.product((int(x) for x in a.queries.split(",")), (int(x) for x in a.targets.split(",")), a.classes.split(",")):
         t, q = seeded_tables(n_q, n_t, 1 if cls == "none" else int(cls), seed=n_q + n_t)
+        if a.no_gpu:
+            for R in WEIGHTED_RADII if a.python_util and (n_q, n_t) == PYTHON_AT and cls != "none" else ():
+                hits, s = python_util(t, q, nat.Cdr3Cost.default(), R)
+                res["tables"][f"{n_q}x{n_t}/{cls}/weighted{R}"] = {"python_util_hits": hits, "python_util_s": round(s, 1)}
+            continue
         index, build_ms, build_all = median_after_warm_up(lambda: nat.Cdr3Index(*t), a.repeats)
-        for metric in a.metrics.split(","):
+        for metric, R in [(m, R) for m in a.metrics.split(",") for R in (WEIGHTED_RADII if m == "weighted" else (None,))]:
+            if metric == "weighted":
+                cost = nat.Cdr3Cost.default()
+                key = f"{n_q}x{n_t}/{cls}/weighted{R}"
+                r = {"queries": n_q, "targets": n_t, "classes": cls, "metric": metric, "radius": R, "gap": cost.gap, "trim": [cost.ntrim, cost.ctrim],
+                     "index_create_ms": build_ms, "index_create_ms_all": build_all, "index_bytes": index.info()["device_bytes"]}
+                r.update(time_weighted_primitive(index, q, cost, R, a.repeats))
+                out, r["match_run_ms"], r["match_run_ms_all"] = median_after_warm_up(lambda: nat.cdr3_match_weighted(index, *q, cost, R), a.repeats)
+                r["stats"] = out["stats"]
+                r["same_hits"] = out["stats"]["hits"] == r["hits"]
+                if a.python_util and (n_q, n_t) == PYTHON_AT and cls != "none":
+                    hits, s = python_util(t, q, cost, R)
+                    r["python_util_s"], r["same_hits"] = round(s, 1), r["same_hits"] and hits == r["hits"]
+                res["tables"][key] = r
+                print(f"{key}: device {r['match_device_ms']} ms, run {r['match_run_ms']} ms, {r['hits']} hits", file=sys.stderr, flush=True)
+                if a.out:
+                    with open(a.out, "w") as fh:
+                        fh.write(json.dumps(res) + "\n")
+                continue
             key = f"{n_q}x{n_t}/{cls}/{metric}"
             r = {"queries": n_q, "targets": n_t, "classes": cls, "metric": metric, "index_create_ms": build_ms, "index_create_ms_all": build_all,
                  "index_bytes": index.info()["device_bytes"]}
