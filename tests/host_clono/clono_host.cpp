@@ -42,4 +42,7 @@ int clono_host_key_equal(const dcrx_cdr3_genes_t *genes, const uint32_t *v_group
   memcpy(&h, blob.data(), sizeof h);
   return key_equal(make_view(h, blob.data()), va, ja, len_a, a, vb, jb, len_b, b) ? 1 : 0;
 }
+
+// Python's s[start:stop] on n characters, as the per-entry code has it
+void clono_host_pyslice(int64_t n, int64_t start, int64_t stop, int64_t *lo, int64_t *hi) { pyslice(n, start, stop, *lo, *hi); }
 }

@@ -83,6 +83,73 @@ def test_keys_compare_in_full_and_equal_keys_hash_equal():
     assert eq(0, 1) == 1 and eq(0, 2) == 0 and eq(0, 3) == 0 and eq(3, 3) == 1
 
 
+# ---- constructed junction geometry (cu.geometry_case): where each residue and each verdict is read from ----
+
+def test_host_build_on_the_full_geometry_product():
+    """13 V x 12 J small genes (cu.GEOMETRY_V, cu.GEOMETRY_J), every vdel in -2 .. len(V) + 2, every jdel in -2 .. len(J) + 2,
+    28 inserts, and the gene indices -1, -n, -n - 1, n: 1 346 592 rows, of which dcrx_cdr3_batch calls 823 645 OK, 149 221
+    INDEX_ERROR and 373 726 BAD_CODON.  Every shared field, arena_off and every junction byte of the host build, exactly."""
+    G, tab = cu.geometry_case()
+    rows, arena = cu.host_calls(G, tab)
+    seen = cu.assert_rows_equal_batch(G, tab, rows, arena)
+    assert len(rows) == 1_346_592 and seen == {nat.CDR3_OK: 823_645, nat.CDR3_INDEX_ERROR: 149_221, nat.CDR3_BAD_CODON: 373_726, nat.CDR3_MOTIF_LEFT: 0}
+
+
+def test_thinned_geometry_list_keeps_its_premises_and_the_reference_is_anchored():
+    """One row in cu.GEOMETRY_STRIDE of the product (122 483 rows; the list the GPU test runs): the premises as
+    cu.geometry_premises counts them on dcrx_cdr3_batch's rows and the plain Python model — 74 951 OK, 13 527 INDEX_ERROR,
+    34 005 BAD_CODON; all 16 flag combinations; 1 749 productive; the rarest edge class (the first invalid V codon at index
+    nv, none read) 869 rows.  dcrx_cdr3_batch itself against translate.cdr3_batch's records and against cu.plain_call, which
+    joins and translates in Python, on every 17th row (7 205)."""
+    G, tab = cu.geometry_case(thin=True)
+    n = cu.geometry_premises(G, tab)
+    assert n["status"][nat.CDR3_MOTIF_LEFT] == 0 and min(n["classes"].values()) == n["classes"]["v_bad_at_nv_no_bad"] == 869
+    assert cu.sample_agrees_with_python_calls(G, tab, 17) >= 3000
+    rows, arena = cu.host_calls(G, tab)
+    cu.assert_rows_equal_batch(G, tab, rows, arena)
+
+
+@pytest.mark.parametrize("case", ["geometry", "coding"])
+def test_respelt_twins_are_one_answer_on_the_host_build(case):
+    """One sequence spelt as several DCRs (cu.respelt_twins: bases moved from the V piece or the J piece into the insert): the
+    residues move between the V table, direct_aa and the (J, phase) table, k0 and the phase change, the calls may not.
+    geometry: 400 sets, 5 080 rows, 150 sets productive.  coding: 300 sets of 22 spellings, all productive, each with the
+    conserved C's codon read from the V table, straddling the V / insert edge, and from the insert."""
+    G, sets = cu.geometry_twins() if case == "geometry" else cu.coding_twins()
+    tab, where = cu.twin_table(sets)
+    rows, arena = cu.host_calls(G, tab)
+    cu.assert_rows_equal_batch(G, tab, rows, arena)
+    productive = cu.assert_twins_agree(rows, arena, where)
+    assert (len(sets), productive) == ((400, 150) if case == "geometry" else (300, 300))
+    assert cu.assert_twin_sets_share_a_clonotype(cu.expected_clonotypes(tab, G), where) == productive
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 513])
+def test_mixed_block_tables_hold_their_premises(n):
+    """cu.mixed_block_table, the tables of the GPU suite's mixed-geometry block-edge test, on the reference side and the host
+    build: 40 twin sets that are 40 clonotypes, non-members of both kinds (a stop in frame or out of frame; a bad codon)."""
+    G, tab, where = cu.mixed_block_table(n)
+    rows, arena = cu.host_calls(G, tab)
+    seen = cu.assert_rows_equal_batch(G, tab, rows, arena)
+    want = cu.expected_clonotypes(tab, G)
+    assert cu.assert_twins_agree(rows, arena, where) == cu.assert_twin_sets_share_a_clonotype(want, where) == want[1]["clonotypes_out"] == 40
+    assert seen[nat.CDR3_BAD_CODON] == want[1]["untranslatable"] > 20 and want[1]["nonproductive"] > 20
+    assert len(set(tab["count"].tolist())) == n
+
+
+def test_pyslice_is_pythons_slice():
+    """make_entry's J slice with a deletion longer than the gene takes nothing whichever way `start > n` is clamped (no base
+    and no table entry is read behind it), so no table can tell; the function itself can."""
+    import ctypes as C
+    lo, hi = C.c_int64(), C.c_int64()
+    for n in range(0, 6):
+        for start in range(-8, 9):
+            for stop in range(-8, 9):
+                cu.host_lib().clono_host_pyslice(n, start, stop, C.byref(lo), C.byref(hi))
+                a, b, _ = slice(start, stop).indices(n)
+                assert (lo.value, hi.value) == (a, max(a, b)), (n, start, stop)
+
+
 # ---- the contract's brute force on hand-made tables ----
 
 def _hand_rows(G):

@@ -84,6 +84,84 @@ def test_primitive_refuses_a_small_work_space_and_sizes_the_arena():
     assert need2 == need and np.array_equal(rows, rows2)
 
 
+# ---- constructed junction geometry: the compiled device code of entry_calls / write_junction, and the grouping behind it ----
+
+def test_primitive_on_the_constructed_geometry_list():
+    """cu.geometry_case(thin=True): one row in 11 of 13 V x 12 J small genes x every vdel in -2 .. len(V) + 2 x every jdel in
+    -2 .. len(J) + 2 x 28 inserts, and the gene indices on the lists' edges — 122 483 rows.  On dcrx_cdr3_batch's rows and the
+    plain Python model (cu.geometry_premises, which asserts the floors: >= 1 000 rows per status, all 16 flag combinations,
+    >= 500 productive, >= 20 per edge class): 74 951 OK, 13 527 INDEX_ERROR, 34 005 BAD_CODON; 1 749 productive; the stop in a
+    straddling codon only 7 362, in the J table only 2 250, in the V table at nv - 1 only 2 331; V's first stop at nv or later
+    and no stop read 10 552 (at nv itself 1 708); the first invalid codon at nv - 1 1 748, at nv or later and none read 7 701
+    (at nv 869); bad_codon_at in the J piece 4 814 (4 015 with k0 > 0); a J stop in front of k0 and none read 4 900; vdel >
+    len(V) 15 154; jdel > len(J) 12 853; the conserved residue read by direct_aa 26 609 (2 904 conserved), from the J table
+    15 124 (1 642); the motif window under 4 residues 42 897; start_cdr3 < 0 1 744.  Every shared field, arena_off, every
+    junction byte."""
+    G, tab = cu.geometry_case(thin=True)
+    n = cu.geometry_premises(G, tab)
+    rows, arena, _ = _device_calls(G, tab)
+    seen = cu.assert_rows_equal_batch(G, tab, rows, arena)
+    assert seen == n["status"] and int((rows["flags"] & 1).sum()) == n["productive"]
+
+
+@pytest.fixture(scope="module", params=["geometry", "coding"])
+def twins(request):
+    G, sets = cu.geometry_twins() if request.param == "geometry" else cu.coding_twins()
+    tab, where = cu.twin_table(sets)
+    want = cu.expected_clonotypes(tab, G)
+    return G, tab, where, want
+
+
+def test_respelt_twins_are_one_answer_on_the_device(twins):
+    """One sequence spelt as several DCRs (cu.respelt_twins; geometry: 400 sets, 5 080 rows, 150 sets productive; coding: 300
+    productive sets of 22 spellings, the conserved C read from the V table, across the edge and from the insert): within a
+    set dcrx_cdr3_device gives one status, flags, start_cdr3 (3 x the codon for BAD_CODON), end_cdr3, seq_len, hash and the
+    same junction bytes; and every row equals dcrx_cdr3_batch's."""
+    G, tab, where, want = twins
+    rows, arena, _ = _device_calls(G, tab)
+    cu.assert_rows_equal_batch(G, tab, rows, arena)
+    assert cu.assert_twins_agree(rows, arena, where) == cu.assert_twin_sets_share_a_clonotype(want, where) >= 150
+
+
+@pytest.mark.parametrize("bits", [64, 0])
+def test_respelt_twins_share_a_clonotype(twins, bits):
+    """Every spelling with a count of its own: each productive set lies in ONE clonotype of the expected result with n_dcrs >=
+    its size (geometry: 143 clonotypes, the largest of 94 DCRs; coding: 296, the largest of 44), and dcrx_clonotypes equals it
+    in every array — with 64 hash bits, where equal keys must hash equal whatever piece each residue was read from, and
+    with none, where SameKey alone decides."""
+    G, tab, where, want = twins
+    assert cu.assert_twin_sets_share_a_clonotype(want, where) >= 150 and want[1]["largest_n_dcrs"] >= 22
+    g = _genes(G)
+    g.set_hash_bits(bits)
+    try:
+        cu.assert_same(nat.clonotypes(g, tab), want)
+    finally:
+        g.set_hash_bits(64)
+
+
+@pytest.mark.parametrize("n,bits", [(255, 64), (256, 64), (257, 64), (513, 64), (255, 0), (256, 0), (257, 0), (513, 0)])
+def test_block_edges_with_members_of_mixed_geometry(n, bits):
+    """cu.mixed_block_table: spellings of 40 coding twin sets dealt round-robin, every third row a non-member (a stop in
+    frame, a letter that is no code, out of frame in turn).  Members and non-members lie in front of row 256 at every size;
+    at 257 row 256 is a member whose set began in the first block; at 513 members and non-members lie on both sides and all
+    40 sets straddle the edge (172 members at 257, 342 at 513, 40 clonotypes)."""
+    G, tab, where = cu.mixed_block_table(n)
+    want = cu.expected_clonotypes(tab, G)
+    non = want[2] == nat.NOT_A_MEMBER
+    assert non[:256].any() and (~non[:256]).any() and want[1]["nonproductive"] > 20 and want[1]["untranslatable"] > 20
+    assert cu.assert_twin_sets_share_a_clonotype(want, where) == len(where) == want[1]["clonotypes_out"] == 40
+    if n > 256:
+        assert (~non[256:]).any() and any(min(ks) < 256 <= max(ks) for ks in where)
+    if n > 258:
+        assert non[256:].any() and all(min(ks) < 256 <= max(ks) for ks in where)
+    g = _genes(G)
+    g.set_hash_bits(bits)
+    try:
+        cu.assert_same(nat.clonotypes(g, tab), want)
+    finally:
+        g.set_hash_bits(64)
+
+
 @pytest.fixture(scope="module")
 def random_case():
     G = cu.golden_genes()
