@@ -1,25 +1,24 @@
 // dcrx_cdr3match.hip — match (`match`): which queries (a sample's clonotypes) are the same as, or one or two residues from, a
 // target (an entry of a database, or of another sample); include/dcrx.h "match" holds the contract, dcrx_cdr3net_core.h the
-// per-node and per-pair code (the CDR3 network's), dcrx_cdr3match_core.h the walk's look-ups.
+// per-node and per-pair code (the CDR3 network's), dcrx_cdr3match_core.h the walk's look-ups, dcrx_cdr3walk.h the kernels
+// that prepare and walk the tables (the network's too).
 //
 // The index (dcrx_cdr3_index_create), once per database: keys, then per bucket order — (class, length) for the Hamming walk,
 // class alone for the Levenshtein walk — a stable radix sort of (key, rank) and the gather of the packed strings (and, in the
 // class order, of the presence masks).  It stays on the device.
 // The primitive (dcrx_cdr3_match_device), all on the caller's stream and in the caller's work space:
-//   keys, sort, gather   the queries, as the network prepares its nodes (cdr3match_keys_kernel, cdr3match_gather_kernel)
-//   degrees  cdr3match_walk_kernel<false>: a block of 256 consecutive sorted queries, one per lane and in registers, finds the
-//            first target at or above its first query's bucket (a binary search over the index's sorted keys, the same for
-//            every lane) and stages the targets from there in LDS tiles of 256 (8 KB of strings, 2 KB of keys, 1 KB of ranks,
-//            1 KB of masks) until a tile starts behind its last query's bucket; every lane of a wave reads the same staged
-//            target (a broadcast), and a wave skips a tile whose buckets miss its own.  A bucket's targets are in rank order:
-//            a query's hits come in ascending rank, with no atomics
+//   keys, sort, gather   the queries, as the network prepares its nodes (cdr3_keys_kernel, cdr3_gather_kernel<false, PRES>)
+//   degrees  cdr3_walk_kernel<false, Bipartite, Pair>: a block of 256 consecutive sorted queries finds the first target at or
+//            above its first query's bucket (a binary search over the index's sorted keys, the same for every lane) and walks
+//            the targets from there until a tile starts behind its last query's bucket.  A bucket's targets are in rank
+//            order: a query's hits come in ascending rank, with no atomics
 //   scan     an exclusive sum of the degrees in rank order: hit_off, whose end is the need
-//   write    cdr3match_walk_kernel<true>: the same walk writes every hit's rank at its exact offset
+//   write    cdr3_walk_kernel<true, Bipartite, Pair>: the same walk writes every hit's rank at its exact offset
 // The host entry (dcrx_cdr3_match_run) runs those two halves around the hits' allocation, then the totals: a lane per query
 // adds its row's hits onto the targets (integer atomics, results unused).
-// The weighted metric (dcrx_cdr3_match_weighted_*; include/dcrx.h "match, weighted"): cdr3match_wwalk_kernel is the
-// Levenshtein walk over the same class-order arrays with weighted_within (dcrx_cdr3w_core.h) as its pair test; it lives in
-// this file because the index, the work space, the handle and the two halves around the walk are this file's own.
+// The weighted metric (dcrx_cdr3_match_weighted_*; include/dcrx.h "match, weighted") is the same walk over the Levenshtein
+// walk's class-order arrays with Weighted (weighted_within, dcrx_cdr3w_core.h) as its pair test; its entries live in this
+// file because the index, the work space, the handle and the two halves around the walk are this file's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,261 +27,13 @@
 #include <vector>
 
 #include "../../include/dcrx.h"
-#include "dcrx_cdr3match_core.h"
-#include "dcrx_cdr3w_core.h"
-#include "dcrx_group.h"
+#include "dcrx_cdr3walk.h"
 #include "dcrx_text.h"
 
 using dcrx::set_err;
-using namespace dcrx_cdr3match;
-using namespace dcrx_cdr3w;
-using namespace dcrx_group;
+using namespace dcrx_cdr3walk;
 
 namespace {
-
-constexpr uint64_t MAX_NODES = 1ull << 30;
-constexpr uint32_t NO_ENTRY = 0xFFFFFFFFu;
-static_assert(BLOCK == (int)QUERIES && BLOCK == (int)TILE, "a lane holds one query and stages one target");
-
-struct Nodes {
-  const uint32_t *cls;
-  const uint64_t *off;
-  const uint8_t *text;
-  uint64_t text_bytes;
-};
-
-// one side in one bucket order: the sorted keys, the ranks, the packed strings and (class order) the presence masks
-struct Sorted {
-  const uint64_t *key;
-  const uint32_t *idx;
-  const uint4 *sj;
-  const uint32_t *pres;
-  uint32_t n;
-};
-
-// the length of node e's string; one past the reach for offsets that go backwards or leave the text
-__device__ __forceinline__ uint64_t node_len(const Nodes &N, uint32_t e, uint64_t *at) {
-  const uint64_t a = N.off[e], b = N.off[e + 1];
-  *at = a;
-  return (b < a || b > N.text_bytes) ? (uint64_t)MAX_LEN + 1 : b - a;
-}
-
-__global__ __launch_bounds__(BLOCK) void cdr3match_keys_kernel(Nodes N, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
-  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
-  if (e >= n) return;
-  uint64_t at;
-  key[e] = node_key(N.cls[e], node_len(N, e, &at));
-  idx[e] = e;
-}
-
-// per sorted position the packed string, and (pres != null) its letter-presence mask
-__global__ __launch_bounds__(BLOCK) void cdr3match_gather_kernel(Nodes N, uint32_t n, const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
-                                                                 uint32_t *__restrict__ pres) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= n) return;
-  uint64_t at;
-  const uint64_t len = node_len(N, idx[s], &at);
-  uint32_t w[WORDS];
-  pack(N.text + (in_reach(len) ? at : 0), len, w);
-  sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
-  sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-  if (pres) pres[s] = presence(w, in_reach(len) ? (uint32_t)len : 0u);
-}
-
-// The walk.  q_*: the queries, t_*: the targets, both sorted in the walk's bucket order.  WRITE false: degree[rank] (and the same
-// as 64 bits, for the scan); true: the hits' ranks at hit_off[rank].  LEV: the buckets are the classes (the keys still hold the
-// lengths), the presence masks are staged with the strings, and a pair is tested by length difference, presence masks and
-// lev_within instead of the Hamming distance.
-template <bool WRITE, bool LEV>
-__global__ __launch_bounds__(BLOCK) void cdr3match_walk_kernel(const uint4 *__restrict__ q_sj, const uint64_t *__restrict__ q_key,
-                                                               const uint32_t *__restrict__ q_idx, const uint32_t *__restrict__ q_pres,
-                                                               uint32_t n_q, const uint4 *__restrict__ t_sj, const uint64_t *__restrict__ t_key,
-                                                               const uint32_t *__restrict__ t_idx, const uint32_t *__restrict__ t_pres,
-                                                               uint32_t n_t, uint32_t limit, uint32_t *__restrict__ degree,
-                                                               uint64_t *__restrict__ deg64, const uint64_t *__restrict__ hit_off,
-                                                               uint32_t *__restrict__ hit, uint64_t hit_cap) {
-  __shared__ uint4 lds_j[TILE * 2];
-  __shared__ uint64_t lds_k[TILE];
-  __shared__ uint32_t lds_r[WRITE ? TILE : 1];
-  __shared__ uint32_t lds_p[LEV ? TILE : 1];
-  const uint32_t s0 = blockIdx.x * BLOCK;
-  const uint32_t s = s0 + threadIdx.x;
-  const bool valid = s < n_q;
-  const uint64_t key_own = valid ? q_key[s] : KEY_OUT_OF_REACH;
-  const bool reach = key_own != KEY_OUT_OF_REACH;
-  const uint64_t k_own = bucket_of<LEV>(key_own);
-  const uint32_t len_own = key_length(key_own), pres_own = LEV && valid ? q_pres[s] : 0u;
-  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t e = 0, count = 0;
-  uint64_t at = 0;
-  if (valid) {
-    e = q_idx[s];
-    if (WRITE) at = hit_off[e];
-    if (reach) {
-      const uint4 a = q_sj[2 * (size_t)s], b = q_sj[2 * (size_t)s + 1];
-      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
-    }
-  }
-  // the wave's buckets (sorted along s; lanes behind the table hold the largest)
-  const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
-  const Range R = block_range<LEV>(q_key, n_q, s0, t_key, n_t);      // (the same for every lane of the block)
-  for (uint32_t t = R.first; t < n_t; t += TILE) {
-    if (!goes_on<LEV>(R, t_key[t])) break;
-    __syncthreads();                                        // the previous tile is no longer read
-    const uint32_t tile_n = min((uint32_t)TILE, n_t - t);
-    if (threadIdx.x < tile_n) {
-      const uint32_t p = t + threadIdx.x;
-      lds_j[2 * threadIdx.x] = t_sj[2 * (size_t)p];
-      lds_j[2 * threadIdx.x + 1] = t_sj[2 * (size_t)p + 1];
-      lds_k[threadIdx.x] = t_key[p];
-      if (WRITE) lds_r[threadIdx.x] = t_idx[p];
-      if (LEV) lds_p[threadIdx.x] = t_pres[p];
-    }
-    __syncthreads();
-    if (wave_skips(bucket_of<LEV>(lds_k[0]), bucket_of<LEV>(lds_k[tile_n - 1]), w_lo, w_hi)) continue;
-    const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
-    if (!LEV) {
-      for (uint32_t q = 0; q < tile_n; q++) {
-        const uint64_t kq = lds_k[q];
-        if (kq < w_lo) continue;
-        if (kq > w_hi) break;
-        if (reach && kq == k_own && distance(own, lj + q * WORDS, limit) <= limit) {
-          if (WRITE && at + count < hit_cap) hit[at + count] = lds_r[q];
-          count++;
-        }
-      }
-      continue;
-    }
-    // LEV: a target that passes the cheap tests waits in `pending` (one per lane), and lev_within runs — for every lane that
-    // has one waiting, each on its own — only once some lane meets its next one, and at the tile's end, as in the network's
-    // walk: the few lanes of a wave that pass at one target would otherwise run it nearly alone.  A lane takes its targets
-    // in order.
-    uint32_t pending = NO_ENTRY;
-    auto settle = [&]() {
-      if (pending != NO_ENTRY) {
-        if (lev_within(own, len_own, lj + pending * WORDS, key_length(lds_k[pending]), limit) <= limit) {
-          if (WRITE && at + count < hit_cap) hit[at + count] = lds_r[pending];
-          count++;
-        }
-        pending = NO_ENTRY;
-      }
-    };
-    for (uint32_t q = 0; q < tile_n; q++) {
-      const uint64_t key_q = lds_k[q], kq = key_class(key_q);
-      if (kq < w_lo) continue;
-      if (kq > w_hi) break;
-      const uint32_t len_q = key_length(key_q);
-      const bool passes = reach && kq == k_own && len_q + limit >= len_own && len_own + limit >= len_q &&
-                          presence_allows(pres_own, lds_p[q], limit);
-      if (__any(passes && pending != NO_ENTRY)) settle();      // (the same for every lane of the wave)
-      if (passes) pending = q;
-    }
-    settle();      // (the next tile overwrites the staged targets)
-  }
-  if (valid && !WRITE) {
-    degree[e] = count;
-    deg64[e] = count;
-  }
-}
-
-// the cost as the weighted walk's launch argument: the table as the 256 dwords the block's lanes copy into LDS, one each
-struct CostArg {
-  uint32_t sub[SUB_BYTES / 4];
-  uint32_t gap, ntrim, ctrim;
-};
-static_assert(SUB_BYTES / 4 == BLOCK, "a lane stages one dword of the cost table");
-
-// The weighted walk: the Levenshtein walk's blocks, tiles and wave skip (the bucket is the class) with another predicate: the
-// class, the length window |la - lb| * gap <= radius, then weighted_within.  The cost table is staged in LDS once per block.
-// The lane that stages a target tests it for letters and stages a key of length 0 for one that fails, which no lane tests;
-// a query that fails takes part in nothing.  The presence masks are not read.  A pair is tested where it is met: at such
-// radii most pairs of a class pass the window, so there is nothing for a pending / settle scheme to collect.  WRITE true
-// also stores the hit's distance (hit_dist may be null).
-template <bool WRITE>
-__global__ __launch_bounds__(BLOCK) void cdr3match_wwalk_kernel(const uint4 *__restrict__ q_sj, const uint64_t *__restrict__ q_key,
-                                                                const uint32_t *__restrict__ q_idx, uint32_t n_q,
-                                                                const uint4 *__restrict__ t_sj, const uint64_t *__restrict__ t_key,
-                                                                const uint32_t *__restrict__ t_idx, uint32_t n_t, const CostArg cost,
-                                                                uint32_t radius, uint32_t *__restrict__ degree, uint64_t *__restrict__ deg64,
-                                                                const uint64_t *__restrict__ hit_off, uint32_t *__restrict__ hit,
-                                                                uint32_t *__restrict__ hit_dist, uint64_t hit_cap) {
-  __shared__ uint4 lds_j[TILE * 2];
-  __shared__ uint64_t lds_k[TILE];
-  __shared__ uint32_t lds_r[WRITE ? TILE : 1];
-  __shared__ uint32_t lds_sub[SUB_BYTES / 4];
-  lds_sub[threadIdx.x] = cost.sub[threadIdx.x];      // (the walk's first barrier stands before its first read)
-  const Cost C{reinterpret_cast<const uint8_t *>(lds_sub), cost.gap, cost.ntrim, cost.ctrim};
-  const uint32_t s0 = blockIdx.x * BLOCK;
-  const uint32_t s = s0 + threadIdx.x;
-  const bool valid = s < n_q;
-  const uint64_t key_own = valid ? q_key[s] : KEY_OUT_OF_REACH;
-  bool reach = key_own != KEY_OUT_OF_REACH;
-  const uint64_t k_own = key_class(key_own);
-  const uint32_t len_own = key_length(key_own);
-  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t e = 0, count = 0;
-  uint64_t at = 0;
-  if (valid) {
-    e = q_idx[s];
-    if (WRITE) at = hit_off[e];
-    if (reach) {
-      const uint4 a = q_sj[2 * (size_t)s], b = q_sj[2 * (size_t)s + 1];
-      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
-      reach = letters_only(own, len_own);
-    }
-  }
-  const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
-  const Range R = block_range<true>(q_key, n_q, s0, t_key, n_t);      // (the same for every lane of the block)
-  for (uint32_t t = R.first; t < n_t; t += TILE) {
-    if (!goes_on<true>(R, t_key[t])) break;
-    __syncthreads();                                        // the previous tile is no longer read
-    const uint32_t tile_n = min((uint32_t)TILE, n_t - t);
-    if (threadIdx.x < tile_n) {
-      const uint32_t p = t + threadIdx.x;
-      const uint4 a = t_sj[2 * (size_t)p], b = t_sj[2 * (size_t)p + 1];
-      const uint32_t w[WORDS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      const uint64_t key = t_key[p];
-      lds_j[2 * threadIdx.x] = a;
-      lds_j[2 * threadIdx.x + 1] = b;
-      lds_k[threadIdx.x] = letters_only(w, key_length(key)) ? key : key & ~LEN_MASK;      // (the class stays: the tile stays sorted)
-      if (WRITE) lds_r[threadIdx.x] = t_idx[p];
-    }
-    __syncthreads();
-    if (wave_skips(key_class(lds_k[0]), key_class(lds_k[tile_n - 1]), w_lo, w_hi)) continue;
-    const uint8_t *lj = reinterpret_cast<const uint8_t *>(lds_j);
-    for (uint32_t q = 0; q < tile_n; q++) {
-      const uint64_t key_q = lds_k[q], kq = key_class(key_q);
-      if (kq < w_lo) continue;
-      if (kq > w_hi) break;
-      const uint32_t len_q = key_length(key_q);      // (0: a target with a non-letter, or out of reach)
-      const uint32_t apart = len_q > len_own ? len_q - len_own : len_own - len_q;
-      if (reach && kq == k_own && len_q != 0 && apart * C.gap <= radius) {
-        const uint32_t dist = weighted_within(own, len_own, lj + q * (WORDS * 4), len_q, C, radius);
-        if (dist <= radius) {
-          if (WRITE && at + count < hit_cap) {
-            hit[at + count] = lds_r[q];
-            if (hit_dist) hit_dist[at + count] = dist;
-          }
-          count++;
-        }
-      }
-    }
-  }
-  if (valid && !WRITE) {
-    degree[e] = count;
-    deg64[e] = count;
-  }
-}
-
-// hit_off[m] and the need behind the scan
-__global__ void cdr3match_need_kernel(const uint64_t *__restrict__ deg64, uint64_t *__restrict__ hit_off, uint32_t n,
-                                      uint64_t *__restrict__ need) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const uint64_t total = hit_off[n - 1] + deg64[n - 1];
-    hit_off[n] = total;
-    if (need) *need = total;
-  }
-}
 
 // the host entry's: every hit of query i onto its target (the results of the atomics are not read)
 __global__ __launch_bounds__(BLOCK) void cdr3match_totals_kernel(const uint64_t *__restrict__ hit_off, const uint32_t *__restrict__ hit,
@@ -298,22 +49,13 @@ __global__ __launch_bounds__(BLOCK) void cdr3match_totals_kernel(const uint64_t 
   }
 }
 
-bool metric_exists(uint32_t metric) { return metric == METRIC_HAMMING || metric == METRIC_LEVENSHTEIN; }
 // D = 0 is byte equality: the (class, length) buckets and the Hamming test serve it under either metric
 bool walks_lev(uint32_t distance, uint32_t metric) { return metric == METRIC_LEVENSHTEIN && distance > 0; }
 
-// keys of n nodes, then their stable sort over the key's bits from begin_bit: (key[1], idx[1])
-int sorted_keys(const Nodes &N, uint64_t n, uint64_t *const key[2], uint32_t *const idx[2], Scratch cub, int begin_bit, bool make_keys,
-                hipStream_t s) {
-  if (make_keys) {
-    cdr3match_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, key[0], idx[0]);
-    HIP_TRY(hipGetLastError());
-  }
-  return sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, KEY_BITS, s, begin_bit);
-}
-
+// the packed strings in sorted order, and (pres != null) the presence masks
 int gather(const Nodes &N, uint64_t n, const uint32_t *idx, uint4 *sj, uint32_t *pres, hipStream_t s) {
-  cdr3match_gather_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, idx, sj, pres);
+  if (pres) cdr3_gather_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, nullptr, idx, sj, nullptr, pres);
+  else cdr3_gather_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, nullptr, idx, sj, nullptr, nullptr);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
@@ -398,32 +140,64 @@ int build_index(dcrx_cdr3_index &I, const uint32_t *cls, const uint64_t *off, co
   return DCRX_OK;
 }
 
+// one pass of the walk (wc: the weighted walk's cost, and then `limit` is the radius and `lev` is set: the class order, without
+// the presence masks)
+template <bool WRITE>
+int run_walk(const dcrx_cdr3_index &I, uint64_t n, uint32_t limit, bool lev, const CostArg *wc, const Out &O, const Work &W, hipStream_t s) {
+  const Sorted Q = W.queries(n, lev), T = I.targets(lev);
+  if (!wc) return walk<WRITE>(Q, T, Bipartite{}, limit, lev, O, s);
+  cdr3_walk_kernel<WRITE><<<grid_for(n), BLOCK, 0, s>>>(Q, T, Bipartite{}, Weighted{*wc, limit}, O);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
 // keys, sort, gather of the queries, the degree pass, the scan and the need
-// (wc: the weighted walk's cost, and then `limit` is the radius and `lev` is set: the class order, without the presence masks)
 int run_degrees(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, uint32_t limit, bool lev, const CostArg *wc, uint32_t *d_degree,
                 uint64_t *d_hit_off, uint64_t *d_need, const Work &W, hipStream_t s) {
   int rc;
   if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, lev ? (int)LEN_BITS : 0, true, s)) ||
-      (rc = gather(N, n, W.idx[1], W.sj, lev ? W.pres : nullptr, s))) return rc;
-  const Sorted Q = W.queries(n, lev), T = I.targets(lev);
-  if (wc) cdr3match_wwalk_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.n, T.sj, T.key, T.idx, T.n, *wc, limit, d_degree, W.deg64, nullptr, nullptr, nullptr, 0);
-  else if (lev) cdr3match_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
-  else cdr3match_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, d_degree, W.deg64, nullptr, nullptr, 0);
-  HIP_TRY(hipGetLastError());
-  if ((rc = exclusive_sum(W.cub, W.deg64, d_hit_off, n, s))) return rc;
-  cdr3match_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_hit_off, (uint32_t)n, d_need);
+      (rc = gather(N, n, W.idx[1], W.sj, lev ? W.pres : nullptr, s)) ||
+      (rc = run_walk<false>(I, n, limit, lev, wc, Out{d_degree, W.deg64, nullptr, nullptr, nullptr, 0}, W, s)) ||
+      (rc = exclusive_sum(W.cub, W.deg64, d_hit_off, n, s))) return rc;
+  cdr3_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_hit_off, (uint32_t)n, d_need);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
 
 int run_write(const dcrx_cdr3_index &I, uint64_t n, uint32_t limit, bool lev, const CostArg *wc, const uint64_t *d_hit_off, uint32_t *d_hit,
               uint32_t *d_hit_dist, uint64_t hit_cap, const Work &W, hipStream_t s) {
-  const Sorted Q = W.queries(n, lev), T = I.targets(lev);
-  if (wc) cdr3match_wwalk_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.n, T.sj, T.key, T.idx, T.n, *wc, limit, nullptr, nullptr, d_hit_off, d_hit, d_hit_dist, hit_cap);
-  else if (lev) cdr3match_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
-  else cdr3match_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(Q.sj, Q.key, Q.idx, Q.pres, Q.n, T.sj, T.key, T.idx, T.pres, T.n, limit, nullptr, nullptr, d_hit_off, d_hit, hit_cap);
-  HIP_TRY(hipGetLastError());
-  return DCRX_OK;
+  return run_walk<true>(I, n, limit, lev, wc, Out{nullptr, nullptr, d_hit_off, d_hit, d_hit_dist, hit_cap}, W, s);
+}
+
+// the device entry under any metric, behind the entry's own refusals (wc: the weighted walk's cost, `limit` its radius, and
+// the carve is the Hamming walk's: no presence masks)
+int match_device(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off, const char *d_text,
+                 uint64_t text_bytes, uint32_t limit, uint32_t metric, const CostArg *wc, uint32_t *d_degree, uint64_t *d_hit_off,
+                 uint32_t *d_hit, uint32_t *d_hit_dist, uint64_t hit_cap, uint64_t *d_hit_need, void *d_work, uint64_t work_bytes,
+                 hipStream_t s) {
+  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  if (m_q && (!d_class || !d_off || !d_degree || !d_hit_off || !d_work || (text_bytes && !d_text) || (hit_cap && !d_hit)))
+    return fail("null argument");
+  dcrx::DeviceGuard on(I->device);      // (the index's device for the launches, the caller's again behind them; no index memory: neither)
+  if (!m_q || !I->m) {      // nothing can hit: no launch
+    if (d_hit_need) HIP_TRY(hipMemsetAsync(d_hit_need, 0, sizeof(uint64_t), s));
+    if (d_hit_off) HIP_TRY(hipMemsetAsync(d_hit_off, 0, (m_q + 1) * sizeof(uint64_t), s));
+    if (m_q) HIP_TRY(hipMemsetAsync(d_degree, 0, m_q * sizeof(uint32_t), s));
+    return DCRX_OK;
+  }
+  if ((uintptr_t)d_work % ALIGN) return fail("the work space is not 256-byte aligned");
+  Pool P(d_work);
+  Work W;
+  int rc = W.carve(P, m_q, metric);
+  if (rc) return rc;
+  if (work_bytes < P.bytes())
+    return fail(wc ? "the work space is smaller than dcrx_cdr3_match_weighted_work_bytes(m_q, text_bytes)"
+                   : "the work space is smaller than dcrx_cdr3_match_work_bytes(m_q, text_bytes, metric)");
+  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
+  const bool lev = wc || walks_lev(limit, metric);
+  if ((rc = run_degrees(*I, N, m_q, limit, lev, wc, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
+  if (!d_hit || !hit_cap) return DCRX_OK;
+  return run_write(*I, m_q, limit, lev, wc, d_hit_off, d_hit, d_hit_dist, hit_cap, W, s);
 }
 
 // what every entry refuses of (index, m_q, distance, metric)
@@ -475,18 +249,6 @@ int run_match(const dcrx_cdr3_index &I, uint64_t m, const uint32_t *cls, const u
       (rc = to_host(M.t_weight.data(), reinterpret_cast<const uint64_t *>(d_tw), mt))) return rc;
   if (wc && (rc = to_host(M.hit_dist.data(), d_dist.get(), need))) return rc;
   return DCRX_OK;
-}
-
-// the Levenshtein distance of two byte strings of any length (the matches file's column): a plain two-row table
-uint64_t host_levenshtein(const char *a, uint64_t la, const char *b, uint64_t lb) {
-  std::vector<uint64_t> prev(lb + 1), cur(lb + 1);
-  for (uint64_t j = 0; j <= lb; j++) prev[j] = j;
-  for (uint64_t i = 1; i <= la; i++) {
-    cur[0] = i;
-    for (uint64_t j = 1; j <= lb; j++) cur[j] = std::min({prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (a[i - 1] != b[j - 1] ? 1u : 0u)});
-    prev.swap(cur);
-  }
-  return prev[lb];
 }
 
 // what every weighted entry refuses of (cost, radius), on the host; the cost as the walk's launch argument
@@ -612,7 +374,7 @@ int64_t format_matches(const char *who, uint64_t m_q, const uint64_t *hit_off, c
           return fail("a hit between strings out of the weighted metric's reach");
         d = host_weighted(q_text + q_off[i], lq, t_text + t_off[j], lt, *cost);
       } else if (metric == METRIC_LEVENSHTEIN) {
-        d = host_levenshtein(q_text + q_off[i], lq, t_text + t_off[j], lt);
+        d = dcrx::host_levenshtein(q_text + q_off[i], lq, t_text + t_off[j], lt);
       } else {
         if (lq != lt) return fail("a hit between strings of two lengths");
         for (uint64_t p = 0; p < lq; p++) d += q_text[q_off[i] + p] != t_text[t_off[j] + p];
@@ -688,27 +450,8 @@ int dcrx_cdr3_match_device(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint3
   static const char who[] = "dcrx_cdr3_match_device";
   int rc = refuse(who, I, m_q, distance, metric);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (m_q && (!d_class || !d_off || !d_degree || !d_hit_off || !d_work || (text_bytes && !d_text) || (hit_cap && !d_hit)))
-    return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: null argument");
-  dcrx::DeviceGuard on(I->device);      // (the index's device for the launches, the caller's again behind them; no index memory: neither)
-  if (!m_q || !I->m) {      // nothing can hit: no launch
-    if (d_hit_need) HIP_TRY(hipMemsetAsync(d_hit_need, 0, sizeof(uint64_t), s));
-    if (d_hit_off) HIP_TRY(hipMemsetAsync(d_hit_off, 0, (m_q + 1) * sizeof(uint64_t), s));
-    if (m_q) HIP_TRY(hipMemsetAsync(d_degree, 0, m_q * sizeof(uint32_t), s));
-    return DCRX_OK;
-  }
-  if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: the work space is not 256-byte aligned");
-  Pool P(d_work);
-  Work W;
-  if ((rc = W.carve(P, m_q, metric))) return rc;
-  if (work_bytes < P.bytes())
-    return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_device: the work space is smaller than dcrx_cdr3_match_work_bytes(m_q, text_bytes, metric)");
-  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
-  const bool lev = walks_lev(distance, metric);
-  if ((rc = run_degrees(*I, N, m_q, distance, lev, nullptr, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
-  if (!d_hit || !hit_cap) return DCRX_OK;
-  return run_write(*I, m_q, distance, lev, nullptr, d_hit_off, d_hit, nullptr, hit_cap, W, s);
+  return match_device(who, I, m_q, d_class, d_off, d_text, text_bytes, distance, metric, nullptr, d_degree, d_hit_off, d_hit, nullptr, hit_cap,
+                      d_hit_need, d_work, work_bytes, (hipStream_t)hip_stream);
 } catch (const std::exception &e) {      // (a message that could not be built)
   return set_err(DCRX_E_NOMEM, e.what());
 }
@@ -788,27 +531,8 @@ int dcrx_cdr3_match_weighted_device(const dcrx_cdr3_index_t *I, uint64_t m_q, co
   CostArg wc;
   int rc = refuse(who, I, m_q, 0, METRIC_HAMMING);
   if (rc || (rc = refuse_cost(who, cost, radius, &wc))) return rc;
-  hipStream_t s = (hipStream_t)hip_stream;
-  if (m_q && (!d_class || !d_off || !d_degree || !d_hit_off || !d_work || (text_bytes && !d_text) || (hit_cap && !d_hit)))
-    return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_weighted_device: null argument");
-  dcrx::DeviceGuard on(I->device);
-  if (!m_q || !I->m) {      // nothing can hit: no launch
-    if (d_hit_need) HIP_TRY(hipMemsetAsync(d_hit_need, 0, sizeof(uint64_t), s));
-    if (d_hit_off) HIP_TRY(hipMemsetAsync(d_hit_off, 0, (m_q + 1) * sizeof(uint64_t), s));
-    if (m_q) HIP_TRY(hipMemsetAsync(d_degree, 0, m_q * sizeof(uint32_t), s));
-    return DCRX_OK;
-  }
-  if ((uintptr_t)d_work % ALIGN) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_weighted_device: the work space is not 256-byte aligned");
-  Pool P(d_work);
-  Work W;
-  if ((rc = W.carve(P, m_q, METRIC_HAMMING))) return rc;
-  if (work_bytes < P.bytes())
-    return set_err(DCRX_E_INVALID,
-                   "dcrx_cdr3_match_weighted_device: the work space is smaller than dcrx_cdr3_match_weighted_work_bytes(m_q, text_bytes)");
-  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
-  if ((rc = run_degrees(*I, N, m_q, radius, true, &wc, d_degree, d_hit_off, d_hit_need, W, s))) return rc;
-  if (!d_hit || !hit_cap) return DCRX_OK;
-  return run_write(*I, m_q, radius, true, &wc, d_hit_off, d_hit, d_hit_dist, hit_cap, W, s);
+  return match_device(who, I, m_q, d_class, d_off, d_text, text_bytes, radius, METRIC_HAMMING, &wc, d_degree, d_hit_off, d_hit, d_hit_dist,
+                      hit_cap, d_hit_need, d_work, work_bytes, (hipStream_t)hip_stream);
 } catch (const std::exception &e) {
   return set_err(DCRX_E_NOMEM, e.what());
 }

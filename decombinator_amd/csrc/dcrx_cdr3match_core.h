@@ -1,6 +1,7 @@
-// dcrx_cdr3match_core.h — the look-ups of the bipartite walk (`match`, dcrx_cdr3match.hip), shared by the kernel and a plain
-// host build (tests/host_cdr3match): a bucket of a key under either metric, where a block of sorted queries starts in the
-// index's sorted targets and at which bucket it stops, whether the walk goes on to a tile, and whether a wave skips one.
+// dcrx_cdr3match_core.h — the look-ups of the tile walk (dcrx_cdr3walk.h: `match` and the CDR3 network), shared by the kernel
+// and a plain host build (tests/host_cdr3match): a bucket of a key under either metric, where a block of sorted queries starts
+// in the sorted targets (the index's, or under the network its own table) and at which bucket it stops, whether the walk goes
+// on to a tile, and whether a wave skips one.
 // The per-node and per-pair code (keys, packed strings, Hamming and edit-distance tests) is dcrx_cdr3net_core.h's.
 #pragma once
 #include <stdint.h>
@@ -38,12 +39,24 @@ struct Range {
   uint32_t first;      // the first target at or above the block's first query's bucket
   uint64_t stop;       // the block's last query's bucket, or the last bucket in reach if that is smaller
 };
-template <bool LEV> DCRX_CDR3NET_HD Range block_range(const uint64_t *q_key, uint32_t n_q, uint32_t s0, const uint64_t *t_key, uint32_t n_t) {
+template <bool LEV> DCRX_CDR3NET_HD uint64_t block_stop(const uint64_t *q_key, uint32_t n_q, uint32_t s0) {
   const uint32_t last = (n_q - s0 < QUERIES ? n_q : s0 + QUERIES) - 1;
   const uint64_t k_last = bucket_of<LEV>(q_key[last]);
+  return k_last < last_bucket<LEV>() ? k_last : last_bucket<LEV>();
+}
+// two tables (`match`): the first target comes from a binary search over the index's sorted keys
+template <bool LEV> DCRX_CDR3NET_HD Range block_range(const uint64_t *q_key, uint32_t n_q, uint32_t s0, const uint64_t *t_key, uint32_t n_t) {
   Range r;
-  r.stop = k_last < last_bucket<LEV>() ? k_last : last_bucket<LEV>();
+  r.stop = block_stop<LEV>(q_key, n_q, s0);
   r.first = first_at_or_above<LEV>(t_key, n_t, bucket_of<LEV>(q_key[s0]));
+  return r;
+}
+// one table walked against itself (the network): bstart[s] is the start of sorted position s's bucket (the gather's run
+// marks, max-scanned), so the first entry is read, not searched
+template <bool LEV> DCRX_CDR3NET_HD Range within_range(const uint64_t *key, uint32_t n, uint32_t s0, const uint32_t *bstart) {
+  Range r;
+  r.stop = block_stop<LEV>(key, n, s0);
+  r.first = bstart[s0];
   return r;
 }
 template <bool LEV> DCRX_CDR3NET_HD bool goes_on(const Range &r, uint64_t tile_first_key) { return bucket_of<LEV>(tile_first_key) <= r.stop; }

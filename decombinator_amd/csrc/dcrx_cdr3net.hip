@@ -1,19 +1,17 @@
 // dcrx_cdr3net.hip — the CDR3 network (`--clonotypes --cdr3-network`): which nodes (clonotypes) of one class and one string
 // length lie within D substitutions of each other, and the connected components of that graph; include/dcrx.h holds the
-// contract, dcrx_cdr3net_core.h the per-node and per-pair code.
+// contract, dcrx_cdr3net_core.h the per-node and per-pair code, dcrx_cdr3walk.h the kernels that prepare and walk the table.
 //
 // The primitive (dcrx_cdr3_neighbours_device), all on the caller's stream and in the caller's work space:
-//   keys     cdr3net_keys_kernel, one lane per node: the bucket key (class, length), out of reach behind every bucket
+//   keys     cdr3_keys_kernel, one lane per node: the bucket key (class, length), out of reach behind every bucket
 //   sort     a stable radix sort of (key, rank): a bucket stays in rank order
-//   gather   cdr3net_gather_kernel, one lane per sorted position: the 32-byte packed string, and the run marks whose max scan
-//            gives every position its bucket's start
-//   degrees  cdr3net_walk_kernel<false>: a block of 256 consecutive sorted nodes walks the sorted entries from its first
-//            node's bucket start to its last node's bucket end in LDS tiles of 256 (8 KB of strings, 2 KB of keys, 1 KB of
-//            ranks); every lane of a wave reads the same staged entry (a broadcast), and a wave skips a tile whose key range
-//            misses its own.  Every node counts its OWN neighbours over its whole bucket: twice the comparisons of a
-//            triangular walk, but no atomics, and the neighbours come in ascending rank
+//   gather   cdr3_gather_kernel<true, LEV>, one lane per sorted position: the 32-byte packed string, and the run marks whose
+//            max scan gives every position its bucket's start
+//   degrees  cdr3_walk_kernel<false, Within, Pair>: the table walked against itself, a block of 256 consecutive sorted nodes
+//            from its first node's bucket start to its last node's bucket end.  Every node counts its OWN neighbours over its
+//            whole bucket: twice the comparisons of a triangular walk, but no atomics, and the neighbours come in ascending rank
 //   scan     an exclusive sum of the degrees in rank order: adj_off, whose end is the need
-//   write    cdr3net_walk_kernel<true>: the same walk writes every neighbour's rank at its exact offset
+//   write    cdr3_walk_kernel<true, Within, Pair>: the same walk writes every neighbour's rank at its exact offset
 // The host entry (dcrx_cdr3_network) runs those two halves around the adjacency's allocation, then the components (rounds of
 // "the smallest label among my neighbours and me" and pointer jumping, double buffered, until a round changes nothing) and
 // the totals (integer atomics onto the heads, results unused; the heads compacted in rank order).
@@ -21,8 +19,8 @@
 //
 // Under the Levenshtein metric (the *_metric entries, DCRX_CDR3NET_LEVENSHTEIN) the bucket is the class alone: the same keys
 // are sorted over their class bits and the out-of-reach bit only — stable, so a class stays in rank order and the sorted keys
-// keep every node's length —, the gather also leaves a letter-presence mask per node, and the walk (the LEV forms of the same
-// kernels) tests a pair by class, length difference, presence masks and then lev_within (on the entry a lane has waiting,
+// keep every node's length —, the gather also leaves a letter-presence mask per node, and the walk (Pair is Levenshtein, not
+// Hamming) tests a pair by class, length difference, presence masks and then lev_within (on the entry a lane has waiting,
 // once some lane of the wave meets its next one).  A node still walks its whole bucket, now its class: the extra pairs fall
 // at one length compare, and the neighbours still come in ascending rank.
 #include <hip/hip_runtime.h>
@@ -34,166 +32,13 @@
 #include <vector>
 
 #include "../../include/dcrx.h"
-#include "dcrx_cdr3net_core.h"
-#include "dcrx_group.h"
+#include "dcrx_cdr3walk.h"
 #include "dcrx_text.h"
 
 using dcrx::set_err;
-using namespace dcrx_cdr3net;
-using namespace dcrx_group;
+using namespace dcrx_cdr3walk;
 
 namespace {
-
-constexpr uint64_t MAX_NODES = 1ull << 30;
-constexpr int TILE = 256;        // staged entries per step
-constexpr uint32_t NO_ENTRY = 0xFFFFFFFFu;
-
-struct Nodes {
-  const uint32_t *cls;
-  const uint64_t *off;
-  const uint8_t *text;
-  uint64_t text_bytes;
-};
-
-// the length of node e's string; one past the reach for offsets that go backwards or leave the text
-__device__ __forceinline__ uint64_t node_len(const Nodes &N, uint32_t e, uint64_t *at) {
-  const uint64_t a = N.off[e], b = N.off[e + 1];
-  *at = a;
-  return (b < a || b > N.text_bytes) ? (uint64_t)MAX_LEN + 1 : b - a;
-}
-
-__global__ __launch_bounds__(BLOCK) void cdr3net_keys_kernel(Nodes N, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
-  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
-  if (e >= n) return;
-  uint64_t at;
-  key[e] = node_key(N.cls[e], node_len(N, e, &at));
-  idx[e] = e;
-}
-
-// the key a bucket is made of: the whole key, or under the Levenshtein metric its class (and out-of-reach) bits
-template <bool LEV> __device__ __forceinline__ uint64_t bucket_of(uint64_t key) { return LEV ? key_class(key) : key; }
-
-// LEV: the run marks are the classes', and every node's letter-presence mask goes beside its string
-template <bool LEV>
-__global__ __launch_bounds__(BLOCK) void cdr3net_gather_kernel(Nodes N, uint32_t n, const uint64_t *__restrict__ key,
-                                                               const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
-                                                               uint32_t *__restrict__ mark, uint32_t *__restrict__ pres) {
-  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-  if (s >= n) return;
-  const uint32_t e = idx[s];
-  uint64_t at;
-  const uint64_t len = node_len(N, e, &at);
-  uint32_t w[WORDS];
-  pack(N.text + (in_reach(len) ? at : 0), len, w);
-  sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
-  sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-  mark[s] = run_mark(s, [&](uint32_t k) { return bucket_of<LEV>(key[k]); });
-  if (LEV) pres[s] = presence(w, in_reach(len) ? (uint32_t)len : 0u);
-}
-
-// The walk.  WRITE false: degree[rank] (and the same as 64 bits, for the scan); true: the neighbours' ranks at adj_off[rank].
-// LEV: the buckets are the classes (the staged keys still hold the lengths), the presence masks are staged with the strings,
-// and a pair is tested by length difference, presence masks and lev_within instead of the Hamming distance.
-template <bool WRITE, bool LEV>
-__global__ __launch_bounds__(BLOCK) void cdr3net_walk_kernel(const uint4 *__restrict__ sj, const uint64_t *__restrict__ key,
-                                                             const uint32_t *__restrict__ idx, const uint32_t *__restrict__ bstart,
-                                                             uint32_t n, uint32_t limit, uint32_t *__restrict__ degree,
-                                                             uint64_t *__restrict__ deg64, const uint64_t *__restrict__ adj_off,
-                                                             uint32_t *__restrict__ adj, uint64_t adj_cap,
-                                                             const uint32_t *__restrict__ pres) {
-  __shared__ uint4 lds_j[TILE * 2];
-  __shared__ uint64_t lds_k[TILE];
-  __shared__ uint32_t lds_r[TILE];
-  __shared__ uint32_t lds_p[LEV ? TILE : 1];
-  const uint32_t s0 = blockIdx.x * BLOCK;
-  const uint32_t s = s0 + threadIdx.x;
-  const bool valid = s < n;
-  const uint64_t key_own = valid ? key[s] : KEY_OUT_OF_REACH;
-  const bool reach = key_own != KEY_OUT_OF_REACH;
-  const uint64_t k_own = bucket_of<LEV>(key_own);
-  const uint32_t len_own = key_length(key_own), pres_own = LEV && valid ? pres[s] : 0u;
-  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t e = 0, count = 0;
-  uint64_t at = 0;
-  if (valid) {
-    e = idx[s];
-    if (WRITE) at = adj_off[e];
-    if (reach) {
-      const uint4 a = sj[2 * (size_t)s], b = sj[2 * (size_t)s + 1];
-      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
-    }
-  }
-  // the wave's keys (sorted along s; lanes behind the table hold the largest key)
-  const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
-  // the block's entries: from its first node's bucket start to its last node's bucket end, nodes out of reach left out
-  const uint64_t k_max = min(bucket_of<LEV>(key[min(n, s0 + (uint32_t)BLOCK) - 1]), bucket_of<LEV>(KEY_OUT_OF_REACH) - 1);
-  for (uint32_t t = bstart[s0]; t < n; t += TILE) {
-    if (bucket_of<LEV>(key[t]) > k_max) break;              // (the same for every lane of the block)
-    __syncthreads();                                        // the previous tile is no longer read
-    const uint32_t tile_n = min((uint32_t)TILE, n - t);
-    if (threadIdx.x < tile_n) {
-      const uint32_t p = t + threadIdx.x;
-      lds_j[2 * threadIdx.x] = sj[2 * (size_t)p];
-      lds_j[2 * threadIdx.x + 1] = sj[2 * (size_t)p + 1];
-      lds_k[threadIdx.x] = key[p];
-      if (WRITE) lds_r[threadIdx.x] = idx[p];
-      if (LEV) lds_p[threadIdx.x] = pres[p];
-    }
-    __syncthreads();
-    if (bucket_of<LEV>(lds_k[tile_n - 1]) < w_lo || bucket_of<LEV>(lds_k[0]) > w_hi) continue;      // the tile holds nothing of this wave's buckets
-    const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
-    if (!LEV) {
-      for (uint32_t q = 0; q < tile_n; q++) {
-        const uint64_t kq = lds_k[q];
-        if (kq < w_lo) continue;
-        if (kq > w_hi) break;
-        if (reach && kq == k_own && t + q != s && distance(own, lj + q * WORDS, limit) <= limit) {
-          if (WRITE && at + count < adj_cap) adj[at + count] = lds_r[q];
-          count++;
-        }
-      }
-      continue;
-    }
-    // LEV: an entry that passes the cheap tests waits in `pending` (one per lane), and lev_within runs — for every lane that
-    // has one waiting, each on its own entry — only once some lane meets its next one, and at the tile's end: the few lanes
-    // of a wave that pass at one entry would otherwise run it nearly alone.  A lane still takes its entries in order.
-    uint32_t pending = NO_ENTRY;
-    auto settle = [&]() {
-      if (pending != NO_ENTRY) {
-        if (lev_within(own, len_own, lj + pending * WORDS, key_length(lds_k[pending]), limit) <= limit) {
-          if (WRITE && at + count < adj_cap) adj[at + count] = lds_r[pending];
-          count++;
-        }
-        pending = NO_ENTRY;
-      }
-    };
-    for (uint32_t q = 0; q < tile_n; q++) {
-      const uint64_t key_q = lds_k[q], kq = key_class(key_q);
-      if (kq < w_lo) continue;
-      if (kq > w_hi) break;
-      const uint32_t len_q = key_length(key_q);
-      const bool passes = reach && kq == k_own && t + q != s && len_q + limit >= len_own && len_own + limit >= len_q &&
-                          presence_allows(pres_own, lds_p[q], limit);
-      if (__any(passes && pending != NO_ENTRY)) settle();      // (the same for every lane of the wave)
-      if (passes) pending = q;
-    }
-    settle();      // (the next tile overwrites the staged entries)
-  }
-  if (valid && !WRITE) {
-    degree[e] = count;
-    deg64[e] = count;
-  }
-}
-
-// adj_off[m] and the need behind the scan
-__global__ void cdr3net_need_kernel(const uint64_t *__restrict__ deg64, uint64_t *__restrict__ adj_off, uint32_t n,
-                                    uint64_t *__restrict__ need) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const uint64_t total = adj_off[n - 1] + deg64[n - 1];
-    adj_off[n] = total;
-    if (need) *need = total;
-  }
-}
 
 // ---- the host entry's kernels ----
 
@@ -255,8 +100,6 @@ __global__ __launch_bounds__(BLOCK) void cdr3net_cluster_of_kernel(const uint32_
   if (i < n) cluster_of[i] = slot[label[i]];
 }
 
-bool metric_exists(uint32_t metric) { return metric == METRIC_HAMMING || metric == METRIC_LEVENSHTEIN; }
-
 // ---- work space of the primitive: the degree pass leaves the sorted keys and ranks (key[1], idx[1]), the bucket starts, the
 // packed strings and the presence masks there for the write pass
 struct Work {
@@ -278,44 +121,32 @@ struct Work {
     if (metric == METRIC_LEVENSHTEIN) P.get(&pres, n);
     return DCRX_OK;
   }
+  Sorted nodes(uint64_t n) const { return Sorted{key[1], idx[1], sj, pres, (uint32_t)n}; }
 };
 
-// keys, sort, gather, the degree pass, the scan and the need
+// keys, sort, gather, the bucket starts, the degree pass, the scan and the need
 int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint64_t *d_need,
                 const Work &W, hipStream_t s) {
   const bool lev = metric == METRIC_LEVENSHTEIN;
   const uint32_t n32 = (uint32_t)n;
   int rc;
-  cdr3net_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[0], W.idx[0]);
+  if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, lev ? (int)LEN_BITS : 0, true, s))) return rc;
+  if (lev) cdr3_gather_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, W.pres);
+  else cdr3_gather_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, nullptr);
   HIP_TRY(hipGetLastError());
-  if ((rc = sort_pairs(W.cub, W.key[0], W.key[1], W.idx[0], W.idx[1], n, KEY_BITS, s, lev ? (int)LEN_BITS : 0))) return rc;
-  if (lev) cdr3net_gather_kernel<true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, W.pres);
-  else cdr3net_gather_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = run_heads(W.cub, W.mark, W.bstart, n, s))) return rc;
-  if (lev)
-    cdr3net_walk_kernel<false, true><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, n32, limit, d_degree, W.deg64, nullptr,
-                                                                   nullptr, 0, W.pres);
-  else
-    cdr3net_walk_kernel<false, false><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, n32, limit, d_degree, W.deg64, nullptr,
-                                                                    nullptr, 0, nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = exclusive_sum(W.cub, W.deg64, d_adj_off, n, s))) return rc;
-  cdr3net_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_adj_off, n32, d_need);
+  const Sorted X = W.nodes(n);
+  if ((rc = run_heads(W.cub, W.mark, W.bstart, n, s)) ||
+      (rc = walk<false>(X, X, Within{W.bstart}, limit, lev, Out{d_degree, W.deg64, nullptr, nullptr, nullptr, 0}, s)) ||
+      (rc = exclusive_sum(W.cub, W.deg64, d_adj_off, n, s))) return rc;
+  cdr3_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_adj_off, n32, d_need);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
 
 int run_write(uint64_t n, uint32_t limit, uint32_t metric, const uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, const Work &W,
               hipStream_t s) {
-  if (metric == METRIC_LEVENSHTEIN)
-    cdr3net_walk_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, (uint32_t)n, limit, nullptr, nullptr,
-                                                                  d_adj_off, d_adj, adj_cap, W.pres);
-  else
-    cdr3net_walk_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(W.sj, W.key[1], W.idx[1], W.bstart, (uint32_t)n, limit, nullptr, nullptr,
-                                                                   d_adj_off, d_adj, adj_cap, nullptr);
-  HIP_TRY(hipGetLastError());
-  return DCRX_OK;
+  const Sorted X = W.nodes(n);
+  return walk<true>(X, X, Within{W.bstart}, limit, metric == METRIC_LEVENSHTEIN, Out{nullptr, nullptr, d_adj_off, d_adj, nullptr, adj_cap}, s);
 }
 
 // an error of the entry `who` (the plain entries and their *_metric forms share one body and name themselves)
@@ -448,18 +279,6 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
   return set_err(DCRX_E_NOMEM, e.what());
 }
 
-// the Levenshtein distance of two byte strings of any length (the edge file's column): a plain two-row table
-uint64_t host_levenshtein(const char *a, uint64_t la, const char *b, uint64_t lb) {
-  std::vector<uint64_t> prev(lb + 1), cur(lb + 1);
-  for (uint64_t j = 0; j <= lb; j++) prev[j] = j;
-  for (uint64_t i = 1; i <= la; i++) {
-    cur[0] = i;
-    for (uint64_t j = 1; j <= lb; j++) cur[j] = std::min({prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (a[i - 1] != b[j - 1] ? 1u : 0u)});
-    prev.swap(cur);
-  }
-  return prev[lb];
-}
-
 int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
                      uint32_t metric, char *out, uint64_t out_cap) try {
   static const char header[] = "a\tb\tdistance\n";
@@ -476,7 +295,7 @@ int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const
       const uint64_t la = off[a + 1] - off[a], lb = off[b + 1] - off[b];
       unsigned long long d = 0;
       if (metric == METRIC_LEVENSHTEIN) {
-        d = host_levenshtein(text + off[a], la, text + off[b], lb);
+        d = dcrx::host_levenshtein(text + off[a], la, text + off[b], lb);
       } else {
         if (la != lb) return fail(DCRX_E_INVALID, who, "an edge between strings of two lengths");
         for (uint64_t p = 0; p < la; p++) d += text[off[a] + p] != text[off[b] + p];

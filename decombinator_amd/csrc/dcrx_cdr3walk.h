@@ -1,0 +1,305 @@
+// dcrx_cdr3walk.h — the tile walk over sorted CDR3 tables and the steps that prepare a table for it, written once for the
+// CDR3 network (dcrx_cdr3net.hip), `match` and its weighted metric (dcrx_cdr3match.hip).  Private to those two translation
+// units (HIP only, internal linkage, as dcrx_group.h: a unit's instances of the kernels are its own).
+//
+// Prepare: cdr3_keys_kernel (the key of every node), a stable radix sort of (key, rank) in the walk's bucket order
+// (sorted_keys), cdr3_gather_kernel (per sorted position the packed string, and on demand the run mark and the presence mask).
+// Walk: cdr3_walk_kernel<WRITE, Side, Pair>.  A block of 256 consecutive sorted nodes of Q, one per lane and in registers,
+// walks the sorted entries of T from its first node's bucket to its last node's in LDS tiles of 256 (8 KB of strings, 2 KB of
+// keys, 1 KB of ranks in the write pass, 1 KB of masks where the pair test reads them); every lane of a wave reads the same
+// staged entry (a broadcast), and a wave skips a tile whose buckets miss its own.  A bucket's entries are in rank order, so a
+// node's hits come in ascending rank with no atomics: the degree pass (WRITE false) counts them, an exclusive sum in rank order
+// gives the offsets (cdr3_need_kernel closes them), and the write pass (WRITE true) walks again and writes every hit at its
+// exact place.
+// Side says which entries a block walks and whether an entry is the lane's own node: Bipartite (two tables) or Within (one
+// table against itself).  Pair is the pair test: Hamming, Levenshtein or Weighted.
+// The per-node and per-pair code is dcrx_cdr3net_core.h's and dcrx_cdr3w_core.h's, the look-ups are dcrx_cdr3match_core.h's.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "dcrx_cdr3match_core.h"
+#include "dcrx_cdr3w_core.h"
+#include "dcrx_group.h"
+
+namespace dcrx_cdr3walk {
+namespace {
+
+using namespace dcrx_cdr3match;
+using namespace dcrx_cdr3w;
+using namespace dcrx_group;
+
+constexpr uint64_t MAX_NODES = 1ull << 30;
+constexpr uint32_t NO_ENTRY = 0xFFFFFFFFu;
+static_assert(BLOCK == (int)QUERIES && BLOCK == (int)TILE, "a lane holds one node and stages one entry");
+
+inline bool metric_exists(uint32_t metric) { return metric == METRIC_HAMMING || metric == METRIC_LEVENSHTEIN; }
+
+struct Nodes {
+  const uint32_t *cls;
+  const uint64_t *off;
+  const uint8_t *text;
+  uint64_t text_bytes;
+};
+
+// one table in one bucket order: the sorted keys, the ranks, the packed strings and (class order) the presence masks
+struct Sorted {
+  const uint64_t *key;
+  const uint32_t *idx;
+  const uint4 *sj;
+  const uint32_t *pres;
+  uint32_t n;
+};
+
+// what a walk leaves, by rank of Q: the degree pass degree and deg64 (the same as 64 bits, for the scan), the write pass the
+// hits' ranks — and their distances, where the pair test stores one and dist is not null — at off[rank], below cap
+struct Out {
+  uint32_t *degree;
+  uint64_t *deg64;
+  const uint64_t *off;
+  uint32_t *hit, *dist;
+  uint64_t cap;
+};
+
+// the length of node e's string; one past the reach for offsets that go backwards or leave the text
+__device__ __forceinline__ uint64_t node_len(const Nodes &N, uint32_t e, uint64_t *at) {
+  const uint64_t a = N.off[e], b = N.off[e + 1];
+  *at = a;
+  return (b < a || b > N.text_bytes) ? (uint64_t)MAX_LEN + 1 : b - a;
+}
+
+__global__ __launch_bounds__(BLOCK) void cdr3_keys_kernel(Nodes N, uint32_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
+  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= n) return;
+  uint64_t at;
+  key[e] = node_key(N.cls[e], node_len(N, e, &at));
+  idx[e] = e;
+}
+
+// keys of n nodes, then their stable sort over the key's bits from begin_bit (0: by (class, length); LEN_BITS: by class, the
+// sorted keys keep the lengths): (key[1], idx[1])
+inline int sorted_keys(const Nodes &N, uint64_t n, uint64_t *const key[2], uint32_t *const idx[2], Scratch cub, int begin_bit, bool make_keys,
+                       hipStream_t s) {
+  if (make_keys) {
+    cdr3_keys_kernel<<<grid_for(n), BLOCK, 0, s>>>(N, (uint32_t)n, key[0], idx[0]);
+    HIP_TRY(hipGetLastError());
+  }
+  return sort_pairs(cub, key[0], key[1], idx[0], idx[1], n, KEY_BITS, s, begin_bit);
+}
+
+// per sorted position the packed string; MARKS: the run mark of its bucket, whose max scan gives every position its bucket's
+// start; PRES: the table is in class order (the marks are the classes'), and its letter-presence mask goes beside the string
+template <bool MARKS, bool PRES>
+__global__ __launch_bounds__(BLOCK) void cdr3_gather_kernel(Nodes N, uint32_t n, const uint64_t *__restrict__ key,
+                                                            const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
+                                                            uint32_t *__restrict__ mark, uint32_t *__restrict__ pres) {
+  const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= n) return;
+  uint64_t at;
+  const uint64_t len = node_len(N, idx[s], &at);
+  uint32_t w[WORDS];
+  pack(N.text + (in_reach(len) ? at : 0), len, w);
+  sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
+  sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+  if (MARKS) mark[s] = run_mark(s, [&](uint32_t k) { return bucket_of<PRES>(key[k]); });
+  if (PRES) pres[s] = presence(w, in_reach(len) ? (uint32_t)len : 0u);
+}
+
+// off[n] and the need behind the scan
+__global__ void cdr3_need_kernel(const uint64_t *__restrict__ deg64, uint64_t *__restrict__ off, uint32_t n, uint64_t *__restrict__ need) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint64_t total = off[n - 1] + deg64[n - 1];
+    off[n] = total;
+    if (need) *need = total;
+  }
+}
+
+// ---- the two sides: range() is the same for every lane of a block
+
+// Q's nodes against another table's entries
+struct Bipartite {
+  template <bool CLS> __device__ __forceinline__ Range range(const Sorted &Q, const Sorted &T, uint32_t s0) const {
+    return block_range<CLS>(Q.key, Q.n, s0, T.key, T.n);
+  }
+  __device__ __forceinline__ bool self(uint32_t, uint32_t) const { return false; }
+};
+
+// a table against itself (Q and T are one): from the block's first node's bucket start, and a node is no neighbour of its own
+struct Within {
+  const uint32_t *bstart;
+  template <bool CLS> __device__ __forceinline__ Range range(const Sorted &Q, const Sorted &, uint32_t s0) const {
+    return within_range<CLS>(Q.key, Q.n, s0, bstart);
+  }
+  __device__ __forceinline__ bool self(uint32_t p, uint32_t s) const { return p == s; }
+};
+
+// ---- the three pair tests.  CLS: the bucket is the class alone (else class and length).  MASKS: the presence masks are
+// staged and handed to window().  DEFER: an entry that passes window() waits, and test() runs on it later (see the walk).
+// DIST: test()'s value is stored beside the hit.  begin() runs once per lane in front of the walk and returns what window()
+// and test() are handed back; admits(): whether the lane's own node takes part at all; staged(): the key a staged entry gets
+// (its two uint4 in hand); window(): the cheap tests of a pair of one bucket; test(): the distance, a hit when <= bound().
+
+struct Hamming {
+  static constexpr bool CLS = false, MASKS = false, DEFER = false, DIST = false;
+  uint32_t limit;
+  struct Ctx {};
+  __device__ __forceinline__ Ctx begin() const { return Ctx{}; }
+  __device__ __forceinline__ bool admits(const uint32_t *, uint32_t) const { return true; }
+  __device__ __forceinline__ uint64_t staged(const uint4 &, const uint4 &, uint64_t key) const { return key; }
+  __device__ __forceinline__ bool window(const Ctx &, uint32_t, uint32_t, uint32_t, uint32_t) const { return true; }      // (one bucket: one length)
+  __device__ __forceinline__ uint32_t test(const Ctx &, const uint32_t *own, uint32_t, const uint32_t *other, uint32_t) const {
+    return distance(own, other, limit);
+  }
+  __device__ __forceinline__ uint32_t bound() const { return limit; }
+};
+
+struct Levenshtein {
+  static constexpr bool CLS = true, MASKS = true, DEFER = true, DIST = false;
+  uint32_t limit;
+  struct Ctx {};
+  __device__ __forceinline__ Ctx begin() const { return Ctx{}; }
+  __device__ __forceinline__ bool admits(const uint32_t *, uint32_t) const { return true; }
+  __device__ __forceinline__ uint64_t staged(const uint4 &, const uint4 &, uint64_t key) const { return key; }
+  __device__ __forceinline__ bool window(const Ctx &, uint32_t len_own, uint32_t pres_own, uint32_t len, uint32_t pres) const {
+    return len + limit >= len_own && len_own + limit >= len && presence_allows(pres_own, pres, limit);
+  }
+  __device__ __forceinline__ uint32_t test(const Ctx &, const uint32_t *own, uint32_t len_own, const uint32_t *other, uint32_t len) const {
+    return lev_within(own, len_own, other, len, limit);
+  }
+  __device__ __forceinline__ uint32_t bound() const { return limit; }
+};
+
+// the cost as the weighted walk's launch argument: the table as the 256 dwords the block's lanes copy into LDS, one each
+struct CostArg {
+  uint32_t sub[SUB_BYTES / 4];
+  uint32_t gap, ntrim, ctrim;
+};
+static_assert(SUB_BYTES / 4 == BLOCK, "a lane stages one dword of the cost table");
+
+// The class, the length window |la - lb| * gap <= radius, then weighted_within.  A string with a non-letter takes part in
+// nothing: such a node is not admitted, and the lane that stages such an entry stages a key of length 0, which no lane tests.
+// The presence masks are not read (a substitution may cost nothing).  A pair is tested where it is met: at such radii most
+// pairs of a class pass the window, so there is nothing for the pending / settle scheme to collect.
+struct Weighted {
+  static constexpr bool CLS = true, MASKS = false, DEFER = false, DIST = true;
+  CostArg cost;
+  uint32_t radius;
+  using Ctx = Cost;
+  __device__ __forceinline__ Cost begin() const {
+    __shared__ uint32_t lds_sub[SUB_BYTES / 4];
+    lds_sub[threadIdx.x] = cost.sub[threadIdx.x];      // (the walk's first barrier stands before its first read)
+    return Cost{reinterpret_cast<const uint8_t *>(lds_sub), cost.gap, cost.ntrim, cost.ctrim};
+  }
+  __device__ __forceinline__ bool admits(const uint32_t *own, uint32_t len_own) const { return letters_only(own, len_own); }
+  __device__ __forceinline__ uint64_t staged(const uint4 &a, const uint4 &b, uint64_t key) const {
+    const uint32_t w[WORDS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    return letters_only(w, key_length(key)) ? key : key & ~LEN_MASK;      // (the class stays: the tile stays sorted)
+  }
+  __device__ __forceinline__ bool window(const Cost &C, uint32_t len_own, uint32_t, uint32_t len, uint32_t) const {
+    const uint32_t apart = len > len_own ? len - len_own : len_own - len;
+    return len != 0 && apart * C.gap <= radius;      // (0: an entry with a non-letter, or out of reach)
+  }
+  __device__ __forceinline__ uint32_t test(const Cost &C, const uint32_t *own, uint32_t len_own, const uint32_t *other, uint32_t len) const {
+    return weighted_within(own, len_own, reinterpret_cast<const uint8_t *>(other), len, C, radius);
+  }
+  __device__ __forceinline__ uint32_t bound() const { return radius; }
+};
+
+// The walk (see the head of the file).  Q: the block's nodes, T: the entries it walks, both sorted in Pair's bucket order.
+template <bool WRITE, class Side, class Pair>
+__global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Side side, Pair pair, Out O) {
+  constexpr bool CLS = Pair::CLS;
+  __shared__ uint4 lds_j[TILE * 2];
+  __shared__ uint64_t lds_k[TILE];
+  __shared__ uint32_t lds_r[WRITE ? TILE : 1];
+  __shared__ uint32_t lds_p[Pair::MASKS ? TILE : 1];
+  const typename Pair::Ctx ctx = pair.begin();
+  const uint32_t s0 = blockIdx.x * BLOCK;
+  const uint32_t s = s0 + threadIdx.x;
+  const bool valid = s < Q.n;
+  const uint64_t key_own = valid ? Q.key[s] : KEY_OUT_OF_REACH;
+  bool reach = key_own != KEY_OUT_OF_REACH;
+  const uint64_t k_own = bucket_of<CLS>(key_own);
+  const uint32_t len_own = key_length(key_own), pres_own = Pair::MASKS && valid ? Q.pres[s] : 0u;
+  uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t e = 0, count = 0;
+  uint64_t at = 0;
+  if (valid) {
+    e = Q.idx[s];
+    if (WRITE) at = O.off[e];
+    if (reach) {
+      const uint4 a = Q.sj[2 * (size_t)s], b = Q.sj[2 * (size_t)s + 1];
+      own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
+      reach = pair.admits(own, len_own);
+    }
+  }
+  // the wave's buckets (sorted along s; lanes behind the table hold the largest)
+  const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
+  const Range R = side.template range<CLS>(Q, T, s0);
+  for (uint32_t t = R.first; t < T.n; t += TILE) {
+    if (!goes_on<CLS>(R, T.key[t])) break;
+    __syncthreads();                                        // the previous tile is no longer read
+    const uint32_t tile_n = min((uint32_t)TILE, T.n - t);
+    if (threadIdx.x < tile_n) {
+      const uint32_t p = t + threadIdx.x;
+      const uint4 a = T.sj[2 * (size_t)p], b = T.sj[2 * (size_t)p + 1];
+      lds_j[2 * threadIdx.x] = a;
+      lds_j[2 * threadIdx.x + 1] = b;
+      lds_k[threadIdx.x] = pair.staged(a, b, T.key[p]);
+      if (WRITE) lds_r[threadIdx.x] = T.idx[p];
+      if (Pair::MASKS) lds_p[threadIdx.x] = T.pres[p];
+    }
+    __syncthreads();
+    if (wave_skips(bucket_of<CLS>(lds_k[0]), bucket_of<CLS>(lds_k[tile_n - 1]), w_lo, w_hi)) continue;
+    const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
+    auto take = [&](uint32_t q, uint32_t len_q) __attribute__((always_inline)) {
+      const uint32_t d = pair.test(ctx, own, len_own, lj + q * WORDS, len_q);
+      if (d <= pair.bound()) {
+        if (WRITE && at + count < O.cap) {
+          O.hit[at + count] = lds_r[q];
+          if (Pair::DIST && O.dist) O.dist[at + count] = d;
+        }
+        count++;
+      }
+    };
+    // DEFER: an entry that passes the cheap tests waits in `pending` (one per lane), and the test runs — for every lane that
+    // has one waiting, each on its own entry — only once some lane meets its next one, and at the tile's end: the few lanes
+    // of a wave that pass at one entry would otherwise run it nearly alone.  A lane still takes its entries in order.
+    uint32_t pending = NO_ENTRY;
+    auto settle = [&]() __attribute__((always_inline)) {
+      if (pending != NO_ENTRY) {      // (per lane: the vote below is the wave's, what waits is the lane's)
+        take(pending, key_length(lds_k[pending]));
+        pending = NO_ENTRY;
+      }
+    };
+    for (uint32_t q = 0; q < tile_n; q++) {
+      const uint64_t key_q = lds_k[q], kq = bucket_of<CLS>(key_q);
+      if (kq < w_lo) continue;
+      if (kq > w_hi) break;
+      const uint32_t len_q = key_length(key_q);
+      const bool passes = reach && kq == k_own && !side.self(t + q, s) && pair.window(ctx, len_own, pres_own, len_q, Pair::MASKS ? lds_p[q] : 0u);
+      if (Pair::DEFER) {
+        if (__any(passes && pending != NO_ENTRY)) settle();      // (the same for every lane of the wave)
+        if (passes) pending = q;
+      } else if (passes) {
+        take(q, len_q);
+      }
+    }
+    if (Pair::DEFER) settle();      // (the next tile overwrites the staged entries)
+  }
+  if (valid && !WRITE) {
+    O.degree[e] = count;
+    O.deg64[e] = count;
+  }
+}
+
+// one pass under the Hamming metric, or (lev) the Levenshtein metric at a distance above 0
+template <bool WRITE, class Side> int walk(const Sorted &Q, const Sorted &T, Side side, uint32_t limit, bool lev, const Out &O, hipStream_t s) {
+  if (lev) cdr3_walk_kernel<WRITE><<<grid_for(Q.n), BLOCK, 0, s>>>(Q, T, side, Levenshtein{limit}, O);
+  else cdr3_walk_kernel<WRITE><<<grid_for(Q.n), BLOCK, 0, s>>>(Q, T, side, Hamming{limit}, O);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
+}  // namespace
+}  // namespace dcrx_cdr3walk

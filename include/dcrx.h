@@ -1157,7 +1157,7 @@ uint64_t dcrx_cdr3_match_work_bytes(uint64_t m_q, uint64_t text_bytes, uint32_t 
  * otherwise (an entry beyond hit_cap is dropped), so a caller that finds *d_hit_need > hit_cap calls again with a larger one
  * (d_hit may be NULL with hit_cap 0 to size it).
  * The steps: the queries are prepared as the network prepares its nodes (keys, a stable radix sort of (key, rank), the
- * packed strings gathered in sorted order, presence masks under Levenshtein); then cdr3match_walk_kernel: a block holds 256
+ * packed strings gathered in sorted order, presence masks under Levenshtein); then cdr3_walk_kernel (Bipartite): a block holds 256
  * sorted queries in registers, finds the first target at or above its first query's bucket by a binary search over the
  * index's sorted keys, and stages the targets from there in LDS tiles of 256 until the staged bucket passes its last query's
  * bucket; a wave skips a tile that holds none of its buckets; the targets of a bucket are in rank order, so a query's hits
@@ -1243,7 +1243,7 @@ uint64_t dcrx_cdr3_match_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes);
  * and copies it (it travels to the kernels as a launch argument), so the caller may release it on return.  d_hit_dist
  * (hit_cap entries, device) receives every written hit's distance beside d_hit; it may be NULL.
  * The steps: keys, the stable sort by class and the gather of the queries as under Levenshtein (no presence masks: a
- * substitution may cost anything from 0 to 255, so they filter nothing), then cdr3match_wwalk_kernel: the Levenshtein walk's
+ * substitution may cost anything from 0 to 255, so they filter nothing), then cdr3_walk_kernel with the Weighted pair test: the Levenshtein walk's
  * blocks, tiles and wave skip over the index's class-order arrays; the block stages the 1 KB cost table in LDS once; the
  * lane that stages a target tests it for letters and marks the staged key (length 0) so that no lane tests it; a lane
  * tests the class, then the length window |la - lb| * gap <= R, then weighted_within (csrc/dcrx_cdr3w_core.h), pair by pair

@@ -1,4 +1,4 @@
-// Test-only: the bipartite walk of `match` (decombinator_amd/csrc/dcrx_cdr3match.hip) step by step on the host, with the
+// Test-only: the bipartite walk of `match` (cdr3_walk_kernel with the Bipartite side, decombinator_amd/csrc/dcrx_cdr3walk.h) step by step on the host, with the
 // kernel's own look-ups (dcrx_cdr3match_core.h: block range, tile test, wave skip) and pair tests (dcrx_cdr3net_core.h): keys,
 // a stable sort of (key, rank) on either side, packed strings and presence masks, then per block of 256 sorted queries the
 // tiles of 256 targets, per wave of 64 lanes the skip, per lane the pair test.  Every array access is a std::vector::at().

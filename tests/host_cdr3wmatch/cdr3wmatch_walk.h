@@ -1,4 +1,4 @@
-// Test-only: the weighted walk of `match` (cdr3match_wwalk_kernel, decombinator_amd/csrc/dcrx_cdr3match.hip) step by step on the
+// Test-only: the weighted walk of `match` (cdr3_walk_kernel with the Weighted pair test, decombinator_amd/csrc/dcrx_cdr3walk.h) step by step on the
 // host, with the kernel's own look-ups (dcrx_cdr3match_core.h) and pair test (dcrx_cdr3w_core.h): keys, a stable sort of
 // (key, rank) by class on either side, packed strings, then per block of 256 sorted queries the tiles of 256 targets with the letters test at staging, per wave
 // of 64 lanes the skip, per lane the class, the length window and weighted_within.  Every array access is a

@@ -11,6 +11,7 @@ import pytest
 
 from decombinator_amd import _native as nat
 from decombinator_amd import pipeline
+from tests import cdr3_lev_util as lu
 from tests import cdr3_match_util as mu
 from tests import cdr3_network_util as cnu
 
@@ -103,6 +104,85 @@ def test_classes_that_differ_in_one_bit_and_nodes_out_of_reach(k):
         want = _check(case, D, metric)
         hits = [(i, int(j)) for i in range(len(case.q_strings)) for j in want["hit"][int(want["hit_off"][i]):int(want["hit_off"][i + 1])]]
         assert hits and all(case.q_classes[i] == case.t_classes[j] for i, j in hits)
+
+
+# ---- the walk's two sides: a table against an index of itself, and the network of that table ----
+
+SELF_SIZES = (1, 255, 256, 257, 513)
+_self_memo = {}
+
+
+def _self_table(n, spread, metric):
+    """(classes, strings, sorted position of every node in the walk's bucket order): n strings of the family generators at
+    length 13 (substitutions alone under hamming, indels too under levenshtein) in one class or spread over three; at 513 a few
+    nodes out of reach are mixed in.  Above 256 nodes the three nodes that sort to positions 254, 255 and 256 are given one
+    family of three (a string and two strings one substitution from it), so that the tile's edge runs through a row whatever
+    the generator drew."""
+    strings = (cnu.families if metric == "hamming" else lu.families_indel)(n, seed=100 + n, length=13)
+    if n == 513:
+        for k, s in ((3, ""), (200, "A" * 33), (256, ""), (400, "C" * 40), (512, "A" * 33)):
+            strings[k] = s
+    classes = [(5 * k + k // 7) % 3 for k in range(n)] if spread else [4] * n
+
+    def positions():
+        bs = cnu.as_bytes(strings)
+        bucket = [(not mu.in_reach(s), c, len(s) if metric == "hamming" else 0) for c, s in zip(classes, bs)]
+        order = sorted(range(n), key=lambda k: bucket[k])      # (stable: a bucket stays in rank order, nodes out of reach last)
+        pos = [0] * n
+        for p, k in enumerate(order):
+            pos[k] = p
+        return order, pos
+    if n > 256:
+        before, _ = positions()
+        for k, s in zip(before[254:257], ("CASSLGQAYEQYF", "CASALGQAYEQYF", "CASSLGQAYEQFF")):
+            strings[k] = s
+    return classes, strings, positions()[1]
+
+
+def _self_network(n, spread, D, metric):
+    """The contract's network of the table, made once per (n, spread, D, metric), with the premise checked on it."""
+    key = (n, spread, D, metric)
+    if key not in _self_memo:
+        classes, strings, pos = _self_table(n, spread, metric)
+        expected = cnu.expected_network if metric == "hamming" else lu.expected_lev_network
+        net, stats = expected(classes, strings, [1] * n, D)
+        rows = [net["adj"][int(net["adj_off"][i]):int(net["adj_off"][i + 1])].tolist() for i in range(n)]
+        if n >= 255:
+            assert stats["edges"] > 20, key
+        if n > 256:      # (up to 256 nodes there is no sorted position at or above 256: the table is one tile)
+            assert any(min(pos[j] for j in r) < 256 <= max(pos[j] for j in r) for r in rows if r), key
+        _self_memo[key] = (classes, strings, net, rows)
+    return _self_memo[key]
+
+
+@pytest.mark.parametrize("spread", (False, True), ids=("one_class", "three_classes"))
+@pytest.mark.parametrize("n", SELF_SIZES)
+def test_a_table_against_itself_is_its_network_with_every_node_in_its_own_row(n, spread):
+    """The bipartite side of the walk against the one-table side: matching X against an index of X gives, row by row, the
+    network's adjacency row with the node's own rank inserted in ascending order — for every node in reach; a node out of reach
+    has neither —, and so the degrees and the offsets.  The premise (more than 20 edges from 255 nodes on; above 256 nodes a row
+    with neighbours on both sides of sorted position 256, the tile's edge) is checked on the Python contract before any device
+    call, under every (D, metric)."""
+    runs = [(D, metric) for metric in mu.METRICS for D in (1, 2)]
+    for D, metric in runs:
+        _self_network(n, spread, D, metric)
+    for D, metric in runs:
+        classes, strings, want_net, rows = _self_network(n, spread, D, metric)
+        off, text = cnu.node_text(strings)
+        bs = cnu.as_bytes(strings)
+        net, _ = nat.cdr3_network(classes, off, text, [1] * n, D, want_edges=True, metric=metric)
+        got = mu.native_match(mu.Case(classes, strings, classes, strings), D, metric)
+        want_rows = [sorted(r + [i]) if mu.in_reach(bs[i]) else [] for i, r in enumerate(rows)]
+        assert all(not r for r, s in zip(rows, bs) if not mu.in_reach(s))
+        adj_off, hit_off = np.asarray(net["adj_off"], np.uint64), np.asarray(got["hit_off"], np.uint64)
+        reach_before = np.concatenate([[0], np.cumsum([mu.in_reach(s) for s in bs])]).astype(np.uint64)
+        what = (n, spread, D, metric)
+        assert np.array_equal(adj_off, want_net["adj_off"]) and np.array_equal(hit_off, adj_off + reach_before), what
+        assert np.array_equal(np.asarray(got["degree"], np.uint64), np.asarray(net["degree"], np.uint64) + np.diff(reach_before)), what
+        for i in range(n):
+            a = np.asarray(net["adj"][int(adj_off[i]):int(adj_off[i + 1])]).tolist()
+            h = np.asarray(got["hit"][int(hit_off[i]):int(hit_off[i + 1])]).tolist()
+            assert a == rows[i] and h == want_rows[i] and (h == sorted(a + [i]) if mu.in_reach(bs[i]) else not a and not h), (what, i)
 
 
 # ---- the primitive ----
