@@ -500,6 +500,8 @@ EXPORTS = [
     "dcrx_cdr3_match_run", "dcrx_cdr3_match_destroy", "dcrx_cdr3_match_info", "dcrx_cdr3_match_export", "dcrx_format_cdr3_matches",
     "dcrx_cdr3_match_weighted_work_bytes", "dcrx_cdr3_match_weighted_device", "dcrx_cdr3_match_weighted_run", "dcrx_cdr3_match_export_dist",
     "dcrx_format_cdr3_matches_weighted",
+    "dcrx_cdr3net_weighted_work_bytes", "dcrx_cdr3_neighbours_weighted_device", "dcrx_cdr3_network_weighted",
+    "dcrx_format_cdr3_edges_weighted",
 ]
 
 _lib = None
@@ -671,6 +673,11 @@ def lib():
         "dcrx_cdr3_match_export_dist": (i32, [vp, vp]),
         "dcrx_format_cdr3_matches_weighted": (C.c_int64, [u64, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp,
                                                           vp, vp, vp, u64]),
+        "dcrx_cdr3net_weighted_work_bytes": (u64, [u64, u64]),
+        "dcrx_cdr3_neighbours_weighted_device": (i32, [u64, vp, vp, vp, u64, vp, u32, vp, vp, vp, vp, u64, vp, vp, u64, vp]),
+        "dcrx_cdr3_network_weighted": (C.c_int64, [u64, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
+                                                   C.POINTER(Cdr3NetworkStatsC)]),
+        "dcrx_format_cdr3_edges_weighted": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1762,6 +1769,76 @@ def format_cdr3_matches(result: dict, v_idx, j_idx, v_calls, j_calls, off, text:
     need = check(int(fmt(*args, None, 0)))
     out = _uninitialised_bytes(max(1, need))
     check(int(fmt(*args, _bytes_address(out), need)))
+    return bytes(out[:need])
+
+
+# ---- the CDR3 network under the weighted metric: include/dcrx.h "the CDR3 network, weighted" ----
+
+def cdr3net_weighted_work_bytes(m: int, text_bytes: int) -> int:
+    """dcrx_cdr3net_weighted_work_bytes."""
+    return int(lib().dcrx_cdr3net_weighted_work_bytes(int(m), int(text_bytes)))
+
+
+def cdr3_neighbours_weighted_device(m: int, d_class, d_off, d_text, text_bytes: int, cost: Cdr3Cost, radius: int, d_degree, d_adj_off,
+                                    d_adj, d_adj_dist, adj_cap: int, d_adj_need, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_neighbours_weighted_device: cdr3_neighbours_device under the weighted metric; d_adj_dist (may be None)
+    receives the neighbours' distances."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    c = cost.as_c() if cost is not None else None      # (alive across the call, which copies it)
+    check(lib().dcrx_cdr3_neighbours_weighted_device(int(m), ptr(d_class), ptr(d_off), ptr(d_text), int(text_bytes),
+                                                     C.addressof(c) if c is not None else None, _radius(radius), ptr(d_degree),
+                                                     ptr(d_adj_off), ptr(d_adj), ptr(d_adj_dist), int(adj_cap), ptr(d_adj_need),
+                                                     ptr(d_work), int(work_bytes), stream))
+
+
+def cdr3_network_weighted(classes, aa_off, aa_text: bytes, weights, cost: Cdr3Cost, radius: int, want_edges: bool = False):
+    """dcrx_cdr3_network_weighted: cdr3_network under the weighted metric — nodes of one class, both of 1 .. 32 letters A .. Z,
+    are linked where their weighted distance under `cost` is at most `radius` -> cdr3_network's (result, statistics), the result
+    with "adj_dist" (the distance of every adjacency entry, as the device computed it) when edges are wanted."""
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    off, text = _node_arrays(aa_off, aa_text)
+    m = len(cls)
+    if len(off) != m + 1 or len(w) != m:
+        raise ValueError("cdr3_network_weighted: one class and one weight per node, m + 1 offsets")
+    if m >= CDR3NET_MAX_NODES:
+        raise ValueError(f"the CDR3 network takes fewer than {CDR3NET_MAX_NODES:,} nodes, not {m:,}")
+    deg, of, head, nn = (np.zeros(max(m, 1), np.uint32) for _ in range(4))
+    cw = np.zeros(max(m, 1), np.uint64)
+    adj_off = np.zeros(m + 1, np.uint64) if want_edges else None
+    need = C.c_uint64(0)
+    st = Cdr3NetworkStatsC()
+    c_cost = cost.as_c() if cost is not None else None
+    R = _radius(radius)
+
+    def call(adj, dist, cap):
+        return check(int(lib().dcrx_cdr3_network_weighted(
+            m, cls.ctypes.data, off.ctypes.data, text.ctypes.data, w.ctypes.data, C.addressof(c_cost) if c_cost is not None else None, R,
+            deg.ctypes.data, of.ctypes.data, head.ctypes.data, nn.ctypes.data, cw.ctypes.data, adj_off.ctypes.data if want_edges else None,
+            adj.ctypes.data if adj is not None else None, dist.ctypes.data if dist is not None else None, cap, C.byref(need), C.byref(st))))
+    c = call(None, None, 0)
+    result = {"degree": deg[:m].copy(), "cluster_of": of[:m].copy(), "cluster_head": head[:c].copy(), "cluster_size": nn[:c].copy(),
+              "cluster_weight": cw[:c].copy()}
+    if want_edges:
+        adj, dist = np.zeros(max(1, need.value), np.uint32), np.zeros(max(1, need.value), np.uint32)
+        if need.value:
+            call(adj, dist, need.value)
+        result["adj_off"], result["adj"], result["adj_dist"] = adj_off, adj[:need.value], dist[:need.value]
+    return result, {k: int(getattr(st, k)) for k in CDR3_NETWORK_STATS}
+
+
+def format_cdr3_edges_weighted(aa_off, aa_text: bytes, result: dict, cost: Cdr3Cost) -> bytes:
+    """dcrx_format_cdr3_edges_weighted: format_cdr3_edges with the weighted distance, computed on the host, in the distance
+    column."""
+    off, text = _node_arrays(aa_off, aa_text)
+    adj_off = np.ascontiguousarray(result["adj_off"], dtype=np.uint64)
+    adj = np.ascontiguousarray(result["adj"], dtype=np.uint32) if len(result["adj"]) else np.zeros(1, np.uint32)
+    c = cost.as_c() if cost is not None else None
+    args = [len(off) - 1, adj_off.ctypes.data, adj.ctypes.data, off.ctypes.data, text.ctypes.data, C.addressof(c) if c is not None else None]
+    need = check(int(lib().dcrx_format_cdr3_edges_weighted(*args, None, 0)))
+    out = _uninitialised_bytes(max(1, need))
+    check(int(lib().dcrx_format_cdr3_edges_weighted(*args, _bytes_address(out), need)))
     return bytes(out[:need])
 
 

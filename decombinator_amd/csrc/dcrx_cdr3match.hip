@@ -251,49 +251,6 @@ int run_match(const dcrx_cdr3_index &I, uint64_t m, const uint32_t *cls, const u
   return DCRX_OK;
 }
 
-// what every weighted entry refuses of (cost, radius), on the host; the cost as the walk's launch argument
-int refuse_cost(const char *who, const dcrx_cdr3_cost_t *cost, uint32_t radius, CostArg *arg) {
-  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
-  if (!cost) return fail("null cost");
-  if (radius > MAX_RADIUS) return fail("the radius is 0 .. 65535");
-  if (cost->gap < 1 || cost->gap > MAX_GAP) return fail("the gap cost is 1 .. 255");
-  if (cost->ntrim > MAX_TRIM || cost->ctrim > MAX_TRIM) return fail("a trim is 0 .. 16");
-  for (uint32_t x = 1; x <= 26; x++) {
-    if (cost->sub[x][x]) return fail("the substitution table is not zero on its diagonal");
-    for (uint32_t y = 1; y < x; y++)
-      if (cost->sub[x][y] != cost->sub[y][x]) return fail("the substitution table is not symmetric");
-  }
-  if (arg) {
-    static_assert(sizeof cost->sub == sizeof arg->sub, "one table");
-    std::memcpy(arg->sub, cost->sub, sizeof arg->sub);
-    arg->gap = cost->gap; arg->ntrim = cost->ntrim; arg->ctrim = cost->ctrim;
-  }
-  return DCRX_OK;
-}
-
-bool host_letters(const char *a, uint64_t la) {
-  for (uint64_t i = 0; i < la; i++)
-    if (a[i] < 'A' || a[i] > 'Z') return false;
-  return true;
-}
-
-// the weighted distance of two strings of letters (the matches file's column): the contract read out, the literal minimum
-// over every gap position p in 0 .. la of the sum over the counted positions
-uint64_t host_weighted(const char *a, uint64_t la, const char *b, uint64_t lb, const dcrx_cdr3_cost_t &cost) {
-  if (la > lb) { std::swap(a, b); std::swap(la, lb); }
-  const uint64_t d = lb - la;
-  uint64_t best = UINT64_MAX;
-  for (uint64_t p = 0; p <= (d ? la : 0); p++) {
-    uint64_t sum = 0;
-    for (uint64_t i = 0; i < la; i++) {
-      if (i < cost.ntrim || i + cost.ctrim >= la) continue;
-      sum += cost.sub[a[i] & 31][b[i < p ? i : i + d] & 31];
-    }
-    best = std::min(best, sum);
-  }
-  return d * cost.gap + best;
-}
-
 // the host entry under any metric, behind the entry's own refusals (wc: the weighted walk's cost, `distance` its radius)
 int run_entry(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *cls, const uint64_t *off, const char *text,
               const uint64_t *weight, uint32_t distance, uint32_t metric, const CostArg *wc, dcrx_cdr3_match_t **match_out) {

@@ -23,6 +23,12 @@
 // Hamming) tests a pair by class, length difference, presence masks and then lev_within (on the entry a lane has waiting,
 // once some lane of the wave meets its next one).  A node still walks its whole bucket, now its class: the extra pairs fall
 // at one length compare, and the neighbours still come in ascending rank.
+//
+// Under the weighted metric (the *_weighted entries; include/dcrx.h "the CDR3 network, weighted") the table is prepared in the
+// same class order, without the presence masks (cdr3_gather_kernel<true, false, true>), and the walk's pair test is Weighted
+// (dcrx_cdr3walk.h): a node with a non-letter is not admitted and is staged with length 0; the write pass stores every
+// neighbour's distance beside its rank.  `wc` below is that walk's cost (null under the other two metrics), `limit` then the
+// radius, and the work space is the Hamming walk's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -124,39 +130,47 @@ struct Work {
   Sorted nodes(uint64_t n) const { return Sorted{key[1], idx[1], sj, pres, (uint32_t)n}; }
 };
 
+// one pass of the walk over the prepared table
+template <bool WRITE> int run_walk(uint64_t n, uint32_t limit, uint32_t metric, const CostArg *wc, const Out &O, const Work &W, hipStream_t s) {
+  const Sorted X = W.nodes(n);
+  if (!wc) return walk<WRITE>(X, X, Within{W.bstart}, limit, metric == METRIC_LEVENSHTEIN, O, s);
+  cdr3_walk_kernel<WRITE><<<grid_for(n), BLOCK, 0, s>>>(X, X, Within{W.bstart}, Weighted{*wc, limit}, O);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
 // keys, sort, gather, the bucket starts, the degree pass, the scan and the need
-int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint64_t *d_need,
-                const Work &W, hipStream_t s) {
+int run_degrees(const Nodes &N, uint64_t n, uint32_t limit, uint32_t metric, const CostArg *wc, uint32_t *d_degree, uint64_t *d_adj_off,
+                uint64_t *d_need, const Work &W, hipStream_t s) {
   const bool lev = metric == METRIC_LEVENSHTEIN;
   const uint32_t n32 = (uint32_t)n;
   int rc;
-  if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, lev ? (int)LEN_BITS : 0, true, s))) return rc;
-  if (lev) cdr3_gather_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, W.pres);
+  if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, lev || wc ? (int)LEN_BITS : 0, true, s))) return rc;
+  if (wc) cdr3_gather_kernel<true, false, true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, nullptr);
+  else if (lev) cdr3_gather_kernel<true, true><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, W.pres);
   else cdr3_gather_kernel<true, false><<<grid_for(n), BLOCK, 0, s>>>(N, n32, W.key[1], W.idx[1], W.sj, W.mark, nullptr);
   HIP_TRY(hipGetLastError());
-  const Sorted X = W.nodes(n);
   if ((rc = run_heads(W.cub, W.mark, W.bstart, n, s)) ||
-      (rc = walk<false>(X, X, Within{W.bstart}, limit, lev, Out{d_degree, W.deg64, nullptr, nullptr, nullptr, 0}, s)) ||
+      (rc = run_walk<false>(n, limit, metric, wc, Out{d_degree, W.deg64, nullptr, nullptr, nullptr, 0}, W, s)) ||
       (rc = exclusive_sum(W.cub, W.deg64, d_adj_off, n, s))) return rc;
   cdr3_need_kernel<<<1, 64, 0, s>>>(W.deg64, d_adj_off, n32, d_need);
   HIP_TRY(hipGetLastError());
   return DCRX_OK;
 }
 
-int run_write(uint64_t n, uint32_t limit, uint32_t metric, const uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap, const Work &W,
-              hipStream_t s) {
-  const Sorted X = W.nodes(n);
-  return walk<true>(X, X, Within{W.bstart}, limit, metric == METRIC_LEVENSHTEIN, Out{nullptr, nullptr, d_adj_off, d_adj, nullptr, adj_cap}, s);
+int run_write(uint64_t n, uint32_t limit, uint32_t metric, const CostArg *wc, const uint64_t *d_adj_off, uint32_t *d_adj, uint32_t *d_adj_dist,
+              uint64_t adj_cap, const Work &W, hipStream_t s) {
+  return run_walk<true>(n, limit, metric, wc, Out{nullptr, nullptr, d_adj_off, d_adj, d_adj_dist, adj_cap}, W, s);
 }
 
 // an error of the entry `who` (the plain entries and their *_metric forms share one body and name themselves)
 int fail(int code, const char *who, const char *what) { return set_err(code, (std::string(who) + ": " + what).c_str()); }
 
 int neighbours_device(const char *who, uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
-                      uint32_t distance, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap,
-                      uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) try {
+                      uint32_t distance, uint32_t metric, const CostArg *wc, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj,
+                      uint32_t *d_adj_dist, uint64_t adj_cap, uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) try {
   if (m >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, who, "2^30 or more nodes");
-  if (distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
+  if (!wc && distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
   if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
   hipStream_t s = (hipStream_t)hip_stream;
   if (!m) {
@@ -172,22 +186,23 @@ int neighbours_device(const char *who, uint64_t m, const uint32_t *d_class, cons
   int rc = W.carve(P, m, metric);
   if (rc) return rc;
   if (work_bytes < P.bytes())
-    return fail(DCRX_E_INVALID, who, metric == METRIC_HAMMING ? "the work space is smaller than dcrx_cdr3net_work_bytes(m, text_bytes)"
-                                                              : "the work space is smaller than dcrx_cdr3net_metric_work_bytes(m, text_bytes, metric)");
+    return fail(DCRX_E_INVALID, who, wc ? "the work space is smaller than dcrx_cdr3net_weighted_work_bytes(m, text_bytes)"
+                                     : metric == METRIC_HAMMING ? "the work space is smaller than dcrx_cdr3net_work_bytes(m, text_bytes)"
+                                                                : "the work space is smaller than dcrx_cdr3net_metric_work_bytes(m, text_bytes, metric)");
   const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
-  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_adj_need, W, s))) return rc;
+  if ((rc = run_degrees(N, m, distance, metric, wc, d_degree, d_adj_off, d_adj_need, W, s))) return rc;
   if (!d_adj || !adj_cap) return DCRX_OK;
-  return run_write(m, distance, metric, d_adj_off, d_adj, adj_cap, W, s);
+  return run_write(m, distance, metric, wc, d_adj_off, d_adj, d_adj_dist, adj_cap, W, s);
 } catch (const std::exception &e) {      // (a message that could not be built)
   return set_err(DCRX_E_NOMEM, e.what());
 }
 
 int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
-                uint32_t distance, uint32_t metric, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
-                uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap,
-                uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) try {
+                uint32_t distance, uint32_t metric, const CostArg *wc, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
+                uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint32_t *adj_dist_out,
+                uint64_t adj_cap, uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) try {
   if (m >= MAX_NODES) return fail(DCRX_E_UNSUPPORTED, who, "2^30 or more nodes");
-  if (distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
+  if (!wc && distance != 1 && distance != 2) return fail(DCRX_E_INVALID, who, "the distance is 1 or 2");
   if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
   if (stats_out) { *stats_out = dcrx_cdr3_network_stats_t{}; stats_out->nodes_in = m; }
   if (adj_need_out) *adj_need_out = 0;
@@ -224,13 +239,15 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
   const Nodes N{d_cls, d_off, d_text, text_bytes};
 
   // the degree pass, then an adjacency of exactly the entries it takes
-  if ((rc = run_degrees(N, m, distance, metric, d_degree, d_adj_off, d_need, W, nullptr))) return rc;
+  if ((rc = run_degrees(N, m, distance, metric, wc, d_degree, d_adj_off, d_need, W, nullptr))) return rc;
   uint64_t need = 0;
   if ((rc = to_host(&need, d_need, 1))) return rc;
   if (adj_need_out) *adj_need_out = need;
-  dcrx::DevBuf<uint32_t> d_adj;
-  if (d_adj.alloc(std::max<uint64_t>(need, 1))) return fail(DCRX_E_NOMEM, who, "the adjacency does not fit the device's memory");
-  if (need && (rc = run_write(m, distance, metric, d_adj_off, d_adj.get(), need, W, nullptr))) return rc;
+  const bool want_dist = wc && adj_dist_out && adj_out && need <= adj_cap;      // (the distances go where the adjacency goes)
+  dcrx::DevBuf<uint32_t> d_adj, d_dist;
+  if (d_adj.alloc(std::max<uint64_t>(need, 1)) || (want_dist && d_dist.alloc(std::max<uint64_t>(need, 1))))
+    return fail(DCRX_E_NOMEM, who, "the adjacency does not fit the device's memory");
+  if (need && (rc = run_write(m, distance, metric, wc, d_adj_off, d_adj.get(), want_dist ? d_dist.get() : nullptr, need, W, nullptr))) return rc;
 
   // components: rounds of the neighbourhood's smallest label, then the labels followed to their ends
   cdr3net_label_init_kernel<<<grid_for(m), BLOCK>>>(m32, d_label[0]);
@@ -263,6 +280,7 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
   if (adj_off_out) {
     if ((rc = to_host(adj_off_out, d_adj_off, m + 1))) return rc;
     if (adj_out && need <= adj_cap && (rc = to_host(adj_out, d_adj.get(), need))) return rc;
+    if (want_dist && (rc = to_host(adj_dist_out, d_dist.get(), need))) return rc;
   }
   if (stats_out) {
     stats_out->out_of_reach = out_of_reach;
@@ -280,9 +298,9 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
 }
 
 int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
-                     uint32_t metric, char *out, uint64_t out_cap) try {
+                     uint32_t metric, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap) try {
   static const char header[] = "a\tb\tdistance\n";
-  if (!metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
+  if (!cost && !metric_exists(metric)) return fail(DCRX_E_INVALID, who, "the metric is DCRX_CDR3NET_HAMMING or DCRX_CDR3NET_LEVENSHTEIN");
   if (m && (!adj_off || !off || (adj_off[m] && !adj))) return fail(DCRX_E_INVALID, who, "null argument");
   dcrx::TextOut T{out, out_cap};
   T.put(header, sizeof header - 1);
@@ -294,7 +312,11 @@ int64_t format_edges(const char *who, uint64_t m, const uint64_t *adj_off, const
       if (b <= a) continue;
       const uint64_t la = off[a + 1] - off[a], lb = off[b + 1] - off[b];
       unsigned long long d = 0;
-      if (metric == METRIC_LEVENSHTEIN) {
+      if (cost) {
+        if (!in_reach(la) || !in_reach(lb) || !host_letters(text + off[a], la) || !host_letters(text + off[b], lb))
+          return fail(DCRX_E_INVALID, who, "an edge between strings out of the weighted metric's reach");
+        d = host_weighted(text + off[a], la, text + off[b], lb, *cost);
+      } else if (metric == METRIC_LEVENSHTEIN) {
         d = dcrx::host_levenshtein(text + off[a], la, text + off[b], lb);
       } else {
         if (la != lb) return fail(DCRX_E_INVALID, who, "an edge between strings of two lengths");
@@ -325,31 +347,31 @@ uint64_t dcrx_cdr3net_work_bytes(uint64_t m, uint64_t text_bytes) { return dcrx_
 int dcrx_cdr3_neighbours_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
                                 uint32_t distance, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj, uint64_t adj_cap,
                                 uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
-  return neighbours_device("dcrx_cdr3_neighbours_device", m, d_class, d_off, d_text, text_bytes, distance, METRIC_HAMMING, d_degree,
-                           d_adj_off, d_adj, adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
+  return neighbours_device("dcrx_cdr3_neighbours_device", m, d_class, d_off, d_text, text_bytes, distance, METRIC_HAMMING, nullptr, d_degree,
+                           d_adj_off, d_adj, nullptr, adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
 }
 
 int dcrx_cdr3_neighbours_metric_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
                                        uint32_t distance, uint32_t metric, uint32_t *d_degree, uint64_t *d_adj_off, uint32_t *d_adj,
                                        uint64_t adj_cap, uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream) {
-  return neighbours_device("dcrx_cdr3_neighbours_metric_device", m, d_class, d_off, d_text, text_bytes, distance, metric, d_degree,
-                           d_adj_off, d_adj, adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
+  return neighbours_device("dcrx_cdr3_neighbours_metric_device", m, d_class, d_off, d_text, text_bytes, distance, metric, nullptr, d_degree,
+                           d_adj_off, d_adj, nullptr, adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
 }
 
 int64_t dcrx_cdr3_network(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
                           uint32_t distance, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out, uint32_t *n_nodes_out,
                           uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap, uint64_t *adj_need_out,
                           dcrx_cdr3_network_stats_t *stats_out) {
-  return network("dcrx_cdr3_network", m, cls, off, text, weight, distance, METRIC_HAMMING, degree_out, cluster_of_out, head_out,
-                 n_nodes_out, weight_out, adj_off_out, adj_out, adj_cap, adj_need_out, stats_out);
+  return network("dcrx_cdr3_network", m, cls, off, text, weight, distance, METRIC_HAMMING, nullptr, degree_out, cluster_of_out, head_out,
+                 n_nodes_out, weight_out, adj_off_out, adj_out, nullptr, adj_cap, adj_need_out, stats_out);
 }
 
 int64_t dcrx_cdr3_network_metric(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
                                  uint32_t distance, uint32_t metric, uint32_t *degree_out, uint32_t *cluster_of_out, uint32_t *head_out,
                                  uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out, uint32_t *adj_out, uint64_t adj_cap,
                                  uint64_t *adj_need_out, dcrx_cdr3_network_stats_t *stats_out) {
-  return network("dcrx_cdr3_network_metric", m, cls, off, text, weight, distance, metric, degree_out, cluster_of_out, head_out,
-                 n_nodes_out, weight_out, adj_off_out, adj_out, adj_cap, adj_need_out, stats_out);
+  return network("dcrx_cdr3_network_metric", m, cls, off, text, weight, distance, metric, nullptr, degree_out, cluster_of_out, head_out,
+                 n_nodes_out, weight_out, adj_off_out, adj_out, nullptr, adj_cap, adj_need_out, stats_out);
 }
 
 int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint32_t *j_idx, uint32_t n_v, const char *v_calls,
@@ -383,12 +405,57 @@ int64_t dcrx_format_cdr3_clusters(uint64_t m, const uint32_t *v_idx, const uint3
 
 int64_t dcrx_format_cdr3_edges(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
                                char *out, uint64_t out_cap) {
-  return format_edges("dcrx_format_cdr3_edges", m, adj_off, adj, off, text, METRIC_HAMMING, out, out_cap);
+  return format_edges("dcrx_format_cdr3_edges", m, adj_off, adj, off, text, METRIC_HAMMING, nullptr, out, out_cap);
 }
 
 int64_t dcrx_format_cdr3_edges_metric(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
                                       uint32_t metric, char *out, uint64_t out_cap) {
-  return format_edges("dcrx_format_cdr3_edges_metric", m, adj_off, adj, off, text, metric, out, out_cap);
+  return format_edges("dcrx_format_cdr3_edges_metric", m, adj_off, adj, off, text, metric, nullptr, out, out_cap);
+}
+
+// ---- the weighted metric's entries (include/dcrx.h "the CDR3 network, weighted")
+
+uint64_t dcrx_cdr3net_weighted_work_bytes(uint64_t m, uint64_t text_bytes) {
+  return dcrx_cdr3net_metric_work_bytes(m, text_bytes, METRIC_HAMMING);      // (the same carve: no presence masks)
+}
+
+int dcrx_cdr3_neighbours_weighted_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
+                                         const dcrx_cdr3_cost_t *cost, uint32_t radius, uint32_t *d_degree, uint64_t *d_adj_off,
+                                         uint32_t *d_adj, uint32_t *d_adj_dist, uint64_t adj_cap, uint64_t *d_adj_need, void *d_work,
+                                         uint64_t work_bytes, void *hip_stream) try {
+  static const char who[] = "dcrx_cdr3_neighbours_weighted_device";
+  CostArg wc;
+  const int rc = refuse_cost(who, cost, radius, &wc);
+  if (rc) return rc;
+  return neighbours_device(who, m, d_class, d_off, d_text, text_bytes, radius, METRIC_HAMMING, &wc, d_degree, d_adj_off, d_adj, d_adj_dist,
+                           adj_cap, d_adj_need, d_work, work_bytes, hip_stream);
+} catch (const std::exception &e) {      // (a message that could not be built)
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int64_t dcrx_cdr3_network_weighted(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                                   const dcrx_cdr3_cost_t *cost, uint32_t radius, uint32_t *degree_out, uint32_t *cluster_of_out,
+                                   uint32_t *head_out, uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out,
+                                   uint32_t *adj_out, uint32_t *adj_dist_out, uint64_t adj_cap, uint64_t *adj_need_out,
+                                   dcrx_cdr3_network_stats_t *stats_out) try {
+  static const char who[] = "dcrx_cdr3_network_weighted";
+  CostArg wc;
+  const int rc = refuse_cost(who, cost, radius, &wc);
+  if (rc) return rc;
+  return network(who, m, cls, off, text, weight, radius, METRIC_HAMMING, &wc, degree_out, cluster_of_out, head_out, n_nodes_out, weight_out,
+                 adj_off_out, adj_out, adj_dist_out, adj_cap, adj_need_out, stats_out);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int64_t dcrx_format_cdr3_edges_weighted(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off, const char *text,
+                                        const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap) try {
+  static const char who[] = "dcrx_format_cdr3_edges_weighted";
+  const int rc = refuse_cost(who, cost, 0, nullptr);
+  if (rc) return rc;
+  return format_edges(who, m, adj_off, adj, off, text, METRIC_WEIGHTED, cost, out, out_cap);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 }  // extern "C"

@@ -13,10 +13,16 @@
 // exact place.
 // Side says which entries a block walks and whether an entry is the lane's own node: Bipartite (two tables) or Within (one
 // table against itself).  Pair is the pair test: Hamming, Levenshtein or Weighted.
+// The weighted metric's host side stands here too, once for both units: what every weighted entry refuses of a cost
+// (refuse_cost) and the distance the formatters print (host_weighted).
 // The per-node and per-pair code is dcrx_cdr3net_core.h's and dcrx_cdr3w_core.h's, the look-ups are dcrx_cdr3match_core.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
 
 #include "dcrx_cdr3match_core.h"
 #include "dcrx_cdr3w_core.h"
@@ -88,8 +94,9 @@ inline int sorted_keys(const Nodes &N, uint64_t n, uint64_t *const key[2], uint3
 }
 
 // per sorted position the packed string; MARKS: the run mark of its bucket, whose max scan gives every position its bucket's
-// start; PRES: the table is in class order (the marks are the classes'), and its letter-presence mask goes beside the string
-template <bool MARKS, bool PRES>
+// start; PRES: its letter-presence mask goes beside the string; CLS: the table is in class order (the marks are the classes':
+// with the masks unless said otherwise — the weighted network's table is in class order and has no masks)
+template <bool MARKS, bool PRES, bool CLS = PRES>
 __global__ __launch_bounds__(BLOCK) void cdr3_gather_kernel(Nodes N, uint32_t n, const uint64_t *__restrict__ key,
                                                             const uint32_t *__restrict__ idx, uint4 *__restrict__ sj,
                                                             uint32_t *__restrict__ mark, uint32_t *__restrict__ pres) {
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(BLOCK) void cdr3_gather_kernel(Nodes N, uint32_t n,
   pack(N.text + (in_reach(len) ? at : 0), len, w);
   sj[2 * (size_t)s] = make_uint4(w[0], w[1], w[2], w[3]);
   sj[2 * (size_t)s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-  if (MARKS) mark[s] = run_mark(s, [&](uint32_t k) { return bucket_of<PRES>(key[k]); });
+  if (MARKS) mark[s] = run_mark(s, [&](uint32_t k) { return bucket_of<CLS>(key[k]); });
   if (PRES) pres[s] = presence(w, in_reach(len) ? (uint32_t)len : 0u);
 }
 
@@ -291,6 +298,51 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
     O.degree[e] = count;
     O.deg64[e] = count;
   }
+}
+
+// ---- the weighted metric on the host: what every weighted entry refuses, and the distance the formatters print
+
+// what every weighted entry refuses of (cost, radius), on the host; the cost as the walk's launch argument
+inline int refuse_cost(const char *who, const dcrx_cdr3_cost_t *cost, uint32_t radius, CostArg *arg) {
+  auto fail = [&](const char *what) { return dcrx::set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  if (!cost) return fail("null cost");
+  if (radius > MAX_RADIUS) return fail("the radius is 0 .. 65535");
+  if (cost->gap < 1 || cost->gap > MAX_GAP) return fail("the gap cost is 1 .. 255");
+  if (cost->ntrim > MAX_TRIM || cost->ctrim > MAX_TRIM) return fail("a trim is 0 .. 16");
+  for (uint32_t x = 1; x <= 26; x++) {
+    if (cost->sub[x][x]) return fail("the substitution table is not zero on its diagonal");
+    for (uint32_t y = 1; y < x; y++)
+      if (cost->sub[x][y] != cost->sub[y][x]) return fail("the substitution table is not symmetric");
+  }
+  if (arg) {
+    static_assert(sizeof cost->sub == sizeof arg->sub, "one table");
+    std::memcpy(arg->sub, cost->sub, sizeof arg->sub);
+    arg->gap = cost->gap; arg->ntrim = cost->ntrim; arg->ctrim = cost->ctrim;
+  }
+  return DCRX_OK;
+}
+
+inline bool host_letters(const char *a, uint64_t la) {
+  for (uint64_t i = 0; i < la; i++)
+    if (a[i] < 'A' || a[i] > 'Z') return false;
+  return true;
+}
+
+// the weighted distance of two strings of letters (the files' distance column): the contract read out, the literal minimum
+// over every gap position p in 0 .. la of the sum over the counted positions
+inline uint64_t host_weighted(const char *a, uint64_t la, const char *b, uint64_t lb, const dcrx_cdr3_cost_t &cost) {
+  if (la > lb) { std::swap(a, b); std::swap(la, lb); }
+  const uint64_t d = lb - la;
+  uint64_t best = UINT64_MAX;
+  for (uint64_t p = 0; p <= (d ? la : 0); p++) {
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < la; i++) {
+      if (i < cost.ntrim || i + cost.ctrim >= la) continue;
+      sum += cost.sub[a[i] & 31][b[i < p ? i : i + d] & 31];
+    }
+    best = std::min(best, sum);
+  }
+  return d * cost.gap + best;
 }
 
 // one pass under the Hamming metric, or (lev) the Levenshtein metric at a distance above 0

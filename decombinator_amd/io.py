@@ -31,6 +31,7 @@ def create_args_dict(
     cluster: bool = False, count_dcrs: bool = False, merge_errors: bool = False, merge_distance: int = 1,
     merge_ratio: int = 10, write_merges: bool = False, clonotypes: bool = False, cdr3_network: bool = False,
     cdr3_distance: int = 1, cdr3_class: str = "v", write_cdr3_edges: bool = False, cdr3_metric: str = None,
+    cdr3_radius: int = None, cdr3_gap_cost: int = None, cdr3_trim: str = None, cdr3_cost_matrix: str = None,
 ) -> dict:
     """The function-argument dictionary threaded through the stages (the reference's 33 keys, `cluster`: run the
     grouping / clustering half of collapse, writing the `.freq`, and `count_dcrs`: with nobarcoding, count the DCRs on the
@@ -41,8 +42,10 @@ def create_args_dict(
     with clonotypes, link the clonotypes of one `cdr3_class` (none, v or vj) whose junction_aa have one length and differ in at
     most `cdr3_distance` (1 or 2) residues, on the GPU, and write `.cdr3_clusters.tsv`, with `write_cdr3_edges` also
     `.cdr3_edges.tsv`; `cdr3_metric` levenshtein (None: hamming) also links junction_aa of two lengths, at most
-    `cdr3_distance` substitutions, insertions and deletions apart.  The defaults v and 1 are a design choice, not a measured
-    optimum)."""
+    `cdr3_distance` substitutions, insertions and deletions apart; `cdr3_metric` weighted links the junction_aa within
+    `cdr3_radius` (None: 24) under match's weighted distance, with `cdr3_gap_cost` (12), `cdr3_trim` ("3,2") and
+    `cdr3_cost_matrix` (a file; None: the default table) as `match` reads them, and `cdr3_distance` does not apply.  The defaults
+    v and 1 are a design choice, not a measured optimum)."""
     return dict(
         infile=infile, chain=chain, bc_read=bc_read, suppresssummary=suppresssummary, dontgzip=dontgzip,
         dontcheck=dontcheck, dontcount=dontcount, extension=extension, prefix=prefix, orientation=orientation,
@@ -55,7 +58,8 @@ def create_args_dict(
         dontsave=dontsave, command=command, sampling_analysis=sampling_analysis, cluster=cluster,
         count_dcrs=count_dcrs, merge_errors=merge_errors, merge_distance=merge_distance, merge_ratio=merge_ratio,
         write_merges=write_merges, clonotypes=clonotypes, cdr3_network=cdr3_network, cdr3_distance=cdr3_distance,
-        cdr3_class=cdr3_class, write_cdr3_edges=write_cdr3_edges, cdr3_metric=cdr3_metric)
+        cdr3_class=cdr3_class, write_cdr3_edges=write_cdr3_edges, cdr3_metric=cdr3_metric, cdr3_radius=cdr3_radius,
+        cdr3_gap_cost=cdr3_gap_cost, cdr3_trim=cdr3_trim, cdr3_cost_matrix=cdr3_cost_matrix)
 
 
 def _common(p: argparse.ArgumentParser):
@@ -128,10 +132,19 @@ def _clonotypes_flag(p: argparse.ArgumentParser):
     p.add_argument("--cdr3-distance", dest="cdr3_distance", type=int, default=None,
                    help="Residues in which two linked CDR3s may differ: 1 (default) or 2.  The default is a design choice, not a "
                         "measured optimum")
-    p.add_argument("--cdr3-metric", dest="cdr3_metric", choices=["hamming", "levenshtein"], default=None,
+    # weighted (match's TCRdist-style distance with a radius; README) is taken with the four flags below it.  The help
+    # texts of decombine, pipeline and translate are pinned word for word (tests/golden/overlap_help), so the metavar and the
+    # help line stay what they were and the four flags are not listed; `match --help` describes them, the refusals name them,
+    # and an unknown metric's error lists all three choices.
+    p.add_argument("--cdr3-metric", dest="cdr3_metric", choices=["hamming", "levenshtein", "weighted"], default=None,
+                   metavar="{hamming,levenshtein}",
                    help="How the residues between two linked CDR3s are counted: hamming (default; substitutions between CDR3s of "
                         "one length) or levenshtein (substitutions, insertions and deletions: the lengths may differ by up to "
                         "--cdr3-distance)")
+    p.add_argument("--cdr3-radius", dest="cdr3_radius", type=int, default=None, help=argparse.SUPPRESS)           # 0 to 65535, default 24
+    p.add_argument("--cdr3-gap-cost", dest="cdr3_gap_cost", type=int, default=None, help=argparse.SUPPRESS)       # 1 to 255, default 12
+    p.add_argument("--cdr3-trim", dest="cdr3_trim", type=str, default=None, help=argparse.SUPPRESS)               # N,C, 0 to 16 each, default 3,2
+    p.add_argument("--cdr3-cost-matrix", dest="cdr3_cost_matrix", type=str, default=None, help=argparse.SUPPRESS)  # a table as `match` reads it
     p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default=None,
                    help="What two linked clonotypes must share beside the CDR3's length: nothing (none), the V call (v, the "
                         "default) or the V and the J call (vj).  The default is a design choice, not a measured optimum")
@@ -288,7 +301,9 @@ def cli_args(argv=None) -> dict:
     if "cdr3_network" in inp:
         # which of the network's options the command line named (they are refused without --cdr3-network), then the defaults
         inp["cdr3_options_given"] = [f for f, k in (("--cdr3-distance", "cdr3_distance"), ("--cdr3-class", "cdr3_class"),
-                                                    ("--cdr3-metric", "cdr3_metric")) if inp[k] is not None]
+                                                    ("--cdr3-metric", "cdr3_metric"), ("--cdr3-radius", "cdr3_radius"),
+                                                    ("--cdr3-gap-cost", "cdr3_gap_cost"), ("--cdr3-trim", "cdr3_trim"),
+                                                    ("--cdr3-cost-matrix", "cdr3_cost_matrix")) if inp[k] is not None]
         inp["cdr3_distance"] = 1 if inp["cdr3_distance"] is None else inp["cdr3_distance"]
         inp["cdr3_class"] = "v" if inp["cdr3_class"] is None else inp["cdr3_class"]
     return inp

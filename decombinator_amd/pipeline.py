@@ -34,6 +34,10 @@ def clonotype_refusal(inp: dict):
 def cdr3_network_refusal(inp: dict):
     """Why the --cdr3-network flags cannot run with these arguments, or None: the network is made of the clonotype table."""
     others = list(inp.get("cdr3_options_given") or []) + (["--write-cdr3-edges"] if inp.get("write_cdr3_edges") else [])
+    from .match import WEIGHTED, WEIGHTED_OPTIONS, weighted_refusal
+    for key, flag in WEIGHTED_OPTIONS.items():      # (a caller's dictionary names them by key)
+        if inp.get(key) is not None and flag not in others:
+            others.append(flag)
     if not inp.get("cdr3_network"):
         return f"{', '.join(others)} belong{'s' if len(others) == 1 else ''} to --cdr3-network" if others else None
     if not inp.get("clonotypes"):
@@ -42,8 +46,20 @@ def cdr3_network_refusal(inp: dict):
         return f"--cdr3-distance is 1 or 2, not {inp['cdr3_distance']}"
     if inp.get("cdr3_class", "v") not in ("none", "v", "vj"):
         return f"--cdr3-class is none, v or vj, not {inp['cdr3_class']}"
-    if (inp.get("cdr3_metric") or "hamming") not in ("hamming", "levenshtein"):
-        return f"--cdr3-metric is hamming or levenshtein, not {inp['cdr3_metric']}"
+    metric = inp.get("cdr3_metric") or "hamming"
+    if metric not in ("hamming", "levenshtein", WEIGHTED):
+        return f"--cdr3-metric is hamming or levenshtein, or weighted (with --cdr3-radius), not {inp['cdr3_metric']}"
+    if metric == WEIGHTED and "--cdr3-distance" in others:
+        return "--cdr3-distance does not apply to --cdr3-metric weighted: the radius is --cdr3-radius"
+    why = weighted_refusal(dict(inp, cdr3_metric=metric))      # (the four flags without the metric, and their ranges)
+    if why:
+        return why
+    if metric == WEIGHTED and inp.get("cdr3_cost_matrix"):      # a bad matrix file: by its line, before the input is read
+        from .match import weighted_settings
+        try:
+            weighted_settings(dict(inp, cdr3_metric=metric))
+        except (ValueError, OSError) as e:
+            return str(e)
     return None
 
 

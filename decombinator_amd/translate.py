@@ -394,6 +394,7 @@ cdr3_network_stats: dict = {}          # the statistics of the last cdr3_network
 chain_cdr3_network_stats: dict = {}    # ... per chain, for `pipeline -c a,b`
 CDR3_CLASSES = ("none", "v", "vj")
 CDR3_METRICS = ("hamming", "levenshtein")
+CDR3_WEIGHTED = "weighted"      # match's weighted distance with a radius (include/dcrx.h "the CDR3 network, weighted")
 
 
 class Cdr3Network:
@@ -401,8 +402,9 @@ class Cdr3Network:
     representatives' V and J genes), the result of _native.cdr3_network and its statistics; text() is the
     `.cdr3_clusters.tsv`'s and edges_text() the `.cdr3_edges.tsv`'s, formatted by libdcrx in one pass."""
 
-    def __init__(self, genes, nodes: dict, result: dict, stats: dict, metric: str = "hamming"):
+    def __init__(self, genes, nodes: dict, result: dict, stats: dict, metric: str = "hamming", cost=None):
         self.genes, self.nodes, self.result, self.stats, self.metric = genes, nodes, result, stats, metric
+        self.cost = cost      # (the weighted metric's _native.Cdr3Cost)
 
     def __len__(self):
         return len(self.nodes["classes"])
@@ -417,6 +419,8 @@ class Cdr3Network:
         from . import _native as nat
         if self.metric == "hamming":
             return nat.format_cdr3_edges(self.nodes["aa_off"], self.nodes["aa_text"], self.result)
+        if self.metric == CDR3_WEIGHTED:
+            return nat.format_cdr3_edges_weighted(self.nodes["aa_off"], self.nodes["aa_text"], self.result, self.cost)
         return nat.format_cdr3_edges(self.nodes["aa_off"], self.nodes["aa_text"], self.result, metric=self.metric)
 
 
@@ -453,16 +457,20 @@ def cdr3_network(inputargs: dict, clonotypes: ClonotypeTable) -> Cdr3Network:
     """The CDR3 network of a clonotype table: its rows as nodes (cdr3_nodes, inputargs["cdr3_class"], default v), linked within
     inputargs["cdr3_distance"] (1 or 2, default 1) substitutions — under inputargs["cdr3_metric"] "levenshtein" (default
     hamming) substitutions, insertions and deletions —: one call of _native.cdr3_network, with the edges when
-    inputargs["write_cdr3_edges"] is set.  Prints the statistics and keeps them in cdr3_network_stats."""
+    inputargs["write_cdr3_edges"] is set.  Under "weighted" the rows are linked within inputargs["cdr3_radius"] of match's
+    weighted distance (match.weighted_settings reads the radius, the gap cost, the trims and the matrix file): one call of
+    _native.cdr3_network_weighted.  Prints the statistics and keeps them in cdr3_network_stats."""
     from . import _native as nat
     global cdr3_network_stats
+    if (inputargs.get("cdr3_metric") or "hamming") == CDR3_WEIGHTED:
+        return _cdr3_network_weighted(inputargs, clonotypes)
     distance = inputargs.get("cdr3_distance")
     distance = 1 if distance is None else int(distance)
     if distance not in (1, 2):
         raise ValueError(f"--cdr3-distance is 1 or 2, not {distance}")
     metric = inputargs.get("cdr3_metric") or "hamming"
     if metric not in CDR3_METRICS:
-        raise ValueError(f"--cdr3-metric is {' or '.join(CDR3_METRICS)}, not {metric}")
+        raise ValueError(f"--cdr3-metric is {' or '.join(CDR3_METRICS)}, or {CDR3_WEIGHTED} (with --cdr3-radius), not {metric}")
     nodes = cdr3_nodes(clonotypes, inputargs.get("cdr3_class") or "v")
     if len(nodes["classes"]) >= nat.CDR3NET_MAX_NODES:
         raise ValueError(f"--cdr3-network takes fewer than {nat.CDR3NET_MAX_NODES:,} clonotypes, not {len(nodes['classes']):,}")
@@ -477,3 +485,31 @@ def cdr3_network(inputargs: dict, clonotypes: ClonotypeTable) -> Cdr3Network:
           f"within {distance}; {stats['clusters_out']:,} clusters, {stats['singletons']:,} of them single (the largest holds "
           f"{stats['largest_cluster']:,}; at most {stats['largest_degree']:,} neighbours)")
     return Cdr3Network(clonotypes.genes, nodes, result, stats, metric)
+
+
+def _cdr3_network_weighted(inputargs: dict, clonotypes: ClonotypeTable) -> Cdr3Network:
+    """cdr3_network() under --cdr3-metric weighted."""
+    from . import _native as nat
+    from . import match
+    global cdr3_network_stats
+    why = match.weighted_refusal(dict(inputargs, cdr3_metric=CDR3_WEIGHTED, cdr3_distance=1))
+    if why:
+        raise ValueError(why)
+    cost, radius = match.weighted_settings(inputargs)
+    nodes = cdr3_nodes(clonotypes, inputargs.get("cdr3_class") or "v")
+    m = len(nodes["classes"])
+    if m >= nat.CDR3NET_MAX_NODES:
+        raise ValueError(f"--cdr3-network takes fewer than {nat.CDR3NET_MAX_NODES:,} clonotypes, not {m:,}")
+    result, stats = nat.cdr3_network_weighted(nodes["classes"], nodes["aa_off"], nodes["aa_text"], nodes["weights"], cost, radius,
+                                              want_edges=bool(inputargs.get("write_cdr3_edges")))
+    off, text = nodes["aa_off"], nodes["aa_text"]
+    not_letters = sum(1 <= len(s) <= nat.CDR3NET_MAX_LEN and not match.letters_only(s)
+                      for s in (text[int(off[i]):int(off[i + 1])] for i in range(m)))
+    cdr3_network_stats = dict(stats, not_letters=not_letters)
+    print(f"CDR3 network metric: weighted (radius {radius}, gap {cost.gap}, trim {cost.ntrim},{cost.ctrim}; linked CDR3s may differ in "
+          "length)")
+    print(f"CDR3 network: {stats['nodes_in']:,} clonotypes in ({stats['out_of_reach']:,} out of reach); {stats['edges']:,} pairs "
+          f"within radius {radius}; {stats['clusters_out']:,} clusters, {stats['singletons']:,} of them single (the largest holds "
+          f"{stats['largest_cluster']:,}; at most {stats['largest_degree']:,} neighbours)")
+    print(f"CDR3 network: {not_letters:,} clonotypes took no part for a byte outside A..Z")
+    return Cdr3Network(clonotypes.genes, nodes, result, cdr3_network_stats, CDR3_WEIGHTED, cost)

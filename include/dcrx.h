@@ -1274,6 +1274,52 @@ int64_t dcrx_format_cdr3_matches_weighted(uint64_t m_q, const uint64_t *hit_off,
                                           const char *db_header, uint64_t db_header_bytes, const uint64_t *db_line_off,
                                           const char *db_lines, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap);
 
+/* ---- the CDR3 network, weighted (`--cdr3-network --cdr3-metric weighted`): which clonotypes of ONE table lie within a radius
+ * of each other under the weighted distance above, and the clusters they form.  The entries only ADD to ABI 5; the network's
+ * *_metric entries keep their signatures and behaviour, and go on refusing metric 2 ----
+ *
+ * Input: the nodes of dcrx_cdr3_network (class c_i, string s_i, weight w_i; m < 2^30), a cost (dcrx_cdr3_cost_t) and a radius R,
+ *   0 .. 65535, with the rules and the DCRX_E_INVALID refusals of "match, weighted" (one routine checks both).
+ * In reach: as under "match, weighted", 1 <= len <= 32 and every byte in 'A' .. 'Z'.  A node outside that reach has no
+ *   neighbours: degree 0, a cluster of its own, in nobody's row.  stats.out_of_reach keeps the network's meaning: length alone.
+ * Edge: i != j, both in reach, c_i == c_j, dist(s_i, s_j) <= R, dist exactly that of "match, weighted".  Equal strings in one
+ *   class are linked at distance 0 (two J calls under class v).
+ * Output: as dcrx_cdr3_network — degree, the CSR adjacency with every row in ascending rank, cluster_of, the cluster rows by
+ *   head ascending, dcrx_cdr3_network_stats_t (edges: the pairs within R) — and per adjacency entry the distance the device
+ *   computed.  The adjacency is symmetric and so are its distances; clusters are the connected components (a chain links its
+ *   ends).  Everything is a function of the input alone.
+ * The steps: keys, the stable sort by class and the run marks by class as under Levenshtein, the gather without presence
+ *   masks, then cdr3_walk_kernel<WRITE, Within, Weighted>: the table walked against itself from each block's first class
+ *   start, a node never testing its own entry.  Every unordered pair is computed twice, once by the shorter string's lane
+ *   (which reads the other string at i and i + d) and once by the longer string's (which shifts its own words down by d bytes). */
+
+/* Bytes of device work space dcrx_cdr3_neighbours_weighted_device needs for m nodes (no presence masks: what
+ * dcrx_cdr3net_work_bytes gives); 0 for m >= 2^30. */
+uint64_t dcrx_cdr3net_weighted_work_bytes(uint64_t m, uint64_t text_bytes);
+
+/* The primitive: dcrx_cdr3_neighbours_metric_device's arguments, adj_cap / d_adj_need rules and null, alignment and
+ * short-work-space refusals, with (cost, radius) in place of (distance, metric).  `cost` is a HOST pointer: the call checks it
+ * and copies it (it travels to the kernels as a launch argument).  d_adj_dist (adj_cap entries, device) receives every written
+ * neighbour's distance beside d_adj; it may be NULL.  Asynchronous on hip_stream. */
+int dcrx_cdr3_neighbours_weighted_device(uint64_t m, const uint32_t *d_class, const uint64_t *d_off, const char *d_text,
+                                         uint64_t text_bytes, const dcrx_cdr3_cost_t *cost, uint32_t radius, uint32_t *d_degree,
+                                         uint64_t *d_adj_off, uint32_t *d_adj, uint32_t *d_adj_dist, uint64_t adj_cap,
+                                         uint64_t *d_adj_need, void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* dcrx_cdr3_network_metric's arguments, rules and errors with (cost, radius) in place of (distance, metric), and adj_dist_out
+ * (adj_cap entries; may be NULL) beside adj_out: written wherever adj_out is. */
+int64_t dcrx_cdr3_network_weighted(uint64_t m, const uint32_t *cls, const uint64_t *off, const char *text, const uint64_t *weight,
+                                   const dcrx_cdr3_cost_t *cost, uint32_t radius, uint32_t *degree_out, uint32_t *cluster_of_out,
+                                   uint32_t *head_out, uint32_t *n_nodes_out, uint64_t *weight_out, uint64_t *adj_off_out,
+                                   uint32_t *adj_out, uint32_t *adj_dist_out, uint64_t adj_cap, uint64_t *adj_need_out,
+                                   dcrx_cdr3_network_stats_t *stats_out);
+
+/* dcrx_format_cdr3_edges with the weighted distance in the distance column, computed here on the host as the literal minimum
+ * over every p in 0 .. la (dcrx_format_cdr3_matches_weighted's routine, not the device's one-pass form).  DCRX_E_INVALID in
+ * addition for a cost the contract refuses and for an edge between strings out of reach or with a byte outside 'A' .. 'Z'. */
+int64_t dcrx_format_cdr3_edges_weighted(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off,
+                                        const char *text, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
