@@ -440,6 +440,23 @@ class Cdr3CostC(C.Structure):      # dcrx_cdr3_cost_t
     _fields_ = [("sub", (C.c_uint8 * 32) * 32), ("gap", C.c_uint32), ("ntrim", C.c_uint32), ("ctrim", C.c_uint32)]
 
 
+CDR3_MOTIF_MAX_SAMPLES = 64          # files of one `motifs` call
+CDR3_MOTIF_MAX_TRIM = 16             # DCRX_CDR3_MOTIF_MAX_TRIM
+CDR3_MOTIF_MAX_RESAMPLES = 65535     # DCRX_CDR3_MOTIF_MAX_RESAMPLES
+CDR3_MOTIF_KS = (2, 3, 4)            # DCRX_CDR3_MOTIF_K_ALL: a k_mask has bit k set for every k of K
+CDR3_MOTIF_MAX_UNITS = 1 << 30       # dcrx_cdr3_motifs: DCRX_E_UNSUPPORTED from here on
+CDR3_MOTIF_STATS = ("sample_units", "sample_take_part", "sample_out_of_reach", "sample_not_letters", "background_units",
+                    "background_take_part", "background_out_of_reach", "background_not_letters", "motifs", "reported")
+CDR3_MOTIF_OUTPUTS = (("k", np.uint32), ("code", np.uint32), ("cs", np.uint32), ("cb", np.uint32), ("ge", np.uint32), ("sum", np.uint64),
+                      ("max", np.uint32))
+CDR3_MOTIF_COLUMNS = ["motif", "k", "cdr3s", "background_cdr3s", "resamples", "resamples_at_least", "resample_sum", "resample_max",
+                      "expected", "fold", "p_value"]
+
+
+class Cdr3MotifStatsC(C.Structure):      # dcrx_cdr3_motif_stats_t
+    _fields_ = [(k, C.c_uint64) for k in CDR3_MOTIF_STATS]
+
+
 OVERLAP_MAX_SAMPLES = 64       # DCRX_OVERLAP_MAX_SAMPLES
 OVERLAP_MAX_ROWS = 1 << 30     # dcrx_overlap_run: DCRX_E_UNSUPPORTED from here on
 OVERLAP_PLANES = ("shared", "shared_weight", "min_weight", "prod_lo", "prod_hi")      # enum dcrx_overlap_plane
@@ -502,6 +519,7 @@ EXPORTS = [
     "dcrx_format_cdr3_matches_weighted",
     "dcrx_cdr3net_weighted_work_bytes", "dcrx_cdr3_neighbours_weighted_device", "dcrx_cdr3_network_weighted",
     "dcrx_format_cdr3_edges_weighted",
+    "dcrx_cdr3_motifs_work_bytes", "dcrx_cdr3_motifs_device", "dcrx_cdr3_motifs",
 ]
 
 _lib = None
@@ -678,6 +696,11 @@ def lib():
         "dcrx_cdr3_network_weighted": (C.c_int64, [u64, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
                                                    C.POINTER(Cdr3NetworkStatsC)]),
         "dcrx_format_cdr3_edges_weighted": (C.c_int64, [u64, vp, vp, vp, vp, vp, vp, u64]),
+        "dcrx_cdr3_motifs_work_bytes": (u64, [u64, u64, u32]),
+        "dcrx_cdr3_motifs_device": (i32, [u64, vp, vp, u64, vp, vp, u32, u32, u32, u32, u32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, u64, vp]),
+        "dcrx_cdr3_motifs": (i32, [u64, vp, vp, u64, vp, vp, u32, u32, u32, u32, u32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   C.POINTER(Cdr3MotifStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1969,6 +1992,67 @@ def abundance_classes(samples, groups, weights, n_samples: int) -> dict:
     k = check(int(lib().dcrx_abundance_classes(S, n, smp.ctypes.data, grp.ctypes.data, w.ctypes.data, off.ctypes.data, count.ctypes.data,
                                                mult.ctypes.data)))
     return {"class_off": off, "class_count": count[:k].copy(), "class_mult": mult[:k].copy()}
+
+
+# ---- motifs (`motifs`): include/dcrx.h "motifs" ----
+
+def cdr3_motif_k_mask(ks) -> int:
+    """The k_mask of K (an iterable of 2, 3, 4)."""
+    ks = [int(k) for k in ks]
+    if not ks or any(k not in CDR3_MOTIF_KS for k in ks):
+        raise ValueError("motifs: K is a non-empty subset of 2, 3, 4")
+    return sum(1 << k for k in set(ks))
+
+
+def cdr3_motif_text(k: int, code: int) -> str:
+    """The letters of the motif (k, code)."""
+    return "".join(chr(65 + code // 26 ** (k - 1 - i) % 26) for i in range(k))
+
+
+def cdr3_motifs_work_bytes(n: int, m: int, resamples: int) -> int:
+    """dcrx_cdr3_motifs_work_bytes: the work space dcrx_cdr3_motifs_device takes (0: refused)."""
+    return int(lib().dcrx_cdr3_motifs_work_bytes(int(n), int(m), int(resamples)))
+
+
+def cdr3_motifs(s_off, s_text: bytes, b_off, b_text: bytes, ks=CDR3_MOTIF_KS, trim=(3, 3), min_count: int = 3, resamples: int = 1000,
+                seed: int = 1, cap: int | None = None) -> dict:
+    """dcrx_cdr3_motifs on the current device: n sample units and m background units (offsets into one text each) -> the
+    reported motifs in motif order: {"k", "code", "cs", "cb", "ge", "max" (uint32), "sum" (uint64): min(need, cap) rows each,
+    "need": the reported motifs, "stats": CDR3_MOTIF_STATS}.  cap None: as many rows as are needed (a second call where the
+    first one's guess fell short)."""
+    so, bo = np.ascontiguousarray(s_off, dtype=np.uint64), np.ascontiguousarray(b_off, dtype=np.uint64)
+    if len(so) < 1 or len(bo) < 1:
+        raise ValueError("motifs: count + 1 offsets per side")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("motifs: the seed is 0 .. 2^64 - 1")
+    n, m = len(so) - 1, len(bo) - 1
+    mask = cdr3_motif_k_mask(ks)
+    st, s_buf, b_buf = Cdr3MotifStatsC(), _buf(s_text), _buf(b_text)
+    rows = min(n * 90, 475228) if cap is None else int(cap)
+    while True:
+        out = {name: np.zeros(max(rows, 1), dt) for name, dt in CDR3_MOTIF_OUTPUTS}
+        need = np.zeros(1, np.uint64)
+        check(lib().dcrx_cdr3_motifs(n, so.ctypes.data, s_buf.ctypes.data, m, bo.ctypes.data, b_buf.ctypes.data, mask, int(trim[0]), int(trim[1]), int(min_count),
+                                     int(resamples), int(seed), rows, *(out[name].ctypes.data for name, _ in CDR3_MOTIF_OUTPUTS[:5]),
+                                     out["sum"].ctypes.data, out["max"].ctypes.data, need.ctypes.data, C.byref(st)))
+        if cap is not None or int(need[0]) <= rows:
+            break
+        rows = int(need[0])
+    got = min(int(need[0]), rows)
+    result = {name: out[name][:got].copy() for name, _ in CDR3_MOTIF_OUTPUTS}
+    result["need"] = int(need[0])
+    result["stats"] = {k: int(getattr(st, k)) for k in CDR3_MOTIF_STATS}
+    return result
+
+
+def cdr3_motifs_device(n: int, d_s_off, d_s_text, m: int, d_b_off, d_b_text, ks, trim, min_count: int, resamples: int, seed: int,
+                       cap: int, d_k, d_code, d_cs, d_cb, d_ge, d_sum, d_max, d_need, d_stats, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_motifs_device: the primitive over units in HBM (DeviceBuffers), asynchronous on `stream`; nothing is copied
+    back."""
+    check(lib().dcrx_cdr3_motifs_device(int(n), d_s_off.ptr, d_s_text.ptr, int(m), d_b_off.ptr, d_b_text.ptr, cdr3_motif_k_mask(ks),
+                                        int(trim[0]), int(trim[1]), int(min_count), int(resamples), int(seed), int(cap), d_k.ptr,
+                                        d_code.ptr, d_cs.ptr, d_cb.ptr, d_ge.ptr, d_sum.ptr, d_max.ptr, d_need.ptr, d_stats.ptr,
+                                        d_work.ptr, int(work_bytes), stream))
 
 
 def merge_parents_device(tables: "Tables", n: int, d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, d_ins_text, text_bytes: int,

@@ -239,6 +239,33 @@ def _match(p: argparse.ArgumentParser):
                    help="The database column that holds the J call (default j_call; a VDJdb export: J); read when the class needs it")
 
 
+def _motifs(p: argparse.ArgumentParser):
+    p.add_argument("-in", "--infile", type=str, nargs="+", required=True,
+                   help="1 to 64 .clonotypes.tsv files (plain or .gz), one per sample; a sample is named by its file name "
+                        "without .clonotypes.tsv[.gz]")
+    p.add_argument("-bg", "--background", type=str, required=True,
+                   help="The background repertoire: a tab-separated table (plain or .gz) with a header line, its CDR3 column found "
+                        "by name; another sample's .clonotypes.tsv is one as it stands")
+    p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
+    p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
+    p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
+    p.add_argument("--bg-cdr3-column", dest="bg_cdr3_column", type=str, default="junction_aa",
+                   help="The background column that holds the CDR3 amino acids (default junction_aa)")
+    p.add_argument("--motif-k", dest="motif_k", type=str, default=None,
+                   help="The motif lengths, a comma-separated list out of 2, 3, 4 (default 2,3,4)")
+    p.add_argument("--motif-trim", dest="motif_trim", type=str, default=None,
+                   help="N,C - the first N and the last C residues of a CDR3 hold no motif, 0 to 16 each (default 3,3, after "
+                        "GLIPH: a design choice, not a measured optimum)")
+    p.add_argument("--motif-min-count", dest="motif_min_count", type=int, default=None,
+                   help="A motif is reported when at least this many of the sample's distinct CDR3s hold it (1 or more; default 3, "
+                        "a design choice)")
+    p.add_argument("--resamples", dest="resamples", type=int, default=None,
+                   help="How many times as many background CDR3s as the sample has are drawn without replacement (GPU), 0 to "
+                        "65535 (default 1000); 0 gives the counts alone")
+    p.add_argument("--seed", dest="seed", type=int, default=None,
+                   help="The seed of the draws, 0 .. 2^64 - 1 (default 1); the same seed gives the same files")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -246,8 +273,9 @@ def create_parser() -> argparse.ArgumentParser:
                     "Sub-commands as in the reference; the grouping / clustering half of `collapse` (UMI clustering, the "
                     ".freq) runs with --cluster.")
     parser.add_argument("-v", "--version", action="version", version=__version__)
-    parser.epilog = ("A further command has a parser of its own: `match` (clonotypes near a database's CDR3s, GPU); see "
-                     "`python -m decombinator_amd match --help`.")
+    parser.epilog = ("Further commands have parsers of their own: `match` (clonotypes near a database's CDR3s, GPU) and `motifs` "
+                     "(CDR3 k-mers enriched against a background, GPU); see `python -m decombinator_amd match --help` and "
+                     "`python -m decombinator_amd motifs --help`.")
     sub = parser.add_subparsers(dest="command", help="Available commands")
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
@@ -287,10 +315,23 @@ def create_match_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def create_motifs_parser() -> argparse.ArgumentParser:
+    """The parser of `motifs`, a sub-command with a parser of its own, as `match` is."""
+    parser = argparse.ArgumentParser(
+        prog="python -m decombinator_amd motifs",
+        description="CDR3 motif enrichment against a background (GPU): which 2-, 3- and 4-mers in the middle of the CDR3s of "
+                    ".clonotypes.tsv files occur in more of a sample's distinct CDR3s than in as many CDR3s drawn from a "
+                    "background repertoire; writes <sample>.cdr3_motifs.tsv per sample.")
+    _motifs(parser)
+    return parser
+
+
 def cli_args(argv=None) -> dict:
     words = sys.argv[1:] if argv is None else list(argv)
     if words and words[0] == "match":
         return dict(vars(create_match_parser().parse_args(words[1:])), command="match")
+    if words and words[0] == "motifs":
+        return dict(vars(create_motifs_parser().parse_args(words[1:])), command="motifs")
     inp = vars(create_parser().parse_args(argv))
     if "merge_errors" in inp:
         # which of the merge options the command line named (they are refused without --merge-errors), then the defaults
@@ -461,6 +502,12 @@ def write_out_match(text: bytes, name: str, inputargs: dict):
     """A file of the `match` sub-command: `<outpath><prefix><name>` (<sample>.cdr3_matches.tsv, match_targets.tsv), with
     write_out_overlap's rules.  Returns the file's name."""
     return write_out_overlap(text, name, inputargs, what="match")
+
+
+def write_out_motifs(text: bytes, name: str, inputargs: dict):
+    """A file of the `motifs` sub-command: `<outpath><prefix><name>` (<sample>.cdr3_motifs.tsv), with write_out_overlap's rules.
+    Returns the file's name."""
+    return write_out_overlap(text, name, inputargs, what="motif")
 
 
 def write_out_cdr3_clusters(network, inputargs: dict):

@@ -194,6 +194,14 @@ def main(argv=None):
             from .io import create_match_parser
             create_match_parser().error(str(e))
         return
+    if inp["command"] == "motifs":      # ... and this one: clonotype tables against a background repertoire
+        from . import motifs
+        try:
+            motifs.run(inp)
+        except ValueError as e:
+            from .io import create_motifs_parser
+            create_motifs_parser().error(str(e))
+        return
     if inp.get("clonotypes"):           # refused before anything is read
         why = clonotype_refusal(inp)
         if why:

@@ -1320,6 +1320,80 @@ int64_t dcrx_cdr3_network_weighted(uint64_t m, const uint32_t *cls, const uint64
 int64_t dcrx_format_cdr3_edges_weighted(uint64_t m, const uint64_t *adj_off, const uint32_t *adj, const uint64_t *off,
                                         const char *text, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap);
 
+/* ---- motifs (`motifs`): which short motifs (2-, 3- and 4-mers in the middle of a CDR3) a sample's CDR3s hold more often than
+ * as many CDR3s drawn from a background do, on the GPU.  The reference has no counterpart: the contract below is this library's
+ * own.  The entries only ADD to ABI 5 ----
+ *
+ * This layer knows nothing about genes or files.
+ * Units: a unit is a byte string.  Input: n sample units and m background units, n, m < 2^30, each side given as offsets
+ *   (count + 1 of them, uint64) into one text.  The units are taken as given: nothing is deduplicated here.
+ * Taking part: a unit takes part when it has 1 .. DCRX_CDR3NET_MAX_LEN (32) bytes, all 'A' .. 'Z'.  A unit of another length is
+ *   counted as out of reach, one in reach with another byte as not letters.  n' is the number of sample units that take part, m'
+ *   the number of background units that do.
+ * Motifs: K is a subset of {2, 3, 4}, given as k_mask (bit k set: k is in K); the trim is (N, C), 0 .. DCRX_CDR3_MOTIF_MAX_TRIM
+ *   (16) each.  A unit of L letters has, per k in K, the windows p with N <= p and p + k <= L - C.  A motif is (k, the k letters).
+ *   A unit contains a motif when at least one of its windows equals it: a motif that occurs twice in a unit counts once.  A unit
+ *   too short for any window still takes part (it counts in n' and m', and it can be drawn).  Motifs are ordered by (k, letters)
+ *   ascending; the code of a motif is its letters ('A' = 0 .. 'Z' = 25) as a number to the base 26, the first letter leading, so
+ *   that (k, code) ascending is the same order.
+ * Counts: cs(motif) = the sample units that take part and contain it; cb(motif) = the background units that take part and
+ *   contain it.  The reported motifs are those with cs >= min_count (min_count >= 1), in motif order; `need` is their number.
+ * Resampling: R resamples, 0 .. DCRX_CDR3_MOTIF_MAX_RESAMPLES (65535).  Resample r keeps the n' background units that take
+ *   part whose key(seed, r, b) are smallest, b the unit's index in the background as given and key the function of "downsample"
+ *   above (sample = r, read = b).  The keys of one resample are pairwise distinct: there is no tie rule.  c_r(motif) = the kept
+ *   units that contain the motif.  Per reported motif: ge = #{r : c_r >= cs}, sum = the sum over r of c_r, max = the largest
+ *   c_r.  n' = m' is legal (every resample is the whole background); n' > m' with R > 0 is DCRX_E_INVALID where the host can
+ *   see it.  R = 0 gives cs and cb alone (ge, sum, max 0).
+ * Everything is an integer and a function of the input alone: no launch shape, order of arrival or work-space size enters it.
+ * Output: rows 0 .. min(need, cap) - 1 of seven caller arrays of `cap` rows — k, code, cs, cb, ge, max (uint32) and sum
+ *   (uint64) —, `need` whole whatever `cap` is, and the statistics. */
+#define DCRX_CDR3_MOTIF_MAX_TRIM 16
+#define DCRX_CDR3_MOTIF_MAX_RESAMPLES 65535
+#define DCRX_CDR3_MOTIF_K_ALL 0x1Cu /* k_mask of K = {2, 3, 4} */
+
+typedef struct dcrx_cdr3_motif_stats {
+  uint64_t sample_units, sample_take_part, sample_out_of_reach, sample_not_letters;
+  uint64_t background_units, background_take_part, background_out_of_reach, background_not_letters;
+  uint64_t motifs;        /* distinct motifs with cs >= 1 */
+  uint64_t reported;      /* ... with cs >= min_count: `need` */
+} dcrx_cdr3_motif_stats_t;
+
+/* Bytes of device work space dcrx_cdr3_motifs_device needs for n sample units, m background units and R resamples; 0 for
+ * n or m >= 2^30 and for R above DCRX_CDR3_MOTIF_MAX_RESAMPLES.  The resamples are worked off in chunks: a chunk's kept lists
+ * (n indices per resample) and its plane of counts (a row of min(475 228, 90 n) motifs per resample) take 2^25 dwords at most,
+ * and a chunk holds 1 .. 64 resamples. */
+uint64_t dcrx_cdr3_motifs_work_bytes(uint64_t n, uint64_t m, uint32_t resamples);
+
+/* The primitive, asynchronous on `hip_stream`, everything in device memory: d_s_off n + 1 and d_b_off m + 1 offsets into
+ * d_s_text and d_b_text; the seven output arrays of `cap` rows each (they may be NULL where cap is 0); d_need one uint64 and
+ * d_stats one dcrx_cdr3_motif_stats_t.  Nothing is copied back and nothing waits.  The steps: a lane per unit packs it as the
+ * CDR3 walk packs a string and decides whether it takes part; a lane per unit adds one onto cs (cb) of each of its motifs in a
+ * table over all 475 228 motifs (integer atomics whose results are not read); an ordered compaction of the table gives the
+ * reported motifs and every motif's row.  Per chunk of resamples: a block per resample finds the resample's threshold — a
+ * histogram of the keys' top 8 bits in LDS, then of the next 8 bits among the keys of the threshold's bin while that bin holds
+ * more than 512 keys, then the bin's keys written out and the one with the wanted number of smaller keys; keys are computed
+ * where they are needed and never stored — and writes the indices of the n' kept units; a lane per kept unit of the chunk
+ * adds one per motif of the unit onto the resample's row of the plane; a lane per reported motif folds the chunk's rows into
+ * ge, sum and max.  The work is split by kept units: only the n' units of a resample are looked at, not the background's m'.
+ * d_work: dcrx_cdr3_motifs_work_bytes(n, m, resamples) bytes, 256-byte aligned; a smaller one is DCRX_E_INVALID, not a launch.
+ * DCRX_E_INVALID also for a null argument, a k_mask that is 0 or has a bit outside DCRX_CDR3_MOTIF_K_ALL, a trim above 16,
+ * min_count 0 and resamples above 65535; DCRX_E_UNSUPPORTED for n or m >= 2^30.  What only the device can see: with n' > m'
+ * and resamples > 0 nothing is resampled (ge, sum and max stay 0; the statistics carry both numbers); offsets that go down
+ * are outside the contract. */
+int dcrx_cdr3_motifs_device(uint64_t n, const uint64_t *d_s_off, const char *d_s_text, uint64_t m, const uint64_t *d_b_off,
+                            const char *d_b_text, uint32_t k_mask, uint32_t ntrim, uint32_t ctrim, uint32_t min_count,
+                            uint32_t resamples, uint64_t seed, uint64_t cap, uint32_t *d_k, uint32_t *d_code, uint32_t *d_cs,
+                            uint32_t *d_cb, uint32_t *d_ge, uint64_t *d_sum, uint32_t *d_max, uint64_t *d_need,
+                            dcrx_cdr3_motif_stats_t *d_stats, void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* The host entry, synchronous on the current device, on host arrays of the same shapes: checks the arguments (all of the
+ * contract's refusals, n' > m' with resamples > 0 among them, and offsets that go down, before any device call), uploads, runs
+ * the primitive on the null stream, copies back the rows below min(need, cap), `need` and the statistics. */
+int dcrx_cdr3_motifs(uint64_t n, const uint64_t *s_off, const char *s_text, uint64_t m, const uint64_t *b_off, const char *b_text,
+                     uint32_t k_mask, uint32_t ntrim, uint32_t ctrim, uint32_t min_count, uint32_t resamples, uint64_t seed,
+                     uint64_t cap, uint32_t *k_out, uint32_t *code_out, uint32_t *cs_out, uint32_t *cb_out, uint32_t *ge_out,
+                     uint64_t *sum_out, uint32_t *max_out, uint64_t *need_out, dcrx_cdr3_motif_stats_t *stats_out);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
