@@ -457,6 +457,17 @@ class Cdr3MotifStatsC(C.Structure):      # dcrx_cdr3_motif_stats_t
     _fields_ = [(k, C.c_uint64) for k in CDR3_MOTIF_STATS]
 
 
+CDR3_MOTIF_COUNT = 26 ** 2 + 26 ** 3 + 26 ** 4      # 475 228: every motif, and the most that can be selected
+CDR3_MOTIF_GROUP_STATS = ("units", "take_part", "selected", "member_pairs", "global_edges", "groups", "singleton_groups", "largest_group",
+                          "mixed_groups", "rounds")
+CDR3_GROUP_COLUMNS = ["junction_aa", "clonotypes", "duplicate_count", "group", "group_cdr3s", "group_duplicate_count", "degree", "motifs"]
+CDR3_MOTIF_MEMBER_COLUMNS = ["motif", "k", "junction_aa", "position", "group"]
+
+
+class Cdr3MotifGroupStatsC(C.Structure):      # dcrx_cdr3_motif_group_stats_t
+    _fields_ = [(k, C.c_uint64) for k in CDR3_MOTIF_GROUP_STATS]
+
+
 OVERLAP_MAX_SAMPLES = 64       # DCRX_OVERLAP_MAX_SAMPLES
 OVERLAP_MAX_ROWS = 1 << 30     # dcrx_overlap_run: DCRX_E_UNSUPPORTED from here on
 OVERLAP_PLANES = ("shared", "shared_weight", "min_weight", "prod_lo", "prod_hi")      # enum dcrx_overlap_plane
@@ -520,6 +531,8 @@ EXPORTS = [
     "dcrx_cdr3net_weighted_work_bytes", "dcrx_cdr3_neighbours_weighted_device", "dcrx_cdr3_network_weighted",
     "dcrx_format_cdr3_edges_weighted",
     "dcrx_cdr3_motifs_work_bytes", "dcrx_cdr3_motifs_device", "dcrx_cdr3_motifs",
+    "dcrx_cdr3_motif_members_work_bytes", "dcrx_cdr3_motif_members_device", "dcrx_cdr3_groups_work_bytes", "dcrx_cdr3_groups_device",
+    "dcrx_cdr3_motif_groups",
 ]
 
 _lib = None
@@ -701,6 +714,12 @@ def lib():
                                           vp, u64, vp]),
         "dcrx_cdr3_motifs": (i32, [u64, vp, vp, u64, vp, vp, u32, u32, u32, u32, u32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp,
                                    C.POINTER(Cdr3MotifStatsC)]),
+        "dcrx_cdr3_motif_members_work_bytes": (u64, [u64, u64]),
+        "dcrx_cdr3_motif_members_device": (i32, [u64, vp, vp, u32, u32, u32, u64, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
+        "dcrx_cdr3_groups_work_bytes": (u64, [u64, u64]),
+        "dcrx_cdr3_groups_device": (i32, [u64, vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "dcrx_cdr3_motif_groups": (i32, [u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
+                                         C.POINTER(Cdr3MotifGroupStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -2053,6 +2072,119 @@ def cdr3_motifs_device(n: int, d_s_off, d_s_text, m: int, d_b_off, d_b_text, ks,
                                         int(trim[0]), int(trim[1]), int(min_count), int(resamples), int(seed), int(cap), d_k.ptr,
                                         d_code.ptr, d_cs.ptr, d_cb.ptr, d_ge.ptr, d_sum.ptr, d_max.ptr, d_need.ptr, d_stats.ptr,
                                         d_work.ptr, int(work_bytes), stream))
+
+
+# ---- motif groups (`motifs --groups`): include/dcrx.h "motif groups" ----
+
+def _selected_arrays(sel_k, sel_code):
+    k, code = np.ascontiguousarray(sel_k, dtype=np.uint32), np.ascontiguousarray(sel_code, dtype=np.uint32)
+    if k.ndim != 1 or k.shape != code.shape:
+        raise ValueError("motif groups: one k and one code per selected motif")
+    return k, code
+
+
+def _ptr(a):
+    return a.ctypes.data if len(a) else None
+
+
+def cdr3_motif_members_work_bytes(n: int, cap: int) -> int:
+    """dcrx_cdr3_motif_members_work_bytes: the work space dcrx_cdr3_motif_members_device takes (0: refused)."""
+    return int(lib().dcrx_cdr3_motif_members_work_bytes(int(n), int(cap)))
+
+
+def cdr3_groups_work_bytes(n: int, S: int) -> int:
+    """dcrx_cdr3_groups_work_bytes: the work space dcrx_cdr3_groups_device takes (0: refused)."""
+    return int(lib().dcrx_cdr3_groups_work_bytes(int(n), int(S)))
+
+
+def cdr3_motif_members_device(n: int, d_off, d_text, ks, trim, S: int, d_sel_k, d_sel_code, cap: int, d_n_motifs, d_mem_off, d_mem, d_need,
+                              d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_motif_members_device: the members primitive over units in HBM (DeviceBuffers), asynchronous on `stream`;
+    nothing is copied back.  d_mem None with cap 0: a counting call."""
+    opt = lambda b: b.ptr if b is not None else None
+    check(lib().dcrx_cdr3_motif_members_device(int(n), d_off.ptr, opt(d_text), cdr3_motif_k_mask(ks), int(trim[0]), int(trim[1]), int(S),
+                                               opt(d_sel_k), opt(d_sel_code), int(cap), d_n_motifs.ptr, d_mem_off.ptr, opt(d_mem), d_need.ptr,
+                                               d_work.ptr, int(work_bytes), stream))
+
+
+def cdr3_groups_device(n: int, d_weight, d_adj_off, d_adj, adj_entries: int, S: int, d_mem_off, d_mem, mem_entries: int, d_group_of, d_head,
+                       d_units, d_weight_out, d_groups, d_work, work_bytes: int, stream=None) -> int:
+    """dcrx_cdr3_groups_device: the groups primitive over an adjacency and member rows in HBM (DeviceBuffers), on `stream`
+    (it waits for the stream once per round); nothing is copied back.  Returns the number of rounds."""
+    opt = lambda b: b.ptr if b is not None else None
+    rounds = C.c_uint32(0)
+    check(lib().dcrx_cdr3_groups_device(int(n), d_weight.ptr, d_adj_off.ptr, opt(d_adj), int(adj_entries), int(S), opt(d_mem_off), opt(d_mem),
+                                        int(mem_entries), d_group_of.ptr, d_head.ptr, d_units.ptr, d_weight_out.ptr, d_groups.ptr,
+                                        C.byref(rounds), d_work.ptr, int(work_bytes), stream))
+    return int(rounds.value)
+
+
+def cdr3_motif_groups(off, text: bytes, weights, ks, trim, sel_k, sel_code, distance: int = 1, mem_cap: int | None = None) -> dict:
+    """dcrx_cdr3_motif_groups on the current device: n units (offsets into one text) with a weight each, the selected motifs
+    (k, code) in motif order and the global distance (0: none) -> {"group_of", "n_motifs", "degree" per unit; "head", "units",
+    "weight" per group; "mem_off" (S + 1) and "mem": the members of every selected motif, rows laid end to end; "need": their
+    number; "stats": CDR3_MOTIF_GROUP_STATS}.  mem_cap None: the members whole (a second call where the first one's guess
+    fell short); otherwise "mem" is empty unless they fit mem_cap."""
+    o = np.ascontiguousarray(off, dtype=np.uint64)
+    if len(o) < 1:
+        raise ValueError("motif groups: count + 1 offsets")
+    n = len(o) - 1
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    if len(w) != n:
+        raise ValueError("motif groups: one weight per unit")
+    k, code = _selected_arrays(sel_k, sel_code)
+    S = len(k)
+    mask, buf, st = cdr3_motif_k_mask(ks), _buf(text), Cdr3MotifGroupStatsC()
+    rows = min(n * min(S, 90), 1 << 22) if mem_cap is None else int(mem_cap)
+    while True:
+        group_of, n_motifs, degree, head, units = (np.zeros(max(n, 1), np.uint32) for _ in range(5))
+        weight_out, mem_off, mem = np.zeros(max(n, 1), np.uint64), np.zeros(S + 1, np.uint64), np.zeros(max(rows, 1), np.uint32)
+        need = C.c_uint64(0)
+        check(lib().dcrx_cdr3_motif_groups(n, o.ctypes.data, buf.ctypes.data, w.ctypes.data, mask, int(trim[0]), int(trim[1]), S, _ptr(k),
+                                           _ptr(code), int(distance), group_of.ctypes.data, n_motifs.ctypes.data, degree.ctypes.data,
+                                           head.ctypes.data, units.ctypes.data, weight_out.ctypes.data, mem_off.ctypes.data,
+                                           mem.ctypes.data if rows else None, rows, C.byref(need), C.byref(st)))
+        if mem_cap is not None or need.value <= rows:
+            break
+        rows = int(need.value)
+    g = int(st.groups)
+    return {"group_of": group_of[:n].copy(), "n_motifs": n_motifs[:n].copy(), "degree": degree[:n].copy(), "head": head[:g].copy(),
+            "units": units[:g].copy(), "weight": weight_out[:g].copy(), "mem_off": mem_off,
+            "mem": mem[:need.value].copy() if need.value <= rows else mem[:0].copy(), "need": int(need.value),
+            "stats": {f: int(getattr(st, f)) for f in CDR3_MOTIF_GROUP_STATS}}
+
+
+def cdr3_motif_members(off, text: bytes, ks, trim, sel_k, sel_code, cap: int | None = None, stream=None) -> dict:
+    """dcrx_cdr3_motif_members_device over host arrays (uploaded here, copied back here): {"n_motifs" per unit, "mem_off"
+    (S + 1), "mem": min(need, cap) members, "need"}.  cap None: a counting call, then exactly `need`; cap 0: the counting call
+    alone."""
+    o = np.ascontiguousarray(off, dtype=np.uint64)
+    n = len(o) - 1
+    k, code = _selected_arrays(sel_k, sel_code)
+    S = len(k)
+    d_off, d_text = DeviceBuffer.from_host(o), DeviceBuffer.from_host(_buf(text))
+    d_k, d_code = (DeviceBuffer.from_host(a) if S else None for a in (k, code))
+    d_nm, d_mo, d_need = DeviceBuffer(4 * max(n, 1)), DeviceBuffer(8 * (S + 1)), DeviceBuffer(16)
+
+    def call(rows):
+        bytes_ = cdr3_motif_members_work_bytes(n, rows)
+        if not bytes_:
+            raise ValueError("motif members: 2^30 units or more, or cap + n is 2^31 or more")
+        d_work, d_mem = DeviceBuffer(bytes_), DeviceBuffer(4 * rows) if rows else None
+        cdr3_motif_members_device(n, d_off, d_text, ks, trim, S, d_k, d_code, rows, d_nm, d_mo, d_mem, d_need, d_work, bytes_, stream)
+        if stream is not None:
+            check(lib().dcrx_stream_synchronize(stream))
+        else:
+            synchronize()
+        return d_mem
+    d_mem = call(0 if cap is None else int(cap))
+    need = int(d_need.to_host(np.uint64, 1)[0])
+    rows = need if cap is None else int(cap)
+    if cap is None and need:
+        d_mem = call(need)
+    got = min(need, rows)
+    return {"n_motifs": d_nm.to_host(np.uint32, n), "mem_off": d_mo.to_host(np.uint64, S + 1),
+            "mem": d_mem.to_host(np.uint32, got) if got else np.zeros(0, np.uint32), "need": need}
 
 
 def merge_parents_device(tables: "Tables", n: int, d_v, d_j, d_vdel, d_jdel, d_count, d_ins_off, d_ins_text, text_bytes: int,

@@ -39,72 +39,13 @@
 
 #include "../../include/dcrx.h"
 #include "dcrx_cdr3walk.h"
+#include "dcrx_components.h"
 #include "dcrx_text.h"
 
 using dcrx::set_err;
 using namespace dcrx_cdr3walk;
 
 namespace {
-
-// ---- the host entry's kernels ----
-
-__global__ __launch_bounds__(BLOCK) void cdr3net_label_init_kernel(uint32_t n, uint32_t *__restrict__ label) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i < n) label[i] = i;
-}
-
-// a round's first half: the smallest label among a node's neighbours and itself
-__global__ __launch_bounds__(BLOCK) void cdr3net_min_kernel(const uint32_t *__restrict__ in, const uint64_t *__restrict__ adj_off,
-                                                            const uint32_t *__restrict__ adj, uint32_t n, uint32_t *__restrict__ out,
-                                                            uint32_t *__restrict__ changed) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  bool moved = false;
-  if (i < n) {
-    const uint32_t mine = in[i];
-    uint32_t l = mine;
-    for (uint64_t k = adj_off[i], end = adj_off[i + 1]; k < end; k++) l = min(l, in[adj[k]]);
-    out[i] = l;
-    moved = l != mine;
-  }
-  if (__ballot(moved) && __lane_id() == 0) *changed = 1u;
-}
-
-// ... and its second: every label followed to where it ends (a label is a rank not above its node: the chain falls)
-__global__ __launch_bounds__(BLOCK) void cdr3net_jump_kernel(const uint32_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ out) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  uint32_t l = in[i];
-  for (uint32_t next = in[l]; next != l; next = in[l]) l = next;
-  out[i] = l;
-}
-
-__global__ __launch_bounds__(BLOCK) void cdr3net_totals_kernel(const uint32_t *__restrict__ label, const uint64_t *__restrict__ weight,
-                                                               uint32_t n, unsigned long long *__restrict__ total,
-                                                               uint32_t *__restrict__ members, uint32_t *__restrict__ is_head) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t h = label[i];
-  atomicAdd(&total[h], (unsigned long long)weight[i]);
-  atomicAdd(&members[h], 1u);
-  is_head[i] = h == i ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(BLOCK) void cdr3net_rows_kernel(const uint32_t *__restrict__ heads, uint32_t c,
-                                                             const unsigned long long *__restrict__ total,
-                                                             const uint32_t *__restrict__ members, uint32_t *__restrict__ nn_out,
-                                                             uint64_t *__restrict__ w_out) {
-  const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
-  if (r >= c) return;
-  const uint32_t h = heads[r];
-  nn_out[r] = members[h];
-  w_out[r] = total[h];
-}
-
-__global__ __launch_bounds__(BLOCK) void cdr3net_cluster_of_kernel(const uint32_t *__restrict__ label, const uint32_t *__restrict__ slot,
-                                                                   uint32_t n, uint32_t *__restrict__ cluster_of) {
-  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-  if (i < n) cluster_of[i] = slot[label[i]];
-}
 
 // ---- work space of the primitive: the degree pass leaves the sorted keys and ranks (key[1], idx[1]), the bucket starts, the
 // packed strings and the presence masks there for the write pass
@@ -219,21 +160,18 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
   if (text_bytes && !text) return fail(DCRX_E_INVALID, who, "text is null");
   const uint32_t m32 = (uint32_t)m;
   int rc;
-  size_t cub_bytes = 0;
-  if ((rc = exclusive_sum_bytes<uint32_t>(m, &cub_bytes))) return rc;
 
   Pool P;
   Work W;
-  uint32_t *d_cls, *d_degree, *d_label[2], *d_changed, *d_members, *d_ishead, *d_slot, *d_heads, *d_kept, *d_nn, *d_of;
+  dcrx_components::TotalsWork T;
+  uint32_t *d_cls, *d_degree, *d_label[2], *d_changed, *d_heads, *d_nn, *d_of;
   uint64_t *d_off, *d_weight, *d_adj_off, *d_need, *d_wout;
-  unsigned long long *d_total;
-  uint8_t *d_text, *d_cub;
+  uint8_t *d_text;
   for (int pass = 0; pass < 2; pass++) {
     P.get(&d_cls, m); P.get(&d_off, m + 1); P.get(&d_text, text_bytes); P.get(&d_weight, m); P.get(&d_degree, m);
-    P.get(&d_adj_off, m + 1); P.get(&d_need, 1); P.get(&d_cub, cub_bytes); P.get(&d_label[0], m);
-    P.get(&d_label[1], m); P.get(&d_changed, 1); P.get(&d_total, m); P.get(&d_members, m); P.get(&d_ishead, m); P.get(&d_slot, m);
-    P.get(&d_heads, m); P.get(&d_kept, 1); P.get(&d_nn, m); P.get(&d_wout, m); P.get(&d_of, m);
-    if ((rc = W.carve(P, m, metric)) || (pass == 0 && (rc = P.allocate()))) return rc;
+    P.get(&d_adj_off, m + 1); P.get(&d_need, 1); P.get(&d_label[0], m); P.get(&d_label[1], m); P.get(&d_changed, 1);
+    P.get(&d_heads, m); P.get(&d_nn, m); P.get(&d_wout, m); P.get(&d_of, m);
+    if ((rc = T.carve(P, m)) || (rc = W.carve(P, m, metric)) || (pass == 0 && (rc = P.allocate()))) return rc;
   }
   if ((rc = upload_spans(m, off, text, d_off, d_text)) || (rc = to_device(d_cls, cls, m)) || (rc = to_device(d_weight, weight, m))) return rc;
   const Nodes N{d_cls, d_off, d_text, text_bytes};
@@ -249,31 +187,12 @@ int64_t network(const char *who, uint64_t m, const uint32_t *cls, const uint64_t
     return fail(DCRX_E_NOMEM, who, "the adjacency does not fit the device's memory");
   if (need && (rc = run_write(m, distance, metric, wc, d_adj_off, d_adj.get(), want_dist ? d_dist.get() : nullptr, need, W, nullptr))) return rc;
 
-  // components: rounds of the neighbourhood's smallest label, then the labels followed to their ends
-  cdr3net_label_init_kernel<<<grid_for(m), BLOCK>>>(m32, d_label[0]);
-  HIP_TRY(hipGetLastError());
-  for (uint32_t changed = need ? 1u : 0u; changed;) {
-    HIP_TRY(hipMemsetAsync(d_changed, 0, 4, nullptr));
-    cdr3net_min_kernel<<<grid_for(m), BLOCK>>>(d_label[0], d_adj_off, d_adj, m32, d_label[1], d_changed);
-    HIP_TRY(hipGetLastError());
-    cdr3net_jump_kernel<<<grid_for(m), BLOCK>>>(d_label[1], m32, d_label[0]);
-    HIP_TRY(hipGetLastError());
-    if ((rc = to_host(&changed, d_changed, 1))) return rc;      // (the round's one synchronisation)
-  }
-
-  // totals onto the heads; the heads in rank order are the rows
-  const Scratch cub{d_cub, cub_bytes};
-  HIP_TRY(hipMemsetAsync(d_total, 0, m * 8, nullptr));
-  HIP_TRY(hipMemsetAsync(d_members, 0, m * 4, nullptr));
-  cdr3net_totals_kernel<<<grid_for(m), BLOCK>>>(d_label[0], d_weight, m32, d_total, d_members, d_ishead);
-  HIP_TRY(hipGetLastError());
-  if ((rc = compact(cub, d_ishead, d_slot, m32, PutIndex{d_heads}, d_kept, nullptr))) return rc;
+  // components (dcrx_components.h): rounds of the neighbourhood's smallest label, then the labels followed to their ends;
+  // totals onto the heads, and the heads in rank order are the rows
+  if ((rc = dcrx_components::components(m32, d_adj_off, d_adj, need != 0, nullptr, d_label, d_changed, nullptr, nullptr)) ||
+      (rc = dcrx_components::totals(m32, d_label[0], d_weight, T, d_of, d_heads, d_nn, d_wout, nullptr))) return rc;
   uint32_t c = 0;
-  if ((rc = to_host(&c, d_kept, 1))) return rc;
-  cdr3net_rows_kernel<<<grid_for(c), BLOCK>>>(d_heads, c, d_total, d_members, d_nn, d_wout);
-  HIP_TRY(hipGetLastError());
-  cdr3net_cluster_of_kernel<<<grid_for(m), BLOCK>>>(d_label[0], d_slot, m32, d_of);
-  HIP_TRY(hipGetLastError());
+  if ((rc = to_host(&c, T.kept, 1))) return rc;
 
   if ((rc = to_host(degree_out, d_degree, m)) || (rc = to_host(cluster_of_out, d_of, m)) || (rc = to_host(head_out, d_heads, c)) ||
       (rc = to_host(n_nodes_out, d_nn, c)) || (rc = to_host(weight_out, d_wout, c))) return rc;

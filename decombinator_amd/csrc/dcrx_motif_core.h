@@ -90,4 +90,29 @@ DCRX_CDR3NET_HD void unit_motifs(const uint32_t *w, uint32_t stride, uint32_t L,
   }
 }
 
+// ---- motif groups (include/dcrx.h "motif groups"): the selected motifs and the members' sort
+
+DCRX_CDR3NET_HD uint32_t codes_of(uint32_t k) { return k == 2 ? 26u * 26 : k == 3 ? 26u * 26 * 26 : k == 4 ? 26u * 26 * 26 * 26 : 0u; }
+// whether (k, code) is a motif of K
+DCRX_CDR3NET_HD bool is_motif(uint32_t k_mask, uint32_t k, uint32_t code) {
+  return k >= K_MIN && k <= K_MAX && (k_mask >> k & 1u) && code < codes_of(k);
+}
+// The first of S selected motifs that is no motif of K or does not come strictly behind the one before it in motif order; S
+// where the list is in order
+DCRX_CDR3NET_HD uint64_t first_selected_fault(uint64_t S, const uint32_t *k, const uint32_t *code, uint32_t k_mask) {
+  for (uint64_t s = 0; s < S; s++) {
+    if (!is_motif(k_mask, k[s], code[s])) return s;
+    if (s && motif_id(k[s], code[s]) <= motif_id(k[s - 1], code[s - 1])) return s;
+  }
+  return S;
+}
+
+// The members' sort: a posting is (row, unit), written in unit order and sorted stably by its row over MEMBER_ROW_BITS bits, so
+// that the rows come out laid end to end, each in unit order.  A slot that holds no posting carries NO_MEMBER_ROW, which lies
+// behind every row under those bits.
+constexpr uint32_t MEMBER_ROW_BITS = 19;
+constexpr uint64_t NO_MEMBER_ROW = ~0ull;
+static_assert(MOTIFS <= (1u << MEMBER_ROW_BITS) - 1, "NO_MEMBER_ROW's low bits lie behind every row");
+constexpr uint64_t MAX_MEMBER_KEYS = 1ull << 31;      // cap + n stays below it: what one sort takes
+
 }  // namespace dcrx_motif

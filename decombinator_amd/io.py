@@ -264,6 +264,20 @@ def _motifs(p: argparse.ArgumentParser):
                         "65535 (default 1000); 0 gives the counts alone")
     p.add_argument("--seed", dest="seed", type=int, default=None,
                    help="The seed of the draws, 0 .. 2^64 - 1 (default 1); the same seed gives the same files")
+    p.add_argument("--groups", dest="groups", action="store_true",
+                   help="Also merge each sample's CDR3s into specificity groups (GPU): CDR3s that share a selected motif or lie "
+                        "within --group-distance residues of each other are linked, and a group is a connected component; writes "
+                        "<sample>.cdr3_groups.tsv (needs --resamples above 0)")
+    p.add_argument("--group-p-value", dest="group_p_value", type=str, default=None,
+                   help="--groups: a motif is selected when its p_value is at most this decimal, above 0 and at most 1 (default "
+                        "0.001, after GLIPH: a design choice, not a measured optimum)")
+    p.add_argument("--group-min-fold", dest="group_min_fold", type=str, default=None,
+                   help="--groups: ... and its fold is at least this decimal, 0 or more (default 10, after GLIPH: a design choice)")
+    p.add_argument("--group-distance", dest="group_distance", type=int, default=None,
+                   help="--groups: CDR3s of one length that differ in at most this many residues are linked, 0, 1 or 2 (default 1, "
+                        "after GLIPH: a design choice; 0: no such links)")
+    p.add_argument("--write-motif-members", dest="write_motif_members", action="store_true",
+                   help="--groups: also write <sample>.cdr3_motif_members.tsv, the CDR3s that hold each selected motif")
 
 
 def create_parser() -> argparse.ArgumentParser:
@@ -321,7 +335,8 @@ def create_motifs_parser() -> argparse.ArgumentParser:
         prog="python -m decombinator_amd motifs",
         description="CDR3 motif enrichment against a background (GPU): which 2-, 3- and 4-mers in the middle of the CDR3s of "
                     ".clonotypes.tsv files occur in more of a sample's distinct CDR3s than in as many CDR3s drawn from a "
-                    "background repertoire; writes <sample>.cdr3_motifs.tsv per sample.")
+                    "background repertoire; writes <sample>.cdr3_motifs.tsv per sample.  With --groups also the specificity groups "
+                    "the enriched motifs and near-identical CDR3s join the sample's CDR3s into.")
     _motifs(parser)
     return parser
 
@@ -505,7 +520,8 @@ def write_out_match(text: bytes, name: str, inputargs: dict):
 
 
 def write_out_motifs(text: bytes, name: str, inputargs: dict):
-    """A file of the `motifs` sub-command: `<outpath><prefix><name>` (<sample>.cdr3_motifs.tsv), with write_out_overlap's rules.
+    """A file of the `motifs` sub-command: `<outpath><prefix><name>` (<sample>.cdr3_motifs.tsv, and with --groups
+    <sample>.cdr3_groups.tsv and <sample>.cdr3_motif_members.tsv), with write_out_overlap's rules.
     Returns the file's name."""
     return write_out_overlap(text, name, inputargs, what="motif")
 

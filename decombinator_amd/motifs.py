@@ -5,6 +5,7 @@ sample's CDR3s than in as many CDR3s drawn from a background repertoire (GLIPH's
     python -m decombinator_amd motifs -in A.clonotypes.tsv [B.clonotypes.tsv.gz ...] -bg naive.clonotypes.tsv[.gz]
            [--bg-cdr3-column junction_aa] [--motif-k 2,3,4] [--motif-trim 3,3] [--motif-min-count 3]
            [--resamples 1000] [--seed 1] [-op DIR] [-pf dcr_] [-dz]
+           [--groups [--group-p-value 0.001] [--group-min-fold 10] [--group-distance 1] [--write-motif-members]]
 
 The samples are 1 to 64 `.clonotypes.tsv` files (overlap.read_table; a sample is named as `overlap` names it).  The background
 is any tab-separated table with a header line, its CDR3 column found by name (match.read_database's reading rules: another
@@ -23,14 +24,35 @@ Per sample `<prefix><sample>.cdr3_motifs.tsv[.gz]`: one line per reported motif,
 descending, k, motif: motif, k, cdr3s (the sample's units that hold it), background_cdr3s, resamples, resamples_at_least (the
 draws that held it at least as often as the sample), resample_sum, resample_max, expected (resample_sum / resamples), fold
 (cdr3s * resamples / resample_sum) and p_value ((resamples_at_least + 1) / (resamples + 1)); the last three exact fractions
-at six decimals, `nan` on a zero denominator."""
+at six decimals, `nan` on a zero denominator.
+
+With --groups the sample's CDR3s are merged into GLIPH-style specificity groups (include/dcrx.h "motif groups"; ONE
+_native.cdr3_motif_groups per sample).  A motif is SELECTED when its p_value is at most --group-p-value and its fold at least
+--group-min-fold (a zero resample_sum passes), both compared as exact fractions of the flags' own text; 0.001 and 10 follow
+GLIPH and are design choices, not measured optima.  Two CDR3s are linked when both hold one selected motif, or when they have one
+length and differ in at most --group-distance residues (1 after GLIPH, a design choice; 0: no such links; any residue may
+differ, not only the untrimmed middle, and V genes are not looked at); a group is a connected component.
+`<prefix><sample>.cdr3_groups.tsv[.gz]` has one line per distinct CDR3 in order of first appearance: junction_aa, clonotypes
+(the table rows with it), duplicate_count (their reads), group (numbered from 0 by first appearance, as `cluster` in
+`.cdr3_clusters.tsv`), group_cdr3s, group_duplicate_count, degree (its links of the second kind) and motifs (its selected
+motifs in motif order, comma-joined, `.` for none).  With --write-motif-members `<prefix><sample>.cdr3_motif_members.tsv[.gz]`
+lists, per selected motif in motif order, the CDR3s that hold it: motif, k, junction_aa, position (of the first window that
+holds it, 0-based from the CDR3's start) and group."""
 from __future__ import annotations
+
+import re
+from fractions import Fraction
+
+import numpy as np
 
 from . import _native as nat
 from .match import letters_only, parse_trim, read_database, spans
 from .overlap import index_fraction, read_table, sample_name
 
-DEFAULTS = {"motif_k": "2,3,4", "motif_trim": "3,3", "motif_min_count": 3, "resamples": 1000, "seed": 1}      # design choices (3,3 and 3 after GLIPH)
+DEFAULTS = {"motif_k": "2,3,4", "motif_trim": "3,3", "motif_min_count": 3, "resamples": 1000, "seed": 1,      # design choices (3,3 and 3 after GLIPH)
+            "group_p_value": "0.001", "group_min_fold": "10", "group_distance": 1}      # ... as these are (after GLIPH)
+GROUP_FLAGS = (("--group-p-value", "group_p_value"), ("--group-min-fold", "group_min_fold"), ("--group-distance", "group_distance"),
+               ("--write-motif-members", "write_motif_members"))
 
 stats: dict = {}      # per sample name, the statistics of the last run()
 
@@ -49,6 +71,12 @@ def _get(inp: dict, key: str):
 
 def _is_int(x) -> bool:
     return isinstance(x, int) and not isinstance(x, bool)
+
+
+def parse_decimal(text):
+    """The exact value of a decimal such as "0.001", "10" or ".5", or None."""
+    text = str(text).strip()
+    return Fraction(text) if re.fullmatch(r"[0-9]+(\.[0-9]*)?|\.[0-9]+", text) else None
 
 
 def refusal(inp: dict):
@@ -76,6 +104,21 @@ def refusal(inp: dict):
     seed = _get(inp, "seed")
     if not _is_int(seed) or not 0 <= seed < 1 << 64:
         return f"--seed is 0 .. 2^64 - 1, not {seed!r}"
+    if not inp.get("groups"):
+        for flag, key in GROUP_FLAGS:
+            if inp.get(key) is not None and inp.get(key) is not False:
+                return f"{flag} belongs to --groups: it is refused without it"
+        return None
+    if resamples == 0:
+        return "--groups selects motifs by their p_value: it is refused with --resamples 0"
+    p = parse_decimal(_get(inp, "group_p_value"))
+    if p is None or not 0 < p <= 1:
+        return f"--group-p-value is a decimal above 0 and at most 1, not {inp.get('group_p_value')!r}"
+    if parse_decimal(_get(inp, "group_min_fold")) is None:
+        return f"--group-min-fold is a decimal, 0 or more, not {inp.get('group_min_fold')!r}"
+    distance = _get(inp, "group_distance")
+    if not _is_int(distance) or distance not in (0, 1, 2):
+        return f"--group-distance is 0, 1 or 2, not {distance!r}"
     return None
 
 
@@ -104,9 +147,70 @@ def motifs_text(result: dict, resamples: int) -> bytes:
     return ("\n".join(out) + "\n").encode("ascii")
 
 
+def selected_rows(result: dict, resamples: int, p: Fraction, fold: Fraction) -> list:
+    """The rows of a cdr3_motifs result (motif order) that --groups selects: p_value at most p and fold at least `fold`, in exact
+    integer arithmetic — (ge + 1) / (R + 1) <= p, and cs R >= fold sum (so a zero sum passes)."""
+    R = int(resamples)
+    return [r for r, (cs, ge, total) in enumerate(zip(result["cs"], result["ge"], result["sum"]))
+            if (int(ge) + 1) * p.denominator <= p.numerator * (R + 1) and int(cs) * R * fold.denominator >= fold.numerator * int(total)]
+
+
+def groups_text(units, rows_of, reads_of, selected, groups: dict) -> bytes:
+    """The `.cdr3_groups.tsv` text: one line per unit, in unit order."""
+    off, mem = groups["mem_off"], groups["mem"]
+    held = [[] for _ in units]
+    for s, (k, code) in enumerate(selected):
+        for i in mem[int(off[s]):int(off[s + 1])]:
+            held[int(i)].append(nat.cdr3_motif_text(k, code))
+    out = ["\t".join(nat.CDR3_GROUP_COLUMNS)]
+    for i, u in enumerate(units):
+        g = int(groups["group_of"][i])
+        out.append("\t".join([u.decode("latin-1"), str(rows_of[i]), str(reads_of[i]), str(g), str(int(groups["units"][g])),
+                              str(int(groups["weight"][g])), str(int(groups["degree"][i])), ",".join(held[i]) or "."]))
+    return ("\n".join(out) + "\n").encode("latin-1")
+
+
+def members_text(units, selected, trim, groups: dict) -> bytes:
+    """The `.cdr3_motif_members.tsv` text: lines in (motif order, unit order)."""
+    off, mem = groups["mem_off"], groups["mem"]
+    out = ["\t".join(nat.CDR3_MOTIF_MEMBER_COLUMNS)]
+    for s, (k, code) in enumerate(selected):
+        motif = nat.cdr3_motif_text(k, code)
+        for i in mem[int(off[s]):int(off[s + 1])]:
+            u = units[int(i)]
+            at = u.find(motif.encode("ascii"), trim[0], len(u) - trim[1])      # the first window that holds it
+            out.append("\t".join([motif, str(k), u.decode("latin-1"), str(at), str(int(groups["group_of"][int(i)]))]))
+    return ("\n".join(out) + "\n").encode("latin-1")
+
+
+def run_groups(inp: dict, name: str, table, s_units, s_off, s_text, result: dict, ks, trim, resamples: int) -> dict:
+    """--groups for one sample: the selection from its motifs result, the one call, the printed line and the files."""
+    from .io import write_out_motifs
+    p_text, fold_text = str(_get(inp, "group_p_value")).strip(), str(_get(inp, "group_min_fold")).strip()
+    distance = int(_get(inp, "group_distance"))
+    rows = selected_rows(result, resamples, parse_decimal(p_text), parse_decimal(fold_text))
+    selected = [(int(result["k"][r]), int(result["code"][r])) for r in rows]
+    index = {u: i for i, u in enumerate(s_units)}
+    rows_of, reads_of = [0] * len(s_units), [0] * len(s_units)
+    for aa, count in zip(table[2], table[3]):
+        rows_of[index[aa]] += 1
+        reads_of[index[aa]] += count
+    groups = nat.cdr3_motif_groups(s_off, s_text, np.array([r % (1 << 64) for r in reads_of], np.uint64), ks, trim, [k for k, _ in selected],
+                                   [c for _, c in selected], distance)
+    st = groups["stats"]
+    print(f"Groups of {name} (motifs with p_value <= {p_text} and fold >= {fold_text}, distance {distance}): {st['units']:,} CDR3s, "
+          f"{st['take_part']:,} take part; {st['selected']:,} motifs selected, {st['member_pairs']:,} motif members; "
+          f"{st['global_edges']:,} links by distance; {st['groups']:,} groups ({st['singleton_groups']:,} of one CDR3, the largest of "
+          f"{st['largest_group']:,}, {st['mixed_groups']:,} with both kinds of link)")
+    files = {"groups": write_out_motifs(groups_text(s_units, rows_of, reads_of, selected, groups), name + ".cdr3_groups.tsv", inp)}
+    if inp.get("write_motif_members"):
+        files["members"] = write_out_motifs(members_text(s_units, selected, trim, groups), name + ".cdr3_motif_members.tsv", inp)
+    return {"files": files, "result": groups, "selected": selected, "stats": st}
+
+
 def run(inp: dict) -> dict:
     """The stage: refusals, the background's units, then per sample its units, the one call, the printed line and the file.
-    Returns {"motifs": [names], "results": [...], "stats": [...]}.  ValueError for what refusal() and read_database() name, for a
+    Returns {"motifs": [names], "results": [...], "stats": [...]}, and with --groups "groups": [run_groups' dicts].  ValueError for what refusal() and read_database() name, for a
     file that is no clonotype table, and for a sample with more units that take part than the background has (both numbers
     named), before the device is touched."""
     from .io import write_out_motifs
@@ -127,7 +231,8 @@ def run(inp: dict) -> dict:
     out = {"motifs": [], "results": [], "stats": []}
     stats.clear()
     for name, path in zip(names, files):
-        s_units = units_of(read_table(path)[2])
+        table = read_table(path)
+        s_units = units_of(table[2])
         s_census = census(s_units)
         if resamples and s_census["take_part"] > b_census["take_part"]:
             raise ValueError(f"{path}: {s_census['take_part']:,} CDR3s take part and the background ({inp['background']}) has only "
@@ -145,4 +250,6 @@ def run(inp: dict) -> dict:
         out["motifs"].append(write_out_motifs(motifs_text(result, resamples), name + ".cdr3_motifs.tsv", inp))
         out["results"].append(result)
         out["stats"].append(st)
+        if inp.get("groups"):
+            out.setdefault("groups", []).append(run_groups(inp, name, table, s_units, s_off, s_text, result, ks, trim, resamples))
     return out

@@ -1394,6 +1394,103 @@ int dcrx_cdr3_motifs(uint64_t n, const uint64_t *s_off, const char *s_text, uint
                      uint64_t cap, uint32_t *k_out, uint32_t *code_out, uint32_t *cs_out, uint32_t *cb_out, uint32_t *ge_out,
                      uint64_t *sum_out, uint32_t *max_out, uint64_t *need_out, dcrx_cdr3_motif_stats_t *stats_out);
 
+/* ---- motif groups (`motifs --groups`): which units hold each of a list of selected motifs, and the specificity groups — the
+ * connected components over shared selected motifs and near-identical units (GLIPH's merge of its "local" and "global"
+ * halves), on the GPU.  The reference has no counterpart: the contract below is this library's own.  The entries only ADD to
+ * ABI 5 ----
+ *
+ * This layer knows nothing about genes or files.
+ * Units: the input of "motifs" above, one side of it: n byte strings given as n + 1 offsets (uint64) into one text, n < 2^30,
+ *   taken as given; k_mask and the trim (N, C) as there.  A unit TAKES PART, and CONTAINS a motif, exactly as "motifs" says.
+ * Selected motifs: S of them, 0 <= S <= 475 228, given as two arrays (k, code) in strictly ascending motif order (so no motif
+ *   twice), every k in K and every code below 26^k.  Anything else is DCRX_E_INVALID where the host entry can see it.
+ * Members: row s holds the indices, ascending, of the units that take part and contain selected motif s.  mem_off has S + 1
+ *   entries (uint64; mem_off[0] = 0, mem_off[S] = need); mem is filled below `cap` (entries 0 .. min(need, cap) - 1 of the
+ *   rows laid end to end), and `need` is reported whole, whatever `cap` is.  n_motifs[i] is the number of selected motifs unit
+ *   i holds (0 for a unit that takes no part).
+ * Global edges: G is 0, 1 or 2; 0 means none.  Otherwise two units are linked exactly as dcrx_cdr3_neighbours_device links two
+ *   nodes under Hamming at distance G when every class is equal: both have 1 .. 32 bytes, one length, and at most G positions
+ *   differ (1 .. G between two DISTINCT strings, which is what a table of distinct units holds; two units with the same bytes
+ *   are linked as well, as that primitive links them).  Whether a byte is a letter does not matter here: a unit that takes no part for a byte outside 'A' .. 'Z' is linked
+ *   all the same.  degree[i] is that primitive's degree (0 with G = 0).  Two choices are made here, and they are choices, not
+ *   measured optima: the differing position is NOT restricted to the untrimmed middle of the string (GLIPH restricts it), and V
+ *   genes are ignored (this layer has none).
+ * Groups: a group is a connected component of the graph on the n units whose edges are the global edges and a link between any
+ *   two units that appear in one member row.  Every unit is in exactly one group; a unit with no edge — one out of reach, one
+ *   that takes no part and has no global edge, one that holds no selected motif — is a group of its own.  Groups are numbered
+ *   0 .. groups - 1 by their smallest unit index, ascending.  Per unit: group_of, n_motifs, degree.  Per group: head (its
+ *   smallest unit), units (how many) and weight (the sum of a caller-supplied uint64 weight per unit, modulo 2^64).
+ * Everything is an integer and a function of the input alone: no launch shape, order of arrival of an atomic or work-space
+ *   size enters a result. */
+typedef struct dcrx_cdr3_motif_group_stats {
+  uint64_t units, take_part;
+  uint64_t selected;          /* S */
+  uint64_t member_pairs;      /* (selected motif, unit that holds it) pairs: the members' `need` */
+  uint64_t global_edges;      /* unordered pairs of units */
+  uint64_t groups, singleton_groups, largest_group;
+  uint64_t mixed_groups;      /* groups that hold a global edge AND a member row of two or more units */
+  uint64_t rounds;            /* label rounds run, the last one (which moved nothing) included */
+} dcrx_cdr3_motif_group_stats_t;
+
+/* Bytes of device work space dcrx_cdr3_motif_members_device needs for n units and `cap` members; 0 for n >= 2^30 and for
+ * cap + n >= 2^31.  (The primitive sorts the postings of the rows that begin below `cap`: at most cap + n keys.) */
+uint64_t dcrx_cdr3_motif_members_work_bytes(uint64_t n, uint64_t cap);
+
+/* The members primitive, asynchronous on `hip_stream`, everything in device memory: d_off n + 1 offsets into d_text; d_sel_k and
+ * d_sel_code S entries each (they may be NULL where S is 0); d_n_motifs n entries; d_mem_off S + 1; d_mem `cap` entries (may be
+ * NULL where cap is 0: a counting call, which gives n_motifs, mem_off and need); d_need one uint64.  Nothing is copied back and
+ * nothing waits.  The steps: row_of over all 475 228 motifs, scattered from the S selected; a lane per unit packs it and decides
+ * whether it takes part ("motifs"' own pack step); a lane per unit counts its selected motifs (n_motifs) and adds one onto
+ * its rows' counts (integer atomics whose results are not read); an exclusive sum over the rows: mem_off and need.  With
+ * cap > 0: a lane per unit counts its postings in the rows that begin below cap; an exclusive sum over the units; a lane per
+ * unit writes (row << 32) | unit keys at its place; a stable radix sort over the keys' 49 significant bits; d_mem is the low
+ * halves of the first min(need, cap) keys.  The order never comes from a cursor moved by atomics.
+ * d_work: dcrx_cdr3_motif_members_work_bytes(n, cap) bytes, 256-byte aligned; a smaller one is DCRX_E_INVALID, not a launch.
+ * DCRX_E_INVALID also for a null argument, a bad k_mask or trim and S above 475 228; DCRX_E_UNSUPPORTED for n >= 2^30 and
+ * cap + n >= 2^31.  What only the device can see: a selected (k, code) that is no motif of K is skipped; a motif selected twice
+ * and offsets that go down are outside the contract. */
+int dcrx_cdr3_motif_members_device(uint64_t n, const uint64_t *d_off, const char *d_text, uint32_t k_mask, uint32_t ntrim,
+                                   uint32_t ctrim, uint64_t S, const uint32_t *d_sel_k, const uint32_t *d_sel_code, uint64_t cap,
+                                   uint32_t *d_n_motifs, uint64_t *d_mem_off, uint32_t *d_mem, uint64_t *d_need, void *d_work,
+                                   uint64_t work_bytes, void *hip_stream);
+
+/* Bytes of device work space dcrx_cdr3_groups_device needs for n units and S member rows; 0 for n >= 2^30 or S above 475 228. */
+uint64_t dcrx_cdr3_groups_work_bytes(uint64_t n, uint64_t S);
+
+/* The groups primitive, on `hip_stream`, everything in device memory: the connected components of the n units under a unit-unit
+ * adjacency in CSR (d_adj_off n + 1 offsets, d_adj; adj_entries, the number of entries d_adj holds, may be 0 and d_adj then
+ * NULL) and S member rows in CSR (d_mem_off S + 1 offsets, d_mem in (row, unit) order; mem_entries, the number of entries d_mem
+ * holds, may be 0 and d_mem then NULL; S may be 0 and d_mem_off then NULL).  Any adjacency serves, not the Hamming one alone; an
+ * entry of d_mem or d_adj outside 0 .. n - 1 is outside the contract (a member outside is skipped).  Outputs: d_group_of n
+ * entries; d_head, d_units, d_weight n entries of room each, filled per group; d_groups one uint32, the number of groups.
+ * Rounds of smallest-label propagation until one moves nothing: every row takes the smallest label among its members (a lane per
+ * member; consecutive lanes share a row, so the minimum is first taken within the wave, then one atomic per row and wave); every
+ * unit takes the smallest among itself, its adjacency and its rows; the labels are followed to their ends.  Then the totals
+ * (integer atomics onto the heads) and the heads compacted in unit order.  The atomics' results are not read and the fixed point
+ * does not depend on their order.  A round WAITS for the stream once (the word that says whether a label moved); *rounds_out
+ * (host, may be NULL) is the number of rounds.  d_work: dcrx_cdr3_groups_work_bytes(n, S) bytes, 256-byte aligned; a smaller
+ * one is DCRX_E_INVALID, not a launch.  DCRX_E_INVALID also for a null argument; DCRX_E_UNSUPPORTED for n >= 2^30. */
+int dcrx_cdr3_groups_device(uint64_t n, const uint64_t *d_weight, const uint64_t *d_adj_off, const uint32_t *d_adj, uint64_t adj_entries,
+                            uint64_t S, const uint64_t *d_mem_off, const uint32_t *d_mem, uint64_t mem_entries, uint32_t *d_group_of,
+                            uint32_t *d_head, uint32_t *d_units, uint64_t *d_weight_out, uint32_t *d_groups, uint32_t *rounds_out,
+                            void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* The host entry, synchronous on the current device, on host arrays: checks the arguments (all of the contract's refusals, the
+ * order of the selected motifs and offsets that go down among them, before any device call), uploads, runs the members
+ * primitive as a counting call, allocates exactly `need` members and runs it again; with distance > 0 the neighbour primitive
+ * (every class 0: the degree pass, an adjacency of exactly the entries it takes, the write pass); the groups primitive; copies
+ * everything back.  Per unit (n entries each): group_of_out, n_motifs_out, degree_out.  Per group (n entries of room each):
+ * head_out, units_out, weight_out.  mem_off_out S + 1 entries; mem_out mem_cap entries (may be NULL where mem_cap is 0), filled
+ * only when the members fit (need <= mem_cap); *mem_need_out the need.  The number of groups is stats_out->groups.
+ * DCRX_E_INVALID for a null argument, a bad k_mask or trim, a distance above 2, S above 475 228, selected motifs out of order or
+ * with a k outside K or a code outside its k, and offsets that go down; DCRX_E_UNSUPPORTED for n >= 2^30 and where the
+ * members' need + n reaches 2^31. */
+int dcrx_cdr3_motif_groups(uint64_t n, const uint64_t *off, const char *text, const uint64_t *weight, uint32_t k_mask, uint32_t ntrim,
+                           uint32_t ctrim, uint64_t S, const uint32_t *sel_k, const uint32_t *sel_code, uint32_t distance,
+                           uint32_t *group_of_out, uint32_t *n_motifs_out, uint32_t *degree_out, uint32_t *head_out, uint32_t *units_out,
+                           uint64_t *weight_out, uint64_t *mem_off_out, uint32_t *mem_out, uint64_t mem_cap, uint64_t *mem_need_out,
+                           dcrx_cdr3_motif_group_stats_t *stats_out);
+
 /* What a handle has settled for its own launches (no counterpart in the reference).  Where the scan kernel takes the tail
  * itself, a handle times the finishing launches of its first calls of a batch-size class (batches of 2^k .. 2^(k+1) - 1 reads,
  * k >= 20) on two settings and keeps the faster for the class: 4096 or 3072 rescue waves for batches below 2^25 reads, 8192 or
