@@ -83,6 +83,42 @@ def components(n: int, pairs) -> list:
     return [number[r] for r in roots]
 
 
+def motifs_held(units, ks, trim, at_least=2) -> list:
+    """The motifs at least `at_least` of the units hold, in motif order, as (k, code)."""
+    count = {}
+    for u in units:
+        if mu.takes_part(u):
+            for mo in mu.motif_set(u, ks, trim):
+                count[mo] = count.get(mo, 0) + 1
+    return sorted(((k, mu.code_of(w)) for (k, w), c in count.items() if c >= at_least), key=lambda kc: motif_number(*kc))
+
+
+def groups_table(n: int, rows, ring=True) -> tuple:
+    """A table for the groups primitive on n units: the weights i * i + 1, an adjacency that is no Hamming one (every seventh unit
+    linked to the next seventh; none without `ring`) beside the member rows `rows`, and what the contract gives for them through
+    components(): (weights, adjacency, {"group_of", "head", "units", "weight"} as lists)."""
+    seventh = list(range(0, n, 7)) if ring else []
+    adjacency = [[] for _ in range(n)]
+    for a, b in zip(seventh, seventh[1:]):
+        adjacency[a].append(b)
+        adjacency[b].append(a)
+    adjacency = [sorted(x) for x in adjacency]
+    weights = [i * i + 1 for i in range(n)]
+    pairs = [(a, b) for a in range(n) for b in adjacency[a]] + [(row[0], x) for row in rows for x in row[1:]]
+    group_of = components(n, pairs)
+    g = max(group_of) + 1 if n else 0
+    want = {"group_of": group_of, "head": [group_of.index(r) for r in range(g)], "units": [group_of.count(r) for r in range(g)],
+            "weight": [sum(w for w, r2 in zip(weights, group_of) if r2 == r) for r in range(g)]}
+    return weights, adjacency, want
+
+
+def csr(lists, dtype=np.uint32) -> tuple:
+    """(offsets, entries) of a list of lists."""
+    off = np.zeros(len(lists) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+    return off, np.array([x for row in lists for x in row], dtype)
+
+
 def expected_groups(units, weights, ks=(2, 3, 4), trim=(3, 3), selected=(), G=1, mem_cap=None) -> dict:
     """What nat.cdr3_motif_groups gives for the units (a list of bytes, taken as given), their weights, the selected motifs (a
     list of (k, code) in motif order) and the global distance G."""

@@ -39,14 +39,7 @@ def _pool():
     return mu.random_units(400, 21, 8, 14)
 
 
-def _motifs_held_twice(units, ks, trim, at_least=2):
-    """The motifs at least `at_least` of the units hold, in motif order, as (k, code)."""
-    count = {}
-    for u in units:
-        if mu.takes_part(u):
-            for mo in mu.motif_set(u, ks, trim):
-                count[mo] = count.get(mo, 0) + 1
-    return sorted(((k, mu.code_of(w)) for (k, w), c in count.items() if c >= at_least), key=lambda kc: gu.motif_number(*kc))
+_motifs_held_twice = gu.motifs_held
 
 
 def _mutants(units, seed):
@@ -271,10 +264,7 @@ def test_members_work_space_short_or_misaligned_is_refused_not_launched():
 
 # ---- the groups primitive ----
 
-def _csr(lists, dtype=np.uint32):
-    off = np.zeros(len(lists) + 1, np.uint64)
-    off[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
-    return off, np.array([x for row in lists for x in row], dtype)
+_csr = gu.csr
 
 
 def _groups_buffers(n, weights, adjacency, rows):
@@ -308,18 +298,7 @@ def _groups_case():
     units = list(_pool()[:300])
     n = len(units)
     rows = gu.expected_members(units, (3,), (3, 3), _motifs_held_twice(units, (3,), (3, 3)))["rows"]
-    ring = list(range(0, n, 7))
-    adjacency = [[] for _ in range(n)]
-    for a, b in zip(ring, ring[1:]):
-        adjacency[a].append(b)
-        adjacency[b].append(a)
-    adjacency = [sorted(x) for x in adjacency]
-    weights = [i * i + 1 for i in range(n)]
-    pairs = [(a, b) for a in range(n) for b in adjacency[a]] + [(row[0], x) for row in rows for x in row[1:]]
-    group_of = gu.components(n, pairs)
-    g = max(group_of) + 1
-    want = {"group_of": group_of, "head": [group_of.index(r) for r in range(g)], "units": [group_of.count(r) for r in range(g)],
-            "weight": [sum(w for w, r2 in zip(weights, group_of) if r2 == r) for r in range(g)]}
+    weights, adjacency, want = gu.groups_table(n, rows)
     return n, weights, adjacency, rows, want
 
 
