@@ -440,6 +440,15 @@ class Cdr3CostC(C.Structure):      # dcrx_cdr3_cost_t
     _fields_ = [("sub", (C.c_uint8 * 32) * 32), ("gap", C.c_uint32), ("ntrim", C.c_uint32), ("ctrim", C.c_uint32)]
 
 
+CDR3_PROFILE_MAX_BINS = 32           # dcrx_cdr3_profile_weighted: bins 1 .. 32, step 1 .. 65535, step * (bins - 1) <= 65535
+CDR3_PROFILE_STATS = ("queries", "targets", "queries_out_of_reach", "queries_not_letters", "targets_out_of_reach", "cells_sum",
+                      "queries_nonzero")
+
+
+class Cdr3ProfileStatsC(C.Structure):      # dcrx_cdr3_profile_stats_t
+    _fields_ = [(k, C.c_uint64) for k in CDR3_PROFILE_STATS]
+
+
 CDR3_MOTIF_MAX_SAMPLES = 64          # files of one `motifs` call
 CDR3_MOTIF_MAX_TRIM = 16             # DCRX_CDR3_MOTIF_MAX_TRIM
 CDR3_MOTIF_MAX_RESAMPLES = 65535     # DCRX_CDR3_MOTIF_MAX_RESAMPLES
@@ -533,6 +542,7 @@ EXPORTS = [
     "dcrx_cdr3_motifs_work_bytes", "dcrx_cdr3_motifs_device", "dcrx_cdr3_motifs",
     "dcrx_cdr3_motif_members_work_bytes", "dcrx_cdr3_motif_members_device", "dcrx_cdr3_groups_work_bytes", "dcrx_cdr3_groups_device",
     "dcrx_cdr3_motif_groups",
+    "dcrx_cdr3_profile_weighted_work_bytes", "dcrx_cdr3_profile_weighted_device", "dcrx_cdr3_profile_weighted",
 ]
 
 _lib = None
@@ -720,6 +730,9 @@ def lib():
         "dcrx_cdr3_groups_device": (i32, [u64, vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
         "dcrx_cdr3_motif_groups": (i32, [u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp,
                                          C.POINTER(Cdr3MotifGroupStatsC)]),
+        "dcrx_cdr3_profile_weighted_work_bytes": (u64, [u64, u64, u32]),
+        "dcrx_cdr3_profile_weighted_device": (i32, [vp, u64, vp, vp, vp, u64, vp, u32, u32, vp, vp, u64, vp]),
+        "dcrx_cdr3_profile_weighted": (i32, [vp, u64, vp, vp, vp, vp, u32, u32, vp, C.POINTER(Cdr3ProfileStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1775,6 +1788,47 @@ def cdr3_match_weighted(index: Cdr3Index, classes, off, text: bytes, weights, co
     check(lib().dcrx_cdr3_match_weighted_run(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data,
                                              C.addressof(c) if c is not None else None, _radius(radius), C.byref(h)))
     return _cdr3_match_take(h, m, True)
+
+
+def _u32(value, what: str) -> int:
+    if not 0 <= int(value) < 1 << 32:
+        raise ValueError(f"{what} does not fit 32 bits: {value}")
+    return int(value)
+
+
+def cdr3_profile_weighted_work_bytes(m_q: int, text_bytes: int, bins: int) -> int:
+    """dcrx_cdr3_profile_weighted_work_bytes."""
+    return int(lib().dcrx_cdr3_profile_weighted_work_bytes(int(m_q), int(text_bytes), _u32(bins, "bins")))
+
+
+def cdr3_profile_weighted_device(index: Cdr3Index, m_q: int, d_class, d_off, d_text, text_bytes: int, cost: Cdr3Cost, step: int, bins: int,
+                                 d_profile, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_profile_weighted_device: per query of a table in HBM (DeviceBuffers) the histogram of its targets' weighted
+    distances, m_q * bins dwords into d_profile, asynchronous on `stream`."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    c = cost.as_c() if cost is not None else None      # (alive across the call, which copies it)
+    check(lib().dcrx_cdr3_profile_weighted_device(index.handle, int(m_q), ptr(d_class), ptr(d_off), ptr(d_text), int(text_bytes),
+                                                  C.addressof(c) if c is not None else None, _u32(step, "step"), _u32(bins, "bins"),
+                                                  ptr(d_profile), ptr(d_work), int(work_bytes), stream))
+
+
+def cdr3_profile_weighted(index: Cdr3Index, classes, off, text: bytes, cost: Cdr3Cost, step: int, bins: int) -> dict:
+    """dcrx_cdr3_profile_weighted: m_q queries (class, string = text[off[i]:off[i + 1]]) against the index's targets ->
+    {"profile": (m_q, bins) uint32, cell [i, b] the targets of query i's class at a weighted distance d with
+    ceil(d / step) == b (not cumulative), "stats": dict over CDR3_PROFILE_STATS}."""
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    o, t = _node_arrays(off, text)
+    m = len(cls)
+    if len(o) != m + 1:
+        raise ValueError("cdr3_profile_weighted: one class per query, m + 1 offsets")
+    step, bins = _u32(step, "step"), _u32(bins, "bins")
+    profile = np.empty(max(m * min(bins, CDR3_PROFILE_MAX_BINS), 1), dtype=np.uint32)
+    st = Cdr3ProfileStatsC()
+    c = cost.as_c() if cost is not None else None
+    check(lib().dcrx_cdr3_profile_weighted(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data,
+                                           C.addressof(c) if c is not None else None, step, bins, profile.ctypes.data, C.byref(st)))
+    return {"profile": profile[:m * bins].reshape(m, bins), "stats": {k: int(getattr(st, k)) for k in CDR3_PROFILE_STATS}}
 
 
 def format_cdr3_matches_weighted(result: dict, v_idx, j_idx, v_calls, j_calls, off, text: bytes, weights, t_off, t_text: bytes,

@@ -19,6 +19,8 @@
 // The weighted metric (dcrx_cdr3_match_weighted_*; include/dcrx.h "match, weighted") is the same walk over the Levenshtein
 // walk's class-order arrays with Weighted (weighted_within, dcrx_cdr3w_core.h) as its pair test; its entries live in this
 // file because the index, the work space, the handle and the two halves around the walk are this file's own.
+// The profile (dcrx_cdr3_profile_weighted_*; include/dcrx.h "profile, weighted") is the weighted walk once more, at the top of a
+// ladder of radii, with a histogram of the hits' distances per query for a sink (Profile, dcrx_cdr3walk.h): one pass, no scan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -296,6 +298,47 @@ int run_entry(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, const u
   return DCRX_OK;
 }
 
+// ---- the profile (include/dcrx.h "profile, weighted"): the weighted walk at radius step * (bins - 1) with the Profile sink
+
+// what both profile entries refuse of (index, m_q, cost, step, bins); the cost as the launch argument and the ladder's top
+int refuse_profile(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, const dcrx_cdr3_cost_t *cost, uint32_t step, uint32_t bins,
+                   CostArg *wc, uint32_t *radius) {
+  int rc = refuse(who, I, m_q, 0, METRIC_HAMMING);
+  if (rc) return rc;
+  if (const char *what = dcrx_cdr3profile::refuse_ladder(step, bins)) return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str());
+  *radius = step * (bins - 1);
+  return refuse_cost(who, cost, *radius, wc);
+}
+
+// the profile's work space: the sorted queries and the sort's scratch (no degrees, no scan, no masks)
+struct ProfileWork {
+  uint64_t *key[2];
+  uint32_t *idx[2];
+  uint4 *sj;
+  Scratch cub;
+  int carve(Pool &P, uint64_t n) {
+    size_t cub_bytes = 0;
+    int rc;
+    if ((rc = sort_pairs_bytes<uint32_t>(std::max<uint64_t>(n, 1), KEY_BITS, &cub_bytes))) return rc;
+    P.get(&key[0], n); P.get(&key[1], n); P.get(&idx[0], n); P.get(&idx[1], n); P.get(&sj, 2 * n); P.get(&cub, cub_bytes);
+    return DCRX_OK;
+  }
+  Sorted queries(uint64_t n) const { return Sorted{key[1], idx[1], sj, nullptr, (uint32_t)n}; }
+};
+
+// keys, sort and gather of the queries as the weighted match prepares them, then the one walk; every cell of d_profile is
+// written (m_q > 0 and targets > 0 here)
+int run_profile(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, const CostArg &wc, uint32_t radius, uint32_t step, uint32_t bins,
+                uint32_t *d_profile, const ProfileWork &W, hipStream_t s) {
+  int rc;
+  if ((rc = sorted_keys(N, n, W.key, W.idx, W.cub, (int)LEN_BITS, true, s)) || (rc = gather(N, n, W.idx[1], W.sj, nullptr, s))) return rc;
+  const size_t hist_bytes = (size_t)bins * BLOCK * sizeof(uint32_t);
+  cdr3_walk_kernel<false><<<grid_for(n), BLOCK, hist_bytes, s>>>(W.queries(n), I.targets(true), Bipartite{}, Weighted{wc, radius},
+                                                                 Profile{d_profile, step, bins});
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
 // the matches text under any metric (cost: the weighted metric's, null otherwise)
 int64_t format_matches(const char *who, uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx, const uint32_t *j_idx,
                                  uint32_t n_v, const char *v_calls, const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
@@ -512,6 +555,99 @@ int dcrx_cdr3_match_export_dist(const dcrx_cdr3_match_t *M, uint32_t *hit_dist) 
   if (!M->weighted) return set_err(DCRX_E_INVALID, "dcrx_cdr3_match_export_dist: the handle is not of dcrx_cdr3_match_weighted_run");
   if (hit_dist && !M->hit_dist.empty()) std::memcpy(hit_dist, M->hit_dist.data(), M->hit_dist.size() * sizeof(uint32_t));
   return DCRX_OK;
+}
+
+// ---- the profile's entries (include/dcrx.h "profile, weighted")
+
+uint64_t dcrx_cdr3_profile_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes, uint32_t bins) {
+  (void)text_bytes;      // (per-query keys, ranks and packed strings; the histogram lives in LDS, whatever `bins` is)
+  Pool P;
+  ProfileWork W;
+  if (m_q >= MAX_NODES || bins < 1 || bins > dcrx_cdr3profile::MAX_BINS || W.carve(P, m_q) != DCRX_OK) return 0;
+  return P.bytes();
+}
+
+int dcrx_cdr3_profile_weighted_device(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off,
+                                      const char *d_text, uint64_t text_bytes, const dcrx_cdr3_cost_t *cost, uint32_t step, uint32_t bins,
+                                      uint32_t *d_profile, void *d_work, uint64_t work_bytes, void *hip_stream) try {
+  static const char who[] = "dcrx_cdr3_profile_weighted_device";
+  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  CostArg wc;
+  uint32_t radius = 0;
+  int rc = refuse_profile(who, I, m_q, cost, step, bins, &wc, &radius);
+  if (rc) return rc;
+  if (!m_q) return DCRX_OK;      // no cell to write
+  if (!d_profile) return fail("null profile");
+  if (!d_class || !d_off || !d_work || (text_bytes && !d_text)) return fail("null argument");
+  if ((uintptr_t)d_work % ALIGN) return fail("the work space is not 256-byte aligned");
+  Pool P(d_work);
+  ProfileWork W;
+  if ((rc = W.carve(P, m_q))) return rc;
+  if (work_bytes < P.bytes()) return fail("the work space is smaller than dcrx_cdr3_profile_weighted_work_bytes(m_q, text_bytes, bins)");
+  hipStream_t s = (hipStream_t)hip_stream;
+  dcrx::DeviceGuard on(I->device);
+  if (!I->m) {      // nothing can hit: every cell is zero, no kernel
+    HIP_TRY(hipMemsetAsync(d_profile, 0, m_q * bins * sizeof(uint32_t), s));
+    return DCRX_OK;
+  }
+  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
+  return run_profile(*I, N, m_q, wc, radius, step, bins, d_profile, W, s);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int dcrx_cdr3_profile_weighted(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *cls, const uint64_t *off, const char *text,
+                               const dcrx_cdr3_cost_t *cost, uint32_t step, uint32_t bins, uint32_t *profile,
+                               dcrx_cdr3_profile_stats_t *stats) try {
+  static const char who[] = "dcrx_cdr3_profile_weighted";
+  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  CostArg wc;
+  uint32_t radius = 0;
+  int rc = refuse_profile(who, I, m_q, cost, step, bins, &wc, &radius);
+  if (rc) return rc;
+  if (m_q && !profile) return fail("null profile");
+  if (m_q && (!cls || !off)) return fail("null argument");
+  dcrx_cdr3_profile_stats_t st{};
+  st.queries = m_q;
+  st.targets = I->m;
+  st.targets_out_of_reach = I->out_of_reach;
+  for (uint64_t k = 0; k < m_q; k++)
+    if (off[k + 1] < off[k]) return fail("offsets go backwards");
+  if (m_q && off[m_q] > off[0] && !text) return fail("text is null");
+  for (uint64_t k = 0; k < m_q; k++) {
+    const uint64_t len = off[k + 1] - off[k];
+    if (!in_reach(len)) st.queries_out_of_reach++;
+    else if (!host_letters(text + off[k], len)) st.queries_not_letters++;
+  }
+  const uint64_t cells = m_q * bins;
+  if (m_q && I->m) {
+    dcrx::DeviceGuard on(I->device);
+    const uint64_t text_bytes = off[m_q] - off[0];
+    Pool P;
+    ProfileWork W;
+    uint32_t *d_cls, *d_profile;
+    uint64_t *d_off;
+    uint8_t *d_text;
+    for (int pass = 0; pass < 2; pass++) {
+      P.get(&d_cls, m_q); P.get(&d_off, m_q + 1); P.get(&d_text, text_bytes); P.get(&d_profile, cells);
+      if ((rc = W.carve(P, m_q)) || (pass == 0 && (rc = P.allocate()))) return rc;
+    }
+    if ((rc = upload_spans(m_q, off, text, d_off, d_text)) || (rc = to_device(d_cls, cls, m_q))) return rc;
+    const Nodes N{d_cls, d_off, d_text, text_bytes};
+    if ((rc = run_profile(*I, N, m_q, wc, radius, step, bins, d_profile, W, nullptr)) || (rc = to_host(profile, d_profile, cells))) return rc;
+  } else if (cells) {
+    std::memset(profile, 0, cells * sizeof(uint32_t));
+  }
+  for (uint64_t k = 0; k < m_q; k++) {
+    uint64_t row = 0;
+    for (uint32_t b = 0; b < bins; b++) row += profile[k * bins + b];
+    st.cells_sum += row;
+    st.queries_nonzero += row != 0;
+  }
+  if (stats) *stats = st;
+  return DCRX_OK;
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
 }
 
 }  // extern "C"

@@ -11,6 +11,9 @@
 // node's hits come in ascending rank with no atomics: the degree pass (WRITE false) counts them, an exclusive sum in rank order
 // gives the offsets (cdr3_need_kernel closes them), and the write pass (WRITE true) walks again and writes every hit at its
 // exact place.
+// Sink says what a walk leaves: Out (the two passes above) or Profile, a histogram of the hits' distances per node
+// (include/dcrx.h "profile, weighted"): a column of `bins` counters per lane in dynamic LDS, one add per hit, read out behind
+// the walk.
 // Side says which entries a block walks and whether an entry is the lane's own node: Bipartite (two tables) or Within (one
 // table against itself).  Pair is the pair test: Hamming, Levenshtein or Weighted.
 // The weighted metric's host side stands here too, once for both units: what every weighted entry refuses of a cost
@@ -25,6 +28,7 @@
 #include <string>
 
 #include "dcrx_cdr3match_core.h"
+#include "dcrx_cdr3profile_core.h"
 #include "dcrx_cdr3w_core.h"
 #include "dcrx_group.h"
 
@@ -60,11 +64,37 @@ struct Sorted {
 // what a walk leaves, by rank of Q: the degree pass degree and deg64 (the same as 64 bits, for the scan), the write pass the
 // hits' ranks — and their distances, where the pair test stores one and dist is not null — at off[rank], below cap
 struct Out {
+  static constexpr bool HIST = false;
   uint32_t *degree;
   uint64_t *deg64;
   const uint64_t *off;
   uint32_t *hit, *dist;
   uint64_t cap;
+};
+
+// what the profile's walk leaves, by rank of Q: row[rank * bins + b] = the hits of the node whose distance falls into bin b
+// (dcrx_cdr3profile_core.h: bin_of).  A lane counts in a column of its own in dynamic LDS, hist[b * BLOCK + lane] (bins * 1 KB
+// a block; lanes fall into different banks whatever their bins): a register array indexed by a run-time bin would go to
+// scratch, and a chain of compares costs `bins` compares a hit where most pairs of a class are hits.  The column is the
+// lane's alone, so it needs no barrier: zeroed in front of the walk, read out behind it.  A node that takes no part keeps its
+// zeros and writes them; lanes behind the table write nothing.
+struct Profile {
+  static constexpr bool HIST = true;
+  uint32_t *row;
+  uint32_t step, bins;
+  __device__ __forceinline__ uint32_t *column() const {
+    extern __shared__ uint32_t lds_hist[];
+    return lds_hist + threadIdx.x;
+  }
+  __device__ __forceinline__ void clear(uint32_t *col) const {
+    for (uint32_t b = 0; b < bins; b++) col[b * BLOCK] = 0;
+  }
+  __device__ __forceinline__ void add(uint32_t *col, uint32_t d) const {
+    atomicAdd(&col[dcrx_cdr3profile::bin_of(d, step) * BLOCK], 1u);      // (no lane shares it: an add whose result is not read)
+  }
+  __device__ __forceinline__ void read_out(const uint32_t *col, uint32_t e) const {
+    for (uint32_t b = 0; b < bins; b++) row[(size_t)e * bins + b] = col[b * BLOCK];
+  }
 };
 
 // the length of node e's string; one past the reach for offsets that go backwards or leave the text
@@ -213,9 +243,10 @@ struct Weighted {
 };
 
 // The walk (see the head of the file).  Q: the block's nodes, T: the entries it walks, both sorted in Pair's bucket order.
-template <bool WRITE, class Side, class Pair>
-__global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Side side, Pair pair, Out O) {
+template <bool WRITE, class Side, class Pair, class Sink = Out>
+__global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Side side, Pair pair, Sink O) {
   constexpr bool CLS = Pair::CLS;
+  static_assert(!(Sink::HIST && WRITE), "a profile is one pass");
   __shared__ uint4 lds_j[TILE * 2];
   __shared__ uint64_t lds_k[TILE];
   __shared__ uint32_t lds_r[WRITE ? TILE : 1];
@@ -231,9 +262,14 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
   uint32_t own[WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t e = 0, count = 0;
   uint64_t at = 0;
+  uint32_t *col = nullptr;
+  if constexpr (Sink::HIST) {
+    col = O.column();
+    O.clear(col);
+  }
   if (valid) {
     e = Q.idx[s];
-    if (WRITE) at = O.off[e];
+    if constexpr (WRITE) at = O.off[e];
     if (reach) {
       const uint4 a = Q.sj[2 * (size_t)s], b = Q.sj[2 * (size_t)s + 1];
       own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
@@ -262,11 +298,15 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
     auto take = [&](uint32_t q, uint32_t len_q) __attribute__((always_inline)) {
       const uint32_t d = pair.test(ctx, own, len_own, lj + q * WORDS, len_q);
       if (d <= pair.bound()) {
-        if (WRITE && at + count < O.cap) {
-          O.hit[at + count] = lds_r[q];
-          if (Pair::DIST && O.dist) O.dist[at + count] = d;
+        if constexpr (Sink::HIST) {
+          O.add(col, d);
+        } else {
+          if (WRITE && at + count < O.cap) {
+            O.hit[at + count] = lds_r[q];
+            if (Pair::DIST && O.dist) O.dist[at + count] = d;
+          }
+          count++;
         }
-        count++;
       }
     };
     // DEFER: an entry that passes the cheap tests waits in `pending` (one per lane), and the test runs — for every lane that
@@ -294,7 +334,9 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
     }
     if (Pair::DEFER) settle();      // (the next tile overwrites the staged entries)
   }
-  if (valid && !WRITE) {
+  if constexpr (Sink::HIST) {
+    if (valid) O.read_out(col, e);
+  } else if (valid && !WRITE) {
     O.degree[e] = count;
     O.deg64[e] = count;
   }

@@ -280,6 +280,52 @@ def _motifs(p: argparse.ArgumentParser):
                    help="--groups: also write <sample>.cdr3_motif_members.tsv, the CDR3s that hold each selected motif")
 
 
+def _metaclonotypes(p: argparse.ArgumentParser):
+    p.add_argument("-in", "--infile", type=str, nargs="+", required=True,
+                   help="1 to 64 .clonotypes.tsv files (plain or .gz), one per sample; a sample is named by its file name "
+                        "without .clonotypes.tsv[.gz]")
+    p.add_argument("-bg", "--background", type=str, default=None,
+                   help="The background repertoire (required): a tab-separated table (plain or .gz) with a header line, its "
+                        "columns found by name; another sample's .clonotypes.tsv is one as it stands")
+    p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
+    p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
+    p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
+    p.add_argument("--cdr3-radius", dest="cdr3_radius", type=int, default=None,
+                   help="The top of the ladder of radii, a multiple of --radius-step with at most 32 rungs (radius / step + 1), "
+                        "0 to 65535 (default 48).  Radius 48, step 2, rate 1e-5 and class v follow tcrdist3's usage: design "
+                        "choices, not measured optima")
+    p.add_argument("--radius-step", dest="radius_step", type=int, default=None,
+                   help="The distance between two radii of the ladder, 1 to 65535 (default 2)")
+    p.add_argument("--max-background-rate", dest="max_background_rate", type=str, default=None,
+                   help="A clonotype's radius is the largest of the ladder at which at most this share of the background's CDR3s "
+                        "lies within it: a decimal or a fraction, 0 to 1, read exactly (1e-5 and 1/100000 are the same; default "
+                        "1e-5)")
+    p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default="v",
+                   help="What two CDR3s must share to be compared: nothing (none), the V call (v, the default) or the V and the "
+                        "J call (vj)")
+    p.add_argument("--strip-alleles", dest="strip_alleles", action="store_true",
+                   help="Compare a call up to its first * on both sides (TRBV7-9*01 and TRBV7-9*03 are then one V)")
+    p.add_argument("--cdr3-gap-cost", dest="cdr3_gap_cost", type=int, default=None,
+                   help="The price of one gapped position, 1 to 255 (default 12)")
+    p.add_argument("--cdr3-trim", dest="cdr3_trim", type=str, default=None,
+                   help="N,C - the first N and the last C residues of the shorter CDR3 do not count, 0 to 16 each (default 3,2)")
+    p.add_argument("--cdr3-cost-matrix", dest="cdr3_cost_matrix", type=str, default=None,
+                   help="A tab-separated square table of substitution costs 0..255, as `match --cdr3-cost-matrix` takes it.  "
+                        "Default: 3 * min(4, 4 - BLOSUM62), as TCRdist's")
+    p.add_argument("--bg-cdr3-column", dest="bg_cdr3_column", type=str, default="junction_aa",
+                   help="The background column that holds the CDR3 amino acids (default junction_aa)")
+    p.add_argument("--bg-v-column", dest="bg_v_column", type=str, default="v_call",
+                   help="The background column that holds the V call (default v_call); read when the class needs it")
+    p.add_argument("--bg-j-column", dest="bg_j_column", type=str, default="j_call",
+                   help="The background column that holds the J call (default j_call); read when the class needs it")
+    p.add_argument("--write-radius-profile", dest="write_radius_profile", action="store_true",
+                   help="Also write <sample>.cdr3_radius_profile.tsv: per clonotype the background's and the sample's CDR3s within "
+                        "every radius of the ladder (cumulative)")
+    p.add_argument("--write-metaclonotype-members", dest="write_metaclonotype_members", action="store_true",
+                   help="Also write <sample>.cdr3_metaclonotype_members.tsv: per clonotype the sample's other clonotypes within "
+                        "its radius, with their distances")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -287,9 +333,10 @@ def create_parser() -> argparse.ArgumentParser:
                     "Sub-commands as in the reference; the grouping / clustering half of `collapse` (UMI clustering, the "
                     ".freq) runs with --cluster.")
     parser.add_argument("-v", "--version", action="version", version=__version__)
-    parser.epilog = ("Further commands have parsers of their own: `match` (clonotypes near a database's CDR3s, GPU) and `motifs` "
-                     "(CDR3 k-mers enriched against a background, GPU); see `python -m decombinator_amd match --help` and "
-                     "`python -m decombinator_amd motifs --help`.")
+    parser.epilog = ("Further commands have parsers of their own: `match` (clonotypes near a database's CDR3s, GPU), `motifs` "
+                     "(CDR3 k-mers enriched against a background, GPU) and `metaclonotypes` (per clonotype the largest CDR3 radius "
+                     "a background still stays out of, GPU); see `python -m decombinator_amd match --help`, "
+                     "`python -m decombinator_amd motifs --help` and `python -m decombinator_amd metaclonotypes --help`.")
     sub = parser.add_subparsers(dest="command", help="Available commands")
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
@@ -341,8 +388,21 @@ def create_motifs_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def create_metaclonotypes_parser() -> argparse.ArgumentParser:
+    """The parser of `metaclonotypes`, a sub-command with a parser of its own, as `match` and `motifs` are."""
+    parser = argparse.ArgumentParser(
+        prog="python -m decombinator_amd metaclonotypes",
+        description="Meta-clonotypes (GPU): per clonotype of .clonotypes.tsv files the largest radius of a TCRdist-style CDR3 "
+                    "distance within which a background repertoire almost never falls, and how many of the sample's own "
+                    "clonotypes fall inside it; writes <sample>.cdr3_metaclonotypes.tsv per sample.")
+    _metaclonotypes(parser)
+    return parser
+
+
 def cli_args(argv=None) -> dict:
     words = sys.argv[1:] if argv is None else list(argv)
+    if words and words[0] == "metaclonotypes":
+        return dict(vars(create_metaclonotypes_parser().parse_args(words[1:])), command="metaclonotypes")
     if words and words[0] == "match":
         return dict(vars(create_match_parser().parse_args(words[1:])), command="match")
     if words and words[0] == "motifs":
@@ -524,6 +584,13 @@ def write_out_motifs(text: bytes, name: str, inputargs: dict):
     <sample>.cdr3_groups.tsv and <sample>.cdr3_motif_members.tsv), with write_out_overlap's rules.
     Returns the file's name."""
     return write_out_overlap(text, name, inputargs, what="motif")
+
+
+def write_out_metaclonotypes(text: bytes, name: str, inputargs: dict):
+    """A file of the `metaclonotypes` sub-command: `<outpath><prefix><name>` (<sample>.cdr3_metaclonotypes.tsv, and on demand
+    <sample>.cdr3_radius_profile.tsv and <sample>.cdr3_metaclonotype_members.tsv), with write_out_overlap's rules.  Returns the
+    file's name."""
+    return write_out_overlap(text, name, inputargs, what="meta-clonotype")
 
 
 def write_out_cdr3_clusters(network, inputargs: dict):

@@ -202,6 +202,14 @@ def main(argv=None):
             from .io import create_motifs_parser
             create_motifs_parser().error(str(e))
         return
+    if inp["command"] == "metaclonotypes":      # ... and this one: per clonotype a radius from a background repertoire
+        from . import metaclonotypes
+        try:
+            metaclonotypes.run(inp)
+        except ValueError as e:
+            from .io import create_metaclonotypes_parser
+            create_metaclonotypes_parser().error(str(e))
+        return
     if inp.get("clonotypes"):           # refused before anything is read
         why = clonotype_refusal(inp)
         if why:

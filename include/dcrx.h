@@ -1274,6 +1274,65 @@ int64_t dcrx_format_cdr3_matches_weighted(uint64_t m_q, const uint64_t *hit_off,
                                           const char *db_header, uint64_t db_header_bytes, const uint64_t *db_line_off,
                                           const char *db_lines, const dcrx_cdr3_cost_t *cost, char *out, uint64_t out_cap);
 
+/* ---- profile, weighted (`metaclonotypes`): per query, HOW MANY targets lie at which weighted distance — a histogram over a
+ * ladder of radii from ONE walk, where "match, weighted" answers one radius.  The reference has no counterpart: the contract
+ * below is this library's own.  The entries only ADD to ABI 5; the entries above keep their signatures and behaviour ----
+ *
+ * Input: a dcrx_cdr3_index_t (the targets), queries as dcrx_cdr3_match_weighted_device takes them (class, string; no weight), a
+ *   cost (dcrx_cdr3_cost_t), a `step` of 1 .. 65535 and `bins` of 1 .. 32.  R = step * (bins - 1) is the ladder's top and is at
+ *   most 65535.
+ * Reach, letters-only, classes and the distance are exactly those of "match, weighted": a node takes part when it has 1 .. 32
+ *   bytes, all 'A' .. 'Z'.
+ * Output: profile[i * bins + b] (uint32) = the number of targets j for which query i and target j both take part, c_i == c_j
+ *   and ceil(dist(i, j) / step) == b.  So bin 0 holds the targets at distance 0 and bin b those with
+ *   (b - 1) * step < dist <= b * step; a target beyond R is in no bin.  The cells are NOT cumulative: the caller takes prefix
+ *   sums, and for every i and b the sum of profile[i][0 .. b] is the degree[i] dcrx_cdr3_match_weighted_run gives at radius
+ *   b * step.  A query that takes no part (out of reach, or with a non-letter) has a row of zeros.  Every one of the m_q * bins
+ *   cells is written by the call: the caller's buffer need not be cleared.  Everything is an integer and a function of the input
+ *   alone; nothing depends on launch shape or on the order of arrival.
+ * Refused on the host before any launch with DCRX_E_INVALID: what "match, weighted" refuses of a cost; step 0 (or above
+ *   65535); bins 0 or above 32; step * (bins - 1) > 65535; a null profile with m_q > 0; a work space that is short or not
+ *   256-byte aligned.  m_q = 0 is valid (nothing is written), and so is an index of 0 targets (all zeros).  m_q < 2^30
+ *   (DCRX_E_UNSUPPORTED beyond). */
+typedef struct dcrx_cdr3_profile_stats {
+  uint64_t queries;
+  uint64_t targets;
+  uint64_t queries_out_of_reach;    /* the network's rule: the length alone */
+  uint64_t queries_not_letters;     /* in that reach, with a byte outside 'A' .. 'Z' */
+  uint64_t targets_out_of_reach;    /* the index's count (length alone) */
+  uint64_t cells_sum;               /* the sum of all cells: the (query, target) pairs within R */
+  uint64_t queries_nonzero;         /* queries with a non-zero row */
+} dcrx_cdr3_profile_stats_t;
+
+/* Bytes of device work space dcrx_cdr3_profile_weighted_device needs for m_q queries (their sorted keys, ranks and packed
+ * strings and the sort's scratch: the histogram itself lives in LDS, so `bins` does not enter the size); 0 for m_q >= 2^30 and
+ * for bins outside 1 .. 32.  Answered on the host. */
+uint64_t dcrx_cdr3_profile_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes, uint32_t bins);
+
+/* The primitive, asynchronous on `hip_stream`, with the device arrays, the device rule (the index's device is made current
+ * for the launches) and the work-space rules of dcrx_cdr3_match_weighted_device; `cost` is a HOST pointer, checked and
+ * copied.  d_profile: m_q * bins dwords of device memory.
+ * The steps: keys, the stable sort by class and the gather without masks, as the weighted match prepares its queries; then
+ * cdr3_walk_kernel<false, Bipartite, Weighted, Profile>: the weighted match's blocks of 256 queries in registers, LDS tiles of
+ * 256 targets, wave skip and staged cost table, with the pair test at radius R (it returns R + 1 for anything beyond and keeps
+ * its early exits).  What happens to a tested pair is the sink's: d <= R adds one to the lane's counter of bin
+ * ceil(d / step) (csrc/dcrx_cdr3profile_core.h: bin_of, a true division).  A lane's counters are a column of its own in
+ * dynamic LDS, hist[b * 256 + lane] — bins KB a block, conflict-free across lanes, one LDS add without a returned value per
+ * hit — zeroed in front of the walk and read out behind it into row Q.idx[s]; lanes behind the table write nothing.  One
+ * launch of the walk whatever `bins` is.  An index of 0 targets zeroes the profile on the stream without a kernel. */
+int dcrx_cdr3_profile_weighted_device(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *d_class,
+                                      const uint64_t *d_off, const char *d_text, uint64_t text_bytes,
+                                      const dcrx_cdr3_cost_t *cost, uint32_t step, uint32_t bins, uint32_t *d_profile,
+                                      void *d_work, uint64_t work_bytes, void *hip_stream);
+
+/* The whole step on host arrays, synchronous on the index's device: checks the arguments (all of the contract's refusals,
+ * offsets that go backwards and null arrays too, before any device call), uploads the queries into ONE allocation that also
+ * holds the profile and the work space, runs the primitive's steps and copies the profile (m_q * bins dwords) back.  `stats`
+ * may be NULL.  m_q == 0, and an index of 0 targets, are answered without a launch. */
+int dcrx_cdr3_profile_weighted(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *cls, const uint64_t *off,
+                               const char *text, const dcrx_cdr3_cost_t *cost, uint32_t step, uint32_t bins,
+                               uint32_t *profile, dcrx_cdr3_profile_stats_t *stats);
+
 /* ---- the CDR3 network, weighted (`--cdr3-network --cdr3-metric weighted`): which clonotypes of ONE table lie within a radius
  * of each other under the weighted distance above, and the clusters they form.  The entries only ADD to ABI 5; the network's
  * *_metric entries keep their signatures and behaviour, and go on refusing metric 2 ----
