@@ -1,8 +1,9 @@
 // dcrx_cdr3match_core.h — the look-ups of the tile walk (dcrx_cdr3walk.h: `match` and the CDR3 network), shared by the kernel
-// and a plain host build (tests/host_cdr3match): a bucket of a key under either metric, where a block of sorted queries starts
+// and a plain host build (tests/host_cdr3walk, the one host walk): a bucket of a key under either metric, where a block of sorted queries starts
 // in the sorted targets (the index's, or under the network its own table) and at which bucket it stops, whether the walk goes
 // on to a tile, and whether a wave skips one.
-// The per-node and per-pair code (keys, packed strings, Hamming and edit-distance tests) is dcrx_cdr3net_core.h's.
+// The per-node and per-pair code (keys, packed strings, Hamming and edit-distance tests) is dcrx_cdr3net_core.h's; the sides
+// and pair tests that call both are dcrx_cdr3pair_core.h's.
 #pragma once
 #include <stdint.h>
 

@@ -15,7 +15,9 @@
 // (include/dcrx.h "profile, weighted"): a column of `bins` counters per lane in dynamic LDS, one add per hit, read out behind
 // the walk.
 // Side says which entries a block walks and whether an entry is the lane's own node: Bipartite (two tables) or Within (one
-// table against itself).  Pair is the pair test: Hamming, Levenshtein or Weighted.
+// table against itself).  Pair is the pair test: Hamming, Levenshtein or Weighted.  Both are dcrx_cdr3pair_core.h's, which a
+// plain host build shares (tests/host_cdr3walk walks the same tiles with the same structs); what needs the device stands
+// here: begin(), which stages the weighted cost table in LDS, Sorted with its uint4, the sinks and the kernels.
 // The weighted metric's host side stands here too, once for both units: what every weighted entry refuses of a cost
 // (refuse_cost) and the distance the formatters print (host_weighted).
 // The per-node and per-pair code is dcrx_cdr3net_core.h's and dcrx_cdr3w_core.h's, the look-ups are dcrx_cdr3match_core.h's.
@@ -27,16 +29,14 @@
 #include <cstring>
 #include <string>
 
-#include "dcrx_cdr3match_core.h"
+#include "dcrx_cdr3pair_core.h"
 #include "dcrx_cdr3profile_core.h"
-#include "dcrx_cdr3w_core.h"
 #include "dcrx_group.h"
 
 namespace dcrx_cdr3walk {
 namespace {
 
-using namespace dcrx_cdr3match;
-using namespace dcrx_cdr3w;
+using namespace dcrx_cdr3pair;
 using namespace dcrx_group;
 
 constexpr uint64_t MAX_NODES = 1ull << 30;
@@ -151,96 +151,17 @@ __global__ void cdr3_need_kernel(const uint64_t *__restrict__ deg64, uint64_t *_
   }
 }
 
-// ---- the two sides: range() is the same for every lane of a block
+// ---- begin() runs once per lane in front of the walk and returns the Pair::Ctx that window() and test() are handed back
+// (the sides and the pair tests themselves are dcrx_cdr3pair_core.h's)
 
-// Q's nodes against another table's entries
-struct Bipartite {
-  template <bool CLS> __device__ __forceinline__ Range range(const Sorted &Q, const Sorted &T, uint32_t s0) const {
-    return block_range<CLS>(Q.key, Q.n, s0, T.key, T.n);
-  }
-  __device__ __forceinline__ bool self(uint32_t, uint32_t) const { return false; }
-};
+template <class Pair> __device__ __forceinline__ typename Pair::Ctx begin(const Pair &) { return {}; }
 
-// a table against itself (Q and T are one): from the block's first node's bucket start, and a node is no neighbour of its own
-struct Within {
-  const uint32_t *bstart;
-  template <bool CLS> __device__ __forceinline__ Range range(const Sorted &Q, const Sorted &, uint32_t s0) const {
-    return within_range<CLS>(Q.key, Q.n, s0, bstart);
-  }
-  __device__ __forceinline__ bool self(uint32_t p, uint32_t s) const { return p == s; }
-};
-
-// ---- the three pair tests.  CLS: the bucket is the class alone (else class and length).  MASKS: the presence masks are
-// staged and handed to window().  DEFER: an entry that passes window() waits, and test() runs on it later (see the walk).
-// DIST: test()'s value is stored beside the hit.  begin() runs once per lane in front of the walk and returns what window()
-// and test() are handed back; admits(): whether the lane's own node takes part at all; staged(): the key a staged entry gets
-// (its two uint4 in hand); window(): the cheap tests of a pair of one bucket; test(): the distance, a hit when <= bound().
-
-struct Hamming {
-  static constexpr bool CLS = false, MASKS = false, DEFER = false, DIST = false;
-  uint32_t limit;
-  struct Ctx {};
-  __device__ __forceinline__ Ctx begin() const { return Ctx{}; }
-  __device__ __forceinline__ bool admits(const uint32_t *, uint32_t) const { return true; }
-  __device__ __forceinline__ uint64_t staged(const uint4 &, const uint4 &, uint64_t key) const { return key; }
-  __device__ __forceinline__ bool window(const Ctx &, uint32_t, uint32_t, uint32_t, uint32_t) const { return true; }      // (one bucket: one length)
-  __device__ __forceinline__ uint32_t test(const Ctx &, const uint32_t *own, uint32_t, const uint32_t *other, uint32_t) const {
-    return distance(own, other, limit);
-  }
-  __device__ __forceinline__ uint32_t bound() const { return limit; }
-};
-
-struct Levenshtein {
-  static constexpr bool CLS = true, MASKS = true, DEFER = true, DIST = false;
-  uint32_t limit;
-  struct Ctx {};
-  __device__ __forceinline__ Ctx begin() const { return Ctx{}; }
-  __device__ __forceinline__ bool admits(const uint32_t *, uint32_t) const { return true; }
-  __device__ __forceinline__ uint64_t staged(const uint4 &, const uint4 &, uint64_t key) const { return key; }
-  __device__ __forceinline__ bool window(const Ctx &, uint32_t len_own, uint32_t pres_own, uint32_t len, uint32_t pres) const {
-    return len + limit >= len_own && len_own + limit >= len && presence_allows(pres_own, pres, limit);
-  }
-  __device__ __forceinline__ uint32_t test(const Ctx &, const uint32_t *own, uint32_t len_own, const uint32_t *other, uint32_t len) const {
-    return lev_within(own, len_own, other, len, limit);
-  }
-  __device__ __forceinline__ uint32_t bound() const { return limit; }
-};
-
-// the cost as the weighted walk's launch argument: the table as the 256 dwords the block's lanes copy into LDS, one each
-struct CostArg {
-  uint32_t sub[SUB_BYTES / 4];
-  uint32_t gap, ntrim, ctrim;
-};
-static_assert(SUB_BYTES / 4 == BLOCK, "a lane stages one dword of the cost table");
-
-// The class, the length window |la - lb| * gap <= radius, then weighted_within.  A string with a non-letter takes part in
-// nothing: such a node is not admitted, and the lane that stages such an entry stages a key of length 0, which no lane tests.
-// The presence masks are not read (a substitution may cost nothing).  A pair is tested where it is met: at such radii most
-// pairs of a class pass the window, so there is nothing for the pending / settle scheme to collect.
-struct Weighted {
-  static constexpr bool CLS = true, MASKS = false, DEFER = false, DIST = true;
-  CostArg cost;
-  uint32_t radius;
-  using Ctx = Cost;
-  __device__ __forceinline__ Cost begin() const {
-    __shared__ uint32_t lds_sub[SUB_BYTES / 4];
-    lds_sub[threadIdx.x] = cost.sub[threadIdx.x];      // (the walk's first barrier stands before its first read)
-    return Cost{reinterpret_cast<const uint8_t *>(lds_sub), cost.gap, cost.ntrim, cost.ctrim};
-  }
-  __device__ __forceinline__ bool admits(const uint32_t *own, uint32_t len_own) const { return letters_only(own, len_own); }
-  __device__ __forceinline__ uint64_t staged(const uint4 &a, const uint4 &b, uint64_t key) const {
-    const uint32_t w[WORDS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return letters_only(w, key_length(key)) ? key : key & ~LEN_MASK;      // (the class stays: the tile stays sorted)
-  }
-  __device__ __forceinline__ bool window(const Cost &C, uint32_t len_own, uint32_t, uint32_t len, uint32_t) const {
-    const uint32_t apart = len > len_own ? len - len_own : len_own - len;
-    return len != 0 && apart * C.gap <= radius;      // (0: an entry with a non-letter, or out of reach)
-  }
-  __device__ __forceinline__ uint32_t test(const Cost &C, const uint32_t *own, uint32_t len_own, const uint32_t *other, uint32_t len) const {
-    return weighted_within(own, len_own, reinterpret_cast<const uint8_t *>(other), len, C, radius);
-  }
-  __device__ __forceinline__ uint32_t bound() const { return radius; }
-};
+// the weighted cost with its table in LDS, a dword from every lane
+__device__ __forceinline__ Cost begin(const Weighted &pair) {
+  __shared__ uint32_t lds_sub[SUB_BYTES / 4];
+  lds_sub[threadIdx.x] = pair.cost.sub[threadIdx.x];      // (the walk's first barrier stands before its first read)
+  return Cost{reinterpret_cast<const uint8_t *>(lds_sub), pair.cost.gap, pair.cost.ntrim, pair.cost.ctrim};
+}
 
 // The walk (see the head of the file).  Q: the block's nodes, T: the entries it walks, both sorted in Pair's bucket order.
 template <bool WRITE, class Side, class Pair, class Sink = Out>
@@ -251,7 +172,7 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
   __shared__ uint64_t lds_k[TILE];
   __shared__ uint32_t lds_r[WRITE ? TILE : 1];
   __shared__ uint32_t lds_p[Pair::MASKS ? TILE : 1];
-  const typename Pair::Ctx ctx = pair.begin();
+  const typename Pair::Ctx ctx = begin(pair);
   const uint32_t s0 = blockIdx.x * BLOCK;
   const uint32_t s = s0 + threadIdx.x;
   const bool valid = s < Q.n;
@@ -278,7 +199,7 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
   }
   // the wave's buckets (sorted along s; lanes behind the table hold the largest)
   const uint64_t w_lo = __shfl(k_own, 0), w_hi = __shfl(k_own, warpSize - 1);
-  const Range R = side.template range<CLS>(Q, T, s0);
+  const Range R = side.template range<CLS>(Q.key, Q.n, T.key, T.n, s0);
   for (uint32_t t = R.first; t < T.n; t += TILE) {
     if (!goes_on<CLS>(R, T.key[t])) break;
     __syncthreads();                                        // the previous tile is no longer read
@@ -288,7 +209,8 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
       const uint4 a = T.sj[2 * (size_t)p], b = T.sj[2 * (size_t)p + 1];
       lds_j[2 * threadIdx.x] = a;
       lds_j[2 * threadIdx.x + 1] = b;
-      lds_k[threadIdx.x] = pair.staged(a, b, T.key[p]);
+      const uint32_t w[WORDS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      lds_k[threadIdx.x] = pair.staged(w, T.key[p]);
       if (WRITE) lds_r[threadIdx.x] = T.idx[p];
       if (Pair::MASKS) lds_p[threadIdx.x] = T.pres[p];
     }

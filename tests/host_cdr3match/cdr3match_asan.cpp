@@ -1,66 +1,22 @@
 // Test-only, stand-alone (its own main; built with -fsanitize=address,undefined by `make asan`): the host walk of `match`
 // over lists that put buckets on the tile and block edges and leave buckets empty on either side, each checked against an
 // all-pairs count.  Exit status 0: every list agreed and the sanitizers saw nothing.
-#include <cstdio>
-#include <string>
+#include "../host_cdr3walk/cdr3walk_check.h"
 
-#include "cdr3match_walk.h"
-
-using namespace cdr3match_host;
+using namespace cdr3walk_check;
 
 namespace {
 
-struct Table {
-  std::vector<uint32_t> cls;
-  std::vector<uint64_t> off{0};
-  std::string text;
-  void add(uint32_t c, const std::string &s) { cls.push_back(c); text += s; off.push_back(text.size()); }
-  uint64_t m() const { return cls.size(); }
-  std::string str(uint64_t i) const { return text.substr(off[i], off[i + 1] - off[i]); }
-};
-
-// string number i of one length: three base-20 digits between fixed ends (two numbers differ in 1 to 3 places)
-std::string code(uint32_t i, const std::string &tail = "EQYF") {
-  static const char amino[] = "ACDEFGHIKLMNPQRSTVWY";
-  std::string s = "CASS";
-  for (int d = 0; d < 3; d++, i /= 20) s += amino[i % 20];
-  return s + tail;
-}
-
-uint64_t lev(const std::string &a, const std::string &b) {
-  std::vector<uint64_t> prev(b.size() + 1), cur(b.size() + 1);
-  std::iota(prev.begin(), prev.end(), 0);
-  for (size_t i = 1; i <= a.size(); i++) {
-    cur[0] = i;
-    for (size_t j = 1; j <= b.size(); j++) cur[j] = std::min({prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (a[i - 1] != b[j - 1])});
-    prev.swap(cur);
-  }
-  return prev[b.size()];
-}
-
-bool pair_hits(const std::string &a, const std::string &b, uint32_t D, uint32_t metric) {
-  if (a.empty() || b.empty() || a.size() > MAX_LEN || b.size() > MAX_LEN) return false;
-  if (metric == METRIC_LEVENSHTEIN) return lev(a, b) <= D;
-  if (a.size() != b.size()) return false;
-  uint32_t d = 0;
-  for (size_t p = 0; p < a.size(); p++) d += a[p] != b[p];
-  return d <= D;
-}
-
 int check(const char *name, const Table &T, const Table &Q) {
   int bad = 0;
+  const std::vector<std::string> t = T.strings(), q = Q.strings();
   for (uint32_t metric = 0; metric < 2; metric++)
     for (uint32_t D = 0; D <= 2; D++) {
-      const auto hits = match(T.m(), T.cls.data(), T.off.data(), reinterpret_cast<const uint8_t *>(T.text.data()), Q.m(), Q.cls.data(),
-                              Q.off.data(), reinterpret_cast<const uint8_t *>(Q.text.data()), D, metric);
+      const Hits hits = match(T.m(), T.cls.data(), T.off.data(), T.bytes(), Q.m(), Q.cls.data(), Q.off.data(), Q.bytes(), D, metric);
       uint64_t total = 0;
-      for (uint64_t i = 0; i < Q.m(); i++) {
-        std::vector<uint32_t> want;
-        for (uint64_t j = 0; j < T.m(); j++)
-          if (Q.cls[i] == T.cls[j] && pair_hits(Q.str(i), T.str(j), D, metric)) want.push_back((uint32_t)j);
-        if (want != hits[i]) bad++;
-        total += want.size();
-      }
+      bad += rows_differ(hits, Q.m(), T.m(), [&](uint64_t i, uint64_t j, uint64_t *d) {
+        return Q.cls[i] == T.cls[j] && plain_hit(q[i], t[j], D, metric, d);
+      }, &total);
       std::printf("%s metric %u D %u: %llu hits, %d rows differ\n", name, metric, D, (unsigned long long)total, bad);
     }
   return bad;

@@ -2,86 +2,19 @@
 // `match` over lists that put buckets on the tile and block edges (grids of 1, 3 and 6 blocks), leave buckets empty on either
 // side, mix in nodes with a non-letter, and hold every length 1 .. 33, each checked against an all-pairs count whose distance is
 // the contract read out (the gapped string built for every p).  Exit status 0: every list agreed and the sanitizers saw nothing.
-#include <cstdio>
-#include <string>
+#include "../host_cdr3walk/cdr3walk_check.h"
 
-#include "cdr3wmatch_walk.h"
-
-using namespace cdr3wmatch_host;
+using namespace cdr3walk_check;
 
 namespace {
 
-struct Table {
-  std::vector<uint32_t> cls;
-  std::vector<uint64_t> off{0};
-  std::string text;
-  void add(uint32_t c, const std::string &s) { cls.push_back(c); text += s; off.push_back(text.size()); }
-  uint64_t m() const { return cls.size(); }
-  std::string str(uint64_t i) const { return text.substr(off[i], off[i + 1] - off[i]); }
-};
-
-// string number i: three base-20 digits between fixed ends (two numbers differ in 1 to 3 places), and a tail of i % 3 letters
-std::string code(uint32_t i, bool tails = false) {
-  static const char amino[] = "ACDEFGHIKLMNPQRSTVWY";
-  std::string s = "CASS";
-  const uint32_t n = i;
-  for (int d = 0; d < 3; d++, i /= 20) s += amino[i % 20];
-  return s + std::string("EQYF").substr(0, tails ? 2 + n % 3 : 4);
-}
-
-std::vector<uint8_t> table(uint32_t seed) {      // symmetric, zero diagonal, cells 0 .. 255
-  std::vector<uint8_t> sub(SUB_BYTES, 0);
-  for (uint32_t x = 1; x <= 26; x++)
-    for (uint32_t y = 1; y < x; y++) {
-      seed = seed * 1664525u + 1013904223u;
-      sub[x * SUB_DIM + y] = sub[y * SUB_DIM + x] = seed ? (uint8_t)(seed >> 24) % (seed & 4 ? 13 : 256) : 0;
-    }
-  return sub;
-}
-
-bool letters(const std::string &s) {
-  for (char c : s)
-    if (c < 'A' || c > 'Z') return false;
-  return true;
-}
-
-// the contract: a with a gap of d put in behind its first p residues, against b, summed over the counted positions
-uint64_t dist(std::string a, std::string b, const Cost &C) {
-  if (a.size() > b.size()) a.swap(b);
-  const size_t la = a.size(), d = b.size() - la;
-  uint64_t best = UINT64_MAX;
-  for (size_t p = 0; p <= la; p++) {
-    const std::string gapped = a.substr(0, p) + std::string(d, '-') + a.substr(p);
-    uint64_t sum = 0;
-    for (size_t k = 0; k < gapped.size(); k++) {
-      if (gapped[k] == '-') continue;
-      const size_t i = k < p ? k : k - d;      // the position in a
-      if (i < C.ntrim || i + C.ctrim >= la) continue;
-      sum += C.sub[(gapped[k] & 31) * SUB_DIM + (b[k] & 31)];
-    }
-    best = std::min(best, sum);
-  }
-  return d * C.gap + best;
-}
-
 int check(const char *name, const Table &T, const Table &Q, const Cost &C, uint32_t radius) {
-  int bad = 0;
-  const auto hits = match(T.m(), T.cls.data(), T.off.data(), reinterpret_cast<const uint8_t *>(T.text.data()), Q.m(), Q.cls.data(),
-                          Q.off.data(), reinterpret_cast<const uint8_t *>(Q.text.data()), C, radius);
+  const Hits hits = match(T.m(), T.cls.data(), T.off.data(), T.bytes(), Q.m(), Q.cls.data(), Q.off.data(), Q.bytes(), weighted(C, radius));
+  const std::vector<std::string> t = T.strings(), q = Q.strings();
   uint64_t total = 0;
-  for (uint64_t i = 0; i < Q.m(); i++) {
-    std::vector<std::pair<uint32_t, uint32_t>> want, got;
-    const std::string q = Q.str(i);
-    for (uint64_t j = 0; j < T.m(); j++) {
-      const std::string t = T.str(j);
-      if (Q.cls[i] != T.cls[j] || q.empty() || t.empty() || q.size() > MAX_LEN || t.size() > MAX_LEN || !letters(q) || !letters(t)) continue;
-      const uint64_t d = dist(q, t, C);
-      if (d <= radius) want.push_back({(uint32_t)j, (uint32_t)d});
-    }
-    for (const Hit &h : hits[i]) got.push_back({h.target, h.dist});
-    if (want != got) bad++;
-    total += want.size();
-  }
+  const int bad = rows_differ(hits, Q.m(), T.m(), [&](uint64_t i, uint64_t j, uint64_t *d) {
+    return Q.cls[i] == T.cls[j] && letters(q[i]) && letters(t[j]) && (*d = dist(q[i], t[j], C)) <= radius;
+  }, &total);
   std::printf("%s, radius %u gap %u trim %u,%u: %llu hits, %d rows differ\n", name, radius, C.gap, C.ntrim, C.ctrim,
               (unsigned long long)total, bad);
   return bad;

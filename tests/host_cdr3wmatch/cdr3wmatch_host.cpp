@@ -1,8 +1,8 @@
-// Test-only: the host walk of the weighted `match` (cdr3wmatch_walk.h) and the pair test of dcrx_cdr3w_core.h built by g++, for
-// a check against Python on the host.
-#include "cdr3wmatch_walk.h"
+// Test-only: the host walk of the weighted `match` (../host_cdr3walk/cdr3walk_host.h: Bipartite with Weighted) and the pair test
+// of dcrx_cdr3w_core.h built by g++, for a check against Python on the host.
+#include "../host_cdr3walk/cdr3walk_host.h"
 
-using namespace cdr3wmatch_host;
+using namespace cdr3walk_host;
 
 extern "C" {
 // weighted_within of two byte strings (1 .. 32 bytes each), as the kernel calls it: a packed in words, b as 32 bytes
@@ -38,17 +38,7 @@ uint64_t cdr3wmatch_host_match(uint64_t m_t, const uint32_t *t_cls, const uint64
                                const uint32_t *q_cls, const uint64_t *q_off, const uint8_t *q_text, const uint8_t *sub, uint32_t gap,
                                uint32_t ntrim, uint32_t ctrim, uint32_t radius, uint32_t *degree, uint64_t *hit_off,
                                uint32_t *hit, uint32_t *hit_dist, uint64_t hit_cap) {
-  const auto hits = match(m_t, t_cls, t_off, t_text, m_q, q_cls, q_off, q_text, Cost{sub, gap, ntrim, ctrim}, radius);
-  uint64_t at = 0;
-  for (uint64_t i = 0; i < m_q; i++) {
-    degree[i] = (uint32_t)hits[i].size();
-    hit_off[i] = at;
-    for (const Hit &h : hits[i]) {
-      if (at < hit_cap) { hit[at] = h.target; hit_dist[at] = h.dist; }
-      at++;
-    }
-  }
-  hit_off[m_q] = at;
-  return at;
+  return flat(match(m_t, t_cls, t_off, t_text, m_q, q_cls, q_off, q_text, weighted(sub, gap, ntrim, ctrim, radius)), degree, hit_off, hit,
+              hit_dist, hit_cap);
 }
 }

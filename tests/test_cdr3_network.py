@@ -6,6 +6,7 @@ import gzip
 import json
 import os
 import random
+import subprocess
 
 import numpy as np
 import pytest
@@ -85,6 +86,15 @@ def test_core_hamming_gives_up_past_the_limit(D):
     # a byte's value does not matter, only whether it is the same: case, 'X', '*', bytes >= 0x80
     assert dist(b"CASSL", b"cASSL") == 1 and dist(b"CAXSL", b"CA*SL") == 1 and dist(b"CA\x80SL", b"CA\xffSL") == 1
     assert dist(b"CA\x00SL", b"CA\x00SL") == 0 and dist(b"\xff" * 32, b"\x7f" * 32) > D
+
+
+def test_sanitizer_run_of_the_host_walk():
+    """The network's two plain walks (Within with Hamming and with Levenshtein) in a stand-alone program (its own main) under
+    AddressSanitizer and UBSan: host code, on the CPU."""
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_cdr3net")
+    got = subprocess.run(["make", "-s", "-C", here, "asan"], capture_output=True, text=True)
+    assert got.returncode == 0, got.stdout[-2000:] + got.stderr[-2000:]
+    assert got.stdout.splitlines()[-1] == "ok" and "rows differ" in got.stdout and "classes over block edges" in got.stdout
 
 
 # ---- the brute force against answers written out here ----
