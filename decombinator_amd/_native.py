@@ -449,6 +449,16 @@ class Cdr3ProfileStatsC(C.Structure):      # dcrx_cdr3_profile_stats_t
     _fields_ = [(k, C.c_uint64) for k in CDR3_PROFILE_STATS]
 
 
+CDR3_NO_RADIUS = 0xFFFFFFFF          # DCRX_CDR3_NO_RADIUS: a target of dcrx_cdr3_tally_weighted that takes part in nothing
+CDR3_TALLY_MAX_SAMPLES = 64          # files of one `tabulate` call
+CDR3_TALLY_STATS = ("queries", "targets", "queries_out_of_reach", "queries_not_letters", "targets_out_of_reach",
+                    "targets_without_radius", "hits", "queries_hit", "queries_hit_weight", "targets_hit")
+
+
+class Cdr3TallyStatsC(C.Structure):      # dcrx_cdr3_tally_stats_t
+    _fields_ = [(k, C.c_uint64) for k in CDR3_TALLY_STATS]
+
+
 CDR3_MOTIF_MAX_SAMPLES = 64          # files of one `motifs` call
 CDR3_MOTIF_MAX_TRIM = 16             # DCRX_CDR3_MOTIF_MAX_TRIM
 CDR3_MOTIF_MAX_RESAMPLES = 65535     # DCRX_CDR3_MOTIF_MAX_RESAMPLES
@@ -543,6 +553,7 @@ EXPORTS = [
     "dcrx_cdr3_motif_members_work_bytes", "dcrx_cdr3_motif_members_device", "dcrx_cdr3_groups_work_bytes", "dcrx_cdr3_groups_device",
     "dcrx_cdr3_motif_groups",
     "dcrx_cdr3_profile_weighted_work_bytes", "dcrx_cdr3_profile_weighted_device", "dcrx_cdr3_profile_weighted",
+    "dcrx_cdr3_tally_weighted_work_bytes", "dcrx_cdr3_tally_weighted_device", "dcrx_cdr3_tally_weighted",
 ]
 
 _lib = None
@@ -733,6 +744,9 @@ def lib():
         "dcrx_cdr3_profile_weighted_work_bytes": (u64, [u64, u64, u32]),
         "dcrx_cdr3_profile_weighted_device": (i32, [vp, u64, vp, vp, vp, u64, vp, u32, u32, vp, vp, u64, vp]),
         "dcrx_cdr3_profile_weighted": (i32, [vp, u64, vp, vp, vp, vp, u32, u32, vp, C.POINTER(Cdr3ProfileStatsC)]),
+        "dcrx_cdr3_tally_weighted_work_bytes": (u64, [u64, u64, u64]),
+        "dcrx_cdr3_tally_weighted_device": (i32, [vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "dcrx_cdr3_tally_weighted": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Cdr3TallyStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -1829,6 +1843,51 @@ def cdr3_profile_weighted(index: Cdr3Index, classes, off, text: bytes, cost: Cdr
     check(lib().dcrx_cdr3_profile_weighted(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data,
                                            C.addressof(c) if c is not None else None, step, bins, profile.ctypes.data, C.byref(st)))
     return {"profile": profile[:m * bins].reshape(m, bins), "stats": {k: int(getattr(st, k)) for k in CDR3_PROFILE_STATS}}
+
+
+def cdr3_tally_weighted_work_bytes(m_q: int, text_bytes: int, m_t: int) -> int:
+    """dcrx_cdr3_tally_weighted_work_bytes."""
+    return int(lib().dcrx_cdr3_tally_weighted_work_bytes(int(m_q), int(text_bytes), int(m_t)))
+
+
+def cdr3_tally_weighted_device(index: Cdr3Index, m_q: int, d_class, d_off, d_text, text_bytes: int, d_weight, cost: Cdr3Cost, d_radius,
+                               d_t_count, d_t_weight, d_q_degree, d_work, work_bytes: int, stream=None):
+    """dcrx_cdr3_tally_weighted_device: per target of the index the queries of a table in HBM (DeviceBuffers) within the target's
+    own radius (d_radius, by rank) and their weight, per query the targets it hits, asynchronous on `stream`."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    c = cost.as_c() if cost is not None else None      # (alive across the call, which copies it)
+    check(lib().dcrx_cdr3_tally_weighted_device(index.handle, int(m_q), ptr(d_class), ptr(d_off), ptr(d_text), int(text_bytes),
+                                                ptr(d_weight), C.addressof(c) if c is not None else None, ptr(d_radius), ptr(d_t_count),
+                                                ptr(d_t_weight), ptr(d_q_degree), ptr(d_work), int(work_bytes), stream))
+
+
+def cdr3_tally_weighted(index: Cdr3Index, classes, off, text: bytes, weights, cost: Cdr3Cost, radii) -> dict:
+    """dcrx_cdr3_tally_weighted: m_q queries (class, string = text[off[i]:off[i + 1]], weight) against the index's targets, each
+    with a radius of its own (radii, by rank: 0 .. 65535 or CDR3_NO_RADIUS) -> {"t_count": per target the queries within its
+    radius (uint32), "t_weight": the sum of their weights (uint64), "q_degree": per query the targets it hits (uint32), "stats":
+    dict over CDR3_TALLY_STATS}."""
+    cls = np.ascontiguousarray(classes, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.uint64)
+    o, t = _node_arrays(off, text)
+    m = len(cls)
+    if len(o) != m + 1 or len(w) != m:
+        raise ValueError("cdr3_tally_weighted: one class and one weight per query, m + 1 offsets")
+    rr = np.asarray(radii)
+    if rr.size and (rr.min() < 0 or rr.max() >= 1 << 32):
+        raise ValueError("cdr3_tally_weighted: a radius does not fit 32 bits")
+    r = np.ascontiguousarray(rr, dtype=np.uint32)
+    m_t = index.info()["targets"]
+    if len(r) != m_t:
+        raise ValueError(f"cdr3_tally_weighted: {len(r)} radii for {m_t} targets")
+    t_count, t_weight, q_degree = np.empty(max(m_t, 1), np.uint32), np.empty(max(m_t, 1), np.uint64), np.empty(max(m, 1), np.uint32)
+    st = Cdr3TallyStatsC()
+    c = cost.as_c() if cost is not None else None
+    check(lib().dcrx_cdr3_tally_weighted(index.handle, m, cls.ctypes.data, o.ctypes.data, t.ctypes.data, w.ctypes.data,
+                                         C.addressof(c) if c is not None else None, r.ctypes.data, t_count.ctypes.data,
+                                         t_weight.ctypes.data, q_degree.ctypes.data, C.byref(st)))
+    return {"t_count": t_count[:m_t], "t_weight": t_weight[:m_t], "q_degree": q_degree[:m],
+            "stats": {k: int(getattr(st, k)) for k in CDR3_TALLY_STATS}}
 
 
 def format_cdr3_matches_weighted(result: dict, v_idx, j_idx, v_calls, j_calls, off, text: bytes, weights, t_off, t_text: bytes,

@@ -21,6 +21,9 @@
 // file because the index, the work space, the handle and the two halves around the walk are this file's own.
 // The profile (dcrx_cdr3_profile_weighted_*; include/dcrx.h "profile, weighted") is the weighted walk once more, at the top of a
 // ladder of radii, with a histogram of the hits' distances per query for a sink (Profile, dcrx_cdr3walk.h): one pass, no scan.
+// The tally (dcrx_cdr3_tally_weighted_*; include/dcrx.h "tally, weighted") is that walk with a radius per TARGET (WeightedPer) and
+// totals per target for a sink (Tally): accumulators by sorted position in the work space, zeroed in front of the walk, and
+// cdr3_tally_scatter_kernel behind it, which writes every target's cell by rank.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -339,6 +342,58 @@ int run_profile(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, const Cost
   return DCRX_OK;
 }
 
+// ---- the tally (include/dcrx.h "tally, weighted"): the weighted walk with a bound per target and the Tally sink
+
+// the accumulators by sorted position onto the outputs by rank: every cell of the two is written
+__global__ __launch_bounds__(BLOCK) void cdr3_tally_scatter_kernel(const uint32_t *__restrict__ idx, uint32_t n, const uint32_t *__restrict__ acc_count,
+                                                                   const unsigned long long *__restrict__ acc_weight,
+                                                                   uint32_t *__restrict__ t_count, uint64_t *__restrict__ t_weight) {
+  const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t j = idx[p];
+  t_count[j] = acc_count[p];
+  t_weight[j] = acc_weight[p];
+}
+
+// the tally's work space: the profile's, and the two accumulators per target
+struct TallyWork {
+  ProfileWork q;
+  uint32_t *acc_count;
+  unsigned long long *acc_weight;
+  int carve(Pool &P, uint64_t n, uint64_t m_t) {
+    const int rc = q.carve(P, n);
+    if (rc) return rc;
+    P.get(&acc_count, m_t); P.get(&acc_weight, m_t);
+    return DCRX_OK;
+  }
+};
+
+// what both tally entries refuse of (index, m_q, cost) and of their outputs; the cost as the launch argument
+int refuse_tally(const char *who, const dcrx_cdr3_index_t *I, uint64_t m_q, const dcrx_cdr3_cost_t *cost, const void *t_count, const void *t_weight,
+                 const void *q_degree, CostArg *wc) {
+  int rc = refuse(who, I, m_q, 0, METRIC_HAMMING);
+  if (rc || (rc = refuse_cost(who, cost, 0, wc))) return rc;
+  if ((I->m && (!t_count || !t_weight)) || (m_q && !q_degree)) return set_err(DCRX_E_INVALID, (std::string(who) + ": null output").c_str());
+  return DCRX_OK;
+}
+
+// keys, sort and gather of the queries as the weighted match prepares them, the accumulators zeroed, the one walk and the
+// scatter; every cell of the three outputs is written (m_q > 0 and targets > 0 here)
+int run_tally(const dcrx_cdr3_index &I, const Nodes &N, uint64_t n, const uint64_t *d_weight, const CostArg &wc, const uint32_t *d_radius,
+              uint32_t *d_t_count, uint64_t *d_t_weight, uint32_t *d_q_degree, const TallyWork &W, hipStream_t s) {
+  int rc;
+  if ((rc = sorted_keys(N, n, W.q.key, W.q.idx, W.q.cub, (int)LEN_BITS, true, s)) || (rc = gather(N, n, W.q.idx[1], W.q.sj, nullptr, s))) return rc;
+  HIP_TRY(hipMemsetAsync(W.acc_count, 0, I.m * sizeof *W.acc_count, s));
+  HIP_TRY(hipMemsetAsync(W.acc_weight, 0, I.m * sizeof *W.acc_weight, s));
+  const Sorted T = I.targets(true);
+  cdr3_walk_kernel<false><<<grid_for(n), BLOCK, 0, s>>>(W.q.queries(n), T, Bipartite{}, WeightedPer{wc, d_radius},
+                                                        Tally{d_weight, W.acc_count, W.acc_weight, d_q_degree});
+  HIP_TRY(hipGetLastError());
+  cdr3_tally_scatter_kernel<<<grid_for(I.m), BLOCK, 0, s>>>(T.idx, T.n, W.acc_count, W.acc_weight, d_t_count, d_t_weight);
+  HIP_TRY(hipGetLastError());
+  return DCRX_OK;
+}
+
 // the matches text under any metric (cost: the weighted metric's, null otherwise)
 int64_t format_matches(const char *who, uint64_t m_q, const uint64_t *hit_off, const uint32_t *hit, const uint32_t *v_idx, const uint32_t *j_idx,
                                  uint32_t n_v, const char *v_calls, const uint32_t *v_call_off, uint32_t n_j, const char *j_calls,
@@ -644,6 +699,107 @@ int dcrx_cdr3_profile_weighted(const dcrx_cdr3_index_t *I, uint64_t m_q, const u
     st.cells_sum += row;
     st.queries_nonzero += row != 0;
   }
+  if (stats) *stats = st;
+  return DCRX_OK;
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+// ---- the tally's entries (include/dcrx.h "tally, weighted")
+
+uint64_t dcrx_cdr3_tally_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes, uint64_t m_t) {
+  (void)text_bytes;      // (per-query keys, ranks and packed strings, and two accumulators per target)
+  Pool P;
+  TallyWork W;
+  if (m_q >= MAX_NODES || m_t >= MAX_NODES || W.carve(P, m_q, m_t) != DCRX_OK) return 0;
+  return P.bytes();
+}
+
+int dcrx_cdr3_tally_weighted_device(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off, const char *d_text,
+                                    uint64_t text_bytes, const uint64_t *d_weight, const dcrx_cdr3_cost_t *cost, const uint32_t *d_radius,
+                                    uint32_t *d_t_count, uint64_t *d_t_weight, uint32_t *d_q_degree, void *d_work, uint64_t work_bytes,
+                                    void *hip_stream) try {
+  static const char who[] = "dcrx_cdr3_tally_weighted_device";
+  auto fail = [&](const char *what) { return set_err(DCRX_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  CostArg wc;
+  int rc = refuse_tally(who, I, m_q, cost, d_t_count, d_t_weight, d_q_degree, &wc);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
+  dcrx::DeviceGuard on(I->device);
+  if (!m_q || !I->m) {      // nothing can hit: every cell is zero, no kernel
+    if (I->m) {
+      HIP_TRY(hipMemsetAsync(d_t_count, 0, I->m * sizeof(uint32_t), s));
+      HIP_TRY(hipMemsetAsync(d_t_weight, 0, I->m * sizeof(uint64_t), s));
+    }
+    if (m_q) HIP_TRY(hipMemsetAsync(d_q_degree, 0, m_q * sizeof(uint32_t), s));
+    return DCRX_OK;
+  }
+  if (!d_class || !d_off || !d_weight || !d_radius || !d_work || (text_bytes && !d_text)) return fail("null argument");
+  if ((uintptr_t)d_work % ALIGN) return fail("the work space is not 256-byte aligned");
+  Pool P(d_work);
+  TallyWork W;
+  if ((rc = W.carve(P, m_q, I->m))) return rc;
+  if (work_bytes < P.bytes()) return fail("the work space is smaller than dcrx_cdr3_tally_weighted_work_bytes(m_q, text_bytes, targets)");
+  const Nodes N{d_class, d_off, reinterpret_cast<const uint8_t *>(d_text), text_bytes};
+  return run_tally(*I, N, m_q, d_weight, wc, d_radius, d_t_count, d_t_weight, d_q_degree, W, s);
+} catch (const std::exception &e) {
+  return set_err(DCRX_E_NOMEM, e.what());
+}
+
+int dcrx_cdr3_tally_weighted(const dcrx_cdr3_index_t *I, uint64_t m_q, const uint32_t *cls, const uint64_t *off, const char *text,
+                             const uint64_t *weight, const dcrx_cdr3_cost_t *cost, const uint32_t *radius, uint32_t *t_count,
+                             uint64_t *t_weight, uint32_t *q_degree, dcrx_cdr3_tally_stats_t *stats) try {
+  static const char who[] = "dcrx_cdr3_tally_weighted";
+  auto fail = [&](int code, const char *what) { return set_err(code, (std::string(who) + ": " + what).c_str()); };
+  CostArg wc;
+  int rc = refuse_tally(who, I, m_q, cost, t_count, t_weight, q_degree, &wc);
+  if (rc) return rc;
+  const uint64_t m_t = I->m;
+  if ((m_q && (!cls || !off || !weight)) || (m_t && !radius)) return fail(DCRX_E_INVALID, "null argument");
+  if (const char *what = refuse_radii(radius, m_t)) return fail(DCRX_E_INVALID, what);
+  dcrx_cdr3_tally_stats_t st{};
+  st.queries = m_q;
+  st.targets = m_t;
+  st.targets_out_of_reach = I->out_of_reach;
+  for (uint64_t j = 0; j < m_t; j++) st.targets_without_radius += radius[j] == NO_RADIUS;
+  uint64_t total = 0;
+  for (uint64_t k = 0; k < m_q; k++) {
+    if (off[k + 1] < off[k]) return fail(DCRX_E_INVALID, "offsets go backwards");
+    if (__builtin_add_overflow(total, weight[k], &total)) return fail(DCRX_E_UNSUPPORTED, "the sum of the query weights is 2^64 or more");
+  }
+  if (m_q && off[m_q] > off[0] && !text) return fail(DCRX_E_INVALID, "text is null");
+  for (uint64_t k = 0; k < m_q; k++) {
+    const uint64_t len = off[k + 1] - off[k];
+    if (!in_reach(len)) st.queries_out_of_reach++;
+    else if (!host_letters(text + off[k], len)) st.queries_not_letters++;
+  }
+  if (m_q && m_t) {
+    dcrx::DeviceGuard on(I->device);
+    const uint64_t text_bytes = off[m_q] - off[0];
+    Pool P;
+    TallyWork W;
+    uint32_t *d_cls, *d_radius, *d_tc, *d_deg;
+    uint64_t *d_off, *d_weight, *d_tw;
+    uint8_t *d_text;
+    for (int pass = 0; pass < 2; pass++) {
+      P.get(&d_cls, m_q); P.get(&d_off, m_q + 1); P.get(&d_text, text_bytes); P.get(&d_weight, m_q); P.get(&d_radius, m_t);
+      P.get(&d_tc, m_t); P.get(&d_tw, m_t); P.get(&d_deg, m_q);
+      if ((rc = W.carve(P, m_q, m_t)) || (pass == 0 && (rc = P.allocate()))) return rc;
+    }
+    if ((rc = upload_spans(m_q, off, text, d_off, d_text)) || (rc = to_device(d_cls, cls, m_q)) || (rc = to_device(d_weight, weight, m_q)) ||
+        (rc = to_device(d_radius, radius, m_t))) return rc;
+    const Nodes N{d_cls, d_off, d_text, text_bytes};
+    if ((rc = run_tally(*I, N, m_q, d_weight, wc, d_radius, d_tc, d_tw, d_deg, W, nullptr)) || (rc = to_host(t_count, d_tc, m_t)) ||
+        (rc = to_host(t_weight, d_tw, m_t)) || (rc = to_host(q_degree, d_deg, m_q))) return rc;
+  } else {
+    if (m_t) { std::memset(t_count, 0, m_t * sizeof(uint32_t)); std::memset(t_weight, 0, m_t * sizeof(uint64_t)); }
+    if (m_q) std::memset(q_degree, 0, m_q * sizeof(uint32_t));
+  }
+  for (uint64_t k = 0; k < m_q; k++) {
+    st.hits += q_degree[k];
+    if (q_degree[k]) { st.queries_hit++; st.queries_hit_weight += weight[k]; }
+  }
+  for (uint64_t j = 0; j < m_t; j++) st.targets_hit += t_count[j] != 0;
   if (stats) *stats = st;
   return DCRX_OK;
 } catch (const std::exception &e) {

@@ -13,7 +13,8 @@
 // exact place.
 // Sink says what a walk leaves: Out (the two passes above) or Profile, a histogram of the hits' distances per node
 // (include/dcrx.h "profile, weighted"): a column of `bins` counters per lane in dynamic LDS, one add per hit, read out behind
-// the walk.
+// the walk.  Tally (include/dcrx.h "tally, weighted") leaves totals per ENTRY: a count and a weight per staged entry in LDS,
+// flushed per tile onto accumulators by sorted position.
 // Side says which entries a block walks and whether an entry is the lane's own node: Bipartite (two tables) or Within (one
 // table against itself).  Pair is the pair test: Hamming, Levenshtein or Weighted.  Both are dcrx_cdr3pair_core.h's, which a
 // plain host build shares (tests/host_cdr3walk walks the same tiles with the same structs); what needs the device stands
@@ -64,7 +65,7 @@ struct Sorted {
 // what a walk leaves, by rank of Q: the degree pass degree and deg64 (the same as 64 bits, for the scan), the write pass the
 // hits' ranks — and their distances, where the pair test stores one and dist is not null — at off[rank], below cap
 struct Out {
-  static constexpr bool HIST = false;
+  static constexpr bool HIST = false, TALLY = false;
   uint32_t *degree;
   uint64_t *deg64;
   const uint64_t *off;
@@ -79,7 +80,7 @@ struct Out {
 // lane's alone, so it needs no barrier: zeroed in front of the walk, read out behind it.  A node that takes no part keeps its
 // zeros and writes them; lanes behind the table write nothing.
 struct Profile {
-  static constexpr bool HIST = true;
+  static constexpr bool HIST = true, TALLY = false;
   uint32_t *row;
   uint32_t step, bins;
   __device__ __forceinline__ uint32_t *column() const {
@@ -95,6 +96,22 @@ struct Profile {
   __device__ __forceinline__ void read_out(const uint32_t *col, uint32_t e) const {
     for (uint32_t b = 0; b < bins; b++) row[(size_t)e * bins + b] = col[b * BLOCK];
   }
+};
+
+// what the tally's walk leaves: per sorted position p of T, acc_count[p] = the nodes of Q that hit the entry and acc_weight[p]
+// the sum of their weights (weight: by rank of Q), ADDED onto what the arrays hold — the caller zeroes them in front of the walk —,
+// and by rank of Q degree = the entries the node hits.  A block keeps a count and a weight per staged entry in LDS (lds_c, lds_w
+// of the walk: 3 KB); a hit adds to them with LDS atomics whose results are not read.  At the top of the next tile, behind the
+// barrier that stands there, and once behind the walk, lane k flushes entry k — where its count is not zero, one global add each
+// onto acc_count[t + k] and acc_weight[t + k], results not read — and zeroes its two cells: at most two global atomics per
+// (block, staged entry) however many lanes hit, on addresses that ascend with the lane because the accumulators are by sorted
+// position (the ranks of a tile are scattered).  A tile that no wave tests adds nothing and so flushes nothing.
+struct Tally {
+  static constexpr bool HIST = false, TALLY = true;
+  const uint64_t *weight;
+  uint32_t *acc_count;
+  unsigned long long *acc_weight;
+  uint32_t *degree;
 };
 
 // the length of node e's string; one past the reach for offsets that go backwards or leave the text
@@ -162,16 +179,24 @@ __device__ __forceinline__ Cost begin(const Weighted &pair) {
   lds_sub[threadIdx.x] = pair.cost.sub[threadIdx.x];      // (the walk's first barrier stands before its first read)
   return Cost{reinterpret_cast<const uint8_t *>(lds_sub), pair.cost.gap, pair.cost.ntrim, pair.cost.ctrim};
 }
+__device__ __forceinline__ Cost begin(const WeightedPer &pair) {      // (an overload of its own: Weighted's stays what it compiled to)
+  __shared__ uint32_t lds_sub[SUB_BYTES / 4];
+  lds_sub[threadIdx.x] = pair.cost.sub[threadIdx.x];
+  return Cost{reinterpret_cast<const uint8_t *>(lds_sub), pair.cost.gap, pair.cost.ntrim, pair.cost.ctrim};
+}
 
 // The walk (see the head of the file).  Q: the block's nodes, T: the entries it walks, both sorted in Pair's bucket order.
 template <bool WRITE, class Side, class Pair, class Sink = Out>
 __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Side side, Pair pair, Sink O) {
   constexpr bool CLS = Pair::CLS;
-  static_assert(!(Sink::HIST && WRITE), "a profile is one pass");
+  static_assert(!((Sink::HIST || Sink::TALLY) && WRITE), "a profile and a tally are one pass");
   __shared__ uint4 lds_j[TILE * 2];
   __shared__ uint64_t lds_k[TILE];
   __shared__ uint32_t lds_r[WRITE ? TILE : 1];
   __shared__ uint32_t lds_p[Pair::MASKS ? TILE : 1];
+  __shared__ uint32_t lds_b[Pair::PER ? TILE : 1];                    // the staged entries' own bounds
+  __shared__ uint32_t lds_c[Sink::TALLY ? TILE : 1];                  // the tally: per staged entry the hits ...
+  __shared__ unsigned long long lds_w[Sink::TALLY ? TILE : 1];        // ... and their weights
   const typename Pair::Ctx ctx = begin(pair);
   const uint32_t s0 = blockIdx.x * BLOCK;
   const uint32_t s = s0 + threadIdx.x;
@@ -188,9 +213,28 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
     col = O.column();
     O.clear(col);
   }
+  unsigned long long w_own = 0;
+  uint32_t flush_at = 0;      // the tile whose totals stand in lds_c and lds_w
+  // lane k flushes entry k of that tile (its own two cells: the barriers around the staging stand between this and the adds)
+  auto flush = [&]() __attribute__((always_inline)) {
+    if constexpr (Sink::TALLY) {
+      const uint32_t c = lds_c[threadIdx.x];
+      if (c != 0 && flush_at + threadIdx.x < T.n) {
+        atomicAdd(&O.acc_count[flush_at + threadIdx.x], c);
+        atomicAdd(&O.acc_weight[flush_at + threadIdx.x], lds_w[threadIdx.x]);
+        lds_c[threadIdx.x] = 0;
+        lds_w[threadIdx.x] = 0;
+      }
+    }
+  };
+  if constexpr (Sink::TALLY) {
+    lds_c[threadIdx.x] = 0;
+    lds_w[threadIdx.x] = 0;
+  }
   if (valid) {
     e = Q.idx[s];
     if constexpr (WRITE) at = O.off[e];
+    if constexpr (Sink::TALLY) w_own = O.weight[e];
     if (reach) {
       const uint4 a = Q.sj[2 * (size_t)s], b = Q.sj[2 * (size_t)s + 1];
       own[0] = a.x; own[1] = a.y; own[2] = a.z; own[3] = a.w; own[4] = b.x; own[5] = b.y; own[6] = b.z; own[7] = b.w;
@@ -203,6 +247,8 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
   for (uint32_t t = R.first; t < T.n; t += TILE) {
     if (!goes_on<CLS>(R, T.key[t])) break;
     __syncthreads();                                        // the previous tile is no longer read
+    flush();
+    flush_at = t;
     const uint32_t tile_n = min((uint32_t)TILE, T.n - t);
     if (threadIdx.x < tile_n) {
       const uint32_t p = t + threadIdx.x;
@@ -210,7 +256,13 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
       lds_j[2 * threadIdx.x] = a;
       lds_j[2 * threadIdx.x + 1] = b;
       const uint32_t w[WORDS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-      lds_k[threadIdx.x] = pair.staged(w, T.key[p]);
+      if constexpr (Pair::PER) {
+        const uint32_t bound = pair.bound_of(T.idx[p]);      // (a gather by rank: the index stays as it is)
+        lds_b[threadIdx.x] = bound;
+        lds_k[threadIdx.x] = pair.staged(w, T.key[p], bound);
+      } else {
+        lds_k[threadIdx.x] = pair.staged(w, T.key[p]);
+      }
       if (WRITE) lds_r[threadIdx.x] = T.idx[p];
       if (Pair::MASKS) lds_p[threadIdx.x] = T.pres[p];
     }
@@ -218,10 +270,21 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
     if (wave_skips(bucket_of<CLS>(lds_k[0]), bucket_of<CLS>(lds_k[tile_n - 1]), w_lo, w_hi)) continue;
     const uint32_t *lj = reinterpret_cast<const uint32_t *>(lds_j);
     auto take = [&](uint32_t q, uint32_t len_q) __attribute__((always_inline)) {
-      const uint32_t d = pair.test(ctx, own, len_own, lj + q * WORDS, len_q);
-      if (d <= pair.bound()) {
+      uint32_t d, bound;
+      if constexpr (Pair::PER) {
+        bound = lds_b[q];      // (a broadcast, as the key)
+        d = pair.test(ctx, own, len_own, lj + q * WORDS, len_q, bound);
+      } else {
+        bound = pair.bound();
+        d = pair.test(ctx, own, len_own, lj + q * WORDS, len_q);
+      }
+      if (d <= bound) {
         if constexpr (Sink::HIST) {
           O.add(col, d);
+        } else if constexpr (Sink::TALLY) {
+          atomicAdd(&lds_c[q], 1u);      // (results not read)
+          atomicAdd(&lds_w[q], w_own);
+          count++;
         } else {
           if (WRITE && at + count < O.cap) {
             O.hit[at + count] = lds_r[q];
@@ -246,7 +309,9 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
       if (kq < w_lo) continue;
       if (kq > w_hi) break;
       const uint32_t len_q = key_length(key_q);
-      const bool passes = reach && kq == k_own && !side.self(t + q, s) && pair.window(ctx, len_own, pres_own, len_q, Pair::MASKS ? lds_p[q] : 0u);
+      bool passes;
+      if constexpr (Pair::PER) passes = reach && kq == k_own && !side.self(t + q, s) && pair.window(ctx, len_own, pres_own, len_q, 0u, lds_b[q]);
+      else passes = reach && kq == k_own && !side.self(t + q, s) && pair.window(ctx, len_own, pres_own, len_q, Pair::MASKS ? lds_p[q] : 0u);
       if (Pair::DEFER) {
         if (__any(passes && pending != NO_ENTRY)) settle();      // (the same for every lane of the wave)
         if (passes) pending = q;
@@ -258,6 +323,10 @@ __global__ __launch_bounds__(BLOCK) void cdr3_walk_kernel(Sorted Q, Sorted T, Si
   }
   if constexpr (Sink::HIST) {
     if (valid) O.read_out(col, e);
+  } else if constexpr (Sink::TALLY) {
+    __syncthreads();      // (the walk's end is the same for every lane of the block: the last tile's adds are done)
+    flush();
+    if (valid) O.degree[e] = count;
   } else if (valid && !WRITE) {
     O.degree[e] = count;
     O.deg64[e] = count;

@@ -326,6 +326,40 @@ def _metaclonotypes(p: argparse.ArgumentParser):
                         "its radius, with their distances")
 
 
+def _tabulate(p: argparse.ArgumentParser):
+    p.add_argument("-in", "--infile", type=str, nargs="+", required=True,
+                   help="1 to 64 .clonotypes.tsv files (plain or .gz), one per bulk sample; a sample is named by its file name "
+                        "without .clonotypes.tsv[.gz]")
+    p.add_argument("-mc", "--metaclonotypes", type=str, default=None,
+                   help="The meta-clonotypes (required): a tab-separated table (plain or .gz) with a header line, its columns found "
+                        "by name; a .cdr3_metaclonotypes.tsv of `metaclonotypes` is one as it stands.  A row whose radius is `.` is "
+                        "left out")
+    p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
+    p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
+    p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
+    p.add_argument("--mc-cdr3-column", dest="mc_cdr3_column", type=str, default="junction_aa",
+                   help="The -mc column that holds the centroid's CDR3 amino acids (default junction_aa)")
+    p.add_argument("--mc-v-column", dest="mc_v_column", type=str, default="v_call",
+                   help="The -mc column that holds the V call (default v_call); read when the class needs it")
+    p.add_argument("--mc-j-column", dest="mc_j_column", type=str, default="j_call",
+                   help="The -mc column that holds the J call (default j_call); read when the class needs it")
+    p.add_argument("--mc-radius-column", dest="mc_radius_column", type=str, default="radius",
+                   help="The -mc column that holds the radius, an integer 0 to 65535 or `.` (default radius)")
+    p.add_argument("--cdr3-class", dest="cdr3_class", choices=["none", "v", "vj"], default="v",
+                   help="What a clonotype and a centroid must share to be compared: nothing (none), the V call (v, the default) or "
+                        "the V and the J call (vj).  The class, --strip-alleles and the three cost flags have to be the ones the "
+                        "meta-clonotypes were made under")
+    p.add_argument("--strip-alleles", dest="strip_alleles", action="store_true",
+                   help="Compare a call up to its first * on both sides (TRBV7-9*01 and TRBV7-9*03 are then one V)")
+    p.add_argument("--cdr3-gap-cost", dest="cdr3_gap_cost", type=int, default=None,
+                   help="The price of one gapped position, 1 to 255 (default 12)")
+    p.add_argument("--cdr3-trim", dest="cdr3_trim", type=str, default=None,
+                   help="N,C - the first N and the last C residues of the shorter CDR3 do not count, 0 to 16 each (default 3,2)")
+    p.add_argument("--cdr3-cost-matrix", dest="cdr3_cost_matrix", type=str, default=None,
+                   help="A tab-separated square table of substitution costs 0..255, as `match --cdr3-cost-matrix` takes it.  "
+                        "Default: 3 * min(4, 4 - BLOSUM62), as TCRdist's")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -334,9 +368,10 @@ def create_parser() -> argparse.ArgumentParser:
                     ".freq) runs with --cluster.")
     parser.add_argument("-v", "--version", action="version", version=__version__)
     parser.epilog = ("Further commands have parsers of their own: `match` (clonotypes near a database's CDR3s, GPU), `motifs` "
-                     "(CDR3 k-mers enriched against a background, GPU) and `metaclonotypes` (per clonotype the largest CDR3 radius "
-                     "a background still stays out of, GPU); see `python -m decombinator_amd match --help`, "
-                     "`python -m decombinator_amd motifs --help` and `python -m decombinator_amd metaclonotypes --help`.")
+                     "(CDR3 k-mers enriched against a background, GPU), `metaclonotypes` (per clonotype the largest CDR3 radius "
+                     "a background still stays out of, GPU) and `tabulate` (meta-clonotypes counted in bulk samples, GPU); see "
+                     "`python -m decombinator_amd match --help`, `python -m decombinator_amd motifs --help`, "
+                     "`python -m decombinator_amd metaclonotypes --help` and `python -m decombinator_amd tabulate --help`.")
     sub = parser.add_subparsers(dest="command", help="Available commands")
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
@@ -399,8 +434,21 @@ def create_metaclonotypes_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def create_tabulate_parser() -> argparse.ArgumentParser:
+    """The parser of `tabulate`, a sub-command with a parser of its own, as `match`, `motifs` and `metaclonotypes` are."""
+    parser = argparse.ArgumentParser(
+        prog="python -m decombinator_amd tabulate",
+        description="Bulk tabulation of meta-clonotypes (GPU): per meta-clonotype (centroid CDR3, class, radius — as "
+                    "`metaclonotypes` writes them) and per .clonotypes.tsv file, how many clonotypes and reads fall inside the "
+                    "meta-clonotype's own radius of a TCRdist-style CDR3 distance; writes tabulate.tsv and tabulate_samples.tsv.")
+    _tabulate(parser)
+    return parser
+
+
 def cli_args(argv=None) -> dict:
     words = sys.argv[1:] if argv is None else list(argv)
+    if words and words[0] == "tabulate":
+        return dict(vars(create_tabulate_parser().parse_args(words[1:])), command="tabulate")
     if words and words[0] == "metaclonotypes":
         return dict(vars(create_metaclonotypes_parser().parse_args(words[1:])), command="metaclonotypes")
     if words and words[0] == "match":
@@ -591,6 +639,12 @@ def write_out_metaclonotypes(text: bytes, name: str, inputargs: dict):
     <sample>.cdr3_radius_profile.tsv and <sample>.cdr3_metaclonotype_members.tsv), with write_out_overlap's rules.  Returns the
     file's name."""
     return write_out_overlap(text, name, inputargs, what="meta-clonotype")
+
+
+def write_out_tabulate(text: bytes, name: str, inputargs: dict):
+    """A file of the `tabulate` sub-command: `<outpath><prefix><name>` (tabulate.tsv, tabulate_samples.tsv), with
+    write_out_overlap's rules.  Returns the file's name."""
+    return write_out_overlap(text, name, inputargs, what="tabulate")
 
 
 def write_out_cdr3_clusters(network, inputargs: dict):

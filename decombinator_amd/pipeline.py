@@ -210,6 +210,14 @@ def main(argv=None):
             from .io import create_metaclonotypes_parser
             create_metaclonotypes_parser().error(str(e))
         return
+    if inp["command"] == "tabulate":      # ... and this one: meta-clonotypes counted in bulk samples
+        from . import tabulate
+        try:
+            tabulate.run(inp)
+        except ValueError as e:
+            from .io import create_tabulate_parser
+            create_tabulate_parser().error(str(e))
+        return
     if inp.get("clonotypes"):           # refused before anything is read
         why = clonotype_refusal(inp)
         if why:

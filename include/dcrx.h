@@ -1333,6 +1333,73 @@ int dcrx_cdr3_profile_weighted(const dcrx_cdr3_index_t *index, uint64_t m_q, con
                                const char *text, const dcrx_cdr3_cost_t *cost, uint32_t step, uint32_t bins,
                                uint32_t *profile, dcrx_cdr3_profile_stats_t *stats);
 
+/* ---- tally, weighted (`tabulate`): per TARGET, how many queries — and how much of their weight — lie within that target's OWN
+ * radius: meta-clonotypes (centroid, class, radius) counted in a bulk sample.  "match, weighted" takes one radius and lists
+ * pairs; this takes a radius per target and leaves totals only: no hit list, no second pass, memory linear in the tables.  The
+ * reference has no counterpart: the contract below is this library's own.  The entries only ADD to ABI 5; the entries above
+ * keep their signatures and behaviour ----
+ *
+ * Input: a dcrx_cdr3_index_t (the targets); per target, by rank, a radius r_j (uint32): 0 .. 65535, or DCRX_CDR3_NO_RADIUS,
+ *   which means that the target takes part in nothing; queries as dcrx_cdr3_match_weighted_device takes them (class, string)
+ *   with a weight w_i (uint64); a cost (dcrx_cdr3_cost_t).
+ * Reach, letters-only, classes and the distance are exactly those of "match, weighted".
+ * Hit: (i, j) is a hit when both take part, c_i == c_j, r_j is a radius and dist(i, j) <= r_j.
+ * Output: t_count[j] (uint32) = the queries that hit target j; t_weight[j] (uint64) = the sum of their weights; q_degree[i]
+ *   (uint32) = the targets query i hits (with it the caller counts the queries inside ANY target without counting one twice).
+ *   Every one of the m_t + m_t + m_q cells is written by the call: the caller's buffers need not be cleared.  Everything is an
+ *   integer and a function of the input alone: integer adds, and atomics whose results are not read.  With every r_j = R the
+ *   three arrays are t_queries, t_weight and degree of dcrx_cdr3_match_weighted_run at R.
+ * Refused on the host before any launch with DCRX_E_INVALID: what "match, weighted" refuses of a cost; a null output with a
+ *   non-zero size; a work space that is short or not 256-byte aligned; in the host entry a radius in 65536 .. 0xFFFFFFFE and
+ *   offsets that go backwards.  A weight sum at or above 2^64 is DCRX_E_UNSUPPORTED (the host entry sees it), and so is
+ *   m_q >= 2^30 (an index holds fewer than 2^30 targets).  m_q = 0 zeroes the target arrays on the stream without a kernel,
+ *   and an index of 0 targets zeroes q_degree the same way; neither looks at the work space. */
+#define DCRX_CDR3_NO_RADIUS 0xFFFFFFFFu
+
+typedef struct dcrx_cdr3_tally_stats {
+  uint64_t queries;
+  uint64_t targets;
+  uint64_t queries_out_of_reach;    /* the network's rule: the length alone */
+  uint64_t queries_not_letters;     /* in that reach, with a byte outside 'A' .. 'Z' */
+  uint64_t targets_out_of_reach;    /* the index's count (length alone) */
+  uint64_t targets_without_radius;  /* r_j == DCRX_CDR3_NO_RADIUS */
+  uint64_t hits;                    /* the sum of q_degree */
+  uint64_t queries_hit;             /* queries with q_degree > 0 */
+  uint64_t queries_hit_weight;      /* the sum of their weights */
+  uint64_t targets_hit;             /* targets with t_count > 0 */
+} dcrx_cdr3_tally_stats_t;
+
+/* Bytes of device work space dcrx_cdr3_tally_weighted_device needs for m_q queries against an index of m_t targets (the
+ * queries' sorted keys, ranks and packed strings, the sort's scratch, and a count and a weight accumulator per target); 0 for
+ * m_q >= 2^30 or m_t >= 2^30.  Answered on the host. */
+uint64_t dcrx_cdr3_tally_weighted_work_bytes(uint64_t m_q, uint64_t text_bytes, uint64_t m_t);
+
+/* The primitive, asynchronous on `hip_stream`, with the device arrays, the device rule (the index's device is made current
+ * for the launches) and the work-space rules of dcrx_cdr3_match_weighted_device; `cost` is a HOST pointer, checked and
+ * copied.  d_weight: m_q uint64; d_radius: m_t uint32 by rank; d_t_count, d_t_weight: m_t; d_q_degree: m_q — all device memory.
+ * The host cannot see the radii here: a value above 65535 is treated on the device as DCRX_CDR3_NO_RADIUS.
+ * The steps: keys, the stable sort by class and the gather without masks, as the weighted match prepares its queries; the two
+ * accumulators zeroed; then cdr3_walk_kernel<false, Bipartite, WeightedPer, Tally>: the weighted match's walk, where the lane
+ * that stages a target also stages its radius (a gather by rank; the index is untouched) and a target without one gets a key
+ * of length 0, as one with a non-letter does; the length window and the pair test run at the staged target's own radius.  A
+ * hit adds one and the lane's weight to the staged target's two cells in LDS; per tile, lane k adds target k's non-zero cells
+ * onto the accumulators in the work space, which are indexed by the index's SORTED position, so that a wave's adds touch
+ * contiguous addresses: at most two global atomics per (block, staged target).  cdr3_tally_scatter_kernel then writes every
+ * target's two cells by rank.  q_degree[i] is written by the lane that holds query i. */
+int dcrx_cdr3_tally_weighted_device(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *d_class, const uint64_t *d_off,
+                                    const char *d_text, uint64_t text_bytes, const uint64_t *d_weight,
+                                    const dcrx_cdr3_cost_t *cost, const uint32_t *d_radius, uint32_t *d_t_count,
+                                    uint64_t *d_t_weight, uint32_t *d_q_degree, void *d_work, uint64_t work_bytes,
+                                    void *hip_stream);
+
+/* The whole step on host arrays, synchronous on the index's device: checks the arguments (all of the contract's refusals and
+ * null arrays, before any device call), uploads the queries and the radii into ONE allocation that also holds the outputs and
+ * the work space, runs the primitive's steps and copies the three arrays back.  `stats` may be NULL.  m_q == 0, and an index
+ * of 0 targets, are answered without a launch and without a device call. */
+int dcrx_cdr3_tally_weighted(const dcrx_cdr3_index_t *index, uint64_t m_q, const uint32_t *cls, const uint64_t *off,
+                             const char *text, const uint64_t *weight, const dcrx_cdr3_cost_t *cost, const uint32_t *radius,
+                             uint32_t *t_count, uint64_t *t_weight, uint32_t *q_degree, dcrx_cdr3_tally_stats_t *stats);
+
 /* ---- the CDR3 network, weighted (`--cdr3-network --cdr3-metric weighted`): which clonotypes of ONE table lie within a radius
  * of each other under the weighted distance above, and the clusters they form.  The entries only ADD to ABI 5; the network's
  * *_metric entries keep their signatures and behaviour, and go on refusing metric 2 ----
