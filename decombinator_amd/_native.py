@@ -502,6 +502,17 @@ class OverlapStatsC(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in OVERLAP_STATS]
 
 
+ASSOC_MAX_SAMPLES = 64                  # DCRX_ASSOC_MAX_SAMPLES: a presence pattern and a relabeling are one uint64
+ASSOC_MAX_PERMUTATIONS = 1 << 20        # DCRX_ASSOC_MAX_PERMUTATIONS
+ASSOC_MAX_FEATURES = 1 << 30            # dcrx_assoc_permute: DCRX_E_UNSUPPORTED from here on
+ASSOC_STATS = ("features", "features_weighted", "weight", "permutations", "tail_total", "min_perm_rank")
+ASSOC_OUTPUTS = ("obs_rank", "labels", "perm_min", "tail")
+
+
+class AssocStatsC(C.Structure):      # dcrx_assoc_stats_t
+    _fields_ = [(k, C.c_uint64) for k in ASSOC_STATS]
+
+
 DOWNSAMPLE_MAX_SAMPLES = 4096      # DCRX_DOWNSAMPLE_MAX_SAMPLES
 DOWNSAMPLE_MAX_ROWS = 1 << 30      # dcrx_downsample: DCRX_E_UNSUPPORTED from here on
 DOWNSAMPLE_MAX_READS = 1 << 40     # ... and for this many reads in all
@@ -554,6 +565,7 @@ EXPORTS = [
     "dcrx_cdr3_motif_groups",
     "dcrx_cdr3_profile_weighted_work_bytes", "dcrx_cdr3_profile_weighted_device", "dcrx_cdr3_profile_weighted",
     "dcrx_cdr3_tally_weighted_work_bytes", "dcrx_cdr3_tally_weighted_device", "dcrx_cdr3_tally_weighted",
+    "dcrx_assoc_permute_device", "dcrx_assoc_permute",
 ]
 
 _lib = None
@@ -747,6 +759,8 @@ def lib():
         "dcrx_cdr3_tally_weighted_work_bytes": (u64, [u64, u64, u64]),
         "dcrx_cdr3_tally_weighted_device": (i32, [vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
         "dcrx_cdr3_tally_weighted": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Cdr3TallyStatsC)]),
+        "dcrx_assoc_permute_device": (i32, [u32, u64, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp]),
+        "dcrx_assoc_permute": (i32, [u32, u64, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, C.POINTER(AssocStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -2107,6 +2121,54 @@ def downsample_device(n_samples: int, m: int, d_sample, d_weight, d_depth, seed:
     back."""
     check(lib().dcrx_downsample_device(int(n_samples), int(m), d_sample.ptr, d_weight.ptr, d_depth.ptr, int(seed), d_kept.ptr,
                                        d_reads.ptr, d_depth_used.ptr, d_threshold.ptr, d_work.ptr, int(work_bytes), stream))
+
+
+# ---- association (`associate`): include/dcrx.h "association" ----
+
+def assoc_permute(masks, mults, n_samples: int, case_mask: int, rank_table, n_ranks: int, tail_ranks: int, permutations: int,
+                  seed: int) -> dict:
+    """dcrx_assoc_permute on the current device: F features (presence mask uint64, multiplicity uint32) of n_samples samples, the
+    case mask, the (n_samples + 1)^2 rank table (uint16, m-major), and `permutations` relabelings from one 64-bit seed ->
+    {"obs_rank": per feature its rank under the case mask (uint32), "labels": the relabelings (uint64), "perm_min": per
+    relabeling the smallest rank over the features with a multiplicity (uint32), "tail": per rank below tail_ranks the
+    (feature, relabeling) pairs that have it, with multiplicity (uint64), "stats": dict over ASSOC_STATS}."""
+    mk = np.asarray(masks)
+    ml = np.asarray(mults)
+    if mk.ndim != 1 or ml.shape != mk.shape:
+        raise ValueError("assoc_permute: one mask and one multiplicity per feature")
+    if ml.size and (int(ml.min()) < 0 or int(ml.max()) >= 1 << 32):
+        raise ValueError("assoc_permute: a multiplicity does not fit 32 bits")
+    if not (0 <= int(seed) < 1 << 64 and 0 <= int(case_mask) < 1 << 64):
+        raise ValueError("assoc_permute: the seed and the case mask are 0 .. 2^64 - 1")
+    for name, v in (("n_samples", n_samples), ("n_ranks", n_ranks), ("tail_ranks", tail_ranks), ("permutations", permutations)):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError(f"assoc_permute: {name} does not fit 32 bits")
+    mk = np.ascontiguousarray(mk, dtype=np.uint64)
+    ml = np.ascontiguousarray(ml, dtype=np.uint32)
+    table = np.ascontiguousarray(np.asarray(rank_table).reshape(-1), dtype=np.uint16)
+    N, F, P, T = int(n_samples), len(mk), int(permutations), int(tail_ranks)
+    if 2 <= N <= ASSOC_MAX_SAMPLES and len(table) != (N + 1) * (N + 1):
+        raise ValueError(f"assoc_permute: the rank table holds {len(table)} cells, not (n_samples + 1)^2 = {(N + 1) * (N + 1)}")
+    big = P > ASSOC_MAX_PERMUTATIONS or T > (ASSOC_MAX_SAMPLES + 1) ** 2      # (refused in there: nothing that large is made here)
+    obs = np.empty(max(F, 1), np.uint32)
+    labels, least = np.empty(1 if big else max(P, 1), np.uint64), np.empty(1 if big else max(P, 1), np.uint32)
+    tail = np.empty(1 if big else max(T, 1), np.uint64)
+    st = AssocStatsC()
+    check(lib().dcrx_assoc_permute(N, int(case_mask), F, mk.ctypes.data, ml.ctypes.data, table.ctypes.data, int(n_ranks), T, P, int(seed),
+                                   obs.ctypes.data, labels.ctypes.data, least.ctypes.data, tail.ctypes.data, C.byref(st)))
+    return {"obs_rank": obs[:F], "labels": labels[:P], "perm_min": least[:P], "tail": tail[:T],
+            "stats": {k: int(getattr(st, k)) for k in ASSOC_STATS}}
+
+
+def assoc_permute_device(n_samples: int, case_mask: int, n_features: int, d_mask, d_mult, d_rank, n_ranks: int, tail_ranks: int,
+                         permutations: int, seed: int, d_obs_rank, d_labels, d_perm_min, d_tail, stream=None):
+    """dcrx_assoc_permute_device: the permutation null over arrays in HBM (DeviceBuffers; None where an array is empty),
+    asynchronous on `stream`; nothing is copied back.  The entry takes no work space."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    check(lib().dcrx_assoc_permute_device(int(n_samples), int(case_mask), int(n_features), ptr(d_mask), ptr(d_mult), ptr(d_rank),
+                                          int(n_ranks), int(tail_ranks), int(permutations), int(seed), ptr(d_obs_rank), ptr(d_labels),
+                                          ptr(d_perm_min), ptr(d_tail), stream))
 
 
 def abundance_classes(samples, groups, weights, n_samples: int) -> dict:

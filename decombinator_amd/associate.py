@@ -1,0 +1,353 @@
+"""The `associate` sub-command: which features of a feature by sample table — the meta-clonotypes of a `tabulate.tsv`, or the
+public clonotypes of an `overlap_public.tsv` — are present in the cases of a cohort more (or less) often than in its controls:
+an exact test per feature, and a label-permutation null over ALL features at once for the multiple-testing correction (the null
+of Emerson et al. 2017 for public CMV clonotypes; what tcrdist3 users run after the bulk tabulation).
+
+    python -m decombinator_amd associate -in out/dcr_tabulate.tsv.gz -ph cohort.tsv --case LABEL [-op DIR] [-pf dcr_] [-dz]
+           [--ph-sample-column sample] [--ph-group-column group] [--value clonotypes|reads] [--min-count 1]
+           [--alternative greater|less|two-sided] [--permutations 10000] [--seed 1] [--max-p 0.05] [--write-null]
+
+-in is ONE table, plain or .gz, recognised by its header: a tabulate.tsv (first column `metaclonotype`; sample X's value is the
+column X_clonotypes, or X_reads under --value reads) or an overlap_public.tsv (sample X's value is the column X: reads, so
+--value clonotypes is refused there).  -ph is a tab-separated table with a header whose sample and group columns are found by
+name; a group of `.` or nothing means unknown (the sample is left out and counted), the rest hold exactly two labels and --case
+names one.  A sample of -ph without a column in -in is an error; a sample of -in without a row in -ph is left out and named in a
+printed line.  The N samples used (2 .. 64, at least one per group) stand in -in's column order.
+
+A feature is PRESENT in a sample when its value is at least --min-count: THE TEST IS ON PRESENCE, NOT ABUNDANCE.  With n1 cases,
+n0 controls, a feature present in m samples, k of them cases, and h(x) = C(n1, x) C(n0, m - x), the p-value is, in exact
+fractions of Python integers: `greater` (the default, as Emerson's) the sum of h(x) over x >= k, `less` over x <= k, `two-sided`
+over the x with h(x) <= h(k), each over C(N, m).  All (m, k) a cohort can produce are a table of (N + 1)^2 cells; its cells are
+ranked (dense: equal fractions share a rank), and everything on the device is done on RANKS — integers only, exact.  The
+features are de-duplicated by presence pattern on the host (np.unique: a cohort's rare features have few patterns however many
+clonotypes carry them), and ONE _native.assoc_permute call (include/dcrx.h "association") scores every pattern under every one of
+--permutations relabelings of the samples, drawn from --seed by the counter-based key `overlap --downsample` uses: per
+relabeling the smallest rank (perm_min), per rank at or below --max-p the (feature, relabeling) pairs that reach it (tail).
+With --permutations 0 no native call is made and the stage needs no GPU.  The reference has no counterpart; with permutations
+there is no CPU fallback.  `greater`, 10 000 permutations and 0.05 are design choices after Emerson et al., not measured optima.
+
+Derived, as exact fractions: p_adjusted(f) = (1 + #{p : perm_min[p] <= rank(f)}) / (P + 1), Westfall and Young's single-step
+min-P; for a tail rank r, O(r) = the features at ranks <= r, V(r) = the sum of tail[r'] over r' <= r, fdr(r) = min(1, V(r) /
+(P O(r))), and q_value(f) = the smallest fdr(r) over r >= rank(f): the permutation FDR, made monotone.
+
+`<prefix>associate.tsv[.gz]`: one line per feature of -in, most significant first (by rank, then by file order): the identity
+columns verbatim, present, present_cases, present_controls, cases, controls, odds_ratio, p_value, p_adjusted, q_value (`.`
+where the p-value is above --max-p; both `.` without permutations).
+`<prefix>associate_null.tsv[.gz]` (--write-null): per tail rank: rank, p_value, features, features_cumulative, null_pairs,
+null_cumulative, expected_false (V / P), fdr."""
+from __future__ import annotations
+
+import gzip
+from fractions import Fraction
+from math import comb
+
+import numpy as np
+
+from . import _native as nat
+
+MAX_SAMPLES = nat.ASSOC_MAX_SAMPLES
+ALTERNATIVES = ("greater", "less", "two-sided")
+VALUES = ("clonotypes", "reads")
+DEFAULTS = {"alternative": "greater", "permutations": 10000, "max_p": "0.05", "seed": 1, "min_count": 1,      # after Emerson et
+            "ph_sample_column": "sample", "ph_group_column": "group"}                                          # al.: design choices
+TABULATE_IDENTITY = ["metaclonotype", "v_call", "j_call", "junction_aa", "radius"]
+TABULATE_COLUMNS = TABULATE_IDENTITY + ["samples"]
+PUBLIC_IDENTITY = nat.OVERLAP_PUBLIC_COLUMNS[:3]
+RESULT_COLUMNS = ["present", "present_cases", "present_controls", "cases", "controls", "odds_ratio", "p_value", "p_adjusted", "q_value"]
+NULL_COLUMNS = ["rank", "p_value", "features", "features_cumulative", "null_pairs", "null_cumulative", "expected_false", "fdr"]
+NO_RANK = 0xFFFF      # what a cell no cohort can produce holds in the table (never read)
+
+stats: dict = {}      # the statistics of the last run()
+
+
+def _get(inp: dict, key: str):
+    return inp.get(key) if inp.get(key) is not None else DEFAULTS[key]
+
+
+def parse_max_p(text):
+    """--max-p as an exact Fraction of its own text ("0.05", "5e-2", "1/20"), or None for what is no number or lies outside 0 .. 1."""
+    if isinstance(text, (bool, float)):
+        text = repr(text)
+    try:
+        p = Fraction(str(text).strip())
+    except (ValueError, ZeroDivisionError):
+        return None
+    return p if 0 <= p <= 1 else None
+
+
+def refusal(inp: dict):
+    """Why these arguments cannot run, or None — decided before any file is opened."""
+    if not inp.get("infile"):
+        return "associate takes one table (-in): a tabulate.tsv of `tabulate` or an overlap_public.tsv of `overlap`, plain or .gz"
+    if not inp.get("phenotype"):
+        return "associate takes the cohort (-ph): a tab-separated table with a header line, a sample and a group column"
+    if inp.get("case") in (None, "", "."):
+        return "associate takes the label of the cases (--case): one of the two labels of the -ph group column"
+    if inp.get("value") not in (None,) + VALUES:
+        return f"--value is clonotypes or reads, not {inp['value']}"
+    if _get(inp, "alternative") not in ALTERNATIVES:
+        return f"--alternative is greater, less or two-sided, not {inp['alternative']}"
+    if int(_get(inp, "min_count")) < 1:
+        return f"--min-count is 1 or more, not {inp['min_count']}"
+    if not 0 <= int(_get(inp, "permutations")) <= nat.ASSOC_MAX_PERMUTATIONS:
+        return f"--permutations is 0 to {nat.ASSOC_MAX_PERMUTATIONS} (2^20), not {inp['permutations']}"
+    if not 0 <= int(_get(inp, "seed")) < 1 << 64:
+        return f"--seed is 0 to 2^64 - 1, not {inp['seed']}"
+    if parse_max_p(_get(inp, "max_p")) is None:
+        return f"--max-p is a decimal or a fraction, 0 to 1, not {_get(inp, 'max_p')!r}"
+    return None
+
+
+# ---- the test: every p-value a cohort of n1 cases among N samples can produce ----
+
+def feasible(N: int, n1: int, m: int) -> range:
+    """The k a feature present in m of N samples can have among n1 cases."""
+    return range(max(0, m - (N - n1)), min(m, n1) + 1)
+
+
+def fisher_table(N: int, n1: int, alternative: str) -> dict:
+    """{(m, k): the exact p-value as a Fraction} over the feasible cells."""
+    n0, out = N - n1, {}
+    for m in range(N + 1):
+        ks = feasible(N, n1, m)
+        h = {x: comb(n1, x) * comb(n0, m - x) for x in ks}
+        total = comb(N, m)
+        for k in ks:
+            if alternative == "greater":
+                num = sum(h[x] for x in ks if x >= k)
+            elif alternative == "less":
+                num = sum(h[x] for x in ks if x <= k)
+            else:
+                num = sum(h[x] for x in ks if h[x] <= h[k])
+            out[(m, k)] = Fraction(num, total)
+    return out
+
+
+def rank_table(N: int, n1: int, alternative: str):
+    """(table, p_of_rank): the (N + 1) x (N + 1) uint16 table of dense ranks of the p-values, smaller = more extreme (NO_RANK
+    where a cell is not feasible), and the p-value of every rank, ascending."""
+    cells = fisher_table(N, n1, alternative)
+    p_of_rank = sorted(set(cells.values()))
+    rank_of = {p: r for r, p in enumerate(p_of_rank)}
+    table = np.full((N + 1, N + 1), NO_RANK, dtype=np.uint16)
+    for (m, k), p in cells.items():
+        table[m, k] = rank_of[p]
+    return table, p_of_rank
+
+
+# ---- the two files ----
+
+def _lines(path: str):
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rb") as fh:
+        lines = fh.read().split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    return [x[:-1] if x.endswith(b"\r") else x for x in lines]
+
+
+def read_features(path: str, value):
+    """-in: {"kind": "tabulate" or "public", "identity": the identity columns' names, "rows": per feature its identity cells
+    joined by tabs (bytes, verbatim), "samples": the sample names in column order, "values": features x samples (int64),
+    "value": what the values are}.  ValueError for a header that is neither table's (naming it), --value clonotypes on an
+    overlap_public.tsv, a short line and a value that is no integer, by line."""
+    lines = _lines(path)
+    header = [h.decode("utf-8", "replace") for h in lines[0].split(b"\t")] if lines else []
+    if header[:len(TABULATE_COLUMNS)] == TABULATE_COLUMNS:
+        kind, identity, value = "tabulate", TABULATE_IDENTITY, value or "clonotypes"
+        rest = header[len(TABULATE_COLUMNS):]
+        suffix = "_" + value
+        at = {h[:-len(suffix)]: len(TABULATE_COLUMNS) + i for i, h in enumerate(rest) if h.endswith(suffix)}
+        samples = [h[:-len("_clonotypes")] for h in rest if h.endswith("_clonotypes")]
+        if len(rest) != 2 * len(samples) or any(s not in at for s in samples):
+            raise ValueError(f"{path}: a tabulate.tsv holds <sample>_clonotypes and <sample>_reads per sample; its header is " + "\t".join(header))
+    elif header[:len(nat.OVERLAP_PUBLIC_COLUMNS)] == nat.OVERLAP_PUBLIC_COLUMNS:
+        if value == "clonotypes":
+            raise ValueError(f"{path} is an overlap_public.tsv: it holds reads per sample, so --value clonotypes cannot be served")
+        kind, identity, value = "public", PUBLIC_IDENTITY, "reads"
+        samples = header[len(nat.OVERLAP_PUBLIC_COLUMNS):]
+        at = {s: len(nat.OVERLAP_PUBLIC_COLUMNS) + i for i, s in enumerate(samples)}
+    else:
+        raise ValueError(f"{path} is neither a tabulate.tsv (first columns {', '.join(TABULATE_COLUMNS)}) nor an overlap_public.tsv "
+                         f"(first columns {', '.join(nat.OVERLAP_PUBLIC_COLUMNS)}); its header is {' '.join(header)!r}")
+    for k, s in enumerate(samples):
+        if s in samples[:k]:
+            raise ValueError(f"{path}: the sample {s!r} has two columns")
+    where_id = [header.index(c) for c in identity]
+    where = [at[s] for s in samples]
+    rows, values = [], np.zeros((len(lines) - 1, len(samples)), dtype=np.int64)
+    for n, line in enumerate(lines[1:], 2):
+        f = line.split(b"\t")
+        if len(f) < len(header):
+            raise ValueError(f"{path}, line {n}: {len(f)} fields, fewer than the header's {len(header)}")
+        rows.append(b"\t".join(f[i] for i in where_id))
+        for c, i in enumerate(where):
+            if not f[i].isdigit():
+                raise ValueError(f"{path}, line {n}: the value {f[i].decode('latin-1')!r} of sample {samples[c]!r} is no count")
+            values[n - 2, c] = int(f[i])
+    return {"kind": kind, "identity": identity, "rows": rows, "samples": samples, "values": values, "value": value}
+
+
+def read_phenotype(path: str, sample_column: str, group_column: str) -> dict:
+    """-ph: {sample: group} in file order, the group "" for unknown (`.` or nothing).  ValueError for a missing column (naming
+    the file's), a short line and a sample with two rows."""
+    lines = _lines(path)
+    if not lines:
+        raise ValueError(f"{path} has no header line")
+    header = [h.decode("utf-8", "replace") for h in lines[0].split(b"\t")]
+    for name, flag in ((sample_column, "--ph-sample-column"), (group_column, "--ph-group-column")):
+        if name not in header:
+            raise ValueError(f"{path} has no column {name!r} ({flag}); its columns are " + ", ".join(header))
+    at_s, at_g = header.index(sample_column), header.index(group_column)
+    out = {}
+    for n, line in enumerate(lines[1:], 2):
+        f = [x.decode("utf-8", "replace") for x in line.split(b"\t")]
+        if len(f) <= max(at_s, at_g):
+            raise ValueError(f"{path}, line {n}: {len(f)} fields, fewer than the header's {len(header)}")
+        if f[at_s] in out:
+            raise ValueError(f"{path}, line {n}: the sample {f[at_s]!r} has two rows")
+        group = f[at_g].strip()
+        out[f[at_s]] = "" if group == "." else group
+    return out
+
+
+def cohort(features: dict, groups: dict, case: str, path_in: str, path_ph: str) -> dict:
+    """Who takes part: {"used": column indices of -in in column order, "names", "case_mask" (bit i: used sample i is a case),
+    "n1", "n0", "unknown": samples of -ph without a group, "not_in_ph": samples of -in without a row}."""
+    have = set(features["samples"])
+    for s in groups:
+        if s not in have:
+            raise ValueError(f"{path_ph}: the sample {s!r} has no column in {path_in}")
+    labels = sorted({g for g in groups.values() if g})
+    if len(labels) != 2:
+        raise ValueError(f"{path_ph}: the group column holds {len(labels)} labels ({', '.join(labels) or 'none'}), not two")
+    if case not in labels:
+        raise ValueError(f"--case {case!r} is none of the two labels of {path_ph}: {labels[0]!r}, {labels[1]!r}")
+    used = [i for i, s in enumerate(features["samples"]) if groups.get(s)]
+    names = [features["samples"][i] for i in used]
+    case_mask = sum(1 << b for b, s in enumerate(names) if groups[s] == case)
+    n1 = bin(case_mask).count("1")
+    if not 2 <= len(used) <= MAX_SAMPLES:
+        raise ValueError(f"associate takes 2 to {MAX_SAMPLES} samples with a group, not {len(used)}")
+    if n1 == 0 or n1 == len(used):
+        raise ValueError(f"every one of the {len(used)} samples used is a {'case' if n1 else 'control'}: at least one sample per group")
+    return {"used": used, "names": names, "case_mask": case_mask, "n1": n1, "n0": len(used) - n1,
+            "unknown": [s for s, g in groups.items() if not g], "not_in_ph": [s for s in features["samples"] if s not in groups]}
+
+
+def presence_masks(values: np.ndarray, used, min_count: int) -> np.ndarray:
+    masks = np.zeros(values.shape[0], dtype=np.uint64)
+    for b, i in enumerate(used):
+        masks |= (values[:, i] >= min_count).astype(np.uint64) << np.uint64(b)
+    return masks
+
+
+# ---- what follows from the null ----
+
+def derive(obs_rank, mult_of_rank, result, P: int, tail_ranks: int) -> dict:
+    """{"p_adjusted": per RANK the Fraction (1 + #{p : perm_min[p] <= rank}) / (P + 1), "O", "V", "fdr" (None where O is 0) and
+    "q" per tail rank}; obs_rank: the ranks that occur, mult_of_rank: the features at each rank (n_ranks entries)."""
+    least = np.sort(np.asarray(result["perm_min"], dtype=np.int64))
+    p_adjusted = {int(r): Fraction(1 + int(np.searchsorted(least, r, side="right")), P + 1) for r in set(int(x) for x in obs_rank)}
+    O, V, fdr, o, v = [], [], [], 0, 0
+    for r in range(tail_ranks):
+        o += int(mult_of_rank[r])
+        v += int(result["tail"][r])
+        O.append(o); V.append(v)
+        fdr.append(min(Fraction(1), Fraction(v, P * o)) if o else None)
+    q, best = [None] * tail_ranks, None
+    for r in range(tail_ranks - 1, -1, -1):
+        if fdr[r] is not None and (best is None or fdr[r] < best):
+            best = fdr[r]
+        q[r] = best
+    return {"p_adjusted": p_adjusted, "O": O, "V": V, "fdr": fdr, "q": q}
+
+
+def odds_ratio(m: int, k: int, n1: int, n0: int) -> str:
+    num, den = k * (n0 - m + k), (m - k) * (n1 - k)
+    if den == 0:
+        return "inf" if num else "nan"
+    return format(float(Fraction(num, den)), ".6g")
+
+
+def sci(x) -> str:
+    return "." if x is None else format(float(x), ".6e")
+
+
+def table_text(features: dict, m, k, ranks, who: dict, p_of_rank, derived, tail_ranks: int) -> bytes:
+    out = ["\t".join(features["identity"] + RESULT_COLUMNS).encode()]
+    n1, n0 = who["n1"], who["n0"]
+    for f in np.argsort(ranks, kind="stable"):
+        r, mf, kf = int(ranks[f]), int(m[f]), int(k[f])
+        cells = [str(mf), str(kf), str(mf - kf), str(n1), str(n0), odds_ratio(mf, kf, n1, n0), sci(p_of_rank[r]),
+                 sci(derived["p_adjusted"][r] if derived else None), sci(derived["q"][r] if derived and r < tail_ranks else None)]
+        out.append(features["rows"][f] + b"\t" + "\t".join(cells).encode())
+    return b"\n".join(out) + b"\n"
+
+
+def null_text(p_of_rank, mult_of_rank, result, derived, P: int, tail_ranks: int) -> bytes:
+    out = ["\t".join(NULL_COLUMNS).encode()]
+    o = 0
+    for r in range(tail_ranks):
+        o += int(mult_of_rank[r])
+        cells = [str(r), sci(p_of_rank[r]), str(int(mult_of_rank[r])), str(o)]
+        if derived:
+            cells += [str(int(result["tail"][r])), str(derived["V"][r]), format(float(Fraction(derived["V"][r], P)), ".6g"), sci(derived["fdr"][r])]
+        else:
+            cells += ["."] * 4
+        out.append("\t".join(cells).encode())
+    return b"\n".join(out) + b"\n"
+
+
+def run(inp: dict) -> dict:
+    """The stage: refusals, the two files, the cohort, the table of ranks, ONE permutation null on the GPU (none with
+    --permutations 0), the derived columns and the files.  Returns {"associate": name, "null": name or None, "result": the native
+    call's (None without permutations), "stats": {...}}.  ValueError for what refusal(), read_features(), read_phenotype() and
+    cohort() name."""
+    from .io import write_out_associate
+    why = refusal(inp)
+    if why:
+        raise ValueError(why)
+    alternative, P, seed = _get(inp, "alternative"), int(_get(inp, "permutations")), int(_get(inp, "seed"))
+    max_p, min_count = parse_max_p(_get(inp, "max_p")), int(_get(inp, "min_count"))
+    features = read_features(inp["infile"], inp.get("value"))
+    groups = read_phenotype(inp["phenotype"], _get(inp, "ph_sample_column"), _get(inp, "ph_group_column"))
+    who = cohort(features, groups, inp["case"], inp["infile"], inp["phenotype"])
+    for s in who["not_in_ph"]:
+        print(f"Sample {s} of {inp['infile']} has no row in {inp['phenotype']}: left out")
+    N, n1 = len(who["used"]), who["n1"]
+    table, p_of_rank = rank_table(N, n1, alternative)
+    n_ranks = len(p_of_rank)
+    tail_ranks = sum(p <= max_p for p in p_of_rank)
+    masks = presence_masks(features["values"], who["used"], min_count)
+    F = len(masks)
+    m = np.array([bin(int(x)).count("1") for x in masks], dtype=np.int64)
+    k = np.array([bin(int(x) & who["case_mask"]).count("1") for x in masks], dtype=np.int64)
+    ranks = table[m, k].astype(np.int64) if F else np.zeros(0, np.int64)
+    mult_of_rank = np.bincount(ranks, minlength=n_ranks)
+    distinct, inverse, counts = np.unique(masks, return_inverse=True, return_counts=True)
+    result = derived = None
+    if P:
+        result = nat.assoc_permute(distinct, counts.astype(np.uint32), N, who["case_mask"], table, n_ranks, tail_ranks, P, seed)
+        if not np.array_equal(np.asarray(result["obs_rank"], dtype=np.int64)[inverse.reshape(-1)], ranks):
+            raise RuntimeError("associate: the device's observed ranks are not the table's")
+        derived = derive(ranks, mult_of_rank, result, P, tail_ranks)
+    out = {"result": result, "null": None}
+    out["associate"] = write_out_associate(table_text(features, m, k, ranks, who, p_of_rank, derived, tail_ranks), "associate.tsv", inp)
+    if inp.get("write_null"):
+        out["null"] = write_out_associate(null_text(p_of_rank, mult_of_rank, result, derived, P, tail_ranks), "associate_null.tsv", inp)
+    best = int(ranks.min()) if F else None
+    q05 = sum(int(mult_of_rank[r]) for r in range(tail_ranks) if derived and derived["q"][r] is not None and derived["q"][r] <= Fraction(1, 20))
+    stats.clear()
+    stats.update({"kind": features["kind"], "value": features["value"], "samples": N, "cases": n1, "controls": N - n1,
+                  "unknown": len(who["unknown"]), "not_in_ph": len(who["not_in_ph"]), "features": F, "masks": len(distinct),
+                  "permutations": P, "seed": seed, "n_ranks": n_ranks, "tail_ranks": tail_ranks,
+                  "min_p": p_of_rank[best] if F else None, "min_p_adjusted": derived["p_adjusted"][best] if derived and F else None,
+                  "q_below_0.05": q05 if derived else None})
+    out["stats"] = dict(stats)
+    print(f"Associated {F:,} features ({len(distinct):,} distinct presence patterns; {features['kind']}, {features['value']} >= {min_count}) "
+          f"with {inp['case']!r}: {N} samples used ({n1} cases, {N - n1} controls; {len(who['unknown'])} left out without a group, "
+          f"{len(who['not_in_ph'])} without a row in -ph), {alternative}, {P:,} permutations, seed {seed}, {tail_ranks} of {n_ranks} ranks "
+          f"at or below {_get(inp, 'max_p')}; smallest p {sci(stats['min_p'])}, smallest adjusted p {sci(stats['min_p_adjusted'])}, "
+          f"{'.' if not derived else q05} features with q <= 0.05")
+    return out

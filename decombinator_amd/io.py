@@ -360,6 +360,44 @@ def _tabulate(p: argparse.ArgumentParser):
                         "Default: 3 * min(4, 4 - BLOSUM62), as TCRdist's")
 
 
+def _associate(p: argparse.ArgumentParser):
+    p.add_argument("-in", "--infile", type=str, default=None,
+                   help="The feature by sample table (required), plain or .gz, recognised by its header: a tabulate.tsv of "
+                        "`tabulate` or an overlap_public.tsv of `overlap`")
+    p.add_argument("-ph", "--phenotype", type=str, default=None,
+                   help="The cohort (required): a tab-separated table (plain or .gz) with a header line, its sample and group "
+                        "columns found by name.  A group of `.` or nothing means unknown: the sample is left out")
+    p.add_argument("--case", dest="case", type=str, default=None,
+                   help="The label of the cases (required): one of the two labels of the group column")
+    p.add_argument("-op", "--outpath", type=str, default="", help="Output directory (default: cwd)")
+    p.add_argument("-pf", "--prefix", type=str, default="dcr_", help='Output file prefix. Default "dcr_"')
+    p.add_argument("-dz", "--dontgzip", action="store_true", help="Do not gzip the output files")
+    p.add_argument("--ph-sample-column", dest="ph_sample_column", type=str, default="sample",
+                   help="The -ph column that holds the sample names, as -in's columns name them (default sample)")
+    p.add_argument("--ph-group-column", dest="ph_group_column", type=str, default="group",
+                   help="The -ph column that holds the group labels (default group)")
+    p.add_argument("--value", dest="value", choices=["clonotypes", "reads"], default=None,
+                   help="Which of a tabulate.tsv's two numbers per sample decides presence (default clonotypes); an "
+                        "overlap_public.tsv holds reads only")
+    p.add_argument("--min-count", dest="min_count", type=int, default=None,
+                   help="A feature is present in a sample when its value is at least this, 1 or more (default 1).  The test is on "
+                        "presence, not abundance")
+    p.add_argument("--alternative", dest="alternative", choices=["greater", "less", "two-sided"], default=None,
+                   help="The exact test's alternative: present in MORE cases than chance (greater, the default, as Emerson et al. "
+                        "2017), in fewer (less), or either (two-sided: the tables no likelier than the observed one)")
+    p.add_argument("--permutations", dest="permutations", type=int, default=None,
+                   help="Relabelings of the samples the null is made of, 0 to 1048576 (default 10000; 0: p-values only, no GPU).  "
+                        "greater, 10000 and 0.05 are design choices after Emerson et al., not measured optima")
+    p.add_argument("--seed", dest="seed", type=int, default=None,
+                   help="The seed of the relabelings, 0 to 2^64 - 1 (default 1): one seed, one set of files")
+    p.add_argument("--max-p", dest="max_p", type=str, default=None,
+                   help="The p-values up to this one form the tail the false discovery rate is estimated on: a decimal or a "
+                        "fraction, 0 to 1, read exactly (0.05 and 1/20 are the same; default 0.05)")
+    p.add_argument("--write-null", dest="write_null", action="store_true",
+                   help="Also write associate_null.tsv: per p-value of the tail the features, the null's pairs and the false "
+                        "discovery rate")
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="decombinator",
@@ -371,7 +409,9 @@ def create_parser() -> argparse.ArgumentParser:
                      "(CDR3 k-mers enriched against a background, GPU), `metaclonotypes` (per clonotype the largest CDR3 radius "
                      "a background still stays out of, GPU) and `tabulate` (meta-clonotypes counted in bulk samples, GPU); see "
                      "`python -m decombinator_amd match --help`, `python -m decombinator_amd motifs --help`, "
-                     "`python -m decombinator_amd metaclonotypes --help` and `python -m decombinator_amd tabulate --help`.")
+                     "`python -m decombinator_amd metaclonotypes --help` and `python -m decombinator_amd tabulate --help`.  "
+                     "`associate` (exact tests over a tabulate.tsv or an overlap_public.tsv with a permutation null, GPU) has one "
+                     "too: `python -m decombinator_amd associate --help`.")
     sub = parser.add_subparsers(dest="command", help="Available commands")
     sub.required = False
     pipe = sub.add_parser("pipeline", help="decombine, then the front half of collapse; with --cluster the whole of collapse and "
@@ -445,8 +485,23 @@ def create_tabulate_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def create_associate_parser() -> argparse.ArgumentParser:
+    """The parser of `associate`, a sub-command with a parser of its own, as `match`, `motifs`, `metaclonotypes` and `tabulate`
+    are."""
+    parser = argparse.ArgumentParser(
+        prog="python -m decombinator_amd associate",
+        description="Association of features with a phenotype (GPU): per meta-clonotype of a tabulate.tsv, or public clonotype of "
+                    "an overlap_public.tsv, an exact test of its presence in the cases against the controls of a cohort, and a "
+                    "label-permutation null over all features for the adjusted p-values and the false discovery rate; writes "
+                    "associate.tsv and, on demand, associate_null.tsv.")
+    _associate(parser)
+    return parser
+
+
 def cli_args(argv=None) -> dict:
     words = sys.argv[1:] if argv is None else list(argv)
+    if words and words[0] == "associate":
+        return dict(vars(create_associate_parser().parse_args(words[1:])), command="associate")
     if words and words[0] == "tabulate":
         return dict(vars(create_tabulate_parser().parse_args(words[1:])), command="tabulate")
     if words and words[0] == "metaclonotypes":
@@ -686,3 +741,9 @@ def write_out_translated(rows, headers, inputargs: dict):
             fh.writelines(lines())
     sort_permissions(outfilename)
     return outfilename
+
+
+def write_out_associate(text: bytes, name: str, inputargs: dict):
+    """A file of the `associate` sub-command: `<outpath><prefix><name>` (associate.tsv, associate_null.tsv), with
+    write_out_overlap's rules.  Returns the file's name."""
+    return write_out_overlap(text, name, inputargs, what="associate")

@@ -218,6 +218,14 @@ def main(argv=None):
             from .io import create_tabulate_parser
             create_tabulate_parser().error(str(e))
         return
+    if inp["command"] == "associate":      # ... and this one: exact tests over a feature by sample table, with a permutation null
+        from . import associate
+        try:
+            associate.run(inp)
+        except ValueError as e:
+            from .io import create_associate_parser
+            create_associate_parser().error(str(e))
+        return
     if inp.get("clonotypes"):           # refused before anything is read
         why = clonotype_refusal(inp)
         if why:

@@ -1400,6 +1400,73 @@ int dcrx_cdr3_tally_weighted(const dcrx_cdr3_index_t *index, uint64_t m_q, const
                              const char *text, const uint64_t *weight, const dcrx_cdr3_cost_t *cost, const uint32_t *radius,
                              uint32_t *t_count, uint64_t *t_weight, uint32_t *q_degree, dcrx_cdr3_tally_stats_t *stats);
 
+/* ---- association (`associate`): the label-permutation null of exact tests over a feature by sample table — every feature
+ * scored again under every relabeling of the samples, on the GPU.  This layer knows nothing about tests, genes or files: the
+ * caller hands it a table of RANKS of p-values and gets integers back.  The reference has no counterpart: the contract below is
+ * this library's own.  The entries only ADD to ABI 5 ----
+ *
+ * Input: N samples, 2 <= N <= DCRX_ASSOC_MAX_SAMPLES (64); a case mask C (uint64, no bit at or above N), n1 = popcount(C),
+ *   1 <= n1 <= N - 1; F features, F < 2^30, each a presence mask M_f (uint64, no bit at or above N) and a multiplicity w_f
+ *   (uint32; 0: the feature takes part in nothing), the sum of the w_f below 2^32; a rank table rank[(N + 1) * (N + 1)] of
+ *   uint16 indexed m * (N + 1) + k, smaller = more extreme: a cell (m, k) is feasible when max(0, m - (N - n1)) <= k <=
+ *   min(m, n1), feasible cells hold 0 .. n_ranks - 1 and the other cells are never read; n_ranks <= (N + 1)^2; tail_ranks in
+ *   0 .. n_ranks; P permutations, 0 <= P <= DCRX_ASSOC_MAX_PERMUTATIONS (2^20); one 64-bit seed.
+ * Relabeling p (p = 0 .. P - 1): L_p is the set of the n1 samples s in 0 .. N - 1 with the smallest key(seed, p, s), key the
+ *   function of "downsample" with p in the sample's place and s in the read's.  The keys of one p are pairwise distinct, as
+ *   there: no tie rule.
+ * Score: m_f = popcount(M_f); r_p(f) = rank[m_f][popcount(M_f & L_p)]; the observed score r(f) = rank[m_f][popcount(M_f & C)].
+ *   Every index reached is a feasible cell, because popcount(L_p) = n1.
+ * Output, every cell written by the call (the caller's buffers need not be cleared), integers only — integer adds, and atomics
+ *   whose results are not read; nothing depends on launch shape or order of arrival:
+ *     obs_rank[f] (uint32) = r(f), also where w_f = 0;   labels[p] (uint64) = L_p;
+ *     perm_min[p] (uint32) = the minimum over f with w_f > 0 of r_p(f), n_ranks when there is no such f;
+ *     tail[r] (uint64), r < tail_ranks, = the sum over p and f of w_f [r_p(f) = r]  (below 2^52 by the limits above).
+ * DCRX_E_INVALID: N outside 2 .. 64; C with a bit at or above N, or n1 of 0 or N; n_ranks of 0 or above (N + 1)^2; tail_ranks
+ *   above n_ranks; a null array with a non-zero size (the table always has one); in the host entry a mask with a bit at or
+ *   above N and a feasible cell at or above n_ranks.  DCRX_E_UNSUPPORTED: F >= 2^30; P > 2^20; in the host entry a multiplicity
+ *   sum of 2^32 or more.  The scalars are judged in this order, before the arrays.
+ * Which test the ranks stand for (one- or two-sided, Fisher's or another), and so whether the table is monotone in k, is the
+ * caller's business: nothing here assumes it. */
+#define DCRX_ASSOC_MAX_SAMPLES 64
+#define DCRX_ASSOC_MAX_PERMUTATIONS (1u << 20)
+
+typedef struct dcrx_assoc_stats {
+  uint64_t features;           /* F */
+  uint64_t features_weighted;  /* those with w_f > 0 */
+  uint64_t weight;             /* the sum of the w_f */
+  uint64_t permutations;       /* P */
+  uint64_t tail_total;         /* the sum of tail[] */
+  uint64_t min_perm_rank;      /* the smallest perm_min (n_ranks where there is none) */
+} dcrx_assoc_stats_t;
+
+/* The primitive, asynchronous on `hip_stream`, all arrays in device memory: d_mask, d_mult and d_obs_rank F entries, d_rank
+ * (N + 1)^2, d_labels and d_perm_min P, d_tail tail_ranks.  Nothing is copied back, nothing waits, nothing is allocated: THE
+ * ENTRY TAKES NO WORK SPACE (the relabelings live in d_labels, everything else in registers and LDS).
+ * The steps: assoc_prepare_kernel, a lane per index, sets tail to 0 and writes obs_rank; assoc_labels_kernel, a lane per
+ * relabeling in blocks of 64, writes the relabeling's N keys once into the lane's own column of LDS, finds L_p by N^2 compares
+ * from there (no array of keys in registers) and sets perm_min to n_ranks; assoc_permute_kernel runs on a grid of (slices of 1024 features) x
+ * (tiles of 1024 relabelings): a block keeps the rank table (uint16) and its own tail cells in LDS, a lane four relabelings and
+ * their running minima in registers; a feature's mask, row and multiplicity are the same for the whole wave; per pair an AND,
+ * a popcount, one LDS read, a min and a compare, and only where the rank is below tail_ranks an LDS add of w_f whose result is
+ * not read.  A block's tail cells are 64 bits wide — a block adds at most 1024 * 1024 multiplicities below 2^32 onto one cell,
+ * below 2^52 — so nothing is flushed before the block's end: one global atomic min per (lane, relabeling), one global 64-bit
+ * atomic add per non-zero tail cell.
+ * What only the device can see: every mask is ANDed with the N-bit mask, and a rank adds to tail only where it is below
+ * tail_ranks, so nothing is read or written outside the arrays, whatever they hold. */
+int dcrx_assoc_permute_device(uint32_t n_samples, uint64_t case_mask, uint64_t n_features, const uint64_t *d_mask,
+                              const uint32_t *d_mult, const uint16_t *d_rank, uint32_t n_ranks, uint32_t tail_ranks,
+                              uint32_t permutations, uint64_t seed, uint32_t *d_obs_rank, uint64_t *d_labels,
+                              uint32_t *d_perm_min, uint64_t *d_tail, void *hip_stream);
+
+/* The host entry, synchronous on the current device, on host arrays of the same shapes: every refusal above before any device
+ * call, ONE allocation, the uploads, the primitive on the null stream, the four arrays copied back.  `stats_out` may be NULL.
+ * F == 0 or P == 0 is answered on the host and touches no device: obs_rank and labels are computed here, perm_min is n_ranks,
+ * tail is 0. */
+int dcrx_assoc_permute(uint32_t n_samples, uint64_t case_mask, uint64_t n_features, const uint64_t *mask, const uint32_t *mult,
+                       const uint16_t *rank, uint32_t n_ranks, uint32_t tail_ranks, uint32_t permutations, uint64_t seed,
+                       uint32_t *obs_rank_out, uint64_t *labels_out, uint32_t *perm_min_out, uint64_t *tail_out,
+                       dcrx_assoc_stats_t *stats_out);
+
 /* ---- the CDR3 network, weighted (`--cdr3-network --cdr3-metric weighted`): which clonotypes of ONE table lie within a radius
  * of each other under the weighted distance above, and the clusters they form.  The entries only ADD to ABI 5; the network's
  * *_metric entries keep their signatures and behaviour, and go on refusing metric 2 ----
