@@ -503,6 +503,7 @@ class OverlapStatsC(C.Structure):
 
 
 ASSOC_MAX_SAMPLES = 64                  # DCRX_ASSOC_MAX_SAMPLES: a presence pattern and a relabeling are one uint64
+ASSOC_WIDE_MAX_SAMPLES = 1024           # DCRX_ASSOC_WIDE_MAX_SAMPLES: patterns and relabelings of up to 16 words
 ASSOC_MAX_PERMUTATIONS = 1 << 20        # DCRX_ASSOC_MAX_PERMUTATIONS
 ASSOC_MAX_FEATURES = 1 << 30            # dcrx_assoc_permute: DCRX_E_UNSUPPORTED from here on
 ASSOC_STATS = ("features", "features_weighted", "weight", "permutations", "tail_total", "min_perm_rank")
@@ -566,6 +567,7 @@ EXPORTS = [
     "dcrx_cdr3_profile_weighted_work_bytes", "dcrx_cdr3_profile_weighted_device", "dcrx_cdr3_profile_weighted",
     "dcrx_cdr3_tally_weighted_work_bytes", "dcrx_cdr3_tally_weighted_device", "dcrx_cdr3_tally_weighted",
     "dcrx_assoc_permute_device", "dcrx_assoc_permute",
+    "dcrx_assoc_permute_wide_device", "dcrx_assoc_permute_wide",
 ]
 
 _lib = None
@@ -761,6 +763,8 @@ def lib():
         "dcrx_cdr3_tally_weighted": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Cdr3TallyStatsC)]),
         "dcrx_assoc_permute_device": (i32, [u32, u64, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp]),
         "dcrx_assoc_permute": (i32, [u32, u64, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, C.POINTER(AssocStatsC)]),
+        "dcrx_assoc_permute_wide_device": (i32, [u32, vp, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp]),
+        "dcrx_assoc_permute_wide": (i32, [u32, vp, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, C.POINTER(AssocStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -2169,6 +2173,72 @@ def assoc_permute_device(n_samples: int, case_mask: int, n_features: int, d_mask
     check(lib().dcrx_assoc_permute_device(int(n_samples), int(case_mask), int(n_features), ptr(d_mask), ptr(d_mult), ptr(d_rank),
                                           int(n_ranks), int(tail_ranks), int(permutations), int(seed), ptr(d_obs_rank), ptr(d_labels),
                                           ptr(d_perm_min), ptr(d_tail), stream))
+
+
+def assoc_case_words(case_words, n_samples: int) -> np.ndarray:
+    """The case mask of "association, wide" as ceil(n_samples / 64) uint64 words (at least one): from an array of words or from
+    one Python integer (bit s: sample s)."""
+    W = max(1, (int(n_samples) + 63) // 64) if 0 <= int(n_samples) <= ASSOC_WIDE_MAX_SAMPLES else 1
+    if isinstance(case_words, int):
+        if case_words < 0 or case_words >> (64 * W):
+            raise ValueError(f"assoc_permute_wide: the case mask does not fit {W} words")
+        case_words = [(case_words >> (64 * w)) & ((1 << 64) - 1) for w in range(W)]
+    words = np.ascontiguousarray(case_words, dtype=np.uint64).reshape(-1)
+    if len(words) != W:
+        raise ValueError(f"assoc_permute_wide: the case mask holds {len(words)} words, not ceil(n_samples / 64) = {W}")
+    return words
+
+
+def assoc_permute_wide(masks, mults, n_samples: int, case_words, rank_table, n_ranks: int, tail_ranks: int, permutations: int,
+                       seed: int) -> dict:
+    """dcrx_assoc_permute_wide on the current device: F features of W = ceil(n_samples / 64) words each (masks[F, W] uint64,
+    sample s is bit s & 63 of word s >> 6; multiplicity uint32), the case mask as W words (or one Python integer), the
+    (n_samples + 1)^2 rank table (uint32, m-major), and `permutations` relabelings from one 64-bit seed -> {"obs_rank": [F]
+    uint32, "labels": [P, W] uint64, "perm_min": [P] uint32, "tail": [tail_ranks] uint64, "stats": dict over ASSOC_STATS}."""
+    for name, v in (("n_samples", n_samples), ("n_ranks", n_ranks), ("tail_ranks", tail_ranks), ("permutations", permutations)):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError(f"assoc_permute_wide: {name} does not fit 32 bits")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("assoc_permute_wide: the seed is 0 .. 2^64 - 1")
+    N, P, T = int(n_samples), int(permutations), int(tail_ranks)
+    cases = assoc_case_words(case_words, N)
+    W = len(cases)
+    mk = np.asarray(masks)
+    ml = np.asarray(mults)
+    if mk.ndim == 1 and W == 1:
+        mk = mk.reshape(-1, 1)
+    if mk.ndim != 2 or mk.shape[1] != W or ml.shape != (mk.shape[0],):
+        raise ValueError(f"assoc_permute_wide: masks are [F, {W}] with one multiplicity per feature")
+    if ml.size and (int(ml.min()) < 0 or int(ml.max()) >= 1 << 32):
+        raise ValueError("assoc_permute_wide: a multiplicity does not fit 32 bits")
+    mk = np.ascontiguousarray(mk, dtype=np.uint64)
+    ml = np.ascontiguousarray(ml, dtype=np.uint32)
+    table = np.ascontiguousarray(np.asarray(rank_table).reshape(-1), dtype=np.uint32)
+    F = len(mk)
+    if 2 <= N <= ASSOC_WIDE_MAX_SAMPLES and len(table) != (N + 1) * (N + 1):
+        raise ValueError(f"assoc_permute_wide: the rank table holds {len(table)} cells, not (n_samples + 1)^2 = {(N + 1) * (N + 1)}")
+    big = P > ASSOC_MAX_PERMUTATIONS or T > (ASSOC_WIDE_MAX_SAMPLES + 1) ** 2      # (refused in there: nothing that large is made here)
+    obs = np.empty(max(F, 1), np.uint32)
+    labels, least = np.empty((1 if big else max(P, 1), W), np.uint64), np.empty(1 if big else max(P, 1), np.uint32)
+    tail = np.empty(1 if big else max(T, 1), np.uint64)
+    st = AssocStatsC()
+    check(lib().dcrx_assoc_permute_wide(N, cases.ctypes.data, F, mk.ctypes.data, ml.ctypes.data, table.ctypes.data, int(n_ranks), T, P,
+                                        int(seed), obs.ctypes.data, labels.ctypes.data, least.ctypes.data, tail.ctypes.data, C.byref(st)))
+    return {"obs_rank": obs[:F], "labels": labels[:P], "perm_min": least[:P], "tail": tail[:T],
+            "stats": {k: int(getattr(st, k)) for k in ASSOC_STATS}}
+
+
+def assoc_permute_wide_device(n_samples: int, case_words, n_features: int, d_mask, d_mult, d_rank, n_ranks: int, tail_ranks: int,
+                              permutations: int, seed: int, d_obs_rank, d_labels, d_perm_min, d_tail, stream=None):
+    """dcrx_assoc_permute_wide_device: the wide permutation null over arrays in HBM (DeviceBuffers; None where an array is empty)
+    — the case mask alone is host memory, W words or one Python integer (None: a null pointer) —, asynchronous on `stream`;
+    nothing is copied back.  The entry takes no work space."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    cases = assoc_case_words(case_words, n_samples) if case_words is not None else None
+    check(lib().dcrx_assoc_permute_wide_device(int(n_samples), cases.ctypes.data if cases is not None else None, int(n_features),
+                                               ptr(d_mask), ptr(d_mult), ptr(d_rank), int(n_ranks), int(tail_ranks), int(permutations),
+                                               int(seed), ptr(d_obs_rank), ptr(d_labels), ptr(d_perm_min), ptr(d_tail), stream))
 
 
 def abundance_classes(samples, groups, weights, n_samples: int) -> dict:

@@ -3,16 +3,23 @@ public clonotypes of an `overlap_public.tsv` — are present in the cases of a c
 an exact test per feature, and a label-permutation null over ALL features at once for the multiple-testing correction (the null
 of Emerson et al. 2017 for public CMV clonotypes; what tcrdist3 users run after the bulk tabulation).
 
-    python -m decombinator_amd associate -in out/dcr_tabulate.tsv.gz -ph cohort.tsv --case LABEL [-op DIR] [-pf dcr_] [-dz]
-           [--ph-sample-column sample] [--ph-group-column group] [--value clonotypes|reads] [--min-count 1]
+    python -m decombinator_amd associate -in out/dcr_tabulate.tsv.gz [more.tsv.gz ...] -ph cohort.tsv --case LABEL [-op DIR]
+           [-pf dcr_] [-dz] [--ph-sample-column sample] [--ph-group-column group] [--value clonotypes|reads] [--min-count 1]
            [--alternative greater|less|two-sided] [--permutations 10000] [--seed 1] [--max-p 0.05] [--write-null]
 
--in is ONE table, plain or .gz, recognised by its header: a tabulate.tsv (first column `metaclonotype`; sample X's value is the
+-in is a table, plain or .gz, recognised by its header: a tabulate.tsv (first column `metaclonotype`; sample X's value is the
 column X_clonotypes, or X_reads under --value reads) or an overlap_public.tsv (sample X's value is the column X: reads, so
---value clonotypes is refused there).  -ph is a tab-separated table with a header whose sample and group columns are found by
-name; a group of `.` or nothing means unknown (the sample is left out and counted), the rest hold exactly two labels and --case
-names one.  A sample of -ph without a column in -in is an error; a sample of -in without a row in -ph is left out and named in a
-printed line.  The N samples used (2 .. 64, at least one per group) stand in -in's column order.
+--value clonotypes is refused there).  SEVERAL tabulate.tsv — the runs of `tabulate` over one -mc file, 64 samples each — are
+joined side by side: their identity columns must hold the same rows in the same order, no sample may occur twice, and the
+samples stand in file order, then column order; more than one overlap_public.tsv is refused (a clonotype missing from one run's
+file was in fewer than --min-samples of that run's samples, not in none).  -ph is a tab-separated table with a header whose
+sample and group columns are found by name; a group of `.` or nothing means unknown (the sample is left out and counted), the
+rest hold exactly two labels and --case names one.  A sample of -ph without a column in -in is an error; a sample of -in
+without a row in -ph is left out and named in a printed line.  The N samples used (2 .. 1024, at least one per group) stand in
+-in's column order.  Up to 64 samples used a presence pattern is one word and _native.assoc_permute runs, every file and line as
+it always was; from 65 on patterns are rows of ceil(N / 64) words, de-duplicated by row and handed over in ascending popcount,
+the table of ranks is built by cumulative sums (rank_table_sums) and holds 32-bit ranks, and _native.assoc_permute_wide runs
+(include/dcrx.h "association, wide").
 
 A feature is PRESENT in a sample when its value is at least --min-count: THE TEST IS ON PRESENCE, NOT ABUNDANCE.  With n1 cases,
 n0 controls, a feature present in m samples, k of them cases, and h(x) = C(n1, x) C(n0, m - x), the p-value is, in exact
@@ -45,7 +52,9 @@ import numpy as np
 
 from . import _native as nat
 
-MAX_SAMPLES = nat.ASSOC_MAX_SAMPLES
+MAX_SAMPLES = nat.ASSOC_MAX_SAMPLES                # up to here the narrow entry: a pattern is one word, a rank 16 bits
+WIDE_MAX_SAMPLES = nat.ASSOC_WIDE_MAX_SAMPLES      # up to here the wide entry: patterns of up to 16 words, ranks of 32 bits
+ANNOUNCE_TABLE_ABOVE = 256                         # samples from which on the table build is announced: it takes seconds
 ALTERNATIVES = ("greater", "less", "two-sided")
 VALUES = ("clonotypes", "reads")
 DEFAULTS = {"alternative": "greater", "permutations": 10000, "max_p": "0.05", "seed": 1, "min_count": 1,      # after Emerson et
@@ -56,6 +65,7 @@ PUBLIC_IDENTITY = nat.OVERLAP_PUBLIC_COLUMNS[:3]
 RESULT_COLUMNS = ["present", "present_cases", "present_controls", "cases", "controls", "odds_ratio", "p_value", "p_adjusted", "q_value"]
 NULL_COLUMNS = ["rank", "p_value", "features", "features_cumulative", "null_pairs", "null_cumulative", "expected_false", "fdr"]
 NO_RANK = 0xFFFF      # what a cell no cohort can produce holds in the table (never read)
+NO_RANK_WIDE = 0xFFFFFFFF      # ... and in the wide layer's table of 32-bit ranks
 
 stats: dict = {}      # the statistics of the last run()
 
@@ -78,7 +88,8 @@ def parse_max_p(text):
 def refusal(inp: dict):
     """Why these arguments cannot run, or None — decided before any file is opened."""
     if not inp.get("infile"):
-        return "associate takes one table (-in): a tabulate.tsv of `tabulate` or an overlap_public.tsv of `overlap`, plain or .gz"
+        return ("associate takes its table (-in): a tabulate.tsv of `tabulate` — or several, the runs over one -mc file — or an "
+                "overlap_public.tsv of `overlap`, plain or .gz")
     if not inp.get("phenotype"):
         return "associate takes the cohort (-ph): a tab-separated table with a header line, a sample and a group column"
     if inp.get("case") in (None, "", "."):
@@ -130,6 +141,50 @@ def rank_table(N: int, n1: int, alternative: str):
     p_of_rank = sorted(set(cells.values()))
     rank_of = {p: r for r, p in enumerate(p_of_rank)}
     table = np.full((N + 1, N + 1), NO_RANK, dtype=np.uint16)
+    for (m, k), p in cells.items():
+        table[m, k] = rank_of[p]
+    return table, p_of_rank
+
+
+def rank_table_sums(N: int, n1: int, alternative: str):
+    """rank_table() for cohorts of any size — the same Fractions and the same dense ranks, as an (N + 1) x (N + 1) uint32 table
+    (NO_RANK_WIDE where a cell is not feasible) — by cumulative sums: fisher_table() sums a row's h(x) again for every k and is
+    cubic in N; here a row is one pass from the top (greater) or from the bottom (less), and for two-sided one sort of the
+    row's h(x), equal h sharing the sum up to the end of their group.  A balanced cohort of 1024 has 131 074 ranks under
+    `greater`; the build takes seconds on one CPU thread (profiles/assoc_wide/bench_assoc_wide.json, "tables", has the times of
+    the recorded run)."""
+    n0 = N - n1
+    of_cases, of_controls = [comb(n1, x) for x in range(n1 + 1)], [comb(n0, y) for y in range(n0 + 1)]
+    cells = {}
+    for m in range(N + 1):
+        ks = feasible(N, n1, m)
+        h = [of_cases[x] * of_controls[m - x] for x in ks]
+        num, run = [0] * len(h), 0
+        if alternative == "greater":
+            for i in range(len(h) - 1, -1, -1):
+                run += h[i]
+                num[i] = run
+        elif alternative == "less":
+            for i in range(len(h)):
+                run += h[i]
+                num[i] = run
+        else:
+            order = sorted(range(len(h)), key=h.__getitem__)
+            a = 0
+            while a < len(order):
+                b = a
+                while b < len(order) and h[order[b]] == h[order[a]]:
+                    run += h[order[b]]
+                    b += 1
+                for i in order[a:b]:
+                    num[i] = run
+                a = b
+        total = comb(N, m)
+        for k, x in zip(ks, num):
+            cells[(m, k)] = Fraction(x, total)
+    p_of_rank = sorted(set(cells.values()))
+    rank_of = {p: r for r, p in enumerate(p_of_rank)}
+    table = np.full((N + 1, N + 1), NO_RANK_WIDE, dtype=np.uint32)
     for (m, k), p in cells.items():
         table[m, k] = rank_of[p]
     return table, p_of_rank
@@ -188,6 +243,45 @@ def read_features(path: str, value):
     return {"kind": kind, "identity": identity, "rows": rows, "samples": samples, "values": values, "value": value}
 
 
+def infiles(inp: dict) -> list:
+    """-in as a list of paths: run() takes one path or a list of them."""
+    given = inp.get("infile")
+    return [given] if isinstance(given, (str, bytes)) or hasattr(given, "__fspath__") else list(given or [])
+
+
+def join_features(paths: list, value):
+    """-in of several tables: the runs of `tabulate` over ONE -mc file, 64 samples each, side by side.  Every file is a
+    tabulate.tsv whose identity columns hold the same rows in the same order; the joined samples stand in file order, then
+    column order.  ValueError for an overlap_public.tsv among several (a clonotype missing from one run's file was in fewer
+    than --min-samples of THAT run's samples, not in none of them: the files cannot be joined), for rows that differ (naming the
+    first file and line that do) and for a sample that occurs in two files."""
+    tables = [read_features(p, value) for p in paths]
+    first = tables[0]
+    if len(tables) == 1:
+        return first
+    for p, t in zip(paths, tables):
+        if t["kind"] != "tabulate":
+            raise ValueError(f"{p} is an overlap_public.tsv, and -in holds {len(paths)} tables: only the tabulate.tsv runs over one -mc file "
+                             "can be joined.  A clonotype missing from one run's overlap_public.tsv was in fewer than --min-samples of "
+                             "that run's samples, not in none of them")
+    seen = {s: paths[0] for s in first["samples"]}
+    for p, t in zip(paths[1:], tables[1:]):
+        for n, (a, b) in enumerate(zip(first["rows"], t["rows"]), 2):
+            if a != b:
+                raise ValueError(f"{p}, line {n}: its identity columns ({', '.join(TABULATE_IDENTITY)}) are not those of {paths[0]}, line "
+                                 f"{n}: the tables of -in are runs of `tabulate` over one -mc file")
+        if len(t["rows"]) != len(first["rows"]):
+            n = min(len(t["rows"]), len(first["rows"])) + 2
+            raise ValueError(f"{p}, line {n}: {p} holds {len(t['rows'])} meta-clonotypes and {paths[0]} holds {len(first['rows'])}: the tables "
+                             "of -in are runs of `tabulate` over one -mc file")
+        for s in t["samples"]:
+            if s in seen:
+                raise ValueError(f"the sample {s!r} has a column in {seen[s]} and in {p}")
+            seen[s] = p
+    return {"kind": "tabulate", "identity": first["identity"], "rows": first["rows"], "samples": [s for t in tables for s in t["samples"]],
+            "values": np.concatenate([t["values"] for t in tables], axis=1), "value": first["value"]}
+
+
 def read_phenotype(path: str, sample_column: str, group_column: str) -> dict:
     """-ph: {sample: group} in file order, the group "" for unknown (`.` or nothing).  ValueError for a missing column (naming
     the file's), a short line and a sample with two rows."""
@@ -227,8 +321,8 @@ def cohort(features: dict, groups: dict, case: str, path_in: str, path_ph: str) 
     names = [features["samples"][i] for i in used]
     case_mask = sum(1 << b for b, s in enumerate(names) if groups[s] == case)
     n1 = bin(case_mask).count("1")
-    if not 2 <= len(used) <= MAX_SAMPLES:
-        raise ValueError(f"associate takes 2 to {MAX_SAMPLES} samples with a group, not {len(used)}")
+    if not 2 <= len(used) <= WIDE_MAX_SAMPLES:
+        raise ValueError(f"associate takes 2 to {WIDE_MAX_SAMPLES} samples with a group, not {len(used)}")
     if n1 == 0 or n1 == len(used):
         raise ValueError(f"every one of the {len(used)} samples used is a {'case' if n1 else 'control'}: at least one sample per group")
     return {"used": used, "names": names, "case_mask": case_mask, "n1": n1, "n0": len(used) - n1,
@@ -240,6 +334,26 @@ def presence_masks(values: np.ndarray, used, min_count: int) -> np.ndarray:
     for b, i in enumerate(used):
         masks |= (values[:, i] >= min_count).astype(np.uint64) << np.uint64(b)
     return masks
+
+
+def presence_words(values: np.ndarray, used, min_count: int) -> np.ndarray:
+    """The presence patterns of a cohort of any size: features x ceil(N / 64) words, used sample b at bit b & 63 of word b >> 6."""
+    words = np.zeros((values.shape[0], (len(used) + 63) // 64), dtype=np.uint64)
+    for b, i in enumerate(used):
+        words[:, b >> 6] |= (values[:, i] >= min_count).astype(np.uint64) << np.uint64(b & 63)
+    return words
+
+
+def popcount_rows(words: np.ndarray) -> np.ndarray:
+    """Per row of a features x words array the bits set (int64)."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(words).astype(np.int64).sum(axis=1)
+    return np.unpackbits(words.view(np.uint8), axis=1).astype(np.int64).sum(axis=1)
+
+
+def case_words(case_mask: int, N: int) -> np.ndarray:
+    return np.array([(case_mask >> (64 * w)) & ((1 << 64) - 1) for w in range((N + 63) // 64)], dtype=np.uint64)
 
 
 # ---- what follows from the null ----
@@ -310,25 +424,48 @@ def run(inp: dict) -> dict:
         raise ValueError(why)
     alternative, P, seed = _get(inp, "alternative"), int(_get(inp, "permutations")), int(_get(inp, "seed"))
     max_p, min_count = parse_max_p(_get(inp, "max_p")), int(_get(inp, "min_count"))
-    features = read_features(inp["infile"], inp.get("value"))
+    paths = infiles(inp)
+    path_in = paths[0] if len(paths) == 1 else ", ".join(str(p) for p in paths)
+    features = join_features(paths, inp.get("value"))
     groups = read_phenotype(inp["phenotype"], _get(inp, "ph_sample_column"), _get(inp, "ph_group_column"))
-    who = cohort(features, groups, inp["case"], inp["infile"], inp["phenotype"])
+    who = cohort(features, groups, inp["case"], path_in, inp["phenotype"])
     for s in who["not_in_ph"]:
-        print(f"Sample {s} of {inp['infile']} has no row in {inp['phenotype']}: left out")
+        print(f"Sample {s} of {path_in} has no row in {inp['phenotype']}: left out")
     N, n1 = len(who["used"]), who["n1"]
-    table, p_of_rank = rank_table(N, n1, alternative)
+    wide = N > MAX_SAMPLES      # 2 .. 64 samples: the narrow entry and everything as it was; 65 .. 1024: the wide one
+    if wide and N > ANNOUNCE_TABLE_ABOVE:
+        print(f"Building the table of exact p-values for {N} samples ({n1} cases): seconds on one CPU thread ...", flush=True)
+    table, p_of_rank = (rank_table_sums if wide else rank_table)(N, n1, alternative)
     n_ranks = len(p_of_rank)
     tail_ranks = sum(p <= max_p for p in p_of_rank)
-    masks = presence_masks(features["values"], who["used"], min_count)
-    F = len(masks)
-    m = np.array([bin(int(x)).count("1") for x in masks], dtype=np.int64)
-    k = np.array([bin(int(x) & who["case_mask"]).count("1") for x in masks], dtype=np.int64)
+    if wide:
+        masks = presence_words(features["values"], who["used"], min_count)
+        F = len(masks)
+        m, k = popcount_rows(masks), popcount_rows(masks & case_words(who["case_mask"], N)[None, :])
+    else:
+        masks = presence_masks(features["values"], who["used"], min_count)
+        F = len(masks)
+        m = np.array([bin(int(x)).count("1") for x in masks], dtype=np.int64)
+        k = np.array([bin(int(x) & who["case_mask"]).count("1") for x in masks], dtype=np.int64)
     ranks = table[m, k].astype(np.int64) if F else np.zeros(0, np.int64)
     mult_of_rank = np.bincount(ranks, minlength=n_ranks)
-    distinct, inverse, counts = np.unique(masks, return_inverse=True, return_counts=True)
+    if wide and F:      # distinct rows, handed over in ascending popcount: the walk's runs of equal popcount are then one a slice
+        distinct, inverse, counts = np.unique(masks, axis=0, return_inverse=True, return_counts=True)
+        order = np.argsort(popcount_rows(distinct), kind="stable")
+        place = np.empty(len(order), dtype=np.int64)
+        place[order] = np.arange(len(order))
+        distinct, counts, inverse = distinct[order], counts[order], place[inverse.reshape(-1)]
+    elif wide:
+        distinct, inverse, counts = masks, np.zeros(0, np.int64), np.zeros(0, np.int64)
+    else:
+        distinct, inverse, counts = np.unique(masks, return_inverse=True, return_counts=True)
     result = derived = None
     if P:
-        result = nat.assoc_permute(distinct, counts.astype(np.uint32), N, who["case_mask"], table, n_ranks, tail_ranks, P, seed)
+        if wide:
+            result = nat.assoc_permute_wide(distinct, counts.astype(np.uint32), N, case_words(who["case_mask"], N), table, n_ranks, tail_ranks,
+                                            P, seed)
+        else:
+            result = nat.assoc_permute(distinct, counts.astype(np.uint32), N, who["case_mask"], table, n_ranks, tail_ranks, P, seed)
         if not np.array_equal(np.asarray(result["obs_rank"], dtype=np.int64)[inverse.reshape(-1)], ranks):
             raise RuntimeError("associate: the device's observed ranks are not the table's")
         derived = derive(ranks, mult_of_rank, result, P, tail_ranks)

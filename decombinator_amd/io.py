@@ -361,9 +361,11 @@ def _tabulate(p: argparse.ArgumentParser):
 
 
 def _associate(p: argparse.ArgumentParser):
-    p.add_argument("-in", "--infile", type=str, default=None,
+    p.add_argument("-in", "--infile", type=str, nargs="+", default=None,
                    help="The feature by sample table (required), plain or .gz, recognised by its header: a tabulate.tsv of "
-                        "`tabulate` or an overlap_public.tsv of `overlap`")
+                        "`tabulate` or an overlap_public.tsv of `overlap`.  Several tabulate.tsv — the runs of `tabulate` over one "
+                        "-mc file, 64 samples each — are joined side by side: same meta-clonotypes in the same order, no sample "
+                        "twice; 2 to 1024 samples with a group take part in all")
     p.add_argument("-ph", "--phenotype", type=str, default=None,
                    help="The cohort (required): a tab-separated table (plain or .gz) with a header line, its sample and group "
                         "columns found by name.  A group of `.` or nothing means unknown: the sample is left out")

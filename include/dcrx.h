@@ -1467,6 +1467,64 @@ int dcrx_assoc_permute(uint32_t n_samples, uint64_t case_mask, uint64_t n_featur
                        uint32_t *obs_rank_out, uint64_t *labels_out, uint32_t *perm_min_out, uint64_t *tail_out,
                        dcrx_assoc_stats_t *stats_out);
 
+/* ---- association, wide (`associate` on cohorts of 65 to 1024 samples): the contract of "association" above with a presence
+ * pattern and a relabeling of W words in place of one, and ranks of 32 bits.  The narrow entries, their limit of 64 samples and
+ * their behaviour stay as they are.  The entries only ADD to ABI 5 ----
+ *
+ * Samples and words: N samples, 2 <= N <= DCRX_ASSOC_WIDE_MAX_SAMPLES (1024), in W = ceil(N / 64) words of uint64: sample s is
+ *   bit s & 63 of word s >> 6.  N <= 64 is served with W = 1 and gives what the narrow layer gives.
+ * Input: a case mask C, a pointer to W words IN HOST MEMORY in both entries (read during the call; no bit at or above N),
+ *   n1 = its popcount, 1 <= n1 <= N - 1; F features, F < 2^30: `mask` is F x W uint64, row-major, feature f's words at
+ *   mask[f W .. f W + W - 1], no bit at or above N; `mult` as above (uint32; 0: the feature takes part in nothing), the sum
+ *   below 2^32; a rank table rank[(N + 1) * (N + 1)] of UINT32 indexed m * (N + 1) + k (a balanced cohort of 1024 has 131 074
+ *   distinct one-sided p-values: sixteen bits do not hold them), feasible cells hold 0 .. n_ranks - 1, the others are never
+ *   read; n_ranks <= (N + 1)^2; tail_ranks in 0 .. n_ranks; P permutations, 0 <= P <= DCRX_ASSOC_MAX_PERMUTATIONS; one seed.
+ * Relabeling p: L_p is the n1 samples with the smallest key(seed, p, s) — the key of "association", so for N <= 64 the
+ *   relabelings are the narrow layer's, bit for bit.
+ * Score: m_f = the sum over the words of popcount(M_f,w); k = the sum over the words of popcount(M_f,w & L_p,w);
+ *   r_p(f) = rank[m_f][k]; the observed score r(f) uses C in L_p's place.
+ * Output, every cell written by the call, integers only — integer adds, and atomics whose results are not read; nothing depends
+ *   on launch shape, on order of arrival or on the ORDER OF THE FEATURES (features may come in any order of popcount: only the
+ *   speed depends on it, fastest in ascending or descending popcount):
+ *     obs_rank[f] (uint32) = r(f), also where w_f = 0;   labels[p W + w] (uint64) = word w of L_p;
+ *     perm_min[p] (uint32) = the minimum over f with w_f > 0 of r_p(f), n_ranks when there is no such f;
+ *     tail[r] (uint64), r < tail_ranks, = the sum over p and f of w_f [r_p(f) = r]  (below 2^52).
+ * Refusals, in this order.  The scalars: DCRX_E_INVALID for N outside 2 .. 1024, n_ranks of 0 or above (N + 1)^2, tail_ranks
+ *   above n_ranks; DCRX_E_UNSUPPORTED for F >= 2^30 and P > 2^20.  Then DCRX_E_INVALID for a null array with a non-zero size
+ *   (the case mask and the table always have one).  Then the case mask: DCRX_E_INVALID for n1 of 0 or N.  What the host entry
+ *   alone can see it alone refuses, in this order: DCRX_E_INVALID for a case-mask bit at or above N (before n1 is judged), for a
+ *   feasible cell at or above n_ranks and for a mask bit at or above N; DCRX_E_UNSUPPORTED for a multiplicity sum of 2^32 or
+ *   more.  The device entry instead ANDs the last word of the case mask and of every mask with the N-bit remainder, adds to
+ *   tail only below tail_ranks and indexes a row of the table only with k <= m <= N: nothing outside the arrays is read or
+ *   written, whatever the arrays hold. */
+#define DCRX_ASSOC_WIDE_MAX_SAMPLES 1024
+
+/* The primitive, asynchronous on `hip_stream`: d_mask F x W, d_mult and d_obs_rank F, d_rank (N + 1)^2 (uint32), d_labels
+ * P x W, d_perm_min P, d_tail tail_ranks, all in device memory; case_mask W words in host memory, copied into the launches'
+ * arguments before the call returns.  Nothing is copied back, nothing waits, nothing is allocated: THE ENTRY TAKES NO WORK
+ * SPACE.
+ * The steps: assoc_wide_prepare_kernel, a lane per index, sets tail to 0 and writes obs_rank; assoc_wide_labels_kernel, a block
+ * per relabeling, stages the N keys once in LDS (8 KB at most), has every lane count the keys smaller than its samples' from
+ * broadcast reads, assembles each word with a ballot and sets perm_min to n_ranks; assoc_wide_permute_kernel<W>, one
+ * instance per W = 1 .. 16 with W a constant in it, runs on a grid of (slices of 1024 features) x (tiles of 1024, 512 or 256 relabelings at up to 4, 8 or 16 words): a
+ * lane keeps 4, 2 or 1 relabelings and their minima in registers, the block walks its slice in runs of equal popcount m with
+ * the row of m (N + 1 uint32) and one 64-bit cell per k in LDS, 12 KB at most whatever tail_ranks is; on a change of m it adds
+ * the non-zero cells to tail[row[k]] where row[k] < tail_ranks and stages the next row.  A feature's words and multiplicity are
+ * the same for the whole block; a word that is 0 is skipped: branched over up to 8 words, and from 9 words on, at one relabeling
+ * a lane, left by the compiler as two popcounts and a select (profiles/assoc_wide/resource_usage.md). */
+int dcrx_assoc_permute_wide_device(uint32_t n_samples, const uint64_t *case_mask, uint64_t n_features, const uint64_t *d_mask,
+                                   const uint32_t *d_mult, const uint32_t *d_rank, uint32_t n_ranks, uint32_t tail_ranks,
+                                   uint32_t permutations, uint64_t seed, uint32_t *d_obs_rank, uint64_t *d_labels,
+                                   uint32_t *d_perm_min, uint64_t *d_tail, void *hip_stream);
+
+/* The host entry, synchronous on the current device, on host arrays of the same shapes: every refusal above before any device
+ * call, ONE allocation, the uploads, the primitive on the null stream, the four arrays copied back.  `stats_out` may be NULL.
+ * F == 0 or P == 0 is answered on the host and touches no device. */
+int dcrx_assoc_permute_wide(uint32_t n_samples, const uint64_t *case_mask, uint64_t n_features, const uint64_t *mask,
+                            const uint32_t *mult, const uint32_t *rank, uint32_t n_ranks, uint32_t tail_ranks,
+                            uint32_t permutations, uint64_t seed, uint32_t *obs_rank_out, uint64_t *labels_out,
+                            uint32_t *perm_min_out, uint64_t *tail_out, dcrx_assoc_stats_t *stats_out);
+
 /* ---- the CDR3 network, weighted (`--cdr3-network --cdr3-metric weighted`): which clonotypes of ONE table lie within a radius
  * of each other under the weighted distance above, and the clusters they form.  The entries only ADD to ABI 5; the network's
  * *_metric entries keep their signatures and behaviour, and go on refusing metric 2 ----
