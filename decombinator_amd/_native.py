@@ -508,10 +508,20 @@ ASSOC_MAX_PERMUTATIONS = 1 << 20        # DCRX_ASSOC_MAX_PERMUTATIONS
 ASSOC_MAX_FEATURES = 1 << 30            # dcrx_assoc_permute: DCRX_E_UNSUPPORTED from here on
 ASSOC_STATS = ("features", "features_weighted", "weight", "permutations", "tail_total", "min_perm_rank")
 ASSOC_OUTPUTS = ("obs_rank", "labels", "perm_min", "tail")
+ASSOC_RANKSUM_PLANES = 7                # DCRX_ASSOC_RANKSUM_PLANES: a score is 0 .. 2 N - 2 <= 126
+ASSOC_RANKSUM_SHIFT = 20                # DCRX_ASSOC_RANKSUM_SHIFT: t = (u scale) >> 20, u clamped to 20 bits
+ASSOC_RANKSUM_MAX_EDGES = 1024          # DCRX_ASSOC_RANKSUM_MAX_EDGES
+ASSOC_RANKSUM_ALTERNATIVES = ("greater", "less", "two-sided")      # the alternative, by number
+ASSOC_RANKSUM_STATS = ("features", "features_weighted", "weight", "permutations", "tail_total", "max_perm_score")
+ASSOC_RANKSUM_OUTPUTS = ("obs_score", "labels", "perm_max", "exceed", "tail")
 
 
 class AssocStatsC(C.Structure):      # dcrx_assoc_stats_t
     _fields_ = [(k, C.c_uint64) for k in ASSOC_STATS]
+
+
+class AssocRanksumStatsC(C.Structure):      # dcrx_assoc_ranksum_stats_t
+    _fields_ = [(k, C.c_uint64) for k in ASSOC_RANKSUM_STATS]
 
 
 DOWNSAMPLE_MAX_SAMPLES = 4096      # DCRX_DOWNSAMPLE_MAX_SAMPLES
@@ -568,6 +578,7 @@ EXPORTS = [
     "dcrx_cdr3_tally_weighted_work_bytes", "dcrx_cdr3_tally_weighted_device", "dcrx_cdr3_tally_weighted",
     "dcrx_assoc_permute_device", "dcrx_assoc_permute",
     "dcrx_assoc_permute_wide_device", "dcrx_assoc_permute_wide",
+    "dcrx_assoc_ranksum_device", "dcrx_assoc_ranksum",
 ]
 
 _lib = None
@@ -765,6 +776,8 @@ def lib():
         "dcrx_assoc_permute": (i32, [u32, u64, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, C.POINTER(AssocStatsC)]),
         "dcrx_assoc_permute_wide_device": (i32, [u32, vp, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, vp]),
         "dcrx_assoc_permute_wide": (i32, [u32, vp, u64, vp, vp, vp, u32, u32, u32, u64, vp, vp, vp, vp, C.POINTER(AssocStatsC)]),
+        "dcrx_assoc_ranksum_device": (i32, [u32, u64, u32, u64, vp, vp, vp, vp, u32, vp, u32, u64, vp, vp, vp, vp, vp, vp]),
+        "dcrx_assoc_ranksum": (i32, [u32, u64, u32, u64, vp, vp, vp, vp, u32, vp, u32, u64, vp, vp, vp, vp, vp, C.POINTER(AssocRanksumStatsC)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not match include/dcrx.h
@@ -2239,6 +2252,73 @@ def assoc_permute_wide_device(n_samples: int, case_words, n_features: int, d_mas
     check(lib().dcrx_assoc_permute_wide_device(int(n_samples), cases.ctypes.data if cases is not None else None, int(n_features),
                                                ptr(d_mask), ptr(d_mult), ptr(d_rank), int(n_ranks), int(tail_ranks), int(permutations),
                                                int(seed), ptr(d_obs_rank), ptr(d_labels), ptr(d_perm_min), ptr(d_tail), stream))
+
+
+def assoc_alternative(alternative) -> int:
+    """The alternative of "association, rank-sum" as its number: a name of ASSOC_RANKSUM_ALTERNATIVES, or the number itself."""
+    if isinstance(alternative, str):
+        if alternative not in ASSOC_RANKSUM_ALTERNATIVES:
+            raise ValueError(f"assoc_ranksum: the alternative is greater, less or two-sided, not {alternative}")
+        return ASSOC_RANKSUM_ALTERNATIVES.index(alternative)
+    if not 0 <= int(alternative) < 1 << 32:
+        raise ValueError("assoc_ranksum: the alternative does not fit 32 bits")
+    return int(alternative)
+
+
+def assoc_ranksum(planes, offsets, scales, mults, n_samples: int, case_mask: int, alternative, edges, permutations: int, seed: int) -> dict:
+    """dcrx_assoc_ranksum on the current device: F features of n_samples samples, each seven bit planes of its scores (planes[F, 7]
+    uint64: bit b of sample s's score is bit s of planes[f, b]), an offset, a scale and a multiplicity (uint32), the case mask,
+    the alternative (a name or 0 .. 2), the strictly ascending edges of the tail (uint32, at most 1024) and `permutations`
+    relabelings from one 64-bit seed -> {"obs_score": per feature its score under the case mask (uint32), "labels": the
+    relabelings (uint64), "perm_max": per relabeling the largest score over the features with a multiplicity (uint32), "exceed":
+    per feature the relabelings that score at least what the case mask does (uint32), "tail": per edge the (feature, relabeling)
+    pairs from it up to the next, with multiplicity (uint64), "stats": dict over ASSOC_RANKSUM_STATS}."""
+    pl = np.asarray(planes)
+    if pl.ndim != 2 or pl.shape[1] != ASSOC_RANKSUM_PLANES:
+        raise ValueError(f"assoc_ranksum: planes are [F, {ASSOC_RANKSUM_PLANES}]")
+    F = pl.shape[0]
+    per_feature = []
+    for name, v in (("offset", offsets), ("scale", scales), ("multiplicity", mults)):
+        a = np.asarray(v)
+        if a.shape != (F,):
+            raise ValueError(f"assoc_ranksum: one {name} per feature")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 32):
+            raise ValueError(f"assoc_ranksum: a {name} does not fit 32 bits")
+        per_feature.append(np.ascontiguousarray(a, dtype=np.uint32))
+    ed = np.asarray(edges)
+    if ed.ndim != 1 or (ed.size and (int(ed.min()) < 0 or int(ed.max()) >= 1 << 32)):
+        raise ValueError("assoc_ranksum: the edges are one array of 32-bit values")
+    if not (0 <= int(seed) < 1 << 64 and 0 <= int(case_mask) < 1 << 64):
+        raise ValueError("assoc_ranksum: the seed and the case mask are 0 .. 2^64 - 1")
+    for name, v in (("n_samples", n_samples), ("permutations", permutations)):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError(f"assoc_ranksum: {name} does not fit 32 bits")
+    alt = assoc_alternative(alternative)
+    pl = np.ascontiguousarray(pl, dtype=np.uint64)
+    ed = np.ascontiguousarray(ed, dtype=np.uint32)
+    off, sc, ml = per_feature
+    N, P, E = int(n_samples), int(permutations), len(ed)
+    big = P > ASSOC_MAX_PERMUTATIONS      # (refused in there: nothing that large is made here)
+    obs, exceed = np.empty(max(F, 1), np.uint32), np.empty(max(F, 1), np.uint32)
+    labels, most = np.empty(1 if big else max(P, 1), np.uint64), np.empty(1 if big else max(P, 1), np.uint32)
+    tail = np.empty(max(E, 1), np.uint64)
+    st = AssocRanksumStatsC()
+    check(lib().dcrx_assoc_ranksum(N, int(case_mask), alt, F, pl.ctypes.data, off.ctypes.data, sc.ctypes.data, ml.ctypes.data, E, ed.ctypes.data,
+                                   P, int(seed), obs.ctypes.data, labels.ctypes.data, most.ctypes.data, exceed.ctypes.data, tail.ctypes.data,
+                                   C.byref(st)))
+    return {"obs_score": obs[:F], "labels": labels[:P], "perm_max": most[:P], "exceed": exceed[:F], "tail": tail[:E],
+            "stats": {k: int(getattr(st, k)) for k in ASSOC_RANKSUM_STATS}}
+
+
+def assoc_ranksum_device(n_samples: int, case_mask: int, alternative, n_features: int, d_plane, d_offset, d_scale, d_mult, n_edges: int,
+                         d_edges, permutations: int, seed: int, d_obs_score, d_labels, d_perm_max, d_exceed, d_tail, stream=None):
+    """dcrx_assoc_ranksum_device: the rank-sum null over arrays in HBM (DeviceBuffers; None where an array is empty), asynchronous
+    on `stream`; nothing is copied back.  The entry takes no work space."""
+    def ptr(b):
+        return b.ptr if b is not None else None
+    check(lib().dcrx_assoc_ranksum_device(int(n_samples), int(case_mask), assoc_alternative(alternative), int(n_features), ptr(d_plane),
+                                          ptr(d_offset), ptr(d_scale), ptr(d_mult), int(n_edges), ptr(d_edges), int(permutations), int(seed),
+                                          ptr(d_obs_score), ptr(d_labels), ptr(d_perm_max), ptr(d_exceed), ptr(d_tail), stream))
 
 
 def abundance_classes(samples, groups, weights, n_samples: int) -> dict:

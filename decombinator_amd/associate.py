@@ -6,6 +6,7 @@ of Emerson et al. 2017 for public CMV clonotypes; what tcrdist3 users run after 
     python -m decombinator_amd associate -in out/dcr_tabulate.tsv.gz [more.tsv.gz ...] -ph cohort.tsv --case LABEL [-op DIR]
            [-pf dcr_] [-dz] [--ph-sample-column sample] [--ph-group-column group] [--value clonotypes|reads] [--min-count 1]
            [--alternative greater|less|two-sided] [--permutations 10000] [--seed 1] [--max-p 0.05] [--write-null]
+           [--test fisher|rank-sum] [--depths dcr_tabulate_samples.tsv]
 
 -in is a table, plain or .gz, recognised by its header: a tabulate.tsv (first column `metaclonotype`; sample X's value is the
 column X_clonotypes, or X_reads under --value reads) or an overlap_public.tsv (sample X's value is the column X: reads, so
@@ -41,12 +42,30 @@ min-P; for a tail rank r, O(r) = the features at ranks <= r, V(r) = the sum of t
 columns verbatim, present, present_cases, present_controls, cases, controls, odds_ratio, p_value, p_adjusted, q_value (`.`
 where the p-value is above --max-p; both `.` without permutations).
 `<prefix>associate_null.tsv[.gz]` (--write-null): per tail rank: rank, p_value, features, features_cumulative, null_pairs,
-null_cumulative, expected_false (V / P), fdr."""
+null_cumulative, expected_false (V / P), fdr.
+
+--test rank-sum (include/dcrx.h "association, rank-sum") asks the other question: is a feature's VALUE — its breadth or
+depth in a sample — higher (or lower) in the cases, whether or not it is present in more of them.  2 to 64 samples used.  Per
+feature the values below --min-count count as 0, the samples are ranked with ties sharing the mid-rank — by value, or by value
+over the sample's depth under --depths (a table with a `sample` column and one named as --value: a tabulate_samples.tsv fits),
+compared by cross-multiplication in integers — and the Wilcoxon / Mann-Whitney rank sum of the cases is standardized in fixed
+point: with doubled mid-ranks d less their minimum, a = d - min d, A = sum a, B = sum a^2, Q = N B - A^2, W the sum of a over
+the cases and D = N W - n1 A, the score is t = (u min(2^32 - 1, isqrt(2^64 / Q))) >> 20, u = D, -D or |D| clamped to 20 bits;
+z = D sqrt((N - 1) / (n1 n0 Q)) is the usual statistic (no continuity correction), and t is z times one factor for all features.
+Rows of equal scores are de-duplicated, and ONE _native.assoc_ranksum call scores every row under every relabeling — the
+relabelings of the default test, word for word.  Derived, as exact fractions: p_value = (1 + #{p : t_p(f) >= t(f)}) / (P + 1),
+the feature's own permutation p-value; p_adjusted = (1 + #{p : max_f t_p(f) >= t(f)}) / (P + 1), Westfall and Young's
+single-step max-T; over the edges e — the up to 1024 largest distinct observed scores — O(e) = the features scoring at least
+e, V(e) = the null's pairs scoring at least e, fdr(e) = min(1, V / (P O)) and q_value = the smallest fdr over the edges at or
+below the feature's score (`.` below the lowest edge).  --max-p has no role there and is refused; --depths is refused under the
+default test.  associate.tsv then holds the identity columns, nonzero, nonzero_cases, nonzero_controls, cases, controls,
+mean_rank_cases, mean_rank_controls, z, score, p_value, p_adjusted, q_value, highest score first; associate_null.tsv per edge,
+highest first: score, z, features, features_cumulative, null_pairs, null_cumulative, expected_false, fdr."""
 from __future__ import annotations
 
 import gzip
 from fractions import Fraction
-from math import comb
+from math import comb, isqrt, sqrt
 
 import numpy as np
 
@@ -56,6 +75,7 @@ MAX_SAMPLES = nat.ASSOC_MAX_SAMPLES                # up to here the narrow entry
 WIDE_MAX_SAMPLES = nat.ASSOC_WIDE_MAX_SAMPLES      # up to here the wide entry: patterns of up to 16 words, ranks of 32 bits
 ANNOUNCE_TABLE_ABOVE = 256                         # samples from which on the table build is announced: it takes seconds
 ALTERNATIVES = ("greater", "less", "two-sided")
+TESTS = ("fisher", "rank-sum")
 VALUES = ("clonotypes", "reads")
 DEFAULTS = {"alternative": "greater", "permutations": 10000, "max_p": "0.05", "seed": 1, "min_count": 1,      # after Emerson et
             "ph_sample_column": "sample", "ph_group_column": "group"}                                          # al.: design choices
@@ -64,6 +84,9 @@ TABULATE_COLUMNS = TABULATE_IDENTITY + ["samples"]
 PUBLIC_IDENTITY = nat.OVERLAP_PUBLIC_COLUMNS[:3]
 RESULT_COLUMNS = ["present", "present_cases", "present_controls", "cases", "controls", "odds_ratio", "p_value", "p_adjusted", "q_value"]
 NULL_COLUMNS = ["rank", "p_value", "features", "features_cumulative", "null_pairs", "null_cumulative", "expected_false", "fdr"]
+RANKSUM_RESULT_COLUMNS = ["nonzero", "nonzero_cases", "nonzero_controls", "cases", "controls", "mean_rank_cases", "mean_rank_controls", "z",
+                          "score", "p_value", "p_adjusted", "q_value"]
+RANKSUM_NULL_COLUMNS = ["score", "z", "features", "features_cumulative", "null_pairs", "null_cumulative", "expected_false", "fdr"]
 NO_RANK = 0xFFFF      # what a cell no cohort can produce holds in the table (never read)
 NO_RANK_WIDE = 0xFFFFFFFF      # ... and in the wide layer's table of 32-bit ranks
 
@@ -87,6 +110,14 @@ def parse_max_p(text):
 
 def refusal(inp: dict):
     """Why these arguments cannot run, or None — decided before any file is opened."""
+    test = inp.get("test") if inp.get("test") is not None else "fisher"
+    if test not in TESTS:
+        return f"--test is fisher or rank-sum, not {inp['test']}"
+    if test == "rank-sum" and inp.get("max_p") is not None:
+        return ("--max-p has no role under --test rank-sum: the tail is the up to 1024 largest distinct observed scores.  Leave it "
+                "out")
+    if test == "fisher" and inp.get("depths"):
+        return "--depths only works with --test rank-sum: the default test is on presence, and a depth does not change presence"
     if not inp.get("infile"):
         return ("associate takes its table (-in): a tabulate.tsv of `tabulate` — or several, the runs over one -mc file — or an "
                 "overlap_public.tsv of `overlap`, plain or .gz")
@@ -356,6 +387,228 @@ def case_words(case_mask: int, N: int) -> np.ndarray:
     return np.array([(case_mask >> (64 * w)) & ((1 << 64) - 1) for w in range((N + 63) // 64)], dtype=np.uint64)
 
 
+# ---- --test rank-sum: scores on the host, in integers ----
+
+def read_depths(path: str, value: str) -> dict:
+    """--depths: {sample: depth} from a tab-separated table with a `sample` column and one named as --value (a
+    tabulate_samples.tsv fits as it stands).  ValueError for a missing column, a short line, a depth that is no count and a
+    sample with two rows."""
+    lines = _lines(path)
+    if not lines:
+        raise ValueError(f"{path} has no header line")
+    header = [h.decode("utf-8", "replace") for h in lines[0].split(b"\t")]
+    for name in ("sample", value):
+        if name not in header:
+            raise ValueError(f"{path} (--depths) has no column {name!r}; its columns are " + ", ".join(header))
+    at_s, at_v = header.index("sample"), header.index(value)
+    out = {}
+    for n, line in enumerate(lines[1:], 2):
+        f = line.split(b"\t")
+        if len(f) <= max(at_s, at_v):
+            raise ValueError(f"{path}, line {n}: {len(f)} fields, fewer than the header's {len(header)}")
+        name = f[at_s].decode("utf-8", "replace")
+        if name in out:
+            raise ValueError(f"{path}, line {n}: the sample {name!r} has two rows")
+        if not f[at_v].isdigit():
+            raise ValueError(f"{path}, line {n}: the depth {f[at_v].decode('latin-1')!r} of sample {name!r} is no count")
+        out[name] = int(f[at_v])
+    return out
+
+
+def rank_scores(values: np.ndarray, used, min_count: int, depths=None, names=None) -> np.ndarray:
+    """The a-matrix of the rank-sum test, features x len(used) (int64): per feature x[s] = the value of used sample s, 0 where it
+    is below min_count; d[s] = 2 #{t : x[t] < x[s]} + #{t : x[t] = x[s]} + 1, the doubled mid-rank; a[s] = d[s] - min d, so the
+    samples holding the smallest value score 0 and a <= 2 N - 2.  depths (one int per used sample, or None): the samples are
+    ordered by x[s] / depths[s] instead, compared by cross-multiplication in integers; ValueError for a depth of 0 under a
+    non-zero value, naming the sample (names[s], or its number)."""
+    x = np.asarray(values, dtype=np.int64)[:, list(used)]
+    x = np.where(x >= min_count, x, 0)
+    F, N = x.shape
+    if depths is not None:
+        depths = [int(v) for v in depths]
+        if len(depths) != N:
+            raise ValueError(f"rank_scores: {len(depths)} depths for {N} samples")
+        for s in range(N):
+            if depths[s] == 0 and F and int(x[:, s].max()) > 0:
+                raise ValueError(f"--depths: the sample {names[s] if names else s!r} has a depth of 0 and a non-zero value")
+        a = np.zeros((F, N), dtype=np.int64)
+        for f in np.flatnonzero(x.any(axis=1)):      # (a row of zeros scores 0 everywhere)
+            key = [Fraction(int(v), d) if v else Fraction(0) for v, d in zip(x[f], depths)]      # Fractions compare by cross-multiplication
+            d2 = [2 * sum(k < mine for k in key) + sum(k == mine for k in key) + 1 for mine in key]
+            a[f] = np.array(d2, dtype=np.int64) - min(d2)
+        return a
+    if not F:
+        return np.zeros((0, N), dtype=np.int64)
+    order = np.argsort(x, axis=1, kind="stable")
+    ranked = np.take_along_axis(x, order, axis=1)
+    at = np.broadcast_to(np.arange(N, dtype=np.int64), (F, N))
+    fresh = np.ones((F, N), dtype=bool)
+    fresh[:, 1:] = ranked[:, 1:] != ranked[:, :-1]
+    first = np.maximum.accumulate(np.where(fresh, at, 0), axis=1)      # where the run of equal values begins: the values below
+    last_flag = np.ones((F, N), dtype=bool)
+    last_flag[:, :-1] = fresh[:, 1:]
+    last = np.minimum.accumulate(np.where(last_flag, at, N - 1)[:, ::-1], axis=1)[:, ::-1]      # ... and where it ends
+    d_ranked = 2 * first + (last - first + 1) + 1
+    d = np.empty((F, N), dtype=np.int64)
+    np.put_along_axis(d, order, d_ranked, axis=1)
+    return d - d.min(axis=1, keepdims=True)
+
+
+def ranksum_inputs(a: np.ndarray, n1: int):
+    """(planes, offsets, scales) of include/dcrx.h "association, rank-sum" from the a-matrix: planes[f, b] holds bit b of a[f, s]
+    at bit s (uint64); offset = n1 A; scale = min(2^32 - 1, isqrt(2^64 // Q)), 0 where Q = 0 (all values equal), with A = sum a,
+    B = sum a^2, Q = N B - A^2 (uint32 both)."""
+    a = np.asarray(a, dtype=np.int64)
+    F, N = a.shape
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << nat.ASSOC_RANKSUM_PLANES):
+        raise ValueError("ranksum_inputs: a score outside 0 .. 127")
+    planes = np.zeros((F, nat.ASSOC_RANKSUM_PLANES), dtype=np.uint64)
+    for b in range(nat.ASSOC_RANKSUM_PLANES):
+        for s in range(N):
+            planes[:, b] |= ((a[:, s] >> b) & 1).astype(np.uint64) << np.uint64(s)
+    A, B = a.sum(axis=1), (a * a).sum(axis=1)
+    Q = N * B - A * A
+    scale_of = {int(q): (min((1 << 32) - 1, isqrt((1 << 64) // int(q))) if q else 0) for q in np.unique(Q)}
+    scales = np.array([scale_of[int(q)] for q in Q], dtype=np.uint32)
+    return planes, (n1 * A).astype(np.uint32), scales
+
+
+def ranksum_D(a: np.ndarray, case_mask: int, n1: int) -> np.ndarray:
+    """D = N W - n1 A per feature (int64), W the sum of a over the cases."""
+    a = np.asarray(a, dtype=np.int64)
+    N = a.shape[1]
+    cases = np.array([(case_mask >> s) & 1 for s in range(N)], dtype=np.int64)
+    return N * (a * cases[None, :]).sum(axis=1) - n1 * a.sum(axis=1)
+
+
+def ranksum_score(D: int, scale: int, alternative: str) -> int:
+    """t of the contract, in Python integers."""
+    u = D if alternative == "greater" else -D if alternative == "less" else abs(D)
+    u = min(max(u, 0), (1 << nat.ASSOC_RANKSUM_SHIFT) - 1)
+    return (u * scale) >> nat.ASSOC_RANKSUM_SHIFT
+
+
+def z_text(D: int, Q: int, N: int, n1: int) -> str:
+    return "nan" if Q == 0 else format(D * sqrt((N - 1) / (n1 * (N - n1) * Q)), ".6g")
+
+
+def z_of_score(t: int, N: int, n1: int) -> float:
+    """The z a score stands for, up to the rounding of scale: t = u 2^32 / (sqrt(Q) 2^20)."""
+    return t / float(1 << (32 - nat.ASSOC_RANKSUM_SHIFT)) * sqrt((N - 1) / (n1 * (N - n1)))
+
+
+def derive_ranksum(scores, edges, result, P: int) -> dict:
+    """{"p_value", "p_adjusted": per feature of `scores` (the de-duplicated rows' observed scores spread back over the features is
+    the caller's), here per distinct SCORE the Fraction (1 + #{p : perm_max[p] >= score}) / (P + 1); "O", "V", "fdr" (None where O
+    is 0) and "q" per edge}."""
+    most = np.sort(np.asarray(result["perm_max"], dtype=np.int64))
+    p_adjusted = {int(t): Fraction(1 + len(most) - int(np.searchsorted(most, t, side="left")), P + 1) for t in set(int(x) for x in scores)}
+    ranked = np.sort(np.asarray(scores, dtype=np.int64))
+    E = len(edges)
+    O, V, fdr, v = [0] * E, [0] * E, [None] * E, 0
+    for j in range(E - 1, -1, -1):
+        v += int(result["tail"][j])
+        O[j] = len(ranked) - int(np.searchsorted(ranked, int(edges[j]), side="left"))
+        V[j] = v
+        fdr[j] = min(Fraction(1), Fraction(v, P * O[j])) if O[j] else None
+    q, best = [None] * E, None
+    for j in range(E):      # the smallest fdr over the edges at or below
+        if fdr[j] is not None and (best is None or fdr[j] < best):
+            best = fdr[j]
+        q[j] = best
+    return {"p_adjusted": p_adjusted, "O": O, "V": V, "fdr": fdr, "q": q}
+
+
+def run_ranksum(inp: dict, features: dict, who: dict, path_in: str) -> dict:
+    """The stage under --test rank-sum, from the cohort on."""
+    from .io import write_out_associate
+    alternative, P, seed = _get(inp, "alternative"), int(_get(inp, "permutations")), int(_get(inp, "seed"))
+    min_count = int(_get(inp, "min_count"))
+    N, n1 = len(who["used"]), who["n1"]
+    if N > MAX_SAMPLES:
+        raise ValueError(f"--test rank-sum takes 2 to {MAX_SAMPLES} samples with a group, not {N}: the wide form (up to {WIDE_MAX_SAMPLES} "
+                         "samples, as the default test has) is not done")
+    depths = None
+    if inp.get("depths"):
+        table = read_depths(inp["depths"], features["value"])
+        for s in who["names"]:
+            if s not in table:
+                raise ValueError(f"{inp['depths']} (--depths): the sample {s!r} is used and has no row")
+        depths = [table[s] for s in who["names"]]
+        print(f"Ranking {features['value']} over the depths of {inp['depths']}")
+    else:
+        print(f"Ranking raw {features['value']}: no --depths, so a deeper sample ranks higher at the same frequency")
+    a = rank_scores(features["values"], who["used"], min_count, depths, who["names"])
+    F = len(a)
+    planes, offsets, scales = ranksum_inputs(a, n1)
+    D = ranksum_D(a, who["case_mask"], n1)
+    A, B = a.sum(axis=1), (a * a).sum(axis=1)
+    Q = N * B - A * A
+    scores = np.array([ranksum_score(int(d), int(sc), alternative) for d, sc in zip(D, scales)], dtype=np.int64)
+    if F:
+        distinct, first, inverse, counts = np.unique(planes, axis=0, return_index=True, return_inverse=True, return_counts=True)
+        inverse = inverse.reshape(-1)
+    else:
+        distinct, first, inverse, counts = planes, np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
+    levels = np.unique(scores)      # ascending
+    edges = levels[-nat.ASSOC_RANKSUM_MAX_EDGES:].astype(np.uint32)
+    result = derived = None
+    if P:
+        result = nat.assoc_ranksum(distinct, offsets[first], scales[first], counts.astype(np.uint32), N, who["case_mask"], alternative, edges, P, seed)
+        if not np.array_equal(np.asarray(result["obs_score"], dtype=np.int64)[inverse], scores):
+            raise RuntimeError("associate: the device's observed scores are not the host's")
+        derived = derive_ranksum(scores, edges, result, P)
+    masks = presence_masks(features["values"], who["used"], min_count)
+    order = np.argsort(-scores, kind="stable")
+    out_lines = ["\t".join(features["identity"] + RANKSUM_RESULT_COLUMNS).encode()]
+    n0 = N - n1
+    cell = np.searchsorted(edges.astype(np.int64), scores, side="right") - 1      # the largest edge at or below the score; -1: none
+    for f in order:
+        t, M = int(scores[f]), int(masks[f])
+        zeros = int((a[f] == 0).sum())      # the samples of the smallest value: d = a + zeros + 1
+        d_cases = sum(int(a[f, s]) + zeros + 1 for s in range(N) if who["case_mask"] >> s & 1)
+        d_all = int(A[f]) + N * (zeros + 1)
+        cells = [str(bin(M).count("1")), str(bin(M & who["case_mask"]).count("1")), str(bin(M & ~who["case_mask"]).count("1")), str(n1), str(n0),
+                 format(d_cases / (2 * n1), ".6g"), format((d_all - d_cases) / (2 * n0), ".6g"), z_text(int(D[f]), int(Q[f]), N, n1), str(t)]
+        if derived:
+            cells += [sci(Fraction(1 + int(result["exceed"][inverse[f]]), P + 1)), sci(derived["p_adjusted"][t]),
+                      sci(derived["q"][cell[f]] if cell[f] >= 0 else None)]
+        else:
+            cells += ["."] * 3
+        out_lines.append(features["rows"][f] + b"\t" + "\t".join(cells).encode())
+    out = {"result": result, "null": None}
+    out["associate"] = write_out_associate(b"\n".join(out_lines) + b"\n", "associate.tsv", inp)
+    if inp.get("write_null"):
+        ranked = np.sort(scores)
+        null = ["\t".join(RANKSUM_NULL_COLUMNS).encode()]
+        for j in range(len(edges) - 1, -1, -1):
+            e = int(edges[j])
+            here = int(np.searchsorted(ranked, e, side="right") - np.searchsorted(ranked, e, side="left"))
+            above = len(ranked) - int(np.searchsorted(ranked, e, side="left"))
+            cells = [str(e), format(z_of_score(e, N, n1), ".6g"), str(here), str(above)]
+            if derived:
+                cells += [str(int(result["tail"][j])), str(derived["V"][j]), format(float(Fraction(derived["V"][j], P)), ".6g"), sci(derived["fdr"][j])]
+            else:
+                cells += ["."] * 4
+            null.append("\t".join(cells).encode())
+        out["null"] = write_out_associate(b"\n".join(null) + b"\n", "associate_null.tsv", inp)
+    best = int(scores.max()) if F else None
+    q05 = None
+    if derived:
+        q05 = sum(1 for j in cell if j >= 0 and derived["q"][j] is not None and derived["q"][j] <= Fraction(1, 20))
+    stats.clear()
+    stats.update({"test": "rank-sum", "kind": features["kind"], "value": features["value"], "samples": N, "cases": n1, "controls": n0,
+                  "unknown": len(who["unknown"]), "not_in_ph": len(who["not_in_ph"]), "features": F, "rows": len(distinct), "permutations": P,
+                  "seed": seed, "edges": len(edges), "depths": bool(depths), "max_score": best,
+                  "min_p_adjusted": derived["p_adjusted"][best] if derived and F else None, "q_below_0.05": q05})
+    out["stats"] = dict(stats)
+    print(f"Associated {F:,} features ({len(distinct):,} distinct rows of scores; {features['kind']}, {features['value']} >= {min_count}, rank-sum) "
+          f"with {inp['case']!r}: {N} samples used ({n1} cases, {n0} controls; {len(who['unknown'])} left out without a group, "
+          f"{len(who['not_in_ph'])} without a row in -ph), {alternative}, {P:,} permutations, seed {seed}, {len(edges)} edges; largest score "
+          f"{'.' if best is None else best}, smallest adjusted p {sci(stats['min_p_adjusted'])}, {'.' if q05 is None else q05} features with q <= 0.05")
+    return out
+
+
 # ---- what follows from the null ----
 
 def derive(obs_rank, mult_of_rank, result, P: int, tail_ranks: int) -> dict:
@@ -431,6 +684,8 @@ def run(inp: dict) -> dict:
     who = cohort(features, groups, inp["case"], path_in, inp["phenotype"])
     for s in who["not_in_ph"]:
         print(f"Sample {s} of {path_in} has no row in {inp['phenotype']}: left out")
+    if inp.get("test") == "rank-sum":
+        return run_ranksum(inp, features, who, path_in)
     N, n1 = len(who["used"]), who["n1"]
     wide = N > MAX_SAMPLES      # 2 .. 64 samples: the narrow entry and everything as it was; 65 .. 1024: the wide one
     if wide and N > ANNOUNCE_TABLE_ABOVE:

@@ -398,6 +398,15 @@ def _associate(p: argparse.ArgumentParser):
     p.add_argument("--write-null", dest="write_null", action="store_true",
                    help="Also write associate_null.tsv: per p-value of the tail the features, the null's pairs and the false "
                         "discovery rate")
+    p.add_argument("--test", dest="test", choices=["fisher", "rank-sum"], default=None,
+                   help="The test per feature: fisher (the default), the exact test on presence above; or rank-sum, a Wilcoxon / "
+                        "Mann-Whitney rank sum on the VALUES — ties share the mid-rank, values below --min-count count as 0 — with "
+                        "Westfall and Young's max-T over the relabelings for the adjusted p-values; 2 to 64 samples; --max-p is "
+                        "refused there")
+    p.add_argument("--depths", dest="depths", type=str, default=None,
+                   help="Only with --test rank-sum: a tab-separated table with a `sample` column and one named as --value "
+                        "(tabulate_samples.tsv fits as it stands); samples are then ranked by value over depth, compared exactly "
+                        "in integers.  Without it raw values are ranked, and a printed line says so")
 
 
 def create_parser() -> argparse.ArgumentParser:
@@ -495,7 +504,10 @@ def create_associate_parser() -> argparse.ArgumentParser:
         description="Association of features with a phenotype (GPU): per meta-clonotype of a tabulate.tsv, or public clonotype of "
                     "an overlap_public.tsv, an exact test of its presence in the cases against the controls of a cohort, and a "
                     "label-permutation null over all features for the adjusted p-values and the false discovery rate; writes "
-                    "associate.tsv and, on demand, associate_null.tsv.")
+                    "associate.tsv and, on demand, associate_null.tsv.  With --test rank-sum the question is abundance: a rank sum "
+                    "of the feature's values in the cases against the controls, standardized in fixed point, with a max-T null over "
+                    "the same relabelings; associate.tsv then holds mean ranks, z, the score, the feature's own permutation p-value, "
+                    "the max-T adjusted p-value and a q-value over the largest observed scores.")
     _associate(parser)
     return parser
 

@@ -1525,6 +1525,83 @@ int dcrx_assoc_permute_wide(uint32_t n_samples, const uint64_t *case_mask, uint6
                             uint32_t permutations, uint64_t seed, uint32_t *obs_rank_out, uint64_t *labels_out,
                             uint32_t *perm_min_out, uint64_t *tail_out, dcrx_assoc_stats_t *stats_out);
 
+/* ---- association, rank-sum (`associate --test rank-sum`): the label-permutation null of a Wilcoxon / Mann-Whitney rank sum per
+ * feature — a test on ABUNDANCE, beside the presence tests of "association" — with what Westfall and Young's single-step max-T
+ * needs.  This layer knows nothing about ranks, ties, depths or files: the caller hands it small integer SCORES per feature and
+ * sample, as bit planes, and two integers per feature that standardize a sum of them.  Integers only; every output an exact
+ * function of the input.  The narrow and the wide entries stay as they are.  The entries only ADD to ABI 5 ----
+ *
+ * Input: N samples, 2 <= N <= DCRX_ASSOC_MAX_SAMPLES (64); a case mask C (uint64, no bit at or above N), n1 = popcount(C),
+ *   1 <= n1 <= N - 1; an alternative: 0 greater, 1 less, 2 two-sided; F features, F < 2^30; P permutations, 0 <= P <=
+ *   DCRX_ASSOC_MAX_PERMUTATIONS (2^20); one 64-bit seed; plane[F][DCRX_ASSOC_RANKSUM_PLANES] (uint64, row-major): bit b of the
+ *   score a[f][s], 0 <= a < 128, is bit s of plane[f * 7 + b], no bit at or above N; offset[F], scale[F] and mult[F] (uint32;
+ *   mult 0: the feature takes part in perm_max and tail not at all), the sum of the mult below 2^32; edges[E] (uint32),
+ *   E <= DCRX_ASSOC_RANKSUM_MAX_EDGES (1024), strictly ascending.
+ * Relabeling p (p = 0 .. P - 1): L_p of "association" — the n1 samples with the smallest key(seed, p, s).  For the same N, C and
+ *   seed these are the words dcrx_assoc_permute returns.
+ * Score of feature f under a labeling L: W = the sum over s in L of a[f][s] = the sum over b of popcount(plane[f][b] & L) << b;
+ *   D = N W - offset[f], a signed 64-bit value; u = D (greater), -D (less) or |D| (two-sided), clamped to 0 .. 2^20 - 1;
+ *   t = (u * scale[f]) >> DCRX_ASSOC_RANKSUM_SHIFT (20), a uint32 whatever the arrays hold (at most 2^32 - 4097).  The caller
+ *   that wants a standardized rank sum hands over a = the doubled mid-rank less its minimum, offset = n1 sum(a) and scale =
+ *   min(2^32 - 1, isqrt(2^64 / (N sum(a^2) - sum(a)^2))), 0 where every value is equal: t_p(f) is L_p's score, the observed
+ *   score is C's.
+ * Output, every cell written by the call (the caller's buffers need not be cleared) — integer adds and maxima, and atomics whose
+ *   results are not read; nothing depends on launch shape or order of arrival:
+ *     obs_score[f] (uint32) = t under C, also where mult[f] = 0;   labels[p] (uint64) = L_p;
+ *     perm_max[p] (uint32) = the maximum over f with mult[f] > 0 of t_p(f), 0 when there is no such f;
+ *     exceed[f] (uint32) = #{p : t_p(f) >= obs_score[f]}, for EVERY feature, mult[f] = 0 included;
+ *     tail[j] (uint64), j < E, = the sum over p and f of mult[f] [j is the largest index with edges[j] <= t_p(f)]: a pair below
+ *       edges[0] falls in no cell (below 2^52 by the limits above).
+ * Refusals, in this order.  The scalars, as "association" judges them with the alternative and E in the place of its two rank
+ *   counts: DCRX_E_INVALID for N outside 2 .. 64, C with a bit at or above N, n1 of 0 or N, an alternative above 2, E above 1024;
+ *   DCRX_E_UNSUPPORTED for F >= 2^30 and P > 2^20.  Then DCRX_E_INVALID for a null array with a non-zero size.  What the host
+ *   entry alone can see it alone refuses, in this order: DCRX_E_INVALID for a plane bit at or above N and for edges that are not
+ *   strictly ascending, DCRX_E_UNSUPPORTED for a multiplicity sum of 2^32 or more.  The device entry instead ANDs every plane
+ *   with the N-bit mask, clamps u, and searches the edges only inside 0 .. E - 1 (what it finds in edges that do not ascend is
+ *   some cell of tail, or none): nothing outside the arrays is read or written, whatever they hold. */
+#define DCRX_ASSOC_RANKSUM_PLANES 7
+#define DCRX_ASSOC_RANKSUM_SHIFT 20
+#define DCRX_ASSOC_RANKSUM_MAX_EDGES 1024
+
+typedef struct dcrx_assoc_ranksum_stats {
+  uint64_t features;           /* F */
+  uint64_t features_weighted;  /* those with mult > 0 */
+  uint64_t weight;             /* the sum of the mult */
+  uint64_t permutations;       /* P */
+  uint64_t tail_total;         /* the sum of tail[] */
+  uint64_t max_perm_score;     /* the largest perm_max (0 where there is none) */
+} dcrx_assoc_ranksum_stats_t;
+
+/* The primitive, asynchronous on `hip_stream`, all arrays in device memory: d_plane 7 F words, d_offset, d_scale, d_mult,
+ * d_obs_score and d_exceed F entries, d_edges and d_tail E, d_labels and d_perm_max P.  Nothing is copied back, nothing waits,
+ * nothing is allocated: THE ENTRY TAKES NO WORK SPACE (the relabelings live in d_labels, everything else in registers and LDS).
+ * The steps: assoc_ranksum_prepare_kernel, a lane per index, sets tail and exceed to 0 and writes obs_score;
+ * assoc_ranksum_labels_kernel, the selection of "association" (the same device function) with perm_max set to 0;
+ * assoc_ranksum_permute_kernel on a grid of (slices of 1024 features) x (tiles of 1024 relabelings), 256 lanes, four relabelings
+ * and their maxima a lane in registers: a feature's seven plane words, offset, scale, multiplicity and observed score are the same
+ * for the whole wave and are asked for four features at a time; a plane word that is 0 is skipped; per pair and non-zero plane an
+ * AND, a popcount and a shift-add, then a multiply-subtract, the alternative's side, a 32 x 32 -> 64 multiply, a shift and a
+ * max.  exceed: a wave ballot of t >= obs over the lanes that hold a relabeling, counted once a wave, one LDS add per (wave,
+ * feature), one global atomic add per non-zero feature of the block.  tail: only where t >= edges[0]; below edges[1] — cell 0,
+ * where most pairs of a null fall — a second ballot and one 64-bit LDS add per (wave, feature), above it a binary search of the
+ * edges in LDS and a 64-bit LDS add of the multiplicity; one global 64-bit atomic add per non-zero cell of the block.  perm_max:
+ * one global atomic max per (lane, relabeling) above 0.  LDS: the tail cells (64 bits, first), the edges and the slice's exceed
+ * counters, 16 KB. */
+int dcrx_assoc_ranksum_device(uint32_t n_samples, uint64_t case_mask, uint32_t alternative, uint64_t n_features,
+                              const uint64_t *d_plane, const uint32_t *d_offset, const uint32_t *d_scale, const uint32_t *d_mult,
+                              uint32_t n_edges, const uint32_t *d_edges, uint32_t permutations, uint64_t seed,
+                              uint32_t *d_obs_score, uint64_t *d_labels, uint32_t *d_perm_max, uint32_t *d_exceed, uint64_t *d_tail,
+                              void *hip_stream);
+
+/* The host entry, synchronous on the current device, on host arrays of the same shapes: every refusal above before any device
+ * call, ONE allocation, the uploads, the primitive on the null stream, the five arrays copied back.  `stats_out` may be NULL.
+ * F == 0 or P == 0 is answered on the host and touches no device: obs_score and labels are computed here, perm_max, exceed and
+ * tail are 0. */
+int dcrx_assoc_ranksum(uint32_t n_samples, uint64_t case_mask, uint32_t alternative, uint64_t n_features, const uint64_t *plane,
+                       const uint32_t *offset, const uint32_t *scale, const uint32_t *mult, uint32_t n_edges, const uint32_t *edges,
+                       uint32_t permutations, uint64_t seed, uint32_t *obs_score_out, uint64_t *labels_out, uint32_t *perm_max_out,
+                       uint32_t *exceed_out, uint64_t *tail_out, dcrx_assoc_ranksum_stats_t *stats_out);
+
 /* ---- the CDR3 network, weighted (`--cdr3-network --cdr3-metric weighted`): which clonotypes of ONE table lie within a radius
  * of each other under the weighted distance above, and the clusters they form.  The entries only ADD to ABI 5; the network's
  * *_metric entries keep their signatures and behaviour, and go on refusing metric 2 ----
